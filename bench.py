@@ -18,9 +18,19 @@ terms + H^-1 + Adam + multiplier ascent (stencil kernel), and the arc-length rep
 are resident in HBM before the timed region; the interpolation draws come from the in-kernel Philox stream.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full  # + CPU baselines and the gated parity block
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR   # + DIR/<name>.npy of the last timed step
     python bench.py --gpus N --steps K --warmup W          # no WORLD_SIZE in the env: starts its own N rank processes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W              # launched from outside: runs as one rank, as before
+
+A plain run sets up (ONF fit, spin-up), warms up, times the K steps and prints the line: the contract's fields, `config`
+and `roofline` (both from the timed steps themselves).  `--full` adds the legs that take runs of their own after the
+timed steps: `cpu_baseline`, `cpu_baseline_reference_faithful`, `cpu_host` and the gated `parity` block (N = 1 only,
+`--cpu-sample 0` skips them).  `--dump-outputs DIR` writes what the last timed step left to a caller, float32:
+`paths` [B, N+2, 3] (endpoints included), `lam` [B, N+1], `cm` [B, N] and, for cfg5, `onf_params` (the learnt field);
+rows of all ranks in global trajectory order, a fixed seeded row sample above 64 MB.  The inputs depend on the
+arguments only (fixed seeds), so two builds can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE is a LAUNCHER: that process never makes a GPU call (it asserts
 so), starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>
@@ -31,11 +41,11 @@ data path uses (== n_gpus, or the run did not span the ranks it claims).
 Rank 0 prints ONE JSON line.  Beside the contract's fields:
   roofline      fused ONF kernel: algorithmic fp32 FLOPs (131 400 per collision sample) over its HIP-event
                 duration, against the pipe it runs on (see `roofline()`).
-  cpu_baseline  the STRONG CPU baseline (batched autograd-free torch restatement, all host cores) on a bounded sample;
+  cpu_baseline  (--full) the STRONG CPU baseline (batched autograd-free torch restatement, all host cores) on a bounded sample;
                 `cpu_baseline_reference_faithful` = the eager-autograd single-trajectory restatement per core
                 (oracle/cpu_baselines.py, both validated against the reference's fixtures in tests/test_cpu_baselines.py;
                 timed in a child process that never touches the GPU).
-  parity        `ok` is a GATE: the run exits with code 4 when it is false (thresholds from the reference's own
+  parity        (--full) `ok` is a GATE: the run exits with code 4 when it is false (thresholds from the reference's own
                 conditioning, `parity_gate`).  "final loss parity": (short) the first trajectories of THIS workload stepped by the GPU and by the numpy
                 oracle (pinned to the reference) on the identical Philox draw stream from the same initial state --
                 waypoint and per-term loss differences; (final) total loss and collision-free rate after all W + K
@@ -377,6 +387,35 @@ def ranks_seen(world, backend, device):
     return int(round(float(one.item())))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, planner, learn, world, rank):
+    """`--dump-outputs DIR`: the state the last timed step left, as a caller of the planner reads it (see the module
+    docstring).  Every rank takes part in the gather; rank 0 writes.  Above DUMP_LIMIT_BYTES the per-trajectory arrays
+    keep a fixed, seeded sample of rows (sorted), the same rows in every file."""
+    eng = planner.engine
+    rows = {"paths": planner.get_paths(), "lam": eng.lam.cpu().numpy(), "cm": eng.cm.cpu().numpy()}
+    if world > 1:
+        parts = [None] * world
+        torch.distributed.all_gather_object(parts, rows)
+        rows = {k: np.concatenate([p[k] for p in parts]) for k in rows}
+    if rank != 0:
+        return
+    out = {"onf_params": planner.onf.flat_parameters.detach().cpu().numpy()} if learn else {}
+    n = len(rows["paths"])
+    per_row = sum(a[0].nbytes for a in rows.values())
+    keep = min(n, (DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values())) // per_row)
+    if keep < n:
+        pick = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        rows = {k: a[pick] for k, a in rows.items()}
+        sys.stderr.write("bench.py: --dump-outputs keeps %d of %d trajectories (64 MB limit)\n" % (keep, n))
+    out.update(rows)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -384,8 +423,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch-per-gpu", type=int, default=B_PER_GPU)
     ap.add_argument("--fit-iters", type=int, default=300)
-    ap.add_argument("--cpu-sample", type=int, default=256, help="trajectories in the CPU-baseline sample (0 = skip the CPU legs)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of each CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=256,
+                    help="--full: trajectories in the CPU-baseline sample (0 = skip the CPU legs)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: time budget of each CPU baseline")
     ap.add_argument("--parity-steps", type=int, default=10)
     ap.add_argument("--workload", choices=("cfg3", "cfg4", "cfg5"), default="cfg3")
     ap.add_argument("--spin-up", type=int, default=300, help="throw-away steps during setup (clock ramp), state reset after")
@@ -393,6 +433,11 @@ def main():
                     help="fused ONF kernel: bf16x3 split-precision MFMA on 32x32x16 tiles (library default, fp32-faithful), the "
                          "same arithmetic on round 2's 16x16x32 kernel, or fp32 MFMA; not given = leave the library's choice "
                          "(NFOPP_MATRIX_PATH) alone")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baselines and the gated parity block (N = 1); a plain run "
+                         "only sets up, warms up, times and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--dry-run-ranks", action="store_true",
                     help="rank flow only (rendezvous + all-reduce of ones on gloo, no GPU call, no workload): launcher test")
     args = ap.parse_args()
@@ -482,6 +527,8 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, planner, learn, world, rank)
 
     parity_failed = False
     if rank == 0:
@@ -509,7 +556,7 @@ def main():
                        "paths_finite": finite, "matrix_path": matrix_path, "planner_steps_per_s": args.steps / elapsed},
             "roofline": roofline(matrix_path, achieved, k1_ms, samples, traffic, traffic_source),
         }
-        if args.cpu_sample > 0 and world == 1:   # the CPU legs run at N = 1 only (bench contract); N > 1 lines carry the rate
+        if args.full and args.cpu_sample > 0 and world == 1:   # CPU legs: N = 1 only (bench contract); N > 1 lines carry the rate
             sample = min(args.cpu_sample, hi - lo)
             flat = onf.flat_parameters.cpu().numpy()
             cpu = cpu_baselines(flat, starts, goals, N, sample, args.cpu_seconds)

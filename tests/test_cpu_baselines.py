@@ -1,10 +1,15 @@
 """The two CPU baselines bench.py times beside the GPU number (oracle/cpu_baselines.py) against the fixtures the
 reference produced: they must BE the reference's step, or their timings mean nothing.  CPU only."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
-from conftest import benchmr_rollout_tol, load_golden, max_abs, max_rel
+from conftest import ROOT, benchmr_rollout_tol, load_golden, max_abs, max_rel
 from oracle import cpu_baselines as cb
 from oracle import nfopp_oracle as orc
 
@@ -106,7 +111,13 @@ def test_timing_harness_runs_on_a_tiny_sample(tmp_path):
     goals = np.concatenate([rng.uniform(5, 95, (4, 2)), rng.uniform(-3, 3, (4, 1))], 1).astype(F32)
     kw = {("sc_" + k): np.asarray(v, np.float64) for k, v in sc.__dict__.items()}
     np.savez(tmp_path / "in.npz", onf_flat=z["params"], onf_cfg=z["cfg"], n_waypoints=32, starts=starts, goals=goals, **kw)
-    out = cb.time_baselines(str(tmp_path / "in.npz"), 0.3, 0.4, 2)
+    # the fork pool (procs > 1) runs where bench.py runs the harness: a child process that sees no GPU.  In a process
+    # that sees one, autograd's device threads -- started by the backward passes of the tests above -- refuse a fork.
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baselines.py"), "--input", str(tmp_path / "in.npz"),
+                          "--seconds-batched", "0.3", "--seconds-eager", "0.4", "--procs", "2"], capture_output=True, text=True,
+                         env=dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES=""), timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    out = json.loads(res.stdout.strip().splitlines()[-1])
     assert out["strong"]["value"] > 0 and out["strong"]["kind"] == "port"
     assert out["reference_faithful"]["value"] > 0 and out["reference_faithful"]["kind"] == "reference-faithful"
     assert out["reference_faithful"]["process_parallel"]["procs"] == 2

@@ -4,9 +4,9 @@
 set -o pipefail
 export TMPDIR=/tmp
 R=$PWD; O=$R/gpurun_out/r04; mkdir -p $O
-timeout -k 10 500 python bench.py --steps 200 --warmup 20 > $O/bench_cfg3.json 2> $O/bench_cfg3.err || { tail -20 $O/bench_cfg3.err; exit 1; }
+timeout -k 10 500 python bench.py --steps 200 --warmup 20 --full > $O/bench_cfg3.json 2> $O/bench_cfg3.err || { tail -20 $O/bench_cfg3.err; exit 1; }
 echo cfg3 done; head -c 300 $O/bench_cfg3.json; echo
-timeout -k 10 500 python bench.py --workload cfg4 --steps 200 --warmup 20 > $O/bench_cfg4.json 2> $O/bench_cfg4.err || { tail -20 $O/bench_cfg4.err; exit 1; }
+timeout -k 10 500 python bench.py --workload cfg4 --steps 200 --warmup 20 --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err || { tail -20 $O/bench_cfg4.err; exit 1; }
 echo cfg4 done; head -c 300 $O/bench_cfg4.json; echo
 timeout -k 10 500 python bench.py --workload cfg5 --steps 30 --warmup 5 --cpu-sample 0 > $O/bench_cfg5.json 2> $O/bench_cfg5.err || { tail -20 $O/bench_cfg5.err; exit 1; }
 echo cfg5 done; head -c 300 $O/bench_cfg5.json; echo
