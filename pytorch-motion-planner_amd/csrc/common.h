@@ -132,32 +132,12 @@ __device__ __forceinline__ float sin_quadrant(float x, int q) {
   return __int_as_float(__float_as_int(res) ^ ((n & 2) << 30));
 }
 
-// Packed pair of sin(x + q*pi/2), q = 2*qh in {0, 1, 2, 3} (qh = "half turns of pi"): the transcendental of the
-// fused ONF kernel, written on 2-vectors so that hipcc emits v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32.
-//   t = x/pi + qh;  j = rint(t) via the 1.5*2^23 magic add (its low mantissa bit is the parity of j);
-//   r = x - (j - qh)*pi  in [-pi/2, pi/2] (fma with a hi/lo split of pi);  result = (-1)^j * sin(r),
-// sin(r) = r + r^3 P(r^2), P minimax of degree 4 (max abs error 1.2e-7 for |x| < 400, checked in
-// tests/test_host_logic.py through an fp32 emulation against float64).
+// Packed-math pairs: the feature evaluation of the fused ONF kernels (onf_layout.h: features2) is written on 2-vectors
+// so that hipcc emits v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
-
-// scalar form of the same routine (bitwise identical arithmetic per element)
-__device__ __forceinline__ float sin_halfturns1(float x, float qh) {
-  const float t = fmaf(x, 0.318309886f, qh);
-  const float jm = t + 12582912.0f;
-  const float jh = (jm - 12582912.0f) - qh;
-  float r = fmaf(jh, -3.14159274101257324f, x);
-  r = fmaf(jh, 8.74227766e-08f, r);
-  r = __uint_as_float(__float_as_uint(r) ^ (__float_as_uint(jm) << 31));
-  const float s = r * r;
-  float p = fmaf(-2.3909535684651928e-08f, s, 2.7526637040864443e-06f);
-  p = fmaf(p, s, -0.00019840894674416631f);
-  p = fmaf(p, s, 0.008333330973982811f);
-  p = fmaf(p, s, -0.1666666716337204f);
-  return fmaf(p, r * s, r);
-}
 
 // Hardware path: exact Cody-Waite reduction of x + qh*pi modulo 2 pi (fma with a hi/lo split of 2 pi), then
 // v_sin_f32 on the remainder expressed in revolutions (|f| <= 0.5).  Measured on gfx950 (tools/micro/
@@ -171,36 +151,12 @@ __device__ __forceinline__ float sin_halfturns_hw(float x, float qq) {  // qq = 
   return __builtin_amdgcn_sinf(fmaf(r, 0.159154943f, qq));  // |revolutions| <= 0.75
 }
 
-#ifndef NFOPP_TRIG_MODE
-#define NFOPP_TRIG_MODE 2  /* 0 = scalar polynomial, 1 = packed polynomial, 2 = reduction + v_sin_f32 */
-#endif
-// sin_halfturns2(x, q * NFOPP_Q_UNIT) = sin(x + q*pi/2): the quadrant offset is pre-scaled to the unit the
-// selected routine works in (half turns of pi for the polynomials, revolutions for v_sin_f32)
-#if NFOPP_TRIG_MODE == 2
+// sin_halfturns2(x, q * NFOPP_Q_UNIT) = sin(x + q*pi/2): the quadrant offset is pre-scaled to revolutions, the unit
+// v_sin_f32 works in
 #define NFOPP_Q_UNIT 0.25f
-#else
-#define NFOPP_Q_UNIT 0.5f
-#endif
 
 __device__ __forceinline__ f32x2 sin_halfturns2(f32x2 x, f32x2 qh) {
-#if NFOPP_TRIG_MODE == 0
-  return f32x2{sin_halfturns1(x.x, qh.x), sin_halfturns1(x.y, qh.y)};
-#elif NFOPP_TRIG_MODE == 2
   return f32x2{sin_halfturns_hw(x.x, qh.x), sin_halfturns_hw(x.y, qh.y)};
-#endif
-  const f32x2 t = fma2(x, splat2(0.318309886f), qh);
-  const f32x2 jm = t + splat2(12582912.0f);
-  const f32x2 jh = (jm - splat2(12582912.0f)) - qh;
-  f32x2 r = fma2(jh, splat2(-3.14159274101257324f), x);
-  r = fma2(jh, splat2(8.74227766e-08f), r);
-  r.x = __uint_as_float(__float_as_uint(r.x) ^ (__float_as_uint(jm.x) << 31));
-  r.y = __uint_as_float(__float_as_uint(r.y) ^ (__float_as_uint(jm.y) << 31));
-  const f32x2 s = r * r;
-  f32x2 p = fma2(splat2(-2.3909535684651928e-08f), s, splat2(2.7526637040864443e-06f));
-  p = fma2(p, s, splat2(-0.00019840894674416631f));
-  p = fma2(p, s, splat2(0.008333330973982811f));
-  p = fma2(p, s, splat2(-0.1666666716337204f));
-  return fma2(p, r * s, r);
 }
 
 // Philox4x32-10, first output word -> uniform [0,1) with 24 random bits (the same u32->float map torch uses).

@@ -12,10 +12,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int H = NFOPP_HIDDEN;
 constexpr int HT = 7;     // hidden tiles of 16 (tile 6 carries features 96..99 in rows (g, r = 0))
 constexpr int S2 = 129;   // LDS row stride of W2 (floats), = 1 mod 32
-#ifndef NFOPP_THREADS
-#define NFOPP_THREADS 512   /* development: 256 = one wave per SIMD (tools/split_speed.py A/B) */
-#endif
-constexpr int THREADS = NFOPP_THREADS;
+constexpr int THREADS = 512;
 constexpr int WAVES = THREADS / 64;
 constexpr int KSTEPS = 25;  // hidden k-steps: ks -> tile ks>>2, register ks&3 (tile 6 only register 0)
 
@@ -39,13 +36,8 @@ struct Lds {
   static constexpr int FT_FLOATS = FT_HALF + (NF / 2) * FTS;
   // entry of feature f, floats from the start of LDS;  ft_rel(x): the part that does not depend on the lane, for
   // x = 32 K + c with c < 16 (block / tile bases and row offsets: bit 4 clear)
-#ifndef NFOPP_FT_PLAIN
   __host__ __device__ static constexpr int ft(int f) { return FT + FT_HALF * ((f >> 4) & 1) + FTS * (((f >> 5) << 4) | (f & 15)); }
   __host__ __device__ static constexpr int ft_rel(int x) { return FTS * (x - 16 * (x >> 5)); }
-#else   /* development A/B: the plain [feature][FTS] table of round 1 (2-way conflicted 16-byte reads) */
-  __host__ __device__ static constexpr int ft(int f) { return FT + FTS * f; }
-  __host__ __device__ static constexpr int ft_rel(int x) { return FTS * x; }
-#endif
   static constexpr int B1 = FT + ((FT_FLOATS + 3) / 4) * 4;   // 112 each, D-layout indexable (see fill)
   static constexpr int B2 = B1 + 16 * HT;
   static constexpr int W3A = B2 + 16 * HT;

@@ -29,13 +29,6 @@
 
 namespace nfopp {
 
-// Fences between MFMA steps pin the MEMORY instructions of a step (so that hipcc does not hoist every load of the
-// unrolled loops to the top and spill) but let vector, scalar and matrix instructions cross, so that the packing and
-// splitting of the next step can be interleaved with the MFMAs of this one.
-#ifndef NFOPP_FENCE
-#define NFOPP_FENCE 0x40E   /* may cross: VALU 0x2 | SALU 0x4 | MFMA 0x8 | transcendental 0x400 */
-#endif
-
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -115,19 +108,6 @@ __device__ __forceinline__ void pack_words(const float w[8], u32x4& hi, u32x4& m
     }                                                                                                          \
   }
 
-// Development build (make EXTRA=-DNFOPP_PHASE_PROFILE): wave 0 of every workgroup accumulates clock ticks per phase of
-// the chunk loop; launch_split_t prints the shares every tenth launch of the <.., 2, 0> kernel.
-#ifdef NFOPP_PHASE_PROFILE
-#define NFOPP_TICK(SLOT)                                           \
-  {                                                                \
-    const unsigned long long now_ = __builtin_readcyclecounter();  \
-    phase_ticks[SLOT] += (float)(now_ - phase_t0);                 \
-    phase_t0 = now_;                                               \
-  }
-#else
-#define NFOPP_TICK(SLOT)
-#endif
-
 // ---- third-level blob: [gemm][step][lane] 16 bytes --------------------------------------------------------------
 template <int NKT>
 struct Blob {
@@ -203,11 +183,9 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
   extern __shared__ __attribute__((aligned(16))) float lds[];
   fill_lds<NKT, TRAIN, true>(lds, a);
   __syncthreads();
-#ifndef NFOPP_NO_PRIO_YOUNG
   // the second-dispatched half of the workgroup loses the vector-issue arbitration (age); one static priority for that
   // half, set once, evens it out (MI355X_MICROARCH.md "static priority for the younger half"; -0.4 % in a same-process A/B)
   if ((threadIdx.x >> 6) >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
-#endif
 
   const OnfGeom& geo = a.geom;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -243,15 +221,10 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(blob_rsrc, lane16, step * 1024, 0));
   };
 
-#ifdef NFOPP_PHASE_PROFILE
-  float phase_ticks[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  unsigned long long phase_t0 = __builtin_readcyclecounter();
-#endif
   for (long long chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
     // ---------------------------------------------------------------- sample / load the wave's points
     float ux[NT], uy[NT], th[NT];
     long long pidx[NT];
-#ifndef NFOPP_NO_SHARED_SAMPLING
     if constexpr (NT == 2 && !TRAIN) {
       // the four lane groups of a point column would each draw and interpolate BOTH tiles' samples (Philox, wrap, lerp):
       // lane group g evaluates the sample of tile g & 1 once and the groups exchange the results
@@ -266,9 +239,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
         ux[tl] = __shfl(uxm, from); uy[tl] = __shfl(uym, from); th[tl] = __shfl(ang, from);
         pidx[tl] = ((long long)__shfl(hi, from) << 32) | (unsigned)__shfl(lo, from);
       }
-    } else
-#endif
-    {
+    } else {
 #pragma unroll
       for (int tl = 0; tl < NT; ++tl) {
         float x, y, ang;
@@ -281,7 +252,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       }
     }
 
-    NFOPP_TICK(0)   // sampling
     // ---------------------------------------------------------------- L1: a1 = W1 in + b1, features just-in-time
     NFOPP_REDERIVE();
     f32x4 acc1[NT][HT];
@@ -516,7 +486,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
           }
         }
     }
-    NFOPP_TICK(1)   // L1 (features + steps)
     // ---------------------------------------------------------------- L2: a2 = W2 relu(a1) + b2
     NFOPP_REDERIVE();
     f32x4 acc2[NT][HT];
@@ -588,7 +557,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       }
     }
 
-    NFOPP_TICK(2)   // L2
     // ---------------------------------------------------------------- logit and dh2 = W3a * [a2 > 0]
     float logit[NT];
 #pragma unroll
@@ -648,7 +616,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       continue;
     }
 
-    NFOPP_TICK(3)   // logit
     // ---------------------------------------------------------------- L2T: dh1 = (W2^T dh2) * [a1 > 0]
     NFOPP_REDERIVE();
     {
@@ -748,7 +715,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       }
     }
 
-    NFOPP_TICK(4)   // L2T
     // ---------------------------------------------------------------- L1T: din = W1^T dh1 + W3b, then the chain rule
     NFOPP_REDERIVE();
     float gx[NT], gy[NT], gt[NT];
@@ -999,7 +965,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
 #pragma unroll 1
       for (int mt = first_angle_kt; mt < NKT; ++mt) l1t_tile(std::true_type{}, mt);
     }
-    NFOPP_TICK(5)   // L1T (steps + epilogues)
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl) {
       gx[tl] += __shfl_xor(gx[tl], 16); gx[tl] += __shfl_xor(gx[tl], 32);
@@ -1010,7 +975,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
         *reinterpret_cast<f32x4*>(a.out4 + pidx[tl] * 4) = o;
       }
     }
-    NFOPP_TICK(6)   // output
   }
   if (TRAIN) {  // fixed-order partials, as onf_fused.hip: loss per wave, dW3[:100] per wave in h2 slot order
 #pragma unroll
@@ -1027,10 +991,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       if (i == 0) *reinterpret_cast<f32x4*>(g4 + 16 * mt + 4 * g) = v;
     }
   }
-#ifdef NFOPP_PHASE_PROFILE
-  if (MODE == 0 && a.ws_u && threadIdx.x == 0)
-    for (int k = 0; k < 8; ++k) atomicAdd(a.ws_u + k, phase_ticks[k]);
-#endif
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
@@ -1108,28 +1068,6 @@ static int launch_split_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_
   long long grid = query_cus();
   if (grid > n_chunks) grid = n_chunks;
   if (grid_out) *grid_out = (int)grid;
-#ifdef NFOPP_PHASE_PROFILE
-  if (MODE == 0 && NT == 2) {   // development only: synchronous, prints to stderr
-    static float* dbg = nullptr;
-    if (!dbg) NFOPP_HIP(hipMalloc(&dbg, 64));
-    NFOPP_HIP(hipMemsetAsync(dbg, 0, 64, stream));
-    OnfKernelArgs b = a;
-    b.ws_u = dbg;   // unused by this mode: carries the tick buffer
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), L::BYTES, stream, b, (const u32x4*)blob);
-    float h[8];
-    NFOPP_HIP(hipMemcpyAsync(h, dbg, 32, hipMemcpyDeviceToHost, stream));
-    NFOPP_HIP(hipStreamSynchronize(stream));
-    static int calls = 0;
-    if (++calls % 10 == 0) {
-      float tot = 0;
-      for (int k = 0; k < 7; ++k) tot += h[k];
-      const char* names[7] = {"sampling", "L1", "L2", "logit", "L2T", "L1T", "output"};
-      fprintf(stderr, "[phase profile] wave 0 of %lld workgroups, share of the chunk loop:\n", grid);
-      for (int k = 0; k < 7; ++k) fprintf(stderr, "   %-10s %5.1f %%\n", names[k], 100.0f * h[k] / tot);
-    }
-    return NFOPP_OK;
-  }
-#endif
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), L::BYTES, stream, a, (const u32x4*)blob);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;
@@ -1138,11 +1076,7 @@ static int launch_split_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_
 template <int MODE>
 static int launch_split_mode(const OnfKernelArgs& a, hipStream_t stream) {
   const int nkt = (a.geom.fin + 15) / 16;
-#ifdef NFOPP_FORCE_NT1
-  const bool small = true;   // development A/B: one point tile per wave at any size
-#else
   const bool small = a.n_points < (long long)query_cus() * WAVES * 16 * 2;
-#endif
   switch (nkt) {
     case 14: return small ? launch_split_t<14, 1, MODE>(a, stream) : launch_split_t<14, 2, MODE>(a, stream);
     case 13: return small ? launch_split_t<13, 1, MODE>(a, stream) : launch_split_t<13, 2, MODE>(a, stream);
@@ -1159,15 +1093,11 @@ static int launch_split_mode(const OnfKernelArgs& a, hipStream_t stream) {
 int launch_onf_split_train_kernel(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
   const int nkt = (a.geom.fin + 15) / 16;
   switch (nkt) {
-#ifdef NFOPP_TRAIN_NT1   /* development A/B: one point tile per wave at any size */
-    case 14: return launch_split_t<14, 1, 1>(a, stream, grid_out);
-#else
     // two tiles per wave once every CU gets a full workgroup of them (as the evaluation kernel decides); smaller fits fill more
     // CUs with one tile per wave (4096 samples: 57 vs 85 us)
     case 14:
       return a.n_points < (long long)query_cus() * WAVES * 16 * 2 ? launch_split_t<14, 1, 1>(a, stream, grid_out)
                                                                    : launch_split_t<14, 2, 1>(a, stream, grid_out);
-#endif
     case 13: return launch_split_t<13, 1, 1>(a, stream, grid_out);
     case 8: return launch_split_t<8, 1, 1>(a, stream, grid_out);
     case 7: return launch_split_t<7, 1, 1>(a, stream, grid_out);

@@ -129,15 +129,6 @@ __device__ __forceinline__ f32x4 features4_scalar(const f32x4& wx, const f32x4& 
   return v;
 }
 
-// the same for four POSITIONAL features (sin / cos of the encoding layer): no angle argument, no select -- the values of
-// features4_scalar for isa == 0, bit for bit
-__device__ __forceinline__ f32x4 features4_positional(const f32x4& wx, const f32x4& wy, const f32x4& b, const f32x4& qh, float ux, float uy) {
-  f32x4 v;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = sin_halfturns_hw(fmaf(wx[k], ux, fmaf(wy[k], uy, b[k])), qh[k]);
-  return v;
-}
-
 template <int NKT>
 __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArgs a) {
   using W = WgLayout<NKT>;
@@ -299,7 +290,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArg
   constexpr int GRP = 7;  // tiles whose operands are in flight together
   // operands of step (tile group, k-step) it+1 are read from LDS while the MFMAs of step it issue
   auto multiply = [&](int off, int j_lo, int j_hi) __attribute__((always_inline)) {
-#ifndef NFOPP_ABL_NO_MFMA
     const int n_it = ((j_hi - j_lo + GRP - 1) / GRP) * (KC / 4);
     float av[2][GRP], bv[2][GRP];
     auto fetch = [&](int it, int buf) __attribute__((always_inline)) {
@@ -321,7 +311,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArg
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[it & 1][j - j0], bv[it & 1][j - j0], acc[j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
   };
   constexpr int SPLIT_AT = GRP * ((W::TPW + GRP - 1) / GRP / 2 + ((W::TPW + GRP - 1) / GRP) % 2);   // groups before barrier A
   for (long long chunk = c0; chunk < n_chunks; chunk += step) {
@@ -331,9 +320,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArg
     if (chunk + 2 * step < n_chunks) prefetch(chunk + 2 * step);
     multiply(off, 0, SPLIT_AT);
     __syncthreads();                                          // A: `nxt` committed by everyone
-#ifndef NFOPP_ABL_NO_REBUILD
     if (has_next) rebuild(nxt);
-#endif
     multiply(off, SPLIT_AT, W::TPW);
     __syncthreads();                                          // B: `cur` consumed, `nxt` rebuilt
     float* t = cur; cur = nxt; nxt = t;
@@ -415,13 +402,6 @@ __device__ __forceinline__ unsigned take_level(float& x0, float& x1) {
 // four consecutive slots of one sample -> 8 bytes per level at dword offset `at` of the three images starting at `img`
 __device__ __forceinline__ void store_split4(float* lds, int img, int plane, int at, f32x4 v) {
   u32x2 h, m, l;
-#ifdef NFOPP_ABL2_NO_SPLIT   /* development ablation: the three stores without the arithmetic */
-  h.x = __float_as_uint(v.x); h.y = __float_as_uint(v.y); m = h; l.x = __float_as_uint(v.z); l.y = __float_as_uint(v.w);
-  *reinterpret_cast<u32x2*>(lds + img + at) = h;
-  *reinterpret_cast<u32x2*>(lds + img + plane + at) = m;
-  *reinterpret_cast<u32x2*>(lds + img + 2 * plane + at) = l;
-  return;
-#endif
   float x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
   h.x = take_level(x0, x1); h.y = take_level(x2, x3);
   m.x = take_level(x0, x1); m.y = take_level(x2, x3);
@@ -436,9 +416,6 @@ __device__ __forceinline__ void store_split4(float* lds, int img, int plane, int
 template <int R>
 __device__ __forceinline__ s16x8 read_frag(const float* lane_base, int dword_off) {
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-#ifdef NFOPP_ABL2_NO_FRAGREAD   /* development ablation */
-  return s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#endif
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lane_base + dword_off));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lane_base + dword_off + 8 * R));
   return s16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -458,19 +435,6 @@ __device__ __forceinline__ void mfma_guard() {
 #endif
 }
 
-// Development build (make EXTRA=-DNFOPP_WG_PROFILE): waves 0 and 4 of workgroup 0 print the clock ticks they spent in their
-// work and at the barriers of the two phases.
-#ifdef NFOPP_WG_PROFILE
-#define WG_TICK(SLOT)                                              \
-  {                                                                \
-    const unsigned long long now_ = __builtin_readcyclecounter();  \
-    wg_ticks[SLOT] += (float)(now_ - wg_t0);                       \
-    wg_t0 = now_;                                                  \
-  }
-#else
-#define WG_TICK(SLOT)
-#endif
-
 // End of a pipeline phase.  The scheduling barrier matters: without it hipcc hoists the NEXT phase's register arithmetic (the
 // splitting of operands whose loads were issued a moment ago) above the barrier, and the s_waitcnt vmcnt(0) that goes with
 // it exposes the full HBM latency once per chunk (0.6 ms of the 1.7 ms the kernel took).
@@ -484,31 +448,12 @@ __device__ __forceinline__ void phase_barrier() {
 // alone waits for its own previous result every time).
 __device__ __forceinline__ void mfma_split_pair(const s16x8 (&a)[3], const s16x8 (&b0)[3], const s16x8 (&b1)[3], f32x4& c0,
                                                 f32x4& c1) {
-#ifdef NFOPP_ABL2_NO_MFMA
-  asm volatile("" :: "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(b0[0]), "v"(b0[1]), "v"(b0[2]), "v"(b1[0]), "v"(b1[1]), "v"(b1[2]));
-  return;
-#endif
-#ifdef NFOPP_ABL2_HALF_MFMA   /* development ablation (timing only): half the matrix instructions (what 32x32x16 tiles would issue) */
-  c0 = mfma_bf16(a[2], b0[0], c0); c0 = mfma_bf16(a[0], b0[2], c0); c0 = mfma_bf16(a[1], b0[1], c0);
-  c1 = mfma_bf16(a[1], b1[0], c1); c1 = mfma_bf16(a[0], b1[1], c1); c1 = mfma_bf16(a[0], b1[0], c1);
-  return;
-#endif
   c0 = mfma_bf16(a[2], b0[0], c0); c1 = mfma_bf16(a[2], b1[0], c1);
   c0 = mfma_bf16(a[0], b0[2], c0); c1 = mfma_bf16(a[0], b1[2], c1);
   c0 = mfma_bf16(a[1], b0[1], c0); c1 = mfma_bf16(a[1], b1[1], c1);
   c0 = mfma_bf16(a[1], b0[0], c0); c1 = mfma_bf16(a[1], b1[0], c1);
   c0 = mfma_bf16(a[0], b0[1], c0); c1 = mfma_bf16(a[0], b1[1], c1);
   c0 = mfma_bf16(a[0], b0[0], c0); c1 = mfma_bf16(a[0], b1[0], c1);
-}
-// The same with an A operand that is EXACT in one bf16 level (a 0 / 1 mask): three products, nothing dropped
-__device__ __forceinline__ void mfma_mask_pair(const s16x8& a, const s16x8 (&b0)[3], const s16x8 (&b1)[3], f32x4& c0, f32x4& c1) {
-#ifdef NFOPP_ABL2_NO_MFMA
-  asm volatile("" :: "v"(a), "v"(b0[0]), "v"(b0[1]), "v"(b0[2]), "v"(b1[0]), "v"(b1[1]), "v"(b1[2]));
-  return;
-#endif
-  c0 = mfma_bf16(a, b0[2], c0); c1 = mfma_bf16(a, b1[2], c1);
-  c0 = mfma_bf16(a, b0[1], c0); c1 = mfma_bf16(a, b1[1], c1);
-  c0 = mfma_bf16(a, b0[0], c0); c1 = mfma_bf16(a, b1[0], c1);
 }
 // XO: the factors are in x32 order (WgradArgs::x32_order, a.x32_order == XO)
 template <int NKT, bool XO>
@@ -591,11 +536,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     // HBM loads as raw buffer loads: one resource per array and chunk (base = the chunk's first row, size = the rows that
     // exist), so the per-item offset q * row + 16 c is a 32-bit chunk-invariant and rows past P read as zeros without a branch
     auto chunk_rsrc = [&](const float* base, long long chunk, int row_floats) __attribute__((always_inline)) {
-#ifdef NFOPP_WG_REVERSE   /* development A/B: walk the samples from the end (what pass 1 wrote last is still in the caches) */
-      const long long p0 = chunk < n_chunks ? (n_chunks - 1 - chunk) * KS : a.P;
-#else
       const long long p0 = chunk * KS;
-#endif
       long long rows = a.P - p0;
       rows = rows > KS ? KS : (rows < 0 ? 0 : rows);
       const float* ptr = base + (rows > 0 ? p0 : 0) * row_floats;
@@ -607,12 +548,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       for (int j = 0; j < N_H; ++j) {
         int q, c;
         unpack(hqc[j], q, c);
-#ifdef NFOPP_ABL2_NO_LOAD   /* development ablation (timing only): no HBM traffic, the arithmetic and LDS work stay */
-        st[j] = f32x4{(float)q, (float)c, 1.0f + (float)chunk, 2.0f};
-        asm volatile("" : "+v"(st[j]));
-#else
         st[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, q * (HS * 4) + 16 * c, 0, 0));
-#endif
       }
     };
     auto load_de = [&](f32x4 (&st)[N_W], long long chunk) __attribute__((always_inline)) {
@@ -621,22 +557,12 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       for (int j = 0; j < N_W; ++j) {
         int q, c;
         unpack(wqc[j], q, c);
-#ifdef NFOPP_ABL2_NO_LOAD
-        st[j] = f32x4{(float)q, (float)c, 1.0f + (float)chunk, 2.0f};
-        asm volatile("" : "+v"(st[j]));
-#else
         st[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, q * (WIN * 4) + 16 * c, 0, 0));
-#endif
       }
     };
     auto load_rec = [&](f32x4& st, long long chunk) __attribute__((always_inline)) {
       const auto rsrc = chunk_rsrc(ws_rec, chunk, 12);
-#ifdef NFOPP_ABL2_NO_LOAD
-      st = f32x4{0.25f, 0.5f, 1.0f, 0.1f * (float)(chunk & 7)};
-      asm volatile("" : "+v"(st));
-#else
       st = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, rq * 48 + 16 * rc, 0, 0));
-#endif
     };
     auto commit_rec = [&](f32x4 st, int parity) __attribute__((always_inline)) {
       *reinterpret_cast<f32x4*>(lds + L::REC + parity * KS * 12 + rq * 12 + 4 * rc) = st;
@@ -656,14 +582,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = v[r] * rho;
         }
-#ifdef NFOPP_ABL2_NO_SPLIT_H   /* development ablation (timing only): h1 / dh1 committed without the split arithmetic */
-        const u32x2 raw{__float_as_uint(st[j].x), __float_as_uint(st[j].z)};
-        *reinterpret_cast<u32x2*>(lds + img + q * L::R_H + 2 * c) = raw;
-        *reinterpret_cast<u32x2*>(lds + img + L::P_H + q * L::R_H + 2 * c) = raw;
-        *reinterpret_cast<u32x2*>(lds + img + 2 * L::P_H + q * L::R_H + 2 * c) = u32x2{__float_as_uint(st[j].y), __float_as_uint(st[j].w)};
-#else
         store_split4(lds, img, L::P_H, q * L::R_H + 2 * c, v);
-#endif
       }
     };
     // Rebuilt operands.  A thread's items keep their columns from chunk to chunk, so the table entries they need sit in
@@ -674,23 +593,9 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     for (int j = 0; j < N_H; ++j) w3a_reg[j] = *reinterpret_cast<const f32x4*>(lds + L::L_W3A + 4 * (hqc[j] & 255));
     constexpr int SP = PT / W4, T_I = SP * W4, N_I = (KS + SP - 1) / SP;
     const int it_in = pt < T_I ? pt : pt - T_I;       // surplus threads repeat other owners' work
-    // x32 order (slots = feature indices): the positional quads are dealt to the first threads, the quads that can hold angle /
-    // ones / pad slots to the last ones, so that whole WAVES evaluate positional features only and skip the angle argument and
-    // the select (4 of 14 instructions per feature; the evaluation is 40 % of the staging waves' work)
-#ifdef NFOPP_POSITIONAL_WAVES
-    constexpr int NPQ = XO ? (NKT >= 13 ? 50 : 25) : 0, NSQ = W4 - NPQ;   // encoding-layer features / 4 (200 or 100 of them)
-    const int in_s4 = !XO ? it_in % W4 : (it_in < NPQ * SP ? it_in % NPQ : NPQ + (it_in - NPQ * SP) % NSQ);
-    const int in_q0 = !XO ? it_in / W4 : (it_in < NPQ * SP ? it_in / NPQ : (it_in - NPQ * SP) / NSQ);
-#else
+    // (Dealing the positional quads to whole waves, which could then skip the angle argument and the select, measured slower:
+    // the instructions saved are fewer than what the changed slot-to-thread map costs the split stores.)
     const int in_s4 = it_in % W4, in_q0 = it_in / W4;
-#endif
-    // OFF by default (make EXTRA=-DNFOPP_POSITIONAL_WAVES): same-box A/B at P = 2.54 M, twice: 1.738 ms with it, 1.680 ms without
-    // -- the instructions saved are fewer than what the changed slot-to-thread map costs the split stores.
-#ifdef NFOPP_POSITIONAL_WAVES
-    const bool pos_only = XO && (wave - WG_WAVES / 2) * 64 + 63 < NPQ * SP;   // wave-uniform
-#else
-    const bool pos_only = false;
-#endif
     f32x4 t_wx, t_wy, t_b, t_fr, t_qh, t_isa;
     {
       const float* e = lds + L::L_FT + 4 * in_s4;
@@ -698,10 +603,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       t_b = *reinterpret_cast<const f32x4*>(e + 2 * WIN); t_fr = *reinterpret_cast<const f32x4*>(e + 3 * WIN);
       t_qh = *reinterpret_cast<const f32x4*>(e + 4 * WIN); t_isa = *reinterpret_cast<const f32x4*>(e + 5 * WIN);
     }
-#ifdef NFOPP_WG_PROFILE
-    float wg_ticks[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    unsigned long long wg_t0 = __builtin_readcyclecounter();
-#endif
     // The input features of chunk k+1 are EVALUATED in phase A(k) -- into registers, from the record committed one phase
     // earlier -- and only split and stored in phase B(k).  (Round 3 evaluated and stored them in phase B: in-kernel stamps showed
     // phase A bound by the multiplying waves' G1 (6.8 k cycles, the staging waves idle for 2.5 k of them) and phase B by this
@@ -713,12 +614,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
         int q = in_q0 + SP * j;   // in slots 4 s4 .. 4 s4 + 3 of sample q = features(u), pass 1's arithmetic
         q = q < KS ? q : KS - 1;
         const float ux = rec[q * 12], uy = rec[q * 12 + 1], th = rec[q * 12 + 3];
-#ifdef NFOPP_ABL2_NO_IN   /* development ablation (timing only): no feature evaluation, the split and the stores stay */
-        feat[j] = f32x4{ux + t_wx.x, uy + t_wx.y, th + t_wx.z, ux + t_wx.w};
-#else
-        feat[j] = pos_only ? features4_positional(t_wx, t_wy, t_b, t_qh, ux, uy)
-                           : features4_scalar(t_wx, t_wy, t_b, t_fr, t_qh, t_isa, ux, uy, th);
-#endif
+        feat[j] = features4_scalar(t_wx, t_wy, t_b, t_fr, t_qh, t_isa, ux, uy, th);
         // pinned: without this LLVM sinks the (pure) evaluation to its use behind the phase barrier, i.e. back into phase B
         asm volatile("" : "+v"(feat[j]));
       }
@@ -739,7 +635,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       const float* rec = lds + L::REC + S * KS * 12;
       commit_h(L::B_H1, st_h1, XO ? rec : nullptr);
       load_h(ws_h1, st_h1, chunk + step);
-      WG_TICK(5)
 #pragma unroll
       for (int j = 0; j < N_W; ++j) {
         int q, c;
@@ -749,20 +644,12 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       load_de(st_de, chunk + step);
       load_rec(st_rec, chunk + 2 * step);
       { const int t = pt & (KS * 4 - 1); lds[L::B_DE + (t >> 2) * L::RS_DE + WIN + (t & 3)] = rec[(t >> 2) * 12 + (t & 3)]; }
-      WG_TICK(6)
 #pragma unroll
       for (int j = 0; j < N_H; ++j) {   // dh2 slots 4c .. 4c+3 = rho * W3a * [a2 > 0]: tile c >> 2, lane group c & 3
         int q, c;
         unpack(hqc[j], q, c);
-        if constexpr (XO) {   // the bare mask [a2 > 0] as bf16 1.0 / 0 (rho rides on h1, W3a is applied by the gather kernel)
-#ifdef NFOPP_MASK_BY_STAGING_WAVES   /* A/B: round 4 first had the staging waves write it */
-          const int word = (int)__float_as_uint(rec[q * 12 + 8 + (c & 3)]), sh = 4 * (c >> 2);
-          const unsigned m0 = (unsigned)__builtin_amdgcn_sbfe(word, sh, 1), m1 = (unsigned)__builtin_amdgcn_sbfe(word, sh + 1, 1);
-          const unsigned m2 = (unsigned)__builtin_amdgcn_sbfe(word, sh + 2, 1), m3 = (unsigned)__builtin_amdgcn_sbfe(word, sh + 3, 1);
-          const unsigned k01 = __builtin_amdgcn_perm(m1, m0, 0x07060302), k23 = __builtin_amdgcn_perm(m3, m2, 0x07060302);
-          *reinterpret_cast<u32x2*>(lds + L::B_DH2 + q * L::R_H + 2 * c) = u32x2{k01 & 0x3f803f80u, k23 & 0x3f803f80u};
-#endif
-          continue;   // (default: the MULTIPLYING waves write the mask plane behind G1, in the time they would wait at the barrier)
+        if constexpr (XO) {   // the bare mask [a2 > 0] as bf16 1.0 / 0 (rho rides on h1, W3a is applied by the gather kernel):
+          continue;           // the MULTIPLYING waves write that plane behind G1, in the time they would wait at the barrier
         }
         const unsigned bits = __float_as_uint(rec[q * 12 + 8 + (c & 3)]) >> (4 * (c >> 2));
         const float rho = rec[q * 12 + 4];
@@ -771,7 +658,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
         for (int r = 0; r < 4; ++r) v[r] = ((bits >> r) & 1u) ? w3a_reg[j][r] * rho : 0.0f;
         store_split4(lds, L::B_DH2, L::P_H, q * L::R_H + 2 * c, v);
       }
-      WG_TICK(7)
       eval_in(lds + L::REC + (S ^ 1) * KS * 12);
     };
     // phase B(k)'s staging, into bufA: dh1 (set s) and the split features of chunk k+1; the record of chunk k+2 -> area s (last read
@@ -781,7 +667,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       commit_rec(st_rec, S);
       commit_h(L::A_DH1, st_dh1);
       load_h(ws_dh1, st_dh1, chunk + 2 * step);
-      WG_TICK(9)
       store_in();
     };
     // prologue: record(c0) -> area 0, record(c0 + step) -> area 1, bufA(c0) in place; h1 / de (c0) and dh1(c0 + step) in set 0
@@ -803,28 +688,17 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     }
     auto one_chunk = [&](auto set_c, long long chunk) __attribute__((always_inline)) {
       stage_b(set_c, chunk);                    // phase A
-      WG_TICK(0)
       phase_barrier();
-      WG_TICK(1)
       stage_a(set_c, chunk);                    // phase B
-      WG_TICK(2)
       phase_barrier();
-      WG_TICK(3)
     };
     for (long long chunk = c0; chunk < n_chunks; chunk += 2 * step) {
       one_chunk(std::integral_constant<int, 0>{}, chunk);
       if (chunk + step < n_chunks) one_chunk(std::integral_constant<int, 1>{}, chunk + step);
     }
-#ifdef NFOPP_WG_PROFILE
-    if (blockIdx.x == 0 && tid == WG_THREADS / 2)
-      printf("producer wave 4: phase A: loads %.0f, h1 %.0f, de + u %.0f, dh2 %.0f, features %.0f | barrier %.0f | phase B: load %.0f, "
-             "rec + dh1 %.0f, in split %.0f | barrier %.0f ticks\n", wg_ticks[4], wg_ticks[5], wg_ticks[6], wg_ticks[7], wg_ticks[0],
-             wg_ticks[1], wg_ticks[8], wg_ticks[9], wg_ticks[2], wg_ticks[3]);
-#endif
     return;
   }
 
-#ifndef NFOPP_WGRAD_16X16
   if constexpr (XO) {
     // ================== consumers, x32 order (round 4): waves 0..3 multiply on v_mfma_f32_32x32x16_bf16 ==================
     // The 16x16x32 form below issues 210 bf16 matrix instructions per wave and chunk, each holding the SIMD's vector issue port for 8
@@ -876,10 +750,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       phase_barrier();
       phase_barrier();
     }
-#ifdef NFOPP_WG_PROFILE
-    float wg_ticks[4] = {0.f, 0.f, 0.f, 0.f};
-    unsigned long long wg_t0 = __builtin_readcyclecounter();
-#endif
     int par = 0;   // record area of the chunk being multiplied (the staging waves' register-set parity)
     for (long long chunk = c0; chunk < n_chunks; chunk += step) {
       // ---- phase A: G1 out of bufA.  Per k step of 16 samples: the A fragments once, the B fragments one column tile ahead
@@ -900,18 +770,18 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
           }
           __builtin_amdgcn_sched_barrier(0);
           const s16x8 (&b)[3] = bf[st & 1];
-#ifndef NFOPP_ABL2_NO_MFMA
           acc1[ct] = mm(af[2], b[0], acc1[ct]);
           acc1[ct] = mm(af[0], b[2], acc1[ct]);
           acc1[ct] = mm(af[1], b[1], acc1[ct]);
           acc1[ct] = mm(af[1], b[0], acc1[ct]);
           acc1[ct] = mm(af[0], b[1], acc1[ct]);
           acc1[ct] = mm(af[0], b[0], acc1[ct]);
-#endif
           __builtin_amdgcn_sched_barrier(0);
         });
       }
-      {   // the mask plane of dh2 for THIS chunk (see the 16x16x32 form below)
+      {   // The mask plane of dh2 for THIS chunk (read by G2 in phase B), from the sign words of record area `par`: the staging
+          // waves bound both phases (8.6 k cycles per chunk against 5.8 k here), these waves would wait ~1.5 k cycles at the
+          // barrier below, and the item needs no registers to speak of (one LDS word in, one 8-byte store out).
         const float* rec = lds + L::REC + par * KS * 12;
 #pragma unroll
         for (int j = 0; j < (KS * H4 + WG_THREADS / 2 - 1) / (WG_THREADS / 2); ++j) {
@@ -925,9 +795,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
         }
         par ^= 1;
       }
-      WG_TICK(0)
       phase_barrier();
-      WG_TICK(1)
       // ---- phase B: G2 and G3 out of bufB
       {
         s16x8 am[2], bf[2][3];
@@ -949,11 +817,9 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
           float ga[4], gb[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) { ga[j] = g3_a[(4 * st + j) * L::RS_DE]; gb[j] = g3_b[(4 * st + j) * L::RS_DE]; }
-#ifndef NFOPP_ABL2_NO_MFMA
           acc2[ct] = mm(am[ks], b[2], acc2[ct]);
           acc2[ct] = mm(am[ks], b[1], acc2[ct]);
           acc2[ct] = mm(am[ks], b[0], acc2[ct]);
-#endif
           if (g3_mine) {
             acc3e = __builtin_amdgcn_mfma_f32_4x4x1f32(ga[0], gb[0], acc3e, 0, 0, 0);
             acc3o = __builtin_amdgcn_mfma_f32_4x4x1f32(ga[1], gb[1], acc3o, 0, 0, 0);
@@ -963,15 +829,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
           __builtin_amdgcn_sched_barrier(0);
         });
       }
-      WG_TICK(2)
       phase_barrier();
-      WG_TICK(3)
     }
-#ifdef NFOPP_WG_PROFILE
-    if (blockIdx.x == 0 && tid == 0)
-      printf("consumer wave 0 (32x32x16): G1 %.0f | barrier %.0f | G2+G3 %.0f | barrier %.0f ticks\n", wg_ticks[0], wg_ticks[1], wg_ticks[2],
-             wg_ticks[3]);
-#endif
     // ---- per-workgroup partial tiles, in the 16 x 16 tile order the reduce / gather kernels read: result (row, col) -> tile
     // (row / 16, col / 16), element 64 (row & 3) + 16 ((row & 15) >> 2) + (col & 15).  A lane of a 32 x 32 accumulator holds column
     // lane & 31 and the rows 8 (r >> 2) + 4 (lane >> 5) + (r & 3), r = 0..15.
@@ -1011,13 +870,12 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     }
     return;
   }
-#endif
   // ================================= consumers: waves 0..3 multiply =======================================================
   // G1 (7 x NKT tiles, dh1^T in): wave w owns the column blocks w, w + 4, w + 8, w + 12, all 7 row blocks each (a column block
   //   past NKT is multiplied on whatever the image holds there and never stored: 28 tiles for every wave).
   // G2 (7 x 7, dh2^T h1): w2 -> column blocks {2, 3}, w3 -> {4, 5}, w0 -> {0, 6}, w1 -> {1, 6}; block 6 is computed by both w0
   //   and w1 and stored by rows (w0: row blocks 0..3, w1: 4..6).   G3 (NKT x 1, de^T u, fp32): row blocks w, w+4, w+8, w+12.
-  const int grp = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3, i16 = lane & 15;
+  const int grp = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
   const int row0 = 16 * (grp >> 1) + 4 * (grp & 1) + qq;   // lane part of every transposing read: sample row, dwords 2p
   const int lane_h = row0 * L::R_H + 2 * pp, lane_in = row0 * L::R_IN + 2 * pp;
   constexpr int R_F = L::R_H, LS_F = L::P_H;   // images of h1 / dh1: three planes [KS][R_H]
@@ -1030,10 +888,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
   const float* const bB_dh2 = lds + L::B_DH2 + lane_h;
   const float* const bB_h1a = lds + L::B_H1 + lane_f + 8 * g2_cb0;
   const float* const bB_h1b = lds + L::B_H1 + lane_f + 8 * g2_cb1;
-#ifdef NFOPP_G3_16X16
-  const float* const rowk = lds + L::B_DE + grp * L::RS_DE + i16;
-#endif
-  f32x4 acc1[4][7], acc2[2][7], acc3[4];
+  f32x4 acc1[4][7], acc2[2][7];
   // G3 = de^T u has 4 useful columns (u_x, u_y, 1, theta): on v_mfma_f32_4x4x1_16b_f32 -- sixteen independent 4 x 4 blocks, one
   // rank-1 update each -- a lane feeds de[sample][64 w + lane] and u[sample][lane & 3], every output is a useful one and an
   // instruction takes 8 pipe cycles; the 16x16x4 form spent 32 cycles on tiles whose 12 other columns are zero, and an fp32 MFMA
@@ -1052,17 +907,13 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
   for (int c = 0; c < 2; ++c)
 #pragma unroll
     for (int r = 0; r < 7; ++r) acc2[c][r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc3[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // 7 row blocks against one pair of column blocks; the A fragments ping-pong between two register sets (no copies)
   // (image geometry as compile-time constants: row length and level step of the A image and of the B image)
-  // NA = levels of the A operand: 3, or 1 for an A that is exact in one bf16 level (the mask of G2 in x32 order)
   auto mul_pair = [&](const float* a_base, const float* b0_base, const float* b1_base, auto ra_c, auto la_c, auto rb_c, auto lb_c,
-                      auto na_c, f32x4 (&c0)[7], f32x4 (&c1)[7]) __attribute__((always_inline)) {
+                      f32x4 (&c0)[7], f32x4 (&c1)[7]) __attribute__((always_inline)) {
     constexpr int RA = decltype(ra_c)::value, LA = decltype(la_c)::value, RB = decltype(rb_c)::value, LB = decltype(lb_c)::value;
-    constexpr int NA = decltype(na_c)::value;
-    s16x8 bf0[3], bf1[3], af[2][NA];
+    s16x8 bf0[3], bf1[3], af[2][3];
     mfma_guard();   // the fragment registers below were operands of the MFMAs just issued
 #pragma unroll
     for (int lv = 0; lv < 3; ++lv) {
@@ -1070,17 +921,16 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       bf1[lv] = read_frag<RB>(b1_base, lv * LB);
     }
 #pragma unroll
-    for (int lv = 0; lv < NA; ++lv) af[0][lv] = read_frag<RA>(a_base, lv * LA);
+    for (int lv = 0; lv < 3; ++lv) af[0][lv] = read_frag<RA>(a_base, lv * LA);
     static_for<0, 7>([&](auto rc) __attribute__((always_inline)) {
       constexpr int r = decltype(rc)::value;
       if constexpr (r + 1 < 7) {
         if constexpr (r > 0) mfma_guard();   // set (r + 1) & 1 was read by step r - 1's MFMAs, issued just before
 #pragma unroll
-        for (int lv = 0; lv < NA; ++lv) af[(r + 1) & 1][lv] = read_frag<RA>(a_base, lv * LA + 8 * (r + 1));
+        for (int lv = 0; lv < 3; ++lv) af[(r + 1) & 1][lv] = read_frag<RA>(a_base, lv * LA + 8 * (r + 1));
       }
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (NA == 3) mfma_split_pair(af[r & 1], bf0, bf1, c0[r], c1[r]);
-      else mfma_mask_pair(af[r & 1][0], bf0, bf1, c0[r], c1[r]);
+      mfma_split_pair(af[r & 1], bf0, bf1, c0[r], c1[r]);
       __builtin_amdgcn_sched_barrier(0);
     });
   };
@@ -1088,11 +938,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     phase_barrier();
     phase_barrier();
   }
-#ifdef NFOPP_WG_PROFILE
-  float wg_ticks[4] = {0.f, 0.f, 0.f, 0.f};
-  unsigned long long wg_t0 = __builtin_readcyclecounter();
-#endif
-  int par = 0;   // record area of the chunk being multiplied (the staging waves' register-set parity)
   for (long long chunk = c0; chunk < n_chunks; chunk += step) {
     // phase A: G1 out of bufA
     using ic_rf = std::integral_constant<int, R_F>;
@@ -1101,34 +946,11 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     using ic_pin = std::integral_constant<int, L::P_IN>;
     using ic_rh = std::integral_constant<int, L::R_H>;
     using ic_ph = std::integral_constant<int, L::P_H>;
-    using ic3 = std::integral_constant<int, 3>;
-    mul_pair(bA_dh1, bA_in, bA_in + 32, ic_rf{}, ic_lf{}, ic_rin{}, ic_pin{}, ic3{}, acc1[0], acc1[1]);
-    mul_pair(bA_dh1, bA_in + 64, bA_in + 96, ic_rf{}, ic_lf{}, ic_rin{}, ic_pin{}, ic3{}, acc1[2], acc1[3]);
-#ifndef NFOPP_MASK_BY_STAGING_WAVES
-    if constexpr (XO) {
-      // The mask plane of dh2 for THIS chunk (read by G2 in phase B), from the sign words of record area `par`: the staging waves
-      // bound both phases (8.6 k cycles per chunk against 5.8 k here), these waves would wait ~1.5 k cycles at the barrier below,
-      // and the item needs no registers to speak of (one LDS word in, one 8-byte store out).
-      const float* rec = lds + L::REC + par * KS * 12;
-#pragma unroll
-      for (int j = 0; j < (KS * H4 + WG_THREADS / 2 - 1) / (WG_THREADS / 2); ++j) {
-        const int idx = tid + j * (WG_THREADS / 2), it = idx < KS * H4 ? idx : KS * H4 - 1;   // surplus threads repeat the last item
-        const int q = it / H4, c = it - q * H4;
-        const int word = (int)__float_as_uint(rec[q * 12 + 8 + (c & 3)]), sh = 4 * (c >> 2);
-        const unsigned m0 = (unsigned)__builtin_amdgcn_sbfe(word, sh, 1), m1 = (unsigned)__builtin_amdgcn_sbfe(word, sh + 1, 1);
-        const unsigned m2 = (unsigned)__builtin_amdgcn_sbfe(word, sh + 2, 1), m3 = (unsigned)__builtin_amdgcn_sbfe(word, sh + 3, 1);
-        const unsigned k01 = __builtin_amdgcn_perm(m1, m0, 0x07060302), k23 = __builtin_amdgcn_perm(m3, m2, 0x07060302);
-        *reinterpret_cast<u32x2*>(lds + L::B_DH2 + q * L::R_H + 2 * c) = u32x2{k01 & 0x3f803f80u, k23 & 0x3f803f80u};
-      }
-      par ^= 1;
-    }
-#endif
-    WG_TICK(0)
+    mul_pair(bA_dh1, bA_in, bA_in + 32, ic_rf{}, ic_lf{}, ic_rin{}, ic_pin{}, acc1[0], acc1[1]);
+    mul_pair(bA_dh1, bA_in + 64, bA_in + 96, ic_rf{}, ic_lf{}, ic_rin{}, ic_pin{}, acc1[2], acc1[3]);
     phase_barrier();
-    WG_TICK(1)
     // phase B: G2 and G3 out of bufB
-    mul_pair(bB_dh2, bB_h1a, bB_h1b, ic_rh{}, ic_ph{}, ic_rf{}, ic_lf{}, std::integral_constant<int, XO ? 1 : 3>{}, acc2[0], acc2[1]);
-#if !defined(NFOPP_ABL2_NO_G3) && !defined(NFOPP_G3_16X16)
+    mul_pair(bB_dh2, bB_h1a, bB_h1b, ic_rh{}, ic_ph{}, ic_rf{}, ic_lf{}, acc2[0], acc2[1]);
     if (g3_mine) {
 #pragma unroll
       for (int q = 0; q < KS; q += 2) {
@@ -1136,27 +958,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
         acc3o = __builtin_amdgcn_mfma_f32_4x4x1f32(g3_a[(q + 1) * G3_RA], g3_b[(q + 1) * G3_RB], acc3o, 0, 0, 0);
       }
     }
-#endif
-#if !defined(NFOPP_ABL2_NO_G3) && defined(NFOPP_G3_16X16)
-#pragma unroll
-    for (int s = 0; s < KS / 4; ++s) {          // G3: four independent fp32 chains, k-step outer
-      const float bu = rowk[4 * s * L::RS_DE + WIN];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int rb = wave + 4 * j < NKT ? wave + 4 * j : NKT - 1;   // idle slot: repeats the last row block, never stored
-        acc3[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(rowk[4 * s * L::RS_DE + 16 * rb], bu, acc3[j], 0, 0, 0);
-      }
-    }
-#endif
-    WG_TICK(2)
     phase_barrier();
-    WG_TICK(3)
   }
-#ifdef NFOPP_WG_PROFILE
-  if (blockIdx.x == 0 && tid == 0)
-    printf("consumer wave 0: G1 %.0f | barrier %.0f | G2+G3 %.0f | barrier %.0f ticks\n", wg_ticks[0], wg_ticks[1], wg_ticks[2],
-           wg_ticks[3]);
-#endif
 
   // ---- per-workgroup partial tiles (tile numbering and element order of the fp32 kernel) ---------------------------------
   auto put = [&](int T, const f32x4& v) __attribute__((always_inline)) {
@@ -1175,11 +978,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     const bool mine = wave >= 2 || (wave == 0 ? r < 4 : r >= 4);   // column block 6 is split by rows between waves 0 and 1
     if (mine) put(7 * NKT + r * 7 + g2_cb1, acc2[1][r]);
   }
-#ifdef NFOPP_G3_16X16
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (wave + 4 * j < NKT) put(7 * NKT + 49 + wave + 4 * j, acc3[j]);
-#else
   // G3 tiles in the 16 x 16 tile order the reduce / gather kernels read: row k, column c -> tile k / 16, element
   // 16 ((k % 16) / 4) + c + 64 (k % 4).  This lane holds rows 64 w + 4 (lane / 4) + i, column lane & 3; the columns 4..15 of
   // the tiles (the zero columns of the 16x16x4 form) are written as zeros by the lanes that own none of the others.
@@ -1201,7 +999,6 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       }
     }
   }
-#endif
 }
 
 // reduced[e] = sum over workgroups of partial[wg][e], fixed order: 64 elements per block, 16 row groups per element (thread
@@ -1392,18 +1189,8 @@ int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samp
   a.ws_h1 = ws + w.h1; a.ws_dh1 = ws + w.dh1; a.ws_de = ws + w.de; a.ws_u = ws + w.rec;
   a.loss_partial = ws + w.loss; a.g4_partial = ws + w.g4_partial;
   int grid_fwd = 0;
-  int rc = NFOPP_OK;
-#ifdef NFOPP_DEV_SKIP_PASS1   /* development timing: pass 2 alone on the factors of the first calls (env NFOPP_DEV_SKIP_PASS1) */
-  static int dev_calls = 0;
-  static int dev_grid = 0;
-  if (getenv("NFOPP_DEV_SKIP_PASS1") && dev_calls++ >= 2) grid_fwd = dev_grid;
-  else
-#endif
-  rc = xo ? launch_onf_x32_train_kernel(a, st, &grid_fwd) : launch_onf_train_kernel(a, st, &grid_fwd);
+  int rc = xo ? launch_onf_x32_train_kernel(a, st, &grid_fwd) : launch_onf_train_kernel(a, st, &grid_fwd);
   if (rc) return rc;
-#ifdef NFOPP_DEV_SKIP_PASS1
-  dev_grid = grid_fwd;
-#endif
 
   WgradArgs wa;
   wa.geom = g; wa.params = params; wa.aug_feature = aug; wa.x32_order = xo ? 1 : 0;

@@ -221,40 +221,19 @@ __device__ __forceinline__ u32x4 lds_tr(const unsigned char* lds, int byte0, int
 // FIRST: the accumulator starts here -- the first product takes a literal zero as its C operand (no register zeroing)
 template <int SLOT0, bool FIRST = false, class W>
 __device__ __forceinline__ void step6(f32x16& acc, const u32x4& ah, const u32x4& am, const u32x4& al, const u32x4 (&b)[3],
-                                      W&& work_in) {
-#ifdef X32_ABL_NOWORK   /* timing-only ablation (results wrong): the MFMA steps without the hooked vector work */
-  auto work = [](auto) {};
-  (void)work_in;
-#else
-  auto& work = work_in;
-#endif
+                                      W&& work) {
   if constexpr (FIRST) {
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     acc = mfma32(al, b[0], zero);
   } else {
     acc = mfma32(al, b[0], acc);
   }
-#if defined(X32_GROUP2)   /* development A/B: MFMAs in pairs, the work of both slots behind the pair */
-  acc = mfma32(ah, b[2], acc); work(ic<SLOT0 + 0>{}); work(ic<SLOT0 + 1>{}); __builtin_amdgcn_sched_barrier(0);
-  acc = mfma32(am, b[1], acc);
-  acc = mfma32(am, b[0], acc); work(ic<SLOT0 + 2>{}); work(ic<SLOT0 + 3>{}); __builtin_amdgcn_sched_barrier(0);
-  acc = mfma32(ah, b[1], acc);
-  acc = mfma32(ah, b[0], acc); work(ic<SLOT0 + 4>{}); work(ic<SLOT0 + 5>{}); __builtin_amdgcn_sched_barrier(0);
-#elif defined(X32_NO_FENCE)   /* development A/B: hipcc places the work items */
-  work(ic<SLOT0 + 0>{});
-  acc = mfma32(ah, b[2], acc); work(ic<SLOT0 + 1>{});
-  acc = mfma32(am, b[1], acc); work(ic<SLOT0 + 2>{});
-  acc = mfma32(am, b[0], acc); work(ic<SLOT0 + 3>{});
-  acc = mfma32(ah, b[1], acc); work(ic<SLOT0 + 4>{});
-  acc = mfma32(ah, b[0], acc); work(ic<SLOT0 + 5>{});
-#else
   work(ic<SLOT0 + 0>{}); __builtin_amdgcn_sched_barrier(0);
   acc = mfma32(ah, b[2], acc); work(ic<SLOT0 + 1>{}); __builtin_amdgcn_sched_barrier(0);
   acc = mfma32(am, b[1], acc); work(ic<SLOT0 + 2>{}); __builtin_amdgcn_sched_barrier(0);
   acc = mfma32(am, b[0], acc); work(ic<SLOT0 + 3>{}); __builtin_amdgcn_sched_barrier(0);
   acc = mfma32(ah, b[1], acc); work(ic<SLOT0 + 4>{}); __builtin_amdgcn_sched_barrier(0);
   acc = mfma32(ah, b[0], acc); work(ic<SLOT0 + 5>{}); __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 
 // one instruction of the exact pair split (11 per pair): x0, x1 -> one word of each level
@@ -289,11 +268,7 @@ __device__ __forceinline__ void eval_item(EvalState& s, const f32x4& tw, float u
   if constexpr (U == 4) s.r = fmaf(s.j, -6.28318548202514648f, s.arg);
   if constexpr (U == 5) s.r = fmaf(s.j, 1.74845553e-07f, s.r);
   if constexpr (U == 6) s.v = fmaf(s.r, 0.159154943f, tw.w);
-#ifdef X32_ABL_NOSIN   /* timing-only ablation (results wrong): a plain vector instruction in place of v_sin_f32 in the hooks */
-  if constexpr (U == 7) s.v = s.v * 0.5f;
-#else
   if constexpr (U == 7) s.v = __builtin_amdgcn_sinf(s.v);
-#endif
 }
 
 // Workgroup shapes: XT = 512 threads (two waves per SIMD, 256 samples per pass) fills the chip at scale; XT = 256 (one wave per
@@ -301,39 +276,13 @@ __device__ __forceinline__ void eval_item(EvalState& s, const f32x4& tw, float u
 // wave alone on its SIMD finishes its tile in about half the time (B = 1 drop-in latency).  A tile's arithmetic does not
 // depend on the shape, so results are bit-identical either way (sharding-independent).
 
-// Development build (make EXTRA=-DX32_PHASE_PROFILE): waves 0 and 4 of every workgroup accumulate clock ticks per phase of the
-// chunk loop; launch_t prints the shares every tenth launch of the mode-0 kernel (synchronous, stderr).
-#ifdef X32_PHASE_PROFILE
-#define X32_TICK(SLOT)                                             \
-  {                                                                \
-    const unsigned long long now_ = __builtin_readcyclecounter();  \
-    phase_ticks[SLOT] += (float)(now_ - phase_t0);                 \
-    phase_t0 = now_;                                               \
-  }
-#else
-#define X32_TICK(SLOT)
-#endif
-
 // Third-level (blob) fragments are fetched LOOK steps ahead into a ring of RL registers sets
-#ifndef X32_LOOK
-#define X32_LOOK 3   /* development A/B: 6 = a ring of 8 */
-#endif
-constexpr int LOOK = X32_LOOK, RL = LOOK <= 3 ? 4 : 8;
-static_assert(LOOK == 3 || LOOK == 6, "look-ahead of the third-level fragments");
+constexpr int LOOK = 3, RL = 4;
 
 // One MFMA step for NT point tiles that share the weight fragments: the six partial products in the order of step6, each
 // issued for tile 0 .. NT-1 in turn (independent accumulators alternate on the matrix pipe); WORK(slot) runs behind MFMA
 // number slot - SLOT0 (6 NT slots per step).
-#ifdef X32_ABL_TILE3_HALF   /* 1: L1's fourth output tile, 2: L1, L2 and L2^T */
-#define X32_HALF_L1(mt) ((mt) == 3)
-#define X32_HALF_L2(mt) ((mt) == 3 && X32_ABL_TILE3_HALF >= 2)
-#else
-#define X32_HALF_L1(mt) false
-#define X32_HALF_L2(mt) false
-#endif
-// HALF (timing-only ablation X32_ABL_TILE3_HALF, results wrong): the step's six products as v_mfma_f32_16x16x32_bf16 -- the same
-// number of matrix instructions and hook slots at half the pipe cycles each: what a 16-row remainder tile could save at best
-template <int NT, int SLOT0, bool FIRST, bool HALF = false, class W>
+template <int NT, int SLOT0, bool FIRST, class W>
 __device__ __forceinline__ void stepN(f32x16 (&acc)[NT], const u32x4& ah, const u32x4& am, const u32x4& al,
                                       const u32x4 (&b)[NT][3], W&& work) {
   sfor<0, 6>([&](auto pc) {
@@ -342,16 +291,7 @@ __device__ __forceinline__ void stepN(f32x16 (&acc)[NT], const u32x4& ah, const 
       constexpr int T = decltype(tc)::value;
       const u32x4& a_ = p == 0 ? al : ((p == 2 || p == 3) ? am : ah);
       const u32x4& b_ = b[T][p == 1 ? 2 : ((p == 2 || p == 4) ? 1 : 0)];
-      if constexpr (HALF) {
-        f32x4 c4 = {acc[T][0], acc[T][1], acc[T][2], acc[T][3]};
-        if constexpr (FIRST && p == 0) c4 = f32x4{0.f, 0.f, 0.f, 0.f};
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a_), __builtin_bit_cast(bf16x8, b_), c4, 0, 0, 0);
-        acc[T][0] = c4[0]; acc[T][1] = c4[1]; acc[T][2] = c4[2]; acc[T][3] = c4[3];
-        if constexpr (FIRST && p == 0) {
-#pragma unroll
-          for (int r = 4; r < 16; ++r) acc[T][r] = 0.0f;
-        }
-      } else if constexpr (FIRST && p == 0) {
+      if constexpr (FIRST && p == 0) {
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         acc[T] = mfma32(a_, b_, zero);
       } else {
@@ -382,9 +322,10 @@ __device__ __forceinline__ void eval_any_item(EvalAnyState& s, const f32x4& tw, 
   if constexpr (U == 11) s.v = is_one ? 1.0f : s.v;
 }
 
-// NT = 32-sample tiles per wave.  Shapes in use (x32::launch_t): <512 threads, NT 1> two waves per SIMD; <256, 2> one wave
-// per SIMD with two tiles sharing every weight fragment (half the LDS / L2 fragment traffic per sample, two independent
-// accumulation and hook chains in one stream); <256, 1> for small launches.  A tile's arithmetic is the same in all of them.
+// NT = 32-sample tiles per wave.  Shapes launched by x32::launch_t: <512 threads, NT 1> two waves per SIMD; <256, 1> for small
+// launches.  NT = 2 (one wave per SIMD with two tiles sharing every weight fragment: half the LDS / L2 fragment traffic per
+// sample, two independent accumulation and hook chains in one stream) ran at exactly the time of <512, 1> and
+// is not launched.  A tile's arithmetic is the same in all of them.
 template <int NKB, int MODE, int XT, int NT>
 __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelArgs a, const u32x4* __restrict__ img,
                                                          const u32x4* __restrict__ blob) {
@@ -406,9 +347,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
   __syncthreads();
   // static priority for the younger half (MI355X_MICROARCH.md); the condition must be provably wave-uniform, or hipcc
   // lowers it to an exec mask around an UNCONDITIONAL s_setprio
-#ifndef X32_NO_PRIO
   if (XT == 512 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
 
   const OnfGeom& geo = a.geom;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -454,22 +393,12 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
   const __amdgpu_buffer_rsrc_t blob_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(blob), 0, (int)C::BLOB_BYTES, 0x00020000);
   auto lo_frag = [&](int step) __attribute__((always_inline)) {
-#ifdef X32_ABL_NOLO   /* timing-only ablation (results wrong): no third-level loads */
-    return u32x4{(unsigned)step, lane16, 0u, 0u};
-#elif defined(X32_ABL_LO_L1)   /* timing-only ablation (results wrong): the same loads from a 7 KB window -- served by the CU's L1 */
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(blob_rsrc, lane16, (step % 7) * 1024, 0));
-#else
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(blob_rsrc, lane16, step * 1024, 0));
-#endif
   };
 
   const long long n_work = TRAIN ? a.n_points : work_points(a);
   const long long n_chunks = (n_work + CH - 1) / CH;
 
-#ifdef X32_PHASE_PROFILE
-  float phase_ticks[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  unsigned long long phase_t0 = __builtin_readcyclecounter();
-#endif
   if (n_chunks <= (long long)blockIdx.x) return;   // (an empty live list: nothing to do)
   // third-level fragments: ring of 4, three steps ahead, running on across the GEMMs (blob steps are consecutive) and,
   // at the end of a chunk, on into the first steps of the next
@@ -486,19 +415,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
   float loss_acc = 0.f;   // TRAIN
   // TRAIN: 16-byte store of four consecutive positions of this lane's sample row (rows past P: dropped by the range check)
   auto st4 = [](const __amdgpu_buffer_rsrc_t& r, int voff, float x0, float x1, float x2, float x3) __attribute__((always_inline)) {
-#ifdef X32_ABL_NOSTORE   /* timing-only ablation: the training pass without its factor stores (values kept alive) */
-    asm volatile("" :: "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(voff));
-    return;
-#endif
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)}, r, voff, 0, 0);
   };
-#ifdef X32_STAGGER   /* development A/B (MI355X_MICROARCH.md, two waves per SIMD, item 9): the second-dispatched half of the workgroup
-                        starts X32_STAGGER x 8 k cycles late, so that SIMD partners are out of phase at the GEMM boundaries */
-  if (XT == 512 && wave >= 4) {
-#pragma unroll 1
-    for (int q = 0; q < X32_STAGGER; ++q) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   for (long long chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
     float ux[NT], uy[NT], th[NT];
     long long pidx[NT];
@@ -544,11 +462,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       asm volatile("" : "+s"(wave_s));
       long long rows = a.n_points - (chunk * CH + wave_s * 32);
       rows = rows > 32 ? 32 : (rows < 0 ? 0 : rows);
-#ifdef X32_ABL_STORE_SAME   /* timing-only ablation (results wrong): every wave stores to the same few rows -- no HBM traffic */
-      const long long p0 = wave_s * 32;
-#else
       const long long p0 = rows > 0 ? chunk * CH + wave_s * 32 : 0;
-#endif
       return __builtin_amdgcn_make_buffer_rsrc(base + p0 * row_floats, 0, (int)(rows * row_floats * 4), 0x00020000);
     };
     __amdgpu_buffer_rsrc_t r_h1 = __builtin_amdgcn_make_buffer_rsrc((float*)nullptr, 0, 0, 0x00020000), r_dh1 = r_h1, r_de = r_h1, r_rec = r_h1;
@@ -593,7 +507,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           split_pair(feature_any(special_c, T, kb, 2 * p), feature_any(special_c, T, kb, 2 * p + 1), out[T], p);
     };
 
-    X32_TICK(0)   // sampling
     // ================================================================ L1: a1 = W1ext in
     f32x16 acc1[4][NT];
     {
@@ -683,7 +596,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           }
           fl[(4 * PAR + mt + LOOK) & (RL - 1)] = lo_frag(C::S_L1 + 4 * kb + mt + LOOK);
           __builtin_amdgcn_sched_barrier(0);
-          stepN<NT, 6 * NT * mt, FIRST, X32_HALF_L1(mt)>(acc1[mt], fh[mt & 1], fm[mt & 1], fl[(4 * PAR + mt) & (RL - 1)], bc, [&](auto slot) {
+          stepN<NT, 6 * NT * mt, FIRST>(acc1[mt], fh[mt & 1], fm[mt & 1], fl[(4 * PAR + mt) & (RL - 1)], bc, [&](auto slot) {
             if constexpr (HOOK == 1) sfor<0, 5>([&](auto i) { l1_item(ic<5 * decltype(slot)::value + decltype(i)::value>{}, bn); });
             if constexpr (HOOK == 2) sfor<0, 6>([&](auto i) { l1_item_any(ic<6 * decltype(slot)::value + decltype(i)::value>{}, bn); });
           });
@@ -708,7 +621,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         else l1_block(ic<HK2>{}, ic<(kb & 1)>{}, kb, bB, bA, std::false_type{});
       });
     }
-    X32_TICK(1)   // L1
     float skipv[NT];   // position 100 = tile 3, g = 1, register 0: W3b . in + b3 (lanes g = 1)
 #pragma unroll
     for (int T = 0; T < NT; ++T) skipv[T] = acc1[3][T][0];
@@ -756,7 +668,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           }
           fl[(C::S_L2 + 4 * kb + mt + LOOK) & (RL - 1)] = lo_frag(C::S_L2 + 4 * kb + mt + LOOK);
           __builtin_amdgcn_sched_barrier(0);
-          stepN<NT, 6 * NT * mt, kb == 0, X32_HALF_L2(mt)>(acc2[mt], fh[mt & 1], fm[mt & 1], fl[(C::S_L2 + 4 * kb + mt) & (RL - 1)], bb[kb & 1], [&](auto slot) {
+          stepN<NT, 6 * NT * mt, kb == 0>(acc2[mt], fh[mt & 1], fm[mt & 1], fl[(C::S_L2 + 4 * kb + mt) & (RL - 1)], bb[kb & 1], [&](auto slot) {
             if constexpr (kb + 1 < HK)
               sfor<0, 3>([&](auto i) { h1_item(ic<kb + 1>{}, ic<3 * decltype(slot)::value + decltype(i)::value>{}, bb[(kb + 1) & 1]); });
           });
@@ -764,7 +676,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       });
     }
 
-    X32_TICK(2)   // L2
     if constexpr (FWD_ONLY) {
       // the summation order of the full kernel (two chains over the element parity, blocks in order): same logits bit for bit
 #pragma unroll
@@ -813,13 +724,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           constexpr int u = !TRAIN ? u0 : (u0 < 8 ? u0 : (u0 < 10 ? 92 + u0 : u0 - 2));
           // (the 28 bit constants live in scalar registers and push a few of those into spill lanes; pushing the bits in with
           // v_alignbit instead frees them but moves the pressure to the vector file: 51 instead of 35 spilled registers, +3 %)
-#ifndef X32_SGN_PUSH
           if constexpr (u == 100) sgn[T][p >> 1] |= mk[T][0] & (1u << (4 * kb + (e0 & 3)));
           if constexpr (u == 101) sgn[T][p >> 1] |= mk[T][1] & (1u << (4 * kb + (e0 & 3) + 1));
-#else   /* development A/B: bits pushed in from the low end, element (kb, r) ends at bit 27 - (4 kb + r) */
-          if constexpr (u == 100) sgn[T][p >> 1] = __builtin_amdgcn_alignbit(sgn[T][p >> 1], mk[T][0], 31);
-          if constexpr (u == 101) sgn[T][p >> 1] = __builtin_amdgcn_alignbit(sgn[T][p >> 1], mk[T][1], 31);
-#endif
           if constexpr (u == 0) hv[T][0] = relu1(acc2[t][T][r0]);
           if constexpr (u == 1) hv[T][1] = relu1(acc2[t][T][r0 + 1]);
           if constexpr (u == 2) mk[T][0] = 0u - __float_as_uint(hv[T][0]);
@@ -853,7 +759,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           else if constexpr (kb + 1 < HK) fetch(kb + 1, 0, kb + 1 == 6, 0);
           fl[(C::S_L2T + 4 * kb + mt + LOOK) & (RL - 1)] = lo_frag(C::S_L2T + 4 * kb + mt + LOOK);
           __builtin_amdgcn_sched_barrier(0);
-          stepN<NT, 6 * NT * mt, kb == 0, X32_HALF_L2(mt)>(accd[mt], fh[mt & 1], fm[mt & 1], fl[(C::S_L2T + 4 * kb + mt) & (RL - 1)], bb[kb & 1], [&](auto slot) {
+          stepN<NT, 6 * NT * mt, kb == 0>(accd[mt], fh[mt & 1], fm[mt & 1], fl[(C::S_L2T + 4 * kb + mt) & (RL - 1)], bb[kb & 1], [&](auto slot) {
             if constexpr (kb + 1 < HK)
               sfor<0, DH2_PS>([&](auto i) { dh2_item(ic<kb + 1>{}, ic<DH2_PS * decltype(slot)::value + decltype(i)::value>{}, bb[(kb + 1) & 1]); });
           });
@@ -881,13 +787,9 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       rho[0] = t_valid ? (sg - yv) * a.inv_count : 0.0f;
       if (t_valid && g == 0) loss_acc += lp * a.inv_count;
       if (g == 0) st4(r_rec, vo_rec + 16, rho[0], 0.0f, 0.0f, 0.0f);
-#ifdef X32_SGN_PUSH
-      sgn[0][0] = __builtin_bitreverse32(sgn[0][0]) >> 4; sgn[0][1] = __builtin_bitreverse32(sgn[0][1]) >> 4;
-#endif
       __builtin_amdgcn_raw_buffer_store_b32(sgn[0][0], r_rec, vo_rec + 32 + 4 * g, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b32(sgn[0][1], r_rec, vo_rec + 40 + 4 * g, 0, 0);
     }
-    X32_TICK(3)   // L2^T
 
     // ================================================================ dh1 = accd * [a1 > 0], dh1[skip row] = 1; three levels
     // Block 0 here; blocks 1..6 behind the steps of L1^T's first output tile (each step kb prepares block kb + 1).
@@ -916,7 +818,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     };
     sfor<0, 4 * DH1_IP * NT>([&](auto w) { dh1_item(ic<0>{}, w); });
 
-    X32_TICK(4)   // dh1
     // ================================================================ L1^T: din = W1ext^T dh1, then the chain rule
     float gxs[NT][2], gys[NT][2], gt[NT];
 #pragma unroll
@@ -1020,7 +921,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
 #pragma unroll
         for (int T = 0; T < NT; ++T) accp[T] = accc[T];
       }
-      X32_TICK(5)   // L1^T steps + hooked epilogues
       ep_any(C::NMT - 1, accp);
 #pragma unroll
       for (int q = 0; q < LOOK; ++q) fl[q] = fl7[q];   // the first steps of the next chunk (fetched during the last tile)
@@ -1032,7 +932,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       if (a.out4 && g == 0 && pidx[T] < a.n_points)
         *reinterpret_cast<f32x4*>(a.out4 + pidx[T] * 4) = f32x4{logit[T], gx / geo.sigma, gy / geo.sigma, gth};
     }
-    X32_TICK(6)   // last epilogue + output
   }
   if constexpr (TRAIN) {   // loss per wave, fixed order; the host sums 8 rows per workgroup whatever the shape
 #pragma unroll
@@ -1042,10 +941,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       if (XT == 256) a.loss_partial[blockIdx.x * 8 + 4 + wave] = 0.0f;
     }
   }
-#ifdef X32_PHASE_PROFILE
-  if (MODE == 0 && a.ws_u && (threadIdx.x == 0 || threadIdx.x == 256))
-    for (int k = 0; k < 8; ++k) atomicAdd(a.ws_u + k + (threadIdx.x ? 8 : 0), phase_ticks[k]);
-#endif
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
@@ -1094,30 +989,6 @@ static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_ou
   long long grid = query_cus();
   if (grid > n_chunks) grid = n_chunks;
   if (grid_out) *grid_out = (int)grid;
-#ifdef X32_PHASE_PROFILE
-  if (MODE == 0) {   // development only: synchronous, prints to stderr
-    static float* dbg = nullptr;
-    if (!dbg) NFOPP_HIP(hipMalloc(&dbg, 64));
-    NFOPP_HIP(hipMemsetAsync(dbg, 0, 64, stream));
-    OnfKernelArgs b = a;
-    b.ws_u = dbg;   // unused by this mode: carries the tick buffer
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(XT), IMG_BYTES, stream, b, (const u32x4*)img, (const u32x4*)blob);
-    float h[16];
-    NFOPP_HIP(hipMemcpyAsync(h, dbg, 64, hipMemcpyDeviceToHost, stream));
-    NFOPP_HIP(hipStreamSynchronize(stream));
-    static int calls = 0;
-    if (++calls % 10 == 0) {
-      const char* names[7] = {"sampling", "L1", "L2", "L2T+logit", "dh1", "L1T", "tail+out"};
-      for (int w = 0; w < 2; ++w) {
-        float tot = 0;
-        for (int k = 0; k < 7; ++k) tot += h[8 * w + k];
-        fprintf(stderr, "[x32 phase profile] wave %d of %lld workgroups: %.0f ticks per workgroup\n", 4 * w, grid, tot / grid);
-        for (int k = 0; k < 7; ++k) fprintf(stderr, "   %-10s %5.1f %%\n", names[k], 100.0f * h[8 * w + k] / tot);
-      }
-    }
-    return NFOPP_OK;
-  }
-#endif
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(XT), IMG_BYTES, stream, a, (const u32x4*)img, (const u32x4*)blob);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;
@@ -1125,15 +996,8 @@ static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_ou
 
 template <int NKB, int MODE>
 static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
-#ifdef X32_THREADS   /* development A/B: one shape at every size (X32_TILES = 32-sample tiles per wave) */
-#ifndef X32_TILES
-#define X32_TILES 1
-#endif
-  return launch_shape<NKB, MODE, X32_THREADS, MODE == 1 ? 1 : X32_TILES>(a, stream, grid_out);
-#else
   return a.n_points < (long long)query_cus() * 256 ? launch_shape<NKB, MODE, 256, 1>(a, stream, grid_out)
                                                    : launch_shape<NKB, MODE, 512, 1>(a, stream, grid_out);
-#endif
 }
 
 // the three modes of one feature dimension (used by csrc/onf_x32_k*.hip)

@@ -17,9 +17,6 @@ constexpr int TU_THREADS = 256;
 // velocity-Hessian weight (a user hyper-parameter the reference accepts at any value: w = 10, N = 512 needs 205 KB);
 // beyond the budget those waypoints read their coefficients from global memory tap by tap.
 constexpr size_t K2_BND_BUDGET = 32 * 1024;
-#ifndef NFOPP_K2_WAVES
-#define NFOPP_K2_WAVES 1   /* minimum waves per SIMD the register allocation aims at (A/B: 6 and 8 below) */
-#endif
 
 struct TrajUpdateArgs {
   nfopp_traj_hyper hp;
@@ -122,7 +119,7 @@ __device__ __forceinline__ void collision_terms(const nfopp_traj_hyper& hp, floa
 }
 
 template <int D>
-__global__ __launch_bounds__(TU_THREADS, NFOPP_K2_WAVES) void traj_update_kernel(const TrajUpdateArgs a) {
+__global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUpdateArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int N = a.n;
   const int W = a.half_width, NB_LO = a.interior_lo;

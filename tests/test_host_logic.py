@@ -270,3 +270,22 @@ def test_traj_steps_validates_its_arguments_without_a_gpu():
     sched.t_mode = 2
     assert lib.nfopp_traj_steps(cfg, params, hp, buf, sched, 0, None, None, None) == -1
     assert lib.nfopp_traj_steps(None, params, hp, buf, sched, 0, None, None, None) == -1
+
+
+def test_kernels_carry_no_build_switches():
+    """The library is built one way only: no HIP source or header tests a macro other than the device-compile pass and the
+    MFMA hazard precaution.  (A development switch left in the product could ship wrong results from one stray -D flag.)"""
+    import glob
+    allowed = {"__HIP_DEVICE_COMPILE__", "NFOPP_MFMA_GUARD"}
+    csrc = os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert files
+    tested = {}
+    for path in files:
+        src = open(path).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, re.M):
+            cond = re.sub(r"/\*.*|//.*", "", m.group(1))
+            for name in set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}:
+                tested.setdefault(name, os.path.basename(path))
+    extra = {n: f for n, f in tested.items() if n not in allowed}
+    assert not extra, extra
