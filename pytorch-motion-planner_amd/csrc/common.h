@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <mutex>
+
 #include "nfopp_hip.h"
 
 namespace nfopp {
@@ -31,12 +33,84 @@ int hip_fail(hipError_t e, const char* what);
 // device's copy of the code object, so "already set" flags are kept per device (csrc/runtime.hip).
 constexpr int MAX_DEVICES = 64;
 int current_device();   // hipGetDevice, -1 on failure (error string set)
+int query_cus();        // CU count of the current device (cached), 256 if it cannot be queried
 // Raises the dynamic-LDS limit of `kernel` on the current device the first time it is launched there.
 // `flags` is the caller's static bool[MAX_DEVICES] for that kernel instantiation.
 int ensure_dynamic_lds(const void* kernel, size_t bytes, bool* flags);
 // Content version the caller registered for a parameter buffer on the current device (nfopp_onf_params_version), 0 = none.
 unsigned long long onf_params_version_of(const float* params_dev);
 void onf_params_invalidate(const float* params_dev);
+
+// Persistent launch of KERNEL: one workgroup of `threads` per CU, fewer when there are only `n_chunks` pieces of work,
+// with `lds` bytes of dynamic LDS; *grid_out (if given) receives the workgroup count.
+template <auto KERNEL, class... Args>
+int launch_persistent(size_t lds, int threads, long long n_chunks, hipStream_t stream, int* grid_out, const Args&... args) {
+  static bool attr_set[MAX_DEVICES] = {};
+  const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, attr_set);
+  if (rc != NFOPP_OK) return rc;
+  long long grid = query_cus();
+  if (grid > n_chunks) grid = n_chunks;
+  if (grid_out) *grid_out = (int)grid;
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(threads), lds, stream, args...);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}
+
+// A scratch device buffer per (device, stream), for kernels that rewrite their scratch on the launch stream in front of
+// every launch: launches of one stream are ordered by the stream itself, and two streams (two planners with different
+// fields) never share a buffer.  16 buffers per device -- a handful of streams is the realistic case, though PyTorch's
+// pool alone hands out 32 per priority -- and once all are taken the least recently used one is reused after one
+// hipDeviceSynchronize (its stream may still be running on it).  Buffers grow on demand.  `Tag` is what the caller
+// records about a buffer's content (csrc/onf_x32.hip: what its weight image was built from); it is kept under the pool's
+// lock and reset to Tag{} whenever the buffer changes stream or is reallocated.
+struct NoTag {};
+template <class Tag = NoTag>
+class StreamScratch {
+ public:
+  // *buf = a buffer of at least `bytes` for `stream` on the current device, *tag = its record, *slot = its handle
+  int acquire(size_t bytes, hipStream_t stream, void** buf, Tag* tag = nullptr, int* slot = nullptr) {
+    const int dev = current_device();
+    if (dev < 0) return NFOPP_ERR_HIP;
+    std::lock_guard<std::mutex> lock(mutex_);
+    Slot* const row = slots_ + dev * SLOTS;
+    Slot* s = nullptr;
+    for (int k = 0; k < SLOTS && !s; ++k)
+      if (row[k].used && row[k].stream == stream) s = &row[k];
+    for (int k = 0; k < SLOTS && !s; ++k)
+      if (!row[k].used) { s = &row[k]; s->used = true; }
+    if (!s) {
+      s = &row[0];
+      for (int k = 1; k < SLOTS; ++k)
+        if (row[k].stamp < s->stamp) s = &row[k];
+      NFOPP_HIP(hipDeviceSynchronize());
+    }
+    if (s->stream != stream) s->tag = Tag{};
+    s->stream = stream;
+    s->stamp = ++stamp_;
+    if (s->bytes < bytes) {
+      if (s->ptr) NFOPP_HIP(hipFree(s->ptr));
+      s->ptr = nullptr; s->bytes = 0; s->tag = Tag{};
+      NFOPP_HIP(hipMalloc(&s->ptr, bytes));
+      s->bytes = bytes;
+    }
+    *buf = s->ptr;
+    if (tag) *tag = s->tag;
+    if (slot) *slot = (int)(s - slots_);
+    return NFOPP_OK;
+  }
+  // records what the buffer of `slot` now holds, unless another stream has taken it over meanwhile
+  void set_tag(int slot, hipStream_t stream, const Tag& tag) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    if (slots_[slot].stream == stream) slots_[slot].tag = tag;
+  }
+
+ private:
+  static constexpr int SLOTS = 16;
+  struct Slot { hipStream_t stream; void* ptr; size_t bytes; bool used; unsigned long long stamp; Tag tag; };
+  Slot slots_[MAX_DEVICES * SLOTS] = {};
+  unsigned long long stamp_ = 0;
+  std::mutex mutex_;
+};
 
 // ---- ONF parameter buffer geometry (state_dict order, include/nfopp_hip.h) --------------------------------------
 struct OnfGeom {

@@ -424,178 +424,38 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
-static int g_num_cus[MAX_DEVICES] = {};
-
-int query_cus() {
-  const int dev = current_device();
-  if (dev < 0) return 256;
-  if (g_num_cus[dev] > 0) return g_num_cus[dev];
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-  g_num_cus[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  return g_num_cus[dev];
-}
-
-template <int NKT, int NT, int MODE = 0>
-static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
-  using L = Lds<NKT>;
-  static bool attr_set[MAX_DEVICES] = {};
-  auto kern = onf_fwd_bwd_kernel<NKT, NT, MODE>;
-  const int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), L::BYTES, attr_set);
-  if (rc_attr != NFOPP_OK) return rc_attr;
+template <int NKT, int NT, int MODE>
+static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
   constexpr int CH = WAVES * 16 * NT;
-  long long n_chunks = (a.n_points + CH - 1) / CH;
-  long long grid = query_cus();
-  if (grid > n_chunks) grid = n_chunks;
-  if (grid_out) *grid_out = (int)grid;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), L::BYTES, stream, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_persistent<onf_fwd_bwd_kernel<NKT, NT, MODE>>(Lds<NKT>::BYTES, THREADS, (a.n_points + CH - 1) / CH, stream,
+                                                              grid_out, a);
 }
 
-int launch_onf_kernel(const OnfKernelArgs& a, hipStream_t stream) {
-  if (a.n_points <= 0) return NFOPP_OK;
-  if (onf_split_enabled()) return launch_onf_split_kernel(a, stream, false);
-  const int nkt = (a.geom.fin + 15) / 16;
-  // small jobs: one tile per wave so that more CUs take part; large jobs: two tiles per wave (half the LDS reads)
-  const bool small = a.n_points < (long long)query_cus() * WAVES * 16 * 2;
+// Small jobs: one tile per wave so that more CUs take part; large jobs: two tiles per wave (half the LDS reads).  7-8 input
+// tiles keep one (NT = 2 spills with S1 = 129 images), and so does the training pass: its factor stores need the registers
+// the second tile would take.
+template <int NKT, int MODE>
+static int launch_nt(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
+  if constexpr (NKT >= 13 && MODE != ONF_TRAIN)
+    if (a.n_points >= (long long)query_cus() * WAVES * 16 * 2) return launch_t<NKT, 2, MODE>(a, stream, grid_out);
+  return launch_t<NKT, 1, MODE>(a, stream, grid_out);
+}
+
+template <int NKT>
+static int launch_mode(int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
+  return mode == ONF_EVAL ? launch_nt<NKT, ONF_EVAL>(a, stream, grid_out)
+         : mode == ONF_TRAIN ? launch_nt<NKT, ONF_TRAIN>(a, stream, grid_out)
+                             : launch_nt<NKT, ONF_LOGITS>(a, stream, grid_out);
+}
+
+int launch_fp32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
   switch (nkt) {
-    case 14: return small ? launch_t<14, 1>(a, stream) : launch_t<14, 2>(a, stream);
-    case 13: return small ? launch_t<13, 1>(a, stream) : launch_t<13, 2>(a, stream);
-    case 8: return launch_t<8, 1>(a, stream);   // 7-8 input tiles: NT = 2 spills (S1 = 129 images), keep one tile
-    case 7: return launch_t<7, 1>(a, stream);
-    default:
-      set_error("unsupported ONF feature dimension %d", a.geom.fin);
-      return NFOPP_ERR_ARG;
+    case 14: return launch_mode<14>(mode, a, stream, grid_out);
+    case 13: return launch_mode<13>(mode, a, stream, grid_out);
+    case 8: return launch_mode<8>(mode, a, stream, grid_out);
+    case 7: return launch_mode<7>(mode, a, stream, grid_out);
+    default: return onf_unsupported(a.geom);
   }
-}
-
-int launch_onf_logits_kernel(const OnfKernelArgs& a, hipStream_t stream) {
-  if (a.n_points <= 0) return NFOPP_OK;
-  if (onf_split_enabled()) return launch_onf_split_kernel(a, stream, true);
-  const int nkt = (a.geom.fin + 15) / 16;
-  const bool small = a.n_points < (long long)query_cus() * WAVES * 16 * 2;
-  switch (nkt) {
-    case 14: return small ? launch_t<14, 1, 2>(a, stream) : launch_t<14, 2, 2>(a, stream);
-    case 13: return small ? launch_t<13, 1, 2>(a, stream) : launch_t<13, 2, 2>(a, stream);
-    case 8: return launch_t<8, 1, 2>(a, stream);
-    case 7: return launch_t<7, 1, 2>(a, stream);
-    default:
-      set_error("unsupported ONF feature dimension %d", a.geom.fin);
-      return NFOPP_ERR_ARG;
-  }
-}
-
-// training forward/backward pass (factor matrices for csrc/onf_wgrad.hip); one tile per wave: the factor stores
-// need the registers the second tile would take
-int launch_onf_train_kernel(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  if (onf_split_enabled()) return launch_onf_split_train_kernel(a, stream, grid_out);
-  const int nkt = (a.geom.fin + 15) / 16;
-  switch (nkt) {
-    case 14: return launch_t<14, 1, 1>(a, stream, grid_out);
-    case 13: return launch_t<13, 1, 1>(a, stream, grid_out);
-    case 8: return launch_t<8, 1, 1>(a, stream, grid_out);
-    case 7: return launch_t<7, 1, 1>(a, stream, grid_out);
-    default:
-      set_error("unsupported ONF feature dimension %d", a.geom.fin);
-      return NFOPP_ERR_ARG;
-  }
-}
-
-int onf_train_grid_upper_bound() { return query_cus(); }
-
-// ---- early stop: stable compaction of the live trajectory indices (one workgroup; B is a few thousand per GPU) ------
-// live[0] = count, live[1 + k] = index of the k-th trajectory with active[b] != 0, ascending.
-constexpr int CP_THREADS = 1024;
-__global__ __launch_bounds__(CP_THREADS) void compact_live_kernel(const unsigned char* active, long long batch, int* live) {
-  __shared__ int wave_sum[CP_THREADS / 64];
-  __shared__ int wave_off[CP_THREADS / 64 + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long per = (batch + CP_THREADS - 1) / CP_THREADS;
-  const long long lo = tid * per, hi = lo + per < batch ? lo + per : batch;
-  int mine = 0;
-  for (long long b = lo; b < hi; ++b) mine += active[b] != 0;
-  int scan = mine;   // inclusive scan over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(scan, o);
-    if (lane >= o) scan += up;
-  }
-  if (lane == 63) wave_sum[wave] = scan;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int w = 0; w < CP_THREADS / 64; ++w) { wave_off[w] = run; run += wave_sum[w]; }
-    wave_off[CP_THREADS / 64] = run;
-    live[0] = run;
-  }
-  __syncthreads();
-  int pos = wave_off[wave] + scan - mine;
-  for (long long b = lo; b < hi; ++b)
-    if (active[b] != 0) live[1 + pos++] = (int)b;
 }
 
 }  // namespace nfopp
-
-using namespace nfopp;
-
-extern "C" int nfopp_onf_eval_points(const nfopp_onf_config* cfg, const float* params_dev, const float* points_dev,
-                                     int64_t n_points, float* out4_dev, void* stream) {
-  OnfKernelArgs a = {};
-  NFOPP_REQUIRE(make_geom(cfg, &a.geom), "bad ONF configuration");
-  NFOPP_REQUIRE(n_points >= 0, "negative point count");
-  NFOPP_REQUIRE(n_points == 0 || (params_dev && points_dev && out4_dev), "null device pointer");
-  a.params = params_dev;
-  a.points = points_dev;
-  a.n_points = n_points;
-  a.out4 = out4_dev;
-  return launch_onf_kernel(a, (hipStream_t)stream);
-}
-
-extern "C" int nfopp_onf_eval_logits(const nfopp_onf_config* cfg, const float* params_dev, const float* points_dev,
-                                     int64_t n_points, float* out4_dev, void* stream) {
-  OnfKernelArgs a = {};
-  NFOPP_REQUIRE(make_geom(cfg, &a.geom), "bad ONF configuration");
-  NFOPP_REQUIRE(n_points >= 0, "negative point count");
-  NFOPP_REQUIRE(n_points == 0 || (params_dev && points_dev && out4_dev), "null device pointer");
-  a.params = params_dev;
-  a.points = points_dev;
-  a.n_points = n_points;
-  a.out4 = out4_dev;
-  return launch_onf_logits_kernel(a, (hipStream_t)stream);
-}
-
-extern "C" int nfopp_traj_collision_eval(const nfopp_onf_config* cfg, const float* params_dev, const float* traj_dev,
-                                         int64_t batch, int32_t n_waypoints, int32_t dim, float* t_dev,
-                                         int32_t t_mode, uint64_t seed, uint64_t rng_offset,
-                                         int64_t traj_index_offset, float* out4_dev, const uint8_t* active_dev,
-                                         int32_t* live_ws_dev, void* stream) {
-  OnfKernelArgs a = {};
-  NFOPP_REQUIRE(make_geom(cfg, &a.geom), "bad ONF configuration");
-  NFOPP_REQUIRE(batch >= 0 && n_waypoints >= 2, "need batch >= 0 and at least 2 waypoints");
-  NFOPP_REQUIRE(batch == 0 || (params_dev && traj_dev && t_dev && out4_dev), "null device pointer");
-  NFOPP_REQUIRE(dim == a.geom.point_dim, "trajectory dim %d does not match the ONF point dim %d", dim,
-                a.geom.point_dim);
-  NFOPP_REQUIRE(t_mode == 0 || t_mode == 1, "t_mode must be 0 (read) or 1 (Philox)");
-  NFOPP_REQUIRE(batch <= 0x7fffffffLL, "batch too large for one launch");
-  NFOPP_REQUIRE(!active_dev || live_ws_dev, "an active mask needs the live-list workspace (batch + 1 int32)");
-  if (batch == 0) return NFOPP_OK;
-  if (active_dev) {
-    hipLaunchKernelGGL(compact_live_kernel, dim3(1), dim3(CP_THREADS), 0, (hipStream_t)stream, active_dev,
-                       (long long)batch, live_ws_dev);
-    NFOPP_HIP(hipGetLastError());
-    a.live = live_ws_dev;
-  }
-  a.params = params_dev;
-  a.traj = traj_dev;
-  a.n_way = n_waypoints;
-  a.dim = dim;
-  a.t = t_dev;
-  a.t_mode = t_mode;
-  a.seed = seed;
-  a.rng_offset = rng_offset;
-  a.traj_index_offset = traj_index_offset;
-  a.n_points = batch * (int64_t)(n_waypoints - 1);
-  a.out4 = out4_dev;
-  return launch_onf_kernel(a, (hipStream_t)stream);
-}

@@ -1,5 +1,5 @@
-// Argument block and launch entry points of the fused ONF kernels (csrc/onf_fused.hip), shared with the
-// weight-gradient path (csrc/onf_wgrad.hip).
+// Argument block, matrix-path route and launchers of the fused ONF kernels, shared by the dispatcher
+// (csrc/onf_dispatch.hip) and the weight-gradient path (csrc/onf_wgrad.hip).
 #pragma once
 #include "common.h"
 
@@ -39,24 +39,33 @@ struct OnfKernelArgs {
   float* loss_partial;  // [grid * WAVES]
 };
 
-int query_cus();
-int launch_onf_kernel(const OnfKernelArgs& a, hipStream_t stream);
-// csrc/onf_split.hip: the same kernels with every GEMM issued as bf16x3 split-precision products (mode 0 / 2)
-int launch_onf_split_kernel(const OnfKernelArgs& a, hipStream_t stream, bool forward_only);
-int launch_onf_split_train_kernel(const OnfKernelArgs& a, hipStream_t stream, int* grid_out);
-bool onf_split_enabled();
-// csrc/onf_x32.hip: the bf16x3 split path on 32x32x16 tiles (mode 0 / 2), one 32-sample tile per wave
-bool onf_x32_supports(const OnfGeom& g);
-bool onf_use_x32(const OnfGeom& g);   // matrix path 1 and a feature dimension the 32x32x16 kernel covers
-int launch_onf_x32_kernel(const OnfKernelArgs& a, hipStream_t stream, bool forward_only);
-// training pass of csrc/onf_x32.hip: factors in x32 order (csrc/onf_wgrad.hip: WgradArgs::x32_order), loss partials [grid * 8]
-int launch_onf_x32_train_kernel(const OnfKernelArgs& a, hipStream_t stream, int* grid_out);
-int launch_onf_logits_kernel(const OnfKernelArgs& a, hipStream_t stream);
-int launch_onf_train_kernel(const OnfKernelArgs& a, hipStream_t stream, int* grid_out);
-int onf_train_grid_upper_bound();
+// The kernel family a launch runs on, one per matrix path (csrc/onf_dispatch.hip: onf_route), and the family's count of
+// 16-wide input tiles.
+enum OnfFamily { ONF_FP32, ONF_SPLIT16, ONF_X32 };
+struct OnfRoute { OnfFamily family; int nkt; };
+// Reads the matrix path once; sets "unsupported ONF feature dimension" and fails if the family has no kernel for g.
+int onf_route(const OnfGeom& g, OnfRoute* r);
+
+// Kernel modes: forward + input gradient (planner step), training pass (pass 1 of csrc/onf_wgrad.hip: factors for the
+// weight-gradient GEMMs, *grid_out = workgroups launched), forward only (logits)
+enum OnfMode { ONF_EVAL = 0, ONF_TRAIN = 1, ONF_LOGITS = 2 };
+// one launcher per family; a.n_points > 0
+int launch_fp32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out);     // csrc/onf_fused.hip
+int launch_split16(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out);  // csrc/onf_split.hip
+int launch_x32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out);      // csrc/onf_x32.hip
+int onf_unsupported(const OnfGeom& g);   // the error of a feature dimension without a kernel
+
+inline int launch_onf(const OnfRoute& r, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
+  switch (r.family) {
+    case ONF_FP32: return launch_fp32(r.nkt, mode, a, stream, grid_out);
+    case ONF_SPLIT16: return launch_split16(r.nkt, mode, a, stream, grid_out);
+    default: return launch_x32(r.nkt, mode, a, stream, grid_out);
+  }
+}
 
 // csrc/onf_wgrad.hip: MFMA weight-gradient path of the ONF fitting step
 size_t wgrad_workspace_bytes(const OnfGeom& g, long long n_samples);
+// (pass 1 on the route of csrc/onf_dispatch.hip, pass 2 on the weight-gradient kernel that reads its factor order)
 int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samples, const float* labels,
                         long long n_samples, float inv_count, float* grad, float* ws, hipStream_t st);
 

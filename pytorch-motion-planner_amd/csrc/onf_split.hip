@@ -21,10 +21,6 @@
 //    products per point tile; activations are split by the vector ALU (5.5 instructions per element) which now
 //    overlaps the matrix pipe.
 // k blocks pair the accumulator tiles (2kb, 2kb+1): element j of a lane's fragment is register j&3 of tile 2kb+(j>>2).
-#include <stdlib.h>
-
-#include <mutex>
-
 #include "onf_layout.h"
 
 namespace nfopp {
@@ -994,134 +990,48 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// -1: read NFOPP_MATRIX_PATH on first use; 0: fp32 MFMA; 1: bf16x3 split (default): the 32x32x16 kernel of csrc/onf_x32.hip
-// at EVERY launch size -- results must not depend on how a batch is sharded -- and this file's 16x16x32 kernel for the
-// training pass and the feature dimensions the other does not cover; 2: bf16x3 split, this file's kernel everywhere
-static int g_split_mode = -1;
-
-static int split_mode() {
-  if (g_split_mode < 0) {
-    const char* e = getenv("NFOPP_MATRIX_PATH");
-    g_split_mode = !e ? 1 : (e[0] == 'f' || e[0] == '0') ? 0 : e[0] == '2' ? 2 : 1;
-  }
-  return g_split_mode;
-}
-
-bool onf_split_enabled() { return split_mode() >= 1; }
-
-// the 32x32x16 kernel takes the launch whenever it covers the feature dimension
-bool onf_use_x32(const OnfGeom& g) { return split_mode() == 1 && onf_x32_supports(g); }
-
-// Third-level blobs.  split_prep_kernel rewrites the blob in front of every launch ON THE LAUNCH STREAM, so launches of
-// one stream are ordered by the stream itself; two streams of one device (two planners with different fields) must not
-// share a blob, so blobs are keyed by (device, stream).  A handful of streams per device is the realistic case.
-constexpr int MAX_BLOBS = 16;
-struct BlobSlot { hipStream_t stream; void* ptr; size_t bytes; bool used; unsigned long long stamp; };
-static unsigned long long g_blob_stamp = 0;
-static BlobSlot g_blobs[MAX_DEVICES][MAX_BLOBS] = {};
-static std::mutex g_blob_mutex;
-
-static int blob_for_stream(size_t bytes, hipStream_t stream, u32x4** out) {
-  const int dev = current_device();
-  if (dev < 0) return NFOPP_ERR_HIP;
-  std::lock_guard<std::mutex> lock(g_blob_mutex);
-  BlobSlot* slot = nullptr;
-  for (int k = 0; k < MAX_BLOBS && !slot; ++k)
-    if (g_blobs[dev][k].used && g_blobs[dev][k].stream == stream) slot = &g_blobs[dev][k];
-  for (int k = 0; k < MAX_BLOBS && !slot; ++k)
-    if (!g_blobs[dev][k].used) { slot = &g_blobs[dev][k]; slot->used = true; }
-  if (!slot) {   // every slot taken (PyTorch's pool alone hands out 32 streams per priority): reuse the least recently used one;
-                 // its stream may still be running on the blob, so wait for the device once
-    slot = &g_blobs[dev][0];
-    for (int k = 1; k < MAX_BLOBS; ++k)
-      if (g_blobs[dev][k].stamp < slot->stamp) slot = &g_blobs[dev][k];
-    NFOPP_HIP(hipDeviceSynchronize());
-  }
-  slot->stream = stream;
-  slot->stamp = ++g_blob_stamp;
-  if (slot->bytes < bytes) {
-    if (slot->ptr) NFOPP_HIP(hipFree(slot->ptr));
-    slot->ptr = nullptr; slot->bytes = 0;
-    NFOPP_HIP(hipMalloc(&slot->ptr, bytes));
-    slot->bytes = bytes;
-  }
-  *out = reinterpret_cast<u32x4*>(slot->ptr);
-  return NFOPP_OK;
-}
+// Third-level blob per (device, stream): split_prep_kernel rewrites it on the launch stream in front of every launch (the
+// parameters may have changed since the last call).  A pool of its own: a blob never evicts an x32 image.
+static StreamScratch<> g_blobs;
 
 template <int NKT, int NT, int MODE>
-static int launch_split_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
-  using L = Lds<NKT>;
+static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
   using B = Blob<NKT>;
-  static bool attr_set[MAX_DEVICES] = {};
-  auto kern = onf_split_kernel<NKT, NT, MODE>;
-  int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), L::BYTES, attr_set);
+  void* blob = nullptr;
+  int rc = g_blobs.acquire(B::BYTES, stream, &blob);
   if (rc != NFOPP_OK) return rc;
-  u32x4* blob = nullptr;
-  rc = blob_for_stream(B::BYTES, stream, &blob);
-  if (rc != NFOPP_OK) return rc;
-  // third weight level in consumption order (the parameters may have changed since the last call: always rebuilt)
-  hipLaunchKernelGGL(split_prep_kernel<NKT>, dim3(B::STEPS), dim3(64), 0, stream, a.geom, a.params, blob);
+  hipLaunchKernelGGL(split_prep_kernel<NKT>, dim3(B::STEPS), dim3(64), 0, stream, a.geom, a.params, (u32x4*)blob);
   NFOPP_HIP(hipGetLastError());
   constexpr int CH = WAVES * 16 * NT;
-  long long n_chunks = (a.n_points + CH - 1) / CH;
-  long long grid = query_cus();
-  if (grid > n_chunks) grid = n_chunks;
-  if (grid_out) *grid_out = (int)grid;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), L::BYTES, stream, a, (const u32x4*)blob);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_persistent<onf_split_kernel<NKT, NT, MODE>>(Lds<NKT>::BYTES, THREADS, (a.n_points + CH - 1) / CH, stream,
+                                                            grid_out, a, (const u32x4*)blob);
 }
 
-template <int MODE>
-static int launch_split_mode(const OnfKernelArgs& a, hipStream_t stream) {
-  const int nkt = (a.geom.fin + 15) / 16;
-  const bool small = a.n_points < (long long)query_cus() * WAVES * 16 * 2;
+// Two point tiles per wave once every CU gets a full workgroup of them; smaller jobs fill more CUs with one tile per wave
+// (a 4096-sample fit: 57 vs 85 us), and so do 7-8 input tiles.  The training pass takes two only on the shadow steps for
+// F = 200..224 (14 tiles), where it spills 344 B of registers and is still 9 % faster than one tile per wave.
+template <int NKT, int MODE>
+static int launch_nt(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
+  if constexpr (NKT == 14 || (NKT == 13 && MODE != ONF_TRAIN))
+    if (a.n_points >= (long long)query_cus() * WAVES * 16 * 2) return launch_t<NKT, 2, MODE>(a, stream, grid_out);
+  return launch_t<NKT, 1, MODE>(a, stream, grid_out);
+}
+
+template <int NKT>
+static int launch_mode(int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
+  return mode == ONF_EVAL ? launch_nt<NKT, ONF_EVAL>(a, stream, grid_out)
+         : mode == ONF_TRAIN ? launch_nt<NKT, ONF_TRAIN>(a, stream, grid_out)
+                             : launch_nt<NKT, ONF_LOGITS>(a, stream, grid_out);
+}
+
+int launch_split16(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
   switch (nkt) {
-    case 14: return small ? launch_split_t<14, 1, MODE>(a, stream) : launch_split_t<14, 2, MODE>(a, stream);
-    case 13: return small ? launch_split_t<13, 1, MODE>(a, stream) : launch_split_t<13, 2, MODE>(a, stream);
-    case 8: return launch_split_t<8, 1, MODE>(a, stream);
-    case 7: return launch_split_t<7, 1, MODE>(a, stream);
-    default:
-      set_error("unsupported ONF feature dimension %d", a.geom.fin);
-      return NFOPP_ERR_ARG;
+    case 14: return launch_mode<14>(mode, a, stream, grid_out);
+    case 13: return launch_mode<13>(mode, a, stream, grid_out);
+    case 8: return launch_mode<8>(mode, a, stream, grid_out);
+    case 7: return launch_mode<7>(mode, a, stream, grid_out);
+    default: return onf_unsupported(a.geom);
   }
-}
-
-// training pass on the split path: two point tiles per wave on the shadow steps for F = 200..224 (spills 344 B of registers and
-// is still 9 % faster than one tile per wave), one tile per wave otherwise
-int launch_onf_split_train_kernel(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  const int nkt = (a.geom.fin + 15) / 16;
-  switch (nkt) {
-    // two tiles per wave once every CU gets a full workgroup of them (as the evaluation kernel decides); smaller fits fill more
-    // CUs with one tile per wave (4096 samples: 57 vs 85 us)
-    case 14:
-      return a.n_points < (long long)query_cus() * WAVES * 16 * 2 ? launch_split_t<14, 1, 1>(a, stream, grid_out)
-                                                                   : launch_split_t<14, 2, 1>(a, stream, grid_out);
-    case 13: return launch_split_t<13, 1, 1>(a, stream, grid_out);
-    case 8: return launch_split_t<8, 1, 1>(a, stream, grid_out);
-    case 7: return launch_split_t<7, 1, 1>(a, stream, grid_out);
-    default:
-      set_error("unsupported ONF feature dimension %d", a.geom.fin);
-      return NFOPP_ERR_ARG;
-  }
-}
-
-int launch_onf_split_kernel(const OnfKernelArgs& a, hipStream_t stream, bool forward_only) {
-  if (a.n_points <= 0) return NFOPP_OK;
-  if (onf_use_x32(a.geom)) return launch_onf_x32_kernel(a, stream, forward_only);
-  return forward_only ? launch_split_mode<2>(a, stream) : launch_split_mode<0>(a, stream);
 }
 
 }  // namespace nfopp
-
-using namespace nfopp;
-
-extern "C" int nfopp_set_matrix_path(int32_t path) {
-  NFOPP_REQUIRE(path >= 0 && path <= 2,
-                "matrix path must be 0 (fp32 MFMA), 1 (bf16x3 split MFMA) or 2 (bf16x3 split MFMA, 16x16x32 kernels only)");
-  g_split_mode = path;
-  return NFOPP_OK;
-}
-
-extern "C" int nfopp_get_matrix_path(void) { return split_mode(); }

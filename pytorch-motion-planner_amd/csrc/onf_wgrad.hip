@@ -1125,7 +1125,7 @@ static WgradWs carve_wgrad(const OnfGeom& g, long long P, int nkt) {
   const long long hrow = HS;
   w.win = 16 * nkt;
   w.ntiles = 8 * nkt + 49;
-  w.grid_cap = onf_train_grid_upper_bound();
+  w.grid_cap = query_cus();   // workgroups of a persistent launch (launch_persistent)
   long long o = 0;
   w.h1 = o; o += P * hrow;     // the kernel addresses these four back to back (f4_source): keep the order
   w.dh1 = o; o += P * hrow;
@@ -1145,41 +1145,37 @@ static WgradWs carve_wgrad(const OnfGeom& g, long long P, int nkt) {
 // so the answer does not depend on the matrix path in force when the fit runs
 size_t wgrad_workspace_bytes(const OnfGeom& g, long long P) { return (size_t)carve_wgrad(g, P, (g.fin + 16) / 16).total * sizeof(float); }
 
+// pass 2 reads the factors in the order pass 1 wrote them: onf_wgrad_kernel behind the fp32 pass, onf_wgrad_split_kernel
+// behind a split pass (slot order after 16x16x32 tiles, x32 order after 32x32x16 tiles)
 template <int NKT>
-static int launch_wgrad(const WgradArgs& a, int grid, hipStream_t st) {
-  using W = WgLayout<NKT>;
-  static bool attr_set[MAX_DEVICES] = {};
-  auto kern = onf_wgrad_kernel<NKT>;
-  const int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), W::LDS_BYTES, attr_set);
-  if (rc_attr != NFOPP_OK) return rc_attr;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WG_THREADS), W::LDS_BYTES, st, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+static int launch_wgrad_t(OnfFamily pass1, const WgradArgs& a, hipStream_t st, int* grid) {
+  if (pass1 == ONF_FP32)
+    return launch_persistent<onf_wgrad_kernel<NKT>>(WgLayout<NKT>::LDS_BYTES, WG_THREADS, (a.P + KC - 1) / KC, st, grid, a);
+  constexpr size_t LDS = WsLayout<NKT>::LDS_BYTES;
+  const long long n_chunks = (a.P + KS - 1) / KS;
+  return pass1 == ONF_X32 ? launch_persistent<onf_wgrad_split_kernel<NKT, true>>(LDS, WG_THREADS, n_chunks, st, grid, a)
+                          : launch_persistent<onf_wgrad_split_kernel<NKT, false>>(LDS, WG_THREADS, n_chunks, st, grid, a);
 }
 
-template <int NKT, bool XO>
-static int launch_wgrad_split_o(const WgradArgs& a, int grid, hipStream_t st) {
-  using L = WsLayout<NKT>;
-  static bool attr_set[MAX_DEVICES] = {};
-  auto kern = onf_wgrad_split_kernel<NKT, XO>;
-  const int rc_attr = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), L::LDS_BYTES, attr_set);
-  if (rc_attr != NFOPP_OK) return rc_attr;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WG_THREADS), L::LDS_BYTES, st, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
-}
-
-template <int NKT>
-static int launch_wgrad_split(const WgradArgs& a, int grid, hipStream_t st) {
-  return a.x32_order ? launch_wgrad_split_o<NKT, true>(a, grid, st) : launch_wgrad_split_o<NKT, false>(a, grid, st);
+static int launch_wgrad(const OnfRoute& r, const WgradArgs& a, hipStream_t st, int* grid) {
+  switch (r.nkt) {
+    case 14: return launch_wgrad_t<14>(r.family, a, st, grid);
+    case 13: return launch_wgrad_t<13>(r.family, a, st, grid);
+    case 8: return launch_wgrad_t<8>(r.family, a, st, grid);
+    case 7: return launch_wgrad_t<7>(r.family, a, st, grid);
+    default: return onf_unsupported(a.geom);
+  }
 }
 
 // gradient of the mean BCE loss over `count` samples (inv_count = 1 / count) into grad[n_params + 2]
 int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samples, const float* labels, long long P,
                         float inv_count, float* grad, float* ws, hipStream_t st) {
-  // pass 1 on the 32x32x16 kernel (matrix path 1, the feature dimensions it covers): factors in x32 order
-  const bool xo = onf_use_x32(g);
-  const int nkt = xo ? (g.fin + 16) / 16 : (g.fin + 15) / 16;
+  OnfRoute r;
+  int rc = onf_route(g, &r);
+  if (rc) return rc;
+  // pass 1 on the 32x32x16 kernel: factors in x32 order
+  const bool xo = r.family == ONF_X32;
+  const int nkt = r.nkt;
   const WgradWs w = carve_wgrad(g, P, nkt);
   const int aug = xo ? g.fin : find_aug_feature(g.fin, nkt);
   NFOPP_REQUIRE(aug >= 0, "no pad feature available for the ones column (fin = %d)", g.fin);
@@ -1189,23 +1185,14 @@ int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samp
   a.ws_h1 = ws + w.h1; a.ws_dh1 = ws + w.dh1; a.ws_de = ws + w.de; a.ws_u = ws + w.rec;
   a.loss_partial = ws + w.loss; a.g4_partial = ws + w.g4_partial;
   int grid_fwd = 0;
-  int rc = xo ? launch_onf_x32_train_kernel(a, st, &grid_fwd) : launch_onf_train_kernel(a, st, &grid_fwd);
+  rc = launch_onf(r, ONF_TRAIN, a, st, &grid_fwd);
   if (rc) return rc;
 
   WgradArgs wa;
   wa.geom = g; wa.params = params; wa.aug_feature = aug; wa.x32_order = xo ? 1 : 0;
   wa.ws = ws + w.h1; wa.P = P; wa.partial = ws + w.partial;   // arrays back to back from w.h1 (see carve_wgrad)
-  const bool split = onf_split_enabled();   // pass 2 follows pass 1's matrix path
-  const int kc = split ? KS : KC;
-  long long n_chunks = (P + kc - 1) / kc;
-  int grid = (int)(n_chunks < w.grid_cap ? n_chunks : w.grid_cap);
-  switch (nkt) {
-    case 14: rc = split ? launch_wgrad_split<14>(wa, grid, st) : launch_wgrad<14>(wa, grid, st); break;
-    case 13: rc = split ? launch_wgrad_split<13>(wa, grid, st) : launch_wgrad<13>(wa, grid, st); break;
-    case 8: rc = split ? launch_wgrad_split<8>(wa, grid, st) : launch_wgrad<8>(wa, grid, st); break;
-    case 7: rc = split ? launch_wgrad_split<7>(wa, grid, st) : launch_wgrad<7>(wa, grid, st); break;
-    default: set_error("unsupported ONF feature dimension %d", g.fin); return NFOPP_ERR_ARG;
-  }
+  int grid = 0;
+  rc = launch_wgrad(r, wa, st, &grid);
   if (rc) return rc;
   const int n_elems = w.ntiles * 256;
   hipLaunchKernelGGL(onf_wgrad_reduce_kernel, dim3((n_elems + 63) / 64), dim3(64 * RED_GROUPS), 0, st, ws + w.partial,

@@ -1,5 +1,5 @@
 // (implementation header: the kernels and their launch templates; csrc/onf_x32.hip holds the per-stream images and the
-// entry points, csrc/onf_x32_k{14,13,8,7}.hip instantiate one feature dimension each so that the build runs in parallel)
+// family's launcher, csrc/onf_x32_k{14,13,8,7}.hip instantiate one feature dimension each so that the build runs in parallel)
 // K1 on 32x32x16 tiles: fused collision sampling + ONF forward + input gradient for gfx950, every GEMM on the bf16 matrix
 // pipe as an exact three-level split of the fp32 operands (the arithmetic of csrc/onf_split.hip: x = hi + mid + lo, six
 // partial products per multiply, fp32 accumulation).  Reference: nfop/onf_model.py:33-50 + autograd, nfop/angle_encoder.py:
@@ -31,10 +31,8 @@
 // feature / hidden-unit index ("x32 order": the accumulator layout gives every lane four consecutive positions per
 // register quad, i.e. one 16-byte store) plus the 48-byte record (u, 1, theta | rho | sign words of a2).  dW3[:100] =
 // sum_p rho_p relu(a2_p) is NOT accumulated here: it falls out of G2 in the gather kernel (WgradArgs::x32_order).
-#include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
 #include <type_traits>
 
 #pragma once
@@ -322,7 +320,7 @@ __device__ __forceinline__ void eval_any_item(EvalAnyState& s, const f32x4& tw, 
   if constexpr (U == 11) s.v = is_one ? 1.0f : s.v;
 }
 
-// NT = 32-sample tiles per wave.  Shapes launched by x32::launch_t: <512 threads, NT 1> two waves per SIMD; <256, 1> for small
+// NT = 32-sample tiles per wave.  Shapes launched by x32::launch_t (host side below): <512 threads, NT 1> two waves per SIMD; <256, 1> for small
 // launches.  NT = 2 (one wave per SIMD with two tiles sharing every weight fragment: half the LDS / L2 fragment traffic per
 // sample, two independent accumulation and hook chains in one stream) ran at exactly the time of <512, 1> and
 // is not launched.  A tile's arithmetic is the same in all of them.
@@ -944,32 +942,24 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// Image + blob per (device, stream), kept by csrc/onf_x32.hip: the prep kernel rewrites them on the launch stream in front of
-// every launch (the parameters may have changed), so launches of one stream are ordered by the stream itself.
-struct Slot {
-  hipStream_t stream; void* ptr; size_t bytes; bool used; unsigned long long stamp;
-  // what the image in `ptr` was built from: parameter buffer, its registered content version (0 = unknown), geometry
-  const float* params; unsigned long long version; OnfGeom geom; int nkb;
-};
-int buffers_for_stream(size_t bytes, hipStream_t stream, void** out, Slot** slot_out);
-void slot_built(Slot* slot, const float* params, unsigned long long version, const OnfGeom& geom, int nkb);
-// one feature dimension each (csrc/onf_x32_k*.hip): mode 0 logits + input gradient, 1 training pass, 2 logits only
+// Image + blob per (device, stream) (defined in csrc/onf_x32.hip), tagged with what the image was built from: parameter
+// buffer, its registered content version (0 = unknown), geometry.
+struct ImageTag { const float* params; unsigned long long version; OnfGeom geom; };
+extern StreamScratch<ImageTag> g_images;
+// one feature dimension each (csrc/onf_x32_k*.hip)
 int launch_nkb14(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
 int launch_nkb13(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
 int launch_nkb8(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
 int launch_nkb7(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
 
-template <int NKB, int MODE, int XT, int NT>
-static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
+template <int NKB, int MODE, int XT>
+static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
   using C = Cfg<NKB>;
-  constexpr int CH = (XT / 64) * 32 * NT;
-  static bool attr_set[MAX_DEVICES] = {};
-  auto kern = onf_x32_kernel<NKB, MODE, XT, NT>;
-  int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), IMG_BYTES, attr_set);
-  if (rc != NFOPP_OK) return rc;
+  constexpr int CH = (XT / 64) * 32;
   void* buf = nullptr;
-  Slot* slot = nullptr;
-  rc = buffers_for_stream(IMG_BYTES + C::BLOB_BYTES, stream, &buf, &slot);
+  ImageTag tag;
+  int slot = 0;
+  int rc = g_images.acquire(IMG_BYTES + C::BLOB_BYTES, stream, &buf, &tag, &slot);
   if (rc != NFOPP_OK) return rc;
   u32x4* img = reinterpret_cast<u32x4*>(buf);
   u32x4* blob = reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(buf) + IMG_BYTES);
@@ -977,34 +967,30 @@ static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_ou
   // for the buffer's content with a version (nfopp_onf_params_version) and this stream's image was built from that very
   // (buffer, version, geometry): a frozen field then costs no prep launch.
   const unsigned long long ver = onf_params_version_of(a.params);
-  const bool fresh = ver != 0 && slot->version == ver && slot->params == a.params && slot->nkb == NKB &&
-                     memcmp(&slot->geom, &a.geom, sizeof(OnfGeom)) == 0;
+  const bool fresh = ver != 0 && tag.version == ver && tag.params == a.params && memcmp(&tag.geom, &a.geom, sizeof(OnfGeom)) == 0;
   if (!fresh) {
     constexpr int N_PIECES = IMG_BYTES / 16 + (C::STEPS + 4) * 64;
     hipLaunchKernelGGL(x32_prep_kernel<NKB>, dim3((N_PIECES + 255) / 256), dim3(256), 0, stream, a.geom, a.params, img, blob);
     NFOPP_HIP(hipGetLastError());
-    slot_built(slot, a.params, ver, a.geom, NKB);
+    g_images.set_tag(slot, stream, ImageTag{a.params, ver, a.geom});
   }
-  const long long n_chunks = (a.n_points + CH - 1) / CH;
-  long long grid = query_cus();
-  if (grid > n_chunks) grid = n_chunks;
-  if (grid_out) *grid_out = (int)grid;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(XT), IMG_BYTES, stream, a, (const u32x4*)img, (const u32x4*)blob);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_persistent<onf_x32_kernel<NKB, MODE, XT, 1>>(IMG_BYTES, XT, (a.n_points + CH - 1) / CH, stream, grid_out, a,
+                                                             (const u32x4*)img, (const u32x4*)blob);
 }
 
+// 256 threads for small launches, 512 (two waves per SIMD) otherwise
 template <int NKB, int MODE>
-static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
-  return a.n_points < (long long)query_cus() * 256 ? launch_shape<NKB, MODE, 256, 1>(a, stream, grid_out)
-                                                   : launch_shape<NKB, MODE, 512, 1>(a, stream, grid_out);
+static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
+  return a.n_points < (long long)query_cus() * 256 ? launch_shape<NKB, MODE, 256>(a, stream, grid_out)
+                                                   : launch_shape<NKB, MODE, 512>(a, stream, grid_out);
 }
 
 // the three modes of one feature dimension (used by csrc/onf_x32_k*.hip)
 template <int NKB>
 static int launch_modes(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out) {
-  return mode == 0 ? launch_t<NKB, 0>(a, stream, grid_out) : mode == 1 ? launch_t<NKB, 1>(a, stream, grid_out)
-                                                                        : launch_t<NKB, 2>(a, stream, grid_out);
+  return mode == ONF_EVAL ? launch_t<NKB, ONF_EVAL>(a, stream, grid_out)
+         : mode == ONF_TRAIN ? launch_t<NKB, ONF_TRAIN>(a, stream, grid_out)
+                             : launch_t<NKB, ONF_LOGITS>(a, stream, grid_out);
 }
 
 }  // namespace x32

@@ -1,4 +1,4 @@
-// Library-level plumbing: error strings, device query, the flat Adam update.
+// Library-level plumbing: error strings, device query and per-device launch state, the flat Adam update.
 #include <stdarg.h>
 #include <string.h>
 
@@ -29,6 +29,18 @@ int current_device() {
   if (e != hipSuccess) { hip_fail(e, "hipGetDevice"); return -1; }
   if (dev < 0 || dev >= MAX_DEVICES) { set_error("device index %d out of range", dev); return -1; }
   return dev;
+}
+
+static int g_num_cus[MAX_DEVICES] = {};
+
+int query_cus() {
+  const int dev = current_device();
+  if (dev < 0) return 256;
+  if (g_num_cus[dev] > 0) return g_num_cus[dev];
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
+  g_num_cus[dev] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  return g_num_cus[dev];
 }
 
 int ensure_dynamic_lds(const void* kernel, size_t bytes, bool* flags) {

@@ -87,6 +87,20 @@ def test_param_count_and_argument_errors_without_gpu():
     assert rc == -1 and b"occupancy grid" in lib.nfopp_last_error()
 
 
+@pytest.mark.parametrize("value, path", [(None, 1), ("fp32", 0), ("0", 0), ("1", 1), ("split", 1), ("2", 2)])
+def test_matrix_path_environment_parse(value, path):
+    """NFOPP_MATRIX_PATH as a fresh process sees it (read once, on first use; the getter touches no device)."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "NFOPP_MATRIX_PATH"}
+    if value is not None:
+        env["NFOPP_MATRIX_PATH"] = value
+    child = "import ctypes, sys; print(ctypes.CDLL(sys.argv[1]).nfopp_get_matrix_path())"
+    res = subprocess.run([sys.executable, "-c", child, _lib.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
+    assert res.returncode == 0, res.stderr
+    assert int(res.stdout) == path
+
+
 def test_device_guard_rejects_buffers_of_another_gpu():
     """every launch uses the CURRENT device's stream / CU count / scratch, so `_lib.ptr` refuses a buffer that
     lives on another card (the check itself is plain Python and needs no GPU)."""
