@@ -292,6 +292,47 @@ int nfopp_path_postprocess(const float* path_dev, int64_t batch, int32_t n_point
 int nfopp_adam_step(float* param_dev, const float* grad_dev, float* m_dev, float* v_dev, int64_t n, float beta2,
                     float omb1, float omb2, float eps, float step_size, float bc2_sqrt, void* stream);
 
+/* ---- grid-search (A*) trajectory seeding for whole batches (csrc/grid_search.hip) ----------------------------------
+ * Replaces AstarTrajectoryInitializer (nfop/astar/astar_trajectory_initializer.py:15-48) with the search of
+ * nfop/astar/jps.py (jps=False: 8-connected, cost 1 / sqrt 2, no corner rule, :99-125) and reparametrize_path
+ * (nfop/utils/math.py:57-65), additive under ABI 6.  Costs are integer pairs (a, b) = (straight, diagonal) moves.
+ *
+ * nfopp_grid_distance_fields (the search, jps.py:56-66 + the expansion loop): occupancy_dev uint8 [rows, cols]
+ *   (non-zero = wall), goal_cells_dev int32 [G, 2] (row, col), callers pass each goal cell once.  fields_dev int32
+ *   [G, rows, cols, 2] <- exact minimum cost (a, b) from every cell to goal g; the goal cell is forced free
+ *   (astar_trajectory_initializer.py:40); walls, cells that cannot reach the goal and every cell of a goal outside the
+ *   grid hold the sentinel (-1, -1).  The result is the unique fixed point of the relaxation: bit-identical from run to
+ *   run.  Grids whose padded field fits 144 KiB of LDS with 16 + 16-bit counts (at most 65535 cells) are relaxed in
+ *   LDS; larger ones, up to 2^21 cells, in `workspace` (nfopp_grid_fields_workspace_bytes, 0 for the LDS form) with
+ *   32 + 32-bit counts, so no count can wrap.
+ * nfopp_grid_trace_paths (find_path's parent walk, jps.py:56-66): problem p starts in start_cells_dev[p], ends in
+ *   goal_cells_dev[p] and reads field field_index_dev[p].  From the start cell it steps to the first neighbour, in
+ *   the order N, W, S, E, NW, NE, SW, SE of (row, col), whose cost plus the move equals the current cost exactly.
+ *   cells_dev int32 [B, max_len, 2] (row, col; first and last cell included), count_dev [B] = cells the path has
+ *   (max_len = 0 sizes the buffer), status_dev [B]: 0 ok, 1 goal unreachable from the start, 2 start or goal cell
+ *   outside the grid; cost_dev [B, 2] (may be null) = (a, b) of the path, (-1, -1) without one.  The start cell is not
+ *   tested for occupancy, as in the reference.
+ * nfopp_grid_seed_trajectories (initialize_trajectory :15-25 + reparametrize_path + initialize_angle): the polyline
+ *   [start xy, cell centres (col * resolution + resolution / 2 + origin_x, row ... origin_y; fp32), goal xy] is
+ *   re-sampled to n_waypoints + 2 points by the quadratic spline over the normalised chord length and the interior
+ *   points are stored as fp32 in traj_dev [B, N, D]; headings as nfopp_init_trajectories writes them, the
+ *   travel-direction pull along the seeded path.  A problem with status != 0 gets exactly nfopp_init_trajectories'
+ *   trajectory.  Paths longer than 64 KiB of LDS allow need `workspace` (nfopp_grid_seed_workspace_bytes, else 0). */
+size_t nfopp_grid_fields_workspace_bytes(int32_t rows, int32_t cols, int64_t n_goals);
+int nfopp_grid_distance_fields(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, const int32_t* goal_cells_dev,
+                               int64_t n_goals, int32_t* fields_dev, void* workspace_dev, size_t workspace_bytes,
+                               void* stream);
+int nfopp_grid_trace_paths(const int32_t* fields_dev, int64_t n_fields, int32_t rows, int32_t cols,
+                           const int32_t* start_cells_dev, const int32_t* goal_cells_dev, const int32_t* field_index_dev,
+                           int64_t batch, int32_t max_len, int32_t* cells_dev, int32_t* count_dev, int32_t* status_dev,
+                           int32_t* cost_dev, void* stream);
+size_t nfopp_grid_seed_workspace_bytes(int64_t batch, int32_t max_len);
+int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int32_t* count_dev, const int32_t* status_dev,
+                                 int64_t batch, int32_t max_len, const float* start_dev, const float* goal_dev,
+                                 int32_t n_waypoints, int32_t dim, int32_t angles_with_direction, double origin_x,
+                                 double origin_y, double resolution, float* traj_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

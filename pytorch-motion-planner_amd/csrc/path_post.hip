@@ -13,6 +13,7 @@
 // tests/golden/g12).  The sequential parts (filter, sums, elimination: O(n)) run on lane 0; evaluation of the
 // `count` output poses is spread over the workgroup.
 #include "common.h"
+#include "spline2.h"
 
 // numpy evaluates every fp32 / float64 operation separately: no fused multiply-adds anywhere in this file
 // (hipcc's `__fmul_rn` / `__fadd_rn` are plain operators and would still be contracted)
@@ -61,36 +62,6 @@ __device__ __forceinline__ float remainder_two_pi(float x) {
   float r = fmodf(x, NFOPP_TWO_PI_F);
   if (r != 0.f && r < 0.f) r = (r + NFOPP_TWO_PI_F);
   return r;
-}
-
-// the three quadratic B-spline basis values B_{ell-2..ell}(x) on knots t, t[ell] <= x < t[ell+1] (de Boor-Cox)
-__device__ __forceinline__ void basis2(const double* t, int ell, double x, double h[3]) {
-  h[0] = 1.0; h[1] = 0.0; h[2] = 0.0;
-#pragma unroll
-  for (int j = 1; j <= 2; ++j) {
-    double hh[2] = {h[0], h[1]};
-    h[0] = 0.0;
-#pragma unroll
-    for (int n = 1; n <= j; ++n) {
-      const double xb = t[ell + n], xa = t[ell + n - j];
-      if (xb == xa) { h[n] = 0.0; continue; }
-      const double w = hh[n - 1] / (xb - xa);
-      h[n - 1] += w * (xb - x);
-      h[n] = w * (x - xa);
-    }
-  }
-}
-
-__device__ __forceinline__ void spline_at(const double* t, const double* c, int m, double x, double p[3]) {
-  int lo = 2, hi = m - 1;   // largest ell in [2, m-1] with t[ell] <= x
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (t[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  double h[3];
-  basis2(t, lo, x, h);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) p[d] = h[0] * c[(lo - 2) * 3 + d] + h[1] * c[(lo - 1) * 3 + d] + h[2] * c[lo * 3 + d];
 }
 
 __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a) {
@@ -191,7 +162,7 @@ __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a)
         for (int q = 0; q < lim; ++q) {
           const double x = q == count - 1 ? 1.0 : (double)q * step;
           double p[3];
-          spline_at(T, C, m, x, p);
+          spline_at<3>(T, C, m, x, p);
           if (q > 0) {
             double dth = fmod(p[2] - prevp[2] + NFOPP_PI_D, 2.0 * NFOPP_PI_D);
             if (dth != 0.0 && dth < 0.0) dth += 2.0 * NFOPP_PI_D;
@@ -229,7 +200,7 @@ __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a)
   for (int q = first + threadIdx.x; q < count && q - first < a.max_out; q += PP_THREADS) {
     const double x = (q == count - 1 && count > 1) ? 1.0 : (double)q * step;
     double p[3];
-    spline_at(T, C, m, x, p);
+    spline_at<3>(T, C, m, x, p);
     out[(q - first) * 3 + 0] = p[0];
     out[(q - first) * 3 + 1] = p[1];
     out[(q - first) * 3 + 2] = p[2];

@@ -248,6 +248,57 @@ void reparametrize(Tensor traj, const Tensor& start, const Tensor& goal, const O
                                    opt_ptr<uint8_t>(active), stream_of(traj)));
 }
 
+// grid-search (A*) seeding of a batch (astar_trajectory_initializer.py:15-48): traj [B, N, D] in place, returns status [B].
+// occupancy uint8 [rows, cols]; start_cells / goal_cells int32 [B, 2] (row, col); unique_goal_cells int32 [G, 2] and
+// field_index int32 [B] = the de-duplicated goal cells and each problem's entry in them (nfopp/grid_search.py builds them).
+Tensor grid_search_init(Tensor traj, const Tensor& start, const Tensor& goal, const Tensor& occupancy, const Tensor& start_cells,
+                        const Tensor& goal_cells, const Tensor& unique_goal_cells, const Tensor& field_index, double origin_x,
+                        double origin_y, double resolution, bool angles_with_direction) {
+  check_tensor(traj, "traj");
+  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
+  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
+  check_tensor(start, "start"); check_tensor(goal, "goal");
+  check_tensor(occupancy, "occupancy", at::kByte);
+  check_tensor(start_cells, "start_cells", at::kInt); check_tensor(goal_cells, "goal_cells", at::kInt);
+  check_tensor(unique_goal_cells, "unique_goal_cells", at::kInt); check_tensor(field_index, "field_index", at::kInt);
+  same_device(traj, start, "start"); same_device(traj, goal, "goal"); same_device(traj, occupancy, "occupancy");
+  same_device(traj, start_cells, "start_cells"); same_device(traj, goal_cells, "goal_cells");
+  same_device(traj, unique_goal_cells, "unique_goal_cells"); same_device(traj, field_index, "field_index");
+  TORCH_CHECK(D == 2 || D == 3, "nfopp: trajectory dim must be 2 or 3");
+  TORCH_CHECK(start.numel() == B * D && goal.numel() == B * D, "nfopp: start / goal must be [B, D]");
+  TORCH_CHECK(occupancy.dim() == 2, "nfopp: occupancy must be [rows, cols] uint8");
+  TORCH_CHECK(start_cells.numel() == 2 * B && goal_cells.numel() == 2 * B && field_index.numel() == B,
+              "nfopp: start_cells / goal_cells must be [B, 2], field_index [B]");
+  TORCH_CHECK(unique_goal_cells.dim() == 2 && unique_goal_cells.size(1) == 2, "nfopp: unique_goal_cells must be [G, 2]");
+  const int64_t rows = occupancy.size(0), cols = occupancy.size(1), G = unique_goal_cells.size(0);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  const auto i32 = traj.options().dtype(at::kInt);
+  Tensor fields = at::empty({G, rows, cols, 2}, i32);
+  const size_t fws = nfopp_grid_fields_workspace_bytes((int32_t)rows, (int32_t)cols, G);
+  Tensor fwork = at::empty({(int64_t)((fws + 7) / 8)}, traj.options().dtype(at::kLong));
+  check_status(nfopp_grid_distance_fields(occupancy.data_ptr<uint8_t>(), (int32_t)rows, (int32_t)cols,
+                                          unique_goal_cells.data_ptr<int32_t>(), G, fields.data_ptr<int32_t>(),
+                                          fws ? fwork.data_ptr() : nullptr, fws, stream_of(traj)));
+  Tensor count = at::empty({B}, i32), status = at::empty({B}, i32);
+  auto trace = [&](int32_t max_len, int32_t* cells) {
+    check_status(nfopp_grid_trace_paths(G ? fields.data_ptr<int32_t>() : nullptr, G, (int32_t)rows, (int32_t)cols,
+                                        start_cells.data_ptr<int32_t>(), goal_cells.data_ptr<int32_t>(),
+                                        field_index.data_ptr<int32_t>(), B, max_len, cells, count.data_ptr<int32_t>(),
+                                        status.data_ptr<int32_t>(), nullptr, stream_of(traj)));
+  };
+  trace(0, nullptr);
+  const int64_t max_len = B ? std::max<int64_t>(count.max().item<int64_t>(), 1) : 1;
+  Tensor cells = at::zeros({B, max_len, 2}, i32);
+  trace((int32_t)max_len, cells.data_ptr<int32_t>());
+  const size_t sws = nfopp_grid_seed_workspace_bytes(B, (int32_t)max_len);
+  Tensor swork = at::empty({(int64_t)((sws + 7) / 8)}, traj.options().dtype(at::kDouble));
+  check_status(nfopp_grid_seed_trajectories(cells.data_ptr<int32_t>(), count.data_ptr<int32_t>(), status.data_ptr<int32_t>(), B,
+                                            (int32_t)max_len, start.data_ptr<float>(), goal.data_ptr<float>(), (int32_t)N,
+                                            (int32_t)D, angles_with_direction ? 1 : 0, origin_x, origin_y, resolution,
+                                            traj.data_ptr<float>(), sws ? swork.data_ptr() : nullptr, sws, stream_of(traj)));
+  return status;
+}
+
 // gradient of the BCE-with-logits fitting loss w.r.t. every ONF parameter (nerf:83-89): [n_params | loss | count]
 Tensor onf_train_grad(const Tensor& params, const Tensor& samples, const Tensor& labels, double inv_count, double mean,
                       double sigma, bool use_cos, bool has_bias, int64_t angle_dim) {
@@ -316,6 +367,9 @@ TORCH_LIBRARY(nfopp, lib) {
   lib.def("onf_train_step(Tensor(a!) params, Tensor(b!) m, Tensor(c!) v, Tensor samples, Tensor labels, float mean, float sigma, "
           "bool use_cos, bool has_bias, int angle_dim, float beta2, float omb1, float omb2, float eps, float step_size, "
           "float bc2_sqrt) -> Tensor");
+  lib.def("grid_search_init(Tensor(a!) traj, Tensor start, Tensor goal, Tensor occupancy, Tensor start_cells, Tensor goal_cells, "
+          "Tensor unique_goal_cells, Tensor field_index, float origin_x, float origin_y, float resolution, "
+          "bool angles_with_direction) -> Tensor");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -329,4 +383,5 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("onf_train_grad", &onf_train_grad);
   lib.impl("adam_step", &adam_step);
   lib.impl("onf_train_step", &onf_train_step);
+  lib.impl("grid_search_init", &grid_search_init);
 }

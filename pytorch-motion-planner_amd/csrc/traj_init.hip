@@ -7,16 +7,11 @@
 // end - (steps-1-i)*step for the second, each as one fused multiply-add with an fp32 step; the same expression is used
 // here so the waypoints are bit-identical to the reference's (headings of the directed variant: atan2 rounding only).
 #include "common.h"
+#include "traj_init.h"
 
 namespace nfopp {
 
 constexpr int TI_THREADS = 256;
-
-__device__ __forceinline__ float linspace_at(float s, float e, int steps, int i) {
-  if (steps <= 1) return s;
-  const float step = (e - s) / (float)(steps - 1);   // IEEE division (hipcc default)
-  return i < steps / 2 ? fmaf(step, (float)i, s) : fmaf(-step, (float)(steps - 1 - i), e);
-}
 
 struct InitArgs {
   const float* start; const float* goal;   // [B, D]
@@ -27,32 +22,11 @@ struct InitArgs {
 template <int D>
 __global__ __launch_bounds__(TI_THREADS) void traj_init_kernel(const InitArgs a) {
   const long long b = blockIdx.x;
-  const int N = a.n, steps = N + 2;
+  const int N = a.n;
   float s[D], g[D];
 #pragma unroll
   for (int d = 0; d < D; ++d) { s[d] = a.start[b * D + d]; g[d] = a.goal[b * D + d]; }
-  float goal_angle = 0.f;
-  if (D == 3) goal_angle = wrap_angle(g[2] - s[2]) + s[2];
-  float* out = a.traj + b * (long long)N * D;
-  for (int i = threadIdx.x; i < N; i += TI_THREADS) {
-    out[i * D + 0] = linspace_at(s[0], g[0], steps, i + 1);
-    out[i * D + 1] = linspace_at(s[1], g[1], steps, i + 1);
-    if (D == 3) {
-      float th = linspace_at(s[2], goal_angle, steps, i + 1);
-      if (a.directed) {
-        // central difference over the FULL path (start, waypoints, goal): neighbours i and i+2 of the full index
-        const float x0 = i == 0 ? s[0] : linspace_at(s[0], g[0], steps, i);
-        const float y0 = i == 0 ? s[1] : linspace_at(s[1], g[1], steps, i);
-        const float x1 = i == N - 1 ? g[0] : linspace_at(s[0], g[0], steps, i + 2);
-        const float y1 = i == N - 1 ? g[1] : linspace_at(s[1], g[1], steps, i + 2);
-        const float heading = atan2f(y1 - y0, x1 - x0);
-        const int h = N / 2;
-        const float w = i < h ? linspace_at(0.f, 1.f, h, i) : linspace_at(1.f, 0.f, (N + 1) / 2, i - h);
-        th = add_mul_unfused(th, wrap_angle(heading - th), w);
-      }
-      out[i * D + 2] = th;
-    }
-  }
+  straight_line_fill<D>(s, g, N, a.directed, a.traj + b * (long long)N * D, threadIdx.x, TI_THREADS);
 }
 
 }  // namespace nfopp

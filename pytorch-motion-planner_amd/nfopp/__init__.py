@@ -6,7 +6,9 @@ from ._lib import LIB_PATH, NfoppError, load as load_library
 from .batch import BatchPlanner, OnfFitter, shard_range, straight_line_init
 from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
-from .host_utils import (AstarTrajectoryInitializer, AttributeDict, CircleCollisionChecker,
+from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fields, grid_search_init, grid_search_paths,
+                          seed_trajectories)
+from .host_utils import (AttributeDict, CircleCollisionChecker,
                          CircleDirectedCollisionChecker, CollisionChecker, Position2, RectangleCollisionChecker,
                          TrajectoryInitializer)
 from .learning import BatchSampler, DeviceCircleChecker, DeviceGridChecker, DeviceRectangleChecker
@@ -19,5 +21,6 @@ __all__ = [
     "DEFAULT_PARAMETERS", "PlannerFactory", "UniversalFactory", "AstarTrajectoryInitializer", "AttributeDict",
     "CircleCollisionChecker", "CircleDirectedCollisionChecker", "CollisionChecker", "Position2",
     "RectangleCollisionChecker", "TrajectoryInitializer", "ONF", "ConstrainedNERFOptPlanner", "ContinuousPlanner",
-    "NERFOptPlanner", "PathPostprocessor", "init_trajectories",
+    "NERFOptPlanner", "PathPostprocessor", "init_trajectories", "OccupancyGrid", "grid_search_init", "grid_search_paths",
+    "distance_fields", "seed_trajectories",
 ]

@@ -104,6 +104,15 @@ _SIGNATURES = {
                                            _P, _P, _P]),
     "nfopp_adam_step": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, ctypes.c_float, ctypes.c_float, _P]),
+    "nfopp_grid_fields_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
+    "nfopp_grid_distance_fields": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, _P, _P,
+                                                  ctypes.c_size_t, _P]),
+    "nfopp_grid_trace_paths": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64,
+                                              ctypes.c_int32, _P, _P, _P, _P, _P]),
+    "nfopp_grid_seed_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32]),
+    "nfopp_grid_seed_trajectories": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

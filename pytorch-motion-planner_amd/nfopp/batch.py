@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .engine import TrajectoryEngine, TrajectoryHyper
+from .grid_search import AstarTrajectoryInitializer, OccupancyGrid, grid_search_init
 from .path_tools import init_trajectories
 
 
@@ -162,14 +163,29 @@ class BatchPlanner(object):
                                         seed=seed + 1, traj_index_offset=traj_index_offset)
             self.fitter = OnfFitter(onf, fit_lr, fit_betas, group=group)
 
-    def init(self, starts, goals, boundaries, trajectories=None):
+    seed_status = None   # per-problem status of the last grid-search seeding (nfopp/grid_search.py), else None
+
+    def init(self, starts, goals, boundaries, trajectories=None, initializer=None):
         eng = self.engine
         eng.set_endpoints(starts, goals)
         h = eng.hyper
         eng.hyper = TrajectoryHyper(h.collision_weight, h.angle_weight, h.constraint_deltas_weight, h.multipliers_lr,
                                     h.collision_multipliers_lr, h.boundary_weight, h.collision_beta,
                                     h.direction_delta_weight, h.lr, h.betas, h.eps, boundaries)
-        if trajectories is None:
+        self.seed_status = None
+        if initializer is not None:
+            # grid-search seeding of the whole batch (csrc/grid_search.hip): an OccupancyGrid or an AstarTrajectoryInitializer
+            if trajectories is not None:
+                raise ValueError("pass trajectories or an initializer, not both")
+            if isinstance(initializer, OccupancyGrid):
+                _, self.seed_status = grid_search_init(initializer, eng.start, eng.goal, eng.N,
+                                                       self.init_angles_with_trajectory and eng.D == 3, out=eng.traj)
+            elif isinstance(initializer, AstarTrajectoryInitializer):
+                initializer.initialize_batch(eng.start, eng.goal, eng.N, out=eng.traj, boundaries=boundaries)
+                self.seed_status = initializer.status
+            else:
+                raise TypeError("initializer must be an OccupancyGrid or an AstarTrajectoryInitializer")
+        elif trajectories is None:
             # device initialiser (trajectory_initializer.py:12-45); eng.start / eng.goal were uploaded just above
             init_trajectories(eng.start, eng.goal, eng.N, self.init_angles_with_trajectory and eng.D == 3, out=eng.traj)
         else:

@@ -12,7 +12,8 @@ import inspect
 
 import torch
 
-from .host_utils import AstarTrajectoryInitializer, AttributeDict, TrajectoryInitializer
+from .grid_search import AstarTrajectoryInitializer
+from .host_utils import AttributeDict, TrajectoryInitializer
 from .onf_model import ONF
 from .planner import ConstrainedNERFOptPlanner, NERFOptPlanner
 

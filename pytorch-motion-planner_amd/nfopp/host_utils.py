@@ -145,10 +145,3 @@ class TrajectoryInitializer(object):
                 w = torch.cat([torch.linspace(0., 1, m // 2), torch.linspace(1., 0, (m + 1) // 2)], dim=0)
                 trajectory[:, 2] = trajectory[:, 2] + wrap_angle_t(angles - trajectory[:, 2]) * w
 
-
-class AstarTrajectoryInitializer(object):
-    """A*/JPS seeding (nfop/astar/) is one-time host work outside the accelerated path."""
-
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("AstarTrajectoryInitializer is outside the hot path rebuilt here; "
-                                  "use TrajectoryInitializer or pass your own initializer object")

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from .engine import TrajectoryEngine, TrajectoryHyper
+from .grid_search import AstarTrajectoryInitializer
 from .host_utils import Position2, TrajectoryInitializer
 from .path_tools import init_trajectories
 
@@ -364,9 +365,13 @@ class ConstrainedNERFOptPlanner(NERFOptPlanner):
         ini = self._trajectory_initializer
         if type(ini) is TrajectoryInitializer:
             # the stock initialiser runs as one device kernel (csrc/traj_init.hip); any other object the caller passes
-            # (e.g. an A* seeder) keeps the reference's host protocol below
+            # keeps the reference's host protocol below
             init_trajectories(self._engine.start, self._engine.goal, self._engine.N, ini._init_angles_with_trajectory,
                               out=self._engine.traj)
+            return
+        if type(ini) is AstarTrajectoryInitializer:
+            # the grid-search seeder runs on the device too (csrc/grid_search.hip), here with a batch of one
+            ini.initialize_batch(self._engine.start, self._engine.goal, self._engine.N, out=self._engine.traj)
             return
         tr = torch.zeros(self._trajectory.shape[0], 3)
         ini.initialize_trajectory(tr, self._engine.start.cpu(), self._engine.goal.cpu())
