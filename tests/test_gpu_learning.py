@@ -56,12 +56,29 @@ def test_batch_sampler_vs_oracle_and_shard_invariance(D, tag):
     # same candidates chosen (as sets: ordering inside the pool is irrelevant), same ages
     for b in range(B):
         assert max_abs(np.sort(got_pool[b].sum(1)), np.sort(pool[b].sum(1))) < 1e-5
+    # ... and the same candidates by INDEX, in the oracle's order: the pool holds the device's own candidate rows bit for bit
+    cand_dev = sm.cand.cpu().numpy()
+    assert np.array_equal(got_pool.view(np.uint32), np.take_along_axis(cand_dev, chosen[..., None], 1).view(np.uint32))
     assert (sm.pool_age.cpu().numpy() == 1).all()
     assert max_abs(s1[:, N - 1:N - 1 + cap], got_pool) == 0
     # second draw: pool carried, ages grow
-    s2 = sm.draw(prev_d, bounds)
+    pool1, page1 = got_pool.copy(), sm.pool_age.cpu().numpy()
+    s2 = sm.draw(prev_d, bounds).cpu().numpy().reshape(B, -1, D)
     ages = sm.pool_age.cpu().numpy()
     assert set(np.unique(ages)) <= {1.0, 2.0} and (ages == 2).any()
+    # ... compared with the oracle as well: pool full, ages 1, offset 1, candidates [pool | new]
+    cand2, age2, smp2 = orc.sample_candidates(prev, pool1, page1, cap, nf, 1.5, 0.02, 0.3, bounds, 21, 1)
+    cand2_dev, age2_dev = sm.cand.cpu().numpy(), sm.cand_age.cpu().numpy()
+    assert np.array_equal(cand2_dev[:, :cap].view(np.uint32), pool1.view(np.uint32)) and np.array_equal(age2_dev, age2)
+    assert max_abs(s2[:, :N - 1], smp2[:, :N - 1]) < 2e-5 and max_abs(s2[:, N - 1 + cap:], smp2[:, N - 1 + cap:]) < 1e-6
+    assert max_abs(cand2_dev, cand2) < 2e-6
+    assert max_abs(s2[:, :N - 1], s1[:, :N - 1]) > 0.1                 # a new draw, not the first one again
+    logits2 = sm.cand_out.cpu().numpy()[..., 0]
+    _, page2, chosen2 = orc.resample_pool(cand2_dev, age2_dev, logits2, cap, 21, 1)
+    got_pool2 = sm.pool.cpu().numpy()
+    assert np.array_equal(got_pool2.view(np.uint32), np.take_along_axis(cand2_dev, chosen2[..., None], 1).view(np.uint32))
+    assert np.array_equal(ages, page2) and (chosen2 < cap).any() and (chosen2 >= cap).any()
+    assert max_abs(s2[:, N - 1:N - 1 + cap], got_pool2) == 0
     # shard invariance: trajectories 3..4 as their own shard give the same poses
     sm2 = nfopp.BatchSampler(onf, 2, N, 1.5, 0.02, 0.3, nf, cap, seed=21, traj_index_offset=3)
     t1 = sm2.draw(prev_d[3:].contiguous(), bounds).cpu().numpy().reshape(2, -1, D)

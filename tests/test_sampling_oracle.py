@@ -6,6 +6,21 @@ import numpy as np
 from oracle import nfopp_oracle as orc
 
 
+def test_philox_known_answers():
+    """Random123's published Philox4x32-10 vectors (kat_vectors: counter c0..c3, key k0 k1), output word 0; the oracle
+    returns (word0 >> 8) * 2^-24.  The device meets the same three in tests/test_gpu_sampling_reference.py."""
+    vectors = [((0, 0, 0, 0), (0, 0), 0x6627e8d5),
+               ((0xffffffff,) * 4, (0xffffffff, 0xffffffff), 0x408f276d),
+               ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0), 0xd16cfe09)]
+    for (c0, c1, c2, c3), (k0, k1), word in vectors:
+        got = orc.philox_uniform(k0 | (k1 << 32), np.array([c0 | (c1 << 32)], np.uint64), c2 | (c3 << 32))
+        assert got.dtype == np.float32 and float(got[0]) == (word >> 8) * 2.0 ** -24, hex(word)
+    # the sampler's counter layout on top of it: c0 = draw index, c1 = stream, (c2, c3) = (trajectory << 24) ^ offset
+    assert float(orc.draw_uniform(0, 0, np.array([0]), 0, 0)[0]) == 0x6627e8 * 2.0 ** -24
+    lo, hi = 7 | (orc.STREAM_KEY << 32), (5 << 24) ^ 9
+    assert orc.draw_uniform(3, 5, np.array([7]), 9, orc.STREAM_KEY)[0] == orc.philox_uniform(3, np.array([lo], np.uint64), hi)[0]
+
+
 def test_draws_have_the_right_moments_and_are_counter_addressed():
     u = orc.draw_uniform(11, 5, np.arange(200000), 3, orc.STREAM_T)
     assert 0 <= u.min() and u.max() < 1 and abs(u.mean() - 0.5) < 3e-3
