@@ -16,7 +16,11 @@
 //    weight read of all four GEMMs bank-conflict-free from the SAME two LDS images;
 //  * input features sin/cos(W_e u + b_e), sin/cos((theta+b)f) are computed just-in-time as the L1 B operand and
 //    re-derived (shifted by a quadrant) in the L1T epilogue, so neither `in` nor `din` is ever stored.
-#include "onf_layout.h"
+//  * the stages around the GEMMs that csrc/onf_split.hip runs too are in csrc/onf_stages.h: feature evaluation (l1_features),
+//    the h1 / dh1 / de factor stores, the chain rule, the logits and out4 stores.  Written out here AND a second time in
+//    onf_split.hip (keep them in step; onf_stages.h has the spill counts that keep them apart): the point load with record
+//    words 0..3, the L1 bias init and lane bases, the logit / BCE loss / record words 4..11 block, the per-wave partials.
+#include "onf_stages.h"
 
 namespace nfopp {
 
@@ -46,7 +50,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
   const long long n_work = work_points(a);
   const long long n_chunks = (n_work + CH - 1) / CH;
   const float b3 = a.params[geo.off_b3];
-  constexpr int WIN = 16 * NKT;   // row length of the input-side factor matrices (TRAIN)
   constexpr int WH = 16 * HT;     // row length of the hidden-side factor matrices
   float loss_acc = 0.f;
   f32x4 g4_acc[HT];   // TRAIN: running sum_p rho_p * relu(a2_p) of this lane's (hidden row, point column) cells
@@ -90,44 +93,12 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
 
     auto l1_tile = [&](auto ang_c, int kt) __attribute__((always_inline)) {
       constexpr bool ANG = decltype(ang_c)::value;
-      constexpr bool ang_tile = ANG;
       const int off = base_p(kt);
-      const float* fte = ftl + L::ft_rel(off);
       const float* pa = w1a + off;
       const float* pb = w1b + off;
       const float* pc = w1c + off;
       float fv[4][NT];
-      if (NT == 2) {  // pair = the two point tiles of this wave
-        const f32x2 ux2 = {ux[0], ux[NT - 1]}, uy2 = {uy[0], uy[NT - 1]}, th2 = {th[0], th[NT - 1]};
-        f32x2 sk = {skip[0], skip[NT - 1]};
-        f32x4 isa4 = {0.f, 0.f, 0.f, 0.f};
-        if (ang_tile) isa4 = *reinterpret_cast<const f32x4*>(isl + off);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const f32x4 e0 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r);      // wx wx wy wy
-          const f32x4 e1 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 4);  // b b fr fr
-          const f32x4 e2 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 8);  // qh qh w3b w3b
-          const f32x2 wx = {e0.x, e0.y}, wy = {e0.z, e0.w}, bb = {e1.x, e1.y}, fr = {e1.z, e1.w};
-          const f32x2 qh = {e2.x, e2.y}, w3 = {e2.z, e2.w};
-          const f32x2 v = features2<ANG, false>(wx, wy, bb, fr, qh, splat2(isa4[r]), ux2, uy2, th2);
-          sk = fma2(w3, v, sk);
-          fv[r][0] = v.x; fv[r][NT - 1] = v.y;
-        }
-        skip[0] = sk.x; skip[NT - 1] = sk.y;
-      } else {        // pair = two consecutive k-steps of the single tile
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const float* ea = fte + L::FTS * r;
-          const float* eb = ea + L::FTS;
-          const f32x2 ux2 = splat2(ux[0]), uy2 = splat2(uy[0]), th2 = splat2(th[0]);
-          const f32x2 wx = {ea[0], eb[0]}, wy = {ea[2], eb[2]}, bb = {ea[4], eb[4]}, fr = {ea[6], eb[6]};
-          const f32x2 qh = {ea[8], eb[8]}, isa = {isl[off + r], isl[off + r + 1]};
-          const f32x2 v = features2<ANG, false>(wx, wy, bb, fr, qh, isa, ux2, uy2, th2);
-          skip[0] = fmaf(ea[10], v.x, skip[0]);
-          skip[0] = fmaf(eb[10], v.y, skip[0]);
-          fv[r][0] = v.x; fv[r + 1][0] = v.y;
-        }
-      }
+      l1_features<NKT, NT, ANG>(ftl + L::ft_rel(off), isl + off, ux, uy, th, skip, fv);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -143,17 +114,15 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
 #pragma unroll 1
     for (int kt = first_angle_kt; kt < NKT; ++kt) l1_tile(std::true_type{}, kt);
 
-    if (TRAIN) {  // h1 (layout Q slots), ones at slot (tile 6, g = 0, r = 1)
+    if (TRAIN) {  // h1 = relu(a1) with the ones column
 #pragma unroll
-      for (int tl = 0; tl < NT; ++tl)
-        if (pidx[tl] < a.n_points) {
+      for (int tl = 0; tl < NT; ++tl) {
+        f32x4 h1[HT];
 #pragma unroll
-          for (int t = 0; t < HT; ++t) {
-            f32x4 v = {relu1(acc1[tl][t][0]), relu1(acc1[tl][t][1]), relu1(acc1[tl][t][2]), relu1(acc1[tl][t][3])};
-            if (t == 6) v = f32x4{v[0], g == 0 ? 1.0f : 0.0f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(a.ws_h1 + pidx[tl] * WH + 16 * t + 4 * g) = v;
-          }
-        }
+        for (int t = 0; t < HT; ++t)
+          h1[t] = f32x4{relu1(acc1[tl][t][0]), relu1(acc1[tl][t][1]), relu1(acc1[tl][t][2]), relu1(acc1[tl][t][3])};
+        if (pidx[tl] < a.n_points) store_factor_row(a.ws_h1 + pidx[tl] * WH, g, h1, 1.0f);
+      }
     }
 
     // ---------------------------------------------------------------- L2: a2 = W2 relu(a1) + b2
@@ -249,10 +218,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
     }
 
     if (FWD_ONLY) {
-#pragma unroll
-      for (int tl = 0; tl < NT; ++tl)
-        if (g == 0 && pidx[tl] < a.n_points)
-          *reinterpret_cast<f32x4*>(a.out4 + pidx[tl] * 4) = f32x4{logit[tl], 0.f, 0.f, 0.f};
+      store_logits(a, g, pidx, logit);
       continue;
     }
 
@@ -294,14 +260,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
       if (TRAIN) {
 #pragma unroll
         for (int tl = 0; tl < NT; ++tl)
-          if (pidx[tl] < a.n_points) {
-#pragma unroll
-            for (int t = 0; t < HT; ++t) {
-              f32x4 v = acc1[tl][t];
-              if (t == 6) v = f32x4{v[0], g == 0 ? rho[tl] : 0.0f, 0.f, 0.f};
-              *reinterpret_cast<f32x4*>(a.ws_dh1 + pidx[tl] * WH + 16 * t + 4 * g) = v;
-            }
-          }
+          if (pidx[tl] < a.n_points) store_factor_row(a.ws_dh1 + pidx[tl] * WH, g, acc1[tl], rho[tl]);
       }
     }
 
@@ -344,66 +303,14 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_fwd_bwd_kernel(con
         __builtin_amdgcn_sched_barrier(0);
       }
       // chain through the encodings: d feature / d arg = sin(arg + (qh + 0.5) pi); rows (g, r) <-> slots (4 mt + r, g)
-      constexpr bool ang_tile = ANG;
-      const float* fte = lds + L::ft(fbase);
-      if (NT == 2) {
-        const f32x2 ux2 = {ux[0], ux[NT - 1]}, uy2 = {uy[0], uy[NT - 1]}, th2 = {th[0], th[NT - 1]};
-        f32x2 gx2 = {gx[0], gx[NT - 1]}, gy2 = {gy[0], gy[NT - 1]}, gt2 = {gt[0], gt[NT - 1]};
-        f32x4 isa4 = {0.f, 0.f, 0.f, 0.f};
-        if (ang_tile) isa4 = *reinterpret_cast<const f32x4*>(lds + L::ISA + fbase);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const f32x4 e0 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r);
-          const f32x4 e1 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 4);
-          const f32x2 qh = *reinterpret_cast<const f32x2*>(fte + L::FTS * r + 8);
-          const f32x2 wx = {e0.x, e0.y}, wy = {e0.z, e0.w}, bb = {e1.x, e1.y}, fr = {e1.z, e1.w};
-          const f32x2 cof = features2<ANG, true>(wx, wy, bb, fr, qh, splat2(isa4[r]), ux2, uy2, th2);
-          const f32x2 de = f32x2{acc[0][r], acc[NT - 1][r]} * cof;
-          if (TRAIN) { acc[0][r] = de.x; acc[NT - 1][r] = de.y; }
-          gx2 = fma2(de, wx, gx2);
-          gy2 = fma2(de, wy, gy2);
-          if (ANG) gt2 = fma2(de, fr, gt2);   // spatial features have no theta dependence (fr = 0)
-        }
-        gx[0] = gx2.x; gx[NT - 1] = gx2.y; gy[0] = gy2.x; gy[NT - 1] = gy2.y; gt[0] = gt2.x; gt[NT - 1] = gt2.y;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const float* ea = fte + L::FTS * r;
-          const float* eb = ea + L::FTS;
-          const f32x2 wx = {ea[0], eb[0]}, wy = {ea[2], eb[2]}, bb = {ea[4], eb[4]}, fr = {ea[6], eb[6]};
-          const f32x2 qh = {ea[8], eb[8]}, isa = {lds[L::ISA + fbase + r], lds[L::ISA + fbase + r + 1]};
-          const f32x2 ux2 = splat2(ux[0]), uy2 = splat2(uy[0]), th2 = splat2(th[0]);
-          const f32x2 cof = features2<ANG, true>(wx, wy, bb, fr, qh, isa, ux2, uy2, th2);
-          const f32x2 de = f32x2{acc[0][r], acc[0][r + 1]} * cof;
-          if (TRAIN) { acc[0][r] = de.x; acc[0][r + 1] = de.y; }
-          if (!TRAIN) {   // the fit needs de only, not d logit / d pose
-            gx[0] = fmaf(de.x, wx.x, gx[0]); gx[0] = fmaf(de.y, wx.y, gx[0]);
-            gy[0] = fmaf(de.x, wy.x, gy[0]); gy[0] = fmaf(de.y, wy.y, gy[0]);
-            if (ANG) { gt[0] = fmaf(de.x, fr.x, gt[0]); gt[0] = fmaf(de.y, fr.y, gt[0]); }
-          }
-        }
-      }
-      if (TRAIN) {
-#pragma unroll
-        for (int tl = 0; tl < NT; ++tl)
-          if (pidx[tl] < a.n_points)
-            *reinterpret_cast<f32x4*>(a.ws_de + pidx[tl] * WIN + 16 * mt + 4 * g) = acc[tl];
-      }
+      chain_rule_tile<NKT, NT, TRAIN, ANG>(lds + L::ft(fbase), lds + L::ISA + fbase, ux, uy, th, acc, gx, gy, gt);
+      if (TRAIN) store_de_tile<NKT>(a, pidx, mt, g, acc);
     };
 #pragma unroll 1
     for (int mt = 0; mt < first_angle_kt; ++mt) l1t_tile(std::false_type{}, mt);
 #pragma unroll 1
     for (int mt = first_angle_kt; mt < NKT; ++mt) l1t_tile(std::true_type{}, mt);
-#pragma unroll
-    for (int tl = 0; tl < NT; ++tl) {
-      gx[tl] += __shfl_xor(gx[tl], 16); gx[tl] += __shfl_xor(gx[tl], 32);
-      gy[tl] += __shfl_xor(gy[tl], 16); gy[tl] += __shfl_xor(gy[tl], 32);
-      gt[tl] += __shfl_xor(gt[tl], 16); gt[tl] += __shfl_xor(gt[tl], 32);
-      if (a.out4 && g == 0 && pidx[tl] < a.n_points) {
-        f32x4 o = {logit[tl], gx[tl] / geo.sigma, gy[tl] / geo.sigma, gt[tl]};
-        *reinterpret_cast<f32x4*>(a.out4 + pidx[tl] * 4) = o;
-      }
-    }
+    store_out4(a, g, pidx, logit, gx, gy, gt);
   }
   if (TRAIN) {  // fixed-order loss partial: lanes of a wave (xor tree), then waves / workgroups in the final kernel
 #pragma unroll
@@ -441,21 +348,10 @@ static int launch_nt(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) 
   return launch_t<NKT, 1, MODE>(a, stream, grid_out);
 }
 
-template <int NKT>
-static int launch_mode(int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  return mode == ONF_EVAL ? launch_nt<NKT, ONF_EVAL>(a, stream, grid_out)
-         : mode == ONF_TRAIN ? launch_nt<NKT, ONF_TRAIN>(a, stream, grid_out)
-                             : launch_nt<NKT, ONF_LOGITS>(a, stream, grid_out);
-}
-
 int launch_fp32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  switch (nkt) {
-    case 14: return launch_mode<14>(mode, a, stream, grid_out);
-    case 13: return launch_mode<13>(mode, a, stream, grid_out);
-    case 8: return launch_mode<8>(mode, a, stream, grid_out);
-    case 7: return launch_mode<7>(mode, a, stream, grid_out);
-    default: return onf_unsupported(a.geom);
-  }
+  return dispatch_nkt(nkt, a.geom, [&](auto k) {
+    return dispatch_mode(mode, [&](auto m) { return launch_nt<decltype(k)::value, decltype(m)::value>(a, stream, grid_out); });
+  });
 }
 
 }  // namespace nfopp

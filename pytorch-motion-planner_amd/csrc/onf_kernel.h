@@ -1,6 +1,8 @@
 // Argument block, matrix-path route and launchers of the fused ONF kernels, shared by the dispatcher
 // (csrc/onf_dispatch.hip) and the weight-gradient path (csrc/onf_wgrad.hip).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace nfopp {
@@ -54,6 +56,25 @@ int launch_fp32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, i
 int launch_split16(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out);  // csrc/onf_split.hip
 int launch_x32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out);      // csrc/onf_x32.hip
 int onf_unsupported(const OnfGeom& g);   // the error of a feature dimension without a kernel
+
+// The ladders of every family's launcher: f(std::integral_constant) for the tile counts that have kernels / the three modes,
+// so that a generic lambda can name its launcher template with decltype(k)::value.
+template <class F>
+int dispatch_nkt(int nkt, const OnfGeom& g, F&& f) {
+  switch (nkt) {
+    case 14: return f(std::integral_constant<int, 14>{});
+    case 13: return f(std::integral_constant<int, 13>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return onf_unsupported(g);
+  }
+}
+template <class F>
+int dispatch_mode(int mode, F&& f) {
+  return mode == ONF_EVAL ? f(std::integral_constant<int, ONF_EVAL>{})
+         : mode == ONF_TRAIN ? f(std::integral_constant<int, ONF_TRAIN>{})
+                             : f(std::integral_constant<int, ONF_LOGITS>{});
+}
 
 inline int launch_onf(const OnfRoute& r, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out = nullptr) {
   switch (r.family) {

@@ -10,8 +10,11 @@
 // (measured: 10x closer to float64 than a sequential fp32 dot product, tools/micro + tests/test_gpu_split_path.py),
 // at 6/16 of the fp32 MFMA time.
 //
-// What changes against onf_fused.hip (same points-on-N / features-on-M orientation, same LDS images and layouts P/Q,
-// same accumulator-as-next-operand chaining, same feature evaluation and epilogues):
+// What changes against onf_fused.hip: the four GEMM loops.  Same points-on-N / features-on-M orientation, same LDS images
+// and layouts P/Q, same accumulator-as-next-operand chaining.  Feature evaluation, the h1 / dh1 / de factor stores, the chain
+// rule and the logits / out4 stores are the SAME code, csrc/onf_stages.h.  Four stages are a second copy of onf_fused.hip's
+// and must change with it (onf_stages.h has the spill counts that keep them apart): the point load with record words 0..3,
+// the L1 bias init and lane bases, the logit / BCE loss / record words 4..11 block, the per-wave partials.  In the GEMMs:
 //  * an LDS weight word holds (bf16 hi | bf16 mid) of the weight instead of its fp32 value: the images keep their
 //    size, their [row][col] addressing and therefore every conflict-free read pattern of the fp32 kernel;
 //  * the third level does not fit in LDS (6 bytes per weight): a small prep kernel writes it to a per-device blob in
@@ -21,7 +24,7 @@
 //    products per point tile; activations are split by the vector ALU (5.5 instructions per element) which now
 //    overlaps the matrix pipe.
 // k blocks pair the accumulator tiles (2kb, 2kb+1): element j of a lane's fragment is register j&3 of tile 2kb+(j>>2).
-#include "onf_layout.h"
+#include "onf_stages.h"
 
 namespace nfopp {
 
@@ -168,8 +171,8 @@ __global__ __launch_bounds__(64) void split_prep_kernel(const OnfGeom geo, const
   blob[step * 64 + lane] = out;
 }
 
-// MODE 0: forward + input gradient (planner step)   1: training pass (factors for the weight-gradient GEMMs, as
-// onf_fused.hip's TRAIN mode: same stores, same record)   2: forward only (logits)
+// MODE 0: forward + input gradient (planner step)   1: training pass (factor matrices, 48-byte record and per-wave partials
+// for the weight-gradient GEMMs, csrc/onf_wgrad.hip)   2: forward only (logits)
 template <int NKT, int NT, int MODE>
 __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const OnfKernelArgs a, const u32x4* __restrict__ blob) {
   constexpr bool FWD_ONLY = MODE == 2;
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
   const long long n_work = work_points(a);
   const long long n_chunks = (n_work + CH - 1) / CH;
   const float b3 = a.params[geo.off_b3];
-  constexpr int WIN = 16 * NKT, WH = 16 * HT;   // row lengths of the stored factors (TRAIN)
+  constexpr int WH = 16 * HT;   // row length of the stored hidden-side factors (TRAIN)
   float loss_acc = 0.f;
   f32x4 g4_acc[HT];   // TRAIN: running sum_p rho_p * relu(a2_p) of this lane's (hidden row, point column) cells
 #pragma unroll
@@ -287,51 +290,27 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
     fetch1(0, 0, wa1);
     pack_words(wa1, ah1, am1);
     fetch1(0, 1, wa1);
-    auto l1_block = [&](auto ang_c, int kb) __attribute__((always_inline)) {
+    // the lane's 8 features of k block kb for every point tile, in three levels: element j = feature 32 kb + 8 (j >> 2) +
+    // colP + (j & 3) (32 kb = base_p(2 kb); the second tile of the pair sits 8 columns further)
+    auto block_features = [&](auto ang_c, int kb, u32x4 (&bh)[NT], u32x4 (&bm)[NT], u32x4 (&bl)[NT]) __attribute__((always_inline)) {
       constexpr bool ANG = decltype(ang_c)::value;
-      const int off = 32 * kb;   // base_p(2 kb); the second tile of the pair sits 8 columns further
-      // the lane's 8 features of this k block for every point tile: element j = feature off + 8 (j >> 2) + colP + (j & 3)
-      u32x4 bh[NT], bm[NT], bl[NT];
-      {
-        float fv[NT][8];
+      float fv[NT][8];
 #pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const float* fte = ftl + L::ft_rel(off + 8 * half);
-          if (NT == 2) {
-            const f32x2 ux2 = {ux[0], ux[NT - 1]}, uy2 = {uy[0], uy[NT - 1]}, th2 = {th[0], th[NT - 1]};
-            f32x2 sk = {skip[0], skip[NT - 1]};
-            f32x4 isa4 = {0.f, 0.f, 0.f, 0.f};
-            if (ANG) isa4 = *reinterpret_cast<const f32x4*>(isl + off + 8 * half);
+      for (int half = 0; half < 2; ++half) {
+        const int off = 32 * kb + 8 * half;
+        float f4[4][NT];
+        l1_features<NKT, NT, ANG>(ftl + L::ft_rel(off), isl + off, ux, uy, th, skip, f4);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const f32x4 e0 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r);
-              const f32x4 e1 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 4);
-              const f32x4 e2 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 8);
-              const f32x2 wx = {e0.x, e0.y}, wy = {e0.z, e0.w}, bb = {e1.x, e1.y}, fr = {e1.z, e1.w};
-              const f32x2 qh = {e2.x, e2.y}, w3 = {e2.z, e2.w};
-              const f32x2 v = features2<ANG, false>(wx, wy, bb, fr, qh, splat2(isa4[r]), ux2, uy2, th2);
-              sk = fma2(w3, v, sk);
-              fv[0][4 * half + r] = v.x; fv[NT - 1][4 * half + r] = v.y;
-            }
-            skip[0] = sk.x; skip[NT - 1] = sk.y;
-          } else {
+        for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int r = 0; r < 4; r += 2) {
-              const float* ea = fte + L::FTS * r;
-              const float* eb = ea + L::FTS;
-              const f32x2 ux2 = splat2(ux[0]), uy2 = splat2(uy[0]), th2 = splat2(th[0]);
-              const f32x2 wx = {ea[0], eb[0]}, wy = {ea[2], eb[2]}, bb = {ea[4], eb[4]}, fr = {ea[6], eb[6]};
-              const f32x2 qh = {ea[8], eb[8]}, isa = {isl[off + 8 * half + r], isl[off + 8 * half + r + 1]};
-              const f32x2 v = features2<ANG, false>(wx, wy, bb, fr, qh, isa, ux2, uy2, th2);
-              skip[0] = fmaf(ea[10], v.x, skip[0]);
-              skip[0] = fmaf(eb[10], v.y, skip[0]);
-              fv[0][4 * half + r] = v.x; fv[0][4 * half + r + 1] = v.y;
-            }
-          }
-        }
-#pragma unroll
-        for (int tl = 0; tl < NT; ++tl) split8(fv[tl], bh[tl], bm[tl], bl[tl]);
+          for (int tl = 0; tl < NT; ++tl) fv[tl][4 * half + r] = f4[r][tl];
       }
+#pragma unroll
+      for (int tl = 0; tl < NT; ++tl) split8(fv[tl], bh[tl], bm[tl], bl[tl]);
+    };
+    auto l1_block = [&](auto ang_c, int kb) __attribute__((always_inline)) {
+      u32x4 bh[NT], bm[NT], bl[NT];
+      block_features(ang_c, kb, bh, bm, bl);
       const int lo_step = B::L1 + kb * HT;
 #pragma unroll
       for (int mt = 0; mt < HT; ++mt) {
@@ -426,34 +405,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      auto upfront = [&](auto ang_c, int kb) __attribute__((always_inline)) {   // l1_block's evaluation, no steps
-        constexpr bool ANG = decltype(ang_c)::value;
-        const int off = 32 * kb;
-        float fv[NT][8];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const float* fte = ftl + L::ft_rel(off + 8 * half);
-          const f32x2 ux2 = {ux[0], ux[NT - 1]}, uy2 = {uy[0], uy[NT - 1]}, th2 = {th[0], th[NT - 1]};
-          f32x2 sk = {skip[0], skip[NT - 1]};
-          f32x4 isa4 = {0.f, 0.f, 0.f, 0.f};
-          if (ANG) isa4 = *reinterpret_cast<const f32x4*>(isl + off + 8 * half);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const f32x4 e0 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r);
-            const f32x4 e1 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 4);
-            const f32x4 e2 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 8);
-            const f32x2 wx = {e0.x, e0.y}, wy = {e0.z, e0.w}, bb = {e1.x, e1.y}, fr = {e1.z, e1.w};
-            const f32x2 qh = {e2.x, e2.y}, w3 = {e2.z, e2.w};
-            const f32x2 v = features2<ANG, false>(wx, wy, bb, fr, qh, splat2(isa4[r]), ux2, uy2, th2);
-            sk = fma2(w3, v, sk);
-            fv[0][4 * half + r] = v.x; fv[NT - 1][4 * half + r] = v.y;
-          }
-          skip[0] = sk.x; skip[NT - 1] = sk.y;
-        }
-#pragma unroll
-        for (int tl = 0; tl < NT; ++tl) split8(fv[tl], bhc[tl], bmc[tl], blc[tl]);
-      };
-      upfront(std::false_type{}, 0);
+      block_features(std::false_type{}, 0, bhc, bmc, blc);
 #pragma unroll 1
       for (int kb = 0; kb < 5; ++kb) {
         l1_steps(std::true_type{}, kb);
@@ -461,7 +413,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
         for (int tl = 0; tl < NT; ++tl) { bhc[tl] = bhn[tl]; bmc[tl] = bmn[tl]; blc[tl] = bln[tl]; }
       }
       l1_steps(std::false_type{}, 5);
-      upfront(std::true_type{}, 6);
+      block_features(std::true_type{}, 6, bhc, bmc, blc);
       l1_steps(std::false_type{}, 6);
     } else {
 #pragma unroll 1
@@ -470,17 +422,15 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       for (int kb = first_angle_kb; kb < B::NKB; ++kb) l1_block(std::true_type{}, kb);
     }
 
-    if (TRAIN) {  // h1 (layout Q slots), ones at slot (tile 6, g = 0, r = 1)
+    if (TRAIN) {  // h1 = relu(a1) with the ones column
 #pragma unroll
-      for (int tl = 0; tl < NT; ++tl)
-        if (pidx[tl] < a.n_points) {
+      for (int tl = 0; tl < NT; ++tl) {
+        f32x4 h1[HT];
 #pragma unroll
-          for (int t = 0; t < HT; ++t) {
-            f32x4 v = {relu1(acc1[tl][t][0]), relu1(acc1[tl][t][1]), relu1(acc1[tl][t][2]), relu1(acc1[tl][t][3])};
-            if (t == 6) v = f32x4{v[0], g == 0 ? 1.0f : 0.0f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(a.ws_h1 + pidx[tl] * WH + 16 * t + 4 * g) = v;
-          }
-        }
+        for (int t = 0; t < HT; ++t)
+          h1[t] = f32x4{relu1(acc1[tl][t][0]), relu1(acc1[tl][t][1]), relu1(acc1[tl][t][2]), relu1(acc1[tl][t][3])};
+        if (pidx[tl] < a.n_points) store_factor_row(a.ws_h1 + pidx[tl] * WH, g, h1, 1.0f);
+      }
     }
     // ---------------------------------------------------------------- L2: a2 = W2 relu(a1) + b2
     NFOPP_REDERIVE();
@@ -578,7 +528,10 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       logit[tl] += __shfl_xor(logit[tl], 32);
       logit[tl] += b3;
       rho[tl] = 1.0f;
-      if (TRAIN) {   // as onf_fused.hip: BCE-with-logits (nerf:25,88), rho = (sigmoid(l) - y) / count
+      if (TRAIN) {
+        // BCE-with-logits, mean over the job's samples (nerf:25,88): rho = (sigmoid(l) - y) / count.  dW3[:100] += rho *
+        // relu(a2) as per-lane running sums; record word 4 = rho, words 8 + g = the sign bits of this lane group's a2 (bit
+        // 4 mt + r), all pass 2 needs to rebuild dh2 = rho * W3a * [a2 > 0]; then acc2 <- dh2
         const bool valid = pidx[tl] < a.n_points;
         const float y = valid ? a.labels[pidx[tl]] : 0.0f;
         const float l = logit[tl];
@@ -605,10 +558,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       }
     }
     if (FWD_ONLY) {
-#pragma unroll
-      for (int tl = 0; tl < NT; ++tl)
-        if (g == 0 && pidx[tl] < a.n_points)
-          *reinterpret_cast<f32x4*>(a.out4 + pidx[tl] * 4) = f32x4{logit[tl], 0.f, 0.f, 0.f};
+      store_logits(a, g, pidx, logit);
       continue;
     }
 
@@ -700,14 +650,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
       if (TRAIN) {
 #pragma unroll
         for (int tl = 0; tl < NT; ++tl)
-          if (pidx[tl] < a.n_points) {
-#pragma unroll
-            for (int t = 0; t < HT; ++t) {
-              f32x4 v = acc1[tl][t];
-              if (t == 6) v = f32x4{v[0], g == 0 ? rho[tl] : 0.0f, 0.f, 0.f};
-              *reinterpret_cast<f32x4*>(a.ws_dh1 + pidx[tl] * WH + 16 * t + 4 * g) = v;
-            }
-          }
+          if (pidx[tl] < a.n_points) store_factor_row(a.ws_dh1 + pidx[tl] * WH, g, acc1[tl], rho[tl]);
       }
     }
 
@@ -782,49 +725,8 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
         for (int j = 0; j < 8; ++j) wat[j] = wbt[j];
         __builtin_amdgcn_sched_barrier(0);
       }
-      const float* fte = lds + L::ft(fbase);
-      if (NT == 2) {
-        const f32x2 ux2 = {ux[0], ux[NT - 1]}, uy2 = {uy[0], uy[NT - 1]}, th2 = {th[0], th[NT - 1]};
-        f32x2 gx2 = {gx[0], gx[NT - 1]}, gy2 = {gy[0], gy[NT - 1]}, gt2 = {gt[0], gt[NT - 1]};
-        f32x4 isa4 = {0.f, 0.f, 0.f, 0.f};
-        if (ANG) isa4 = *reinterpret_cast<const f32x4*>(lds + L::ISA + fbase);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const f32x4 e0 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r);
-          const f32x4 e1 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 4);
-          const f32x2 qh = *reinterpret_cast<const f32x2*>(fte + L::FTS * r + 8);
-          const f32x2 wx = {e0.x, e0.y}, wy = {e0.z, e0.w}, bb = {e1.x, e1.y}, fr = {e1.z, e1.w};
-          const f32x2 cof = features2<ANG, true>(wx, wy, bb, fr, qh, splat2(isa4[r]), ux2, uy2, th2);
-          const f32x2 de = f32x2{acc[0][r], acc[NT - 1][r]} * cof;
-          gx2 = fma2(de, wx, gx2);
-          gy2 = fma2(de, wy, gy2);
-          if (ANG) gt2 = fma2(de, fr, gt2);
-        }
-        gx[0] = gx2.x; gx[NT - 1] = gx2.y; gy[0] = gy2.x; gy[NT - 1] = gy2.y; gt[0] = gt2.x; gt[NT - 1] = gt2.y;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const float* ea = fte + L::FTS * r;
-          const float* eb = ea + L::FTS;
-          const f32x2 wx = {ea[0], eb[0]}, wy = {ea[2], eb[2]}, bb = {ea[4], eb[4]}, fr = {ea[6], eb[6]};
-          const f32x2 qh = {ea[8], eb[8]}, isa = {lds[L::ISA + fbase + r], lds[L::ISA + fbase + r + 1]};
-          const f32x2 ux2 = splat2(ux[0]), uy2 = splat2(uy[0]), th2 = splat2(th[0]);
-          const f32x2 cof = features2<ANG, true>(wx, wy, bb, fr, qh, isa, ux2, uy2, th2);
-          const f32x2 de = f32x2{acc[0][r], acc[0][r + 1]} * cof;
-          if (TRAIN) { acc[0][r] = de.x; acc[0][r + 1] = de.y; }
-          if (!TRAIN) {   // the fit needs de only, not d logit / d pose
-            gx[0] = fmaf(de.x, wx.x, gx[0]); gx[0] = fmaf(de.y, wx.y, gx[0]);
-            gy[0] = fmaf(de.x, wy.x, gy[0]); gy[0] = fmaf(de.y, wy.y, gy[0]);
-            if (ANG) { gt[0] = fmaf(de.x, fr.x, gt[0]); gt[0] = fmaf(de.y, fr.y, gt[0]); }
-          }
-        }
-      }
-      if (TRAIN) {
-#pragma unroll
-        for (int tl = 0; tl < NT; ++tl)
-          if (pidx[tl] < a.n_points)
-            *reinterpret_cast<f32x4*>(a.ws_de + pidx[tl] * WIN + 16 * mt + 4 * g) = acc[tl];
-      }
+      chain_rule_tile<NKT, NT, TRAIN, ANG>(lds + L::ft(fbase), lds + L::ISA + fbase, ux, uy, th, acc, gx, gy, gt);
+      if (TRAIN) store_de_tile<NKT>(a, pidx, mt, g, acc);
     };
     const int first_angle_kt = 2 * first_angle_kb < NKT ? 2 * first_angle_kb : NKT;
     if constexpr (NT == 2 && B::NKB == 7) {
@@ -867,11 +769,6 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
           if (u == 10) gy[tl] = fmaf(d_de, dwy[b], gy[tl]);
         }
       };
-      auto store_de = [&](int mt, const f32x4 (&de)[NT]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int tl = 0; tl < NT; ++tl)
-          if (pidx[tl] < a.n_points) *reinterpret_cast<f32x4*>(a.ws_de + pidx[tl] * WIN + 16 * mt + 4 * g) = de[tl];
-      };
       auto l1t_steps = [&](auto hook_c, int mt, f32x4 (&acc)[NT]) __attribute__((always_inline)) {
         constexpr bool HOOK = decltype(hook_c)::value;
         const int fbase = base_p(mt) + colP;
@@ -910,32 +807,11 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      auto epilogue = [&](auto ang_c, int mt, const f32x4 (&acc)[NT]) __attribute__((always_inline)) {   // as l1t_tile
+      auto epilogue = [&](auto ang_c, int mt, f32x4 (&acc)[NT]) __attribute__((always_inline)) {
         constexpr bool ANG = decltype(ang_c)::value;
         const int fbase = base_p(mt) + colP;
-        const float* fte = lds + L::ft(fbase);
-        const f32x2 ux2 = {ux[0], ux[NT - 1]}, uy2 = {uy[0], uy[NT - 1]}, th2 = {th[0], th[NT - 1]};
-        f32x2 gx2 = {gx[0], gx[NT - 1]}, gy2 = {gy[0], gy[NT - 1]}, gt2 = {gt[0], gt[NT - 1]};
-        f32x4 isa4 = {0.f, 0.f, 0.f, 0.f};
-        if (ANG) isa4 = *reinterpret_cast<const f32x4*>(lds + L::ISA + fbase);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const f32x4 e0 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r);
-          const f32x4 e1 = *reinterpret_cast<const f32x4*>(fte + L::FTS * r + 4);
-          const f32x2 qh = *reinterpret_cast<const f32x2*>(fte + L::FTS * r + 8);
-          const f32x2 wx = {e0.x, e0.y}, wy = {e0.z, e0.w}, bb = {e1.x, e1.y}, fr = {e1.z, e1.w};
-          const f32x2 cof = features2<ANG, true>(wx, wy, bb, fr, qh, splat2(isa4[r]), ux2, uy2, th2);
-          const f32x2 de = f32x2{acc[0][r], acc[NT - 1][r]} * cof;
-          if constexpr (TRAIN) {
-            de_prev[0][r] = de.x; de_prev[NT - 1][r] = de.y;
-          } else {
-            gx2 = fma2(de, wx, gx2);
-            gy2 = fma2(de, wy, gy2);
-            if (ANG) gt2 = fma2(de, fr, gt2);
-          }
-        }
-        if constexpr (TRAIN) store_de(mt, de_prev);
-        gx[0] = gx2.x; gx[NT - 1] = gx2.y; gy[0] = gy2.x; gy[NT - 1] = gy2.y; gt[0] = gt2.x; gt[NT - 1] = gt2.y;
+        chain_rule_tile<NKT, NT, TRAIN, ANG>(lds + L::ft(fbase), lds + L::ISA + fbase, ux, uy, th, acc, gx, gy, gt);
+        if constexpr (TRAIN) store_de_tile<NKT>(a, pidx, mt, g, acc);
       };
       // tiles 0 .. first_angle_kt-1 carry no angle features: their epilogues hide behind the next tile's steps
       const int plain_tiles = first_angle_kt < NKT ? first_angle_kt : NKT - 1;   // epilogues that get a host tile
@@ -943,7 +819,7 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
 #pragma unroll 1
       for (int mt = 1; mt <= plain_tiles; ++mt) {
         l1t_steps(std::true_type{}, mt, acc_cur);
-        if constexpr (TRAIN) store_de(mt - 1, de_prev);   // the epilogue of tile mt - 1 ran behind tile mt's steps
+        if constexpr (TRAIN) store_de_tile<NKT>(a, pidx, mt - 1, g, de_prev);   // the epilogue of tile mt - 1 ran behind tile mt's steps
 #pragma unroll
         for (int tl = 0; tl < NT; ++tl) acc_prev[tl] = acc_cur[tl];
       }
@@ -961,18 +837,11 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void onf_split_kernel(const
 #pragma unroll 1
       for (int mt = first_angle_kt; mt < NKT; ++mt) l1t_tile(std::true_type{}, mt);
     }
-#pragma unroll
-    for (int tl = 0; tl < NT; ++tl) {
-      gx[tl] += __shfl_xor(gx[tl], 16); gx[tl] += __shfl_xor(gx[tl], 32);
-      gy[tl] += __shfl_xor(gy[tl], 16); gy[tl] += __shfl_xor(gy[tl], 32);
-      gt[tl] += __shfl_xor(gt[tl], 16); gt[tl] += __shfl_xor(gt[tl], 32);
-      if (a.out4 && g == 0 && pidx[tl] < a.n_points) {
-        f32x4 o = {logit[tl], gx[tl] / geo.sigma, gy[tl] / geo.sigma, gt[tl]};
-        *reinterpret_cast<f32x4*>(a.out4 + pidx[tl] * 4) = o;
-      }
-    }
+    store_out4(a, g, pidx, logit, gx, gy, gt);
   }
-  if (TRAIN) {  // fixed-order partials, as onf_fused.hip: loss per wave, dW3[:100] per wave in h2 slot order
+  if (TRAIN) {
+    // fixed-order partials of this wave: the loss over its lanes (xor tree; waves and workgroups are summed in the final
+    // kernel) and dW3[:100] over its 16 point lanes, h2 slot = 16 mt + 4 g + r (layout P)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) loss_acc += __shfl_xor(loss_acc, o);
     if (lane == 0) a.loss_partial[blockIdx.x * WAVES + wave] = loss_acc;
@@ -1017,21 +886,10 @@ static int launch_nt(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) 
   return launch_t<NKT, 1, MODE>(a, stream, grid_out);
 }
 
-template <int NKT>
-static int launch_mode(int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  return mode == ONF_EVAL ? launch_nt<NKT, ONF_EVAL>(a, stream, grid_out)
-         : mode == ONF_TRAIN ? launch_nt<NKT, ONF_TRAIN>(a, stream, grid_out)
-                             : launch_nt<NKT, ONF_LOGITS>(a, stream, grid_out);
-}
-
 int launch_split16(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  switch (nkt) {
-    case 14: return launch_mode<14>(mode, a, stream, grid_out);
-    case 13: return launch_mode<13>(mode, a, stream, grid_out);
-    case 8: return launch_mode<8>(mode, a, stream, grid_out);
-    case 7: return launch_mode<7>(mode, a, stream, grid_out);
-    default: return onf_unsupported(a.geom);
-  }
+  return dispatch_nkt(nkt, a.geom, [&](auto k) {
+    return dispatch_mode(mode, [&](auto m) { return launch_nt<decltype(k)::value, decltype(m)::value>(a, stream, grid_out); });
+  });
 }
 
 }  // namespace nfopp

@@ -11,13 +11,7 @@ StreamScratch<ImageTag> g_images;
 }  // namespace x32
 
 int launch_x32(int nkt, int mode, const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  switch (nkt) {
-    case 14: return x32::launch_nkb14(a, stream, mode, grid_out);
-    case 13: return x32::launch_nkb13(a, stream, mode, grid_out);
-    case 8: return x32::launch_nkb8(a, stream, mode, grid_out);
-    case 7: return x32::launch_nkb7(a, stream, mode, grid_out);
-    default: return onf_unsupported(a.geom);
-  }
+  return dispatch_nkt(nkt, a.geom, [&](auto k) { return x32::launch_nkb<decltype(k)::value>(a, stream, mode, grid_out); });
 }
 
 }  // namespace nfopp

@@ -946,11 +946,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
 // buffer, its registered content version (0 = unknown), geometry.
 struct ImageTag { const float* params; unsigned long long version; OnfGeom geom; };
 extern StreamScratch<ImageTag> g_images;
-// one feature dimension each (csrc/onf_x32_k*.hip)
-int launch_nkb14(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
-int launch_nkb13(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
-int launch_nkb8(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
-int launch_nkb7(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out);
 
 template <int NKB, int MODE, int XT>
 static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
@@ -985,13 +980,15 @@ static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
                                                    : launch_shape<NKB, MODE, 512>(a, stream, grid_out);
 }
 
-// the three modes of one feature dimension (used by csrc/onf_x32_k*.hip)
+// the three modes of one feature dimension, instantiated in a translation unit each (csrc/onf_x32_k*.hip) and nowhere else
 template <int NKB>
-static int launch_modes(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out) {
-  return mode == ONF_EVAL ? launch_t<NKB, ONF_EVAL>(a, stream, grid_out)
-         : mode == ONF_TRAIN ? launch_t<NKB, ONF_TRAIN>(a, stream, grid_out)
-                             : launch_t<NKB, ONF_LOGITS>(a, stream, grid_out);
+int launch_nkb(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out) {
+  return dispatch_mode(mode, [&](auto m) { return launch_t<NKB, decltype(m)::value>(a, stream, grid_out); });
 }
+extern template int launch_nkb<14>(const OnfKernelArgs&, hipStream_t, int, int*);
+extern template int launch_nkb<13>(const OnfKernelArgs&, hipStream_t, int, int*);
+extern template int launch_nkb<8>(const OnfKernelArgs&, hipStream_t, int, int*);
+extern template int launch_nkb<7>(const OnfKernelArgs&, hipStream_t, int, int*);
 
 }  // namespace x32
 }  // namespace nfopp

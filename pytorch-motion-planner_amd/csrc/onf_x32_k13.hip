@@ -4,6 +4,6 @@
 
 namespace nfopp {
 namespace x32 {
-int launch_nkb13(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out) { return launch_modes<13>(a, stream, mode, grid_out); }
+template int launch_nkb<13>(const OnfKernelArgs&, hipStream_t, int, int*);
 }  // namespace x32
 }  // namespace nfopp

@@ -4,6 +4,6 @@
 
 namespace nfopp {
 namespace x32 {
-int launch_nkb8(const OnfKernelArgs& a, hipStream_t stream, int mode, int* grid_out) { return launch_modes<8>(a, stream, mode, grid_out); }
+template int launch_nkb<8>(const OnfKernelArgs&, hipStream_t, int, int*);
 }  // namespace x32
 }  // namespace nfopp
