@@ -1,5 +1,7 @@
 // LDS image layout, staging and feature evaluation shared by the fused ONF kernels: csrc/onf_fused.hip (fp32 MFMA)
 // and csrc/onf_split.hip (bf16x3 split-precision MFMA).  See the header comment of onf_fused.hip for the design.
+// Also what every ONF kernel family shares with them: the decode of an input feature from the parameter buffer
+// (decode_feature; csrc/onf_x32_impl.h, csrc/onf_wgrad.hip) and the slot maps of layouts P and Q (csrc/onf_wgrad.hip).
 #pragma once
 #include <type_traits>
 
@@ -56,6 +58,29 @@ struct Lds {
 
 __device__ __forceinline__ int base_p(int t) { return 32 * (t >> 1) + 8 * (t & 1); }
 
+// ---- slot maps of the 16x16 K1 kernels -------------------------------------------------------------------------------
+// An MFMA accumulator holds row 4 g + r of tile t in register r of lane group g ("slot" 16 t + 4 g + r), and the next GEMM
+// takes it as its B operand with the k index permuted (header comment of onf_fused.hip).  Which feature / hidden unit a
+// slot holds is the layout: P for the input features and h2 / dh2 (a pair of tiles covers a block of 32: tile 2 K + tpar
+// has the units 32 K + 8 tpar + 16 (g & 1) + 4 (g >> 1) + r, cf. base_p and colP), Q for h1 / dh1 (tile t has the units
+// 16 t + 8 (g & 1) + 4 (g >> 1) + r, cf. colQ).  In both, tile 6 holds unit 96 + g in register 0.  Pass 1 stores its factor
+// matrices in slot order (csrc/onf_stages.h); pass 2 and its gather kernel (csrc/onf_wgrad.hip) index them with these.
+__host__ __device__ inline int slot_layout_p(int f) {  // input features, h2 / dh2 (features < 96)
+  const int o = f & 31, tpar = (o >> 3) & 1, op = o - 8 * tpar, ap = op & ~3, r = op & 3;
+  const int g = ((ap >> 4) & 1) | (((ap >> 2) & 1) << 1);
+  return 16 * (2 * (f >> 5) + tpar) + 4 * g + r;
+}
+__host__ __device__ inline int slot_layout_q(int f) {  // h1 / dh1 (features < 96)
+  const int o = f & 15, aq = o & 12, r = o & 3;
+  const int g = ((aq >> 3) & 1) | (((aq >> 2) & 1) << 1);
+  return 16 * (f >> 4) + 4 * g + r;
+}
+__host__ __device__ inline int hidden_slot(int h, bool layout_q) {
+  if (h >= 96) return 96 + 4 * (h - 96);
+  return layout_q ? slot_layout_q(h) : slot_layout_p(h);
+}
+constexpr int AUG_HIDDEN_SLOT = 16 * 6 + 1;  // tile 6, g = 0, r = 1: the ones unit of h1, the rho row of dh1 (store_factor_row)
+
 // max(x, 0) as ONE integer instruction: for IEEE floats max_i32(bits, 0) clears every negative value (and -0)
 // and keeps every positive one.  (fmaxf lowers to canonicalize + max; an inline-asm v_max_f32 would hide the
 // VALU->MFMA operand hazard from hipcc.)
@@ -88,6 +113,34 @@ __device__ __forceinline__ unsigned lo_level(float w) {
   return __float_as_uint(w) >> 16;   // third level: exactly representable, low half-word is zero
 }
 
+// ---- input feature f, decoded from the flat parameter buffer ----------------------------------------------------------
+// feature = sin(arg + q pi/2) with q = 1 for a cosine feature, kept as qh = q * NFOPP_Q_UNIT (revolutions);
+//   f < n_enc:  arg = wx u_x + wy u_y + b     encoding_layer W_e u + b_e (onf_model.py:39), cosine half onf_model.py:41
+//   f < fin:    arg = (theta + b) * fr        angle_encoder.py:16, cosine half for k >= ang_dim
+//   pads:       all zero, sin(0) = 0 -- except `ones_feature` (-1: none), which evaluates to cos(0) = 1.
+// Every K1 kernel and pass 2 of the fit (which re-evaluates the features pass 1 used) fill their tables from this.
+struct FeatureEntry {
+  float wx, wy, b, fr, qh, is_angle;
+};
+__device__ __forceinline__ FeatureEntry decode_feature(const OnfGeom& g, const float* P, int f, int ones_feature) {
+  FeatureEntry e = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (f < g.n_enc) {
+    e.wx = P[g.off_we + 2 * f];
+    e.wy = P[g.off_we + 2 * f + 1];
+    e.b = g.off_be >= 0 ? P[g.off_be + f] : 0.0f;
+    e.qh = (g.n_enc > g.n_sin && f >= g.n_sin) ? NFOPP_Q_UNIT : 0.0f;
+  } else if (f < g.fin) {
+    const int k = f - g.n_enc;
+    e.b = P[g.off_ang_b + k];
+    e.fr = P[g.off_ang_f + k];
+    e.qh = k >= g.ang_dim ? NFOPP_Q_UNIT : 0.0f;
+    e.is_angle = 1.0f;
+  } else if (f == ones_feature) {
+    e.qh = NFOPP_Q_UNIT;
+  }
+  return e;
+}
+
 // ---- stage the flat parameter buffer into LDS ---------------------------------------------------------------
 // PACKED: weight words hold (bf16 hi | bf16 mid) of the weight instead of its fp32 value (onf_split.hip)
 template <int NKT, bool TRAIN, bool PACKED = false>
@@ -107,32 +160,16 @@ __device__ void fill_lds(float* lds, const OnfKernelArgs& a) {
     lds[L::W2 + idx] = PACKED ? pack_hi_mid(w) : w;
   }
   for (int f = tid; f < L::NF; f += THREADS) {
-    // feature = sin(arg + q*pi/2), q = 1 for cosine features, stored as qh = q * NFOPP_Q_UNIT; every scalar is
-    // stored twice (a packed-math pair)
-    float wx = 0.f, wy = 0.f, b = 0.f, fr = 0.f, w3b = 0.f, qh = 0.f, is_angle = 0.f;
-    if (f < g.n_enc) {
-      wx = P[g.off_we + 2 * f];
-      wy = P[g.off_we + 2 * f + 1];
-      b = g.off_be >= 0 ? P[g.off_be + f] : 0.0f;
-      qh = (g.n_enc > g.n_sin && f >= g.n_sin) ? NFOPP_Q_UNIT : 0.0f;
-      w3b = P[g.off_w3 + H + f];
-    } else if (f < g.fin) {
-      int k = f - g.n_enc;
-      b = P[g.off_ang_b + k];
-      fr = P[g.off_ang_f + k];
-      qh = k >= g.ang_dim ? NFOPP_Q_UNIT : 0.0f;
-      is_angle = 1.0f;
-      w3b = P[g.off_w3 + H + f];
-    } else if (TRAIN && f == a.aug_feature) {
-      qh = NFOPP_Q_UNIT;  // all weights zero: sin(0 + pi/2) = 1
-    }
+    // every scalar is stored twice (a packed-math pair); the ones column exists in training mode only
+    const FeatureEntry d = decode_feature(g, P, f, TRAIN ? a.aug_feature : -1);
+    const float w3b = f < g.fin ? P[g.off_w3 + H + f] : 0.0f;
     float* e = lds + L::ft(f);
-    e[0] = e[1] = wx; e[2] = e[3] = wy; e[4] = e[5] = b; e[6] = e[7] = fr;
-    e[8] = e[9] = qh; e[10] = e[11] = w3b;
+    e[0] = e[1] = d.wx; e[2] = e[3] = d.wy; e[4] = e[5] = d.b; e[6] = e[7] = d.fr;
+    e[8] = e[9] = d.qh; e[10] = e[11] = w3b;
     float* c = lds + L::fc(f);
-    c[0] = wx; c[1] = wy; c[2] = b; c[3] = qh;
+    c[0] = d.wx; c[1] = d.wy; c[2] = d.b; c[3] = d.qh;
     lds[L::W3B + f] = w3b;
-    lds[L::ISA + f] = is_angle;
+    lds[L::ISA + f] = d.is_angle;
   }
   // hidden-indexed vectors: entries 0..95 natural; entries 96 + 4g + r hold feature 96+g for r == 0, else 0
   for (int k = tid; k < 16 * HT; k += THREADS) {

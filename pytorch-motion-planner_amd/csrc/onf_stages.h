@@ -59,7 +59,8 @@ __device__ __forceinline__ void l1_features(const float* fte, const float* isa, 
 }
 
 // ---- TRAIN: a point's 112-float row of a hidden-side factor matrix (layout Q slots): v = relu(a1) with slot6 = 1 (the ones
-// column of h1), or v = dh1 with slot6 = rho;  slot6 sits at (tile 6, g = 0, r = 1), the rest of tile 6 past unit 96 + g is 0
+// column of h1), or v = dh1 with slot6 = rho;  slot6 sits at (tile 6, g = 0, r = 1) = AUG_HIDDEN_SLOT, the rest of tile 6
+// past unit 96 + g is 0
 __device__ __forceinline__ void store_factor_row(float* row, int g, const f32x4 (&acc)[HT], float slot6) {
 #pragma unroll
   for (int t = 0; t < HT; ++t) {

@@ -43,22 +43,18 @@ __global__ __launch_bounds__(256) void onf_rows_reduce_kernel(const float* parti
   if (t == 0) out[e] = tree[0];
 }
 
-// ---- slot maps (see csrc/onf_fused.hip for the layouts) --------------------------------------------------------
-__host__ __device__ inline int slot_layout_p(int f) {  // input features, h2 / dh2 (features < 96)
-  const int o = f & 31, tpar = (o >> 3) & 1, op = o - 8 * tpar, ap = op & ~3, r = op & 3;
-  const int g = ((ap >> 4) & 1) | (((ap >> 2) & 1) << 1);
-  return 16 * (2 * (f >> 5) + tpar) + 4 * g + r;
+// ---- partial tiles: [NTILES][256] per workgroup, a 16 x 16 tile in the accumulator order of the 16x16x4 MFMA ------------
+// (register r of lane l holds row 4 (l >> 4) + r, column l & 15).  Every pass-2 kernel writes this order, the gather kernel
+// reads it (the slot maps that turn a parameter into a row / column are in csrc/onf_layout.h).
+__device__ __forceinline__ int tile_elem_offset(int tile, int row_in_tile, int col_in_tile) {
+  return tile * 256 + 64 * (row_in_tile & 3) + 16 * (row_in_tile >> 2) + col_in_tile;
 }
-__host__ __device__ inline int slot_layout_q(int f) {  // h1 / dh1 (features < 96)
-  const int o = f & 15, aq = o & 12, r = o & 3;
-  const int g = ((aq >> 3) & 1) | (((aq >> 2) & 1) << 1);
-  return 16 * (f >> 4) + 4 * g + r;
+// a lane's accumulator quad of tile T:  tile_elem_offset(T, 4 (lane >> 4) + r, lane & 15) = 256 T + lane + 64 r
+__device__ __forceinline__ void store_acc_tile(float* part, int T, int lane, const f32x4& v) {
+  float* o = part + T * 256 + lane;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[64 * r] = v[r];
 }
-__host__ __device__ inline int hidden_slot(int h, bool layout_q) {
-  if (h >= 96) return 96 + 4 * (h - 96);
-  return layout_q ? slot_layout_q(h) : slot_layout_p(h);
-}
-constexpr int AUG_HIDDEN_SLOT = 97;  // tile 6, g = 0, r = 1
 
 template <int NKT>
 struct WgLayout {
@@ -84,10 +80,6 @@ struct WgradArgs {
   OnfGeom geom;
   const float* params;
   int aug_feature;
-  // 0: pass 1 was onf_fused.hip / onf_split.hip (factors in their slot orders, layouts P and Q);  1: pass 1 was onf_x32.hip:
-  // a factor's slot IS the feature / hidden-unit index, ones feature = geom.fin, h1's ones unit = 101, rho row of dh1 = 100,
-  // and dh2 is rebuilt WITHOUT W3a (G2 = sum_p rho_p [a2_p > 0] h1_p^T; the gather kernel applies W3a)
-  int x32_order;
   // stored factors, back to back in this order (carve_wgrad):  h1 [P,112] | dh1 [P,112] | de [P,WIN] | record [P,12]
   const float* ws;
   long long P;
@@ -129,6 +121,28 @@ __device__ __forceinline__ f32x4 features4_scalar(const f32x4& wx, const f32x4& 
   return v;
 }
 
+// Tables of the factors pass 2 rebuilds, at `tab`: the feature table of `in` as six planes [6][WIN] (wx | wy | b | fr | qh |
+// is_angle) and behind it the factor of dh2 [HS], both in the order of pass 1's factors: slot order (layouts P of
+// csrc/onf_layout.h; pads evaluate to sin(0) = 0, the pad feature `aug_feature` to cos(0) = 1: the ones column, as in
+// fill_lds; W3a) or, XO, by feature / hidden-unit index (ones: rho [a2 > 0] alone, the gather kernel applies W3a).
+// Ends with the tables written but NOT yet visible: the caller's next barrier publishes them.
+template <int WIN, bool XO>
+__device__ __forceinline__ void fill_wgrad_tables(float* tab, const WgradArgs& a) {
+  const OnfGeom& g = a.geom;
+  const int tid = threadIdx.x;
+  float* w3a = tab + 6 * WIN;
+  for (int k = tid; k < 6 * WIN + HS; k += WG_THREADS) tab[k] = 0.0f;
+  __syncthreads();
+  for (int f = tid; f < 32 * ((WIN / 16 + 1) / 2); f += WG_THREADS) {
+    const int slot = XO ? f : slot_layout_p(f);
+    if (slot >= WIN) continue;
+    const FeatureEntry d = decode_feature(g, a.params, f, a.aug_feature);
+    float* e = tab + slot;
+    e[0] = d.wx; e[WIN] = d.wy; e[2 * WIN] = d.b; e[3 * WIN] = d.fr; e[4 * WIN] = d.qh; e[5 * WIN] = d.is_angle;
+  }
+  for (int h = tid; h < NFOPP_HIDDEN; h += WG_THREADS) w3a[XO ? h : hidden_slot(h, false)] = XO ? 1.0f : a.params[g.off_w3 + h];
+}
+
 template <int NKT>
 __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArgs a) {
   using W = WgLayout<NKT>;
@@ -159,35 +173,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArg
   // zero the unused columns 4..15 of the u tile once (both buffers)
   for (int k = tid; k < 2 * KC * 12; k += WG_THREADS)
     lds[(k / (KC * 12)) * W::BUF + ((k / 12) % KC) * W::STRIDE + W::C_U + 4 + (k % 12)] = 0.0f;
-  // tables in SLOT order for the rebuilt factors: feature table of `in` (pads evaluate to sin(0) = 0, the pad feature
-  // `aug_feature` to cos(0) = 1: the ones column, as in fill_lds) and W3a for dh2
-  {
-    const OnfGeom& g = a.geom;
-    const float* P = a.params;
-    for (int k = tid; k < 6 * W::WIN; k += WG_THREADS) lds[W::L_FT + k] = 0.0f;
-    for (int k = tid; k < HS; k += WG_THREADS) lds[W::L_W3A + k] = 0.0f;
-    __syncthreads();
-    for (int f = tid; f < 32 * ((NKT + 1) / 2); f += WG_THREADS) {
-      const int slot = slot_layout_p(f);
-      if (slot >= W::WIN) continue;
-      float wx = 0.f, wy = 0.f, b = 0.f, fr = 0.f, qh = 0.f, isa = 0.f;
-      if (f < g.n_enc) {
-        wx = P[g.off_we + 2 * f]; wy = P[g.off_we + 2 * f + 1];
-        b = g.off_be >= 0 ? P[g.off_be + f] : 0.0f;
-        qh = (g.n_enc > g.n_sin && f >= g.n_sin) ? NFOPP_Q_UNIT : 0.0f;
-      } else if (f < g.fin) {
-        const int k = f - g.n_enc;
-        b = P[g.off_ang_b + k]; fr = P[g.off_ang_f + k];
-        qh = k >= g.ang_dim ? NFOPP_Q_UNIT : 0.0f;
-        isa = 1.0f;
-      } else if (f == a.aug_feature) {
-        qh = NFOPP_Q_UNIT;
-      }
-      float* e = lds + W::L_FT + slot;
-      e[0] = wx; e[W::WIN] = wy; e[2 * W::WIN] = b; e[3 * W::WIN] = fr; e[4 * W::WIN] = qh; e[5 * W::WIN] = isa;
-    }
-    for (int h = tid; h < NFOPP_HIDDEN; h += WG_THREADS) lds[W::L_W3A + hidden_slot(h, false)] = P[g.off_w3 + h];
-  }
+  static_assert(W::L_W3A == W::L_FT + 6 * W::WIN, "fill_wgrad_tables: W3a right behind the feature planes");
+  fill_wgrad_tables<W::WIN, false>(lds + W::L_FT, a);   // visible behind the barrier in front of the first rebuild
 
   // Per-thread staging descriptors, computed ONCE: float4 number tid + k * WG_THREADS of a chunk always comes from the same
   // array / column of sample q_k and goes to the same LDS place; from chunk to chunk only the sample index moves, by a
@@ -325,14 +312,11 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_kernel(const WgradArg
     __syncthreads();                                          // B: `cur` consumed, `nxt` rebuilt
     float* t = cur; cur = nxt; nxt = t;
   }
+  float* const part = a.partial + (long long)blockIdx.x * W::NTILES * 256;
 #pragma unroll
   for (int j = 0; j < W::TPW; ++j) {
     const int T = wave + WG_WAVES * j;
-    if (T < W::NTILES) {
-      float* o = a.partial + ((long long)blockIdx.x * W::NTILES + T) * 256 + lane;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[64 * r] = acc[j][r];
-    }
+    if (T < W::NTILES) store_acc_tile(part, T, lane, acc[j]);
   }
 }
 
@@ -412,29 +396,19 @@ __device__ __forceinline__ void store_split4(float* lds, int img, int plane, int
   *reinterpret_cast<u32x2*>(lds + img + 2 * plane + at) = l;
 }
 
-// fragment of one level: two transposing reads (sample rows +0 and +8 of this lane group's set)
-template <int R>
+// fragment of one level: two transposing reads, the second D2 dwords behind the first (16x16x32: sample rows +0 and +8 of
+// this lane group's set, D2 = 8 row lengths;  32x32x16: the even and the odd rows of the half's eight, D2 = one row length)
+template <int D2>
 __device__ __forceinline__ s16x8 read_frag(const float* lane_base, int dword_off) {
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lane_base + dword_off));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lane_base + dword_off + 8 * R));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lane_base + dword_off + D2));
   return s16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 }
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x4 mfma_bf16(s16x8 a, s16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-// Wait states behind a group of MFMAs before its fragment registers are reloaded (make EXTRA=-DNFOPP_MFMA_GUARD).  A precaution of
-// round 2 against run-to-run differences that turned out to come from a packed fma with op_sel on freshly loaded LDS values
-// (DESIGN.md K5); hipcc's hazard recogniser handles MFMA operand reuse for builtins.
-__device__ __forceinline__ void mfma_guard() {
-#ifdef NFOPP_MFMA_GUARD   /* round 4: OFF by default -- 24 guards x 64 wait states per chunk were 13 % of the kernel once the
-                             multiplying waves had become its critical path; the bit-for-bit repeat tests pass without them */
-  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15");   // 64 wait states: four MFMA issue slots
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-
 // End of a pipeline phase.  The scheduling barrier matters: without it hipcc hoists the NEXT phase's register arithmetic (the
 // splitting of operands whose loads were issued a moment ago) above the barrier, and the s_waitcnt vmcnt(0) that goes with
 // it exposes the full HBM latency once per chunk (0.6 ms of the 1.7 ms the kernel took).
@@ -455,7 +429,26 @@ __device__ __forceinline__ void mfma_split_pair(const s16x8 (&a)[3], const s16x8
   c0 = mfma_bf16(a[0], b0[1], c0); c1 = mfma_bf16(a[0], b1[1], c1);
   c0 = mfma_bf16(a[0], b0[0], c0); c1 = mfma_bf16(a[0], b1[0], c1);
 }
-// XO: the factors are in x32 order (WgradArgs::x32_order, a.x32_order == XO)
+// G3 of a multiplying wave (rows 64 w + 4 (lane >> 2) + i in register i, column lane & 3: the 4x4x1 form) as partial tiles
+// 4 w .. 4 w + 3 behind tile T0; the columns 4..15 of the tiles (the zero columns of the 16x16x4 form) are written as
+// zeros by the lanes that own none of the others.
+template <int NKT>
+__device__ __forceinline__ void store_g3_tiles(float* part, int T0, int wave, int lane, const f32x4& g3) {
+  const int rb = 4 * wave + (lane >> 4);
+  if (rb < NKT) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[tile_elem_offset(T0 + rb, 4 * ((lane >> 2) & 3) + i, lane & 3)] = g3[i];
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int rz = 4 * wave + t;
+    if (rz < NKT && (lane & 15) >= 4) store_acc_tile(part, T0 + rz, lane, f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+}
+
+// XO: the factors are in x32 order -- pass 1 was onf_x32.hip, not onf_fused.hip / onf_split.hip (slot orders, layouts P and Q):
+// a factor's slot IS the feature / hidden-unit index, ones feature = geom.fin, h1's ones unit = 101, rho row of dh1 = 100,
+// and dh2 is rebuilt WITHOUT W3a (G2 = sum_p rho_p [a2_p > 0] h1_p^T; the gather kernel applies W3a: GatherArgs::x32_order)
 template <int NKT, bool XO>
 __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const WgradArgs a) {
   using L = WsLayout<NKT>;
@@ -467,33 +460,9 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
   const long long c0 = blockIdx.x, step = gridDim.x;
 
   // ---- tables (slot order) and the constant parts of the images -----------------------------------------------------
-  {
-    const OnfGeom& g = a.geom;
-    const float* P = a.params;
-    for (int k = tid; k < L::L_TOTAL; k += WG_THREADS) lds[k] = 0.0f;   // also: u-tile columns 4..15, image pad columns
-    __syncthreads();
-    for (int f = tid; f < 32 * ((NKT + 1) / 2); f += WG_THREADS) {
-      const int slot = XO ? f : slot_layout_p(f);
-      if (slot >= WIN) continue;
-      float wx = 0.f, wy = 0.f, b = 0.f, fr = 0.f, qh = 0.f, isa = 0.f;
-      if (f < g.n_enc) {
-        wx = P[g.off_we + 2 * f]; wy = P[g.off_we + 2 * f + 1];
-        b = g.off_be >= 0 ? P[g.off_be + f] : 0.0f;
-        qh = (g.n_enc > g.n_sin && f >= g.n_sin) ? NFOPP_Q_UNIT : 0.0f;
-      } else if (f < g.fin) {
-        const int k = f - g.n_enc;
-        b = P[g.off_ang_b + k]; fr = P[g.off_ang_f + k];
-        qh = k >= g.ang_dim ? NFOPP_Q_UNIT : 0.0f;
-        isa = 1.0f;
-      } else if (f == a.aug_feature) {
-        qh = NFOPP_Q_UNIT;
-      }
-      float* e = lds + L::L_FT + slot;
-      e[0] = wx; e[WIN] = wy; e[2 * WIN] = b; e[3 * WIN] = fr; e[4 * WIN] = qh; e[5 * WIN] = isa;
-    }
-    // factor of the rebuilt dh2: W3a in slot order, or 1 (x32 order: rho * [a2 > 0] alone, see WgradArgs)
-    for (int h = tid; h < NFOPP_HIDDEN; h += WG_THREADS) lds[L::L_W3A + (XO ? h : hidden_slot(h, false))] = XO ? 1.0f : P[g.off_w3 + h];
-  }
+  static_assert(L::L_W3A == L::L_FT + 6 * WIN && L::L_TOTAL == L::L_W3A + HS, "fill_wgrad_tables: the tables end the image");
+  for (int k = tid; k < L::L_FT; k += WG_THREADS) lds[k] = 0.0f;   // u-tile columns 4..15, image pad columns
+  fill_wgrad_tables<WIN, XO>(lds + L::L_FT, a);
   __syncthreads();   // the tables are read into registers below
 
   // ---- two kinds of waves ---------------------------------------------------------------------------------------------
@@ -699,8 +668,22 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     return;
   }
 
+  // ================================= consumers: waves 0..3 multiply =======================================================
+  // G3 = de^T u, in either order: it has 4 useful columns (u_x, u_y, 1, theta): on v_mfma_f32_4x4x1_16b_f32 -- sixteen
+  // independent 4 x 4 blocks, one rank-1 update each -- a lane feeds de[sample][64 w + lane] and u[sample][lane & 3], every
+  // output is a useful one and an instruction takes 8 pipe cycles; the 16x16x4 form spent 32 cycles on tiles whose 12 other
+  // columns are zero, and an fp32 MFMA blocks the SIMD's vector issue for its whole duration (no co-execution), i.e. the
+  // staging partner too.  Wave w owns rows 64 w .. 64 w + 63 of the  de | u tile  rows (stride RS_DE); two alternating
+  // accumulators (even / odd samples), added at the end in a fixed order.
+  f32x4 acc3e = f32x4{0.f, 0.f, 0.f, 0.f}, acc3o = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* const g3_a = lds + L::B_DE + 64 * wave + lane;
+  const float* const g3_b = lds + L::B_DE + WIN + (lane & 3);
+  const bool g3_mine = 64 * wave < WIN;
+  constexpr int T_G2 = 7 * NKT, T_G3 = 7 * NKT + 49;   // first partial tile of G2 / of G3
+  float* const part = a.partial + (long long)blockIdx.x * L::NTILES * 256;
+
   if constexpr (XO) {
-    // ================== consumers, x32 order (round 4): waves 0..3 multiply on v_mfma_f32_32x32x16_bf16 ==================
+    // ================== x32 order (round 4): v_mfma_f32_32x32x16_bf16 ======================================================
     // The 16x16x32 form below issues 210 bf16 matrix instructions per wave and chunk, each holding the SIMD's vector issue port for 8
     // of its 16 cycles -- the port this wave shares with its staging partner, whose instruction total bounds the kernel (timing
     // ablation with half the matrix instructions: -8 %).  32x32x16 tiles need half as many issues for the same products.
@@ -720,18 +703,9 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     const float* const fA_in = lds + L::A_IN + rowl * L::R_IN + coll;
     const float* const fB_msk = lds + L::B_DH2 + rowl * L::R_H + coll + 16 * wave;
     const float* const fB_h1 = lds + L::B_H1 + rowl * L::R_H + coll;
-    auto frag32 = [](const float* base, int dword_off, auto r_c) __attribute__((always_inline)) {
-      constexpr int R = decltype(r_c)::value;
-      typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + dword_off));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + dword_off + R));
-      return s16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    };
     auto mm = [](const s16x8& x, const s16x8& y, f32x16 c) __attribute__((always_inline)) {
       return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
     };
-    using ic_rh = std::integral_constant<int, L::R_H>;
-    using ic_rin = std::integral_constant<int, L::R_IN>;
     constexpr int NCT = (WIN + 31) / 32;   // 32-column tiles of G1 (input slots)
     f32x16 acc1[NCT], acc2[4];
 #pragma unroll
@@ -742,11 +716,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[t][r] = 0.0f;
-    f32x4 acc3e = f32x4{0.f, 0.f, 0.f, 0.f}, acc3o = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* const g3_a = lds + L::B_DE + 64 * wave + lane;
-    const float* const g3_b = lds + L::B_DE + WIN + (lane & 3);
-    const bool g3_mine = 64 * wave < WIN;
-    if (c0 < n_chunks) {
+    if (c0 < n_chunks) {   // the two barriers of the staging waves' prologue
       phase_barrier();
       phase_barrier();
     }
@@ -756,17 +726,17 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       {
         s16x8 af[3], bf[2][3];
 #pragma unroll
-        for (int lv = 0; lv < 3; ++lv) bf[0][lv] = frag32(fA_in, lv * L::P_IN, ic_rin{});
+        for (int lv = 0; lv < 3; ++lv) bf[0][lv] = read_frag<L::R_IN>(fA_in, lv * L::P_IN);
         static_for<0, 2 * NCT>([&](auto sc) __attribute__((always_inline)) {
           constexpr int st = decltype(sc)::value, ks = st / NCT, ct = st % NCT;
           if constexpr (ct == 0) {
 #pragma unroll
-            for (int lv = 0; lv < 3; ++lv) af[lv] = frag32(fA_dh1, lv * L::P_H + 16 * ks * L::R_H, ic_rh{});
+            for (int lv = 0; lv < 3; ++lv) af[lv] = read_frag<L::R_H>(fA_dh1, lv * L::P_H + 16 * ks * L::R_H);
           }
           if constexpr (st + 1 < 2 * NCT) {
             constexpr int ks1 = (st + 1) / NCT, ct1 = (st + 1) % NCT;
 #pragma unroll
-            for (int lv = 0; lv < 3; ++lv) bf[(st + 1) & 1][lv] = frag32(fA_in, lv * L::P_IN + 16 * ct1 + 16 * ks1 * L::R_IN, ic_rin{});
+            for (int lv = 0; lv < 3; ++lv) bf[(st + 1) & 1][lv] = read_frag<L::R_IN>(fA_in, lv * L::P_IN + 16 * ct1 + 16 * ks1 * L::R_IN);
           }
           __builtin_amdgcn_sched_barrier(0);
           const s16x8 (&b)[3] = bf[st & 1];
@@ -800,15 +770,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       {
         s16x8 am[2], bf[2][3];
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) am[ks] = frag32(fB_msk, 16 * ks * L::R_H, ic_rh{});
+        for (int ks = 0; ks < 2; ++ks) am[ks] = read_frag<L::R_H>(fB_msk, 16 * ks * L::R_H);
 #pragma unroll
-        for (int lv = 0; lv < 3; ++lv) bf[0][lv] = frag32(fB_h1, lv * L::P_H, ic_rh{});
+        for (int lv = 0; lv < 3; ++lv) bf[0][lv] = read_frag<L::R_H>(fB_h1, lv * L::P_H);
         static_for<0, 8>([&](auto sc) __attribute__((always_inline)) {
           constexpr int st = decltype(sc)::value, ct = st >> 1, ks = st & 1;
           if constexpr (st + 1 < 8) {
             constexpr int ct1 = (st + 1) >> 1, ks1 = (st + 1) & 1;
 #pragma unroll
-            for (int lv = 0; lv < 3; ++lv) bf[(st + 1) & 1][lv] = frag32(fB_h1, lv * L::P_H + 16 * ct1 + 16 * ks1 * L::R_H, ic_rh{});
+            for (int lv = 0; lv < 3; ++lv) bf[(st + 1) & 1][lv] = read_frag<L::R_H>(fB_h1, lv * L::P_H + 16 * ct1 + 16 * ks1 * L::R_H);
           }
           __builtin_amdgcn_sched_barrier(0);
           const s16x8 (&b)[3] = bf[st & 1];
@@ -831,46 +801,23 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
       }
       phase_barrier();
     }
-    // ---- per-workgroup partial tiles, in the 16 x 16 tile order the reduce / gather kernels read: result (row, col) -> tile
-    // (row / 16, col / 16), element 64 (row & 3) + 16 ((row & 15) >> 2) + (col & 15).  A lane of a 32 x 32 accumulator holds column
-    // lane & 31 and the rows 8 (r >> 2) + 4 (lane >> 5) + (r & 3), r = 0..15.
-    float* const part = a.partial + (long long)blockIdx.x * L::NTILES * 256;
-    const int cj = lane & 31, g = lane >> 5;
-#pragma unroll
-    for (int t = 0; t < NCT; ++t)
+    // ---- per-workgroup partial tiles: result (row, col) -> tile (row / 16, col / 16), tile_elem_offset.  A lane of a 32 x 32
+    // accumulator holds column lane & 31 and the rows 8 (r >> 2) + 4 (lane >> 5) + (r & 3), r = 0..15.
+    auto put32 = [&](const f32x16& v, int t, int tile0, int tiles_per_row, int n_cols) __attribute__((always_inline)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = 32 * wave + 8 * (r >> 2) + 4 * g + (r & 3), col = 32 * t + cj;
-        if (row < HS && col < WIN) part[((row >> 4) * NKT + (col >> 4)) * 256 + 64 * (row & 3) + 16 * ((row & 15) >> 2) + (col & 15)] = acc1[t][r];
+        const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3), col = 32 * t + (lane & 31);
+        if (row < HS && col < n_cols) part[tile_elem_offset(tile0 + (row >> 4) * tiles_per_row + (col >> 4), row & 15, col & 15)] = v[r];
       }
+    };
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < NCT; ++t) put32(acc1[t], t, 0, NKT, WIN);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = 32 * wave + 8 * (r >> 2) + 4 * g + (r & 3), col = 32 * t + cj;
-        if (row < HS && col < HS) part[(7 * NKT + (row >> 4) * 7 + (col >> 4)) * 256 + 64 * (row & 3) + 16 * ((row & 15) >> 2) + (col & 15)] = acc2[t][r];
-      }
-    {
-      const f32x4 g3 = acc3e + acc3o;
-      const int rb = 4 * wave + (lane >> 4);
-      float* o = part + (7 * NKT + 49 + rb) * 256;
-      if (rb < NKT) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[16 * ((lane >> 2) & 3) + (lane & 3) + 64 * i] = g3[i];
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int rz = 4 * wave + t;
-        if (rz < NKT && (lane & 15) >= 4) {
-          float* z = part + (7 * NKT + 49 + rz) * 256 + lane;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) z[64 * r] = 0.0f;
-        }
-      }
-    }
+    for (int t = 0; t < 4; ++t) put32(acc2[t], t, T_G2, 7, HS);
+    store_g3_tiles<NKT>(part, T_G3, wave, lane, acc3e + acc3o);
     return;
   }
-  // ================================= consumers: waves 0..3 multiply =======================================================
+  // ================== slot order: v_mfma_f32_16x16x32_bf16 ==================================================================
   // G1 (7 x NKT tiles, dh1^T in): wave w owns the column blocks w, w + 4, w + 8, w + 12, all 7 row blocks each (a column block
   //   past NKT is multiplied on whatever the image holds there and never stored: 28 tiles for every wave).
   // G2 (7 x 7, dh2^T h1): w2 -> column blocks {2, 3}, w3 -> {4, 5}, w0 -> {0, 6}, w1 -> {1, 6}; block 6 is computed by both w0
@@ -878,27 +825,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
   const int grp = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
   const int row0 = 16 * (grp >> 1) + 4 * (grp & 1) + qq;   // lane part of every transposing read: sample row, dwords 2p
   const int lane_h = row0 * L::R_H + 2 * pp, lane_in = row0 * L::R_IN + 2 * pp;
-  constexpr int R_F = L::R_H, LS_F = L::P_H;   // images of h1 / dh1: three planes [KS][R_H]
-  const int lane_f = lane_h;
   const int g2_cb0 = wave < 2 ? wave : 2 * wave - 2, g2_cb1 = wave < 2 ? 6 : 2 * wave - 1;
   // one base register per image, with this wave's first column block folded in: every read offset below is a compile-time
   // constant under 64 KB and goes into the instruction's offset field
-  const float* const bA_dh1 = lds + L::A_DH1 + lane_f;
+  const float* const bA_dh1 = lds + L::A_DH1 + lane_h;
   const float* const bA_in = lds + L::A_IN + lane_in + 8 * wave;          // + 32 dwords per further column block
   const float* const bB_dh2 = lds + L::B_DH2 + lane_h;
-  const float* const bB_h1a = lds + L::B_H1 + lane_f + 8 * g2_cb0;
-  const float* const bB_h1b = lds + L::B_H1 + lane_f + 8 * g2_cb1;
+  const float* const bB_h1a = lds + L::B_H1 + lane_h + 8 * g2_cb0;
+  const float* const bB_h1b = lds + L::B_H1 + lane_h + 8 * g2_cb1;
   f32x4 acc1[4][7], acc2[2][7];
-  // G3 = de^T u has 4 useful columns (u_x, u_y, 1, theta): on v_mfma_f32_4x4x1_16b_f32 -- sixteen independent 4 x 4 blocks, one
-  // rank-1 update each -- a lane feeds de[sample][64 w + lane] and u[sample][lane & 3], every output is a useful one and an
-  // instruction takes 8 pipe cycles; the 16x16x4 form spent 32 cycles on tiles whose 12 other columns are zero, and an fp32 MFMA
-  // blocks the SIMD's vector issue for its whole duration (no co-execution), i.e. the staging partner too.  Wave w owns rows
-  // 64 w .. 64 w + 63; two alternating accumulators (even / odd samples), added at the end in a fixed order.
-  f32x4 acc3e = f32x4{0.f, 0.f, 0.f, 0.f}, acc3o = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int G3_RA = L::RS_DE, G3_RB = L::RS_DE;   // row stride of the  de | u tile  rows
-  const float* const g3_a = lds + L::B_DE + 64 * wave + lane;
-  const float* const g3_b = lds + L::B_DE + WIN + (lane & 3);
-  const bool g3_mine = 64 * wave < WIN;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -908,97 +843,69 @@ __global__ __launch_bounds__(WG_THREADS, 2) void onf_wgrad_split_kernel(const Wg
 #pragma unroll
     for (int r = 0; r < 7; ++r) acc2[c][r] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // 7 row blocks against one pair of column blocks; the A fragments ping-pong between two register sets (no copies)
-  // (image geometry as compile-time constants: row length and level step of the A image and of the B image)
-  auto mul_pair = [&](const float* a_base, const float* b0_base, const float* b1_base, auto ra_c, auto la_c, auto rb_c, auto lb_c,
-                      f32x4 (&c0)[7], f32x4 (&c1)[7]) __attribute__((always_inline)) {
-    constexpr int RA = decltype(ra_c)::value, LA = decltype(la_c)::value, RB = decltype(rb_c)::value, LB = decltype(lb_c)::value;
+  // 7 row blocks against one pair of column blocks; the A fragments ping-pong between two register sets (no copies).  The A
+  // image is a hidden-side one (dh1, dh2: three planes [KS][R_H]); the B image's row length and level step are compile-time
+  // constants
+  auto mul_pair = [&](const float* a_base, const float* b0_base, const float* b1_base, auto rb_c, auto lb_c, f32x4 (&c0)[7],
+                      f32x4 (&c1)[7]) __attribute__((always_inline)) {
+    constexpr int RA = L::R_H, LA = L::P_H, RB = decltype(rb_c)::value, LB = decltype(lb_c)::value;
     s16x8 bf0[3], bf1[3], af[2][3];
-    mfma_guard();   // the fragment registers below were operands of the MFMAs just issued
 #pragma unroll
     for (int lv = 0; lv < 3; ++lv) {
-      bf0[lv] = read_frag<RB>(b0_base, lv * LB);
-      bf1[lv] = read_frag<RB>(b1_base, lv * LB);
+      bf0[lv] = read_frag<8 * RB>(b0_base, lv * LB);
+      bf1[lv] = read_frag<8 * RB>(b1_base, lv * LB);
     }
 #pragma unroll
-    for (int lv = 0; lv < 3; ++lv) af[0][lv] = read_frag<RA>(a_base, lv * LA);
+    for (int lv = 0; lv < 3; ++lv) af[0][lv] = read_frag<8 * RA>(a_base, lv * LA);
     static_for<0, 7>([&](auto rc) __attribute__((always_inline)) {
       constexpr int r = decltype(rc)::value;
       if constexpr (r + 1 < 7) {
-        if constexpr (r > 0) mfma_guard();   // set (r + 1) & 1 was read by step r - 1's MFMAs, issued just before
 #pragma unroll
-        for (int lv = 0; lv < 3; ++lv) af[(r + 1) & 1][lv] = read_frag<RA>(a_base, lv * LA + 8 * (r + 1));
+        for (int lv = 0; lv < 3; ++lv) af[(r + 1) & 1][lv] = read_frag<8 * RA>(a_base, lv * LA + 8 * (r + 1));
       }
       __builtin_amdgcn_sched_barrier(0);
       mfma_split_pair(af[r & 1], bf0, bf1, c0[r], c1[r]);
       __builtin_amdgcn_sched_barrier(0);
     });
   };
-  if (c0 < n_chunks) {
+  if (c0 < n_chunks) {   // the two barriers of the staging waves' prologue
     phase_barrier();
     phase_barrier();
   }
   for (long long chunk = c0; chunk < n_chunks; chunk += step) {
     // phase A: G1 out of bufA
-    using ic_rf = std::integral_constant<int, R_F>;
-    using ic_lf = std::integral_constant<int, LS_F>;
     using ic_rin = std::integral_constant<int, L::R_IN>;
     using ic_pin = std::integral_constant<int, L::P_IN>;
     using ic_rh = std::integral_constant<int, L::R_H>;
     using ic_ph = std::integral_constant<int, L::P_H>;
-    mul_pair(bA_dh1, bA_in, bA_in + 32, ic_rf{}, ic_lf{}, ic_rin{}, ic_pin{}, acc1[0], acc1[1]);
-    mul_pair(bA_dh1, bA_in + 64, bA_in + 96, ic_rf{}, ic_lf{}, ic_rin{}, ic_pin{}, acc1[2], acc1[3]);
+    mul_pair(bA_dh1, bA_in, bA_in + 32, ic_rin{}, ic_pin{}, acc1[0], acc1[1]);
+    mul_pair(bA_dh1, bA_in + 64, bA_in + 96, ic_rin{}, ic_pin{}, acc1[2], acc1[3]);
     phase_barrier();
     // phase B: G2 and G3 out of bufB
-    mul_pair(bB_dh2, bB_h1a, bB_h1b, ic_rh{}, ic_ph{}, ic_rf{}, ic_lf{}, acc2[0], acc2[1]);
+    mul_pair(bB_dh2, bB_h1a, bB_h1b, ic_rh{}, ic_ph{}, acc2[0], acc2[1]);
     if (g3_mine) {
 #pragma unroll
       for (int q = 0; q < KS; q += 2) {
-        acc3e = __builtin_amdgcn_mfma_f32_4x4x1f32(g3_a[q * G3_RA], g3_b[q * G3_RB], acc3e, 0, 0, 0);
-        acc3o = __builtin_amdgcn_mfma_f32_4x4x1f32(g3_a[(q + 1) * G3_RA], g3_b[(q + 1) * G3_RB], acc3o, 0, 0, 0);
+        acc3e = __builtin_amdgcn_mfma_f32_4x4x1f32(g3_a[q * L::RS_DE], g3_b[q * L::RS_DE], acc3e, 0, 0, 0);
+        acc3o = __builtin_amdgcn_mfma_f32_4x4x1f32(g3_a[(q + 1) * L::RS_DE], g3_b[(q + 1) * L::RS_DE], acc3o, 0, 0, 0);
       }
     }
     phase_barrier();
   }
 
   // ---- per-workgroup partial tiles (tile numbering and element order of the fp32 kernel) ---------------------------------
-  auto put = [&](int T, const f32x4& v) __attribute__((always_inline)) {
-    float* o = a.partial + ((long long)blockIdx.x * L::NTILES + T) * 256 + lane;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[64 * r] = v[r];
-  };
 #pragma unroll
   for (int c = 0; c < 4; ++c)
     if (wave + 4 * c < NKT)
 #pragma unroll
-      for (int r = 0; r < 7; ++r) put(r * NKT + wave + 4 * c, acc1[c][r]);
+      for (int r = 0; r < 7; ++r) store_acc_tile(part, r * NKT + wave + 4 * c, lane, acc1[c][r]);
 #pragma unroll
   for (int r = 0; r < 7; ++r) {
-    put(7 * NKT + r * 7 + g2_cb0, acc2[0][r]);
+    store_acc_tile(part, T_G2 + r * 7 + g2_cb0, lane, acc2[0][r]);
     const bool mine = wave >= 2 || (wave == 0 ? r < 4 : r >= 4);   // column block 6 is split by rows between waves 0 and 1
-    if (mine) put(7 * NKT + r * 7 + g2_cb1, acc2[1][r]);
+    if (mine) store_acc_tile(part, T_G2 + r * 7 + g2_cb1, lane, acc2[1][r]);
   }
-  // G3 tiles in the 16 x 16 tile order the reduce / gather kernels read: row k, column c -> tile k / 16, element
-  // 16 ((k % 16) / 4) + c + 64 (k % 4).  This lane holds rows 64 w + 4 (lane / 4) + i, column lane & 3; the columns 4..15 of
-  // the tiles (the zero columns of the 16x16x4 form) are written as zeros by the lanes that own none of the others.
-  {
-    const f32x4 g3 = acc3e + acc3o;
-    const int rb = 4 * wave + (lane >> 4);
-    float* o = a.partial + ((long long)blockIdx.x * L::NTILES + 7 * NKT + 49 + rb) * 256;
-    if (rb < NKT) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) o[16 * ((lane >> 2) & 3) + (lane & 3) + 64 * i] = g3[i];
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int rz = 4 * wave + t;
-      if (rz < NKT && (lane & 15) >= 4) {
-        float* z = a.partial + ((long long)blockIdx.x * L::NTILES + 7 * NKT + 49 + rz) * 256 + lane;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z[64 * r] = 0.0f;
-      }
-    }
-  }
+  store_g3_tiles<NKT>(part, T_G3, wave, lane, acc3e + acc3o);
 }
 
 // reduced[e] = sum over workgroups of partial[wg][e], fixed order: 64 elements per block, 16 row groups per element (thread
@@ -1032,7 +939,7 @@ __global__ __launch_bounds__(64 * RED_GROUPS) void onf_wgrad_reduce_kernel(const
 struct GatherArgs {
   OnfGeom geom;
   int nkt, aug_in_slot;
-  int x32_order;              // WgradArgs::x32_order
+  int x32_order;              // the factors were in x32 order (onf_wgrad_split_kernel<NKT, XO = true>)
   const float* params;
   const float* reduced;       // [NTILES][256]
   const float* g4;            // [112] dW3[:100] in h2 slot order (reduced per-wave partials of pass 1)
@@ -1040,10 +947,6 @@ struct GatherArgs {
   float* grad;                // [n_params + 2]
   float count;
 };
-
-__device__ __forceinline__ float tile_elem(const float* reduced, int T, int rs, int cs) {
-  return reduced[T * 256 + (rs & 3) * 64 + (rs >> 2) * 16 + cs];
-}
 
 __global__ __launch_bounds__(256) void onf_wgrad_gather_kernel(const GatherArgs a) {
   const OnfGeom& g = a.geom;
@@ -1056,9 +959,10 @@ __global__ __launch_bounds__(256) void onf_wgrad_gather_kernel(const GatherArgs 
   auto h1_slot = [&](int h) { return xo ? h : hidden_slot(h, true); };
   auto h2_slot = [&](int h) { return xo ? h : hidden_slot(h, false); };
   const int ones_h1 = xo ? 101 : AUG_HIDDEN_SLOT, rho_row = xo ? 100 : AUG_HIDDEN_SLOT;
-  auto g1 = [&](int rs, int cs) { return tile_elem(a.reduced, (rs / 16) * NKT + cs / 16, rs % 16, cs % 16); };
-  auto g2 = [&](int rs, int cs) { return tile_elem(a.reduced, T_G2 + (rs / 16) * 7 + cs / 16, rs % 16, cs % 16); };
-  auto g3 = [&](int s, int c) { return tile_elem(a.reduced, T_G3 + s / 16, s % 16, c); };
+  auto tile_elem = [&](int T, int rs, int cs) { return a.reduced[tile_elem_offset(T, rs, cs)]; };
+  auto g1 = [&](int rs, int cs) { return tile_elem((rs / 16) * NKT + cs / 16, rs % 16, cs % 16); };
+  auto g2 = [&](int rs, int cs) { return tile_elem(T_G2 + (rs / 16) * 7 + cs / 16, rs % 16, cs % 16); };
+  auto g3 = [&](int s, int c) { return tile_elem(T_G3 + s / 16, s % 16, c); };
   if (o < g.n_params) {
     float v = 0.f;
     if (g.n_ang && o < g.off_ang_b + g.n_ang) {            // d/d angle bias = f_k * sum dz_k
@@ -1120,7 +1024,7 @@ struct WgradWs {  // float offsets into the workspace
   int win, ntiles, grid_cap;
 };
 
-static WgradWs carve_wgrad(const OnfGeom& g, long long P, int nkt) {
+static WgradWs carve_wgrad(long long P, int nkt) {
   WgradWs w;
   const long long hrow = HS;
   w.win = 16 * nkt;
@@ -1143,7 +1047,7 @@ static WgradWs carve_wgrad(const OnfGeom& g, long long P, int nkt) {
 
 // sized for the longer of the two row lengths (x32 order reserves a pad position for the ones feature: (fin + 16) / 16 tiles),
 // so the answer does not depend on the matrix path in force when the fit runs
-size_t wgrad_workspace_bytes(const OnfGeom& g, long long P) { return (size_t)carve_wgrad(g, P, (g.fin + 16) / 16).total * sizeof(float); }
+size_t wgrad_workspace_bytes(const OnfGeom& g, long long P) { return (size_t)carve_wgrad(P, (g.fin + 16) / 16).total * sizeof(float); }
 
 // pass 2 reads the factors in the order pass 1 wrote them: onf_wgrad_kernel behind the fp32 pass, onf_wgrad_split_kernel
 // behind a split pass (slot order after 16x16x32 tiles, x32 order after 32x32x16 tiles)
@@ -1176,7 +1080,7 @@ int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samp
   // pass 1 on the 32x32x16 kernel: factors in x32 order
   const bool xo = r.family == ONF_X32;
   const int nkt = r.nkt;
-  const WgradWs w = carve_wgrad(g, P, nkt);
+  const WgradWs w = carve_wgrad(P, nkt);
   const int aug = xo ? g.fin : find_aug_feature(g.fin, nkt);
   NFOPP_REQUIRE(aug >= 0, "no pad feature available for the ones column (fin = %d)", g.fin);
   OnfKernelArgs a = {};
@@ -1189,7 +1093,7 @@ int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samp
   if (rc) return rc;
 
   WgradArgs wa;
-  wa.geom = g; wa.params = params; wa.aug_feature = aug; wa.x32_order = xo ? 1 : 0;
+  wa.geom = g; wa.params = params; wa.aug_feature = aug;
   wa.ws = ws + w.h1; wa.P = P; wa.partial = ws + w.partial;   // arrays back to back from w.h1 (see carve_wgrad)
   int grid = 0;
   rc = launch_wgrad(r, wa, st, &grid);
@@ -1206,8 +1110,16 @@ int onf_train_grad_mfma(const OnfGeom& g, const float* params, const float* samp
     NFOPP_HIP(hipGetLastError());
   }
   GatherArgs ga;
+  ga.geom = g;
+  ga.nkt = nkt;
+  ga.aug_in_slot = xo ? aug : slot_layout_p(aug);
   ga.x32_order = xo ? 1 : 0;
-  ga.geom = g; ga.nkt = nkt; ga.aug_in_slot = xo ? aug : slot_layout_p(aug);   ga.params = params; ga.reduced = ws + w.reduced; ga.g4 = ws + w.g4; ga.loss_partial = ws + w.loss_sum; ga.grad = grad; ga.count = (float)P;
+  ga.params = params;
+  ga.reduced = ws + w.reduced;
+  ga.g4 = ws + w.g4;
+  ga.loss_partial = ws + w.loss_sum;
+  ga.grad = grad;
+  ga.count = (float)P;
   hipLaunchKernelGGL(onf_wgrad_gather_kernel, dim3((g.n_params + 255) / 256), dim3(256), 0, st, ga);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;

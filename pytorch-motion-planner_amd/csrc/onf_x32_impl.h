@@ -30,7 +30,7 @@
 // only known once the logit is complete -- and multiplies rho in where the factors are stored:  h1 | rho dh1 | rho de  by
 // feature / hidden-unit index ("x32 order": the accumulator layout gives every lane four consecutive positions per
 // register quad, i.e. one 16-byte store) plus the 48-byte record (u, 1, theta | rho | sign words of a2).  dW3[:100] =
-// sum_p rho_p relu(a2_p) is NOT accumulated here: it falls out of G2 in the gather kernel (WgradArgs::x32_order).
+// sum_p rho_p relu(a2_p) is NOT accumulated here: it falls out of G2 in the gather kernel (GatherArgs::x32_order).
 #include <string.h>
 
 #include <type_traits>
@@ -161,20 +161,11 @@ __global__ __launch_bounds__(256) void x32_prep_kernel(const OnfGeom geo, const 
   } else if (byte < O_ISA) {   // feature tables: sin(arg + q pi/2), q in revolutions (v_sin_f32 unit); FTD: + a quarter turn
     const bool deriv = byte >= O_FTD;
     const int f = (byte - (deriv ? O_FTD : O_FT)) >> 4;
-    float c0 = 0.f, c1 = 0.f, b = 0.f, q = 0.f;
-    if (f < geo.n_enc) {         // encoding_layer: W_e u + b_e (onf_model.py:39), cosine half: onf_model.py:41
-      c0 = P[geo.off_we + 2 * f]; c1 = P[geo.off_we + 2 * f + 1];
-      b = geo.off_be >= 0 ? P[geo.off_be + f] : 0.0f;
-      q = (geo.n_enc > geo.n_sin && f >= geo.n_sin) ? 0.25f : 0.0f;
-    } else if (f < geo.fin) {    // angle_encoder.py:16: (theta + b) * f
-      const int k = f - geo.n_enc;
-      c0 = P[geo.off_ang_f + k]; b = P[geo.off_ang_b + k];
-      q = k >= geo.ang_dim ? 0.25f : 0.0f;
-    } else if (f == geo.fin) {
-      q = 0.25f;                 // the ones feature (its value is forced to exactly 1 where it is evaluated)
-    }
-    if (deriv) q += 0.25f;
-    out = u32x4{__float_as_uint(c0), __float_as_uint(c1), __float_as_uint(b), __float_as_uint(q)};
+    // (decode_feature, csrc/onf_layout.h) the ones feature sits at position fin (its value is forced to exactly 1 where it is
+    // evaluated); an angle feature keeps its frequency where a spatial one keeps wx: arg = (theta + b) * c0
+    const FeatureEntry d = decode_feature(geo, P, f, geo.fin);
+    const float c0 = d.is_angle != 0.0f ? d.fr : d.wx, q = deriv ? d.qh + NFOPP_Q_UNIT : d.qh;
+    out = u32x4{__float_as_uint(c0), __float_as_uint(d.wy), __float_as_uint(d.b), __float_as_uint(q)};
   } else if (byte < O_W3A) {
     const int f0 = (byte - O_ISA) >> 2;
 #pragma unroll

@@ -308,7 +308,7 @@ def test_fit_gradient_every_feature_dimension_on_every_matrix_path_vs_oracle(use
 @pytest.mark.parametrize("use_cos,angle", [(True, True), (False, False)])
 def test_fit_pass1_factors_on_the_32x32_kernel_vs_oracle(use_cos, angle):
     """White box: what pass 1 of the fit leaves in the workspace on matrix path 1 -- the contract between csrc/onf_x32_impl.h's
-    training mode and csrc/onf_wgrad.hip (WgradArgs::x32_order): rows  h1 [P,112] | rho*dh1 [P,112] | rho*de [P,16*NKB] |
+    training mode and csrc/onf_wgrad.hip (onf_wgrad_split_kernel<NKT, XO>): rows  h1 [P,112] | rho*dh1 [P,112] | rho*de [P,16*NKB] |
     record [P,12]  indexed by hidden unit / input feature, ones unit 101, rho row 100, sign bit of a2[s] in word (s>>2)&3 at
     bit 4*(s>>4) + (s&3) -- against the oracle's intermediates (nerf_opt_planner.py:83-89 unrolled), for an even (F = 220) and
     an odd (F = 100) number of input blocks and a ragged sample count."""

@@ -293,10 +293,10 @@ def test_traj_steps_validates_its_arguments_without_a_gpu():
 
 
 def test_kernels_carry_no_build_switches():
-    """The library is built one way only: no HIP source or header tests a macro other than the device-compile pass and the
-    MFMA hazard precaution.  (A development switch left in the product could ship wrong results from one stray -D flag.)"""
+    """The library is built one way only: no HIP source or header tests a macro other than the device-compile pass.
+    (A development switch left in the product could ship wrong results from one stray -D flag.)"""
     import glob
-    allowed = {"__HIP_DEVICE_COMPILE__", "NFOPP_MFMA_GUARD"}
+    allowed = {"__HIP_DEVICE_COMPILE__"}
     csrc = os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
     assert files
