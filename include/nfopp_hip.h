@@ -129,6 +129,24 @@ int nfopp_reparametrize(int64_t batch, int32_t n_waypoints, int32_t dim, float* 
                         const float* start_dev, const float* goal_dev, float* lam_dev, float* cm_dev,
                         const float* u_dev, const uint8_t* active_dev, void* stream);
 
+/* Start / goal update of a batch in one launch: the receding-horizon tick of nfop/ros/goal_planner_adapter.py:44-53 calls
+ * update_start_point every 100 ms.  Replaces, per trajectory, the op sequence of constrained:178-194 (D = 3) / nerf:202-218
+ * (D = 2):  delta = torch.sum((traj[:, :2] - point[:, :2]) ** 2, dim=1);  min_index = torch.argmin(delta)
+ *           D = 3 only: min_index = min(min_index + 1, N)          (the reference's own asymmetry between its two classes)
+ *           which = 1: traj[min_index:] = goal = point;   which = 0: traj[:min_index] = start = point
+ *           reparametrize_trajectory()                             (bit for bit what nfopp_reparametrize computes)
+ * delta is rounded op by op (no fma) and argmin keeps torch's order: first minimal index, a NaN counts as smallest.
+ *   new_points_dev [B, dim]; the rows are also written to start_dev (which = 0) or goal_dev (which = 1)
+ *   moved_dev [B] uint8 or NULL (= all): rows with 0 keep traj, lam, cm and their endpoint bit for bit.  A row is updated
+ *       whether or not an early-stop `active` mask has retired it.
+ *   lam_dev / cm_dev: required for dim 3 (interpolated, never overwritten), ignored for dim 2
+ *   min_index_out_dev [B] int32 or NULL: the cut index min_index above (rows with moved = 0 are not written)
+ * LDS budget and the limit on N are those of nfopp_reparametrize.  Added within ABI 6 (no existing entry changed). */
+int nfopp_update_endpoints(int64_t batch, int32_t n_waypoints, int32_t dim, int32_t which,
+                           const float* new_points_dev, const uint8_t* moved_dev, float* traj_dev, float* start_dev,
+                           float* goal_dev, float* lam_dev, float* cm_dev, const float* u_dev,
+                           int32_t* min_index_out_dev, void* stream);
+
 /* n planner steps of a FROZEN-field batch from one call (ABI 6): the step loops that drive the reference's hot path --
  * nfop/ros/goal_planner_adapter.py:50-52 (`while time < timeout: planner.step()`), scripts/run_planner.py:76-77,
  * scripts/run_bench_mr.py:109-132 -- without a host round trip per step.  Per step k = 0 .. n_steps-1, on `stream`:

@@ -1,0 +1,129 @@
+// Start / goal update of a batch (HBM-bound; one workgroup per trajectory): the receding-horizon re-rooting of
+// nfop/constrained_nerf_opt_planner.py:178-194 (SE(2)) and nfop/nerf_opt_planner.py:202-218 (2-D) in ONE launch --
+//   delta = sum((traj[:, :2] - point[:, :2]) ** 2, dim=1);  min_index = argmin(delta) [+ 1, capped at N, for SE(2)]
+//   traj[min_index:] = goal   or   traj[:min_index] = start;   reparametrize_trajectory()
+// The trajectory is edited in the LDS image the reparametrisation (csrc/reparam.h) then works on, so the overwritten
+// rows never travel to HBM.
+//
+// argmin is INDEX work: a delta that differs in the last bit flips a near-tie and with it every output.  So each delta
+// is rn(rn(dx*dx) + rn(dy*dy)) -- torch's separate `** 2` and two-element `sum`, no contraction to fma -- and the
+// order is torch's: a NaN is smaller than every number, equal keys (and NaNs among themselves) go to the lower index.
+// The +1 of the SE(2) class and its absence in the 2-D class are the reference's own and are kept.
+#include <limits.h>
+
+#include "reparam.h"
+
+namespace nfopp {
+
+__device__ __forceinline__ float sq_dist_unfused(float dx, float dy) {
+#pragma clang fp contract(off)
+  const float xx = dx * dx;
+  const float yy = dy * dy;
+  return xx + yy;
+}
+
+// torch.argmin's order on (key, index) pairs (ATen LessOrNan): is pair a in front of pair b?
+__device__ __forceinline__ bool argmin_before(float ka, int ia, float kb, int ib) {
+  if (ka != ka) return (kb != kb) ? ia < ib : true;
+  return ka == kb ? ia < ib : ka < kb;
+}
+
+struct EndpointArgs {
+  int n, which;                 // which: 0 = start, 1 = goal
+  const float* points;          // [B, D] new endpoints
+  const unsigned char* moved;   // [B] or NULL (= all)
+  float* traj;
+  float* start;
+  float* goal;
+  float* lam;
+  float* cm;
+  const float* u;
+  int* min_index;               // [B] or NULL
+};
+
+template <int D>
+__global__ __launch_bounds__(RP_THREADS) void endpoint_update_kernel(const EndpointArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int N = a.n, tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  if (a.moved && !a.moved[b]) return;  // this trajectory keeps its endpoint: nothing of it is touched
+  const bool is_goal = a.which == 1;
+  const ReparamLds L = reparam_lds<D>(sm, N);
+  float* traj = a.traj + b * N * D;
+  float* lam = D == 3 ? a.lam + b * (N + 1) : nullptr;
+  float* cm = D == 3 ? a.cm + b * N : nullptr;
+  const float* point = a.points + b * D;
+  reparam_load<D>(L, N, tid, traj, is_goal ? a.start + b * D : point, is_goal ? point : a.goal + b * D, lam, cm);
+  if (tid < D) (is_goal ? a.goal : a.start)[b * D + tid] = point[tid];
+  __syncthreads();
+
+  // nearest waypoint: per-thread scan in rising index order, xor butterfly inside the wave, the four waves through LDS
+  float* Q = L.Q;
+  const float* P = Q + (is_goal ? (N + 1) * D : 0);   // the new endpoint's row of the image
+  const float px = P[0], py = P[1];
+  float key = __builtin_inff();
+  int idx = INT_MAX;                                 // a thread without waypoints loses to every waypoint, inf keys included
+  for (int w = tid; w < N; w += RP_THREADS) {
+    const float k = sq_dist_unfused(Q[(w + 1) * D] - px, Q[(w + 1) * D + 1] - py);
+    if (argmin_before(k, w, key, idx)) { key = k; idx = w; }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ok = __shfl_xor(key, o);
+    const int oi = __shfl_xor(idx, o);
+    if (argmin_before(ok, oi, key, idx)) { key = ok; idx = oi; }
+  }
+  constexpr int WAVES = RP_THREADS / 64;
+  float* wkey = L.red;                               // `red` is idle until the reparametrisation's sum
+  int* widx = reinterpret_cast<int*>(L.red + WAVES);
+  if ((tid & 63) == 0) { wkey[tid >> 6] = key; widx[tid >> 6] = idx; }
+  __syncthreads();
+  key = wkey[0]; idx = widx[0];
+#pragma unroll
+  for (int w2 = 1; w2 < WAVES; ++w2)
+    if (argmin_before(wkey[w2], widx[w2], key, idx)) { key = wkey[w2]; idx = widx[w2]; }
+  const int m = D == 3 ? min(idx + 1, N) : idx;       // constrained:182,190 vs nerf:206,214
+  if (tid == 0 && a.min_index) a.min_index[b] = m;
+
+  // traj[m:] = goal / traj[:m] = start (all D columns), on the image; the multipliers are interpolated, not overwritten
+  float p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = P[k];
+  for (int w = tid; w < N; w += RP_THREADS) {
+    if (is_goal ? w >= m : w < m) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) Q[(w + 1) * D + k] = p[k];
+    }
+  }
+  __syncthreads();
+  reparam_from_lds<D>(L, N, tid, traj, lam, cm, a.u);
+}
+
+}  // namespace nfopp
+
+using namespace nfopp;
+
+extern "C" int nfopp_update_endpoints(int64_t batch, int32_t n_waypoints, int32_t dim, int32_t which,
+                                      const float* new_points_dev, const uint8_t* moved_dev, float* traj_dev,
+                                      float* start_dev, float* goal_dev, float* lam_dev, float* cm_dev, const float* u_dev,
+                                      int32_t* min_index_out_dev, void* stream) {
+  NFOPP_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
+  NFOPP_REQUIRE(which == 0 || which == 1, "which must be 0 (start) or 1 (goal)");
+  NFOPP_REQUIRE(batch >= 0 && n_waypoints >= 2, "need batch >= 0 and at least 2 waypoints");
+  NFOPP_REQUIRE(batch <= 0x7fffffffLL, "batch too large for one launch");
+  if (batch == 0) return NFOPP_OK;
+  NFOPP_REQUIRE(new_points_dev && traj_dev && start_dev && goal_dev && u_dev, "null device pointer");
+  NFOPP_REQUIRE(dim == 2 || (lam_dev && cm_dev), "the SE(2) endpoint update needs the multiplier arrays");
+  const size_t lds = reparam_lds_bytes(n_waypoints, dim);
+  NFOPP_REQUIRE(lds <= 160 * 1024, "trajectory too long for one workgroup's LDS (%zu bytes)", lds);
+  EndpointArgs a;
+  a.n = n_waypoints; a.which = which; a.points = new_points_dev; a.moved = moved_dev; a.traj = traj_dev;
+  a.start = start_dev; a.goal = goal_dev; a.lam = lam_dev; a.cm = cm_dev; a.u = u_dev; a.min_index = min_index_out_dev;
+  auto kern = dim == 3 ? endpoint_update_kernel<3> : endpoint_update_kernel<2>;
+  if (lds > 64 * 1024)
+    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(RP_THREADS), lds, (hipStream_t)stream, a);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}

@@ -248,6 +248,46 @@ void reparametrize(Tensor traj, const Tensor& start, const Tensor& goal, const O
                                    opt_ptr<uint8_t>(active), stream_of(traj)));
 }
 
+// start (which = 0) / goal (which = 1) update of a batch (constrained:178-194 / nerf:202-218), in place: nearest waypoint,
+// cut, endpoint write and reparametrisation from one launch.  moved [B] uint8 or None (= all); min_index [B] int32 or None.
+void update_endpoints(Tensor traj, Tensor start, Tensor goal, const OptTensor& lam, const OptTensor& cm, const Tensor& u,
+                      const Tensor& points, int64_t which, const OptTensor& moved, const OptTensor& min_index) {
+  check_tensor(traj, "traj");
+  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
+  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
+  TORCH_CHECK(which == 0 || which == 1, "nfopp: which must be 0 (start) or 1 (goal)");
+  check_tensor(start, "start"); check_tensor(goal, "goal"); check_tensor(u, "u"); check_tensor(points, "points");
+  same_device(traj, start, "start"); same_device(traj, goal, "goal"); same_device(traj, u, "u");
+  same_device(traj, points, "points");
+  TORCH_CHECK(start.numel() == B * D && goal.numel() == B * D && points.numel() == B * D,
+              "nfopp: start / goal / points must be [B, D]");
+  TORCH_CHECK(u.numel() == N, "nfopp: u must be torch.linspace(0, 1, N + 2)[1:-1]");
+  if (D == 3) {
+    TORCH_CHECK(lam.has_value() && cm.has_value(), "nfopp: the SE(2) endpoint update needs lam [B, N+1] and cm [B, N]");
+    check_tensor(*lam, "lam"); check_tensor(*cm, "cm");
+    same_device(traj, *lam, "lam"); same_device(traj, *cm, "cm");
+    TORCH_CHECK(lam->numel() == B * (N + 1) && cm->numel() == B * N, "nfopp: lam must be [B, N+1], cm [B, N]");
+  } else {
+    TORCH_CHECK(D == 2, "nfopp: trajectory dim must be 2 or 3");
+    TORCH_CHECK(!lam.has_value() && !cm.has_value(), "nfopp: the 2-D endpoint update takes no multiplier tensors");
+  }
+  if (moved.has_value()) {
+    check_tensor(*moved, "moved", at::kByte);
+    same_device(traj, *moved, "moved");
+    TORCH_CHECK(moved->numel() == B, "nfopp: moved must be [B] uint8");
+  }
+  if (min_index.has_value()) {
+    check_tensor(*min_index, "min_index", at::kInt);
+    same_device(traj, *min_index, "min_index");
+    TORCH_CHECK(min_index->numel() == B, "nfopp: min_index must be [B] int32");
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  check_status(nfopp_update_endpoints(B, (int32_t)N, (int32_t)D, (int32_t)which, points.data_ptr<float>(),
+                                      opt_ptr<uint8_t>(moved), traj.data_ptr<float>(), start.data_ptr<float>(),
+                                      goal.data_ptr<float>(), opt_ptr<float>(lam), opt_ptr<float>(cm), u.data_ptr<float>(),
+                                      opt_ptr<int32_t>(min_index), stream_of(traj)));
+}
+
 // grid-search (A*) seeding of a batch (astar_trajectory_initializer.py:15-48): traj [B, N, D] in place, returns status [B].
 // occupancy uint8 [rows, cols]; start_cells / goal_cells int32 [B, 2] (row, col); unique_goal_cells int32 [G, 2] and
 // field_index int32 [B] = the de-duplicated goal cells and each problem's entry in them (nfopp/grid_search.py builds them).
@@ -360,6 +400,8 @@ TORCH_LIBRARY(nfopp, lib) {
       "Tensor u, float[] hyper, float adam_lr, float adam_beta1, float adam_beta2, int adam_steps_done, int step_count, "
       "int reparam_freq, int n_steps, Tensor(h!)? terms, Tensor? active, Tensor(i!)? live_ws) -> ()");
   lib.def("reparametrize(Tensor(a!) traj, Tensor start, Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor u, Tensor? active) -> ()");
+  lib.def("update_endpoints(Tensor(a!) traj, Tensor(b!) start, Tensor(c!) goal, Tensor(d!)? lam, Tensor(e!)? cm, Tensor u, "
+          "Tensor points, int which, Tensor? moved, Tensor(f!)? min_index) -> ()");
   lib.def("onf_train_grad(Tensor params, Tensor samples, Tensor labels, float inv_count, float mean, float sigma, bool use_cos, "
           "bool has_bias, int angle_dim) -> Tensor");
   lib.def("adam_step(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float beta2, float omb1, float omb2, float eps, "
@@ -380,6 +422,7 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("traj_step", &traj_step);
   lib.impl("traj_steps", &traj_steps);
   lib.impl("reparametrize", &reparametrize);
+  lib.impl("update_endpoints", &update_endpoints);
   lib.impl("onf_train_grad", &onf_train_grad);
   lib.impl("adam_step", &adam_step);
   lib.impl("onf_train_step", &onf_train_step);

@@ -70,6 +70,8 @@ _SIGNATURES = {
     "nfopp_traj_steps": (ctypes.c_int, [ctypes.POINTER(OnfConfigC), _P, ctypes.POINTER(TrajHyperC), ctypes.POINTER(TrajBuffersC),
                                         ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P, _P]),
     "nfopp_reparametrize": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nfopp_update_endpoints": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P,
+                                              _P, _P, _P, _P, _P]),
     "nfopp_path_interpolate": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               _P, _P, _P]),
     "nfopp_path_select_best": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

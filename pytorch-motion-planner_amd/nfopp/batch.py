@@ -234,6 +234,55 @@ class BatchPlanner(object):
             self.engine.reparametrize()
         self.step_count += 1
 
+    # ---- receding-horizon replanning (nfop/ros/goal_planner_adapter.py:44-53: update_start_point -> step()s -> get_path) ----
+    def _update_endpoints(self, which, points, moved):
+        """One nfopp_update_endpoints launch plus the bookkeeping the new endpoints invalidate.  `step_count` goes back to
+        0 as in the reference (the next step fits, if learning is on, and reparametrises); the Adam moments and `adam_step`
+        stay, as the reference keeps its optimiser state.  Nothing here synchronises when `points` / `moved` are device tensors."""
+        eng = self.engine
+        if moved is not None and not isinstance(moved, torch.Tensor):
+            moved = torch.from_numpy(np.ascontiguousarray(moved).astype(np.uint8)).to(eng.device)
+        eng.update_endpoints(which, points, moved)
+        # the best path on record joined the old endpoints, and a retired trajectory has to move again: masked device ops
+        if eng.active is not None:
+            if moved is None:
+                eng.active.fill_(1)
+            else:
+                eng.active.masked_fill_(moved.view(-1) != 0, 1)
+        if hasattr(self, "best_length"):
+            if moved is None:
+                self.best_length.fill_(float("inf"))
+            else:
+                self.best_length.masked_fill_(moved.view(-1) != 0, float("inf"))
+        self.step_count = 0
+
+    def update_start_points(self, points, moved=None):
+        """Batched `update_start_point` (constrained:187-194 / nerf:210-216): every trajectory -- or those with
+        `moved[b] != 0` -- is cut back to its new start [B, D] and reparametrised; the others are left bit for bit."""
+        self._update_endpoints(0, points, moved)
+
+    def update_goal_points(self, points, moved=None):
+        """Batched `update_goal_point` (constrained:178-185 / nerf:202-208)."""
+        self._update_endpoints(1, points, moved)
+
+    def set_boundaries(self, boundaries):
+        """`set_boundaries` (nerf:218-220): new sampling / boundary-loss box, `step_count` back to 0.  The hyper block is
+        rebuilt as `init()` builds it, so the kernels' cached scalar block is formed afresh."""
+        h = self.engine.hyper
+        self.engine.hyper = TrajectoryHyper(h.collision_weight, h.angle_weight, h.constraint_deltas_weight, h.multipliers_lr,
+                                            h.collision_multipliers_lr, h.boundary_weight, h.collision_beta,
+                                            h.direction_delta_weight, h.lr, h.betas, h.eps, tuple(boundaries))
+        self.step_count = 0
+
+    def replan(self, starts=None, goals=None, moved=None, n=1):
+        """One tick of the receding-horizon loop: endpoint update(s), then `step(n=n)`.  With a frozen field and
+        device-tensor inputs the whole tick is enqueued without a host synchronisation."""
+        if starts is not None:
+            self.update_start_points(starts, moved)
+        if goals is not None:
+            self.update_goal_points(goals, moved)
+        self.step(n=n)
+
     def get_paths(self):
         return self.engine.full_trajectory().detach().cpu().numpy()
 

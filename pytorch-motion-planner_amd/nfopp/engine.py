@@ -236,6 +236,28 @@ class TrajectoryEngine(object):
                                            _lib.ptr(self.goal), _lib.ptr(self.lam), _lib.ptr(self.cm),
                                            _lib.ptr(self.u), _lib.ptr(self.active, torch.uint8), _lib.stream_ptr()))
 
+    def update_endpoints(self, which, points, moved=None, min_index_out=None):
+        """Moves the start (`which` = 0 / "start") or goal (1 / "goal") of the batch and re-roots the trajectories on it
+        (constrained:178-194 / nerf:202-218 per trajectory) from ONE launch: nearest waypoint, cut, endpoint write,
+        reparametrisation.  `points` [B, D]: a numpy array (one upload) or an fp32 device tensor (no copy, no sync).
+        `moved` uint8 [B] device mask or None (= all): rows with 0 stay bit for bit as they are; a moved row is updated
+        whether or not `active` has retired it.  `min_index_out` int32 [B] device tensor or None: the cut indices."""
+        which = {"start": 0, "goal": 1}.get(which, which)
+        if which not in (0, 1):
+            raise ValueError("which must be 0 / 'start' or 1 / 'goal'")
+        if not isinstance(points, torch.Tensor):
+            points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(self.device)
+        if points.numel() != self.B * self.D:
+            raise ValueError("points must be [%d, %d]" % (self.B, self.D))
+        if moved is not None and moved.numel() != self.B:
+            raise ValueError("moved must be a uint8 mask of %d rows" % self.B)
+        if min_index_out is not None and min_index_out.numel() != self.B:
+            raise ValueError("min_index_out must hold %d int32" % self.B)
+        P = _lib.ptr
+        _lib.check(_lib.load().nfopp_update_endpoints(self.B, self.N, self.D, which, P(points), P(moved, torch.uint8),
+                                                      P(self.traj), P(self.start), P(self.goal), P(self.lam), P(self.cm),
+                                                      P(self.u), P(min_index_out, torch.int32), _lib.stream_ptr()))
+
     # ---- helpers --------------------------------------------------------------------------------------------------
     def set_endpoints(self, start, goal):
         self.start.copy_(torch.as_tensor(np.asarray(start, np.float32)).reshape(self.B, self.D))

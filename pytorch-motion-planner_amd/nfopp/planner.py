@@ -291,25 +291,14 @@ class NERFOptPlanner(ContinuousPlanner):
             positions = self._uniform_poses(self._init_collision_points)
             self._optimize_collision_model(positions)
 
-    def _endpoint_update(self, point, is_goal):
-        eng = self._engine
-        tr = eng.traj.view(eng.N, eng.D)
-        (eng.goal if is_goal else eng.start).copy_(torch.tensor(np.asarray(point, np.float32))[None])
-        ref = eng.goal if is_goal else eng.start
-        return tr, ref
-
     def update_goal_point(self, goal_point):
-        tr, ref = self._endpoint_update(goal_point, True)
-        min_index = int(torch.argmin(torch.sum((tr - ref) ** 2, dim=1)))
-        tr[min_index:] = ref
-        self.reparametrize_trajectory()
+        """nerf:202-208 / constrained:178-185, one launch and no host sync (engine.update_endpoints)."""
+        self._engine.update_endpoints(1, np.asarray(goal_point, np.float32)[None])
         self._step_count = 0
 
     def update_start_point(self, start_point):
-        tr, ref = self._endpoint_update(start_point, False)
-        min_index = int(torch.argmin(torch.sum((tr - ref) ** 2, dim=1)))
-        tr[:min_index] = ref
-        self.reparametrize_trajectory()
+        """nerf:210-216 / constrained:187-194."""
+        self._engine.update_endpoints(0, np.asarray(start_point, np.float32)[None])
         self._step_count = 0
 
     def set_boundaries(self, boundaries):
@@ -386,19 +375,3 @@ class ConstrainedNERFOptPlanner(NERFOptPlanner):
         if self._rng == "device":
             return None
         return torch.rand(self._trajectory.shape[0] - 1, 1)[:, 0]
-
-    def _endpoint_min_index(self, tr, ref):
-        delta = torch.sum((tr[:, :2] - ref[:, :2]) ** 2, dim=1)
-        return min(int(torch.argmin(delta)) + 1, tr.shape[0])
-
-    def update_goal_point(self, goal_point):
-        tr, ref = self._endpoint_update(goal_point, True)
-        tr[self._endpoint_min_index(tr, ref):] = ref
-        self.reparametrize_trajectory()
-        self._step_count = 0
-
-    def update_start_point(self, start_point):
-        tr, ref = self._endpoint_update(start_point, False)
-        tr[:self._endpoint_min_index(tr, ref)] = ref
-        self.reparametrize_trajectory()
-        self._step_count = 0
