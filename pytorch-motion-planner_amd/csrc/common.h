@@ -56,6 +56,24 @@ int launch_persistent(size_t lds, int threads, long long n_chunks, hipStream_t s
   return NFOPP_OK;
 }
 
+// Launch of KERNEL(args) on `grid` workgroups of `threads` with `lds` bytes of dynamic LDS that follow the problem size
+// (trajectory length, candidate count): the 160 KiB a gfx950 workgroup can hold (`what` opens the message of a request
+// beyond it), the attribute that lifts HIP's 64 KiB default, the launch and its status.  The attribute is set in front of
+// every launch above 64 KiB with that launch's own size.  ensure_dynamic_lds (above) sets it once per device instead and
+// stays with launch_persistent and the grid search: their kernels have ONE LDS size each, so a flag is enough there and
+// saves the call; here a flag would pin the first -- possibly smaller -- size.
+template <class Args>
+int launch_dynamic_lds(void (*kernel)(Args), long long grid, int threads, size_t lds, void* stream, const Args& args,
+                       const char* what) {
+  NFOPP_REQUIRE(lds <= 160 * 1024, "%s for one workgroup's LDS (%zu bytes)", what, lds);
+  if (lds > 64 * 1024)
+    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, (hipStream_t)stream, args);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}
+
 // A scratch device buffer per (device, stream), for kernels that rewrite their scratch on the launch stream in front of
 // every launch: launches of one stream are ordered by the stream itself, and two streams (two planners with different
 // fields) never share a buffer.  16 buffers per device -- a handful of streams is the realistic case, though PyTorch's

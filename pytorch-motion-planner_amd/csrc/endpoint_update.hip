@@ -114,16 +114,9 @@ extern "C" int nfopp_update_endpoints(int64_t batch, int32_t n_waypoints, int32_
   if (batch == 0) return NFOPP_OK;
   NFOPP_REQUIRE(new_points_dev && traj_dev && start_dev && goal_dev && u_dev, "null device pointer");
   NFOPP_REQUIRE(dim == 2 || (lam_dev && cm_dev), "the SE(2) endpoint update needs the multiplier arrays");
-  const size_t lds = reparam_lds_bytes(n_waypoints, dim);
-  NFOPP_REQUIRE(lds <= 160 * 1024, "trajectory too long for one workgroup's LDS (%zu bytes)", lds);
   EndpointArgs a;
   a.n = n_waypoints; a.which = which; a.points = new_points_dev; a.moved = moved_dev; a.traj = traj_dev;
   a.start = start_dev; a.goal = goal_dev; a.lam = lam_dev; a.cm = cm_dev; a.u = u_dev; a.min_index = min_index_out_dev;
-  auto kern = dim == 3 ? endpoint_update_kernel<3> : endpoint_update_kernel<2>;
-  if (lds > 64 * 1024)
-    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(RP_THREADS), lds, (hipStream_t)stream, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_dynamic_lds(dim == 3 ? endpoint_update_kernel<3> : endpoint_update_kernel<2>, batch, RP_THREADS,
+                            reparam_lds_bytes(n_waypoints, dim), stream, a, "trajectory too long");
 }

@@ -224,10 +224,5 @@ extern "C" int nfopp_path_postprocess(const float* path_dev, int64_t batch, int3
   a.out = out_dev; a.count = count_dev;
   // doubles: knots n+3, coefficients 3n, parameter n, pivots n, super-diagonal n; floats: poses 3n, lengths n
   const size_t lds = (size_t)(7 * n_points + 3) * 8 + (size_t)(4 * n_points) * 4;
-  if (lds > 64 * 1024)
-    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(path_post_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(path_post_kernel, dim3((unsigned)batch), dim3(PP_THREADS), lds, (hipStream_t)stream, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_dynamic_lds(path_post_kernel, batch, PP_THREADS, lds, stream, a, "path too long");   // 1026 poses: 72 KiB
 }

@@ -47,13 +47,6 @@ extern "C" int nfopp_reparametrize(int64_t batch, int32_t n_waypoints, int32_t d
   ReparamArgs a;
   a.n = n_waypoints; a.dim = dim; a.traj = traj_dev; a.start = start_dev; a.goal = goal_dev;
   a.lam = lam_dev; a.cm = cm_dev; a.u = u_dev; a.active = active_dev;
-  const size_t lds = reparam_lds_bytes(n_waypoints, dim);
-  NFOPP_REQUIRE(lds <= 160 * 1024, "trajectory too long for one workgroup's LDS (%zu bytes)", lds);
-  auto kern = dim == 3 ? reparam_kernel<3> : reparam_kernel<2>;
-  if (lds > 64 * 1024)
-    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(RP_THREADS), lds, (hipStream_t)stream, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_dynamic_lds(dim == 3 ? reparam_kernel<3> : reparam_kernel<2>, batch, RP_THREADS,
+                            reparam_lds_bytes(n_waypoints, dim), stream, a, "trajectory too long");
 }

@@ -360,10 +360,6 @@ extern "C" int nfopp_resample_pool(int64_t batch, int32_t n_candidates, int32_t 
   int n2 = 1;
   while (n2 < n_candidates) n2 <<= 1;
   const size_t lds = (size_t)n2 * 8;
-  auto kern = dim == 3 ? resample_pool_kernel<3> : resample_pool_kernel<2>;
-  if (lds > 64 * 1024)
-    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(SM_THREADS), lds, (hipStream_t)stream, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_dynamic_lds(dim == 3 ? resample_pool_kernel<3> : resample_pool_kernel<2>, batch, SM_THREADS, lds, stream, a,
+                            "too many candidates");   // 16384 candidates: 128 KiB
 }

@@ -88,6 +88,85 @@ Tensor onf_logits(const Tensor& params, const Tensor& points, double mean, doubl
   return out.narrow(1, 0, 1);
 }
 
+// x belongs to the batch of `traj`: fp32 (or `dtype`), contiguous, on traj's device, of exactly this shape
+void need(const Tensor& traj, const Tensor& x, const char* name, at::IntArrayRef shape, at::ScalarType dtype = at::kFloat) {
+  check_tensor(x, name, dtype);
+  same_device(traj, x, name);
+  TORCH_CHECK(x.sizes() == shape, "nfopp: ", name, " must have shape ", shape, ", got ", x.sizes());
+}
+
+// The state tensors of a batch of B trajectories, stated once for every op that takes them: traj [B, N, D], start / goal
+// [B, D], the SE(2) multipliers lam [B, N+1] / cm [B, N] (D == 3: both; D == 2: neither), the reparametrisation grid u [N]
+// and a uint8 row mask [B] with the int32 live-list workspace (>= B + 1) the ONF kernel needs beside it.
+struct Batch {
+  int64_t B = 0, N = 0, D = 0;
+  float *traj = nullptr, *start = nullptr, *goal = nullptr, *lam = nullptr, *cm = nullptr, *u = nullptr;
+  uint8_t* mask = nullptr;
+  int32_t* live_ws = nullptr;
+};
+
+// traj, start and goal alone (the grid search seeds a batch that has no multipliers yet)
+Batch batch_endpoints(const Tensor& traj, const Tensor& start, const Tensor& goal) {
+  check_tensor(traj, "traj");
+  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
+  Batch b;
+  b.B = traj.size(0); b.N = traj.size(1); b.D = traj.size(2);
+  TORCH_CHECK(b.D == 2 || b.D == 3, "nfopp: trajectory dim must be 2 or 3");
+  need(traj, start, "start", {b.B, b.D}); need(traj, goal, "goal", {b.B, b.D});
+  b.traj = traj.data_ptr<float>(); b.start = start.data_ptr<float>(); b.goal = goal.data_ptr<float>();
+  return b;
+}
+
+// `u`, `mask` and `live_ws` are null for an op that has no such argument; `mask_name` is the op's name for its row mask
+Batch batch_state(const Tensor& traj, const Tensor& start, const Tensor& goal, const OptTensor& lam, const OptTensor& cm,
+                  const Tensor* u, const OptTensor* mask, const char* mask_name, const OptTensor* live_ws) {
+  Batch b = batch_endpoints(traj, start, goal);
+  TORCH_CHECK(b.N >= 2, "nfopp: need at least 2 waypoints");
+  if (b.D == 3) {
+    TORCH_CHECK(lam.has_value() && cm.has_value(), "nfopp: an SE(2) batch needs the multiplier tensors lam [B, N+1], cm [B, N]");
+    need(traj, *lam, "lam", {b.B, b.N + 1}); need(traj, *cm, "cm", {b.B, b.N});
+    b.lam = lam->data_ptr<float>(); b.cm = cm->data_ptr<float>();
+  } else {
+    // a 2-D batch has no multipliers: a tensor passed here would reach the kernel unvalidated
+    TORCH_CHECK(!lam.has_value() && !cm.has_value(), "nfopp: a 2-D batch takes no multiplier tensors (lam / cm must be None)");
+  }
+  if (u) {
+    need(traj, *u, "u", {b.N});
+    b.u = u->data_ptr<float>();
+  }
+  const bool masked = mask && mask->has_value();
+  if (masked) {
+    need(traj, **mask, mask_name, {b.B}, at::kByte);
+    b.mask = (*mask)->data_ptr<uint8_t>();
+  }
+  if (live_ws && masked) {
+    TORCH_CHECK(live_ws->has_value(), "nfopp: an active mask needs the live-list workspace (B + 1 int32)");
+    check_tensor(**live_ws, "live_ws", at::kInt);
+    same_device(traj, **live_ws, "live_ws");
+    TORCH_CHECK((*live_ws)->numel() >= b.B + 1, "nfopp: live_ws must hold B + 1 int32");
+    b.live_ws = (*live_ws)->data_ptr<int32_t>();
+  } else if (live_ws) {
+    TORCH_CHECK(!live_ws->has_value(), "nfopp: live_ws without an active mask");
+  }
+  return b;
+}
+
+// what traj_step and traj_steps check beyond the batch: the ONF, the Adam moments, the per-step scratch, the band
+Batch step_state(const Tensor& params, const nfopp_onf_config& c, int64_t angle_dim, const Tensor& traj, const Tensor& start,
+                 const Tensor& goal, const OptTensor& lam, const OptTensor& cm, const Tensor& adam_m, const Tensor& adam_v,
+                 const Tensor& t, const Tensor& onf_out, const Tensor& hinv_band, int64_t half_width, const Tensor* u,
+                 const OptTensor& terms, const OptTensor& active, const OptTensor& live_ws) {
+  check_params(params, c);
+  const Batch b = batch_state(traj, start, goal, lam, cm, u, &active, "active", &live_ws);
+  TORCH_CHECK(b.D == (angle_dim > 0 ? 3 : 2), "nfopp: trajectory dim ", b.D, " does not match the ONF point dim");
+  same_device(traj, params, "params");
+  need(traj, adam_m, "adam_m", {b.B, b.N, b.D}); need(traj, adam_v, "adam_v", {b.B, b.N, b.D});
+  need(traj, t, "t", {b.B, b.N - 1}); need(traj, onf_out, "onf_out", {b.B, b.N - 1, 4});
+  need(traj, hinv_band, "hinv_band", {2 * half_width + 1, b.N});
+  if (terms.has_value()) need(traj, *terms, "terms", {b.B, NFOPP_NUM_TERMS});
+  return b;
+}
+
 // one `_optimize_trajectory` for a batch: collision sampling + ONF (nfopp_traj_collision_eval), then losses, H^-1 g, Adam and
 // the multiplier ascent (nfopp_traj_update).  State tensors are updated in place.
 void traj_step(const Tensor& params, double mean, double sigma, bool use_cos, bool has_bias, int64_t angle_dim, Tensor traj,
@@ -96,56 +175,18 @@ void traj_step(const Tensor& params, double mean, double sigma, bool use_cos, bo
                const Tensor& hinv_band, int64_t half_width, int64_t interior_lo, int64_t interior_hi, at::ArrayRef<double> hyper,
                const OptTensor& terms, const OptTensor& active, const OptTensor& live_ws) {
   const nfopp_onf_config c = make_cfg(mean, sigma, use_cos, has_bias, angle_dim);
-  check_params(params, c);
-  check_tensor(traj, "traj");
-  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
-  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
-  TORCH_CHECK(D == (angle_dim > 0 ? 3 : 2), "nfopp: trajectory dim ", D, " does not match the ONF point dim");
-  TORCH_CHECK(N >= 2, "nfopp: need at least 2 waypoints");
-  auto need = [&](const Tensor& x, const char* name, at::IntArrayRef shape) {
-    check_tensor(x, name);
-    same_device(traj, x, name);
-    TORCH_CHECK(x.sizes() == shape, "nfopp: ", name, " must have shape ", shape, ", got ", x.sizes());
-  };
-  same_device(traj, params, "params");
-  need(start, "start", {B, D}); need(goal, "goal", {B, D});
-  need(adam_m, "adam_m", {B, N, D}); need(adam_v, "adam_v", {B, N, D});
-  need(t, "t", {B, N - 1}); need(onf_out, "onf_out", {B, N - 1, 4});
-  check_tensor(hinv_band, "hinv_band");
-  same_device(traj, hinv_band, "hinv_band");
-  TORCH_CHECK(hinv_band.dim() == 2 && hinv_band.size(0) == 2 * half_width + 1 && hinv_band.size(1) == N,
-              "nfopp: hinv_band must be [2 * half_width + 1, N]");
-  if (D == 3) {
-    TORCH_CHECK(lam.has_value() && cm.has_value(), "nfopp: the SE(2) step needs the multiplier tensors lam [B, N+1], cm [B, N]");
-    need(*lam, "lam", {B, N + 1}); need(*cm, "cm", {B, N});
-  } else {
-    // the 2-D step has no multipliers: a tensor passed here would reach the kernel unvalidated
-    TORCH_CHECK(!lam.has_value() && !cm.has_value(), "nfopp: the 2-D step takes no multiplier tensors (lam / cm must be None)");
-  }
-  if (terms.has_value()) need(*terms, "terms", {B, NFOPP_NUM_TERMS});
-  if (active.has_value()) {
-    check_tensor(*active, "active", at::kByte);
-    same_device(traj, *active, "active");
-    TORCH_CHECK(active->numel() == B, "nfopp: active must be [B] uint8");
-    TORCH_CHECK(live_ws.has_value(), "nfopp: an active mask needs the live-list workspace (B + 1 int32)");
-    check_tensor(*live_ws, "live_ws", at::kInt);
-    same_device(traj, *live_ws, "live_ws");
-    TORCH_CHECK(live_ws->numel() >= B + 1, "nfopp: live_ws must hold B + 1 int32");
-  } else {
-    TORCH_CHECK(!live_ws.has_value(), "nfopp: live_ws without an active mask");
-  }
+  const Batch b = step_state(params, c, angle_dim, traj, start, goal, lam, cm, adam_m, adam_v, t, onf_out, hinv_band, half_width,
+                             nullptr, terms, active, live_ws);
   const nfopp_traj_hyper hp = make_hyper(hyper);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
   void* st = stream_of(traj);
-  check_status(nfopp_traj_collision_eval(&c, params.data_ptr<float>(), traj.data_ptr<float>(), B, (int32_t)N, (int32_t)D,
+  check_status(nfopp_traj_collision_eval(&c, params.data_ptr<float>(), b.traj, b.B, (int32_t)b.N, (int32_t)b.D,
                                          t.data_ptr<float>(), (int32_t)t_mode, (uint64_t)seed, (uint64_t)rng_offset,
-                                         traj_index_offset, onf_out.data_ptr<float>(), opt_ptr<uint8_t>(active),
-                                         opt_ptr<int32_t>(live_ws), st));
-  check_status(nfopp_traj_update(&hp, B, (int32_t)N, (int32_t)D, traj.data_ptr<float>(), start.data_ptr<float>(),
-                                 goal.data_ptr<float>(), opt_ptr<float>(lam), opt_ptr<float>(cm), adam_m.data_ptr<float>(),
-                                 adam_v.data_ptr<float>(), t.data_ptr<float>(), onf_out.data_ptr<float>(),
-                                 hinv_band.data_ptr<float>(), (int32_t)half_width, (int32_t)interior_lo, (int32_t)interior_hi,
-                                 opt_ptr<float>(terms), opt_ptr<uint8_t>(active), st));
+                                         traj_index_offset, onf_out.data_ptr<float>(), b.mask, b.live_ws, st));
+  check_status(nfopp_traj_update(&hp, b.B, (int32_t)b.N, (int32_t)b.D, b.traj, b.start, b.goal, b.lam, b.cm,
+                                 adam_m.data_ptr<float>(), adam_v.data_ptr<float>(), t.data_ptr<float>(),
+                                 onf_out.data_ptr<float>(), hinv_band.data_ptr<float>(), (int32_t)half_width,
+                                 (int32_t)interior_lo, (int32_t)interior_hi, opt_ptr<float>(terms), b.mask, st));
 }
 
 // n frozen-field planner steps from one call (nfopp_traj_steps, ABI 6): the callers' step loops
@@ -159,55 +200,15 @@ void traj_steps(const Tensor& params, double mean, double sigma, bool use_cos, b
                 int64_t step_count, int64_t reparam_freq, int64_t n_steps, const OptTensor& terms, const OptTensor& active,
                 const OptTensor& live_ws) {
   const nfopp_onf_config c = make_cfg(mean, sigma, use_cos, has_bias, angle_dim);
-  check_params(params, c);
-  check_tensor(traj, "traj");
-  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
-  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
-  TORCH_CHECK(D == (angle_dim > 0 ? 3 : 2), "nfopp: trajectory dim ", D, " does not match the ONF point dim");
-  TORCH_CHECK(N >= 2, "nfopp: need at least 2 waypoints");
+  const Batch b = step_state(params, c, angle_dim, traj, start, goal, lam, cm, adam_m, adam_v, t, onf_out, hinv_band, half_width,
+                             &u, terms, active, live_ws);
   TORCH_CHECK(n_steps >= 0 && reparam_freq >= 1 && adam_steps_done >= 0 && step_count >= 0, "nfopp: bad step schedule");
-  auto need = [&](const Tensor& x, const char* name, at::IntArrayRef shape) {
-    check_tensor(x, name);
-    same_device(traj, x, name);
-    TORCH_CHECK(x.sizes() == shape, "nfopp: ", name, " must have shape ", shape, ", got ", x.sizes());
-  };
-  same_device(traj, params, "params");
-  need(start, "start", {B, D}); need(goal, "goal", {B, D});
-  need(adam_m, "adam_m", {B, N, D}); need(adam_v, "adam_v", {B, N, D});
-  need(t, "t", {B, N - 1}); need(onf_out, "onf_out", {B, N - 1, 4}); need(u, "u", {N});
-  check_tensor(hinv_band, "hinv_band");
-  same_device(traj, hinv_band, "hinv_band");
-  TORCH_CHECK(hinv_band.dim() == 2 && hinv_band.size(0) == 2 * half_width + 1 && hinv_band.size(1) == N,
-              "nfopp: hinv_band must be [2 * half_width + 1, N]");
-  if (D == 3) {
-    TORCH_CHECK(lam.has_value() && cm.has_value(), "nfopp: the SE(2) step needs the multiplier tensors lam [B, N+1], cm [B, N]");
-    need(*lam, "lam", {B, N + 1}); need(*cm, "cm", {B, N});
-  } else {
-    TORCH_CHECK(!lam.has_value() && !cm.has_value(), "nfopp: the 2-D step takes no multiplier tensors (lam / cm must be None)");
-  }
-  if (t_steps.has_value()) need(*t_steps, "t_steps", {n_steps, B, N - 1});
-  if (terms.has_value()) need(*terms, "terms", {B, NFOPP_NUM_TERMS});
-  if (active.has_value()) {
-    check_tensor(*active, "active", at::kByte);
-    same_device(traj, *active, "active");
-    TORCH_CHECK(active->numel() == B, "nfopp: active must be [B] uint8");
-    TORCH_CHECK(live_ws.has_value(), "nfopp: an active mask needs the live-list workspace (B + 1 int32)");
-    check_tensor(*live_ws, "live_ws", at::kInt);
-    same_device(traj, *live_ws, "live_ws");
-    TORCH_CHECK(live_ws->numel() >= B + 1, "nfopp: live_ws must hold B + 1 int32");
-  } else {
-    TORCH_CHECK(!live_ws.has_value(), "nfopp: live_ws without an active mask");
-  }
+  if (t_steps.has_value()) need(traj, *t_steps, "t_steps", {n_steps, b.B, b.N - 1});
   const nfopp_traj_hyper hp = make_hyper(hyper);
-  nfopp_traj_buffers buf;
-  buf.traj_dev = traj.data_ptr<float>(); buf.start_dev = start.data_ptr<float>(); buf.goal_dev = goal.data_ptr<float>();
-  buf.lam_dev = opt_ptr<float>(lam); buf.cm_dev = opt_ptr<float>(cm);
-  buf.adam_m_dev = adam_m.data_ptr<float>(); buf.adam_v_dev = adam_v.data_ptr<float>();
-  buf.t_dev = t.data_ptr<float>(); buf.onf_out4_dev = onf_out.data_ptr<float>();
-  buf.hinv_band_dev = hinv_band.data_ptr<float>(); buf.u_dev = u.data_ptr<float>();
-  buf.active_dev = opt_ptr<uint8_t>(active); buf.live_ws_dev = opt_ptr<int32_t>(live_ws);
-  buf.batch = B; buf.n_waypoints = (int32_t)N; buf.dim = (int32_t)D; buf.half_width = (int32_t)half_width;
-  buf.interior_lo = (int32_t)interior_lo; buf.interior_hi = (int32_t)interior_hi;
+  const nfopp_traj_buffers buf = {b.traj, b.start, b.goal, b.lam, b.cm, adam_m.data_ptr<float>(), adam_v.data_ptr<float>(),
+                                  t.data_ptr<float>(), onf_out.data_ptr<float>(), hinv_band.data_ptr<float>(), b.u, b.mask,
+                                  b.live_ws, b.B, (int32_t)b.N, (int32_t)b.D, (int32_t)half_width, (int32_t)interior_lo,
+                                  (int32_t)interior_hi};
   nfopp_step_schedule sc;
   sc.adam_lr = adam_lr; sc.adam_beta1 = adam_beta1; sc.adam_beta2 = adam_beta2;
   sc.adam_steps_done = adam_steps_done; sc.step_count = step_count; sc.traj_index_offset = traj_index_offset;
@@ -221,71 +222,23 @@ void traj_steps(const Tensor& params, double mean, double sigma, bool use_cos, b
 // arc-length reparametrisation (constrained:132-171 / nerf:224-244), in place
 void reparametrize(Tensor traj, const Tensor& start, const Tensor& goal, const OptTensor& lam, const OptTensor& cm,
                    const Tensor& u, const OptTensor& active) {
-  check_tensor(traj, "traj");
-  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
-  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
-  check_tensor(start, "start"); check_tensor(goal, "goal"); check_tensor(u, "u");
-  same_device(traj, start, "start"); same_device(traj, goal, "goal"); same_device(traj, u, "u");
-  TORCH_CHECK(start.numel() == B * D && goal.numel() == B * D, "nfopp: start / goal must be [B, D]");
-  TORCH_CHECK(u.numel() == N, "nfopp: u must be torch.linspace(0, 1, N + 2)[1:-1]");
-  if (D == 3) {
-    TORCH_CHECK(lam.has_value() && cm.has_value(), "nfopp: the SE(2) reparametrisation needs lam [B, N+1] and cm [B, N]");
-    check_tensor(*lam, "lam"); check_tensor(*cm, "cm");
-    same_device(traj, *lam, "lam"); same_device(traj, *cm, "cm");
-    TORCH_CHECK(lam->numel() == B * (N + 1) && cm->numel() == B * N, "nfopp: lam must be [B, N+1], cm [B, N]");
-  } else {
-    TORCH_CHECK(D == 2, "nfopp: trajectory dim must be 2 or 3");
-    TORCH_CHECK(!lam.has_value() && !cm.has_value(), "nfopp: the 2-D reparametrisation takes no multiplier tensors");
-  }
-  if (active.has_value()) {
-    check_tensor(*active, "active", at::kByte);
-    same_device(traj, *active, "active");
-    TORCH_CHECK(active->numel() == B, "nfopp: active must be [B] uint8");
-  }
+  const Batch b = batch_state(traj, start, goal, lam, cm, &u, &active, "active", nullptr);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
-  check_status(nfopp_reparametrize(B, (int32_t)N, (int32_t)D, traj.data_ptr<float>(), start.data_ptr<float>(),
-                                   goal.data_ptr<float>(), opt_ptr<float>(lam), opt_ptr<float>(cm), u.data_ptr<float>(),
-                                   opt_ptr<uint8_t>(active), stream_of(traj)));
+  check_status(nfopp_reparametrize(b.B, (int32_t)b.N, (int32_t)b.D, b.traj, b.start, b.goal, b.lam, b.cm, b.u, b.mask,
+                                   stream_of(traj)));
 }
 
 // start (which = 0) / goal (which = 1) update of a batch (constrained:178-194 / nerf:202-218), in place: nearest waypoint,
 // cut, endpoint write and reparametrisation from one launch.  moved [B] uint8 or None (= all); min_index [B] int32 or None.
 void update_endpoints(Tensor traj, Tensor start, Tensor goal, const OptTensor& lam, const OptTensor& cm, const Tensor& u,
                       const Tensor& points, int64_t which, const OptTensor& moved, const OptTensor& min_index) {
-  check_tensor(traj, "traj");
-  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
-  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
+  const Batch b = batch_state(traj, start, goal, lam, cm, &u, &moved, "moved", nullptr);
   TORCH_CHECK(which == 0 || which == 1, "nfopp: which must be 0 (start) or 1 (goal)");
-  check_tensor(start, "start"); check_tensor(goal, "goal"); check_tensor(u, "u"); check_tensor(points, "points");
-  same_device(traj, start, "start"); same_device(traj, goal, "goal"); same_device(traj, u, "u");
-  same_device(traj, points, "points");
-  TORCH_CHECK(start.numel() == B * D && goal.numel() == B * D && points.numel() == B * D,
-              "nfopp: start / goal / points must be [B, D]");
-  TORCH_CHECK(u.numel() == N, "nfopp: u must be torch.linspace(0, 1, N + 2)[1:-1]");
-  if (D == 3) {
-    TORCH_CHECK(lam.has_value() && cm.has_value(), "nfopp: the SE(2) endpoint update needs lam [B, N+1] and cm [B, N]");
-    check_tensor(*lam, "lam"); check_tensor(*cm, "cm");
-    same_device(traj, *lam, "lam"); same_device(traj, *cm, "cm");
-    TORCH_CHECK(lam->numel() == B * (N + 1) && cm->numel() == B * N, "nfopp: lam must be [B, N+1], cm [B, N]");
-  } else {
-    TORCH_CHECK(D == 2, "nfopp: trajectory dim must be 2 or 3");
-    TORCH_CHECK(!lam.has_value() && !cm.has_value(), "nfopp: the 2-D endpoint update takes no multiplier tensors");
-  }
-  if (moved.has_value()) {
-    check_tensor(*moved, "moved", at::kByte);
-    same_device(traj, *moved, "moved");
-    TORCH_CHECK(moved->numel() == B, "nfopp: moved must be [B] uint8");
-  }
-  if (min_index.has_value()) {
-    check_tensor(*min_index, "min_index", at::kInt);
-    same_device(traj, *min_index, "min_index");
-    TORCH_CHECK(min_index->numel() == B, "nfopp: min_index must be [B] int32");
-  }
+  need(traj, points, "points", {b.B, b.D});
+  if (min_index.has_value()) need(traj, *min_index, "min_index", {b.B}, at::kInt);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
-  check_status(nfopp_update_endpoints(B, (int32_t)N, (int32_t)D, (int32_t)which, points.data_ptr<float>(),
-                                      opt_ptr<uint8_t>(moved), traj.data_ptr<float>(), start.data_ptr<float>(),
-                                      goal.data_ptr<float>(), opt_ptr<float>(lam), opt_ptr<float>(cm), u.data_ptr<float>(),
-                                      opt_ptr<int32_t>(min_index), stream_of(traj)));
+  check_status(nfopp_update_endpoints(b.B, (int32_t)b.N, (int32_t)b.D, (int32_t)which, points.data_ptr<float>(), b.mask, b.traj,
+                                      b.start, b.goal, b.lam, b.cm, b.u, opt_ptr<int32_t>(min_index), stream_of(traj)));
 }
 
 // grid-search (A*) seeding of a batch (astar_trajectory_initializer.py:15-48): traj [B, N, D] in place, returns status [B].
@@ -294,18 +247,14 @@ void update_endpoints(Tensor traj, Tensor start, Tensor goal, const OptTensor& l
 Tensor grid_search_init(Tensor traj, const Tensor& start, const Tensor& goal, const Tensor& occupancy, const Tensor& start_cells,
                         const Tensor& goal_cells, const Tensor& unique_goal_cells, const Tensor& field_index, double origin_x,
                         double origin_y, double resolution, bool angles_with_direction) {
-  check_tensor(traj, "traj");
-  TORCH_CHECK(traj.dim() == 3, "nfopp: traj must be [B, N, D]");
-  const int64_t B = traj.size(0), N = traj.size(1), D = traj.size(2);
-  check_tensor(start, "start"); check_tensor(goal, "goal");
+  const Batch b = batch_endpoints(traj, start, goal);
+  const int64_t B = b.B, N = b.N, D = b.D;
   check_tensor(occupancy, "occupancy", at::kByte);
   check_tensor(start_cells, "start_cells", at::kInt); check_tensor(goal_cells, "goal_cells", at::kInt);
   check_tensor(unique_goal_cells, "unique_goal_cells", at::kInt); check_tensor(field_index, "field_index", at::kInt);
-  same_device(traj, start, "start"); same_device(traj, goal, "goal"); same_device(traj, occupancy, "occupancy");
+  same_device(traj, occupancy, "occupancy");
   same_device(traj, start_cells, "start_cells"); same_device(traj, goal_cells, "goal_cells");
   same_device(traj, unique_goal_cells, "unique_goal_cells"); same_device(traj, field_index, "field_index");
-  TORCH_CHECK(D == 2 || D == 3, "nfopp: trajectory dim must be 2 or 3");
-  TORCH_CHECK(start.numel() == B * D && goal.numel() == B * D, "nfopp: start / goal must be [B, D]");
   TORCH_CHECK(occupancy.dim() == 2, "nfopp: occupancy must be [rows, cols] uint8");
   TORCH_CHECK(start_cells.numel() == 2 * B && goal_cells.numel() == 2 * B && field_index.numel() == B,
               "nfopp: start_cells / goal_cells must be [B, 2], field_index [B]");
@@ -333,9 +282,8 @@ Tensor grid_search_init(Tensor traj, const Tensor& start, const Tensor& goal, co
   const size_t sws = nfopp_grid_seed_workspace_bytes(B, (int32_t)max_len);
   Tensor swork = at::empty({(int64_t)((sws + 7) / 8)}, traj.options().dtype(at::kDouble));
   check_status(nfopp_grid_seed_trajectories(cells.data_ptr<int32_t>(), count.data_ptr<int32_t>(), status.data_ptr<int32_t>(), B,
-                                            (int32_t)max_len, start.data_ptr<float>(), goal.data_ptr<float>(), (int32_t)N,
-                                            (int32_t)D, angles_with_direction ? 1 : 0, origin_x, origin_y, resolution,
-                                            traj.data_ptr<float>(), sws ? swork.data_ptr() : nullptr, sws, stream_of(traj)));
+                                            (int32_t)max_len, b.start, b.goal, (int32_t)N, (int32_t)D,
+                                            angles_with_direction ? 1 : 0, origin_x, origin_y, resolution, b.traj, sws ? swork.data_ptr() : nullptr, sws, stream_of(traj)));
   return status;
 }
 

@@ -369,14 +369,7 @@ extern "C" int nfopp_traj_update(const nfopp_traj_hyper* hp, int64_t batch, int3
   if (!a.bnd_in_lds) n_boundary = 0;
   const size_t lds = (size_t)((n_waypoints + 2) * dim + (n_waypoints + 2 * half_width) * dim + 2 * n_waypoints + 1 +
                               (n_boundary + 1) * (2 * half_width + 1) + NFOPP_NUM_TERMS * (TU_THREADS / 64)) * 4;
-  NFOPP_REQUIRE(lds <= 160 * 1024, "trajectory too long for one workgroup's LDS (%zu bytes)", lds);
   NFOPP_REQUIRE(batch <= 0x7fffffffLL, "batch too large for one launch");
-  auto kern = dim == 3 ? traj_update_kernel<3> : traj_update_kernel<2>;
-  if (lds > 64 * 1024)
-    NFOPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  const long long grid = batch;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(TU_THREADS), lds, (hipStream_t)stream, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  return launch_dynamic_lds(dim == 3 ? traj_update_kernel<3> : traj_update_kernel<2>, batch, TU_THREADS, lds, stream, a,
+                            "trajectory too long");
 }

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import TrajectoryEngine, TrajectoryHyper
+from .engine import TrajectoryEngine
 from .grid_search import AstarTrajectoryInitializer, OccupancyGrid, grid_search_init
 from .path_tools import init_trajectories
 
@@ -168,10 +168,7 @@ class BatchPlanner(object):
     def init(self, starts, goals, boundaries, trajectories=None, initializer=None):
         eng = self.engine
         eng.set_endpoints(starts, goals)
-        h = eng.hyper
-        eng.hyper = TrajectoryHyper(h.collision_weight, h.angle_weight, h.constraint_deltas_weight, h.multipliers_lr,
-                                    h.collision_multipliers_lr, h.boundary_weight, h.collision_beta,
-                                    h.direction_delta_weight, h.lr, h.betas, h.eps, boundaries)
+        eng.hyper = eng.hyper.replace(bounds=boundaries)
         self.seed_status = None
         if initializer is not None:
             # grid-search seeding of the whole batch (csrc/grid_search.hip): an OccupancyGrid or an AstarTrajectoryInitializer
@@ -266,12 +263,9 @@ class BatchPlanner(object):
         self._update_endpoints(1, points, moved)
 
     def set_boundaries(self, boundaries):
-        """`set_boundaries` (nerf:218-220): new sampling / boundary-loss box, `step_count` back to 0.  The hyper block is
-        rebuilt as `init()` builds it, so the kernels' cached scalar block is formed afresh."""
-        h = self.engine.hyper
-        self.engine.hyper = TrajectoryHyper(h.collision_weight, h.angle_weight, h.constraint_deltas_weight, h.multipliers_lr,
-                                            h.collision_multipliers_lr, h.boundary_weight, h.collision_beta,
-                                            h.direction_delta_weight, h.lr, h.betas, h.eps, tuple(boundaries))
+        """`set_boundaries` (nerf:218-220): new sampling / boundary-loss box, `step_count` back to 0.  The hyper value is
+        replaced as `init()` replaces it, so the kernels' cached scalar block is formed afresh."""
+        self.engine.hyper = self.engine.hyper.replace(bounds=boundaries)
         self.step_count = 0
 
     def replan(self, starts=None, goals=None, moved=None, n=1):

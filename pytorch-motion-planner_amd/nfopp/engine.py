@@ -8,6 +8,7 @@ One step = 2 launches:  nfopp_traj_collision_eval (fused sampling + ONF fwd/bwd,
 (stencil terms, banded H^-1, Adam, multiplier ascent); every `reparam_freq` steps a third: nfopp_reparametrize.
 """
 import math
+import operator
 
 import numpy as np
 import torch
@@ -64,51 +65,72 @@ def interior_range(band):
     return (lo, hi) if hi - lo >= 64 else (0, 0)
 
 
+# the fields of TrajectoryHyper, in constructor order: the one list its slots, equality and replace() are built from
+_HYPER_FIELDS = ("collision_weight", "angle_weight", "constraint_deltas_weight", "multipliers_lr", "collision_multipliers_lr",
+                 "boundary_weight", "collision_beta", "direction_delta_weight", "lr", "betas", "eps", "bounds")
+_hyper_values = operator.attrgetter(*_HYPER_FIELDS)
+
+
 class TrajectoryHyper(object):
-    """Scalars of the trajectory step (nfop/constrained_nerf_opt_planner.py:13-40 + the Adam group)."""
+    """Scalars of the trajectory step (nfop/constrained_nerf_opt_planner.py:13-40 + the Adam group).
+
+    An immutable value: a change is made with `replace()`, which returns a new object, so the C block `to_c` caches
+    can never go stale.  Equality and hash are over `FIELDS`."""
+
+    FIELDS = _HYPER_FIELDS
+    __slots__ = FIELDS + ("_c_block",)
 
     def __init__(self, collision_weight=1.0, angle_weight=0.5, constraint_deltas_weight=20.0, multipliers_lr=0.1,
                  collision_multipliers_lr=1e-3, boundary_weight=1.0, collision_beta=1.0, direction_delta_weight=0.0,
                  lr=1e-2, betas=(0.9, 0.9), eps=1e-8, bounds=(0.0, 0.0, 0.0, 0.0)):
-        self.collision_weight = collision_weight
-        self.angle_weight = angle_weight
-        self.constraint_deltas_weight = constraint_deltas_weight
-        self.multipliers_lr = multipliers_lr
-        self.collision_multipliers_lr = collision_multipliers_lr
-        self.boundary_weight = boundary_weight
-        self.collision_beta = collision_beta
-        self.direction_delta_weight = direction_delta_weight
-        self.lr, self.betas, self.eps = lr, tuple(betas), eps
-        self.bounds = tuple(bounds)
+        values = (collision_weight, angle_weight, constraint_deltas_weight, multipliers_lr, collision_multipliers_lr,
+                  boundary_weight, collision_beta, direction_delta_weight, lr, tuple(betas), eps, tuple(bounds))
+        for name, value in zip(self.FIELDS, values):
+            object.__setattr__(self, name, value)
+        object.__setattr__(self, "_c_block", None)
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError("TrajectoryHyper is immutable (tried to change %r): replace() returns a changed copy" % name)
+
+    __delattr__ = __setattr__
+
+    def replace(self, **changes):
+        """A new object with the given fields changed; this one (and its cached C block) stays as it is."""
+        values = dict(zip(self.FIELDS, _hyper_values(self)))
+        values.update(changes)
+        return TrajectoryHyper(**values)
+
+    def __eq__(self, other):
+        return type(other) is TrajectoryHyper and _hyper_values(self) == _hyper_values(other)
+
+    def __hash__(self):
+        return hash(_hyper_values(self))
 
     def to_c(self, adam_step):
-        """`adam_step` = 1-based count of the step being taken.  Scalars are formed in Python doubles like torch."""
+        """`adam_step` = 1-based count of the step being taken.  Scalars are formed in Python doubles like torch.
+        One block per object: the step-invariant fields are filled once (the object cannot change afterwards) and only
+        the two step scalars are refreshed per call -- B = 1 latency is host-bound (tools/b1_breakdown.py)."""
         b1, b2 = self.betas
-        bc1 = 1 - b1 ** adam_step
-        bc2 = 1 - b2 ** adam_step
-        c = getattr(self, "_c_block", None)
-        if c is not None:                    # the step-invariant fields were filled when the block was made (the object is
-            c.adam_step_size = self.lr / bc1   # treated as immutable: the planners build a new one when a scalar changes)
-            c.adam_bc2_sqrt = math.sqrt(bc2)
-            return c
-        c = _lib.TrajHyperC()
-        c.collision_weight = self.collision_weight
-        c.angle_weight = self.angle_weight
-        c.constraint_deltas_weight = self.constraint_deltas_weight
-        c.multipliers_lr = self.multipliers_lr
-        c.collision_multipliers_lr = self.collision_multipliers_lr
-        c.boundary_weight = self.boundary_weight
-        c.collision_beta = self.collision_beta
-        c.direction_delta_weight = self.direction_delta_weight
-        for k in range(4):
-            c.bounds[k] = self.bounds[k]
-        c.adam_beta2 = b2
-        c.adam_omb1 = 1 - b1
-        c.adam_omb2 = 1 - b2
-        c.adam_eps = self.eps
-        c.adam_step_size = self.lr / bc1
-        c.adam_bc2_sqrt = math.sqrt(bc2)
-        self._c_block = c
+        c = self._c_block
+        if c is None:
+            c = _lib.TrajHyperC()
+            c.collision_weight = self.collision_weight
+            c.angle_weight = self.angle_weight
+            c.constraint_deltas_weight = self.constraint_deltas_weight
+            c.multipliers_lr = self.multipliers_lr
+            c.collision_multipliers_lr = self.collision_multipliers_lr
+            c.boundary_weight = self.boundary_weight
+            c.collision_beta = self.collision_beta
+            c.direction_delta_weight = self.direction_delta_weight
+            for k in range(4):
+                c.bounds[k] = self.bounds[k]
+            c.adam_beta2 = b2
+            c.adam_omb1 = 1 - b1
+            c.adam_omb2 = 1 - b2
+            c.adam_eps = self.eps
+            object.__setattr__(self, "_c_block", c)
+        c.adam_step_size = self.lr / (1 - b1 ** adam_step)
+        c.adam_bc2_sqrt = math.sqrt(1 - b2 ** adam_step)
         return c
 
 
@@ -157,6 +179,15 @@ class TrajectoryEngine(object):
             raise _lib.NfoppError("trajectory must be a contiguous fp32 HIP tensor with %d elements" %
                                   (self.B * self.N * self.D))
 
+    def _active_ptrs(self):
+        """(active mask, live-list workspace) pointers of the ONF kernel's sample compaction; (None, None) without a mask.
+        The workspace is allocated the first time a mask is present."""
+        if self.active is None:
+            return None, None
+        if self._live is None:
+            self._live = torch.zeros(self.B + 1, dtype=torch.int32, device=self.device)
+        return _lib.ptr(self.active, torch.uint8), _lib.ptr(self._live, torch.int32)
+
     # ---- pipeline stages ------------------------------------------------------------------------------------------
     def collision_eval(self, t=None):
         """ONF logits + input gradients at the collision samples.  `t` [B,N-1] injects the draws (parity mode);
@@ -168,14 +199,11 @@ class TrajectoryEngine(object):
         else:
             mode = 1
         cfg = self.onf.config_c()
-        if self.active is not None and self._live is None:
-            self._live = torch.zeros(self.B + 1, dtype=torch.int32, device=self.device)
+        active, live = self._active_ptrs()
         _lib.check(lib.nfopp_traj_collision_eval(cfg, _lib.ptr(self.onf.flat_parameters), _lib.ptr(self.traj), self.B,
                                                  self.N, self.D, _lib.ptr(self.t), mode, self.seed, self.rng_offset,
                                                  self.traj_index_offset, _lib.ptr(self.onf_out),
-                                                 _lib.ptr(self.active, torch.uint8),
-                                                 _lib.ptr(self._live, torch.int32) if self.active is not None else None,
-                                                 _lib.stream_ptr()))
+                                                 active, live, _lib.stream_ptr()))
         if mode == 1:
             self.rng_offset += 1
 
@@ -208,13 +236,11 @@ class TrajectoryEngine(object):
         lib = _lib.load()
         cfg = self.onf.config_c()
         hp = self.hyper.to_c(self.adam_step + 1)
-        if self.active is not None and self._live is None:
-            self._live = torch.zeros(self.B + 1, dtype=torch.int32, device=self.device)
+        active, live = self._active_ptrs()
         P = _lib.ptr
         buf = _lib.TrajBuffersC(P(self.traj), P(self.start), P(self.goal), P(self.lam), P(self.cm), P(self.adam_m),
                                 P(self.adam_v), P(self.t), P(self.onf_out), P(self.hinv_band), P(self.u),
-                                P(self.active, torch.uint8), P(self._live, torch.int32) if self.active is not None else None,
-                                self.B, self.N, self.D, self.half_width, self.interior[0], self.interior[1])
+                                active, live, self.B, self.N, self.D, self.half_width, self.interior[0], self.interior[1])
         tdev = None
         if t_steps is not None:
             tdev = torch.as_tensor(t_steps, dtype=torch.float32).reshape(n, self.B, self.N - 1).to(self.device).contiguous()

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .batch import OnfFitter
 from .engine import TrajectoryEngine, TrajectoryHyper
 from .grid_search import AstarTrajectoryInitializer
 from .host_utils import Position2, TrajectoryInitializer
@@ -99,13 +100,8 @@ class NERFOptPlanner(ContinuousPlanner):
         self._engine = TrajectoryEngine(collision_model, 1, n, d, self._make_hyper(), velocity_hessian_weight,
                                         self._device, traj=trajectory.detach())
         self._inv_hessian = torch.tensor(self._engine.hinv, device=self._device)
-        # ONF Adam state (flat, same order as the parameter buffer)
-        self._onf_m = torch.zeros_like(collision_model.flat_parameters)
-        self._onf_v = torch.zeros_like(collision_model.flat_parameters)
-        self._onf_step = 0
-        self._onf_grad = torch.zeros(collision_model.n_params + 2, dtype=torch.float32, device=self._device)
-        self._onf_ws = None
-        self.last_onf_loss = None
+        # the fitting step and its Adam state; lr / betas / eps are taken from the caller's optimiser before every step
+        self._fitter = OnfFitter(collision_model, *_adam_group(collision_optimizer), distributed=False)
 
     # ---- configuration ---------------------------------------------------------------------------------------------
     def _make_hyper(self):
@@ -114,12 +110,10 @@ class NERFOptPlanner(ContinuousPlanner):
                                bounds=self._random_sample_border)
 
     def _sync_hyper(self):
-        """Attributes may be edited between steps (drivers do): the kernel scalars follow them, rebuilt only when one changed."""
+        """Attributes may be edited between steps (drivers do): the kernel scalars follow them, replaced only when one changed
+        (an equal value keeps the engine's object and with it the cached C block)."""
         h = self._make_hyper()
-        key = (h.collision_weight, h.angle_weight, h.constraint_deltas_weight, h.multipliers_lr, h.collision_multipliers_lr,
-               h.boundary_weight, h.collision_beta, h.direction_delta_weight, h.lr, h.betas, h.eps, h.bounds)
-        if key != getattr(self, "_hyper_key", None):
-            self._hyper_key = key
+        if h != self._engine.hyper:
             self._engine.hyper = h
 
     @property
@@ -173,33 +167,18 @@ class NERFOptPlanner(ContinuousPlanner):
             positions = self._host_training_poses(self._previous_trajectory)
             self._previous_trajectory = self._trajectory.detach().cpu().numpy().copy()
         truth = self._calculate_truth_collision(positions)
-        self._fit_step(positions, np.asarray(truth))
-
-    def _fit_step(self, positions, truth):
-        """One BCE/Adam step of the field on host-provided samples: gradient kernel + flat Adam kernel."""
-        lib = _lib.load()
-        model = self._collision_model
         # one upload for poses and labels (two pageable copies cost 2 x 25 us at B = 1): [P * D | P] floats, two contiguous views
         pos32 = np.ascontiguousarray(positions, dtype=np.float32)
         p, d = pos32.shape
         packed = torch.from_numpy(np.concatenate([pos32.reshape(-1), np.asarray(truth).astype(np.float32).reshape(-1)])).to(self._device)
-        samples, labels = packed[:p * d].view(p, d), packed[p * d:]
-        cfg = model.config_c()
-        need = lib.nfopp_onf_train_workspace_bytes(cfg, p)
-        if self._onf_ws is None or self._onf_ws.numel() * 4 < need:
-            self._onf_ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self._device)
-        _lib.check(lib.nfopp_onf_train_grad(cfg, _lib.ptr(model.flat_parameters), _lib.ptr(samples), _lib.ptr(labels),
-                                            p, 1.0 / p, _lib.ptr(self._onf_grad), _lib.ptr(self._onf_ws),
-                                            self._onf_ws.numel() * 4, _lib.stream_ptr()))
-        lr, (b1, b2), eps = _adam_group(self._collision_optimizer)
-        self._onf_step += 1
-        bc1 = 1 - b1 ** self._onf_step
-        bc2 = 1 - b2 ** self._onf_step
-        _lib.check(lib.nfopp_adam_step(_lib.ptr(model.flat_parameters), _lib.ptr(self._onf_grad), _lib.ptr(self._onf_m),
-                                       _lib.ptr(self._onf_v), model.n_params, b2, 1 - b1, 1 - b2, eps, lr / bc1,
-                                       bc2 ** 0.5, _lib.stream_ptr()))
-        model.mark_modified()   # a raw-pointer write: torch's version counter does not see it
-        self.last_onf_loss = self._onf_grad[model.n_params]
+        fit = self._fitter
+        fit.lr, fit.betas, fit.eps = _adam_group(self._collision_optimizer)   # drivers edit the group between steps
+        fit.step(packed[:p * d].view(p, d), packed[p * d:], global_count=p)
+
+    @property
+    def last_onf_loss(self):
+        """BCE loss of the most recent fitting step (a device scalar; None before the first)."""
+        return self._fitter.last_loss
 
     def _calculate_truth_collision(self, positions):
         self.checked_positions = positions.copy()

@@ -144,6 +144,78 @@ def test_2d_planner_factory_shapes_and_steps():
     assert terms["total"] > 0 and terms["lambda_dot_c"] == 0
 
 
+def _former_two_call_fit(model, group, st, positions, truth):
+    """One fit step as NERFOptPlanner stated it before the step moved into OnfFitter: two library calls with the scalars
+    1 / p, lr / (1 - b1 ** k) and (1 - b2 ** k) ** 0.5 formed in Python doubles, here on the cloned state `st`."""
+    from nfopp import _lib
+    lib = _lib.load()
+    pos32 = np.ascontiguousarray(positions, dtype=np.float32)
+    p, d = pos32.shape
+    packed = torch.from_numpy(np.concatenate([pos32.reshape(-1), np.asarray(truth).astype(np.float32).reshape(-1)])).to("cuda")
+    samples, labels = packed[:p * d].view(p, d), packed[p * d:]
+    cfg = model.config_c()
+    need = lib.nfopp_onf_train_workspace_bytes(cfg, p)
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib.nfopp_onf_train_grad(cfg, _lib.ptr(st["params"]), _lib.ptr(samples), _lib.ptr(labels), p, 1.0 / p,
+                                        _lib.ptr(st["grad"]), _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()))
+    lr, (b1, b2), eps = float(group["lr"]), tuple(float(b) for b in group["betas"]), float(group["eps"])
+    st["step"] += 1
+    bc1 = 1 - b1 ** st["step"]
+    bc2 = 1 - b2 ** st["step"]
+    _lib.check(lib.nfopp_adam_step(_lib.ptr(st["params"]), _lib.ptr(st["grad"]), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
+                                   model.n_params, b2, 1 - b1, 1 - b2, eps, lr / bc1, bc2 ** 0.5, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    return st["grad"][model.n_params]
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_fit_through_the_fitter_equals_its_former_formulation(dim):
+    """`_optimize_collision_model` now runs OnfFitter.step; parameters, both Adam moments and the loss stay bit for bit
+    what the planner's own two library calls gave, including an lr edited on the caller's optimiser between steps.
+    P = 7 poses: neither a tile nor a wave multiple."""
+    torch.random.manual_seed(100)
+    np.random.seed(400)
+    g11 = load_golden("g11_init_checkers.npz")
+    if dim == 3:
+        cc = nfopp.CircleDirectedCollisionChecker(0.3, (0, 3, 0, 3))
+        cc.update_obstacle_points(g11["corridor_obstacles"])
+        planner = nfopp.PlannerFactory.make_constrained_onf_planner(cc, _params(100))
+        assert type(planner) is nfopp.ConstrainedNERFOptPlanner
+        ends = np.array([0.5, 0.5, 0.1], np.float32), np.array([2.5, 2.5, -0.2], np.float32)
+    else:
+        cc = nfopp.CircleCollisionChecker(0.3, (0, 3, 0, 3))
+        cc.update_obstacle_points(g11["corridor_obstacles"])
+        planner = nfopp.PlannerFactory.make_onf_planner(cc)
+        assert type(planner) is nfopp.NERFOptPlanner
+        ends = np.array([0.5, 0.5], np.float32), np.array([2.5, 2.5], np.float32)
+    planner._init_collision_iteration = 0
+    planner.init(ends[0], ends[1], (-0.1, 3.1, -0.1, 3.1))
+    model, group = planner._collision_model, planner._collision_optimizer.param_groups[0]
+    positions = np.random.default_rng(5).uniform(0.0, 3.0, (7, dim))
+    n = model.n_params
+    st = dict(params=model.flat_parameters.detach().clone(), m=torch.zeros(n, device="cuda"), v=torch.zeros(n, device="cuda"),
+              grad=torch.zeros(n + 2, device="cuda"), step=0)
+    assert planner.last_onf_loss is None
+    for k in range(3):
+        if k == 2:
+            # the same step without the edit, on a copy: the edit has to show in the planner's result
+            stale = {key: (val.clone() if isinstance(val, torch.Tensor) else val) for key, val in st.items()}
+            stale_group = dict(group)
+            group["lr"] = group["lr"] * 0.25
+        planner._optimize_collision_model(positions)
+        truth = np.asarray(planner.truth_collision)
+        assert truth.shape == (7,)
+        loss = _former_two_call_fit(model, group, st, positions, truth)
+        fit = planner._fitter
+        assert torch.equal(model.flat_parameters.detach(), st["params"]), k
+        assert torch.equal(fit.m, st["m"]) and torch.equal(fit.v, st["v"]), k
+        assert planner.last_onf_loss.is_cuda and planner.last_onf_loss.dim() == 0
+        assert torch.equal(planner.last_onf_loss, loss), k
+    assert fit.step_count == 3 and float(loss) > 0
+    _former_two_call_fit(model, stale_group, stale, positions, truth)
+    assert not torch.equal(model.flat_parameters.detach(), stale["params"])
+
+
 def test_factory_rejects_cpu_device():
     p = _params()
     p.device = "cpu"

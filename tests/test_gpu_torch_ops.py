@@ -94,3 +94,63 @@ def test_onf_train_step_op_vs_golden():
     # Adam ran on the kernel's own gradient (the ctypes test feeds the golden one): parameters agree to the gradient's rounding
     assert max_abs(params.cpu().numpy(), z["params_after"]) < 2e-5
     assert max_abs(m.cpu().numpy(), z["adam_m_after"]) < 1e-6
+
+
+def _call_batch_op(ops, op, onf, cfg, e, **bad):
+    """One of the four ops that take a batch's state, on engine `e`'s tensors with `bad` replacing some of them."""
+    a = dict(traj=e.traj, start=e.start, goal=e.goal, lam=e.lam, cm=e.cm, u=e.u, mask=None)
+    a.update(bad)
+    live = None if a["mask"] is None else torch.zeros(e.B + 1, dtype=torch.int32, device="cuda")
+    hyper = torch_ops.hyper_list(e.hyper.to_c(1))
+    if op == "traj_step":
+        ops.traj_step(onf.flat_parameters, *_cfg_args(cfg), a["traj"], a["start"], a["goal"], a["lam"], a["cm"], e.adam_m,
+                      e.adam_v, e.t, 0, 0, 0, 0, e.onf_out, e.hinv_band, e.half_width, e.interior[0], e.interior[1], hyper,
+                      e.terms, a["mask"], live)
+    elif op == "traj_steps":
+        ops.traj_steps(onf.flat_parameters, *_cfg_args(cfg), a["traj"], a["start"], a["goal"], a["lam"], a["cm"], e.adam_m,
+                       e.adam_v, e.t, None, 0, 0, 0, e.onf_out, e.hinv_band, e.half_width, e.interior[0], e.interior[1],
+                       a["u"], hyper, 1e-2, 0.9, 0.9, 0, 0, 10, 2, e.terms, a["mask"], live)
+    elif op == "reparametrize":
+        ops.reparametrize(a["traj"], a["start"], a["goal"], a["lam"], a["cm"], a["u"], a["mask"])
+    else:
+        ops.update_endpoints(a["traj"], a["start"], a["goal"], a["lam"], a["cm"], a["u"], e.goal.clone(), 1, a["mask"], None)
+
+
+@pytest.mark.parametrize("d", [3, 2])
+def test_batch_ops_share_one_validation(d):
+    """traj_step, traj_steps, reparametrize and update_endpoints state a batch's tensors through one helper
+    (csrc/torch_ops.cpp batch_state): a wrong lam shape, multipliers beside a 2-D trajectory, a row mask of the wrong dtype
+    and a flattened start are refused by all four with the same text, naming the argument, before anything is launched.
+    update_endpoints has no `active`: its row mask is `moved`, and the text differs in that name alone."""
+    ops = torch_ops.load()
+    torch.random.manual_seed(3)
+    B, N = 2, 4
+    onf = nfopp.ONF(0, 1, use_cos=True, use_normal_init=True, bias=True, angle_encoding=d == 3).to("cuda")
+    cfg = orc.OnfConfig(0, 1, True, True, d == 3)
+    e = nfopp.TrajectoryEngine(onf, B, N, d, nfopp.TrajectoryHyper(bounds=(0, 3, 0, 3)), 0.5, "cuda")
+    z = lambda *shape, **kw: torch.zeros(*shape, device="cuda", **kw)   # noqa: E731
+    state = [x for x in (e.traj, e.start, e.goal, e.lam, e.cm, e.adam_m, e.adam_v, e.t, e.onf_out, e.terms) if x is not None]
+    for x in state:
+        x.copy_(torch.rand(x.shape))
+    before = [x.clone() for x in state]
+    params = onf.flat_parameters.detach().clone()
+    cases = [("lam", dict(lam=z(B, N), cm=z(B, N))),
+             ("active", dict(mask=z(B, dtype=torch.int32))),
+             ("start", dict(start=z(B * d)))]
+    if d == 2:
+        cases.append(("lam", dict(lam=z(B, N + 1), cm=z(B, N))))
+    for name, bad in cases:
+        texts = {}
+        for op in ("traj_step", "traj_steps", "reparametrize", "update_endpoints"):
+            with pytest.raises(RuntimeError) as err:
+                _call_batch_op(ops, op, onf, cfg, e, **bad)
+            texts[op] = str(err.value).splitlines()[0]
+        assert "moved" in texts["update_endpoints"] or name != "active", texts
+        texts["update_endpoints"] = texts["update_endpoints"].replace("moved", "active")
+        assert len(set(texts.values())) == 1 and name in texts["traj_step"], texts
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, w) for x, w in zip(state, before))
+    assert torch.equal(onf.flat_parameters.detach(), params)
+    _call_batch_op(ops, "reparametrize", onf, cfg, e)       # the untouched arguments are a valid call
+    torch.cuda.synchronize()
+    assert not torch.equal(e.traj, before[0])

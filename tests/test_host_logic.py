@@ -45,7 +45,8 @@ def test_no_packed_fp32_op_reads_a_high_dword_into_its_low_lane():
     assert "nothing was checked" in host_only.stderr, host_only.stderr
     missing = subprocess.run([os.path.join(ROOT, "tools", "check_packed_opsel.sh"), _lib.LIB_PATH], capture_output=True, text=True,
                              env=dict(os.environ, OBJDUMP="/nonexistent/llvm-objdump"))
-    assert missing.returncode == 2 and "failing closed" in missing.stderr
+    assert missing.returncode == 2, missing.stderr
+    assert "failing closed" in missing.stderr, missing.stderr
     # the pattern the script looks for does match the offending form and not the harmless direction
     import re as _re
     pat = _re.compile(r"op_sel:\[[01,]*1[01,]*\]")
@@ -205,6 +206,59 @@ def test_hyper_scalars_formed_like_torch():
     assert c.adam_step_size == np.float32(1e-2 / (1 - 0.9 ** 3))
     assert c.adam_bc2_sqrt == np.float32((1 - 0.9 ** 3) ** 0.5)
     assert list(c.bounds) == [0, 1, 2, 3]
+
+
+def _c_fields(block):
+    """Every field of a TrajHyperC as plain Python values (the bounds array as a list)."""
+    return {name: (list(getattr(block, name)) if name == "bounds" else getattr(block, name)) for name, _ in block._fields_}
+
+
+def test_hyper_is_an_immutable_value():
+    h = nfopp.TrajectoryHyper(collision_weight=3, betas=[0.9, 0.8], bounds=[0, 1, 2, 3])
+    assert len(h.FIELDS) == 12 and h.betas == (0.9, 0.8) and h.bounds == (0, 1, 2, 3)
+    for name in h.FIELDS:
+        with pytest.raises(AttributeError, match=r"replace\(\)"):
+            setattr(h, name, getattr(h, name))
+    with pytest.raises(AttributeError):
+        h.no_such_field = 1
+    with pytest.raises(AttributeError):
+        del h.lr
+    with pytest.raises(TypeError):
+        h.replace(no_such_field=1)
+    # equal exactly when every field is equal
+    assert h == nfopp.TrajectoryHyper(collision_weight=3, betas=(0.9, 0.8), bounds=(0, 1, 2, 3)) and not (h != h.replace())
+    assert hash(h) == hash(h.replace())
+    fresh = dict(collision_weight=4, angle_weight=1, constraint_deltas_weight=2, multipliers_lr=3, collision_multipliers_lr=5,
+                 boundary_weight=6, collision_beta=7, direction_delta_weight=8, lr=9, betas=(0.5, 0.8), eps=1e-3,
+                 bounds=(0, 1, 2, 4))
+    assert set(fresh) == set(h.FIELDS)
+    for name, value in fresh.items():
+        other = h.replace(**{name: value})
+        assert other != h and not (other == h), name
+        assert getattr(other, name) == value and getattr(h, name) != value
+    assert h != "hyper" and h != None  # noqa: E711
+
+
+def test_hyper_replace_leaves_the_original_and_its_block_alone():
+    h = nfopp.TrajectoryHyper(collision_weight=3, angle_weight=0.25, lr=2e-2, betas=(0.9, 0.8), eps=1e-6, bounds=(0, 1, 2, 3))
+    c = h.to_c(5)
+    assert h.to_c(5) is c and h.to_c(6) is c              # one block per object, refreshed in place
+    before = _c_fields(h.to_c(5))
+    g = h.replace(bounds=(1, 2, 3, 4))
+    cg = g.to_c(5)
+    assert cg is not c and g.to_c(5) is cg
+    assert h.bounds == (0, 1, 2, 3) and _c_fields(h.to_c(5)) == before
+    after = _c_fields(cg)
+    assert after["bounds"] == [1, 2, 3, 4] and before["bounds"] == [0, 1, 2, 3]
+    assert {k: v for k, v in after.items() if k != "bounds"} == {k: v for k, v in before.items() if k != "bounds"}
+    # betas drive three step-invariant fields and both step scalars: all follow together, none on the original
+    b = h.replace(betas=(0.5, 0.75))
+    cb = _c_fields(b.to_c(5))
+    assert cb["adam_beta2"] == np.float32(0.75) and cb["adam_omb1"] == np.float32(1 - 0.5) and cb["adam_omb2"] == np.float32(1 - 0.75)
+    assert cb["adam_step_size"] == np.float32(2e-2 / (1 - 0.5 ** 5)) and cb["adam_bc2_sqrt"] == np.float32((1 - 0.75 ** 5) ** 0.5)
+    assert _c_fields(h.to_c(5)) == before
+    changed = {k for k in cb if cb[k] != before[k]}
+    assert changed == {"adam_beta2", "adam_omb1", "adam_omb2", "adam_step_size", "adam_bc2_sqrt"}
 
 
 def test_shard_range_partitions_the_batch():
