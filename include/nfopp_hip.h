@@ -227,6 +227,15 @@ int nfopp_check_collision_circle_cells(const float* poses_dev, int64_t n, int32_
                                        float* labels_dev, void* stream);
 int nfopp_check_collision_rectangle(const float* poses_dev, int64_t n, const float* obstacles_dev, int32_t n_obstacles,
                                     const float* box4, const float* bounds4, float* labels_dev, void* stream);
+/* The rectangle checker over the same cell index (additive under ABI 6): `reach` = the largest distance from the robot
+ * origin to a corner of box4 (the box need not contain the origin), formed by the caller; cell_size >= reach, so every
+ * point inside the box lies in the 3 x 3 cells around the pose's cell.  The per-point predicate is the one function the
+ * brute-force kernel calls: identical labels. */
+int nfopp_check_collision_rectangle_cells(const float* poses_dev, int64_t n, const float* obstacles_sorted_dev,
+                                          int32_t n_obstacles, const int32_t* cell_start_dev, int32_t cells_x,
+                                          int32_t cells_y, float cell_x0, float cell_y0, float cell_size,
+                                          const float* box4, float reach, const float* bounds4, float* labels_dev,
+                                          void* stream);
 int nfopp_check_collision_grid(const float* poses_dev, int64_t n, int32_t pose_dim, const uint8_t* grid_dev,
                                int32_t rows, int32_t cols, double origin_x, double origin_y, double cell_size,
                                float* labels_dev, void* stream);
@@ -350,6 +359,39 @@ int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int32_t* count_
                                  int32_t n_waypoints, int32_t dim, int32_t angles_with_direction, double origin_x,
                                  double origin_y, double resolution, float* traj_dev, void* workspace_dev,
                                  size_t workspace_bytes, void* stream);
+
+
+/* ---- the obstacle update of the receding-horizon loop (csrc/obstacle_map.hip), additive under ABI 6 ------------------
+ * What every sensor message does in the reference's deployment (nfop/ros/collision_checker_adapter.py:17-27,
+ * nfop/ros/map_adapter.py): occupancy grid -> point cloud -> the checker that labels the ONF's training poses.
+ *
+ * nfopp_grid_to_points: GridMap.as_point_cloud (nfop/ros/grid_map.py:14-20) and, with is_int8 != 0, the unpacking of
+ *   from_ros_occupancy_grid (:31-40).  grid_dev [rows, cols] is fp32 (occupied: v > threshold, compared in fp32) or the
+ *   raw int8 ROS image (value fp32(v < 0 ? 0 : v) / 100.0f, then the same comparison); at most 2^24 cells.  The occupied
+ *   cells leave in row-major order (np.nonzero's).  Cell (row, col) -> p = (col, row) * resolution + resolution / 2,
+ *   then the origin pose: (x c - y s + origin_x, x s + y c + origin_y), all in float64 with every operation rounded on
+ *   its own; origin_cos / origin_sin are the caller's np.cos / np.sin of the origin angle (no device libm result enters
+ *   the output).  points_dev [max_points, 2] <- fp32 rounding of the float64 points (what the checkers read),
+ *   points64_dev (may be null) <- the float64 points, count_dev <- occupied cells (may exceed max_points: only the first
+ *   max_points are written; call with max_points = 0 to size the buffer).  Compaction: chunk counts by ballot +
+ *   popcount, a fixed-order exclusive scan, the predicate again with rank = offset + position in the chunk.
+ * nfopp_build_cell_index: obstacles_sorted_dev [n, 2] <- obstacles_dev stably sorted by cell, cell_start_dev
+ *   [cells_x * cells_y + 1] <- first sorted point of each cell, bit for bit np.argsort(cell, kind="stable") and
+ *   np.searchsorted(cell[order], arange(cells + 1)).  cell = cy * cells_x + cx with cx = floorf((x - cell_x0) /
+ *   cell_size) in fp32 clamped to [0, cells_x - 1] (cy alike): the arithmetic of the *_cells check kernels.
+ *   cells_x * cells_y <= 65536: an LSD radix sort over the 16-bit cell id in two 8-bit passes, per-wave digit
+ *   histograms in LDS, fixed-order scans, no atomics.  Points outside the index region are clamped into its border
+ *   cells, and the 3 x 3 search of the check kernels stays exhaustive: clamping to an interval is monotone and
+ *   non-expansive, so a point whose true cell is within one cell of a pose's true cell (in x and in y) is still within
+ *   one after both are clamped.  n_obstacles = 0 is valid: cell_start_dev <- zeros, nothing else is touched.
+ *   workspace: nfopp_cell_index_workspace_bytes(n_obstacles) bytes of device scratch. */
+int nfopp_grid_to_points(const void* grid_dev, int32_t is_int8, int32_t rows, int32_t cols, float threshold,
+                         double resolution, double origin_x, double origin_y, double origin_cos, double origin_sin,
+                         int32_t max_points, float* points_dev, double* points64_dev, int32_t* count_dev, void* stream);
+size_t nfopp_cell_index_workspace_bytes(int32_t n_obstacles);
+int nfopp_build_cell_index(const float* obstacles_dev, int32_t n_obstacles, float cell_x0, float cell_y0, float cell_size,
+                           int32_t cells_x, int32_t cells_y, float* obstacles_sorted_dev, int32_t* cell_start_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

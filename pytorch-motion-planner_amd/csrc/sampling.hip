@@ -159,6 +159,14 @@ __device__ __forceinline__ bool closer_than(float dx, float dy, float radius) {
   return sqrtf(__builtin_fmaf(dx, dx, dy * dy)) < radius;
 }
 
+// obstacle (dx, dy away from the pose) strictly inside the box of a robot heading (c, s) = (cos, sin), ONE arithmetic for
+// both rectangle kernels: the explicit fmas are the form the brute-force kernel has always compiled to, so its labels
+// stay where they were and the indexed kernel cannot be contracted differently
+__device__ __forceinline__ bool inside_box(float dx, float dy, float c, float s, const float* box) {
+  const float rx = __builtin_fmaf(c, dx, s * dy), ry = __builtin_fmaf(c, dy, -(s * dx));
+  return (rx > box[0]) & (rx < box[1]) & (ry > box[2]) & (ry < box[3]);
+}
+
 __device__ __forceinline__ bool out_of_bounds(const CheckArgs& a, float x, float y) {
   // nfop/collision_checker/collision_checker.py:12-19
   return a.has_bounds && (x > a.bounds[1] || x < a.bounds[0] || y > a.bounds[3] || y < a.bounds[2]);
@@ -191,22 +199,25 @@ __global__ __launch_bounds__(SM_THREADS) void check_points_kernel(const CheckArg
       if (MODE == 0) {
         hit |= closer_than(dx, dy, a.radius);
       } else {
-        const float rx = c * dx + s * dy, ry = -s * dx + c * dy;
-        hit |= rx > a.box[0] && rx < a.box[1] && ry > a.box[2] && ry < a.box[3];
+        hit |= inside_box(dx, dy, c, s, a.box);
       }
     }
   }
   if (valid) a.labels[p] = (hit || out_of_bounds(a, x, y)) ? 1.0f : 0.0f;
 }
 
-// mode 0 with a uniform cell index: the obstacle points are sorted by cell (cell_start[c] .. cell_start[c+1]) and the cell
-// size is at least the robot radius, so every point closer than the radius lies in the 3 x 3 cells around the pose's
-// cell.  The per-point predicate is the same fp32 arithmetic as check_points_kernel<0>: identical labels, 1/40 of the
-// distance tests on the 300-disc map.
+// modes 0 and 1 with a uniform cell index: the obstacle points are sorted by cell (cell_start[c] .. cell_start[c+1]) and
+// the cell size is at least the robot's reach (the disc's radius; the largest distance from the box robot's origin to a
+// corner of its box), so every point the predicate can accept lies in the 3 x 3 cells around the pose's cell.  The
+// per-point predicate is the same fp32 arithmetic as check_points_kernel<MODE>: identical labels, 1/40 of the distance
+// tests on the 300-disc map.  The index comes from nfopp_build_cell_index (csrc/obstacle_map.hip).
+template <int MODE>
 __global__ __launch_bounds__(SM_THREADS) void check_points_cells_kernel(const CheckArgs a) {
   const long long p = blockIdx.x * (long long)SM_THREADS + threadIdx.x;
   if (p >= a.n) return;
   const float x = a.poses[p * a.dim], y = a.poses[p * a.dim + 1];
+  float c = 1.f, s = 0.f;
+  if (MODE == 1) { const float th = a.poses[p * a.dim + 2]; c = cosf(th); s = sinf(th); }
   int cx = (int)floorf((x - a.cell_x0) / a.cell_size), cy = (int)floorf((y - a.cell_y0) / a.cell_size);
   cx = min(max(cx, 0), a.cells_x - 1);
   cy = min(max(cy, 0), a.cells_y - 1);
@@ -215,7 +226,7 @@ __global__ __launch_bounds__(SM_THREADS) void check_points_cells_kernel(const Ch
     const int c0 = yy * a.cells_x + max(cx - 1, 0), c1 = yy * a.cells_x + min(cx + 1, a.cells_x - 1);
     for (int k = a.cell_start[c0]; k < a.cell_start[c1 + 1]; ++k) {   // the row's cells are contiguous in the sorted array
       const float dx = a.obstacles[2 * k] - x, dy = a.obstacles[2 * k + 1] - y;
-      hit |= closer_than(dx, dy, a.radius);
+      hit |= MODE == 0 ? closer_than(dx, dy, a.radius) : inside_box(dx, dy, c, s, a.box);
     }
   }
   a.labels[p] = (hit || out_of_bounds(a, x, y)) ? 1.0f : 0.0f;
@@ -241,7 +252,8 @@ static int launch_check(const CheckArgs& a, int mode, hipStream_t st) {
   const unsigned grid = (unsigned)((a.n + SM_THREADS - 1) / SM_THREADS);
   if (mode == 0) hipLaunchKernelGGL(check_points_kernel<0>, dim3(grid), dim3(SM_THREADS), 0, st, a);
   else if (mode == 1) hipLaunchKernelGGL(check_points_kernel<1>, dim3(grid), dim3(SM_THREADS), 0, st, a);
-  else if (mode == 3) hipLaunchKernelGGL(check_points_cells_kernel, dim3(grid), dim3(SM_THREADS), 0, st, a);
+  else if (mode == 3) hipLaunchKernelGGL(check_points_cells_kernel<0>, dim3(grid), dim3(SM_THREADS), 0, st, a);
+  else if (mode == 4) hipLaunchKernelGGL(check_points_cells_kernel<1>, dim3(grid), dim3(SM_THREADS), 0, st, a);
   else hipLaunchKernelGGL(check_grid_kernel, dim3(grid), dim3(SM_THREADS), 0, st, a);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;
@@ -300,6 +312,27 @@ extern "C" int nfopp_check_collision_rectangle(const float* poses_dev, int64_t n
   a.obstacles = obstacles_dev; a.n_obstacles = n_obstacles;
   for (int k = 0; k < 4; ++k) a.box[k] = box4[k];
   return launch_check(a, 1, (hipStream_t)stream);
+}
+
+extern "C" int nfopp_check_collision_rectangle_cells(const float* poses_dev, int64_t n,
+                                                     const float* obstacles_sorted_dev, int32_t n_obstacles,
+                                                     const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y,
+                                                     float cell_x0, float cell_y0, float cell_size, const float* box4,
+                                                     float reach, const float* bounds4, float* labels_dev, void* stream) {
+  CheckArgs a = {};
+  int rc = fill_common(&a, poses_dev, n, 3, bounds4, labels_dev);
+  if (rc) return rc;
+  NFOPP_REQUIRE(box4, "null box");
+  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev && cell_start_dev, "bad obstacle index");
+  float corner = 0.f;   // the reach the caller states must cover every corner of the box (up to its fp32 rounding)
+  for (int k = 0; k < 4; ++k) corner = fmaxf(corner, hypotf(box4[k & 1], box4[2 + (k >> 1)]));
+  NFOPP_REQUIRE(cells_x > 0 && cells_y > 0 && reach > 0.f && reach * 1.00001f >= corner && cell_size >= reach,
+                "the cell size must be at least the robot's reach, and the reach must cover the corners of the box");
+  a.obstacles = obstacles_sorted_dev; a.n_obstacles = n_obstacles;
+  for (int k = 0; k < 4; ++k) a.box[k] = box4[k];
+  a.cell_start = cell_start_dev; a.cells_x = cells_x; a.cells_y = cells_y;
+  a.cell_x0 = cell_x0; a.cell_y0 = cell_y0; a.cell_size = cell_size;
+  return launch_check(a, 4, (hipStream_t)stream);
 }
 
 extern "C" int nfopp_check_collision_grid(const float* poses_dev, int64_t n, int32_t pose_dim, const uint8_t* grid_dev,

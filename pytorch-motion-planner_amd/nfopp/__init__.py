@@ -11,13 +11,13 @@ from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fi
 from .host_utils import (AttributeDict, CircleCollisionChecker,
                          CircleDirectedCollisionChecker, CollisionChecker, Position2, RectangleCollisionChecker,
                          TrajectoryInitializer)
-from .learning import BatchSampler, DeviceCircleChecker, DeviceGridChecker, DeviceRectangleChecker
+from .learning import BatchSampler, DeviceCircleChecker, DeviceGridChecker, DeviceGridMap, DeviceRectangleChecker
 from .onf_model import ONF
 from .path_tools import PathPostprocessor, init_trajectories
 from .planner import ConstrainedNERFOptPlanner, ContinuousPlanner, NERFOptPlanner
 
 __all__ = [
-    "BatchPlanner", "BatchSampler", "DeviceCircleChecker", "DeviceGridChecker", "DeviceRectangleChecker", "OnfFitter", "shard_range", "straight_line_init", "LIB_PATH", "NfoppError", "load_library", "TrajectoryEngine", "TrajectoryHyper", "band_of", "inverse_hessian",
+    "BatchPlanner", "BatchSampler", "DeviceCircleChecker", "DeviceGridChecker", "DeviceGridMap", "DeviceRectangleChecker", "OnfFitter", "shard_range", "straight_line_init", "LIB_PATH", "NfoppError", "load_library", "TrajectoryEngine", "TrajectoryHyper", "band_of", "inverse_hessian",
     "DEFAULT_PARAMETERS", "PlannerFactory", "UniversalFactory", "AstarTrajectoryInitializer", "AttributeDict",
     "CircleCollisionChecker", "CircleDirectedCollisionChecker", "CollisionChecker", "Position2",
     "RectangleCollisionChecker", "TrajectoryInitializer", "ONF", "ConstrainedNERFOptPlanner", "ContinuousPlanner",

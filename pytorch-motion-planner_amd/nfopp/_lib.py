@@ -95,6 +95,10 @@ _SIGNATURES = {
                                                           ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float), _P, _P]),
     "nfopp_check_collision_rectangle": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int32,
                                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _P, _P]),
+    "nfopp_check_collision_rectangle_cells": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int32, _P, ctypes.c_int32,
+                                                             ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                             ctypes.POINTER(ctypes.c_float), ctypes.c_float,
+                                                             ctypes.POINTER(ctypes.c_float), _P, _P]),
     "nfopp_check_collision_grid": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
                                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "nfopp_sample_candidates": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -115,6 +119,12 @@ _SIGNATURES = {
     "nfopp_grid_seed_trajectories": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int32,
                                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
                                                     ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
+    "nfopp_grid_to_points": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P]),
+    "nfopp_cell_index_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
+    "nfopp_build_cell_index": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                              ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -20,31 +20,135 @@ def _f4(values):
     return (ctypes.c_float * 4)(*[float(v) for v in values])
 
 
-class DeviceCircleChecker(object):
-    """Disc robot against a point cloud + bounds (nfop/collision_checker/circle_collision_checker.py).  With more than a
-    few obstacle points they are sorted into a uniform cell index (cell >= robot radius) once, on the host, and every
-    pose tests the points of its 3 x 3 cells only: same predicate, same labels."""
+class DeviceGridMap(object):
+    """Occupancy grid on the device (nfop/ros/grid_map.py).  `data` [rows, cols] is the fp32 image of `GridMap` (a cell is
+    occupied above `threshold`) or, through `from_occupancy_data`, the raw int8 image of a ROS OccupancyGrid; `origin` =
+    (x, y, theta) of the map frame.  The point cloud is built by nfopp_grid_to_points in float64 like the reference's and
+    handed to the checkers as fp32; reading its size back is the one host synchronisation per map."""
+
+    def __init__(self, data, resolution, origin=(0.0, 0.0, 0.0), threshold=0.5, device="cuda"):
+        if isinstance(data, torch.Tensor):
+            raw = data.dtype == torch.int8
+            self._map = data.detach().to(device=device, dtype=torch.int8 if raw else torch.float32).contiguous()
+        else:
+            data = np.asarray(data)
+            raw = data.dtype == np.int8
+            self._map = torch.tensor(np.ascontiguousarray(data, dtype=np.int8 if raw else np.float32), device=device)
+        if self._map.dim() != 2:
+            raise ValueError("the map is a [rows, cols] image")
+        self._raw = raw
+        self._resolution, self._threshold = float(resolution), float(threshold)
+        self._origin = tuple(float(v) for v in origin)
+        self._points = self._points64 = None
+
+    @classmethod
+    def from_occupancy_data(cls, int8_data, width, height, resolution, origin, device="cuda"):
+        """`GridMap.from_ros_occupancy_grid` (grid_map.py:31-40) without the message: `int8_data` is OccupancyGrid.data
+        (row-major, -1 unknown, 0..100 occupancy percent); the unpacking happens in the kernel."""
+        if isinstance(int8_data, torch.Tensor):
+            data = int8_data.to(torch.int8).reshape(int(height), int(width))
+        else:
+            data = np.asarray(int8_data).astype(np.int8).reshape(int(height), int(width))
+        return cls(data, resolution, origin, device=device)
+
+    def _build(self):
+        rows, cols = self._map.shape
+        x, y, theta = self._origin
+        c, s = float(np.cos(theta)), float(np.sin(theta))   # the calls Position2.apply makes
+        lib, grid = _lib.load(), _lib.ptr(self._map, self._map.dtype)
+        count = torch.zeros(1, dtype=torch.int32, device=self._map.device)
+
+        def run(max_points, p32, p64):
+            _lib.check(lib.nfopp_grid_to_points(grid, int(self._raw), rows, cols, self._threshold, self._resolution, x, y,
+                                                c, s, max_points, _lib.ptr(p32), _lib.ptr(p64, torch.float64),
+                                                _lib.ptr(count, torch.int32), _lib.stream_ptr()))
+        run(0, None, None)
+        n = int(count.item())
+        self._points = torch.empty(n, 2, dtype=torch.float32, device=self._map.device)
+        self._points64 = torch.empty(n, 2, dtype=torch.float64, device=self._map.device)
+        if n:
+            run(n, self._points, self._points64)
+
+    def as_point_cloud(self, dtype=torch.float32):
+        """Device tensor [n, 2] of the occupied cells' centres in row-major cell order (cached); fp32 is the rounding of
+        the float64 cloud (`dtype=torch.float64`), which equals the reference's."""
+        if self._points is None:
+            self._build()
+        return self._points64 if dtype == torch.float64 else self._points
+
+    @property
+    def boundaries(self):
+        rows, cols = self._map.shape   # grid_map.py:22-29
+        left, bottom = self._origin[0], self._origin[1]
+        return left, left + cols * self._resolution, bottom, bottom + rows * self._resolution
+
+
+class _PointCloudChecker(object):
+    """What the two point-cloud checkers share: the obstacle set, its cell index and the reference's update interface
+    (nfop/collision_checker/collision_checker.py:21-28).  With INDEX_FROM points or more the points are sorted into a
+    uniform cell index on the device (nfopp_build_cell_index; cell >= the robot's reach) and every pose tests the points
+    of its 3 x 3 cells only: same predicate, same labels.  `cells` = (cell_start, nx, ny, x0, y0, size) or None."""
+
+    def _setup(self, obstacle_points, boundaries, device):
+        self.device, self.boundaries = device, boundaries
+        self.update_obstacle_points(obstacle_points)
+
+    def update_obstacle_points(self, points):
+        """Replaces the obstacle set by `points` [n, 2] (numpy array or device tensor) and rebuilds the index."""
+        if isinstance(points, torch.Tensor):
+            pts = points.detach().to(device=self.device, dtype=torch.float32).reshape(-1, 2).contiguous()
+        else:
+            pts = torch.tensor(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2), device=self.device)
+        n, reach = pts.shape[0], self._reach()
+        self.cells, self.obstacles = None, pts
+        if n < self.INDEX_FROM or n == 0 or not reach > 0:
+            return
+        lo, hi = (v.cpu().numpy() for v in torch.aminmax(pts, dim=0))   # fp32; the geometry is fixed on the host
+        # a little more than the reach: fp32 rounding of the cell arithmetic must not move a point two cells away
+        size = np.float32(max(reach * 1.001, float((hi - lo).max()) / 64.0))
+        nx, ny = (int(np.floor((hi[k] - lo[k]) / size)) + 1 for k in (0, 1))
+        lib = _lib.load()
+        nbytes = lib.nfopp_cell_index_workspace_bytes(n)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+        ordered = torch.empty_like(pts)
+        start = torch.empty(nx * ny + 1, dtype=torch.int32, device=pts.device)
+        _lib.check(lib.nfopp_build_cell_index(_lib.ptr(pts), n, float(lo[0]), float(lo[1]), float(size), nx, ny,
+                                              _lib.ptr(ordered), _lib.ptr(start, torch.int32), _lib.ptr(work, torch.uint8),
+                                              nbytes, _lib.stream_ptr()))
+        self.obstacles = ordered
+        self.cells = (start, nx, ny, float(lo[0]), float(lo[1]), float(size))
+
+    def update_boundaries(self, boundaries):
+        self.boundaries = boundaries
+
+    def get_boundaries(self):
+        return self.boundaries
+
+    def update_from_map(self, grid_map, extra_points=None):
+        """One sensor message (`CollisionCheckerAdapter._callback`, nfop/ros/collision_checker_adapter.py:17-27): the
+        sensor's points first, then the map's, and the boundaries from the map."""
+        pts = grid_map.as_point_cloud()
+        if extra_points is not None:
+            if isinstance(extra_points, torch.Tensor):
+                extra = extra_points.detach().to(device=pts.device, dtype=torch.float32).reshape(-1, 2)
+            else:
+                extra = torch.tensor(np.ascontiguousarray(extra_points, dtype=np.float32).reshape(-1, 2), device=pts.device)
+            pts = torch.cat([extra, pts], 0)
+        self.update_obstacle_points(pts)
+        self.update_boundaries(grid_map.boundaries)
+
+
+class DeviceCircleChecker(_PointCloudChecker):
+    """Disc robot against a point cloud + bounds (nfop/collision_checker/circle_collision_checker.py)."""
 
     INDEX_FROM = 32   # obstacle points from which the cell index pays
 
     def __init__(self, obstacle_points, robot_radius, boundaries=None, device="cuda"):
-        pts = np.ascontiguousarray(obstacle_points, dtype=np.float32).reshape(-1, 2)
-        self.radius, self.boundaries = float(robot_radius), boundaries
-        self.cells = None
-        if len(pts) >= self.INDEX_FROM and self.radius > 0:
-            lo, hi = pts.min(0), pts.max(0)
-            # a little more than the radius: fp32 rounding of the cell arithmetic must not move a point two cells away
-            size = np.float32(max(self.radius * 1.001, float((hi - lo).max()) / 64.0))
-            nx, ny = (int(np.floor((hi[k] - lo[k]) / size)) + 1 for k in (0, 1))
-            # the kernel's own cell arithmetic (fp32 subtract, divide, floor), so points and poses agree on the cells
-            cx = np.clip(np.floor((pts[:, 0] - lo[0]) / size).astype(np.int64), 0, nx - 1)
-            cy = np.clip(np.floor((pts[:, 1] - lo[1]) / size).astype(np.int64), 0, ny - 1)
-            cell = cy * nx + cx
-            order = np.argsort(cell, kind="stable")
-            start = np.searchsorted(cell[order], np.arange(nx * ny + 1)).astype(np.int32)
-            pts = pts[order]
-            self.cells = (torch.tensor(start, device=device), nx, ny, float(lo[0]), float(lo[1]), float(size))
-        self.obstacles = torch.tensor(pts, device=device)
+        self.radius = float(robot_radius)
+        self._setup(obstacle_points, boundaries, device)
+
+    def _reach(self):
+        return self.radius
 
     def labels(self, poses, out=None):
         n, d = poses.shape
@@ -63,20 +167,35 @@ class DeviceCircleChecker(object):
         return out
 
 
-class DeviceRectangleChecker(object):
+class DeviceRectangleChecker(_PointCloudChecker):
     """Box robot (x0, x1, y0, y1 in its own frame) against a point cloud (rectangle_collision_checker.py)."""
 
+    INDEX_FROM = 48   # obstacle points from which the cell index pays: the measured crossover (profiles/obstacle_map.txt)
+
     def __init__(self, obstacle_points, box, boundaries=None, device="cuda"):
-        self.obstacles = torch.tensor(np.ascontiguousarray(obstacle_points, dtype=np.float32), device=device).reshape(-1, 2)
-        self.box, self.boundaries = tuple(box), boundaries
+        self.box = tuple(float(v) for v in box)
+        self._setup(obstacle_points, boundaries, device)
+
+    def _reach(self):
+        """Largest distance from the robot origin to a corner of the box (the box need not contain the origin)."""
+        x0, x1, y0, y1 = self.box
+        return float(np.hypot(max(abs(x0), abs(x1)), max(abs(y0), abs(y1))))
 
     def labels(self, poses, out=None):
         n = poses.shape[0]
         out = torch.empty(n, dtype=torch.float32, device=poses.device) if out is None else out
         b = _f4(self.boundaries) if self.boundaries is not None else None
-        _lib.check(_lib.load().nfopp_check_collision_rectangle(_lib.ptr(poses), n, _lib.ptr(self.obstacles),
-                                                               self.obstacles.shape[0], _f4(self.box), b, _lib.ptr(out),
-                                                               _lib.stream_ptr()))
+        lib = _lib.load()
+        if self.cells is None:
+            _lib.check(lib.nfopp_check_collision_rectangle(_lib.ptr(poses), n, _lib.ptr(self.obstacles),
+                                                           self.obstacles.shape[0], _f4(self.box), b, _lib.ptr(out),
+                                                           _lib.stream_ptr()))
+        else:
+            start, nx, ny, x0, y0, size = self.cells
+            _lib.check(lib.nfopp_check_collision_rectangle_cells(_lib.ptr(poses), n, _lib.ptr(self.obstacles),
+                                                                 self.obstacles.shape[0], _lib.ptr(start, torch.int32), nx,
+                                                                 ny, x0, y0, size, _f4(self.box), self._reach(), b,
+                                                                 _lib.ptr(out), _lib.stream_ptr()))
         return out
 
 
