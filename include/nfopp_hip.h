@@ -393,6 +393,84 @@ int nfopp_build_cell_index(const float* obstacles_dev, int32_t n_obstacles, floa
                            int32_t cells_x, int32_t cells_y, float* obstacles_sorted_dev, int32_t* cell_start_dev,
                            void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- nearest-obstacle clearance and per-path statistics (csrc/clearance.hip), additive under ABI 6 -------------------
+ * What a user who picks among the paths of a batch asks beside `collides` and `length`.  The batch axis is this library's
+ * own and so are these definitions (the reference reports a length; bench-mr's metric code is not part of it).
+ *
+ * nfopp_nearest_obstacle / nfopp_nearest_obstacle_cells: dist_dev[p] <- the minimum over ALL obstacle points k of d(p, k),
+ *   index_dev[p] (may be null) <- the smallest k attaining it, an index into the obstacle array passed in (the sorted one
+ *   for _cells).  box4 is a host pointer, as in the checkers:
+ *     box4 = NULL, disc robot: dx = ox - x, dy = oy - y, d = sqrtf(fmaf(dx, dx, dy * dy)) -- the argument
+ *       nfopp_check_collision_circle compares with the radius, through the one function both call.  sqrtf and `<` are
+ *       monotone, so dist < radius IS that checker's obstacle term for every pose, bit for bit.
+ *     box4 = (x0, x1, y0, y1), box robot, pose_dim must be 3: (rx, ry) as nfopp_check_collision_rectangle forms them
+ *       (the same function), ex = max(x0 - rx, rx - x1, 0), ey alike, d = sqrtf(fmaf(ex, ex, ey * ey)): the distance from
+ *       the obstacle point to the CLOSED box, 0 inside it.  A point the rectangle checker accepts has d == 0, and d > 0
+ *       implies that the checker's obstacle term is false; a point exactly on the rim has d == 0 without being a collision.
+ *   n_obstacles = 0: every pose gets +inf and -1.  A pose with a non-finite component gets +inf and -1, and so does a
+ *   pose so far away that every fp32 distance overflows.  n = 0 is a no-op.
+ *   nfopp_nearest_obstacle tests all pairs with the points staged in LDS: for small clouds, and the independent
+ *   cross-check.  nfopp_nearest_obstacle_cells takes the index of nfopp_build_cell_index (any cell size: there is no
+ *   "at least the reach" condition here) and searches outward from the pose's clamped cell in rings of growing Chebyshev
+ *   radius r, one thread per pose, keeping the lexicographic minimum of (d, k).  It stops after ring r when the visited
+ *   rectangle of cells has reached the index's border on all four sides, or when
+ *       (r - 1/16) * cell_size * (1 - 2^-18) - reach  >  best distance so far        (strictly: ties go to the smaller k)
+ *   with reach = 0 for the disc and the largest corner distance of the box, formed inside the call, otherwise.  The left
+ *   side is a lower bound on the computed distance of every unvisited point: a side of the visited rectangle that lies on
+ *   the border has nothing beyond it, because the border cells hold every point clamped into them; on the other sides a
+ *   point in an unvisited column (row) differs from the pose by more than r - 2.1 * 2^-24 * 2^17 cells, the fp32 rounding
+ *   of the two cell numbers, however far outside the region the pose is; the box is contained in the disc of radius reach
+ *   about the robot's origin; 2^-18 covers the rounding of the distance itself (csrc/clearance.hip has the full argument).
+ *   At most max(cells_x, cells_y) rings, whatever the pose holds.  No atomics; both entries return the same bits, run
+ *   after run.
+ * nfopp_nearest_obstacle_cells_probe: the measurements behind the work distribution (tools/clearance_timing.py).
+ *   what = 0: the same search with one wave per group of 4 poses, the lanes sharing each run of points -- the same bits,
+ *   5 % slower at the checkers' cell sizes, kept as a cross-check.  what = 1: index_dev[p] <- the
+ *   rings pose p's search takes, dist_dev untouched.
+ *
+ * nfopp_path_stats: stats_dev [B, NFOPP_NUM_PATH_STATS] float64, one workgroup per path, for the polyline start,
+ *   waypoints, goal (N + 2 points p_0 .. p_{N+1}, read as fp32, widened), segments e_i = p_{i+1} - p_i with
+ *   n_i = sqrt(ex * ex + ey * ey).  Everything in float64 with every operation rounded on its own; sums in a fixed order
+ *   (strided partial sums, a tree inside each wave, then the waves in order), extrema with the first index attaining them.
+ *     0 NFOPP_PATH_STAT_LENGTH         sum of n_i
+ *     1 NFOPP_PATH_STAT_MAX_CURVATURE  max over interior vertices i = 1..N of the Menger curvature
+ *                                      (2 * |ex0 * ey1 - ey0 * ex1|) / ((n0 * n1) * |p_{i+1} - p_{i-1}|), e0 = e_{i-1}, e1 = e_i;
+ *                                      a vertex with a zero factor in the denominator is no candidate; 0 without candidates
+ *     2 NFOPP_PATH_STAT_CURVATURE_AT   full-trajectory index i of the first vertex attaining it, -1 without candidates
+ *     3 NFOPP_PATH_STAT_CUSPS          vertices with n0 > 0, n1 > 0 and ex0 * ex1 + ey0 * ey1 < cos_cusp * (n0 * n1)
+ *     4 NFOPP_PATH_STAT_REVERSALS      dim 3 only, else 0: with s_i = cos(theta_i) * ex_i + sin(theta_i) * ey_i (theta_i the
+ *                                      heading of p_i; the device's float64 cos / sin), pairs of consecutive NON-ZERO s_i
+ *                                      of opposite sign
+ *     5 NFOPP_PATH_STAT_MIN_CLEARANCE  min of pose_dist_dev[b, 0 .. poses_per_path)   (+inf when pose_dist_dev is null)
+ *     6 NFOPP_PATH_STAT_CLEARANCE_AT   the first pose index attaining it              (-1)
+ *     7 NFOPP_PATH_STAT_MEAN_CLEARANCE sum / poses_per_path                           (+inf)
+ *   pose_dist_dev [B, poses_per_path] (may be null) is whatever the caller measured along the densified path
+ *   (nfopp_path_interpolate, then a nearest-obstacle query).  active_dev (may be null) is accepted for symmetry with the
+ *   other per-path calls and NOT consulted: rows with active == 0 are written too, statistics are wanted for retired paths. */
+#define NFOPP_NUM_PATH_STATS 8
+#define NFOPP_PATH_STAT_LENGTH 0
+#define NFOPP_PATH_STAT_MAX_CURVATURE 1
+#define NFOPP_PATH_STAT_CURVATURE_AT 2
+#define NFOPP_PATH_STAT_CUSPS 3
+#define NFOPP_PATH_STAT_REVERSALS 4
+#define NFOPP_PATH_STAT_MIN_CLEARANCE 5
+#define NFOPP_PATH_STAT_CLEARANCE_AT 6
+#define NFOPP_PATH_STAT_MEAN_CLEARANCE 7
+int nfopp_nearest_obstacle(const float* poses_dev, int64_t n, int32_t pose_dim, const float* obstacles_dev,
+                           int32_t n_obstacles, const float* box4, float* dist_dev, int32_t* index_dev, void* stream);
+int nfopp_nearest_obstacle_cells(const float* poses_dev, int64_t n, int32_t pose_dim, const float* obstacles_sorted_dev,
+                                 int32_t n_obstacles, const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y,
+                                 float cell_x0, float cell_y0, float cell_size, const float* box4, float* dist_dev,
+                                 int32_t* index_dev, void* stream);
+int nfopp_nearest_obstacle_cells_probe(int32_t what, const float* poses_dev, int64_t n, int32_t pose_dim,
+                                       const float* obstacles_sorted_dev, int32_t n_obstacles,
+                                       const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y, float cell_x0,
+                                       float cell_y0, float cell_size, const float* box4, float* dist_dev,
+                                       int32_t* index_dev, void* stream);
+int nfopp_path_stats(const float* traj_dev, const float* start_dev, const float* goal_dev, int64_t batch,
+                     int32_t n_waypoints, int32_t dim, const float* pose_dist_dev, int32_t poses_per_path,
+                     double cos_cusp, double* stats_dev, const uint8_t* active_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,428 @@
+// Nearest-obstacle distance for a set of poses, and per-path statistics for a batch of trajectories: what a user who picks
+// among the paths of a batch asks beside `collides` and `length` (csrc/path_eval.hip) -- how far a path stays from the
+// obstacles, how sharply it turns, whether it reverses.  The batch axis and these statistics are this library's own (the
+// reference plans one path and reports its length); the definitions are stated in include/nfopp_hip.h.
+//
+//   * nfopp_nearest_obstacle        all pairs, obstacle points staged in LDS (the shape of check_points_kernel)
+//   * nfopp_nearest_obstacle_cells  the same minimum over the checkers' cell index, searched ring by ring (below)
+//   * nfopp_path_stats              one workgroup per path, float64, fixed-order reductions
+// The per-point distance is the fp32 expression of csrc/point_dist.h that the ground-truth checkers compare, so the
+// query and the checkers cannot disagree about a pose.  No atomics; every minimum is the lexicographic minimum of
+// (distance, index), which does not depend on the order the points are visited in: the two entries, the two work
+// distributions of the indexed one and any two runs give the same bits.
+#include "common.h"
+#include "point_dist.h"
+
+// nfopp_path_stats is compared with numpy bit for bit: every float64 operation rounded on its own.  (The fp32 distance
+// expressions hold their fmas explicitly and are unaffected.)
+#pragma clang fp contract(off)
+
+namespace nfopp {
+
+constexpr int NR_THREADS = 256;
+constexpr int NR_WAVE_POSES = 4;              // poses one wave searches one after the other in the wave form
+constexpr int NR_MAX_CELLS = 65536;           // nfopp_build_cell_index's limit
+
+struct NearArgs {
+  const float* poses; long long n; int dim;
+  const float* obstacles; int n_obstacles;
+  float box[4]; float reach;
+  const int* cell_start; int cells_x, cells_y; float cell_x0, cell_y0, cell_size;
+  float* dist; int* index;
+};
+
+struct Pose { float x, y, c, s; bool finite; };
+
+// MODE 0: disc robot, the pose's origin.  MODE 1: box robot.  A pose with a non-finite component has no distance
+// (fmaxf would drop a NaN of the box arithmetic and report 0): it is flagged here and answered +inf / -1.
+template <int MODE>
+__device__ __forceinline__ Pose load_pose(const NearArgs& a, long long p) {
+  Pose q;
+  q.x = a.poses[p * a.dim];
+  q.y = a.poses[p * a.dim + 1];
+  q.c = 1.f; q.s = 0.f;
+  q.finite = isfinite(q.x) && isfinite(q.y);
+  if (MODE == 1) {
+    const float th = a.poses[p * a.dim + 2];
+    q.finite = q.finite && isfinite(th);
+    q.c = cosf(th); q.s = sinf(th);
+  }
+  return q;
+}
+
+// distance from obstacle point (ox, oy) to the robot at pose q: the argument of the circle checker's comparison, or the
+// distance to the closed box (0 inside it and on its rim) with (rx, ry) as the rectangle checker forms them
+template <int MODE>
+__device__ __forceinline__ float point_distance(const NearArgs& a, const Pose& q, float ox, float oy) {
+  const float dx = ox - q.x, dy = oy - q.y;
+  if (MODE == 0) return disc_distance(dx, dy);
+  float rx, ry;
+  robot_frame(dx, dy, q.c, q.s, &rx, &ry);
+  const float ex = fmaxf(fmaxf(a.box[0] - rx, rx - a.box[1]), 0.f);
+  const float ey = fmaxf(fmaxf(a.box[2] - ry, ry - a.box[3]), 0.f);
+  return sqrtf(__builtin_fmaf(ex, ex, ey * ey));
+}
+
+// (best, bestk) <- lexicographic minimum with (d, k).  A NaN or +inf distance never enters: the initial (+inf, -1) stays.
+__device__ __forceinline__ void take_min(float d, int k, float* best, int* bestk) {
+  if (d < *best || (d == *best && k < *bestk)) { *best = d; *bestk = k; }
+}
+
+__device__ __forceinline__ void store_result(const NearArgs& a, long long p, bool finite, float best, int bestk) {
+  a.dist[p] = finite ? best : __builtin_inff();
+  if (a.index) a.index[p] = finite ? bestk : -1;
+}
+
+// ---- all pairs ------------------------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(NR_THREADS) void nearest_kernel(const NearArgs a) {
+  __shared__ float ox[NR_THREADS], oy[NR_THREADS];
+  const long long p = blockIdx.x * (long long)NR_THREADS + threadIdx.x;
+  const bool valid = p < a.n;
+  Pose q = {0.f, 0.f, 1.f, 0.f, false};
+  if (valid) q = load_pose<MODE>(a, p);
+  float best = __builtin_inff();
+  int bestk = -1;
+  for (int base = 0; base < a.n_obstacles; base += NR_THREADS) {
+    __syncthreads();
+    if (base + (int)threadIdx.x < a.n_obstacles) {
+      ox[threadIdx.x] = a.obstacles[2 * (long long)(base + threadIdx.x)];
+      oy[threadIdx.x] = a.obstacles[2 * (long long)(base + threadIdx.x) + 1];
+    }
+    __syncthreads();
+    const int m = min(NR_THREADS, a.n_obstacles - base);
+    for (int k = 0; k < m; ++k) take_min(point_distance<MODE>(a, q, ox[k], oy[k]), base + k, &best, &bestk);
+  }
+  if (valid) store_result(a, p, q.finite, best, bestk);
+}
+
+// ---- cell index: search in rings, and when it may stop -----------------------------------------------------------------
+// The pose's cell (cx, cy) is formed like a point's (nfopp_build_cell_index: u = fl(fl(v - x0) / size), floor, clamp).
+// Ring r holds the cells at Chebyshev distance exactly r from it, clipped to the index; after ring r the cells of the
+// rectangle [cx - r, cx + r] x [cy - r, cy + r] have been visited.  A side of that rectangle that has reached the index's
+// border has nothing beyond it: the border cells hold every point that was clamped into them, however far outside the
+// region it lies, so that side of the visited area extends to infinity.  The search stops after ring r when all four
+// sides are at the border (every point has been visited; at r = max(cells_x, cells_y) - 1 at the latest, which bounds the
+// loop whatever the pose holds) or when   L(r) = (r - 1/16) * size * (1 - 2^-18) - reach  >  best,
+// reach = 0 for the disc, the largest corner distance of the box (rounded up) otherwise.  Why L(r) is a lower bound on
+// the COMPUTED distance of every unvisited point, say one whose cell column qx exceeds cx + r (the other three cases
+// mirror it):
+//  (1) qx >= cx + r + 1 is a clamped value >= 1, so the point's unclamped floor is at least as large: u(point) >= cx + r + 1.
+//      Unvisited columns to the right exist only if cx + r < cells_x - 1; then cx was not clamped from above, the pose's
+//      unclamped floor is <= cx, and u(pose) < cx + 1 -- also for a pose left of the region, whose negative floor was
+//      clamped to 0.  A pose outside the region therefore needs no case of its own.
+//  (2) u(v) = t(v) (1 + e), t(v) = (v - x0) / size exactly, |e| <= 2.1 * 2^-24 (one subtraction, one correctly rounded
+//      division).  From (1): t(point) >= (cx + r + 1)(1 - |e|), and t(pose) < (cx + 1)(1 + |e|) or t(pose) <= 0, so
+//      t(point) - t(pose) > r - |e| (2 cx + r + 2) >= r - 2.1 * 2^-24 * 2^17 > r - 1/16   (cx + r + 1 <= 65535).
+//      Only cell numbers enter, never the pose's own magnitude: the bound holds for a pose 10^6 cells away.
+//  (3) The point is therefore more than A = (r - 1/16) * size away along x, exactly.  Disc: dx = fl(ox - x) >= A (1 - 2^-24),
+//      and sqrtf(fma(dx, dx, dy * dy)) >= |dx| (1 - 2^-23) as rounding and sqrtf are monotone and dy * dy >= 0.
+//      Box: the box lies inside the disc of radius `reach` about the robot's origin, so the exact distance to it is at
+//      least |point - pose| - reach >= A - reach; the fp32 evaluation (cosf / sinf within 2 ulp, five roundings for rx, ry,
+//      three for the distance) is below the exact one by less than 10 * 2^-24 (|dx| + |dy|) <= 15 * 2^-24 |point - pose|,
+//      and a bound of the form |point - pose| (1 - k 2^-24) - reach grows with |point - pose|, so it holds at A.
+//      The factor 1 - 2^-18 (64 * 2^-24) covers both cases and the roundings of forming L(r) itself.
+//  (4) Ties: a point at exactly the best distance with a smaller index must still be found, hence the strict L(r) > best.
+// L(0) < 0: ring 1 is always searched, unless the index is a single cell.
+template <int MODE, bool WAVE>
+__device__ __forceinline__ void scan_points(const NearArgs& a, const Pose& q, int k0, int k1, float* best, int* bestk) {
+  for (int k = k0 + (WAVE ? (int)(threadIdx.x & 63) : 0); k < k1; k += WAVE ? 64 : 1)
+    take_min(point_distance<MODE>(a, q, a.obstacles[2 * (long long)k], a.obstacles[2 * (long long)k + 1]), k, best, bestk);
+}
+
+// WAVE = false: the calling thread visits every point.  WAVE = true: the 64 lanes of a wave hold the same pose, split
+// each run of points among them and combine their minima after every ring.  *rings (may be null) <- rings searched.
+template <int MODE, bool WAVE>
+__device__ __forceinline__ void nearest_in_cells(const NearArgs& a, const Pose& q, float* best_out, int* bestk_out,
+                                                 int* rings) {
+  const int nx = a.cells_x, ny = a.cells_y;
+  // clamped as a float, like cell_of (csrc/obstacle_map.hip): no out-of-range value is converted to int
+  const int cx = (int)fminf(fmaxf(floorf((q.x - a.cell_x0) / a.cell_size), 0.f), (float)(nx - 1));
+  const int cy = (int)fminf(fmaxf(floorf((q.y - a.cell_y0) / a.cell_size), 0.f), (float)(ny - 1));
+  float best = __builtin_inff();
+  int bestk = -1, r = 0;
+  const int r_end = max(nx, ny);
+  for (; r < r_end; ++r) {
+    const int x_lo = max(cx - r, 0), x_hi = min(cx + r, nx - 1);
+    // the two rows of the ring: their cells are contiguous in the sorted array
+    if (cy - r >= 0) {
+      const int row = (cy - r) * nx;
+      scan_points<MODE, WAVE>(a, q, a.cell_start[row + x_lo], a.cell_start[row + x_hi + 1], &best, &bestk);
+    }
+    if (r > 0 && cy + r <= ny - 1) {
+      const int row = (cy + r) * nx;
+      scan_points<MODE, WAVE>(a, q, a.cell_start[row + x_lo], a.cell_start[row + x_hi + 1], &best, &bestk);
+    }
+    // the two columns between them
+    for (int yy = max(cy - r + 1, 0); yy <= min(cy + r - 1, ny - 1); ++yy) {
+      if (cx - r >= 0) {
+        const int c = yy * nx + cx - r;
+        scan_points<MODE, WAVE>(a, q, a.cell_start[c], a.cell_start[c + 1], &best, &bestk);
+      }
+      if (cx + r <= nx - 1) {
+        const int c = yy * nx + cx + r;
+        scan_points<MODE, WAVE>(a, q, a.cell_start[c], a.cell_start[c + 1], &best, &bestk);
+      }
+    }
+    if (WAVE) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) take_min(__shfl_xor(best, o), __shfl_xor(bestk, o), &best, &bestk);
+    }
+    const bool closed = cx - r <= 0 && cx + r >= nx - 1 && cy - r <= 0 && cy + r >= ny - 1;
+    const float lower = __builtin_fmaf(((float)r - 0.0625f) * a.cell_size, 1.0f - 3.814697265625e-06f, -a.reach);
+    if (closed || lower > best) { ++r; break; }
+  }
+  *best_out = best;
+  *bestk_out = bestk;
+  if (rings) *rings = r;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(NR_THREADS) void nearest_cells_kernel(const NearArgs a) {
+  const long long p = blockIdx.x * (long long)NR_THREADS + threadIdx.x;
+  if (p >= a.n) return;
+  const Pose q = load_pose<MODE>(a, p);
+  float best = __builtin_inff();
+  int bestk = -1;
+  if (q.finite) nearest_in_cells<MODE, false>(a, q, &best, &bestk, nullptr);
+  store_result(a, p, q.finite, best, bestk);
+}
+
+// the other work distribution: a wave searches NR_WAVE_POSES poses one after the other, 64 points at a time
+template <int MODE>
+__global__ __launch_bounds__(NR_THREADS) void nearest_cells_wave_kernel(const NearArgs a) {
+  const long long wave = blockIdx.x * (long long)(NR_THREADS / 64) + (threadIdx.x >> 6);
+  for (int j = 0; j < NR_WAVE_POSES; ++j) {
+    const long long p = wave * NR_WAVE_POSES + j;
+    if (p >= a.n) return;   // the same for every lane of the wave
+    const Pose q = load_pose<MODE>(a, p);
+    float best = __builtin_inff();
+    int bestk = -1;
+    if (q.finite) nearest_in_cells<MODE, true>(a, q, &best, &bestk, nullptr);
+    if ((threadIdx.x & 63) == 0) store_result(a, p, q.finite, best, bestk);
+  }
+}
+
+// rings each pose's search takes (tools/clearance_timing.py reports their distribution)
+template <int MODE>
+__global__ __launch_bounds__(NR_THREADS) void nearest_rings_kernel(const NearArgs a) {
+  const long long p = blockIdx.x * (long long)NR_THREADS + threadIdx.x;
+  if (p >= a.n) return;
+  const Pose q = load_pose<MODE>(a, p);
+  float best;
+  int bestk, rings = 0;
+  if (q.finite) nearest_in_cells<MODE, false>(a, q, &best, &bestk, &rings);
+  a.index[p] = rings;
+}
+
+// ---- per-path statistics ------------------------------------------------------------------------------------------------
+struct StatsArgs {
+  const float* traj; const float* start; const float* goal;
+  int n, dim;
+  const float* pose_dist; int poses;
+  double cos_cusp;
+  double* stats;
+};
+
+constexpr int PS_THREADS = 256;
+constexpr int PS_WAVES = PS_THREADS / 64;
+
+// workgroup sum in a fixed order: xor tree inside each wave, then the waves one after the other (path_interpolate_kernel's)
+__device__ __forceinline__ double block_sum(double v, double* red /* LDS [PS_WAVES] */) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
+  __syncthreads();   // `red` may still be read by a previous call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < PS_WAVES; ++w) s = s + red[w];
+  return s;
+}
+
+// workgroup extremum with the first index attaining it: SIGN = +1 maximum, -1 minimum; index -1 = no candidate
+template <int SIGN>
+__device__ __forceinline__ bool better(double v, int i, double o, int oi) {
+  if (i < 0) return false;
+  if (oi < 0) return true;
+  return (SIGN > 0 ? v > o : v < o) || (v == o && i < oi);
+}
+template <int SIGN>
+__device__ __forceinline__ void block_extremum(double* v, int* i, double* red, int* redi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(*v, o);
+    const int oi = __shfl_xor(*i, o);
+    if (better<SIGN>(ov, oi, *v, *i)) { *v = ov; *i = oi; }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = *v; redi[threadIdx.x >> 6] = *i; }
+  __syncthreads();
+  double bv = red[0];
+  int bi = redi[0];
+  for (int w = 1; w < PS_WAVES; ++w)
+    if (better<SIGN>(red[w], redi[w], bv, bi)) { bv = red[w]; bi = redi[w]; }
+  *v = bv; *i = bi;
+}
+
+template <int D>
+__global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs a) {
+  extern __shared__ signed char sgn[];   // [N + 1]: sign of each segment's forward component (dim 3)
+  __shared__ double red[PS_WAVES];
+  __shared__ int redi[PS_WAVES];
+  const long long b = blockIdx.x;
+  const int N = a.n;
+  const float* tr = a.traj + b * N * D;
+  auto point = [&](int f, int d) {  // full trajectory index 0..N+1, widened
+    return (double)(f == 0 ? a.start[b * D + d] : (f == N + 1 ? a.goal[b * D + d] : tr[(long long)(f - 1) * D + d]));
+  };
+  // segments i = 0..N: length, forward sign
+  double len = 0.0;
+  for (int i = threadIdx.x; i <= N; i += PS_THREADS) {
+    const double ex = point(i + 1, 0) - point(i, 0), ey = point(i + 1, 1) - point(i, 1);
+    len = len + sqrt(ex * ex + ey * ey);
+    if (D == 3) {
+      const double th = point(i, 2);
+      const double fwd = cos(th) * ex + sin(th) * ey;
+      sgn[i] = fwd > 0.0 ? 1 : (fwd < 0.0 ? -1 : 0);
+    }
+  }
+  len = block_sum(len, red);   // its barriers also publish sgn[]
+  // interior vertices i = 1..N between segments i - 1 and i
+  double kmax = 0.0;
+  int kidx = -1, cusps = 0, reversals = 0;
+  for (int i = 1 + threadIdx.x; i <= N; i += PS_THREADS) {
+    const double x0 = point(i - 1, 0), y0 = point(i - 1, 1), x1 = point(i, 0), y1 = point(i, 1);
+    const double x2 = point(i + 1, 0), y2 = point(i + 1, 1);
+    const double ex0 = x1 - x0, ey0 = y1 - y0, ex1 = x2 - x1, ey1 = y2 - y1, cx = x2 - x0, cy = y2 - y0;
+    const double n0 = sqrt(ex0 * ex0 + ey0 * ey0), n1 = sqrt(ex1 * ex1 + ey1 * ey1), ch = sqrt(cx * cx + cy * cy);
+    if (n0 > 0.0 && n1 > 0.0) {
+      if (ch > 0.0) {
+        const double k = (2.0 * fabs(ex0 * ey1 - ey0 * ex1)) / ((n0 * n1) * ch);
+        if (kidx < 0 || k > kmax) { kmax = k; kidx = i; }
+      }
+      if (ex0 * ex1 + ey0 * ey1 < a.cos_cusp * (n0 * n1)) ++cusps;
+    }
+    if (D == 3 && sgn[i] != 0) {   // against the last non-zero sign before it
+      int j = i - 1;
+      while (j >= 0 && sgn[j] == 0) --j;
+      if (j >= 0 && sgn[j] != sgn[i]) ++reversals;
+    }
+  }
+  block_extremum<+1>(&kmax, &kidx, red, redi);
+  const double n_cusps = block_sum((double)cusps, red), n_rev = block_sum((double)reversals, red);   // integers: exact
+  // clearance along the densified path
+  double dmin = (double)__builtin_inff(), dmean = (double)__builtin_inff();
+  int didx = -1;
+  if (a.pose_dist) {
+    const float* pd = a.pose_dist + b * a.poses;
+    double sum = 0.0, m = 0.0;
+    int mi = -1;
+    for (int k = threadIdx.x; k < a.poses; k += PS_THREADS) {
+      const double v = (double)pd[k];
+      sum = sum + v;
+      if (mi < 0 || v < m) { m = v; mi = k; }
+    }
+    block_extremum<-1>(&m, &mi, red, redi);
+    sum = block_sum(sum, red);
+    dmin = m; didx = mi; dmean = sum / (double)a.poses;
+  }
+  if (threadIdx.x == 0) {
+    double* o = a.stats + b * NFOPP_NUM_PATH_STATS;
+    o[0] = len; o[1] = kidx < 0 ? 0.0 : kmax; o[2] = (double)kidx; o[3] = n_cusps; o[4] = n_rev;
+    o[5] = dmin; o[6] = (double)didx; o[7] = dmean;
+  }
+}
+
+template <int MODE>
+static void launch_nearest(const NearArgs& a, int form, hipStream_t st) {
+  const unsigned grid = (unsigned)((a.n + NR_THREADS - 1) / NR_THREADS);
+  if (form == 0) hipLaunchKernelGGL(nearest_kernel<MODE>, dim3(grid), dim3(NR_THREADS), 0, st, a);
+  else if (form == 1) hipLaunchKernelGGL(nearest_cells_kernel<MODE>, dim3(grid), dim3(NR_THREADS), 0, st, a);
+  else if (form == 3) hipLaunchKernelGGL(nearest_rings_kernel<MODE>, dim3(grid), dim3(NR_THREADS), 0, st, a);
+  else {
+    const long long per_group = (long long)(NR_THREADS / 64) * NR_WAVE_POSES;
+    hipLaunchKernelGGL(nearest_cells_wave_kernel<MODE>, dim3((unsigned)((a.n + per_group - 1) / per_group)),
+                       dim3(NR_THREADS), 0, st, a);
+  }
+}
+
+// form: 0 all pairs, 1 cell index with one thread per pose, 2 cell index with one wave per group of poses, 3 ring counts
+static int nearest(int form, const float* poses_dev, int64_t n, int32_t pose_dim, const float* obstacles_dev,
+                   int32_t n_obstacles, const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y, float cell_x0,
+                   float cell_y0, float cell_size, const float* box4, float* dist_dev, int32_t* index_dev, void* stream) {
+  NFOPP_REQUIRE(n >= 0 && (pose_dim == 2 || pose_dim == 3), "need n >= 0 and pose_dim 2 or 3");
+  NFOPP_REQUIRE(n <= (int64_t)0x7fffffff * NR_WAVE_POSES, "too many poses for one call");
+  NFOPP_REQUIRE(!box4 || pose_dim == 3, "the box robot needs poses with a heading (pose_dim 3)");
+  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
+  if (form != 0) {
+    NFOPP_REQUIRE(cells_x > 0 && cells_y > 0 && (long long)cells_x * cells_y <= NR_MAX_CELLS,
+                  "the index holds between 1 and 65536 cells");
+    NFOPP_REQUIRE(cell_size > 0.f && cell_size == cell_size, "the cell size must be positive");
+    NFOPP_REQUIRE(cell_start_dev || (n_obstacles == 0 && form != 3), "null cell index");
+  }
+  if (n == 0) return NFOPP_OK;
+  NFOPP_REQUIRE(poses_dev && dist_dev && (form != 3 || index_dev), "null device pointer");
+  NearArgs a = {};
+  a.poses = poses_dev; a.n = n; a.dim = pose_dim; a.obstacles = obstacles_dev; a.n_obstacles = n_obstacles;
+  a.cell_start = cell_start_dev; a.cells_x = cells_x; a.cells_y = cells_y;
+  a.cell_x0 = cell_x0; a.cell_y0 = cell_y0; a.cell_size = cell_size;
+  a.dist = dist_dev; a.index = index_dev;
+  if (box4) {
+    for (int k = 0; k < 4; ++k) a.box[k] = box4[k];
+    // the largest distance from the robot's origin to a corner of the box, rounded up
+    a.reach = hypotf(fmaxf(fabsf(box4[0]), fabsf(box4[1])), fmaxf(fabsf(box4[2]), fabsf(box4[3]))) * 1.000001f;
+  }
+  if (n_obstacles == 0 && form != 3) form = 0;   // nothing to search: the all-pairs kernel writes +inf / -1
+  if (box4) launch_nearest<1>(a, form, (hipStream_t)stream);
+  else launch_nearest<0>(a, form, (hipStream_t)stream);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}
+
+}  // namespace nfopp
+
+using namespace nfopp;
+
+extern "C" int nfopp_nearest_obstacle(const float* poses_dev, int64_t n, int32_t pose_dim, const float* obstacles_dev,
+                                      int32_t n_obstacles, const float* box4, float* dist_dev, int32_t* index_dev,
+                                      void* stream) {
+  return nearest(0, poses_dev, n, pose_dim, obstacles_dev, n_obstacles, nullptr, 0, 0, 0.f, 0.f, 0.f, box4, dist_dev,
+                 index_dev, stream);
+}
+
+extern "C" int nfopp_nearest_obstacle_cells(const float* poses_dev, int64_t n, int32_t pose_dim,
+                                            const float* obstacles_sorted_dev, int32_t n_obstacles,
+                                            const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y, float cell_x0,
+                                            float cell_y0, float cell_size, const float* box4, float* dist_dev,
+                                            int32_t* index_dev, void* stream) {
+  return nearest(1, poses_dev, n, pose_dim, obstacles_sorted_dev, n_obstacles, cell_start_dev, cells_x, cells_y, cell_x0,
+                 cell_y0, cell_size, box4, dist_dev, index_dev, stream);
+}
+
+extern "C" int nfopp_nearest_obstacle_cells_probe(int32_t what, const float* poses_dev, int64_t n, int32_t pose_dim,
+                                                  const float* obstacles_sorted_dev, int32_t n_obstacles,
+                                                  const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y,
+                                                  float cell_x0, float cell_y0, float cell_size, const float* box4,
+                                                  float* dist_dev, int32_t* index_dev, void* stream) {
+  NFOPP_REQUIRE(what == 0 || what == 1, "what: 0 = the wave form, 1 = ring counts");
+  return nearest(what == 0 ? 2 : 3, poses_dev, n, pose_dim, obstacles_sorted_dev, n_obstacles, cell_start_dev, cells_x,
+                 cells_y, cell_x0, cell_y0, cell_size, box4, dist_dev, index_dev, stream);
+}
+
+extern "C" int nfopp_path_stats(const float* traj_dev, const float* start_dev, const float* goal_dev, int64_t batch,
+                                int32_t n_waypoints, int32_t dim, const float* pose_dist_dev, int32_t poses_per_path,
+                                double cos_cusp, double* stats_dev, const uint8_t* active_dev, void* stream) {
+  (void)active_dev;   // statistics are wanted for retired paths too: every row is written
+  NFOPP_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
+  NFOPP_REQUIRE(batch >= 0 && batch <= 0x7fffffffLL && n_waypoints >= 1, "bad batch / waypoint count");
+  NFOPP_REQUIRE(poses_per_path >= (pose_dist_dev ? 1 : 0), "bad pose count");
+  NFOPP_REQUIRE(cos_cusp == cos_cusp, "cos_cusp is not a number");
+  if (batch == 0) return NFOPP_OK;
+  NFOPP_REQUIRE(traj_dev && start_dev && goal_dev && stats_dev, "null device pointer");
+  StatsArgs a;
+  a.traj = traj_dev; a.start = start_dev; a.goal = goal_dev; a.n = n_waypoints; a.dim = dim;
+  a.pose_dist = pose_dist_dev; a.poses = poses_per_path; a.cos_cusp = cos_cusp; a.stats = stats_dev;
+  const size_t lds = ((size_t)n_waypoints + 1 + 15) & ~(size_t)15;
+  return launch_dynamic_lds(dim == 3 ? path_stats_kernel<3> : path_stats_kernel<2>, batch, PS_THREADS, lds, stream, a,
+                            "path too long");
+}

@@ -12,6 +12,7 @@
 // All draws come from Philox4x32-10 (key = seed, counter = (draw index, trajectory, offset, stream)), so a run is
 // reproducible and independent of how trajectories are sharded over GPUs; oracle/nfopp_oracle.py restates it.
 #include "common.h"
+#include "point_dist.h"
 
 namespace nfopp {
 
@@ -156,14 +157,15 @@ struct CheckArgs {
 // |obstacle - pose| < radius, ONE arithmetic for every circle kernel (an explicit fma: left to the compiler the two kernels
 // contracted dx*dx + dy*dy differently and disagreed on poses within an ulp of a rim)
 __device__ __forceinline__ bool closer_than(float dx, float dy, float radius) {
-  return sqrtf(__builtin_fmaf(dx, dx, dy * dy)) < radius;
+  return disc_distance(dx, dy) < radius;
 }
 
 // obstacle (dx, dy away from the pose) strictly inside the box of a robot heading (c, s) = (cos, sin), ONE arithmetic for
 // both rectangle kernels: the explicit fmas are the form the brute-force kernel has always compiled to, so its labels
 // stay where they were and the indexed kernel cannot be contracted differently
 __device__ __forceinline__ bool inside_box(float dx, float dy, float c, float s, const float* box) {
-  const float rx = __builtin_fmaf(c, dx, s * dy), ry = __builtin_fmaf(c, dy, -(s * dx));
+  float rx, ry;
+  robot_frame(dx, dy, c, s, &rx, &ry);
   return (rx > box[0]) & (rx < box[1]) & (ry > box[2]) & (ry < box[3]);
 }
 

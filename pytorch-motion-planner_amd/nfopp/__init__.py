@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's planner interface over libnfopp_hip.so (C ABI: include/nfopp_hip.h).
 """
-from ._lib import LIB_PATH, NfoppError, load as load_library
+from ._lib import LIB_PATH, NUM_PATH_STATS, PATH_STAT_NAMES, NfoppError, load as load_library
 from .batch import BatchPlanner, OnfFitter, shard_range, straight_line_init
 from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
@@ -16,11 +16,17 @@ from .onf_model import ONF
 from .path_tools import PathPostprocessor, init_trajectories
 from .planner import ConstrainedNERFOptPlanner, ContinuousPlanner, NERFOptPlanner
 
+# slots of BatchPlanner.path_stats' [B, 8] result (NFOPP_PATH_STAT_* of include/nfopp_hip.h)
+(PATH_STAT_LENGTH, PATH_STAT_MAX_CURVATURE, PATH_STAT_CURVATURE_AT, PATH_STAT_CUSPS, PATH_STAT_REVERSALS,
+ PATH_STAT_MIN_CLEARANCE, PATH_STAT_CLEARANCE_AT, PATH_STAT_MEAN_CLEARANCE) = range(NUM_PATH_STATS)
+
 __all__ = [
     "BatchPlanner", "BatchSampler", "DeviceCircleChecker", "DeviceGridChecker", "DeviceGridMap", "DeviceRectangleChecker", "OnfFitter", "shard_range", "straight_line_init", "LIB_PATH", "NfoppError", "load_library", "TrajectoryEngine", "TrajectoryHyper", "band_of", "inverse_hessian",
     "DEFAULT_PARAMETERS", "PlannerFactory", "UniversalFactory", "AstarTrajectoryInitializer", "AttributeDict",
     "CircleCollisionChecker", "CircleDirectedCollisionChecker", "CollisionChecker", "Position2",
     "RectangleCollisionChecker", "TrajectoryInitializer", "ONF", "ConstrainedNERFOptPlanner", "ContinuousPlanner",
     "NERFOptPlanner", "PathPostprocessor", "init_trajectories", "OccupancyGrid", "grid_search_init", "grid_search_paths",
-    "distance_fields", "seed_trajectories",
+    "distance_fields", "seed_trajectories", "NUM_PATH_STATS", "PATH_STAT_NAMES", "PATH_STAT_LENGTH",
+    "PATH_STAT_MAX_CURVATURE", "PATH_STAT_CURVATURE_AT", "PATH_STAT_CUSPS", "PATH_STAT_REVERSALS",
+    "PATH_STAT_MIN_CLEARANCE", "PATH_STAT_CLEARANCE_AT", "PATH_STAT_MEAN_CLEARANCE",
 ]

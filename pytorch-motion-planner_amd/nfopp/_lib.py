@@ -12,6 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libnfopp_hip.so")
 ABI_VERSION = 6
 NUM_TERMS = 8
+NUM_PATH_STATS = 8   # NFOPP_NUM_PATH_STATS; slot names: NFOPP_PATH_STAT_* of include/nfopp_hip.h
+PATH_STAT_NAMES = ("length", "max_curvature", "curvature_at", "cusps", "reversals", "min_clearance", "clearance_at",
+                   "mean_clearance")
 TERM_NAMES = ("total", "distance", "softplus_sum", "lambda_dot_c", "c_squared", "boundary", "cm_tanh", "direction")
 
 
@@ -125,6 +128,16 @@ _SIGNATURES = {
     "nfopp_cell_index_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
     "nfopp_build_cell_index": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                               ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
+    "nfopp_nearest_obstacle": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                                              ctypes.POINTER(ctypes.c_float), _P, _P, _P]),
+    "nfopp_nearest_obstacle_cells": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                    ctypes.POINTER(ctypes.c_float), _P, _P, _P]),
+    "nfopp_nearest_obstacle_cells_probe": (ctypes.c_int, [ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                                                          _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                                          ctypes.c_float, ctypes.POINTER(ctypes.c_float), _P, _P, _P]),
+    "nfopp_path_stats": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
+                                        ctypes.c_double, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

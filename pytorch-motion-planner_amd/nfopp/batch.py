@@ -281,10 +281,12 @@ class BatchPlanner(object):
         return self.engine.full_trajectory().detach().cpu().numpy()
 
     # ---- path evaluation, best-path bookkeeping, early stop (scripts/run_bench_mr.py:109-132 for the batch) ---------
-    def evaluate(self, checker=None, sub=4, early_stop=False):
+    def evaluate(self, checker=None, sub=4, early_stop=False, min_clearance=None):
         """Densifies every path (`sub` poses per segment), labels the poses with the ground-truth `checker`, keeps
         the shortest collision-free path per trajectory and -- with early_stop -- retires trajectories that are
-        collision-free but no longer improving.  Returns device tensors (collides uint8 [B], length [B])."""
+        collision-free but no longer improving.  With `min_clearance` (point-cloud checkers only) a pose also counts as
+        colliding when the footprint's clearance is below it: a safety margin without a fatter robot.  Returns device
+        tensors (collides uint8 [B], length [B])."""
         from . import _lib as L
         checker = checker or self.checker
         if checker is None:
@@ -308,11 +310,47 @@ class BatchPlanner(object):
         L.check(lib.nfopp_path_interpolate(L.ptr(eng.traj), L.ptr(eng.start), L.ptr(eng.goal), B, N, D, int(sub),
                                            L.ptr(self._poses), L.ptr(self._length), L.stream_ptr()))
         checker.labels(self._poses.view(B * m, D), out=self._pose_labels)
+        if min_clearance is not None:   # combined on the device, no synchronisation
+            clearance = checker.clearance(self._poses.view(B * m, D), out=self._pose_clearance(B * m))
+            self._pose_labels.masked_fill_(clearance < float(min_clearance), 1.0)
         L.check(lib.nfopp_path_select_best(L.ptr(self._pose_labels), L.ptr(self._length), L.ptr(eng.traj), B, m, N, D,
                                            L.ptr(self.best_traj), L.ptr(self.best_length),
                                            L.ptr(self._collides, torch.uint8),
                                            L.ptr(eng.active, torch.uint8) if early_stop else None, L.stream_ptr()))
         return self._collides, self._length
+
+    def _pose_clearance(self, count):
+        buf = getattr(self, "_clearance", None)
+        if buf is None or buf.numel() != count:
+            buf = self._clearance = torch.empty(count, dtype=torch.float32, device=self.engine.device)
+        return buf
+
+    def path_stats(self, checker=None, sub=4, cusp_angle=np.pi / 3):
+        """[B, 8] float64 device tensor of per-path statistics (nfopp_path_stats; slots nfopp.PATH_STAT_*): length, maximum
+        Menger curvature and its vertex, cusps, reversals, minimum clearance and its pose, mean clearance.  The clearance
+        is the checker's footprint clearance at the poses `evaluate` tests (`sub` per segment); without a point-cloud
+        checker those three slots are +inf, -1, +inf.  A vertex is a cusp when the path folds back there to within
+        `cusp_angle` of the way it came (the segments' directions differ by more than pi - cusp_angle).  Retired
+        trajectories are included.  Nothing here synchronises."""
+        from . import _lib as L
+        checker = checker or self.checker
+        eng = self.engine
+        B, N, D = eng.B, eng.N, eng.D
+        lib = L.load()
+        dist, m = None, 0
+        if checker is not None and hasattr(checker, "nearest"):
+            m = (N + 1) * int(sub) + 1
+            poses = torch.empty(B, m, D, dtype=torch.float32, device=eng.device)
+            length = torch.empty(B, dtype=torch.float32, device=eng.device)
+            L.check(lib.nfopp_path_interpolate(L.ptr(eng.traj), L.ptr(eng.start), L.ptr(eng.goal), B, N, D, int(sub),
+                                               L.ptr(poses), L.ptr(length), L.stream_ptr()))
+            dist = checker.clearance(poses.view(B * m, D))
+            self._stat_poses, self._stat_clearance = poses, dist.view(B, m)
+        stats = torch.empty(B, L.NUM_PATH_STATS, dtype=torch.float64, device=eng.device)
+        L.check(lib.nfopp_path_stats(L.ptr(eng.traj), L.ptr(eng.start), L.ptr(eng.goal), B, N, D, L.ptr(dist), m,
+                                     float(np.cos(np.pi - float(cusp_angle))), L.ptr(stats, torch.float64),
+                                     L.ptr(eng.active, torch.uint8), L.stream_ptr()))
+        return stats
 
     def best_paths(self):
         """[B, N+2, D]: the best collision-free path found so far, the current path where none was found yet."""

@@ -124,6 +124,37 @@ class _PointCloudChecker(object):
     def get_boundaries(self):
         return self.boundaries
 
+    _box = None   # the rectangle checker's (x0, x1, y0, y1); None = disc robot
+
+    def nearest(self, poses, out=None, index_out=None):
+        """(dist [n] fp32, index [n] int32) of the nearest obstacle point per pose (nfopp_nearest_obstacle[_cells]): for the
+        disc the distance to the robot's origin, the very number `labels` compares with the radius; for the box the
+        distance to the closed box, 0 inside it.  `index` points into `self.obstacles` (cell-sorted once an index exists),
+        the smallest index among equidistant points; +inf / -1 without obstacles.  The bounds play no part."""
+        n, d = poses.shape
+        dist = torch.empty(n, dtype=torch.float32, device=poses.device) if out is None else out
+        index = torch.empty(n, dtype=torch.int32, device=poses.device) if index_out is None else index_out
+        box = _f4(self._box) if self._box is not None else None
+        lib = _lib.load()
+        if self.cells is None:
+            _lib.check(lib.nfopp_nearest_obstacle(_lib.ptr(poses), n, d, _lib.ptr(self.obstacles), self.obstacles.shape[0],
+                                                  box, _lib.ptr(dist), _lib.ptr(index, torch.int32), _lib.stream_ptr()))
+        else:
+            start, nx, ny, x0, y0, size = self.cells
+            _lib.check(lib.nfopp_nearest_obstacle_cells(_lib.ptr(poses), n, d, _lib.ptr(self.obstacles),
+                                                        self.obstacles.shape[0], _lib.ptr(start, torch.int32), nx, ny, x0,
+                                                        y0, size, box, _lib.ptr(dist), _lib.ptr(index, torch.int32),
+                                                        _lib.stream_ptr()))
+        return dist, index
+
+    def clearance(self, poses, out=None):
+        """Free space around the robot's footprint at each pose [n] fp32: max(dist - radius, 0) for the disc (fp32 torch ops
+        on the device), the distance to the box itself for the rectangle.  0 where `labels` reports an obstacle."""
+        dist, _ = self.nearest(poses, out=out)
+        if self._box is None:
+            torch.sub(dist, self.radius, out=dist).clamp_(min=0)
+        return dist
+
     def update_from_map(self, grid_map, extra_points=None):
         """One sensor message (`CollisionCheckerAdapter._callback`, nfop/ros/collision_checker_adapter.py:17-27): the
         sensor's points first, then the map's, and the boundaries from the map."""
@@ -173,7 +204,7 @@ class DeviceRectangleChecker(_PointCloudChecker):
     INDEX_FROM = 48   # obstacle points from which the cell index pays: the measured crossover (profiles/obstacle_map.txt)
 
     def __init__(self, obstacle_points, box, boundaries=None, device="cuda"):
-        self.box = tuple(float(v) for v in box)
+        self.box = self._box = tuple(float(v) for v in box)
         self._setup(obstacle_points, boundaries, device)
 
     def _reach(self):
@@ -213,6 +244,10 @@ class DeviceGridChecker(object):
                                                           self.grid.shape[0], self.grid.shape[1], self.origin_x,
                                                           self.origin_y, self.cell_size, _lib.ptr(out), _lib.stream_ptr()))
         return out
+
+    def clearance(self, poses, out=None):
+        raise NotImplementedError("clearance needs a point cloud: use DeviceCircleChecker or DeviceRectangleChecker "
+                                  "(the occupancy image has no nearest-obstacle query)")
 
 
 class BatchSampler(object):
