@@ -378,7 +378,8 @@ int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int32_t* count_
  * nfopp_build_cell_index: obstacles_sorted_dev [n, 2] <- obstacles_dev stably sorted by cell, cell_start_dev
  *   [cells_x * cells_y + 1] <- first sorted point of each cell, bit for bit np.argsort(cell, kind="stable") and
  *   np.searchsorted(cell[order], arange(cells + 1)).  cell = cy * cells_x + cx with cx = floorf((x - cell_x0) /
- *   cell_size) in fp32 clamped to [0, cells_x - 1] (cy alike): the arithmetic of the *_cells check kernels.
+ *   cell_size) in fp32 clamped to [0, cells_x - 1] (cy alike): CellIndex::cell of csrc/point_cloud.h, the one function
+ *   the *_cells check kernels and the nearest-obstacle search form a pose's cell with.
  *   cells_x * cells_y <= 65536: an LSD radix sort over the 16-bit cell id in two 8-bit passes, per-wave digit
  *   histograms in LDS, fixed-order scans, no atomics.  Points outside the index region are clamped into its border
  *   cells, and the 3 x 3 search of the check kernels stays exhaustive: clamping to an interval is monotone and

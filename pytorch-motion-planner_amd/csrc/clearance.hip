@@ -3,65 +3,30 @@
 // obstacles, how sharply it turns, whether it reverses.  The batch axis and these statistics are this library's own (the
 // reference plans one path and reports its length); the definitions are stated in include/nfopp_hip.h.
 //
-//   * nfopp_nearest_obstacle        all pairs, obstacle points staged in LDS (the shape of check_points_kernel)
+//   * nfopp_nearest_obstacle        all pairs, obstacle points staged in LDS (for_all_points, as in check_points_kernel)
 //   * nfopp_nearest_obstacle_cells  the same minimum over the checkers' cell index, searched ring by ring (below)
 //   * nfopp_path_stats              one workgroup per path, float64, fixed-order reductions
-// The per-point distance is the fp32 expression of csrc/point_dist.h that the ground-truth checkers compare, so the
+// The per-point distance is the fp32 expression of csrc/point_cloud.h that the ground-truth checkers compare, so the
 // query and the checkers cannot disagree about a pose.  No atomics; every minimum is the lexicographic minimum of
 // (distance, index), which does not depend on the order the points are visited in: the two entries, the two work
 // distributions of the indexed one and any two runs give the same bits.
 #include "common.h"
-#include "point_dist.h"
+#include "point_cloud.h"
 
-// nfopp_path_stats is compared with numpy bit for bit: every float64 operation rounded on its own.  (The fp32 distance
-// expressions hold their fmas explicitly and are unaffected.)
+// nfopp_path_stats is compared with numpy bit for bit: every float64 operation rounded on its own.  (The fp32 expressions
+// of point_cloud.h hold their fmas explicitly and are unaffected.)
 #pragma clang fp contract(off)
 
 namespace nfopp {
 
 constexpr int NR_THREADS = 256;
 constexpr int NR_WAVE_POSES = 4;              // poses one wave searches one after the other in the wave form
-constexpr int NR_MAX_CELLS = 65536;           // nfopp_build_cell_index's limit
 
-struct NearArgs {
+struct NearArgs {   // a pose that load_pose flags as not finite is answered +inf / -1
   const float* poses; long long n; int dim;
-  const float* obstacles; int n_obstacles;
-  float box[4]; float reach;
-  const int* cell_start; int cells_x, cells_y; float cell_x0, cell_y0, cell_size;
+  PointCloud cloud; Robot robot;
   float* dist; int* index;
 };
-
-struct Pose { float x, y, c, s; bool finite; };
-
-// MODE 0: disc robot, the pose's origin.  MODE 1: box robot.  A pose with a non-finite component has no distance
-// (fmaxf would drop a NaN of the box arithmetic and report 0): it is flagged here and answered +inf / -1.
-template <int MODE>
-__device__ __forceinline__ Pose load_pose(const NearArgs& a, long long p) {
-  Pose q;
-  q.x = a.poses[p * a.dim];
-  q.y = a.poses[p * a.dim + 1];
-  q.c = 1.f; q.s = 0.f;
-  q.finite = isfinite(q.x) && isfinite(q.y);
-  if (MODE == 1) {
-    const float th = a.poses[p * a.dim + 2];
-    q.finite = q.finite && isfinite(th);
-    q.c = cosf(th); q.s = sinf(th);
-  }
-  return q;
-}
-
-// distance from obstacle point (ox, oy) to the robot at pose q: the argument of the circle checker's comparison, or the
-// distance to the closed box (0 inside it and on its rim) with (rx, ry) as the rectangle checker forms them
-template <int MODE>
-__device__ __forceinline__ float point_distance(const NearArgs& a, const Pose& q, float ox, float oy) {
-  const float dx = ox - q.x, dy = oy - q.y;
-  if (MODE == 0) return disc_distance(dx, dy);
-  float rx, ry;
-  robot_frame(dx, dy, q.c, q.s, &rx, &ry);
-  const float ex = fmaxf(fmaxf(a.box[0] - rx, rx - a.box[1]), 0.f);
-  const float ey = fmaxf(fmaxf(a.box[2] - ry, ry - a.box[3]), 0.f);
-  return sqrtf(__builtin_fmaf(ex, ex, ey * ey));
-}
 
 // (best, bestk) <- lexicographic minimum with (d, k).  A NaN or +inf distance never enters: the initial (+inf, -1) stays.
 __device__ __forceinline__ void take_min(float d, int k, float* best, int* bestk) {
@@ -80,40 +45,31 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_kernel(const NearArgs a) {
   const long long p = blockIdx.x * (long long)NR_THREADS + threadIdx.x;
   const bool valid = p < a.n;
   Pose q = {0.f, 0.f, 1.f, 0.f, false};
-  if (valid) q = load_pose<MODE>(a, p);
+  if (valid) q = load_pose<MODE>(a.poses, a.dim, p);
   float best = __builtin_inff();
   int bestk = -1;
-  for (int base = 0; base < a.n_obstacles; base += NR_THREADS) {
-    __syncthreads();
-    if (base + (int)threadIdx.x < a.n_obstacles) {
-      ox[threadIdx.x] = a.obstacles[2 * (long long)(base + threadIdx.x)];
-      oy[threadIdx.x] = a.obstacles[2 * (long long)(base + threadIdx.x) + 1];
-    }
-    __syncthreads();
-    const int m = min(NR_THREADS, a.n_obstacles - base);
-    for (int k = 0; k < m; ++k) take_min(point_distance<MODE>(a, q, ox[k], oy[k]), base + k, &best, &bestk);
-  }
+  for_all_points<NR_THREADS>(a.cloud, ox, oy, [&](float px, float py, int k) {
+    take_min(a.robot.point_distance<MODE>(q, px, py), k, &best, &bestk);
+  });
   if (valid) store_result(a, p, q.finite, best, bestk);
 }
 
 // ---- cell index: search in rings, and when it may stop -----------------------------------------------------------------
-// The pose's cell (cx, cy) is formed like a point's (nfopp_build_cell_index: u = fl(fl(v - x0) / size), floor, clamp).
-// Ring r holds the cells at Chebyshev distance exactly r from it, clipped to the index; after ring r the cells of the
-// rectangle [cx - r, cx + r] x [cy - r, cy + r] have been visited.  A side of that rectangle that has reached the index's
-// border has nothing beyond it: the border cells hold every point that was clamped into them, however far outside the
-// region it lies, so that side of the visited area extends to infinity.  The search stops after ring r when all four
-// sides are at the border (every point has been visited; at r = max(cells_x, cells_y) - 1 at the latest, which bounds the
-// loop whatever the pose holds) or when   L(r) = (r - 1/16) * size * (1 - 2^-18) - reach  >  best,
-// reach = 0 for the disc, the largest corner distance of the box (rounded up) otherwise.  Why L(r) is a lower bound on
-// the COMPUTED distance of every unvisited point, say one whose cell column qx exceeds cx + r (the other three cases
-// mirror it):
-//  (1) qx >= cx + r + 1 is a clamped value >= 1, so the point's unclamped floor is at least as large: u(point) >= cx + r + 1.
-//      Unvisited columns to the right exist only if cx + r < cells_x - 1; then cx was not clamped from above, the pose's
-//      unclamped floor is <= cx, and u(pose) < cx + 1 -- also for a pose left of the region, whose negative floor was
-//      clamped to 0.  A pose outside the region therefore needs no case of its own.
+// Ring r holds the cells at Chebyshev distance exactly r from the pose's cell (cx, cy), clipped to the index; after ring r
+// the rectangle [cx - r, cx + r] x [cy - r, cy + r] of cells has been visited.  A side of it that has reached the index's
+// border has nothing beyond it: the border cells hold every point that was clamped into them, so that side extends to
+// infinity.  The search stops after ring r when all four sides are at the border (at r = max(cells_x, cells_y) - 1 at the
+// latest, which bounds the loop whatever the pose holds) or when
+//     L(r) = (r - 1/16) * size * (1 - 2^-18) - reach  >  best        (reach: Robot::reach, 0 for the disc).
+// Why L(r) is a lower bound on the COMPUTED distance of every unvisited point, say one whose cell column qx exceeds
+// cx + r (the other three cases mirror it):
+//  (1) Pose and points get their cells from one function, CellIndex::cell: u(v) = fl(fl(v - x0) / size), floor, clamp.
+//      qx >= cx + r + 1 >= 1 is clamped, so the point's own u >= cx + r + 1.  Unvisited columns to the right exist only if
+//      cx + r < cells_x - 1; then cx was not clamped from above and u(pose) < cx + 1 -- also for a pose left of the
+//      region, whose negative floor was clamped to 0.  A pose outside the region needs no case of its own.
 //  (2) u(v) = t(v) (1 + e), t(v) = (v - x0) / size exactly, |e| <= 2.1 * 2^-24 (one subtraction, one correctly rounded
 //      division).  From (1): t(point) >= (cx + r + 1)(1 - |e|), and t(pose) < (cx + 1)(1 + |e|) or t(pose) <= 0, so
-//      t(point) - t(pose) > r - |e| (2 cx + r + 2) >= r - 2.1 * 2^-24 * 2^17 > r - 1/16   (cx + r + 1 <= 65535).
+//      t(point) - t(pose) > r - |e| (2 cx + r + 2) >= r - 2.1 * 2^-24 * 2^17 > r - 1/16   (cx + r + 1 < MAX_INDEX_CELLS).
 //      Only cell numbers enter, never the pose's own magnitude: the bound holds for a pose 10^6 cells away.
 //  (3) The point is therefore more than A = (r - 1/16) * size away along x, exactly.  Disc: dx = fl(ox - x) >= A (1 - 2^-24),
 //      and sqrtf(fma(dx, dx, dy * dy)) >= |dx| (1 - 2^-23) as rounding and sqrtf are monotone and dy * dy >= 0.
@@ -124,52 +80,44 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_kernel(const NearArgs a) {
 //      The factor 1 - 2^-18 (64 * 2^-24) covers both cases and the roundings of forming L(r) itself.
 //  (4) Ties: a point at exactly the best distance with a smaller index must still be found, hence the strict L(r) > best.
 // L(0) < 0: ring 1 is always searched, unless the index is a single cell.
+// the points of cells x_lo..x_hi of row yy.  WAVE = false: the calling thread visits every one.  WAVE = true: the 64 lanes
+// of a wave hold the same pose and split the run among them.
 template <int MODE, bool WAVE>
-__device__ __forceinline__ void scan_points(const NearArgs& a, const Pose& q, int k0, int k1, float* best, int* bestk) {
-  for (int k = k0 + (WAVE ? (int)(threadIdx.x & 63) : 0); k < k1; k += WAVE ? 64 : 1)
-    take_min(point_distance<MODE>(a, q, a.obstacles[2 * (long long)k], a.obstacles[2 * (long long)k + 1]), k, best, bestk);
+__device__ __forceinline__ void scan_cells(const NearArgs& a, const Pose& q, int yy, int x_lo, int x_hi, float* best,
+                                           int* bestk) {
+  int k, k1;
+  a.cloud.index.row_range(yy, x_lo, x_hi, &k, &k1);
+  const float* pt = a.cloud.points;
+  for (k += WAVE ? (int)(threadIdx.x & 63) : 0; k < k1; k += WAVE ? 64 : 1)
+    take_min(a.robot.point_distance<MODE>(q, pt[2 * (long long)k], pt[2 * (long long)k + 1]), k, best, bestk);
 }
 
-// WAVE = false: the calling thread visits every point.  WAVE = true: the 64 lanes of a wave hold the same pose, split
-// each run of points among them and combine their minima after every ring.  *rings (may be null) <- rings searched.
+// In the wave form the lanes combine their minima after every ring.  *rings (may be null) <- rings searched.
 template <int MODE, bool WAVE>
 __device__ __forceinline__ void nearest_in_cells(const NearArgs& a, const Pose& q, float* best_out, int* bestk_out,
                                                  int* rings) {
-  const int nx = a.cells_x, ny = a.cells_y;
-  // clamped as a float, like cell_of (csrc/obstacle_map.hip): no out-of-range value is converted to int
-  const int cx = (int)fminf(fmaxf(floorf((q.x - a.cell_x0) / a.cell_size), 0.f), (float)(nx - 1));
-  const int cy = (int)fminf(fmaxf(floorf((q.y - a.cell_y0) / a.cell_size), 0.f), (float)(ny - 1));
+  const int nx = a.cloud.index.cells_x, ny = a.cloud.index.cells_y;
+  int cx, cy;
+  a.cloud.index.cell(q.x, q.y, &cx, &cy);
   float best = __builtin_inff();
   int bestk = -1, r = 0;
   const int r_end = max(nx, ny);
   for (; r < r_end; ++r) {
     const int x_lo = max(cx - r, 0), x_hi = min(cx + r, nx - 1);
-    // the two rows of the ring: their cells are contiguous in the sorted array
-    if (cy - r >= 0) {
-      const int row = (cy - r) * nx;
-      scan_points<MODE, WAVE>(a, q, a.cell_start[row + x_lo], a.cell_start[row + x_hi + 1], &best, &bestk);
-    }
-    if (r > 0 && cy + r <= ny - 1) {
-      const int row = (cy + r) * nx;
-      scan_points<MODE, WAVE>(a, q, a.cell_start[row + x_lo], a.cell_start[row + x_hi + 1], &best, &bestk);
-    }
-    // the two columns between them
+    // the two rows of the ring
+    if (cy - r >= 0) scan_cells<MODE, WAVE>(a, q, cy - r, x_lo, x_hi, &best, &bestk);
+    if (r > 0 && cy + r <= ny - 1) scan_cells<MODE, WAVE>(a, q, cy + r, x_lo, x_hi, &best, &bestk);
+    // the two columns between them, a cell at a time
     for (int yy = max(cy - r + 1, 0); yy <= min(cy + r - 1, ny - 1); ++yy) {
-      if (cx - r >= 0) {
-        const int c = yy * nx + cx - r;
-        scan_points<MODE, WAVE>(a, q, a.cell_start[c], a.cell_start[c + 1], &best, &bestk);
-      }
-      if (cx + r <= nx - 1) {
-        const int c = yy * nx + cx + r;
-        scan_points<MODE, WAVE>(a, q, a.cell_start[c], a.cell_start[c + 1], &best, &bestk);
-      }
+      if (cx - r >= 0) scan_cells<MODE, WAVE>(a, q, yy, cx - r, cx - r, &best, &bestk);
+      if (cx + r <= nx - 1) scan_cells<MODE, WAVE>(a, q, yy, cx + r, cx + r, &best, &bestk);
     }
     if (WAVE) {
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) take_min(__shfl_xor(best, o), __shfl_xor(bestk, o), &best, &bestk);
     }
     const bool closed = cx - r <= 0 && cx + r >= nx - 1 && cy - r <= 0 && cy + r >= ny - 1;
-    const float lower = __builtin_fmaf(((float)r - 0.0625f) * a.cell_size, 1.0f - 3.814697265625e-06f, -a.reach);
+    const float lower = __builtin_fmaf(((float)r - 0.0625f) * a.cloud.index.size, 1.0f - 3.814697265625e-06f, -a.robot.reach);
     if (closed || lower > best) { ++r; break; }
   }
   *best_out = best;
@@ -181,7 +129,7 @@ template <int MODE>
 __global__ __launch_bounds__(NR_THREADS) void nearest_cells_kernel(const NearArgs a) {
   const long long p = blockIdx.x * (long long)NR_THREADS + threadIdx.x;
   if (p >= a.n) return;
-  const Pose q = load_pose<MODE>(a, p);
+  const Pose q = load_pose<MODE>(a.poses, a.dim, p);
   float best = __builtin_inff();
   int bestk = -1;
   if (q.finite) nearest_in_cells<MODE, false>(a, q, &best, &bestk, nullptr);
@@ -195,7 +143,7 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_cells_wave_kernel(const Ne
   for (int j = 0; j < NR_WAVE_POSES; ++j) {
     const long long p = wave * NR_WAVE_POSES + j;
     if (p >= a.n) return;   // the same for every lane of the wave
-    const Pose q = load_pose<MODE>(a, p);
+    const Pose q = load_pose<MODE>(a.poses, a.dim, p);
     float best = __builtin_inff();
     int bestk = -1;
     if (q.finite) nearest_in_cells<MODE, true>(a, q, &best, &bestk, nullptr);
@@ -208,7 +156,7 @@ template <int MODE>
 __global__ __launch_bounds__(NR_THREADS) void nearest_rings_kernel(const NearArgs a) {
   const long long p = blockIdx.x * (long long)NR_THREADS + threadIdx.x;
   if (p >= a.n) return;
-  const Pose q = load_pose<MODE>(a, p);
+  const Pose q = load_pose<MODE>(a.poses, a.dim, p);
   float best;
   int bestk, rings = 0;
   if (q.finite) nearest_in_cells<MODE, false>(a, q, &best, &bestk, &rings);
@@ -354,24 +302,18 @@ static int nearest(int form, const float* poses_dev, int64_t n, int32_t pose_dim
   NFOPP_REQUIRE(n <= (int64_t)0x7fffffff * NR_WAVE_POSES, "too many poses for one call");
   NFOPP_REQUIRE(!box4 || pose_dim == 3, "the box robot needs poses with a heading (pose_dim 3)");
   NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
+  NearArgs a = {};
   if (form != 0) {
-    NFOPP_REQUIRE(cells_x > 0 && cells_y > 0 && (long long)cells_x * cells_y <= NR_MAX_CELLS,
-                  "the index holds between 1 and 65536 cells");
-    NFOPP_REQUIRE(cell_size > 0.f && cell_size == cell_size, "the cell size must be positive");
-    NFOPP_REQUIRE(cell_start_dev || (n_obstacles == 0 && form != 3), "null cell index");
+    const int rc = fill_cell_index(&a.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size,
+                                   n_obstacles > 0 || form == 3);
+    if (rc) return rc;
+    NFOPP_REQUIRE((long long)cells_x * cells_y <= MAX_INDEX_CELLS, "the index holds between 1 and 65536 cells");
   }
   if (n == 0) return NFOPP_OK;
   NFOPP_REQUIRE(poses_dev && dist_dev && (form != 3 || index_dev), "null device pointer");
-  NearArgs a = {};
-  a.poses = poses_dev; a.n = n; a.dim = pose_dim; a.obstacles = obstacles_dev; a.n_obstacles = n_obstacles;
-  a.cell_start = cell_start_dev; a.cells_x = cells_x; a.cells_y = cells_y;
-  a.cell_x0 = cell_x0; a.cell_y0 = cell_y0; a.cell_size = cell_size;
+  a.poses = poses_dev; a.n = n; a.dim = pose_dim; a.cloud.points = obstacles_dev; a.cloud.n = n_obstacles;
   a.dist = dist_dev; a.index = index_dev;
-  if (box4) {
-    for (int k = 0; k < 4; ++k) a.box[k] = box4[k];
-    // the largest distance from the robot's origin to a corner of the box, rounded up
-    a.reach = hypotf(fmaxf(fabsf(box4[0]), fabsf(box4[1])), fmaxf(fabsf(box4[2]), fabsf(box4[3]))) * 1.000001f;
-  }
+  if (box4) set_box(&a.robot, box4);
   if (n_obstacles == 0 && form != 3) form = 0;   // nothing to search: the all-pairs kernel writes +inf / -1
   if (box4) launch_nearest<1>(a, form, (hipStream_t)stream);
   else launch_nearest<0>(a, form, (hipStream_t)stream);

@@ -7,6 +7,7 @@
 // Everything here is integer counting plus per-element arithmetic: no atomics, every sum in a fixed order, so both
 // results are bit-identical from run to run.  All kernels are latency-bound helpers that run at map rate.
 #include "common.h"
+#include "point_cloud.h"
 
 namespace nfopp {
 
@@ -155,22 +156,19 @@ static int launch_grid_to_points(const GridArgs& a, hipStream_t st) {
 // the points move.
 constexpr int IX_ROUNDS = 8;
 constexpr int IX_SEGMENT = 64 * IX_ROUNDS;            // 512 points per wave
-constexpr int IX_MAX_CELLS = 65536;
 
 struct IndexArgs {
   const float* in; float* out; int n, n_seg, shift;
-  float x0, y0, size; int cells_x, cells_y;
-  int* table;        // [256][n_seg]
+  CellIndex index;   // its cell_start is what index_cell_start_kernel writes:
   int* cell_start;   // [cells_x * cells_y + 1]
+  int* table;        // [256][n_seg]
 };
 
-// the cell arithmetic of check_points_cells_kernel (fp32 subtract, divide, floor, clamp); clamped as a float so that no
-// out-of-range value is converted to int (same cell for every finite coordinate, cell 0 of the axis for a NaN)
+// the sort key: the cell number the searching kernels will form for the same coordinates (CellIndex::cell)
 __device__ __forceinline__ int cell_of(const IndexArgs& a, float x, float y) {
-  const float fx = floorf((x - a.x0) / a.size), fy = floorf((y - a.y0) / a.size);
-  const int cx = (int)fminf(fmaxf(fx, 0.f), (float)(a.cells_x - 1));
-  const int cy = (int)fminf(fmaxf(fy, 0.f), (float)(a.cells_y - 1));
-  return cy * a.cells_x + cx;
+  int cx, cy;
+  a.index.cell(x, y, &cx, &cy);
+  return cy * a.index.cells_x + cx;
 }
 
 // lanes of the wave that hold a valid point with this lane's digit
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(OM_THREADS) void index_scan_kernel(const IndexArgs 
 // cell_start[c] = first sorted point whose cell is >= c (np.searchsorted, side="left")
 __global__ __launch_bounds__(OM_THREADS) void index_cell_start_kernel(const IndexArgs a) {
   const int c = blockIdx.x * OM_THREADS + threadIdx.x;
-  if (c > a.cells_x * a.cells_y) return;
+  if (c > a.index.cells_x * a.index.cells_y) return;
   int lo = 0, hi = a.n;
   while (lo < hi) {
     const int mid = lo + (hi - lo) / 2;
@@ -281,10 +279,10 @@ extern "C" int nfopp_build_cell_index(const float* obstacles_dev, int32_t n_obst
                                       int32_t* cell_start_dev, void* workspace_dev, size_t workspace_bytes,
                                       void* stream) {
   NFOPP_REQUIRE(n_obstacles >= 0, "negative obstacle count");
-  NFOPP_REQUIRE(cells_x > 0 && cells_y > 0 && (long long)cells_x * cells_y <= IX_MAX_CELLS,
-                "the index holds between 1 and 65536 cells");
-  NFOPP_REQUIRE(cell_size > 0.f && cell_size == cell_size, "the cell size must be positive");
-  NFOPP_REQUIRE(cell_start_dev, "null device pointer");
+  IndexArgs a = {};
+  const int rc = fill_cell_index(&a.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size);
+  if (rc) return rc;
+  NFOPP_REQUIRE((long long)cells_x * cells_y <= MAX_INDEX_CELLS, "the index holds between 1 and 65536 cells");
   hipStream_t st = (hipStream_t)stream;
   const int cells = cells_x * cells_y;
   if (n_obstacles == 0) {
@@ -294,9 +292,7 @@ extern "C" int nfopp_build_cell_index(const float* obstacles_dev, int32_t n_obst
   NFOPP_REQUIRE(obstacles_dev && obstacles_sorted_dev && workspace_dev, "null device pointer");
   NFOPP_REQUIRE(workspace_bytes >= nfopp_cell_index_workspace_bytes(n_obstacles),
                 "workspace smaller than nfopp_cell_index_workspace_bytes");
-  IndexArgs a = {};
   a.n = n_obstacles; a.n_seg = (n_obstacles + IX_SEGMENT - 1) / IX_SEGMENT;
-  a.x0 = cell_x0; a.y0 = cell_y0; a.size = cell_size; a.cells_x = cells_x; a.cells_y = cells_y;
   float* tmp = static_cast<float*>(workspace_dev);
   a.table = reinterpret_cast<int*>(static_cast<char*>(workspace_dev) + index_points_bytes(n_obstacles));
   a.cell_start = cell_start_dev;

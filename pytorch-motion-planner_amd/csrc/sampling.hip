@@ -12,7 +12,7 @@
 // All draws come from Philox4x32-10 (key = seed, counter = (draw index, trajectory, offset, stream)), so a run is
 // reproducible and independent of how trajectories are sharded over GPUs; oracle/nfopp_oracle.py restates it.
 #include "common.h"
-#include "point_dist.h"
+#include "point_cloud.h"
 
 namespace nfopp {
 
@@ -143,101 +143,62 @@ __global__ __launch_bounds__(SM_THREADS) void resample_pool_kernel(const Resampl
 }
 
 // ---- ground-truth checkers ------------------------------------------------------------------------------------
+// The cell index, the robot's predicate (Robot::hits<MODE>) and the all-pairs visit are those of csrc/point_cloud.h.
 struct CheckArgs {
   const float* poses; long long n; int dim;
-  const float* obstacles; int n_obstacles;
-  float radius; float box[4];
+  PointCloud cloud; Robot robot;
   int has_bounds; float bounds[4];
-  const unsigned char* grid; int rows, cols; double origin_x, origin_y, cell;
-  // circle checker with a cell index over the (cell-sorted) obstacle points
-  const int* cell_start; int cells_x, cells_y; float cell_x0, cell_y0, cell_size;
   float* labels;
 };
-
-// |obstacle - pose| < radius, ONE arithmetic for every circle kernel (an explicit fma: left to the compiler the two kernels
-// contracted dx*dx + dy*dy differently and disagreed on poses within an ulp of a rim)
-__device__ __forceinline__ bool closer_than(float dx, float dy, float radius) {
-  return disc_distance(dx, dy) < radius;
-}
-
-// obstacle (dx, dy away from the pose) strictly inside the box of a robot heading (c, s) = (cos, sin), ONE arithmetic for
-// both rectangle kernels: the explicit fmas are the form the brute-force kernel has always compiled to, so its labels
-// stay where they were and the indexed kernel cannot be contracted differently
-__device__ __forceinline__ bool inside_box(float dx, float dy, float c, float s, const float* box) {
-  float rx, ry;
-  robot_frame(dx, dy, c, s, &rx, &ry);
-  return (rx > box[0]) & (rx < box[1]) & (ry > box[2]) & (ry < box[3]);
-}
 
 __device__ __forceinline__ bool out_of_bounds(const CheckArgs& a, float x, float y) {
   // nfop/collision_checker/collision_checker.py:12-19
   return a.has_bounds && (x > a.bounds[1] || x < a.bounds[0] || y > a.bounds[3] || y < a.bounds[2]);
 }
 
-// mode 0: disc robot against a point cloud (circle_collision_checker.py:11-14)
-// mode 1: box robot, obstacle points moved into the robot frame (rectangle_collision_checker.py:11-26)
+// MODE 0: disc robot, MODE 1: box robot against every point of the cloud
 template <int MODE>
 __global__ __launch_bounds__(SM_THREADS) void check_points_kernel(const CheckArgs a) {
   __shared__ float ox[SM_THREADS], oy[SM_THREADS];
   const long long p = blockIdx.x * (long long)SM_THREADS + threadIdx.x;
   const bool valid = p < a.n;
-  float x = 0.f, y = 0.f, c = 1.f, s = 0.f;
-  if (valid) {
-    x = a.poses[p * a.dim];
-    y = a.poses[p * a.dim + 1];
-    if (MODE == 1) { const float th = a.poses[p * a.dim + 2]; c = cosf(th); s = sinf(th); }
-  }
+  Pose q = {0.f, 0.f, 1.f, 0.f, false};
+  if (valid) q = load_pose<MODE>(a.poses, a.dim, p);
   bool hit = false;
-  for (int base = 0; base < a.n_obstacles; base += SM_THREADS) {
-    __syncthreads();
-    if (base + (int)threadIdx.x < a.n_obstacles) {
-      ox[threadIdx.x] = a.obstacles[2 * (base + threadIdx.x)];
-      oy[threadIdx.x] = a.obstacles[2 * (base + threadIdx.x) + 1];
-    }
-    __syncthreads();
-    const int m = min(SM_THREADS, a.n_obstacles - base);
-    for (int k = 0; k < m; ++k) {
-      const float dx = ox[k] - x, dy = oy[k] - y;
-      if (MODE == 0) {
-        hit |= closer_than(dx, dy, a.radius);
-      } else {
-        hit |= inside_box(dx, dy, c, s, a.box);
-      }
-    }
-  }
-  if (valid) a.labels[p] = (hit || out_of_bounds(a, x, y)) ? 1.0f : 0.0f;
+  for_all_points<SM_THREADS>(a.cloud, ox, oy, [&](float px, float py, int) { hit |= a.robot.hits<MODE>(q, px, py); });
+  if (valid) a.labels[p] = (hit || out_of_bounds(a, q.x, q.y)) ? 1.0f : 0.0f;
 }
 
-// modes 0 and 1 with a uniform cell index: the obstacle points are sorted by cell (cell_start[c] .. cell_start[c+1]) and
-// the cell size is at least the robot's reach (the disc's radius; the largest distance from the box robot's origin to a
-// corner of its box), so every point the predicate can accept lies in the 3 x 3 cells around the pose's cell.  The
-// per-point predicate is the same fp32 arithmetic as check_points_kernel<MODE>: identical labels, 1/40 of the distance
-// tests on the 300-disc map.  The index comes from nfopp_build_cell_index (csrc/obstacle_map.hip).
+// The same with the cell index: the cell size is at least the robot's reach (the disc's radius; the largest distance from
+// the box robot's origin to a corner of its box), so every point the predicate can accept lies in the 3 x 3 cells around
+// the pose's cell.  Same predicate, identical labels, 1/40 of the distance tests on the 300-disc map.
 template <int MODE>
 __global__ __launch_bounds__(SM_THREADS) void check_points_cells_kernel(const CheckArgs a) {
   const long long p = blockIdx.x * (long long)SM_THREADS + threadIdx.x;
   if (p >= a.n) return;
-  const float x = a.poses[p * a.dim], y = a.poses[p * a.dim + 1];
-  float c = 1.f, s = 0.f;
-  if (MODE == 1) { const float th = a.poses[p * a.dim + 2]; c = cosf(th); s = sinf(th); }
-  int cx = (int)floorf((x - a.cell_x0) / a.cell_size), cy = (int)floorf((y - a.cell_y0) / a.cell_size);
-  cx = min(max(cx, 0), a.cells_x - 1);
-  cy = min(max(cy, 0), a.cells_y - 1);
+  const Pose q = load_pose<MODE>(a.poses, a.dim, p);
+  const CellIndex& ix = a.cloud.index;
+  int cx, cy;
+  ix.cell(q.x, q.y, &cx, &cy);
   bool hit = false;
-  for (int yy = max(cy - 1, 0); yy <= min(cy + 1, a.cells_y - 1); ++yy) {
-    const int c0 = yy * a.cells_x + max(cx - 1, 0), c1 = yy * a.cells_x + min(cx + 1, a.cells_x - 1);
-    for (int k = a.cell_start[c0]; k < a.cell_start[c1 + 1]; ++k) {   // the row's cells are contiguous in the sorted array
-      const float dx = a.obstacles[2 * k] - x, dy = a.obstacles[2 * k + 1] - y;
-      hit |= MODE == 0 ? closer_than(dx, dy, a.radius) : inside_box(dx, dy, c, s, a.box);
-    }
+  for (int yy = max(cy - 1, 0); yy <= min(cy + 1, ix.cells_y - 1); ++yy) {
+    int k, k1;
+    ix.row_range(yy, max(cx - 1, 0), min(cx + 1, ix.cells_x - 1), &k, &k1);
+    for (; k < k1; ++k) hit |= a.robot.hits<MODE>(q, a.cloud.points[2 * k], a.cloud.points[2 * k + 1]);
   }
-  a.labels[p] = (hit || out_of_bounds(a, x, y)) ? 1.0f : 0.0f;
+  a.labels[p] = (hit || out_of_bounds(a, q.x, q.y)) ? 1.0f : 0.0f;
 }
 
 // occupancy grid (onf_planner_image_map.ipynb cell 2): cell = int((x - origin - cell/2) / cell) truncated toward zero,
 // evaluated in float64 like the reference's numpy (poses are float64 there; geometry scalars are Python doubles), so the
 // labels of fp32 poses equal the reference's bit for bit (tests/golden/g16); outside [0, cols-1) x [0, rows-1) = collision
-__global__ __launch_bounds__(SM_THREADS) void check_grid_kernel(const CheckArgs a) {
+struct GridCheckArgs {
+  const float* poses; long long n; int dim;
+  const unsigned char* grid; int rows, cols; double origin_x, origin_y, cell;
+  float* labels;
+};
+
+__global__ __launch_bounds__(SM_THREADS) void check_grid_kernel(const GridCheckArgs a) {
   const long long p = blockIdx.x * (long long)SM_THREADS + threadIdx.x;
   if (p >= a.n) return;
   const double x = a.poses[p * a.dim], y = a.poses[p * a.dim + 1];
@@ -249,14 +210,10 @@ __global__ __launch_bounds__(SM_THREADS) void check_grid_kernel(const CheckArgs 
   a.labels[p] = hit ? 1.0f : 0.0f;
 }
 
-static int launch_check(const CheckArgs& a, int mode, hipStream_t st) {
+template <class Args>
+static int launch_check(void (*kernel)(Args), const Args& a, hipStream_t st) {
   if (a.n == 0) return NFOPP_OK;
-  const unsigned grid = (unsigned)((a.n + SM_THREADS - 1) / SM_THREADS);
-  if (mode == 0) hipLaunchKernelGGL(check_points_kernel<0>, dim3(grid), dim3(SM_THREADS), 0, st, a);
-  else if (mode == 1) hipLaunchKernelGGL(check_points_kernel<1>, dim3(grid), dim3(SM_THREADS), 0, st, a);
-  else if (mode == 3) hipLaunchKernelGGL(check_points_cells_kernel<0>, dim3(grid), dim3(SM_THREADS), 0, st, a);
-  else if (mode == 4) hipLaunchKernelGGL(check_points_cells_kernel<1>, dim3(grid), dim3(SM_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(check_grid_kernel, dim3(grid), dim3(SM_THREADS), 0, st, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n + SM_THREADS - 1) / SM_THREADS)), dim3(SM_THREADS), 0, st, a);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;
 }
@@ -265,14 +222,19 @@ static int launch_check(const CheckArgs& a, int mode, hipStream_t st) {
 
 using namespace nfopp;
 
-static int fill_common(CheckArgs* a, const float* poses_dev, int64_t n, int32_t pose_dim, const float* bounds4,
-                       float* labels_dev) {
+template <class Args>
+static int fill_poses(Args* a, const float* poses_dev, int64_t n, int32_t pose_dim, float* labels_dev) {
   NFOPP_REQUIRE(n >= 0 && (pose_dim == 2 || pose_dim == 3), "need n >= 0 and pose_dim 2 or 3");
   NFOPP_REQUIRE(n == 0 || (poses_dev && labels_dev), "null device pointer");
   a->poses = poses_dev; a->n = n; a->dim = pose_dim; a->labels = labels_dev;
+  return NFOPP_OK;
+}
+
+static int fill_common(CheckArgs* a, const float* poses_dev, int64_t n, int32_t pose_dim, const float* bounds4,
+                       float* labels_dev) {
   a->has_bounds = bounds4 ? 1 : 0;
   for (int k = 0; k < 4; ++k) a->bounds[k] = bounds4 ? bounds4[k] : 0.f;
-  return NFOPP_OK;
+  return fill_poses(a, poses_dev, n, pose_dim, labels_dev);
 }
 
 extern "C" int nfopp_check_collision_circle(const float* poses_dev, int64_t n, int32_t pose_dim,
@@ -282,8 +244,8 @@ extern "C" int nfopp_check_collision_circle(const float* poses_dev, int64_t n, i
   int rc = fill_common(&a, poses_dev, n, pose_dim, bounds4, labels_dev);
   if (rc) return rc;
   NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
-  a.obstacles = obstacles_dev; a.n_obstacles = n_obstacles; a.radius = radius;
-  return launch_check(a, 0, (hipStream_t)stream);
+  a.cloud.points = obstacles_dev; a.cloud.n = n_obstacles; a.robot.radius = radius;
+  return launch_check(check_points_kernel<0>, a, (hipStream_t)stream);
 }
 
 extern "C" int nfopp_check_collision_circle_cells(const float* poses_dev, int64_t n, int32_t pose_dim,
@@ -294,13 +256,12 @@ extern "C" int nfopp_check_collision_circle_cells(const float* poses_dev, int64_
   CheckArgs a = {};
   int rc = fill_common(&a, poses_dev, n, pose_dim, bounds4, labels_dev);
   if (rc) return rc;
-  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev && cell_start_dev, "bad obstacle index");
-  NFOPP_REQUIRE(cells_x > 0 && cells_y > 0 && cell_size >= radius && radius > 0.f,
-                "the cell size must be at least the robot radius");
-  a.obstacles = obstacles_sorted_dev; a.n_obstacles = n_obstacles; a.radius = radius;
-  a.cell_start = cell_start_dev; a.cells_x = cells_x; a.cells_y = cells_y;
-  a.cell_x0 = cell_x0; a.cell_y0 = cell_y0; a.cell_size = cell_size;
-  return launch_check(a, 3, (hipStream_t)stream);
+  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev, "bad obstacle index");
+  rc = fill_cell_index(&a.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size);
+  if (rc) return rc;
+  NFOPP_REQUIRE(cell_size >= radius && radius > 0.f, "the cell size must be at least the robot radius");
+  a.cloud.points = obstacles_sorted_dev; a.cloud.n = n_obstacles; a.robot.radius = radius;
+  return launch_check(check_points_cells_kernel<0>, a, (hipStream_t)stream);
 }
 
 extern "C" int nfopp_check_collision_rectangle(const float* poses_dev, int64_t n, const float* obstacles_dev,
@@ -311,9 +272,9 @@ extern "C" int nfopp_check_collision_rectangle(const float* poses_dev, int64_t n
   if (rc) return rc;
   NFOPP_REQUIRE(box4, "null box");
   NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
-  a.obstacles = obstacles_dev; a.n_obstacles = n_obstacles;
-  for (int k = 0; k < 4; ++k) a.box[k] = box4[k];
-  return launch_check(a, 1, (hipStream_t)stream);
+  a.cloud.points = obstacles_dev; a.cloud.n = n_obstacles;
+  set_box(&a.robot, box4);
+  return launch_check(check_points_kernel<1>, a, (hipStream_t)stream);
 }
 
 extern "C" int nfopp_check_collision_rectangle_cells(const float* poses_dev, int64_t n,
@@ -325,27 +286,26 @@ extern "C" int nfopp_check_collision_rectangle_cells(const float* poses_dev, int
   int rc = fill_common(&a, poses_dev, n, 3, bounds4, labels_dev);
   if (rc) return rc;
   NFOPP_REQUIRE(box4, "null box");
-  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev && cell_start_dev, "bad obstacle index");
-  float corner = 0.f;   // the reach the caller states must cover every corner of the box (up to its fp32 rounding)
-  for (int k = 0; k < 4; ++k) corner = fmaxf(corner, hypotf(box4[k & 1], box4[2 + (k >> 1)]));
-  NFOPP_REQUIRE(cells_x > 0 && cells_y > 0 && reach > 0.f && reach * 1.00001f >= corner && cell_size >= reach,
+  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev, "bad obstacle index");
+  rc = fill_cell_index(&a.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size);
+  if (rc) return rc;
+  // the reach the caller states must cover every corner of the box (up to its fp32 rounding)
+  NFOPP_REQUIRE(reach > 0.f && reach * 1.00001f >= box_corner(box4) && cell_size >= reach,
                 "the cell size must be at least the robot's reach, and the reach must cover the corners of the box");
-  a.obstacles = obstacles_sorted_dev; a.n_obstacles = n_obstacles;
-  for (int k = 0; k < 4; ++k) a.box[k] = box4[k];
-  a.cell_start = cell_start_dev; a.cells_x = cells_x; a.cells_y = cells_y;
-  a.cell_x0 = cell_x0; a.cell_y0 = cell_y0; a.cell_size = cell_size;
-  return launch_check(a, 4, (hipStream_t)stream);
+  a.cloud.points = obstacles_sorted_dev; a.cloud.n = n_obstacles;
+  set_box(&a.robot, box4);
+  return launch_check(check_points_cells_kernel<1>, a, (hipStream_t)stream);
 }
 
 extern "C" int nfopp_check_collision_grid(const float* poses_dev, int64_t n, int32_t pose_dim, const uint8_t* grid_dev,
                                           int32_t rows, int32_t cols, double origin_x, double origin_y, double cell_size,
                                           float* labels_dev, void* stream) {
-  CheckArgs a = {};
-  int rc = fill_common(&a, poses_dev, n, pose_dim, nullptr, labels_dev);
+  GridCheckArgs a = {};
+  const int rc = fill_poses(&a, poses_dev, n, pose_dim, labels_dev);
   if (rc) return rc;
   NFOPP_REQUIRE(grid_dev && rows > 1 && cols > 1 && cell_size > 0.0, "bad occupancy grid");
   a.grid = grid_dev; a.rows = rows; a.cols = cols; a.origin_x = origin_x; a.origin_y = origin_y; a.cell = cell_size;
-  return launch_check(a, 2, (hipStream_t)stream);
+  return launch_check(check_grid_kernel, a, (hipStream_t)stream);
 }
 
 extern "C" int nfopp_sample_candidates(const float* prev_traj_dev, int64_t batch, int32_t n_waypoints, int32_t dim,

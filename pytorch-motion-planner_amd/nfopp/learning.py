@@ -20,6 +20,13 @@ def _f4(values):
     return (ctypes.c_float * 4)(*[float(v) for v in values])
 
 
+def _as_points(points, device):
+    """`points` (numpy array or tensor, anything that reshapes to [n, 2]) as an fp32 [n, 2] tensor on `device`."""
+    if isinstance(points, torch.Tensor):
+        return points.detach().to(device=device, dtype=torch.float32).reshape(-1, 2).contiguous()
+    return torch.tensor(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2), device=device)
+
+
 class DeviceGridMap(object):
     """Occupancy grid on the device (nfop/ros/grid_map.py).  `data` [rows, cols] is the fp32 image of `GridMap` (a cell is
     occupied above `threshold`) or, through `from_occupancy_data`, the raw int8 image of a ROS OccupancyGrid; `origin` =
@@ -95,10 +102,7 @@ class _PointCloudChecker(object):
 
     def update_obstacle_points(self, points):
         """Replaces the obstacle set by `points` [n, 2] (numpy array or device tensor) and rebuilds the index."""
-        if isinstance(points, torch.Tensor):
-            pts = points.detach().to(device=self.device, dtype=torch.float32).reshape(-1, 2).contiguous()
-        else:
-            pts = torch.tensor(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2), device=self.device)
+        pts = _as_points(points, self.device)
         n, reach = pts.shape[0], self._reach()
         self.cells, self.obstacles = None, pts
         if n < self.INDEX_FROM or n == 0 or not reach > 0:
@@ -124,6 +128,12 @@ class _PointCloudChecker(object):
     def get_boundaries(self):
         return self.boundaries
 
+    def _cloud_args(self):
+        """What every C entry over the obstacle set takes after the poses: points, count and, with an index, its six
+        parameters (CellIndex of csrc/point_cloud.h)."""
+        index = () if self.cells is None else (_lib.ptr(self.cells[0], torch.int32),) + tuple(self.cells[1:])
+        return (_lib.ptr(self.obstacles), self.obstacles.shape[0]) + index
+
     _box = None   # the rectangle checker's (x0, x1, y0, y1); None = disc robot
 
     def nearest(self, poses, out=None, index_out=None):
@@ -136,15 +146,9 @@ class _PointCloudChecker(object):
         index = torch.empty(n, dtype=torch.int32, device=poses.device) if index_out is None else index_out
         box = _f4(self._box) if self._box is not None else None
         lib = _lib.load()
-        if self.cells is None:
-            _lib.check(lib.nfopp_nearest_obstacle(_lib.ptr(poses), n, d, _lib.ptr(self.obstacles), self.obstacles.shape[0],
-                                                  box, _lib.ptr(dist), _lib.ptr(index, torch.int32), _lib.stream_ptr()))
-        else:
-            start, nx, ny, x0, y0, size = self.cells
-            _lib.check(lib.nfopp_nearest_obstacle_cells(_lib.ptr(poses), n, d, _lib.ptr(self.obstacles),
-                                                        self.obstacles.shape[0], _lib.ptr(start, torch.int32), nx, ny, x0,
-                                                        y0, size, box, _lib.ptr(dist), _lib.ptr(index, torch.int32),
-                                                        _lib.stream_ptr()))
+        entry = lib.nfopp_nearest_obstacle if self.cells is None else lib.nfopp_nearest_obstacle_cells
+        _lib.check(entry(_lib.ptr(poses), n, d, *self._cloud_args(), box, _lib.ptr(dist), _lib.ptr(index, torch.int32),
+                         _lib.stream_ptr()))
         return dist, index
 
     def clearance(self, poses, out=None):
@@ -160,11 +164,7 @@ class _PointCloudChecker(object):
         sensor's points first, then the map's, and the boundaries from the map."""
         pts = grid_map.as_point_cloud()
         if extra_points is not None:
-            if isinstance(extra_points, torch.Tensor):
-                extra = extra_points.detach().to(device=pts.device, dtype=torch.float32).reshape(-1, 2)
-            else:
-                extra = torch.tensor(np.ascontiguousarray(extra_points, dtype=np.float32).reshape(-1, 2), device=pts.device)
-            pts = torch.cat([extra, pts], 0)
+            pts = torch.cat([_as_points(extra_points, pts.device), pts], 0)
         self.update_obstacle_points(pts)
         self.update_boundaries(grid_map.boundaries)
 
@@ -186,15 +186,8 @@ class DeviceCircleChecker(_PointCloudChecker):
         out = torch.empty(n, dtype=torch.float32, device=poses.device) if out is None else out
         b = _f4(self.boundaries) if self.boundaries is not None else None
         lib = _lib.load()
-        if self.cells is None:
-            _lib.check(lib.nfopp_check_collision_circle(_lib.ptr(poses), n, d, _lib.ptr(self.obstacles),
-                                                        self.obstacles.shape[0], self.radius, b, _lib.ptr(out),
-                                                        _lib.stream_ptr()))
-        else:
-            start, nx, ny, x0, y0, size = self.cells
-            _lib.check(lib.nfopp_check_collision_circle_cells(_lib.ptr(poses), n, d, _lib.ptr(self.obstacles),
-                                                              self.obstacles.shape[0], _lib.ptr(start, torch.int32), nx, ny,
-                                                              x0, y0, size, self.radius, b, _lib.ptr(out), _lib.stream_ptr()))
+        entry = lib.nfopp_check_collision_circle if self.cells is None else lib.nfopp_check_collision_circle_cells
+        _lib.check(entry(_lib.ptr(poses), n, d, *self._cloud_args(), self.radius, b, _lib.ptr(out), _lib.stream_ptr()))
         return out
 
 
@@ -208,7 +201,8 @@ class DeviceRectangleChecker(_PointCloudChecker):
         self._setup(obstacle_points, boundaries, device)
 
     def _reach(self):
-        """Largest distance from the robot origin to a corner of the box (the box need not contain the origin)."""
+        """Largest distance from the robot origin to a corner of the box (the box need not contain the origin); `box_reach`
+        of csrc/point_cloud.h is its C counterpart (fp32, rounded up)."""
         x0, x1, y0, y1 = self.box
         return float(np.hypot(max(abs(x0), abs(x1)), max(abs(y0), abs(y1))))
 
@@ -218,15 +212,11 @@ class DeviceRectangleChecker(_PointCloudChecker):
         b = _f4(self.boundaries) if self.boundaries is not None else None
         lib = _lib.load()
         if self.cells is None:
-            _lib.check(lib.nfopp_check_collision_rectangle(_lib.ptr(poses), n, _lib.ptr(self.obstacles),
-                                                           self.obstacles.shape[0], _f4(self.box), b, _lib.ptr(out),
-                                                           _lib.stream_ptr()))
+            _lib.check(lib.nfopp_check_collision_rectangle(_lib.ptr(poses), n, *self._cloud_args(), _f4(self.box), b,
+                                                           _lib.ptr(out), _lib.stream_ptr()))
         else:
-            start, nx, ny, x0, y0, size = self.cells
-            _lib.check(lib.nfopp_check_collision_rectangle_cells(_lib.ptr(poses), n, _lib.ptr(self.obstacles),
-                                                                 self.obstacles.shape[0], _lib.ptr(start, torch.int32), nx,
-                                                                 ny, x0, y0, size, _f4(self.box), self._reach(), b,
-                                                                 _lib.ptr(out), _lib.stream_ptr()))
+            _lib.check(lib.nfopp_check_collision_rectangle_cells(_lib.ptr(poses), n, *self._cloud_args(), _f4(self.box),
+                                                                 self._reach(), b, _lib.ptr(out), _lib.stream_ptr()))
         return out
 
 

@@ -252,6 +252,27 @@ def test_cell_indexed_rectangle_checker_equals_the_plain_one(box):
     assert bad[:n_far].mean() <= 300 * perimeter * 2e-4 / 140.0 ** 2 and not bad[-4:].any()
 
 
+def test_indexed_and_all_pairs_labels_agree_on_unrepresentable_poses():
+    """Poses whose cell arithmetic leaves int's range (NaN, +-inf, +-3e9, +-1e30) in x, y or both: the pose's cell comes
+    from the float-clamped CellIndex::cell (csrc/point_cloud.h) that sorted the points, so the indexed kernels label them
+    like the all-pairs kernels; the finite ones are far from every obstacle and outside the bounds."""
+    pts = np.random.default_rng(5).uniform(0, 20, (64, 2))
+    values = [np.nan, np.inf, -np.inf, 3e9, -3e9, 1e30, -1e30, 10.0]
+    poses = np.array([(x, y, 0.3) for x in values for y in values if not (x == 10.0 and y == 10.0)], F32)
+    assert len(poses) == 63
+    finite = np.isfinite(poses).all(1)
+    p = torch.tensor(poses, device="cuda")
+    for name, shape in (("circle", 0.4), ("rect", (0.1, 0.5, -0.2, 0.2))):
+        for bounds in (None, (0.0, 20.0, 0.0, 20.0)):
+            fast = make_checker(name, shape, pts, bounds)
+            assert fast.cells is not None and len(pts) >= type(fast).INDEX_FROM
+            slow = make_checker(name, shape, pts, bounds)
+            slow.cells, slow.obstacles = None, torch.tensor(pts.astype(F32), device="cuda")
+            a, b = fast.labels(p).cpu().numpy(), slow.labels(p).cpu().numpy()
+            assert np.array_equal(a, b), (name, bounds, poses[a != b][:5])
+            assert np.array_equal(a[finite], np.full(int(finite.sum()), 0.0 if bounds is None else 1.0, F32))
+
+
 # ---- end to end -----------------------------------------------------------------------------------------------------
 def test_batch_planner_follows_a_map_update(g21):
     """Continuous learning, B = 4, N = 32: after update_from_map between two steps the next fit is labelled by the new
