@@ -472,6 +472,28 @@ int nfopp_path_stats(const float* traj_dev, const float* start_dev, const float*
                      int32_t n_waypoints, int32_t dim, const float* pose_dist_dev, int32_t poses_per_path,
                      double cos_cusp, double* stats_dev, const uint8_t* active_dev, void* stream);
 
+/* ---- exact Euclidean distance transform of an occupancy grid (csrc/grid_edt.hip), additive under ABI 6 ----------------
+ * What a clearance margin for the grid-search seeds is decided on (nfopp/grid_search.py: OccupancyGrid.inflated).
+ *
+ * nfopp_grid_edt: occupancy_dev uint8 [rows, cols], non-zero = occupied (as in nfopp_grid_distance_fields).
+ *   dist2_dev int32 [rows, cols] <- the squared Euclidean distance, in cells, from each cell to the nearest occupied
+ *   cell: 0 on occupied cells, INT32_MAX everywhere when no cell is occupied.
+ *   nearest_dev int32 [rows, cols] (may be null) <- the flat index row * cols + col of the occupied cell that attains
+ *   dist2; among equidistant cells the SMALLEST flat index (smallest row, then smallest column); -1 everywhere when no
+ *   cell is occupied.  dist2_dev holds the same bytes with and without nearest_dev.
+ *   border != 0: cells outside the matrix count as occupied, dist2 <- min(dist2, b * b) with
+ *   b = min(row + 1, rows - row, col + 1, cols - col).  nearest still names real cells only: it is what it is without
+ *   the border (so dist2 may be smaller than the distance to `nearest`, and nearest stays -1 on an empty grid).
+ *   Separable: a column pass keeps, per cell, the nearest occupied row of its column (above and below equally far: the
+ *   smaller row), a row pass takes the minimum over col' of ((col - col')^2 + (row - g(row, col'))^2, g, col'), scanning
+ *   outward from the cell over a copy of the row of g in LDS until (col - col')^2 alone exceeds the best distance.
+ *   Integer arithmetic throughout, no atomics: the same bytes from run to run.
+ *   Limits: 1 <= rows, cols <= 4096 and rows * cols <= 2^24 (the limit of nfopp_grid_to_points); larger input is an
+ *   argument error.  workspace: nfopp_grid_edt_workspace_bytes(rows, cols) bytes of device scratch (0 = bad shape). */
+size_t nfopp_grid_edt_workspace_bytes(int32_t rows, int32_t cols);
+int nfopp_grid_edt(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, int32_t border, int32_t* dist2_dev,
+                   int32_t* nearest_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,23 +35,46 @@ def _cell_centres(boundaries, resolution):
 
 class OccupancyGrid(object):
     """uint8 occupancy [rows = y cells, cols = x cells] (non-zero = wall) with the geometry of the reference's raster:
-    cell of a point = int((x - b0) // resolution), cell centre = j * resolution + resolution / 2 + b0."""
+    cell of a point = int((x - b0) // resolution), cell centre = j * resolution + resolution / 2 + b0.
+
+    The occupancy of a grid never changes after construction, so its distance transform (csrc/grid_edt.hip) and the images
+    inflated from it are computed once and kept."""
 
     def __init__(self, occupancy_uint8, boundaries, resolution, device="cuda"):
         occ = np.ascontiguousarray(np.asarray(occupancy_uint8) != 0, dtype=np.uint8)
         if occ.ndim != 2 or occ.size == 0:
             raise ValueError("occupancy must be a non-empty [rows, cols] array")
-        self.occupancy_host = occ
+        self._occupancy_host = occ
+        self._shape = occ.shape
         self.boundaries = tuple(float(b) for b in boundaries)
         self.resolution = float(resolution)
         if not self.resolution > 0:
             raise ValueError("resolution must be positive")
         self.device = device
         self._occupancy_dev = None
+        self._edt = {}        # border -> (dist2, nearest)
+        self._inflated = {}   # (cells2, border) -> OccupancyGrid
+
+    @classmethod
+    def _from_device(cls, occupancy_dev, boundaries, resolution):
+        """A grid around a uint8 0 / 1 device image; the host copy is read back only if someone asks for it."""
+        grid = cls.__new__(cls)
+        grid._occupancy_host = None
+        grid._shape = tuple(occupancy_dev.shape)
+        grid.boundaries, grid.resolution, grid.device = boundaries, resolution, occupancy_dev.device
+        grid._occupancy_dev = occupancy_dev
+        grid._edt, grid._inflated = {}, {}
+        return grid
 
     @property
     def shape(self):
-        return self.occupancy_host.shape
+        return self._shape
+
+    @property
+    def occupancy_host(self):
+        if self._occupancy_host is None:
+            self._occupancy_host = self._occupancy_dev.cpu().numpy()
+        return self._occupancy_host
 
     @property
     def occupancy(self):
@@ -98,6 +121,61 @@ class OccupancyGrid(object):
         row = torch.floor((xy[:, 1] - b[2]) / self.resolution)
         lim = float(2 ** 30)
         return torch.stack([row, col], 1).clamp_(-lim, lim).to(torch.int32).contiguous()
+
+    def distance_transform(self, border=False):
+        """-> (dist2, nearest), int32 [rows, cols] on the device (nfopp_grid_edt): the squared Euclidean distance, in cells,
+        to the nearest wall cell (INT32_MAX on a grid without walls) and that cell's flat index row * cols + col, the
+        smallest among equidistant ones (-1 without walls).  With `border` the cells outside the grid count as walls for
+        dist2; nearest still names cells of the grid.  Computed once per `border` value."""
+        border = bool(border)
+        if border not in self._edt:
+            lib = _lib.load()
+            occ = self.occupancy
+            rows, cols = self.shape
+            dist2 = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
+            nearest = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
+            ws_bytes = lib.nfopp_grid_edt_workspace_bytes(rows, cols)
+            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=occ.device) if ws_bytes else None
+            _lib.check(lib.nfopp_grid_edt(_lib.ptr(occ, torch.uint8), rows, cols, int(border), _lib.ptr(dist2, torch.int32),
+                                          _lib.ptr(nearest, torch.int32), _lib.ptr(ws, torch.int32), ws_bytes, _lib.stream_ptr()))
+            self._edt[border] = (dist2, nearest)
+        return self._edt[border]
+
+    def clearance_field(self, border=False):
+        """-> fp32 [rows, cols] on the device: the distance in metres from each cell's centre to the centre of the nearest
+        wall cell, resolution * sqrt(dist2) formed in float64 and rounded once; +inf on a grid without walls."""
+        dist2, _ = self.distance_transform(border)
+        metres = (torch.sqrt(dist2.double()) * self.resolution).float()
+        return torch.where(dist2 == EDT_NONE, torch.full_like(metres, float("inf")), metres)
+
+    def inflated(self, margin=None, *, cells2=None, border=False):
+        """-> the OccupancyGrid (same boundaries and resolution) whose walls are the cells with dist2 <= k: every cell
+        within sqrt(k) cells of a wall.  k = `cells2`, or margin_cells2(margin, resolution) for a `margin` in metres.
+        k = 0 gives an image equal to this one.  Decided on the device; nothing is read back."""
+        if (margin is None) == (cells2 is None):
+            raise TypeError("inflated() takes a margin in metres or cells2=k, not both and not neither")
+        k = margin_cells2(margin, self.resolution) if cells2 is None else int(cells2)
+        if k < 0 or k >= EDT_NONE or (cells2 is not None and k != cells2):
+            raise ValueError("cells2 must be a non-negative integer below 2^31 - 1")
+        key = (k, bool(border))
+        if key not in self._inflated:
+            dist2, _ = self.distance_transform(border)
+            self._inflated[key] = OccupancyGrid._from_device((dist2 <= k).to(torch.uint8), self.boundaries, self.resolution)
+        return self._inflated[key]
+
+
+EDT_NONE = 2 ** 31 - 1   # dist2 on a grid without walls (INT32_MAX)
+
+
+def margin_cells2(margin, resolution):
+    """The threshold on dist2 for a margin in metres: floor((margin / resolution)^2 * (1 + 1e-9)).  The slack keeps a
+    margin that is a whole number of cells up to the rounding of the division (0.7 / 0.1) at its square (49); dist2 is an
+    integer, so it admits nothing else."""
+    margin = float(margin)
+    if not (margin >= 0.0 and np.isfinite(margin)):
+        raise ValueError("a clearance margin must be finite and >= 0")
+    q = margin / float(resolution)
+    return int(np.floor(q * q * (1.0 + 1e-9)))
 
 
 def _as_device_points(grid, pts):
@@ -167,9 +245,53 @@ def _search(grid, starts, goals):
     return cells, count, status, cost, starts, goals
 
 
-def grid_search_paths(grid, starts, goals):
-    """-> (cells int32 [B, max_len, 2] (row, col), counts [B], status [B], costs [B, 2] = (straight, diagonal) moves)."""
-    return _search(grid, starts, goals)[:4]
+def _margins(clearance):
+    """clearance (a margin in metres or a descending sequence of them) -> list of floats."""
+    margins = [float(clearance)] if np.ndim(clearance) == 0 else [float(m) for m in clearance]
+    for m in margins:
+        if not (m >= 0.0 and np.isfinite(m)):
+            raise ValueError("a clearance margin must be finite and >= 0")
+    if any(a <= b for a, b in zip(margins, margins[1:])):
+        raise ValueError("clearance margins must be strictly descending")
+    return margins
+
+
+def _search_with_clearance(grid, starts, goals, clearance):
+    """_search on the plain grid and on grid.inflated(margin) for every margin; each problem keeps the result of the largest
+    margin at which its search returns status 0, else the plain grid's (with its status 1 / 2).  The levels are merged on
+    the device.  -> (cells, count, status, cost, starts, goals, seed_margin fp32 [B])."""
+    starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
+    cells, count, status, cost = _search(grid, starts, goals)[:4]
+    seed_margin = torch.zeros(count.shape[0], dtype=torch.float32, device=count.device)
+    levels = []
+    for m in _margins(clearance):
+        if margin_cells2(m, grid.resolution) > 0:   # k = 0 is the plain grid
+            levels.append((m, _search(grid.inflated(m), starts, goals)[:4]))
+    if not levels:
+        return cells, count, status, cost, starts, goals, seed_margin
+    max_len = max([cells.shape[1]] + [lv[1][0].shape[1] for lv in levels])
+
+    def padded(c):
+        return c if c.shape[1] == max_len else torch.nn.functional.pad(c, (0, 0, 0, max_len - c.shape[1]))
+
+    cells = padded(cells)
+    for m, (l_cells, l_count, l_status, l_cost) in reversed(levels):   # ascending: the largest margin is applied last
+        ok = l_status == STATUS_OK
+        cells = torch.where(ok[:, None, None], padded(l_cells), cells)
+        count = torch.where(ok, l_count, count)
+        cost = torch.where(ok[:, None], l_cost, cost)
+        status = torch.where(ok, l_status, status)
+        seed_margin = torch.where(ok, torch.full_like(seed_margin, m), seed_margin)
+    return cells.contiguous(), count.contiguous(), status.contiguous(), cost.contiguous(), starts, goals, seed_margin
+
+
+def grid_search_paths(grid, starts, goals, clearance=None):
+    """-> (cells int32 [B, max_len, 2] (row, col), counts [B], status [B], costs [B, 2] = (straight, diagonal) moves).
+    With a `clearance` (see grid_search_init) also seed_margin fp32 [B] at the end."""
+    if clearance is None:
+        return _search(grid, starts, goals)[:4]
+    r = _search_with_clearance(grid, starts, goals, clearance)
+    return r[:4] + r[6:]
 
 
 def seed_trajectories(grid, cells, counts, status, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None):
@@ -197,20 +319,32 @@ def seed_trajectories(grid, cells, counts, status, starts, goals, n_waypoints, i
     return out.view(b, int(n_waypoints), d)
 
 
-def grid_search_init(grid, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None):
+def grid_search_init(grid, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None, clearance=None):
     """Batched `AstarTrajectoryInitializer.initialize_trajectory`: -> (traj [B, N, D] fp32, status [B] int32), on the
     device.  status 0 = seeded along a shortest grid path; 1 = goal unreachable, 2 = start or goal outside the grid: those
-    problems get the straight line of `init_trajectories`."""
-    cells, count, status, _, starts, goals = _search(grid, starts, goals)
+    problems get the straight line of `init_trajectories`.
+
+    `clearance` is a margin in metres or a strictly descending sequence of margins: each problem is seeded along a shortest
+    path of grid.inflated(margin) for the largest margin at which that search succeeds, and on the plain grid, exactly as
+    without the argument, if none does.  The start cell stays untested and the goal cell forced free on every level.  The
+    call then returns (traj, status, seed_margin): seed_margin fp32 [B] is the margin each problem was seeded at, 0 for
+    the plain grid."""
+    if clearance is None:
+        cells, count, status, _, starts, goals = _search(grid, starts, goals)
+        traj = seed_trajectories(grid, cells, count, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
+        return traj, status
+    cells, count, status, _, starts, goals, seed_margin = _search_with_clearance(grid, starts, goals, clearance)
     traj = seed_trajectories(grid, cells, count, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
-    return traj, status
+    return traj, status, seed_margin
 
 
 class AstarTrajectoryInitializer(object):
     """Drop-in for nfop/astar/astar_trajectory_initializer.py (same constructor, same `initialize_trajectory`); the
-    search runs on the device, and BatchPlanner / ConstrainedNERFOptPlanner seed whole batches through it."""
+    search runs on the device, and BatchPlanner / ConstrainedNERFOptPlanner seed whole batches through it.  `clearance`
+    (after the reference's own arguments) is grid_search_init's; `seed_margin` then holds the margin of each problem of the
+    last call, all zero without a clearance."""
 
-    def __init__(self, collision_checker, resolution=_MISSING, init_angles_with_trajectory=False):
+    def __init__(self, collision_checker, resolution=_MISSING, init_angles_with_trajectory=False, clearance=None):
         if not hasattr(collision_checker, "check_collision") and not hasattr(collision_checker, "labels"):
             raise NotImplementedError("AstarTrajectoryInitializer rasterises its collision checker: %r offers no "
                                       "check_collision, so there is no map to search" % (collision_checker,))
@@ -219,8 +353,10 @@ class AstarTrajectoryInitializer(object):
         self._collision_checker = collision_checker
         self._resolution = resolution
         self._init_angles_with_trajectory = init_angles_with_trajectory
+        self._clearance = clearance
         self._grid = None
         self.status = None
+        self.seed_margin = None
 
     def grid(self, boundaries=None, device=None):
         """The rasterised map (built on first use; the reference rasterises on every call, the checker is static)."""
@@ -231,8 +367,9 @@ class AstarTrajectoryInitializer(object):
 
     def initialize_batch(self, starts, goals, n_waypoints, out=None, boundaries=None):
         device = out.device if out is not None else None
-        traj, self.status = grid_search_init(self.grid(boundaries, device), starts, goals, n_waypoints,
-                                             self._init_angles_with_trajectory, out=out)
+        traj, self.status, self.seed_margin = grid_search_init(
+            self.grid(boundaries, device), starts, goals, n_waypoints, self._init_angles_with_trajectory, out=out,
+            clearance=() if self._clearance is None else self._clearance)
         return traj
 
     def initialize_trajectory(self, trajectory, start_point, goal_point):

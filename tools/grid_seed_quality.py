@@ -3,9 +3,11 @@
 
 The same problems (bench.py's generator) are planned twice for the same number of steps with the frozen pre-fitted field:
 once from the stock straight line, once from the grid-search seed (nfopp/grid_search.py).  Prints the collision-free rate
-from BatchPlanner.evaluate for both, and the seeding time split into its three stages by events.  Information, not a gate.
+from BatchPlanner.evaluate for both, and the seeding time split into its three stages by events.  With --clearance the
+grid-search seed is planned once more per margin (metres; the cfg4 cell is 1 m), seeded off the walls by that margin
+(grid_search_init's `clearance`).  Information, not a gate.
 
-Usage:  python tools/grid_seed_quality.py [--problems 256] [--steps 500] [--time-batch 4096]
+Usage:  python tools/grid_seed_quality.py [--problems 256] [--steps 500] [--time-batch 4096] [--clearance 1 2]
 """
 import argparse
 import json
@@ -61,6 +63,8 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--time-batch", type=int, default=4096)
     ap.add_argument("--fit-iters", type=int, default=300)
+    ap.add_argument("--clearance", type=float, nargs="*", default=[],
+                    help="margins in metres: one more grid-search row per margin")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -74,9 +78,11 @@ def main():
     grid = nfopp.OccupancyGrid.from_checker(truth, 1.0, boundaries=(0.5, 100.0, 0.5, 100.0))
     N, B = 256, args.problems
     result = {"map": env.name, "problems": B, "steps": args.steps, "waypoints": N, "onf_fit_loss": fit_loss}
-    for name, ini in (("straight_line", None), ("grid_search", grid)):
+    rows = [("straight_line", None, None), ("grid_search", grid, None)]
+    rows += [("grid_search_clearance_%g" % m, grid, m) for m in args.clearance]
+    for name, ini, margin in rows:
         planner = nfopp.BatchPlanner(onf, B, N, bench.bench_hyper(), velocity_hessian_weight=0.5, device=device, seed=bench.SEED)
-        planner.init(starts[:B], goals[:B], bench.BOUNDS, initializer=ini)
+        planner.init(starts[:B], goals[:B], bench.BOUNDS, initializer=ini, seed_clearance=margin)
         collides0, _ = planner.evaluate(truth)
         free0 = 1.0 - float(collides0.float().mean())
         planner.step(n=args.steps)
@@ -86,6 +92,8 @@ def main():
                         "mean_length_of_free_paths": float(length[free].mean()) if bool(free.any()) else None}
         if ini is not None:
             result[name]["seed_status_counts"] = np.bincount(planner.seed_status.cpu().numpy(), minlength=3).tolist()
+        if margin is not None:
+            result[name]["seeded_at_the_margin"] = int((planner.seed_margin > 0).sum())
     result["seeding_ms_%dx%d" % (args.time_batch, N)] = stage_times(grid, starts[:args.time_batch], goals[:args.time_batch], N)
     print(json.dumps(result))
 
