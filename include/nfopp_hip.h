@@ -472,6 +472,74 @@ int nfopp_path_stats(const float* traj_dev, const float* start_dev, const float*
                      int32_t n_waypoints, int32_t dim, const float* pose_dist_dev, int32_t poses_per_path,
                      double cos_cusp, double* stats_dev, const uint8_t* active_dev, void* stream);
 
+/* ---- swept collision check between consecutive poses (csrc/swept.hip), additive under ABI 6 ---------------------------
+ * `collides`, the clearance and the path statistics judge SAMPLED poses.  These entries judge what lies between two of
+ * them.  A segment is a pair of poses (a_dev[p], b_dev[p]) of pose_dim 2 or 3; between them x and y are linear and theta
+ * is linear along the wrapped shortest difference (wrap_angle, fp32), the motion nfopp_path_interpolate lays its poses on.
+ *
+ * nfopp_swept_segments / nfopp_swept_segments_cells: value_dev[p] <- one fp32 value per segment, index_dev[p] (may be
+ *   null) <- the obstacle point that attains it, the smallest k among equals, an index into the array passed in.
+ *     box4 = NULL, disc robot -- exact.  With e = b - a, |e|^2 = fmaf(ex, ex, ey * ey), d = o - a:
+ *         value = min over obstacle points o of  min( disc(o - a), disc(o - b), interior ? |cross| / sqrtf(|e|^2) : +inf ),
+ *         interior: 0 < fmaf(ex, dx, ey * dy) < |e|^2 (strictly),  cross = fmaf(ex, dy, -(ey * dx)),
+ *       disc(dx, dy) = sqrtf(fmaf(dx, dx, dy * dy)), the one expression nfopp_nearest_obstacle and the circle checker
+ *       evaluate.  So, bit for bit: value <= min(nearest(a), nearest(b)); either end pose's circle label implies
+ *       value < radius; a zero-length segment returns nfopp_nearest_obstacle's distance and index.  The disc swept along
+ *       the segment is a capsule: value < radius IS the swept collision test.
+ *     box4 = (x0, x1, y0, y1), box robot, pose_dim must be 3 -- a sound certificate.  With d_a(o), d_b(o) the distances from
+ *       o to the closed box at either end (nfopp_nearest_obstacle's expression), reach = the box's largest corner distance
+ *       (rounded up, formed inside the call) and  delta = fmaf(reach, |wrap_angle(theta_b - theta_a)|, |e|):
+ *         value = fl( min over o of fl(d_a(o) + d_b(o))  -  delta ).
+ *       On the way from a to the interpolation parameter s no body point travels more than s * delta, and the distance
+ *       from a fixed point to the box is 1-Lipschitz in that displacement: an obstacle inside the box at some s needs
+ *       d_a <= s delta and d_b <= (1 - s) delta, so d_a + d_b <= delta.  Hence
+ *         value > slack = nfopp_swept_slack(box4) = reach * NFOPP_SWEPT_SLACK_REL (2^-16 = 256 * 2^-24)
+ *       certifies the whole segment free.  slack bounds the rounding of `value` for every point that can decide it
+ *       (d_a + d_b near delta, so |o - a| + |o - b| <= 2 reach + delta), in units of u = 2^-24:
+ *         9.5 u (|dx| + |dy|) per distance (cosf / sinf to 2 ulp, the roundings of dx, dy, of the two fmas of the robot
+ *           frame and of the distance; derived in tests/test_gpu_clearance.py)  -> 13.5 u (2 reach + delta) for the two,
+ *         1 u delta for their sum,
+ *         delta itself: 4 u |e|, 2 u delta for its fma, and reach times the error of the wrapped difference, at most
+ *           (2.5 |theta_b - theta_a| + 17) u <= 80 u for a raw difference of at most 8 pi,
+ *       together (107 reach + 20.5 delta) u: below 189 u reach while delta <= 4 reach.  A segment with delta > 4 reach or
+ *       |theta_b - theta_a| > 8 pi (fp32) is outside that derivation and gets value -inf, index -1: not certifiable at
+ *       this pose spacing.  A segment with value <= slack whose end poses are free is UNDECIDED: the caller needs more
+ *       poses per segment (there is no adaptive subdivision here).
+ *   horizon >= 0 (+inf allowed): a segment whose value exceeds it gets +inf and -1, which bounds the indexed search.  Both
+ *   entries apply the same cap and write the same bytes, run after run (no atomics).
+ *   n = 0 is a no-op.  n_obstacles = 0: every segment gets +inf and -1.  A segment with a non-finite component in either
+ *   pose (x, y; theta too for the box) gets +inf and -1; nfopp_path_swept_labels treats it as not certified.  Coordinates
+ *   are taken to be below 2^60 in magnitude (squares must not overflow).  box4 with pose_dim != 3, and a negative or NaN
+ *   horizon, are argument errors.
+ *   nfopp_swept_segments tests all pairs with the points staged in LDS: for small clouds, and the independent cross-check.
+ *   nfopp_swept_segments_cells takes the index of nfopp_build_cell_index (any cell size), one thread per segment, and
+ *   visits the rows of cells that cover the bounding box of the two end points inflated by R, plus one cell on each side:
+ *     disc: R = horizon + 2^-18 (horizon + |e|);   box: R = (reach + delta + horizon)(1 + 2^-18).
+ *   Every point whose computed value is <= horizon lies inside (disc: within `value` of the segment; box: d_a <= delta +
+ *   horizon, so within reach + delta + horizon of a's origin; 2^-18 covers the fp32 evaluation), the bounds are rounded
+ *   outward, and points and bounds get their cells from one monotone function (csrc/swept.hip has the full argument).
+ *
+ * nfopp_path_swept_labels: for B densified paths of m = poses_per_path poses, value_dev [B, m - 1] (segment j joins poses
+ *   j and j + 1) and labels_dev [B * m] as the checker wrote them: labels_dev[b, j] <- 1 where segment j is not certified
+ *   -- box == 0: value < threshold (the radius); box != 0: value <= threshold (the slack); a segment with a non-finite
+ *   pose component either way.  The last pose keeps its label.  The result is what nfopp_path_select_best reads.
+ *   status_dev [B] uint8 (may be null): 0 every segment certified and no pose in collision; 1 a pose, or for the disc a
+ *   segment, in collision; 2 (box only) no pose collides but a segment is undecided.
+ *   worst_dev [B, 2] fp32 (may be null): the smallest segment value of the path and the first segment index attaining it
+ *   (+inf, 0 when every segment is beyond the horizon).  One workgroup per path, reductions in a fixed order. */
+#define NFOPP_SWEPT_SLACK_REL 1.52587890625e-05f /* 2^-16 */
+float nfopp_swept_slack(const float* box4);
+int nfopp_swept_segments(const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim, const float* obstacles_dev,
+                         int32_t n_obstacles, const float* box4, float horizon, float* value_dev, int32_t* index_dev,
+                         void* stream);
+int nfopp_swept_segments_cells(const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim,
+                               const float* obstacles_sorted_dev, int32_t n_obstacles, const int32_t* cell_start_dev,
+                               int32_t cells_x, int32_t cells_y, float cell_x0, float cell_y0, float cell_size,
+                               const float* box4, float horizon, float* value_dev, int32_t* index_dev, void* stream);
+int nfopp_path_swept_labels(const float* poses_dev, const float* value_dev, float* labels_dev, int64_t batch,
+                            int32_t poses_per_path, int32_t dim, float threshold, int32_t box, uint8_t* status_dev,
+                            float* worst_dev, void* stream);
+
 /* ---- exact Euclidean distance transform of an occupancy grid (csrc/grid_edt.hip), additive under ABI 6 ----------------
  * What a clearance margin for the grid-search seeds is decided on (nfopp/grid_search.py: OccupancyGrid.inflated).
  *

@@ -28,11 +28,6 @@ struct NearArgs {   // a pose that load_pose flags as not finite is answered +in
   float* dist; int* index;
 };
 
-// (best, bestk) <- lexicographic minimum with (d, k).  A NaN or +inf distance never enters: the initial (+inf, -1) stays.
-__device__ __forceinline__ void take_min(float d, int k, float* best, int* bestk) {
-  if (d < *best || (d == *best && k < *bestk)) { *best = d; *bestk = k; }
-}
-
 __device__ __forceinline__ void store_result(const NearArgs& a, long long p, bool finite, float best, int bestk) {
   a.dist[p] = finite ? best : __builtin_inff();
   if (a.index) a.index[p] = finite ? bestk : -1;

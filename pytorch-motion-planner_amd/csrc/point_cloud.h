@@ -1,5 +1,6 @@
 // What every kernel over the obstacle point cloud shares: the uniform cell index (built by csrc/obstacle_map.hip, searched
-// by the *_cells checkers of csrc/sampling.hip and the nearest-obstacle query of csrc/clearance.hip), the robot's shape and
+// by the *_cells checkers of csrc/sampling.hip, the nearest-obstacle query of csrc/clearance.hip and the swept check of
+// csrc/swept.hip), the robot's shape and
 // the all-pairs visit.  The index is sound only if all three form a cell number the same way, and `dist < radius` of the
 // query is the circle checker's obstacle term only if both evaluate one expression: each is written once, here.
 //
@@ -89,6 +90,12 @@ struct Robot {
     return disc_distance(ex, ey);
   }
 };
+
+// (best, bestk) <- lexicographic minimum with (d, k): what "the nearest point, the smallest index among equals" means in
+// csrc/clearance.hip and csrc/swept.hip.  A NaN or +inf distance never enters: the initial (+inf, -1) stays.
+__device__ __forceinline__ void take_min(float d, int k, float* best, int* bestk) {
+  if (d < *best || (d == *best && k < *bestk)) { *best = d; *bestk = k; }
+}
 
 // All pairs: f(ox, oy, k) for every point k of the cloud in ascending k.  The points pass through the workgroup's LDS arrays
 // ox, oy [THREADS] a tile at a time between two barriers, so every thread has to call this, one without a pose included.

@@ -1,0 +1,302 @@
+// Swept collision check between consecutive poses of a path: what `collides` (csrc/path_eval.hip) and the clearance of
+// csrc/clearance.hip do not see.  Both judge SAMPLED poses; a robot whose dense poses lie either side of a one-cell wall is
+// reported free by both.  Here the unit is the segment (a, b) between two poses -- x and y linear, theta linear along the
+// wrapped shortest difference, the motion nfopp_path_interpolate lays its poses on.  Definitions: include/nfopp_hip.h.
+//
+//   * nfopp_swept_segments        all pairs, obstacle points staged in LDS (for_all_points)
+//   * nfopp_swept_segments_cells  the same minimum over the rows of cells that cover the segment (below)
+//   * nfopp_path_swept_labels     one workgroup per path: segment values -> the labels nfopp_path_select_best reads
+// The per-point terms are the fp32 expressions of csrc/point_cloud.h that the checkers and the nearest-obstacle query
+// evaluate.  No atomics; every minimum is the lexicographic minimum of (value, index), which does not depend on the order
+// the points are visited in: both entries and any two runs give the same bits.
+#include "common.h"
+#include "point_cloud.h"
+
+// the arithmetic rule of point_cloud.h holds here too: explicit fmas, one operation per statement
+#pragma clang fp contract(off)
+
+namespace nfopp {
+
+constexpr int SW_THREADS = 256;
+constexpr float SW_COVER = 1.0f + 3.814697265625e-06f;   // 1 + 2^-18: what the cell coverage allows for rounding (below)
+constexpr float SW_MAX_TURN = 25.1327419f;                // 8 pi: the largest |theta_b - theta_a| the box certificate takes
+
+struct Segment {
+  Pose a, b;
+  float ex, ey, len2, len;   // e = b - a, |e|^2, |e|
+  float delta;               // box: NFOPP_SWEPT delta, the bound on any body point's travel; 0 for the disc
+  bool finite;               // both poses finite
+  bool in_domain;            // box: delta <= 4 reach and |theta_b - theta_a| <= 8 pi (what `slack` was derived for)
+};
+
+struct SweptArgs {
+  const float* a; const float* b; long long n; int dim;
+  PointCloud cloud; Robot robot;
+  float horizon;
+  float* value; int* index;
+};
+
+template <int MODE>
+__device__ __forceinline__ Segment load_segment(const SweptArgs& g, long long p) {
+  Segment s;
+  s.a = load_pose<MODE>(g.a, g.dim, p);
+  s.b = load_pose<MODE>(g.b, g.dim, p);
+  s.finite = s.a.finite && s.b.finite;
+  s.ex = s.b.x - s.a.x;
+  s.ey = s.b.y - s.a.y;
+  const float eyey = s.ey * s.ey;
+  s.len2 = __builtin_fmaf(s.ex, s.ex, eyey);
+  s.len = sqrtf(s.len2);          // disc_distance(ex, ey)
+  s.delta = 0.f;
+  s.in_domain = true;
+  if (MODE == 1) {
+    const float turn = g.b[p * g.dim + 2] - g.a[p * g.dim + 2];
+    const float dth = fabsf(wrap_angle(turn));
+    s.delta = __builtin_fmaf(g.robot.reach, dth, s.len);
+    const float limit = 4.f * g.robot.reach;
+    s.in_domain = s.delta <= limit && fabsf(turn) <= SW_MAX_TURN;
+  }
+  return s;
+}
+
+// MODE 0: the distance from the obstacle to the segment [a, b].  The end terms are the disc_distance the circle checker
+// compares; the perpendicular term enters only where the obstacle projects strictly inside the segment.
+// MODE 1: d_a + d_b, the two distances from the obstacle to the closed box at either end (delta is taken off once, at the end:
+// one subtraction of a per-segment constant is monotone, so it does not change which point wins).
+template <int MODE>
+__device__ __forceinline__ float segment_term(const SweptArgs& g, const Segment& s, float ox, float oy) {
+  if (MODE == 1) return g.robot.point_distance<1>(s.a, ox, oy) + g.robot.point_distance<1>(s.b, ox, oy);
+  const float ax = ox - s.a.x, ay = oy - s.a.y;
+  const float bx = ox - s.b.x, by = oy - s.b.y;
+  float v = fminf(disc_distance(ax, ay), disc_distance(bx, by));
+  const float eyay = s.ey * ay;
+  const float t = __builtin_fmaf(s.ex, ax, eyay);
+  if (t > 0.f && t < s.len2) {     // never for a zero-length segment: t == len2 == 0
+    const float eyax = s.ey * ax;
+    const float cross = __builtin_fmaf(s.ex, ay, -eyax);
+    v = fminf(v, fabsf(cross) / s.len);
+  }
+  return v;
+}
+
+// One rule for both entries, so that they write the same bytes: a non-finite segment and an empty cloud give +inf / -1, a
+// box segment outside the certificate's domain -inf / -1, a value above the horizon +inf / -1.
+template <int MODE>
+__device__ __forceinline__ void store_segment(const SweptArgs& g, long long p, const Segment& s, float best, int bestk) {
+  float v = best;
+  int k = bestk;
+  if (MODE == 1 && bestk >= 0) v = best - s.delta;
+  if (!s.finite || g.cloud.n == 0) { v = __builtin_inff(); k = -1; }
+  else if (!s.in_domain) { v = -__builtin_inff(); k = -1; }
+  else if (!(v <= g.horizon)) { v = __builtin_inff(); k = -1; }
+  g.value[p] = v;
+  if (g.index) g.index[p] = k;
+}
+
+// ---- all pairs ------------------------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(SW_THREADS) void swept_kernel(const SweptArgs g) {
+  __shared__ float ox[SW_THREADS], oy[SW_THREADS];
+  const long long p = blockIdx.x * (long long)SW_THREADS + threadIdx.x;
+  const bool valid = p < g.n;
+  Segment s = {};
+  if (valid) s = load_segment<MODE>(g, p);
+  float best = __builtin_inff();
+  int bestk = -1;
+  for_all_points<SW_THREADS>(g.cloud, ox, oy, [&](float px, float py, int k) {
+    take_min(segment_term<MODE>(g, s, px, py), k, &best, &bestk);
+  });
+  if (valid) store_segment<MODE>(g, p, s, best, bestk);
+}
+
+// ---- cell index: which cells a segment has to look at --------------------------------------------------------------------
+// The indexed entry must write what the all-pairs entry writes.  That one takes the minimum over every point and then
+// discards it when it exceeds the horizon, so it is enough to visit every point k whose COMPUTED value is <= horizon: the
+// winner and everything tied with it are among them, and if there is none both entries write +inf / -1.
+//  (1) Disc.  The computed value of a point is min(da, db, perp).  Each of the three is a lower bound, up to rounding, on
+//      a true distance from the point to a point of the segment: da and db within 3 * 2^-24 relative (test_gpu_clearance's
+//      count), perp = |cross| / |e| within 12 * 2^-24 (|o - a| + |e|) of the true distance to the line (cross: four
+//      roundings of products of two rounded differences, |e|: three; the count is in tests/test_gpu_swept.py).  So a
+//      point with computed value <= h lies within h + 12 * 2^-24 (2 h + 2 |e|) of the segment, hence inside the bounding
+//      box of a and b inflated by  R = h + 2^-18 (h + |e|)   (2^-18 = 64 * 2^-24).
+//  (2) Box.  value <= h means fl(fl(da + db) - delta) <= h with db >= 0, so da <= (delta + h)(1 + 2 * 2^-24).  The box lies in
+//      the disc of radius `reach` about the robot's origin and the fp32 distance is below the exact one by less than
+//      15 * 2^-24 |o - a| (csrc/clearance.hip, (3)), so |o - a| (1 - 15 * 2^-24) <= reach + (delta + h)(1 + 2 * 2^-24): the point
+//      lies within  R = (reach + delta + h)(1 + 2^-18)  of a's origin, a fortiori inside the bounding box of a and b
+//      inflated by R (the same holds about b; one rectangle serves both shapes).
+//  (3) From coordinates to cells.  Each bound w = min - R or max + R is formed in fp32 and then moved outward by
+//      4 * 2^-24 |w|, more than the rounding of its own two operations, so the fp32 bound encloses the exact one.
+//      CellIndex::axis_cell is a chain of monotone operations (correctly rounded subtraction and division, floor, clamp),
+//      and points and bounds go through that one function: lo <= ox <= hi implies cell(lo) <= cell(ox) <= cell(hi), for a
+//      point clamped into a border cell too.  One further cell is visited on each side: it costs a few points per segment
+//      and keeps the coverage from resting on the last bit of (1) to (3).
+//  Cells are formed only through CellIndex::cell and row_range; the loops run over at most cells_y rows of the index.
+template <int MODE>
+__device__ __forceinline__ float cover_radius(const SweptArgs& g, const Segment& s) {
+  if (MODE == 0) return __builtin_fmaf(3.814697265625e-06f, g.horizon + s.len, g.horizon);
+  const float reach_delta = g.robot.reach + s.delta;
+  const float r = reach_delta + g.horizon;
+  return r * SW_COVER;
+}
+
+__device__ __forceinline__ float outward(float w, float sign) {   // w moved by 4 * 2^-24 |w| towards sign * inf
+  return __builtin_fmaf(fabsf(w), sign * 2.384185791015625e-07f, w);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(SW_THREADS) void swept_cells_kernel(const SweptArgs g) {
+  const long long p = blockIdx.x * (long long)SW_THREADS + threadIdx.x;
+  if (p >= g.n) return;
+  const Segment s = load_segment<MODE>(g, p);
+  float best = __builtin_inff();
+  int bestk = -1;
+  if (s.finite && s.in_domain) {
+    const float r = cover_radius<MODE>(g, s);
+    const float lox = outward(fminf(s.a.x, s.b.x) - r, -1.f), hix = outward(fmaxf(s.a.x, s.b.x) + r, 1.f);
+    const float loy = outward(fminf(s.a.y, s.b.y) - r, -1.f), hiy = outward(fmaxf(s.a.y, s.b.y) + r, 1.f);
+    int x_lo, y_lo, x_hi, y_hi;
+    g.cloud.index.cell(lox, loy, &x_lo, &y_lo);
+    g.cloud.index.cell(hix, hiy, &x_hi, &y_hi);
+    x_lo = max(x_lo - 1, 0); x_hi = min(x_hi + 1, g.cloud.index.cells_x - 1);
+    y_lo = max(y_lo - 1, 0); y_hi = min(y_hi + 1, g.cloud.index.cells_y - 1);
+    const float* pt = g.cloud.points;
+    for (int yy = y_lo; yy <= y_hi; ++yy) {
+      int k, k1;
+      g.cloud.index.row_range(yy, x_lo, x_hi, &k, &k1);
+      for (; k < k1; ++k)
+        take_min(segment_term<MODE>(g, s, pt[2 * (long long)k], pt[2 * (long long)k + 1]), k, &best, &bestk);
+    }
+  }
+  store_segment<MODE>(g, p, s, best, bestk);
+}
+
+// ---- path reduction -------------------------------------------------------------------------------------------------
+struct SweptLabelArgs {
+  const float* poses;   // [B, m, D]
+  const float* value;   // [B, m - 1]
+  float* labels;        // [B * m] in / out
+  int m, dim, box;
+  float threshold;      // radius (disc) or slack (box)
+  unsigned char* status; float* worst;
+};
+
+constexpr int SL_THREADS = 256;
+constexpr int SL_WAVES = SL_THREADS / 64;
+
+__global__ __launch_bounds__(SL_THREADS) void path_swept_labels_kernel(const SweptLabelArgs g) {
+  __shared__ float red[SL_WAVES];
+  __shared__ int redi[SL_WAVES], redf[SL_WAVES];
+  const long long b = blockIdx.x;
+  const int m = g.m, D = g.dim;
+  const float* poses = g.poses + b * m * D;
+  const float* value = g.value + b * (m - 1);
+  float* labels = g.labels + b * m;
+  const int used = g.box ? 3 : 2;   // the components the segment kernels' `finite` looks at
+  float best = __builtin_inff();
+  int bestj = 0x7fffffff, flags = 0;   // bit 0: a pose in collision, bit 1: a segment not certified
+  for (int j = threadIdx.x; j < m; j += SL_THREADS) {
+    if (labels[j] != 0.0f) flags |= 1;
+    if (j == m - 1) break;            // the last pose keeps its label
+    const float v = value[j];
+    bool finite = true;
+    for (int d = 0; d < used; ++d) finite = finite && isfinite(poses[j * D + d]) && isfinite(poses[(j + 1) * D + d]);
+    const bool certified = finite && (g.box ? v > g.threshold : v >= g.threshold);
+    if (!certified) { flags |= 2; labels[j] = 1.0f; }
+    if (v < best || (v == best && j < bestj)) { best = v; bestj = j; }
+  }
+  // fixed order: xor tree inside each wave, then the waves one after the other
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o);
+    const int oj = __shfl_xor(bestj, o);
+    flags |= __shfl_xor(flags, o);
+    if (ov < best || (ov == best && oj < bestj)) { best = ov; bestj = oj; }
+  }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = best; redi[threadIdx.x >> 6] = bestj; redf[threadIdx.x >> 6] = flags; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < SL_WAVES; ++w) {
+      flags |= redf[w];
+      if (red[w] < best || (red[w] == best && redi[w] < bestj)) { best = red[w]; bestj = redi[w]; }
+    }
+    // a disc segment that is not certified IS a collision; a box segment is only undecided
+    if (g.status) g.status[b] = (flags & 1) || (!g.box && (flags & 2)) ? 1 : ((flags & 2) ? 2 : 0);
+    if (g.worst) { g.worst[2 * b] = best; g.worst[2 * b + 1] = (float)bestj; }
+  }
+}
+
+template <int MODE>
+static void launch_swept(const SweptArgs& g, bool cells, hipStream_t st) {
+  const unsigned grid = (unsigned)((g.n + SW_THREADS - 1) / SW_THREADS);
+  if (cells) hipLaunchKernelGGL(swept_cells_kernel<MODE>, dim3(grid), dim3(SW_THREADS), 0, st, g);
+  else hipLaunchKernelGGL(swept_kernel<MODE>, dim3(grid), dim3(SW_THREADS), 0, st, g);
+}
+
+static int swept(bool cells, const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim,
+                 const float* obstacles_dev, int32_t n_obstacles, const int32_t* cell_start_dev, int32_t cells_x,
+                 int32_t cells_y, float cell_x0, float cell_y0, float cell_size, const float* box4, float horizon,
+                 float* value_dev, int32_t* index_dev, void* stream) {
+  NFOPP_REQUIRE(n >= 0 && (pose_dim == 2 || pose_dim == 3), "need n >= 0 and pose_dim 2 or 3");
+  NFOPP_REQUIRE(n <= (int64_t)0x7fffffff * SW_THREADS, "too many segments for one call");
+  NFOPP_REQUIRE(!box4 || pose_dim == 3, "the box robot needs poses with a heading (pose_dim 3)");
+  NFOPP_REQUIRE(horizon >= 0.f, "the horizon must be >= 0");   // false for a NaN too
+  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
+  SweptArgs g = {};
+  if (cells) {
+    const int rc = fill_cell_index(&g.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size,
+                                   n_obstacles > 0);
+    if (rc) return rc;
+    NFOPP_REQUIRE((long long)cells_x * cells_y <= MAX_INDEX_CELLS, "the index holds between 1 and 65536 cells");
+  }
+  if (n == 0) return NFOPP_OK;
+  NFOPP_REQUIRE(a_dev && b_dev && value_dev, "null device pointer");
+  g.a = a_dev; g.b = b_dev; g.n = n; g.dim = pose_dim; g.cloud.points = obstacles_dev; g.cloud.n = n_obstacles;
+  g.horizon = horizon; g.value = value_dev; g.index = index_dev;
+  if (box4) set_box(&g.robot, box4);
+  if (n_obstacles == 0) cells = false;   // nothing to search: the all-pairs kernel writes +inf / -1
+  if (box4) launch_swept<1>(g, cells, (hipStream_t)stream);
+  else launch_swept<0>(g, cells, (hipStream_t)stream);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}
+
+}  // namespace nfopp
+
+using namespace nfopp;
+
+extern "C" float nfopp_swept_slack(const float* box4) {
+  return box4 ? box_reach(box4) * NFOPP_SWEPT_SLACK_REL : 0.f;
+}
+
+extern "C" int nfopp_swept_segments(const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim,
+                                    const float* obstacles_dev, int32_t n_obstacles, const float* box4, float horizon,
+                                    float* value_dev, int32_t* index_dev, void* stream) {
+  return swept(false, a_dev, b_dev, n, pose_dim, obstacles_dev, n_obstacles, nullptr, 0, 0, 0.f, 0.f, 0.f, box4, horizon,
+               value_dev, index_dev, stream);
+}
+
+extern "C" int nfopp_swept_segments_cells(const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim,
+                                          const float* obstacles_sorted_dev, int32_t n_obstacles,
+                                          const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y, float cell_x0,
+                                          float cell_y0, float cell_size, const float* box4, float horizon,
+                                          float* value_dev, int32_t* index_dev, void* stream) {
+  return swept(true, a_dev, b_dev, n, pose_dim, obstacles_sorted_dev, n_obstacles, cell_start_dev, cells_x, cells_y, cell_x0,
+               cell_y0, cell_size, box4, horizon, value_dev, index_dev, stream);
+}
+
+extern "C" int nfopp_path_swept_labels(const float* poses_dev, const float* value_dev, float* labels_dev, int64_t batch,
+                                       int32_t poses_per_path, int32_t dim, float threshold, int32_t box,
+                                       uint8_t* status_dev, float* worst_dev, void* stream) {
+  NFOPP_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
+  NFOPP_REQUIRE(!box || dim == 3, "the box robot needs poses with a heading (dim 3)");
+  NFOPP_REQUIRE(batch >= 0 && batch <= 0x7fffffffLL && poses_per_path >= 2, "bad batch / pose count");
+  NFOPP_REQUIRE(threshold >= 0.f, "the radius / slack must be >= 0");
+  if (batch == 0) return NFOPP_OK;
+  NFOPP_REQUIRE(poses_dev && value_dev && labels_dev, "null device pointer");
+  SweptLabelArgs g;
+  g.poses = poses_dev; g.value = value_dev; g.labels = labels_dev; g.m = poses_per_path; g.dim = dim; g.box = box != 0;
+  g.threshold = threshold; g.status = status_dev; g.worst = worst_dev;
+  hipLaunchKernelGGL(path_swept_labels_kernel, dim3((unsigned)batch), dim3(SL_THREADS), 0, (hipStream_t)stream, g);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}

@@ -140,6 +140,15 @@ _SIGNATURES = {
                                                           ctypes.c_float, ctypes.POINTER(ctypes.c_float), _P, _P, _P]),
     "nfopp_path_stats": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32,
                                         ctypes.c_double, _P, _P, _P]),
+    "nfopp_swept_slack": (ctypes.c_float, [ctypes.POINTER(ctypes.c_float)]),
+    "nfopp_swept_segments": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                                            ctypes.POINTER(ctypes.c_float), ctypes.c_float, _P, _P, _P]),
+    "nfopp_swept_segments_cells": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P,
+                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.c_float, _P, _P,
+                                                  _P]),
+    "nfopp_path_swept_labels": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                               ctypes.c_int32, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -287,12 +287,14 @@ class BatchPlanner(object):
         return self.engine.full_trajectory().detach().cpu().numpy()
 
     # ---- path evaluation, best-path bookkeeping, early stop (scripts/run_bench_mr.py:109-132 for the batch) ---------
-    def evaluate(self, checker=None, sub=4, early_stop=False, min_clearance=None):
+    def evaluate(self, checker=None, sub=4, early_stop=False, min_clearance=None, swept=False):
         """Densifies every path (`sub` poses per segment), labels the poses with the ground-truth `checker`, keeps
         the shortest collision-free path per trajectory and -- with early_stop -- retires trajectories that are
         collision-free but no longer improving.  With `min_clearance` (point-cloud checkers only) a pose also counts as
-        colliding when the footprint's clearance is below it: a safety margin without a fatter robot.  Returns device
-        tensors (collides uint8 [B], length [B])."""
+        colliding when the footprint's clearance is below it: a safety margin without a fatter robot.  With `swept`
+        (point-cloud checkers only) a path also counts as colliding unless every segment between two consecutive dense
+        poses is certified free (`checker.swept`): the best path and the early stop then advance on certified paths only.
+        Returns device tensors (collides uint8 [B], length [B])."""
         from . import _lib as L
         checker = checker or self.checker
         if checker is None:
@@ -319,11 +321,52 @@ class BatchPlanner(object):
         if min_clearance is not None:   # combined on the device, no synchronisation
             clearance = checker.clearance(self._poses.view(B * m, D), out=self._pose_clearance(B * m))
             self._pose_labels.masked_fill_(clearance < float(min_clearance), 1.0)
+        if swept:
+            self._swept_labels(checker, self._poses, self._pose_labels)
         L.check(lib.nfopp_path_select_best(L.ptr(self._pose_labels), L.ptr(self._length), L.ptr(eng.traj), B, m, N, D,
                                            L.ptr(self.best_traj), L.ptr(self.best_length),
                                            L.ptr(self._collides, torch.uint8),
                                            L.ptr(eng.active, torch.uint8) if early_stop else None, L.stream_ptr()))
         return self._collides, self._length
+
+    def _swept_labels(self, checker, poses, labels, status=None, worst=None):
+        """Segment values of the dense `poses` [B, m, D] and their reduction into `labels` [B * m]; no synchronisation."""
+        if not hasattr(checker, "swept_labels"):
+            raise NotImplementedError("the swept check needs a point cloud: use DeviceCircleChecker or "
+                                      "DeviceRectangleChecker, not %s" % type(checker).__name__)
+        B, m, D = poses.shape
+        buf = getattr(self, "_segments", None)
+        if buf is None or buf[0].shape != (B, m - 1, D):
+            f32 = dict(dtype=torch.float32, device=poses.device)
+            buf = self._segments = (torch.empty(B, m - 1, D, **f32), torch.empty(B, m - 1, D, **f32),
+                                    torch.empty(B, m - 1, **f32))
+        seg_a, seg_b, values = buf
+        seg_a.copy_(poses[:, :-1])
+        seg_b.copy_(poses[:, 1:])
+        checker.swept(seg_a, seg_b, out=values.view(-1), index_out=False)
+        checker.swept_labels(poses, values, labels, status, worst)
+
+    def certify(self, checker=None, sub=4):
+        """(status uint8 [B], worst fp32 [B, 2]) device tensors for the current paths, densified as `evaluate` densifies them:
+        status 0 = every segment between consecutive poses certified free and no pose in collision, 1 = a pose (for the disc
+        robot: or a segment) in collision, 2 = box robot only, no pose collides but a segment could not be certified --
+        raise `sub`.  worst = the smallest segment value (`checker.swept`) and the segment attaining it.  The best-path
+        bookkeeping is not touched; nothing synchronises."""
+        from . import _lib as L
+        checker = checker or self.checker
+        if checker is None:
+            raise ValueError("certify() needs a ground-truth checker")
+        eng = self.engine
+        B, N, D = eng.B, eng.N, eng.D
+        m = (N + 1) * int(sub) + 1
+        f32 = dict(dtype=torch.float32, device=eng.device)
+        poses, length = torch.empty(B, m, D, **f32), torch.empty(B, **f32)
+        L.check(L.load().nfopp_path_interpolate(L.ptr(eng.traj), L.ptr(eng.start), L.ptr(eng.goal), B, N, D, int(sub),
+                                                L.ptr(poses), L.ptr(length), L.stream_ptr()))
+        labels = checker.labels(poses.view(B * m, D))
+        status, worst = torch.empty(B, dtype=torch.uint8, device=eng.device), torch.empty(B, 2, **f32)
+        self._swept_labels(checker, poses, labels, status, worst)
+        return status, worst
 
     def _pose_clearance(self, count):
         buf = getattr(self, "_clearance", None)

@@ -159,6 +159,46 @@ class _PointCloudChecker(object):
             torch.sub(dist, self.radius, out=dist).clamp_(min=0)
         return dist
 
+    swept_slack = 0.0   # the rectangle checker's rounding allowance (nfopp_swept_slack); the disc's test is exact
+
+    def swept(self, poses_a, poses_b, horizon=None, out=None, index_out=None):
+        """(value [n] fp32, index [n] int32) per segment poses_a[p] -> poses_b[p] (nfopp_swept_segments[_cells]; x, y linear,
+        theta along the wrapped difference).  Disc: the exact distance from the nearest obstacle point to the segment, so
+        `value < radius` is the swept collision test.  Box: min (d_a + d_b) - delta, a certificate -- `value > swept_slack`
+        proves the whole segment free, anything else with free end poses is undecided (-inf: the poses are too far apart to
+        certify at all).  A value above `horizon` comes back as +inf / -1; the default, the radius for the disc and
+        `swept_slack` for the box, is the smallest that decides the verdicts: every value the comparison can reject is
+        kept.  `index_out=False` skips the index (None is returned for it).  Leading dimensions are flattened; views
+        are copied."""
+        d = poses_a.shape[-1]
+        a, b = poses_a.reshape(-1, d).contiguous(), poses_b.reshape(-1, d).contiguous()
+        if a.shape != b.shape:
+            raise ValueError("swept() needs as many start poses as end poses")
+        n = a.shape[0]
+        if horizon is None:
+            horizon = self.radius if self._box is None else self.swept_slack
+        value = torch.empty(n, dtype=torch.float32, device=a.device) if out is None else out
+        if index_out is False:
+            index = None
+        else:
+            index = torch.empty(n, dtype=torch.int32, device=a.device) if index_out is None else index_out
+        box = _f4(self._box) if self._box is not None else None
+        lib = _lib.load()
+        entry = lib.nfopp_swept_segments if self.cells is None else lib.nfopp_swept_segments_cells
+        _lib.check(entry(_lib.ptr(a), _lib.ptr(b), n, d, *self._cloud_args(), box, float(horizon), _lib.ptr(value),
+                         _lib.ptr(index, torch.int32), _lib.stream_ptr()))
+        return value, index
+
+    def swept_labels(self, poses, values, labels, status=None, worst=None):
+        """nfopp_path_swept_labels for `poses` [B, m, D], `values` [B, m - 1] of `swept` and the `labels` [B * m] this
+        checker wrote: marks, in place, the first pose of every segment that is not certified."""
+        B, m, d = poses.shape
+        threshold = self.radius if self._box is None else self.swept_slack
+        _lib.check(_lib.load().nfopp_path_swept_labels(_lib.ptr(poses), _lib.ptr(values), _lib.ptr(labels), B, m, d,
+                                                       float(threshold), int(self._box is not None),
+                                                       _lib.ptr(status, torch.uint8), _lib.ptr(worst), _lib.stream_ptr()))
+        return labels
+
     def update_from_map(self, grid_map, extra_points=None):
         """One sensor message (`CollisionCheckerAdapter._callback`, nfop/ros/collision_checker_adapter.py:17-27): the
         sensor's points first, then the map's, and the boundaries from the map."""
@@ -198,6 +238,7 @@ class DeviceRectangleChecker(_PointCloudChecker):
 
     def __init__(self, obstacle_points, box, boundaries=None, device="cuda"):
         self.box = self._box = tuple(float(v) for v in box)
+        self.swept_slack = float(_lib.load().nfopp_swept_slack(_f4(self.box)))
         self._setup(obstacle_points, boundaries, device)
 
     def _reach(self):
@@ -238,6 +279,10 @@ class DeviceGridChecker(object):
     def clearance(self, poses, out=None):
         raise NotImplementedError("clearance needs a point cloud: use DeviceCircleChecker or DeviceRectangleChecker "
                                   "(the occupancy image has no nearest-obstacle query)")
+
+    def swept(self, poses_a, poses_b, horizon=None, out=None, index_out=None):
+        raise NotImplementedError("the swept check needs a point cloud: use DeviceCircleChecker or DeviceRectangleChecker "
+                                  "(DeviceGridMap.as_point_cloud gives the occupancy image's)")
 
 
 class BatchSampler(object):
