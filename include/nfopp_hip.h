@@ -309,7 +309,8 @@ int nfopp_get_matrix_path(void);
  *   path_dev [B, n_points, 3] (3 <= n_points <= 1026): near-duplicate filter, quadratic-spline re-sampling every
  *   distance_step metres over the chord-length parameter (float64), leading direction flip trimmed.  count_dev[b] =
  *   poses path b produces (may exceed max_out: only the first max_out are written to out_dev [B, max_out, 3] float64;
- *   call with max_out = 0 to size the buffer), -1 when fewer than 3 poses survive the filter (the reference raises). */
+ *   call with max_out = 0 to size the buffer), -1 when fewer than 3 poses survive the filter or two surviving poses
+ *   share a parameter value (a segment rounded away in the fp32 running length): the reference raises for both. */
 int nfopp_init_trajectories(const float* start_dev, const float* goal_dev, int64_t batch, int32_t n_waypoints,
                             int32_t dim, int32_t angles_with_direction, float* traj_dev, void* stream);
 int nfopp_path_postprocess(const float* path_dev, int64_t batch, int32_t n_points, float minimal_distance,

@@ -810,6 +810,10 @@ def path_postprocess(path, minimal_distance=0.001, distance_step=0.05):
         acc = F32(acc + dist[i])
         cum[i + 1] = acc
     param = cum.astype(np.float64) / np.float64(cum[-1])
+    if np.any(param[1:] == param[:-1]):
+        # a segment rounded away in the fp32 running sum (possible only for minimal_distance < ~1e-6 * 2^24 of path):
+        # scipy's make_interp_spline refuses the sites
+        raise ValueError("Expect x to not have duplicates")
     total = _pairwise_sum_f32(dist)
     count = int(F32(total / F32(distance_step)))
     # unfold_angles (utils/math.py:38-43) in fp32, first heading added in float64, stored back as fp32

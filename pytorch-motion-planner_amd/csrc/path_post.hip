@@ -28,7 +28,8 @@ struct PostArgs {
   int n, max_out;
   float min_dist, dist_step;
   double* out;         // [B, max_out, 3]
-  int* count;          // [B]: poses the path needs (after trimming); -1 = fewer than 3 poses survive the filter
+  int* count;          // [B]: poses the path needs (after trimming); -1 = no spline through the path: fewer than 3 poses
+                       // survive the filter, or two of them share a parameter value
 };
 
 // numpy's pairwise float summation order (8 partial sums per block of <= 128, halves split at a multiple of 8);
@@ -99,6 +100,7 @@ __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a)
     const int m = n - w;
     float* Q = P + 3 * w;
     int count = -1;
+    bool spline_exists = m >= 3;
     if (m >= 3) {
       // ---- parametrisation (:27-33) and total length (:21-25)
       float acc = 0.f;
@@ -112,6 +114,12 @@ __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a)
       }
       const double last = PAR[m - 1];
       for (int i = 0; i < m; ++i) PAR[i] = PAR[i] / last;
+      // scipy refuses duplicate sites ("Expect x to not have duplicates"): with minimal_distance below 1e-6 * 2^24 a
+      // segment can round away in the fp32 running sum, and the collocation matrix is then singular
+      for (int i = 1; i < m; ++i)
+        if (PAR[i] == PAR[i - 1]) spline_exists = false;
+    }
+    if (spline_exists) {
       const float total = pairwise_sum<4>(DIST, m - 1);
       count = (int)(total / a.dist_step);
       // ---- unfold headings (utils/math.py:38-43)

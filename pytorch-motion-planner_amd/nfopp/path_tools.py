@@ -37,7 +37,8 @@ class PathPostprocessor(object):
 
     def process_batch(self, paths):
         """paths: [B, n, 3] fp32 (tensor or array) -> (poses [B, max_count, 3] float64 HIP tensor, counts [B] int32);
-        poses[b, :counts[b]] is path b's result.  A path that collapses to < 3 poses raises like the reference."""
+        poses[b, :counts[b]] is path b's result.  A path that collapses to < 3 poses, or whose fp32 running length does
+        not advance between two kept poses (duplicate spline sites), raises like the reference."""
         paths = torch.as_tensor(np.asarray(paths, np.float32) if not torch.is_tensor(paths) else paths,
                                 dtype=torch.float32, device=self._device).contiguous()
         b, n, d = paths.shape
@@ -48,7 +49,8 @@ class PathPostprocessor(object):
         _lib.check(lib.nfopp_path_postprocess(_lib.ptr(paths), b, n, float(self._minimal_distance),
                                               float(self._distance_step), 0, None, _lib.ptr(counts, torch.int32), _lib.stream_ptr()))
         if b and int(counts.min()) < 0:
-            raise ValueError("a path collapses to fewer than 3 poses: no quadratic spline through it")
+            raise ValueError("a path collapses to fewer than 3 poses, or two of its poses share a parameter value: "
+                             "no quadratic spline through it")
         cap = int(counts.max()) if b else 0
         out = torch.zeros(b, max(cap, 1), 3, dtype=torch.float64, device=paths.device)
         if cap:

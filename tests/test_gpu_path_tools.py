@@ -1,5 +1,7 @@
 """GPU: device trajectory initialiser (csrc/traj_init.hip) and path post-processor (csrc/path_post.hip) through the
-C ABI, against outputs of the reference itself (tests/golden/g11, g12) and the oracle on random batches."""
+C ABI, against outputs of the reference itself (tests/golden/g11, g12) and the oracle on random batches.  The edges of
+both kernels (lengths, thresholds, count boundaries, +-pi, batch and max_out behaviour) are in
+tests/test_gpu_path_tools_edges.py."""
 import numpy as np
 import pytest
 import torch
