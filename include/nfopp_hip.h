@@ -541,6 +541,74 @@ int nfopp_path_swept_labels(const float* poses_dev, const float* value_dev, floa
                             int32_t poses_per_path, int32_t dim, float threshold, int32_t box, uint8_t* status_dev,
                             float* worst_dev, void* stream);
 
+/* ---- box robot: undecided swept segments resolved by bisection (csrc/swept.hip), additive under ABI 6 ------------------
+ * nfopp_swept_refine / nfopp_swept_refine_cells: box robot only (box4 required, pose_dim 3).  The certificate above is
+ * applied to dyadic pieces of the segment and the rectangle checker's label to their midpoints until every piece is proven
+ * free, a colliding pose is found or a limit is reached.
+ *
+ * Sub-poses.  For a segment (a, b), a depth d and an index i in 0 .. 2^d the parameter is s = i * 2^-d (exact in fp32):
+ *   pose(0) = a as loaded, pose(1) = b as loaded, with its raw heading; otherwise
+ *   x = fmaf(s, ex, a.x), y = fmaf(s, ey, a.y), theta = fmaf(s, dth, theta_a),
+ *   ex = b.x - a.x, ey = b.y - a.y, dth = wrap_angle(theta_b - theta_a): the motion nfopp_path_interpolate lays its poses on.
+ * Piece test.  cert(p, q) = the box value nfopp_swept_segments gives the segment (p, q) at horizon = slack, the domain rule
+ *   included (delta > 4 reach or |theta_q - theta_p| > 8 pi, raw: not certified).  A piece is certified iff cert > slack; an
+ *   empty cloud certifies everything.  hits(p) = the rectangle checker's label over the cloud: a point strictly inside.
+ * Decision, refine(a, b; max_depth, node_budget), in this order:
+ *   1. a non-finite component in either pose: UNDECIDED, s = -1, depth = 0 (as nfopp_path_swept_labels treats it);
+ *   2. hits(a): HIT, s = 0; else hits(b): HIT, s = 1; both at depth 0;
+ *   3. a pre-order walk of the dyadic tree from node (d = 0, i = 0); node (d, i) covers [i 2^-d, (i + 1) 2^-d]:
+ *        cert certifies the piece: the node is FREE;  else d == max_depth: the node is UNDECIDED;
+ *        else the midpoint pose hits: the whole segment is HIT, s = (2 i + 1) 2^-(d + 1), stop;
+ *        else the left child, then the right child
+ *      (no stack: after finishing (d, i), while i is odd i >>= 1, d -= 1; stop if d == 0; else i += 1);
+ *   4. without a HIT the segment is UNDECIDED when any node was, else FREE;
+ *   5. node_budget bounds the work: every piece test and every midpoint test is one evaluation of the candidate points,
+ *      and each counts one against node_budget.  When node_budget evaluations are spent the walk stops UNDECIDED (a HIT
+ *      found before that stands).  The order is fixed, so the outcome is deterministic.  node_budget = 1 pays for the
+ *      root piece alone: the max_depth = 0 answer;
+ *   6. depth = the deepest level at which a piece was tested.
+ * Consequences.  FREE is a proof: the Lipschitz argument above on each certified piece, and the pieces cover [0, 1].  HIT is a
+ *   proof: a pose of the motion has an obstacle point strictly inside the box.  depth == 0 && FREE is today's value > slack
+ *   (where no end pose hits).  s is the first hit in pre-order, not necessarily the smallest s.  A segment the domain rule
+ *   refuses is simply split -- except that the last piece keeps b's RAW heading, so a raw turn above 8 pi stays UNDECIDED
+ *   (or becomes a HIT): wrap the headings first.  Termination: if every obstacle point stays at least c from the box along
+ *   the whole motion every piece has d_a + d_b >= 2 c, so a piece is certified once its delta is below 2 c - slack, and
+ *   the segment is decided by depth ceil(log2(delta / (2 c - slack))) + 1 (the + 1 absorbs the rounding of a piece's delta).
+ * Defaults of the Python layer: max_depth = 8 (0 <= max_depth <= 20; at delta = 4 reach, about 2 m, the pieces are 8 mm long:
+ *   more than about 4 mm of clearance is decided), node_budget = 1024 (>= 1).
+ * status_dev uint8 [n]: 0 free, 1 hit, 2 undecided.  s_dev fp32 [n] (may be null): the parameter of the hit, -1 where there
+ *   is none.  depth_dev uint8 [n] (may be null).  status_dev holds the same bytes with and without the other two.  Both
+ *   entries write the same bytes, run after run (no atomics; only comparisons leave the reductions over the points, and a
+ *   minimum and an OR do not depend on the order).  n = 0 is a no-op.  Null a / b / status, a missing box4, pose_dim != 3,
+ *   max_depth outside 0 .. 20 and node_budget < 1 are argument errors.
+ * Work shape: one thread per segment decides 1, 2 and the root piece; each remaining segment is walked by one wavefront
+ *   over the segment's candidate points staged in LDS (1024 of them; further ones are read from global memory, none is
+ *   dropped).  nfopp_swept_refine_cells gathers the candidates ONCE per segment from the rows of cells covering the
+ *   bounding box of a and b inflated by (reach + delta_root + slack)(1 + 2^-18), bounds moved outward, one further cell per
+ *   side; delta_root is the fp32 delta of the whole segment, inside the certificate's domain or not.  Every sub-pose lies
+ *   in that bounding box, a piece's cert <= slack needs a point within reach + delta_piece + slack of a sub-pose, a midpoint
+ *   hit a point within reach (csrc/swept.hip has the argument).
+ *
+ * nfopp_path_refined_labels: for B paths of m = poses_per_path poses, seg_status_dev uint8 [B, m - 1] and seg_s_dev fp32
+ *   [B, m - 1] as nfopp_swept_refine wrote them, labels_dev [B * m] as the checker wrote them: labels_dev[b, j] <- 1 where
+ *   segment j is not free; the last pose keeps its label.  status_dev [B] uint8 (may be null): 1 if a pose label was set on
+ *   entry or a segment is a hit, else 2 if a segment is undecided, else 0.  first_dev [B, 2] fp32 (may be null; needs
+ *   seg_s_dev): the first segment that is not free and its s, (-1, -1) if there is none.  One workgroup per path,
+ *   reductions in a fixed order.  nfopp_path_select_best reads the labels unchanged. */
+#define NFOPP_REFINE_FREE 0
+#define NFOPP_REFINE_HIT 1
+#define NFOPP_REFINE_UNDECIDED 2
+int nfopp_swept_refine(const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim, const float* obstacles_dev,
+                       int32_t n_obstacles, const float* box4, int32_t max_depth, int32_t node_budget, uint8_t* status_dev,
+                       float* s_dev, uint8_t* depth_dev, void* stream);
+int nfopp_swept_refine_cells(const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim,
+                             const float* obstacles_sorted_dev, int32_t n_obstacles, const int32_t* cell_start_dev,
+                             int32_t cells_x, int32_t cells_y, float cell_x0, float cell_y0, float cell_size,
+                             const float* box4, int32_t max_depth, int32_t node_budget, uint8_t* status_dev, float* s_dev,
+                             uint8_t* depth_dev, void* stream);
+int nfopp_path_refined_labels(const uint8_t* seg_status_dev, const float* seg_s_dev, float* labels_dev, int64_t batch,
+                              int32_t poses_per_path, uint8_t* status_dev, float* first_dev, void* stream);
+
 /* ---- exact Euclidean distance transform of an occupancy grid (csrc/grid_edt.hip), additive under ABI 6 ----------------
  * What a clearance margin for the grid-search seeds is decided on (nfopp/grid_search.py: OccupancyGrid.inflated).
  *

@@ -149,6 +149,13 @@ _SIGNATURES = {
                                                   _P]),
     "nfopp_path_swept_labels": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                                ctypes.c_int32, _P, _P, _P]),
+    "nfopp_swept_refine": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                                          ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
+    "nfopp_swept_refine_cells": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                                ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.c_int32,
+                                                ctypes.c_int32, _P, _P, _P, _P]),
+    "nfopp_path_refined_labels": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -287,18 +287,24 @@ class BatchPlanner(object):
         return self.engine.full_trajectory().detach().cpu().numpy()
 
     # ---- path evaluation, best-path bookkeeping, early stop (scripts/run_bench_mr.py:109-132 for the batch) ---------
-    def evaluate(self, checker=None, sub=4, early_stop=False, min_clearance=None, swept=False):
+    def evaluate(self, checker=None, sub=4, early_stop=False, min_clearance=None, swept=False, refine=None):
         """Densifies every path (`sub` poses per segment), labels the poses with the ground-truth `checker`, keeps
         the shortest collision-free path per trajectory and -- with early_stop -- retires trajectories that are
         collision-free but no longer improving.  With `min_clearance` (point-cloud checkers only) a pose also counts as
         colliding when the footprint's clearance is below it: a safety margin without a fatter robot.  With `swept`
         (point-cloud checkers only) a path also counts as colliding unless every segment between two consecutive dense
         poses is certified free (`checker.swept`): the best path and the early stop then advance on certified paths only.
-        Returns device tensors (collides uint8 [B], length [B])."""
+        With `refine=<max_depth>` as well (box checker only) the segments the one-shot certificate leaves undecided are
+        bisected on the device (`checker.swept_refine`): a path counts as colliding only where a segment is a proven hit or
+        still undecided at that depth.  Returns device tensors (collides uint8 [B], length [B])."""
         from . import _lib as L
         checker = checker or self.checker
         if checker is None:
             raise ValueError("evaluate() needs a ground-truth checker")
+        if refine is not None:   # before anything is launched or overwritten
+            if not swept:
+                raise ValueError("refine= belongs to the swept check: pass swept=True")
+            self._check_refine(checker, refine)
         eng = self.engine
         B, N, D = eng.B, eng.N, eng.D
         m = (N + 1) * int(sub) + 1
@@ -322,15 +328,19 @@ class BatchPlanner(object):
             clearance = checker.clearance(self._poses.view(B * m, D), out=self._pose_clearance(B * m))
             self._pose_labels.masked_fill_(clearance < float(min_clearance), 1.0)
         if swept:
-            self._swept_labels(checker, self._poses, self._pose_labels)
+            self._swept_labels(checker, self._poses, self._pose_labels, refine=refine)
         L.check(lib.nfopp_path_select_best(L.ptr(self._pose_labels), L.ptr(self._length), L.ptr(eng.traj), B, m, N, D,
                                            L.ptr(self.best_traj), L.ptr(self.best_length),
                                            L.ptr(self._collides, torch.uint8),
                                            L.ptr(eng.active, torch.uint8) if early_stop else None, L.stream_ptr()))
         return self._collides, self._length
 
-    def _swept_labels(self, checker, poses, labels, status=None, worst=None):
-        """Segment values of the dense `poses` [B, m, D] and their reduction into `labels` [B * m]; no synchronisation."""
+    def _swept_labels(self, checker, poses, labels, status=None, worst=None, refine=None):
+        """Segment values of the dense `poses` [B, m, D] and their reduction into `labels` [B * m]; no synchronisation.
+        With `refine` (a depth) the segments go through `checker.swept_refine` and nfopp_path_refined_labels instead, and
+        `worst` receives the reduction's `first`; the segment buffers are the same, the values' holding the hits' s."""
+        if refine is not None:
+            self._check_refine(checker, refine)
         if not hasattr(checker, "swept_labels"):
             raise NotImplementedError("the swept check needs a point cloud: use DeviceCircleChecker or "
                                       "DeviceRectangleChecker, not %s" % type(checker).__name__)
@@ -343,19 +353,41 @@ class BatchPlanner(object):
         seg_a, seg_b, values = buf
         seg_a.copy_(poses[:, :-1])
         seg_b.copy_(poses[:, 1:])
+        if refine is not None:
+            seg_status = getattr(self, "_segment_status", None)
+            if seg_status is None or seg_status.shape != (B, m - 1):
+                seg_status = self._segment_status = torch.empty(B, m - 1, dtype=torch.uint8, device=poses.device)
+            checker.swept_refine(seg_a, seg_b, max_depth=int(refine), status_out=seg_status.view(-1), s_out=values.view(-1),
+                                 depth_out=False)
+            checker.refined_labels(seg_status, values, labels, status, worst)
+            return
         checker.swept(seg_a, seg_b, out=values.view(-1), index_out=False)
         checker.swept_labels(poses, values, labels, status, worst)
 
-    def certify(self, checker=None, sub=4):
+    @staticmethod
+    def _check_refine(checker, refine):
+        """refine= is a depth of the box robot's bisection: ValueError for any other checker or depth."""
+        if getattr(checker, "_box", None) is None or not hasattr(checker, "swept_refine"):
+            raise ValueError("refine= is the box robot's (DeviceRectangleChecker), not %s's: the disc's swept test is exact "
+                             "and an occupancy image has no swept check" % type(checker).__name__)
+        if int(refine) != refine or not 0 <= int(refine) <= 20:
+            raise ValueError("refine= is a depth between 0 and 20, not %r" % (refine,))
+
+    def certify(self, checker=None, sub=4, refine=None):
         """(status uint8 [B], worst fp32 [B, 2]) device tensors for the current paths, densified as `evaluate` densifies them:
         status 0 = every segment between consecutive poses certified free and no pose in collision, 1 = a pose (for the disc
         robot: or a segment) in collision, 2 = box robot only, no pose collides but a segment could not be certified --
-        raise `sub`.  worst = the smallest segment value (`checker.swept`) and the segment attaining it.  The best-path
-        bookkeeping is not touched; nothing synchronises."""
+        raise `sub`, or pass `refine`.  worst = the smallest segment value (`checker.swept`) and the segment attaining it.
+        With `refine=<max_depth>` (box checker only; ValueError otherwise) the segments are bisected on the device
+        (`checker.swept_refine`) and the result is (status, first): status 1 = a pose collides or a segment is a proven hit,
+        2 = a segment is still undecided at that depth, 0 = proven free; first fp32 [B, 2] = the first segment that is not
+        proven free and its s, (-1, -1) without one.  The best-path bookkeeping is not touched; nothing synchronises."""
         from . import _lib as L
         checker = checker or self.checker
         if checker is None:
             raise ValueError("certify() needs a ground-truth checker")
+        if refine is not None:
+            self._check_refine(checker, refine)
         eng = self.engine
         B, N, D = eng.B, eng.N, eng.D
         m = (N + 1) * int(sub) + 1
@@ -365,7 +397,7 @@ class BatchPlanner(object):
                                                 L.ptr(poses), L.ptr(length), L.stream_ptr()))
         labels = checker.labels(poses.view(B * m, D))
         status, worst = torch.empty(B, dtype=torch.uint8, device=eng.device), torch.empty(B, 2, **f32)
-        self._swept_labels(checker, poses, labels, status, worst)
+        self._swept_labels(checker, poses, labels, status, worst, refine=refine)
         return status, worst
 
     def _pose_clearance(self, count):

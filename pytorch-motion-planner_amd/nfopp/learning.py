@@ -230,6 +230,10 @@ class DeviceCircleChecker(_PointCloudChecker):
         _lib.check(entry(_lib.ptr(poses), n, d, *self._cloud_args(), self.radius, b, _lib.ptr(out), _lib.stream_ptr()))
         return out
 
+    def swept_refine(self, poses_a, poses_b, max_depth=8, node_budget=1024, status_out=None, s_out=None, depth_out=None):
+        raise NotImplementedError("the disc's swept() is already exact (value < radius is the swept collision test): "
+                                  "there is nothing to refine; swept_refine is DeviceRectangleChecker's")
+
 
 class DeviceRectangleChecker(_PointCloudChecker):
     """Box robot (x0, x1, y0, y1 in its own frame) against a point cloud (rectangle_collision_checker.py)."""
@@ -260,6 +264,51 @@ class DeviceRectangleChecker(_PointCloudChecker):
                                                                  self._reach(), b, _lib.ptr(out), _lib.stream_ptr()))
         return out
 
+    def swept_refine(self, poses_a, poses_b, max_depth=8, node_budget=1024, status_out=None, s_out=None, depth_out=None):
+        """(status [n] uint8, s [n] fp32, depth [n] uint8) per segment poses_a[p] -> poses_b[p] (nfopp_swept_refine[_cells]):
+        the certificate of `swept` on dyadic pieces of the segment and `labels`' predicate at their midpoints, in pre-order,
+        down to `max_depth` (0 .. 20) and for at most `node_budget` (>= 1) piece and midpoint tests per segment.  status 0 =
+        proven free, 1 = a pose of the motion has an obstacle point inside the box, at parameter `s` (0 and 1: the end
+        poses; the first hit in pre-order, -1 without one), 2 = undecided; `depth` = the deepest level tested.
+        `s_out=False` / `depth_out=False` skip that output (None is returned for it).  Leading dimensions are flattened;
+        views are copied.  Nothing synchronises."""
+        d = poses_a.shape[-1]
+        a, b = poses_a.reshape(-1, d).contiguous(), poses_b.reshape(-1, d).contiguous()
+        if a.shape != b.shape:
+            raise ValueError("swept_refine() needs as many start poses as end poses")
+        n = a.shape[0]
+
+        def output(given, dtype, what):
+            """A fresh [n] tensor, or the caller's once it is known to hold n elements of `dtype` on the poses' device."""
+            if given is None:
+                return torch.empty(n, dtype=dtype, device=a.device)
+            if not (isinstance(given, torch.Tensor) and given.dtype == dtype and given.device == a.device
+                    and given.numel() == n and given.is_contiguous()):
+                raise ValueError("%s must be a contiguous %s tensor of %d elements on %s, got %s"
+                                 % (what, dtype, n, a.device, _lib._describe(given)))
+            return given
+        status = output(status_out, torch.uint8, "status_out")
+        s = None if s_out is False else output(s_out, torch.float32, "s_out")
+        depth = None if depth_out is False else output(depth_out, torch.uint8, "depth_out")
+        lib = _lib.load()
+        entry = lib.nfopp_swept_refine if self.cells is None else lib.nfopp_swept_refine_cells
+        _lib.check(entry(_lib.ptr(a), _lib.ptr(b), n, d, *self._cloud_args(), _f4(self.box), int(max_depth), int(node_budget),
+                         _lib.ptr(status, torch.uint8), _lib.ptr(s), _lib.ptr(depth, torch.uint8), _lib.stream_ptr()))
+        return status, s, depth
+
+    def refined_labels(self, seg_status, seg_s, labels, status=None, first=None):
+        """nfopp_path_refined_labels for `seg_status`, `seg_s` [B, m - 1] of `swept_refine` and the `labels` [B * m] this
+        checker wrote: marks, in place, the first pose of every segment that is not proven free."""
+        B, m = seg_status.shape[0], seg_status.shape[1] + 1
+        if seg_s.shape != seg_status.shape or labels.numel() != B * m:
+            raise ValueError("refined_labels() needs seg_s of seg_status' shape [B, m - 1] and B * m labels")
+        if (status is not None and status.numel() != B) or (first is not None and first.numel() != 2 * B):
+            raise ValueError("refined_labels() writes B path statuses and [B, 2] first segments")
+        _lib.check(_lib.load().nfopp_path_refined_labels(_lib.ptr(seg_status, torch.uint8), _lib.ptr(seg_s), _lib.ptr(labels),
+                                                         B, m, _lib.ptr(status, torch.uint8), _lib.ptr(first),
+                                                         _lib.stream_ptr()))
+        return labels
+
 
 class DeviceGridChecker(object):
     """uint8 occupancy image (MapCollisionChecker of notebooks/onf_planner_image_map.ipynb cell 2)."""
@@ -282,6 +331,10 @@ class DeviceGridChecker(object):
 
     def swept(self, poses_a, poses_b, horizon=None, out=None, index_out=None):
         raise NotImplementedError("the swept check needs a point cloud: use DeviceCircleChecker or DeviceRectangleChecker "
+                                  "(DeviceGridMap.as_point_cloud gives the occupancy image's)")
+
+    def swept_refine(self, poses_a, poses_b, max_depth=8, node_budget=1024, status_out=None, s_out=None, depth_out=None):
+        raise NotImplementedError("the swept check needs a point cloud: use DeviceRectangleChecker "
                                   "(DeviceGridMap.as_point_cloud gives the occupancy image's)")
 
 
