@@ -631,6 +631,61 @@ size_t nfopp_grid_edt_workspace_bytes(int32_t rows, int32_t cols);
 int nfopp_grid_edt(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, int32_t border, int32_t* dist2_dev,
                    int32_t* nearest_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- any-angle shortening of grid-search paths by exact line of sight (csrc/grid_any_angle.hip), additive under ABI 6 --
+ * A shortest 8-connected path is a staircase and the spline through every cell centre wiggles with the cell size.  The two
+ * entries below skip the cells between path cells that see each other and seed the spline through the shortened polyline
+ * (nfopp/grid_search.py: shorten_paths, seed_polylines, grid_search_init(any_angle=True)).  The rule is this library's own.
+ *
+ * Line of sight.  Cells are unit squares, cell (r, c) the open square (c, c + 1) x (r, r + 1).  A = (r0, c0) sees
+ *   B = (r1, c1) iff no BLOCKED cell other than A and B has an open interior met by the segment between the two centres.
+ *   Such a segment never lies on a grid line; where it passes exactly through a lattice corner it meets the two diagonal
+ *   cells only, not the two beside the corner -- the search's "no corner rule" (a diagonal move between two walls is
+ *   legal), so consecutive cells of a traced path always see each other.
+ *   The cells are visited by an integer merge of the two crossing sequences: with ar = |r1 - r0|, ac = |c1 - c0|, column
+ *   crossing i = 1..ac lies at parameter (2i - 1) / (2 ac), row crossing j = 1..ar at (2j - 1) / (2 ar); compare
+ *   (2i - 1) ar with (2j - 1) ac: smaller steps the column, larger the row, equal both at once (only the diagonal cell is
+ *   visited).  Every product is at most 2 * 4096 * 4096 = 2^25: int32.  The merge visits exactly the cells whose interior
+ *   the segment meets, each once.
+ * Blocked.  Cell x is blocked for problem p iff dist2[x] <= cells2[p].  dist2_dev int32 [rows, cols] is the output of
+ *   nfopp_grid_edt with border = 0 (one image serves every clearance level; INT32_MAX everywhere on a grid without walls,
+ *   where nothing is blocked); cells2_dev int32 [batch] is the threshold of the level problem p was searched on, 0 on the
+ *   plain grid (dist2 <= 0 is exactly "wall"), null = all 0.  dist2 >= 0, so a negative threshold blocks nothing; it is
+ *   device data and not tested here (the Python wrapper refuses it).  The two end cells of a query are never tested: the
+ *   search forces the goal free and leaves the start untested.
+ * Anchors.  For a path p[0 .. n - 1]: a_0 = 0; a_{k+1} = the LARGEST j in (a_k, min(a_k + lookahead, n - 1)] such that
+ *   p[a_k] sees p[j], or a_k + 1 if there is none (only possible with a caller-made list that is not 8-connected); the
+ *   last anchor is n - 1.  Farthest visible, not "the first blocked cell ends the scan": visibility along a path is not
+ *   monotone.  lookahead >= 1 bounds the work on maze paths of thousands of cells.
+ * Dense points.  Each segment between anchors A -> B is refilled at the cell path's density: with m = max(|dr|, |dc|), for
+ *   t = 0 .. m - 1 the point in cell units is u_c = (double)c0 + (double)(dc * t) / (double)m, u_r alike, stored as fp32
+ *   metres x = (float)((u_c * resolution + resolution / 2) + origin_x), y from u_r and origin_y, float64 with every
+ *   operation rounded on its own; the centre of the last anchor is appended; m = 0 (a repeated cell) emits nothing.  For an
+ *   integer u this is bit for bit the centre nfopp_grid_seed_trajectories forms, so a path with nothing to shorten yields
+ *   exactly its polyline.  For a traced path the point count never exceeds the cell count.
+ *
+ * nfopp_grid_shorten_paths: cells_dev / count_dev / status_dev as nfopp_grid_trace_paths wrote them.  A row with
+ *   status != 0, count < 1, count > max_len or a cell outside the grid gets anchor_count = point_count = 0 and nothing else
+ *   of it is written.  Otherwise anchor_dev int32 [batch, max_len] <- the anchors (indices into the cell path),
+ *   anchor_count_dev [batch] their number; point_count_dev [batch] <- the number of dense points the path HAS, of which
+ *   the first max_points are written to points_dev fp32 [batch, max_points, 2] (xy; may be null: counts and anchors only).
+ *   count = 1 gives one anchor and one point.  One wavefront per problem: the lanes take the candidates j = hi - lane of a
+ *   round of 64, farthest first, each walks its own traversal up to its first blocked cell, and the highest visible
+ *   candidate of the first round that has one is taken by ballot; no atomics, the same bytes from run to run.
+ *   Argument errors: lookahead < 1, a grid beyond the limits of nfopp_grid_edt, resolution <= 0, max_len > 2^21 + 1.
+ * nfopp_grid_seed_polylines: nfopp_grid_seed_trajectories with the interior of the polyline read from points_dev fp32
+ *   [batch, max_len, 2] (count_dev points per row) instead of formed from cell centres: [start, points, goal] -> spline ->
+ *   waypoints, the same arithmetic, fallback rows (status != 0, count < 1, count > max_len) and workspace rule
+ *   (nfopp_grid_seed_workspace_bytes). */
+int nfopp_grid_shorten_paths(const int32_t* dist2_dev, int32_t rows, int32_t cols, const int32_t* cells_dev,
+                             const int32_t* count_dev, const int32_t* status_dev, const int32_t* cells2_dev, int64_t batch,
+                             int32_t max_len, int32_t lookahead, int32_t* anchor_dev, int32_t* anchor_count_dev,
+                             double origin_x, double origin_y, double resolution, int32_t max_points, float* points_dev,
+                             int32_t* point_count_dev, void* stream);
+int nfopp_grid_seed_polylines(const float* points_dev, const int32_t* count_dev, const int32_t* status_dev, int64_t batch,
+                              int32_t max_len, const float* start_dev, const float* goal_dev, int32_t n_waypoints,
+                              int32_t dim, int32_t angles_with_direction, float* traj_dev, void* workspace_dev,
+                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,7 @@ constexpr int SD_THREADS = 256;
 
 struct SeedArgs {
   const int* cells; const int* count; const int* status;
+  const float* points;      // [B, max_len, 2] fp32 xy: the interior of the polyline as given (cells is then null), else null
   int max_len, n, directed;
   const float* start; const float* goal;
   double ox, oy, res;
@@ -298,11 +299,13 @@ __device__ __forceinline__ void seed_body(const SeedArgs& a, double* W, long lon
   double* UP = DD + M;           // m super-diagonal
   float* P = reinterpret_cast<float*>(UP + M);   // 2m polyline (fp32, as the reference builds it)
   const int2* cells = reinterpret_cast<const int2*>(a.cells) + b * (long long)a.max_len;
+  const float* points = a.points ? a.points + b * (long long)a.max_len * 2 : nullptr;
   // polyline = [start, cell centres, goal] (astar_trajectory_initializer.py:19-20, 45-47: centres in float64, stored fp32)
   for (int k = threadIdx.x; k < m; k += SD_THREADS) {
     float x, y;
     if (k == 0) { x = s[0]; y = s[1]; }
     else if (k == m - 1) { x = g[0]; y = g[1]; }
+    else if (points) { x = points[2 * (k - 1)]; y = points[2 * (k - 1) + 1]; }
     else {
       const int2 rc = cells[k - 1];
       x = (float)(((double)rc.y * a.res + a.res / 2.0) + a.ox);
@@ -461,22 +464,20 @@ extern "C" size_t nfopp_grid_seed_workspace_bytes(int64_t batch, int32_t max_len
   return bytes <= SD_LDS_BYTES ? 0 : (size_t)bytes * (size_t)batch;
 }
 
-extern "C" int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int32_t* count_dev, const int32_t* status_dev,
-                                            int64_t batch, int32_t max_len, const float* start_dev, const float* goal_dev,
-                                            int32_t n_waypoints, int32_t dim, int32_t angles_with_direction,
-                                            double origin_x, double origin_y, double resolution, float* traj_dev,
-                                            void* workspace_dev, size_t workspace_bytes, void* stream) {
+// the launch both seeding entries share: `a` holds the source of the polyline's interior (cells or points) and its geometry
+static int seed_launch(SeedArgs a, const int32_t* count_dev, const int32_t* status_dev, int64_t batch, int32_t max_len,
+                       const float* start_dev, const float* goal_dev, int32_t n_waypoints, int32_t dim,
+                       int32_t angles_with_direction, float* traj_dev, void* workspace_dev, size_t workspace_bytes,
+                       void* stream) {
   NFOPP_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
   NFOPP_REQUIRE(batch >= 0 && batch <= 0x7fffffffLL && n_waypoints >= 1 && max_len >= 0, "bad sizes");
   NFOPP_REQUIRE(max_len <= (1 << 21) + 1, "path buffer longer than any path of a supported grid");
   NFOPP_REQUIRE(!(angles_with_direction && dim != 3), "heading initialisation needs SE(2) trajectories (dim 3)");
-  NFOPP_REQUIRE(resolution > 0.0, "bad resolution");
   if (batch == 0) return NFOPP_OK;
-  NFOPP_REQUIRE(count_dev && status_dev && start_dev && goal_dev && traj_dev && (cells_dev || max_len == 0), "null device pointer");
-  SeedArgs a;
-  a.cells = cells_dev; a.count = count_dev; a.status = status_dev; a.max_len = max_len; a.n = n_waypoints;
-  a.directed = angles_with_direction ? 1 : 0; a.start = start_dev; a.goal = goal_dev;
-  a.ox = origin_x; a.oy = origin_y; a.res = resolution; a.traj = traj_dev;
+  NFOPP_REQUIRE(count_dev && status_dev && start_dev && goal_dev && traj_dev && (a.cells || a.points || max_len == 0),
+                "null device pointer");
+  a.count = count_dev; a.status = status_dev; a.max_len = max_len; a.n = n_waypoints;
+  a.directed = angles_with_direction ? 1 : 0; a.start = start_dev; a.goal = goal_dev; a.traj = traj_dev;
   a.work = nullptr; a.work_stride = seed_doubles(max_len);
   size_t lds = (size_t)a.work_stride * 8;
   if ((long long)lds > SD_LDS_BYTES) {
@@ -490,4 +491,26 @@ extern "C" int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int3
   else hipLaunchKernelGGL(seed_kernel<2>, dim3((unsigned)batch), dim3(SD_THREADS), lds, (hipStream_t)stream, a);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;
+}
+
+extern "C" int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int32_t* count_dev, const int32_t* status_dev,
+                                            int64_t batch, int32_t max_len, const float* start_dev, const float* goal_dev,
+                                            int32_t n_waypoints, int32_t dim, int32_t angles_with_direction,
+                                            double origin_x, double origin_y, double resolution, float* traj_dev,
+                                            void* workspace_dev, size_t workspace_bytes, void* stream) {
+  NFOPP_REQUIRE(resolution > 0.0, "bad resolution");
+  SeedArgs a;
+  a.cells = cells_dev; a.points = nullptr; a.ox = origin_x; a.oy = origin_y; a.res = resolution;
+  return seed_launch(a, count_dev, status_dev, batch, max_len, start_dev, goal_dev, n_waypoints, dim, angles_with_direction,
+                     traj_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int nfopp_grid_seed_polylines(const float* points_dev, const int32_t* count_dev, const int32_t* status_dev,
+                                         int64_t batch, int32_t max_len, const float* start_dev, const float* goal_dev,
+                                         int32_t n_waypoints, int32_t dim, int32_t angles_with_direction, float* traj_dev,
+                                         void* workspace_dev, size_t workspace_bytes, void* stream) {
+  SeedArgs a;
+  a.cells = nullptr; a.points = points_dev; a.ox = a.oy = 0.0; a.res = 1.0;   // the geometry is in the points already
+  return seed_launch(a, count_dev, status_dev, batch, max_len, start_dev, goal_dev, n_waypoints, dim, angles_with_direction,
+                     traj_dev, workspace_dev, workspace_bytes, stream);
 }

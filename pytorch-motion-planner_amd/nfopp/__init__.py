@@ -7,7 +7,7 @@ from .batch import BatchPlanner, OnfFitter, shard_range, straight_line_init
 from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
 from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fields, grid_search_init, grid_search_paths,
-                          margin_cells2, seed_trajectories)
+                          margin_cells2, seed_polylines, seed_trajectories, shorten_paths)
 from .host_utils import (AttributeDict, CircleCollisionChecker,
                          CircleDirectedCollisionChecker, CollisionChecker, Position2, RectangleCollisionChecker,
                          TrajectoryInitializer)
@@ -26,7 +26,7 @@ __all__ = [
     "CircleCollisionChecker", "CircleDirectedCollisionChecker", "CollisionChecker", "Position2",
     "RectangleCollisionChecker", "TrajectoryInitializer", "ONF", "ConstrainedNERFOptPlanner", "ContinuousPlanner",
     "NERFOptPlanner", "PathPostprocessor", "init_trajectories", "OccupancyGrid", "grid_search_init", "grid_search_paths",
-    "distance_fields", "seed_trajectories", "margin_cells2", "NUM_PATH_STATS", "PATH_STAT_NAMES", "PATH_STAT_LENGTH",
+    "distance_fields", "seed_trajectories", "seed_polylines", "shorten_paths", "margin_cells2", "NUM_PATH_STATS", "PATH_STAT_NAMES", "PATH_STAT_LENGTH",
     "PATH_STAT_MAX_CURVATURE", "PATH_STAT_CURVATURE_AT", "PATH_STAT_CUSPS", "PATH_STAT_REVERSALS",
     "PATH_STAT_MIN_CLEARANCE", "PATH_STAT_CLEARANCE_AT", "PATH_STAT_MEAN_CLEARANCE",
 ]

@@ -124,6 +124,11 @@ _SIGNATURES = {
                                                     ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
     "nfopp_grid_edt_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "nfopp_grid_edt": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
+    "nfopp_grid_shorten_paths": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_int64,
+                                                ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_int32, _P, _P, _P]),
+    "nfopp_grid_seed_polylines": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_size_t, _P]),
     "nfopp_grid_to_points": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P]),

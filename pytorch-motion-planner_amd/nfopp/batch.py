@@ -166,15 +166,17 @@ class BatchPlanner(object):
     seed_status = None   # per-problem status of the last grid-search seeding (nfopp/grid_search.py), else None
     seed_margin = None   # the clearance margin each problem was seeded at (all zero without one); None without grid seeding
 
-    def init(self, starts, goals, boundaries, trajectories=None, initializer=None, seed_clearance=None):
-        """`seed_clearance`: grid_search_init's `clearance` for an OccupancyGrid initializer (an AstarTrajectoryInitializer
-        carries its own)."""
+    def init(self, starts, goals, boundaries, trajectories=None, initializer=None, seed_clearance=None, seed_any_angle=False):
+        """`seed_clearance` / `seed_any_angle`: grid_search_init's `clearance` / `any_angle` for an OccupancyGrid initializer
+        (an AstarTrajectoryInitializer carries its own)."""
         eng = self.engine
         eng.set_endpoints(starts, goals)
         eng.hyper = eng.hyper.replace(bounds=boundaries)
         self.seed_status = self.seed_margin = None
         if seed_clearance is not None and not isinstance(initializer, OccupancyGrid):
             raise ValueError("seed_clearance goes with an OccupancyGrid initializer")
+        if seed_any_angle and not isinstance(initializer, OccupancyGrid):
+            raise ValueError("seed_any_angle goes with an OccupancyGrid initializer")
         if initializer is not None:
             # grid-search seeding of the whole batch (csrc/grid_search.hip): an OccupancyGrid or an AstarTrajectoryInitializer
             if trajectories is not None:
@@ -182,7 +184,7 @@ class BatchPlanner(object):
             if isinstance(initializer, OccupancyGrid):
                 _, self.seed_status, self.seed_margin = grid_search_init(
                     initializer, eng.start, eng.goal, eng.N, self.init_angles_with_trajectory and eng.D == 3, out=eng.traj,
-                    clearance=() if seed_clearance is None else seed_clearance)
+                    clearance=() if seed_clearance is None else seed_clearance, any_angle=bool(seed_any_angle))
             elif isinstance(initializer, AstarTrajectoryInitializer):
                 initializer.initialize_batch(eng.start, eng.goal, eng.N, out=eng.traj, boundaries=boundaries)
                 self.seed_status, self.seed_margin = initializer.status, initializer.seed_margin

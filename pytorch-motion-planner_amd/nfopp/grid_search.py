@@ -259,16 +259,18 @@ def _margins(clearance):
 def _search_with_clearance(grid, starts, goals, clearance):
     """_search on the plain grid and on grid.inflated(margin) for every margin; each problem keeps the result of the largest
     margin at which its search returns status 0, else the plain grid's (with its status 1 / 2).  The levels are merged on
-    the device.  -> (cells, count, status, cost, starts, goals, seed_margin fp32 [B])."""
+    the device.  -> (cells, count, status, cost, starts, goals, seed_margin fp32 [B], seed_cells2 int32 [B]): the margin each
+    problem was seeded at and the threshold on dist2 of that level, both 0 for the plain grid."""
     starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
     cells, count, status, cost = _search(grid, starts, goals)[:4]
     seed_margin = torch.zeros(count.shape[0], dtype=torch.float32, device=count.device)
+    seed_cells2 = torch.zeros(count.shape[0], dtype=torch.int32, device=count.device)
     levels = []
     for m in _margins(clearance):
         if margin_cells2(m, grid.resolution) > 0:   # k = 0 is the plain grid
             levels.append((m, _search(grid.inflated(m), starts, goals)[:4]))
     if not levels:
-        return cells, count, status, cost, starts, goals, seed_margin
+        return cells, count, status, cost, starts, goals, seed_margin, seed_cells2
     max_len = max([cells.shape[1]] + [lv[1][0].shape[1] for lv in levels])
 
     def padded(c):
@@ -282,7 +284,8 @@ def _search_with_clearance(grid, starts, goals, clearance):
         cost = torch.where(ok[:, None], l_cost, cost)
         status = torch.where(ok, l_status, status)
         seed_margin = torch.where(ok, torch.full_like(seed_margin, m), seed_margin)
-    return cells.contiguous(), count.contiguous(), status.contiguous(), cost.contiguous(), starts, goals, seed_margin
+        seed_cells2 = torch.where(ok, torch.full_like(seed_cells2, margin_cells2(m, grid.resolution)), seed_cells2)
+    return cells.contiguous(), count.contiguous(), status.contiguous(), cost.contiguous(), starts, goals, seed_margin, seed_cells2
 
 
 def grid_search_paths(grid, starts, goals, clearance=None):
@@ -291,7 +294,15 @@ def grid_search_paths(grid, starts, goals, clearance=None):
     if clearance is None:
         return _search(grid, starts, goals)[:4]
     r = _search_with_clearance(grid, starts, goals, clearance)
-    return r[:4] + r[6:]
+    return r[:4] + r[6:7]
+
+
+def _seed_out(b, n_waypoints, d, dev, out):
+    if out is None:
+        return torch.empty(b, int(n_waypoints), d, dtype=torch.float32, device=dev)
+    if out.numel() != b * int(n_waypoints) * d or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous fp32 tensor of B * N * D elements")
+    return out
 
 
 def seed_trajectories(grid, cells, counts, status, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None):
@@ -305,10 +316,7 @@ def seed_trajectories(grid, cells, counts, status, starts, goals, n_waypoints, i
     counts = torch.as_tensor(counts, dtype=i32, device=dev).contiguous()
     status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
     max_len = cells.shape[1]
-    if out is None:
-        out = torch.empty(b, int(n_waypoints), d, dtype=torch.float32, device=dev)
-    elif out.numel() != b * int(n_waypoints) * d or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous fp32 tensor of B * N * D elements")
+    out = _seed_out(b, n_waypoints, d, dev, out)
     ws_bytes = lib.nfopp_grid_seed_workspace_bytes(b, max_len)
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
     bd = grid.boundaries
@@ -319,7 +327,81 @@ def seed_trajectories(grid, cells, counts, status, starts, goals, n_waypoints, i
     return out.view(b, int(n_waypoints), d)
 
 
-def grid_search_init(grid, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None, clearance=None):
+def _shorten_paths(grid, cells, counts, status, cells2, lookahead, max_points=None):
+    """shorten_paths on int32 device tensors that are already contiguous; cells2 is not looked at on the host."""
+    lib = _lib.load()
+    i32 = torch.int32
+    dev = cells.device
+    b, max_len = cells.shape[0], cells.shape[1]
+    max_points = max_len if max_points is None else int(max_points)
+    dist2, _ = grid.distance_transform(False)
+    rows, cols = grid.shape
+    anchors = torch.zeros(b, max_len, dtype=i32, device=dev)
+    anchor_counts = torch.zeros(b, dtype=i32, device=dev)
+    points = torch.zeros(b, max_points, 2, dtype=torch.float32, device=dev)
+    point_counts = torch.zeros(b, dtype=i32, device=dev)
+    bd = grid.boundaries
+    _lib.check(lib.nfopp_grid_shorten_paths(
+        _lib.ptr(dist2, i32), rows, cols, _lib.ptr(cells, i32), _lib.ptr(counts, i32), _lib.ptr(status, i32),
+        _lib.ptr(cells2, i32), b, max_len, int(lookahead), _lib.ptr(anchors, i32), _lib.ptr(anchor_counts, i32), bd[0], bd[2],
+        grid.resolution, max_points, _lib.ptr(points), _lib.ptr(point_counts, i32), _lib.stream_ptr()))
+    return points, point_counts, anchors, anchor_counts
+
+
+def shorten_paths(grid, cells, counts, status, cells2=None, lookahead=256, max_points=None):
+    """Any-angle shortening of cell paths by exact line of sight (csrc/grid_any_angle.hip; the rule: include/nfopp_hip.h).
+    cells int32 [B, max_len, 2], counts, status as grid_search_paths returns them; cells2 int32 [B] the threshold on the
+    grid's dist2 at or below which a cell blocks the view for that problem (None = 0 everywhere: walls only); from each
+    anchor the farthest cell within `lookahead` that it sees is the next.  -> (points fp32 [B, max_points, 2] xy in
+    metres, point_counts [B], anchors int32 [B, max_len] indices into the cell path, anchor_counts [B]), all on the device;
+    what lies behind a row's count is zero.  max_points defaults to max_len, which holds every traced path; a caller-made
+    list may have more points than cells, point_counts then still reports them all.  Uses grid.distance_transform(False),
+    which is computed once per grid."""
+    if int(lookahead) < 1:
+        raise ValueError("lookahead must be at least 1")
+    i32 = torch.int32
+    dev = grid.occupancy.device
+    cells = torch.as_tensor(cells, dtype=i32, device=dev).contiguous()
+    counts = torch.as_tensor(counts, dtype=i32, device=dev).contiguous()
+    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
+    if cells.dim() != 3 or cells.shape[2] != 2 or counts.shape != (cells.shape[0],) or status.shape != counts.shape:
+        raise ValueError("cells must be [B, max_len, 2], counts and status [B]")
+    if cells2 is not None:
+        cells2 = torch.as_tensor(cells2, dtype=i32, device=dev).contiguous()
+        if cells2.shape != counts.shape:
+            raise ValueError("cells2 must be [B]")
+        if bool((cells2 < 0).any()):
+            raise ValueError("a threshold on dist2 must be >= 0")
+    return _shorten_paths(grid, cells, counts, status, cells2, lookahead, max_points)
+
+
+def seed_polylines(grid, points, point_counts, status, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None):
+    """The seeding stage on given polylines: [start, the first point_counts[b] of points[b], goal] -> [B, N, D]
+    trajectories, with the arithmetic of seed_trajectories (which forms the points from cell centres).  points fp32
+    [B, max_len, 2] xy in metres; rows with status != 0 or a count outside 1..max_len get the straight line."""
+    lib = _lib.load()
+    starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
+    b, d = starts.shape
+    dev = starts.device
+    i32 = torch.int32
+    points = torch.as_tensor(points, dtype=torch.float32, device=dev).contiguous()
+    point_counts = torch.as_tensor(point_counts, dtype=i32, device=dev).contiguous()
+    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
+    if points.dim() != 3 or points.shape[0] != b or points.shape[2] != 2:
+        raise ValueError("points must be [B, max_len, 2]")
+    max_len = points.shape[1]
+    out = _seed_out(b, n_waypoints, d, dev, out)
+    ws_bytes = lib.nfopp_grid_seed_workspace_bytes(b, max_len)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+    _lib.check(lib.nfopp_grid_seed_polylines(
+        _lib.ptr(points), _lib.ptr(point_counts, i32), _lib.ptr(status, i32), b, max_len, _lib.ptr(starts), _lib.ptr(goals),
+        int(n_waypoints), d, 1 if (init_angles_with_trajectory and d == 3) else 0, _lib.ptr(out),
+        _lib.ptr(ws, torch.float64) if ws is not None else None, ws_bytes, _lib.stream_ptr()))
+    return out.view(b, int(n_waypoints), d)
+
+
+def grid_search_init(grid, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None, clearance=None,
+                     any_angle=False, lookahead=256):
     """Batched `AstarTrajectoryInitializer.initialize_trajectory`: -> (traj [B, N, D] fp32, status [B] int32), on the
     device.  status 0 = seeded along a shortest grid path; 1 = goal unreachable, 2 = start or goal outside the grid: those
     problems get the straight line of `init_trajectories`.
@@ -328,23 +410,35 @@ def grid_search_init(grid, starts, goals, n_waypoints, init_angles_with_trajecto
     path of grid.inflated(margin) for the largest margin at which that search succeeds, and on the plain grid, exactly as
     without the argument, if none does.  The start cell stays untested and the goal cell forced free on every level.  The
     call then returns (traj, status, seed_margin): seed_margin fp32 [B] is the margin each problem was seeded at, 0 for
-    the plain grid."""
+    the plain grid.
+
+    `any_angle`: the cell path is shortened by line of sight before the spline (shorten_paths with the given `lookahead`):
+    cells between two path cells that see each other are replaced by points on the straight segment.  A cell blocks the
+    view iff it is a wall of the level the problem was searched on, so a seed keeps the clearance it was found with.
+    What is returned does not change; without the flag nothing changes, down to the bits."""
+    if any_angle and int(lookahead) < 1:
+        raise ValueError("lookahead must be at least 1")
     if clearance is None:
         cells, count, status, _, starts, goals = _search(grid, starts, goals)
+        seed_margin = cells2 = None
+    else:
+        cells, count, status, _, starts, goals, seed_margin, cells2 = _search_with_clearance(grid, starts, goals, clearance)
+    if any_angle:
+        points, point_counts = _shorten_paths(grid, cells, count, status, cells2, lookahead)[:2]
+        traj = seed_polylines(grid, points, point_counts, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
+    else:
         traj = seed_trajectories(grid, cells, count, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
-        return traj, status
-    cells, count, status, _, starts, goals, seed_margin = _search_with_clearance(grid, starts, goals, clearance)
-    traj = seed_trajectories(grid, cells, count, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
-    return traj, status, seed_margin
+    return (traj, status) if clearance is None else (traj, status, seed_margin)
 
 
 class AstarTrajectoryInitializer(object):
     """Drop-in for nfop/astar/astar_trajectory_initializer.py (same constructor, same `initialize_trajectory`); the
     search runs on the device, and BatchPlanner / ConstrainedNERFOptPlanner seed whole batches through it.  `clearance`
-    (after the reference's own arguments) is grid_search_init's; `seed_margin` then holds the margin of each problem of the
-    last call, all zero without a clearance."""
+    (after the reference's own arguments) is grid_search_init's, as are `any_angle` and `lookahead`; `seed_margin` then holds
+    the margin of each problem of the last call, all zero without a clearance."""
 
-    def __init__(self, collision_checker, resolution=_MISSING, init_angles_with_trajectory=False, clearance=None):
+    def __init__(self, collision_checker, resolution=_MISSING, init_angles_with_trajectory=False, clearance=None,
+                 any_angle=False, lookahead=256):
         if not hasattr(collision_checker, "check_collision") and not hasattr(collision_checker, "labels"):
             raise NotImplementedError("AstarTrajectoryInitializer rasterises its collision checker: %r offers no "
                                       "check_collision, so there is no map to search" % (collision_checker,))
@@ -354,6 +448,7 @@ class AstarTrajectoryInitializer(object):
         self._resolution = resolution
         self._init_angles_with_trajectory = init_angles_with_trajectory
         self._clearance = clearance
+        self._any_angle, self._lookahead = bool(any_angle), lookahead
         self._grid = None
         self.status = None
         self.seed_margin = None
@@ -369,7 +464,8 @@ class AstarTrajectoryInitializer(object):
         device = out.device if out is not None else None
         traj, self.status, self.seed_margin = grid_search_init(
             self.grid(boundaries, device), starts, goals, n_waypoints, self._init_angles_with_trajectory, out=out,
-            clearance=() if self._clearance is None else self._clearance)
+            clearance=() if self._clearance is None else self._clearance, any_angle=self._any_angle,
+            lookahead=self._lookahead)
         return traj
 
     def initialize_trajectory(self, trajectory, start_point, goal_point):

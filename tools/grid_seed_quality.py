@@ -5,9 +5,10 @@ The same problems (bench.py's generator) are planned twice for the same number o
 once from the stock straight line, once from the grid-search seed (nfopp/grid_search.py).  Prints the collision-free rate
 from BatchPlanner.evaluate for both, and the seeding time split into its three stages by events.  With --clearance the
 grid-search seed is planned once more per margin (metres; the cfg4 cell is 1 m), seeded off the walls by that margin
-(grid_search_init's `clearance`).  Information, not a gate.
+(grid_search_init's `clearance`).  With --any-angle every grid-search row is planned once more from the any-angle seed
+(grid_search_init's `any_angle`).  Information, not a gate.
 
-Usage:  python tools/grid_seed_quality.py [--problems 256] [--steps 500] [--time-batch 4096] [--clearance 1 2]
+Usage:  python tools/grid_seed_quality.py [--problems 256] [--steps 500] [--time-batch 4096] [--clearance 1 2] [--any-angle]
 """
 import argparse
 import json
@@ -65,6 +66,8 @@ def main():
     ap.add_argument("--fit-iters", type=int, default=300)
     ap.add_argument("--clearance", type=float, nargs="*", default=[],
                     help="margins in metres: one more grid-search row per margin")
+    ap.add_argument("--any-angle", action="store_true",
+                    help="one more row per grid-search row: the seed shortened by line of sight")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -78,11 +81,13 @@ def main():
     grid = nfopp.OccupancyGrid.from_checker(truth, 1.0, boundaries=(0.5, 100.0, 0.5, 100.0))
     N, B = 256, args.problems
     result = {"map": env.name, "problems": B, "steps": args.steps, "waypoints": N, "onf_fit_loss": fit_loss}
-    rows = [("straight_line", None, None), ("grid_search", grid, None)]
-    rows += [("grid_search_clearance_%g" % m, grid, m) for m in args.clearance]
-    for name, ini, margin in rows:
+    rows = [("straight_line", None, None, False), ("grid_search", grid, None, False)]
+    rows += [("grid_search_clearance_%g" % m, grid, m, False) for m in args.clearance]
+    if args.any_angle:
+        rows += [(name + "_any_angle", ini, margin, True) for name, ini, margin, _ in rows[1:]]
+    for name, ini, margin, any_angle in rows:
         planner = nfopp.BatchPlanner(onf, B, N, bench.bench_hyper(), velocity_hessian_weight=0.5, device=device, seed=bench.SEED)
-        planner.init(starts[:B], goals[:B], bench.BOUNDS, initializer=ini, seed_clearance=margin)
+        planner.init(starts[:B], goals[:B], bench.BOUNDS, initializer=ini, seed_clearance=margin, seed_any_angle=any_angle)
         collides0, _ = planner.evaluate(truth)
         free0 = 1.0 - float(collides0.float().mean())
         planner.step(n=args.steps)
