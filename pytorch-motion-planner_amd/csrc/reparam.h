@@ -153,7 +153,13 @@ __device__ __forceinline__ void reparam_from_lds(const ReparamLds& L, int N, int
     ok = ok && (q >= 0.0f) && (q <= 1.0f);    // (false for NaN)
   }
   ok = ok && qmin >= 1.862645149230957e-09f;   // 2^-29
-  const bool exact = __syncthreads_and(ok);
+  // Block-wide AND: a wave vote, then the four wave flags through `red` (its lane sums were consumed before the last
+  // barrier).  Not __syncthreads_and: that builtin brings a 256-byte STATIC LDS array, which comes off the 160 KB a
+  // workgroup can hold, so the longest trajectories that pass reparam_lds_bytes' limit could not be launched.
+  const bool wave_ok = __all(ok);
+  if ((tid & 63) == 0) red[tid >> 6] = wave_ok ? 1.0f : 0.0f;
+  __syncthreads();
+  const bool exact = red[0] != 0.0f && red[1] != 0.0f && red[2] != 0.0f && red[3] != 0.0f;
   if (exact) {
     double part = 0.0;
     for (int s2 = lo_s; s2 < hi_s; ++s2) part += (double)cdf[s2];

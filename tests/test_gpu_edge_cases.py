@@ -1,5 +1,6 @@
 """GPU edge cases against the oracle: minimum / ragged / long trajectories, wide preconditioner bands, empty batch,
-2-D fields, both step kernels and the reparametrisation on random (not optimised) states."""
+2-D fields, both step kernels and the reparametrisation on random (not optimised) states (the latter bit for bit on the
+device's own state)."""
 import numpy as np
 import pytest
 import torch
@@ -10,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 gc = pytest.importorskip("gpu_common")
 import nfopp  # noqa: E402
+import reparam_cases as rc  # noqa: E402
 from oracle import nfopp_oracle as orc  # noqa: E402
 
 F32 = np.float32
@@ -64,15 +66,24 @@ def test_se2_step_and_reparam_vs_oracle(B, N, w):
     for ours, ref in (("total", "total"), ("distance", "l_dist"), ("softplus_sum", "l_col"), ("lambda_dot_c", "l_lin"),
                       ("c_squared", "l_c2"), ("boundary", "l_bnd"), ("cm_tanh", "l_cm"), ("direction", "l_dir")):
         assert np.allclose(got[ours], terms[ref], rtol=3e-5, atol=3e-5 * scale), ours
+    torch.cuda.synchronize()
+    # the device's own state after the step
+    dev = [x.cpu().numpy().copy() for x in (eng.traj.view(B, N, 3), eng.start, eng.goal, eng.lam, eng.cm)]
     eng.reparametrize()
     rtr, rlam, rcm = orc.reparametrize(tr, s["start"], s["goal"], lam, cm)
     torch.cuda.synchronize()
-    # random zig-zag paths have arbitrarily short segments: tau = (u - cdf_b) / (cdf_a - cdf_b) amplifies the 1-ulp
-    # difference in the cdf normalisation by 1 / segment-fraction (the well-conditioned cases are pinned by the
-    # golden fixtures in test_gpu_parity.py); positions move by at most |q_a - q_b| * d tau
+    # The kernel's reparametrisation is the oracle's bit for bit (below), so these tolerances measure only how the
+    # difference in the INPUTS -- the device's step is within 6e-6 of the oracle's, above -- is amplified: random zig-zag
+    # paths have arbitrarily short segments and tau = (u - cdf_b) / (cdf_a - cdf_b) magnifies a moved cdf by
+    # 1 / segment-fraction; positions move by at most |q_a - q_b| * d tau
     assert max_abs(eng.traj.cpu().numpy(), rtr) < 1e-3
     assert max_abs(eng.cm.cpu().numpy(), rcm) < 1e-3
     assert max_abs(eng.lam.cpu().numpy(), rlam) < 1e-2
+    # on the state the device itself was in: every bit (tests/test_gpu_reparam_shapes.py pins the branches one by one)
+    etr, elam, ecm = orc.reparametrize(*dev)
+    for got, want, name in ((eng.traj, etr, "traj"), (eng.lam, elam, "lam"), (eng.cm, ecm, "cm")):
+        got = got.cpu().numpy().reshape(want.shape)
+        assert rc.same(got, want), (name, rc.first_difference(got, want))
 
 
 @pytest.mark.parametrize("B,N", [(1, 2), (4, 37), (2, 300)])
@@ -93,8 +104,13 @@ def test_2d_step_and_reparam_vs_oracle(B, N):
     assert gc.scaled_err(eng.adam_m.cpu().numpy(), m) < 2e-5
     got = eng.loss_terms()
     assert np.allclose(got["total"], terms["total"], rtol=3e-5)
+    torch.cuda.synchronize()
+    dev = [x.cpu().numpy().copy() for x in (eng.traj.view(B, N, 2), eng.start, eng.goal)]
     eng.reparametrize()
-    assert max_abs(eng.traj.cpu().numpy(), orc.reparametrize(tr, s["start"], s["goal"])) < 2e-4
+    assert max_abs(eng.traj.cpu().numpy(), orc.reparametrize(tr, s["start"], s["goal"])) < 2e-4   # amplified input difference
+    want = orc.reparametrize(*dev)                           # on the device's own state: every bit
+    got = eng.traj.cpu().numpy().reshape(want.shape)
+    assert rc.same(got, want), rc.first_difference(got, want)
 
 
 def test_empty_batch_and_argument_errors():
