@@ -686,6 +686,87 @@ int nfopp_grid_seed_polylines(const float* points_dev, const int32_t* count_dev,
                               int32_t dim, int32_t angles_with_direction, float* traj_dev, void* workspace_dev,
                               size_t workspace_bytes, void* stream);
 
+/* ---- time parametrisation under motion limits (csrc/time_profile.hip), additive under ABI 6 --------------------------------
+ * Everything above is geometry; these two entries say WHEN the robot is where and how fast it may go, for a whole batch,
+ * without a host round trip.  Float64 throughout, every operation rounded on its own; the two prefix sums are integers, so
+ * a parallel scan and a sequential loop give the same bits (tests/time_profile_ref.py restates the rule in numpy and the
+ * device is compared with it bit for bit).  No atomics; the same bits run after run.
+ *
+ * Polyline p_0 .. p_{N+1} = start, waypoints, goal (read as fp32, widened); segment i = 0..N joins p_i and p_{i+1}, ex, ey its
+ * xy difference.  A = 2 * a_max, Dd = 2 * d_max.  v_start_dev / v_goal_dev [B] fp32 >= 0 (null = rest).
+ * Arc length.  n_i = sqrt(ex * ex + ey * ey), L_i = llrint(n_i * 2^32), S_i = L_0 + .. + L_{i-1} (integers), s_i = S_i * 2^-32.
+ * Gear (dim 3; +1 throughout for dim 2).  The sign of the forward component cos(theta_i) * ex + sin(theta_i) * ey as
+ *   NFOPP_PATH_STAT_REVERSALS forms it; a zero takes the last non-zero sign before it, else the first after it, else +1.
+ * Vertex caps on v^2.  kappa_i = the Menger curvature of NFOPP_PATH_STAT_MAX_CURVATURE at interior vertex i (same candidate
+ *   rule); k_i = min(a_lat / kappa_i, (w_max / kappa_i)^2) where kappa_i exists and is > 0, else +inf; k_0 = k_{N+1} = +inf.
+ *   Vertex i is a STOP when it is a cusp by NFOPP_PATH_STAT_CUSPS' rule with limits->cos_cusp (never when cos_cusp == -1) or
+ *   when the gears of segments i - 1 and i differ.  c_i = 0 at a stop, else min(v_max^2, k_i); c_0 = v_start^2,
+ *   c_{N+1} = v_goal^2.
+ * Speeds, the closed form of a forward and a backward sweep (two scans of exact, order-free minima):
+ *   fwd_i = min_{j <= i}(c_j - A * s_j) + A * s_i,  bwd_i = min_{j >= i}(c_j + Dd * s_j) - Dd * s_i,
+ *   u_i = max(0, min(c_i, fwd_i, bwd_i)),  v_i = sqrt(u_i).
+ * Segment i, time-optimal on a straight piece.  ds = L_i * 2^-32, g = min(v_max^2, max(k_i, k_{i+1})),
+ *   u_p = max(min(g, (((A * d_max) * ds + d_max * u_i) + a_max * u_{i+1}) / (a_max + d_max)), max(u_i, u_{i+1})), v_p = sqrt(u_p),
+ *   t_acc = (v_p - v_i) / a_max, t_dec = (v_p - v_{i+1}) / d_max, l_cruise = max(0, (ds - (u_p - u_i) / A) - (u_p - u_{i+1}) / Dd),
+ *   t_cruise = l_cruise > 0 ? l_cruise / v_p : 0, duration = (t_acc + t_cruise) + t_dec, Q_i = llrint(duration * 2^32),
+ *   T_i = Q_0 + .. + Q_{i-1} (integers), t_i = T_i * 2^-32.  A segment between two stops takes finite time, and a dense
+ *   smooth curve does not bulge above the larger of its two neighbouring caps.
+ *
+ * nfopp_path_time_profile: one workgroup per path, the path's image in LDS; N + 2 <= 3032 (dim 3) / 3275 (dim 2), beyond
+ *   that "path too long".  Writes
+ *     profile_dev [B, N + 2, NFOPP_NUM_TIME_SLOTS] float64: s_i, t_i, v_i, and v_p of the segment that STARTS at vertex i
+ *                 (the last vertex: its own v)
+ *     gear_dev    [B, N + 1] int8 (may be null)
+ *     summary_dev [B, NFOPP_NUM_TIME_SUMMARY] float64: total time t_{N+1}, length s_{N+1}, number of stops, status
+ *   status bits: NFOPP_TIME_START_TOO_FAST u_0 < v_start^2; NFOPP_TIME_GOAL_UNREACHABLE u_{N+1} < v_goal^2;
+ *   NFOPP_TIME_OUT_OF_RANGE (always alone): a non-finite coordinate, a speed not in [0, inf), a segment of 2^20 m or more, a
+ *   total of 2^21 m or more, or a duration not below 2^20 s -- the row's profile and its first three summary slots are NaN
+ *   and its gear is 0.
+ * nfopp_path_time_sample: states_dev [B, count, dim + 1] fp32 <- pose and SIGNED speed (gear * speed) at the instants
+ *   t = t0 + k * dt, k = 0 .. count - 1 (k * dt rounded, then the sum); segment_dev [B, count] int32 (may be null).  One
+ *   thread per instant, the path's t column in LDS.  profile_dev / gear_dev as written above; a null gear_dev means +1.
+ *   Before t_0: start pose, speed 0, segment -1.  At or after t_{N+1}: goal pose, gear_N * v_{N+1}, segment N + 1.  A NaN
+ *   profile row: NaN states, segment -1.  Else i = the largest i <= N with t_i <= t (binary search; ties over zero-duration
+ *   segments go to the largest i), tau = t - t_i, dur = t_{i+1} - t_i, rem = dur - tau, ds = s_{i+1} - s_i,
+ *   t_acc = (v_p - v_i) / a_max, t_dec = (v_p - v_{i+1}) / d_max, ha = 0.5 * a_max, hd = 0.5 * d_max:
+ *     tau < t_acc:       dist = v_i * tau + (ha * tau) * tau,                                speed = v_i + a_max * tau
+ *     else rem < t_dec:  dist = ds - (v_{i+1} * rem + (hd * rem) * rem),                     speed = v_{i+1} + d_max * rem
+ *     else:              dist = (v_i * t_acc + (ha * t_acc) * t_acc) + v_p * (tau - t_acc),  speed = v_p
+ *   dist = min(max(dist, 0), ds), speed = min(speed, v_p), frac = ds > 0 ? dist / ds : 0; x = fp32(x_i + frac * (x_{i+1} - x_i)),
+ *   y alike, theta = fp32(theta_i + frac * dth) with dth the fp32 wrap_angle(theta_{i+1} - theta_i) that
+ *   nfopp_path_interpolate lays its poses on, widened.
+ * Argument errors (both): dim, n_waypoints < 1, batch < 0, null limits, v_max / a_max / d_max not positive and finite,
+ *   a_lat / w_max not positive (+inf allowed, NaN not), cos_cusp outside [-1, 1]; for the sampler also dt not positive and
+ *   finite, t0 not finite, count < 0.  batch == 0 returns 0 with null pointers. */
+typedef struct nfopp_motion_limits {
+  double v_max;     /* m/s */
+  double a_max;     /* acceleration, m/s^2 */
+  double d_max;     /* deceleration, m/s^2 */
+  double a_lat;     /* lateral acceleration v^2 * kappa, +inf = none */
+  double w_max;     /* turn rate v * kappa, +inf = none */
+  double cos_cusp;  /* cusp threshold of nfopp_path_stats; -1 = no cusp stops */
+} nfopp_motion_limits;
+#define NFOPP_NUM_TIME_SLOTS 4
+#define NFOPP_TIME_SLOT_S 0
+#define NFOPP_TIME_SLOT_T 1
+#define NFOPP_TIME_SLOT_V 2
+#define NFOPP_TIME_SLOT_V_PEAK 3
+#define NFOPP_NUM_TIME_SUMMARY 4
+#define NFOPP_TIME_SUMMARY_TIME 0
+#define NFOPP_TIME_SUMMARY_LENGTH 1
+#define NFOPP_TIME_SUMMARY_STOPS 2
+#define NFOPP_TIME_SUMMARY_STATUS 3
+#define NFOPP_TIME_START_TOO_FAST 1
+#define NFOPP_TIME_GOAL_UNREACHABLE 2
+#define NFOPP_TIME_OUT_OF_RANGE 4
+int nfopp_path_time_profile(const float* traj_dev, const float* start_dev, const float* goal_dev, int64_t batch,
+                            int32_t n_waypoints, int32_t dim, const nfopp_motion_limits* limits, const float* v_start_dev,
+                            const float* v_goal_dev, double* profile_dev, int8_t* gear_dev, double* summary_dev, void* stream);
+int nfopp_path_time_sample(const float* traj_dev, const float* start_dev, const float* goal_dev, int64_t batch,
+                           int32_t n_waypoints, int32_t dim, const nfopp_motion_limits* limits, const double* profile_dev,
+                           const int8_t* gear_dev, double t0, double dt, int32_t count, float* states_dev,
+                           int32_t* segment_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

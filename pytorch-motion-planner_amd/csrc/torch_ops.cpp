@@ -331,6 +331,51 @@ Tensor onf_train_step(Tensor params, Tensor m, Tensor v, const Tensor& samples, 
   return grad;
 }
 
+// the 6 doubles of nfopp_motion_limits in declaration order
+nfopp_motion_limits make_limits(at::ArrayRef<double> l) {
+  TORCH_CHECK(l.size() == 6, "nfopp: limits must hold the 6 doubles of nfopp_motion_limits (include/nfopp_hip.h), got ", l.size());
+  static_assert(sizeof(nfopp_motion_limits) == 6 * sizeof(double), "nfopp_motion_limits layout");
+  return nfopp_motion_limits{l[0], l[1], l[2], l[3], l[4], l[5]};
+}
+
+// velocity profile of a batch of paths under motion limits (nfopp_path_time_profile): (profile [B, N+2, 4] float64,
+// gear [B, N+1] int8, summary [B, 4] float64).  v_start / v_goal: [B] fp32 or None (rest).
+std::tuple<Tensor, Tensor, Tensor> path_time_profile(const Tensor& traj, const Tensor& start, const Tensor& goal,
+                                                     at::ArrayRef<double> limits, const OptTensor& v_start,
+                                                     const OptTensor& v_goal) {
+  const Batch b = batch_endpoints(traj, start, goal);
+  const nfopp_motion_limits lim = make_limits(limits);
+  if (v_start.has_value()) need(traj, *v_start, "v_start", {b.B});
+  if (v_goal.has_value()) need(traj, *v_goal, "v_goal", {b.B});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  const auto f64 = traj.options().dtype(at::kDouble);
+  Tensor profile = at::empty({b.B, b.N + 2, NFOPP_NUM_TIME_SLOTS}, f64), summary = at::empty({b.B, NFOPP_NUM_TIME_SUMMARY}, f64);
+  Tensor gear = at::empty({b.B, b.N + 1}, traj.options().dtype(at::kChar));
+  check_status(nfopp_path_time_profile(b.traj, b.start, b.goal, b.B, (int32_t)b.N, (int32_t)b.D, &lim, opt_ptr<float>(v_start),
+                                       opt_ptr<float>(v_goal), profile.data_ptr<double>(), gear.data_ptr<int8_t>(),
+                                       summary.data_ptr<double>(), stream_of(traj)));
+  return std::make_tuple(profile, gear, summary);
+}
+
+// pose and signed speed at t0 + k * dt (nfopp_path_time_sample): (states [B, count, D+1] fp32, segment [B, count] int32).
+// gear: int8 [B, N+1] or None (+1).
+std::tuple<Tensor, Tensor> path_time_sample(const Tensor& traj, const Tensor& start, const Tensor& goal,
+                                            at::ArrayRef<double> limits, const Tensor& profile, const OptTensor& gear, double t0,
+                                            double dt, int64_t count) {
+  const Batch b = batch_endpoints(traj, start, goal);
+  const nfopp_motion_limits lim = make_limits(limits);
+  need(traj, profile, "profile", {b.B, b.N + 2, NFOPP_NUM_TIME_SLOTS}, at::kDouble);
+  if (gear.has_value()) need(traj, *gear, "gear", {b.B, b.N + 1}, at::kChar);
+  TORCH_CHECK(count >= 0 && count <= 0x7fffffffLL, "nfopp: count must lie in [0, 2^31)");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  Tensor states = at::empty({b.B, count, b.D + 1}, traj.options());
+  Tensor segment = at::empty({b.B, count}, traj.options().dtype(at::kInt));
+  check_status(nfopp_path_time_sample(b.traj, b.start, b.goal, b.B, (int32_t)b.N, (int32_t)b.D, &lim, profile.data_ptr<double>(),
+                                      opt_ptr<int8_t>(gear), t0, dt, (int32_t)count, states.numel() ? states.data_ptr<float>() : nullptr,
+                                      segment.numel() ? segment.data_ptr<int32_t>() : nullptr, stream_of(traj)));
+  return std::make_tuple(states, segment);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nfopp, lib) {
@@ -360,6 +405,10 @@ TORCH_LIBRARY(nfopp, lib) {
   lib.def("grid_search_init(Tensor(a!) traj, Tensor start, Tensor goal, Tensor occupancy, Tensor start_cells, Tensor goal_cells, "
           "Tensor unique_goal_cells, Tensor field_index, float origin_x, float origin_y, float resolution, "
           "bool angles_with_direction) -> Tensor");
+  lib.def("path_time_profile(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor? v_start, Tensor? v_goal) -> "
+          "(Tensor, Tensor, Tensor)");
+  lib.def("path_time_sample(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor profile, Tensor? gear, float t0, "
+          "float dt, int count) -> (Tensor, Tensor)");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -375,4 +424,6 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("adam_step", &adam_step);
   lib.impl("onf_train_step", &onf_train_step);
   lib.impl("grid_search_init", &grid_search_init);
+  lib.impl("path_time_profile", &path_time_profile);
+  lib.impl("path_time_sample", &path_time_sample);
 }

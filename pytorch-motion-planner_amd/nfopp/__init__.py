@@ -15,6 +15,9 @@ from .learning import BatchSampler, DeviceCircleChecker, DeviceGridChecker, Devi
 from .onf_model import ONF
 from .path_tools import PathPostprocessor, init_trajectories
 from .planner import ConstrainedNERFOptPlanner, ContinuousPlanner, NERFOptPlanner
+from .time_profile import (TIME_GOAL_UNREACHABLE, TIME_OUT_OF_RANGE, TIME_SLOT_S, TIME_SLOT_T, TIME_SLOT_V, TIME_SLOT_V_PEAK,
+                           TIME_START_TOO_FAST, TIME_SUMMARY_LENGTH, TIME_SUMMARY_STATUS, TIME_SUMMARY_STOPS,
+                           TIME_SUMMARY_TIME, MotionLimits, TimedPaths, time_parametrize)
 
 # slots of BatchPlanner.path_stats' [B, 8] result (NFOPP_PATH_STAT_* of include/nfopp_hip.h)
 (PATH_STAT_LENGTH, PATH_STAT_MAX_CURVATURE, PATH_STAT_CURVATURE_AT, PATH_STAT_CUSPS, PATH_STAT_REVERSALS,
@@ -29,4 +32,7 @@ __all__ = [
     "distance_fields", "seed_trajectories", "seed_polylines", "shorten_paths", "margin_cells2", "NUM_PATH_STATS", "PATH_STAT_NAMES", "PATH_STAT_LENGTH",
     "PATH_STAT_MAX_CURVATURE", "PATH_STAT_CURVATURE_AT", "PATH_STAT_CUSPS", "PATH_STAT_REVERSALS",
     "PATH_STAT_MIN_CLEARANCE", "PATH_STAT_CLEARANCE_AT", "PATH_STAT_MEAN_CLEARANCE",
+    "MotionLimits", "TimedPaths", "time_parametrize", "TIME_SLOT_S", "TIME_SLOT_T", "TIME_SLOT_V", "TIME_SLOT_V_PEAK",
+    "TIME_SUMMARY_TIME", "TIME_SUMMARY_LENGTH", "TIME_SUMMARY_STOPS", "TIME_SUMMARY_STATUS", "TIME_START_TOO_FAST",
+    "TIME_GOAL_UNREACHABLE", "TIME_OUT_OF_RANGE",
 ]

@@ -15,6 +15,8 @@ NUM_TERMS = 8
 NUM_PATH_STATS = 8   # NFOPP_NUM_PATH_STATS; slot names: NFOPP_PATH_STAT_* of include/nfopp_hip.h
 PATH_STAT_NAMES = ("length", "max_curvature", "curvature_at", "cusps", "reversals", "min_clearance", "clearance_at",
                    "mean_clearance")
+NUM_TIME_SLOTS = 4      # NFOPP_NUM_TIME_SLOTS: s, t, v, peak v of the segment that starts at the vertex
+NUM_TIME_SUMMARY = 4    # NFOPP_NUM_TIME_SUMMARY: total time, length, stops, status
 TERM_NAMES = ("total", "distance", "softplus_sum", "lambda_dot_c", "c_squared", "boundary", "cm_tanh", "direction")
 
 
@@ -35,6 +37,12 @@ class TrajHyperC(ctypes.Structure):
                 ("bounds", ctypes.c_float * 4),
                 ("adam_beta2", ctypes.c_float), ("adam_omb1", ctypes.c_float), ("adam_omb2", ctypes.c_float),
                 ("adam_eps", ctypes.c_float), ("adam_step_size", ctypes.c_float), ("adam_bc2_sqrt", ctypes.c_float)]
+
+
+class MotionLimitsC(ctypes.Structure):
+    """nfopp_motion_limits (include/nfopp_hip.h): 6 doubles."""
+    _fields_ = [("v_max", ctypes.c_double), ("a_max", ctypes.c_double), ("d_max", ctypes.c_double),
+                ("a_lat", ctypes.c_double), ("w_max", ctypes.c_double), ("cos_cusp", ctypes.c_double)]
 
 
 _P = ctypes.c_void_p
@@ -161,6 +169,11 @@ _SIGNATURES = {
                                                 ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.c_int32,
                                                 ctypes.c_int32, _P, _P, _P, _P]),
     "nfopp_path_refined_labels": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P]),
+    "nfopp_path_time_profile": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.POINTER(MotionLimitsC), _P, _P, _P, _P, _P, _P]),
+    "nfopp_path_time_sample": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(MotionLimitsC), _P, _P, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int32, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

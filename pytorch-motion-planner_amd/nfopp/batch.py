@@ -435,11 +435,27 @@ class BatchPlanner(object):
                                      L.ptr(eng.active, torch.uint8), L.stream_ptr()))
         return stats
 
+    def _best_traj(self):
+        """[B, N, D] device tensor: the waypoints `best_paths` returns."""
+        eng = self.engine
+        tr = eng.traj.view(eng.B, eng.N, eng.D)
+        if not hasattr(self, "best_length"):
+            return tr
+        return torch.where(torch.isfinite(self.best_length)[:, None, None], self.best_traj, tr)
+
     def best_paths(self):
         """[B, N+2, D]: the best collision-free path found so far, the current path where none was found yet."""
         eng = self.engine
         if not hasattr(self, "best_length"):
             return self.get_paths()
-        found = torch.isfinite(self.best_length)[:, None, None]
-        tr = torch.where(found, self.best_traj, eng.traj.view(eng.B, eng.N, eng.D))
-        return torch.cat([eng.start[:, None], tr, eng.goal[:, None]], dim=1).cpu().numpy()
+        return torch.cat([eng.start[:, None], self._best_traj(), eng.goal[:, None]], dim=1).cpu().numpy()
+
+    def timed_paths(self, limits, v_start=None, v_goal=None, best=False):
+        """The velocity profile of every path under `limits` (nfopp.MotionLimits) as an nfopp.TimedPaths: `.profile`,
+        `.gear`, `.summary` and `.sample(dt, count)` -- of the current paths, or with `best` of what `best_paths()` returns.
+        `v_start` / `v_goal`: None (rest), a number or [B]; in a replanning tick `v_start` is the robot's current speed.
+        With device-tensor (or no) speeds nothing here synchronises."""
+        from .time_profile import time_parametrize
+        eng = self.engine
+        traj = self._best_traj() if best else eng.traj.view(eng.B, eng.N, eng.D)
+        return time_parametrize(traj, eng.start, eng.goal, limits, v_start, v_goal)

@@ -159,6 +159,33 @@ class NERFOptPlanner(ContinuousPlanner):
     def get_path(self):
         return self.full_trajectory().detach().cpu().numpy()
 
+    def get_timed_path(self, limits, dt, v_start=0.0):
+        """The path as a timed trajectory under `limits` (nfopp.MotionLimits), from `v_start` to rest at the goal: numpy rows
+        (t, pose, signed speed) at every k * dt below the total time, then one row at the total time (the goal pose); the
+        stamps increase strictly.  Raises ValueError when the path cannot be timed (a coordinate or speed that is not finite
+        or out of range) and when `v_start` is too fast for the path (status bit TIME_START_TOO_FAST: a stop or a bend lies
+        closer than the robot can brake for, so the profile would begin below the robot's speed)."""
+        from .time_profile import TIME_OUT_OF_RANGE, TIME_START_TOO_FAST, TIME_SUMMARY_STATUS, TIME_SUMMARY_TIME, time_parametrize
+        eng = self._engine
+        dt = float(dt)
+        if not (0.0 < dt < np.inf):
+            raise ValueError("dt must be positive and finite")
+        timed = time_parametrize(eng.traj.view(eng.B, eng.N, eng.D)[:1], eng.start[:1], eng.goal[:1], limits, v_start=v_start)
+        summary = timed.summary[0].cpu().numpy()
+        status, total = int(summary[TIME_SUMMARY_STATUS]), float(summary[TIME_SUMMARY_TIME])
+        if status & TIME_OUT_OF_RANGE:
+            raise ValueError("the path cannot be timed: a coordinate or speed is not finite, or out of range")
+        if status & TIME_START_TOO_FAST:
+            raise ValueError("v_start = %g m/s is too fast for this path: the robot cannot slow down in time" % float(v_start))
+        count = int(np.ceil(total / dt))              # the stamps k * dt < total are k = 0 .. count - 1; the quotient is rounded,
+        while count > 0 and (count - 1) * dt >= total:   # so settle the last one on the products themselves
+            count -= 1
+        while count * dt < total:
+            count += 1
+        stamps = np.append(np.arange(count, dtype=np.float64) * dt, total)
+        states = np.concatenate([timed.sample(dt, count)[0].cpu().numpy(), timed.sample(1.0, 1, t0=total)[0].cpu().numpy()])
+        return np.concatenate([stamps[:, None], states.astype(np.float64)], axis=1)
+
     # ---- ONF fitting (nerf:76-141) ---------------------------------------------------------------------------------
     def _optimize_collision_model(self, positions=None):
         if positions is None:

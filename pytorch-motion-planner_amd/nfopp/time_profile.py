@@ -1,0 +1,113 @@
+"""Time parametrisation of planned paths under motion limits (csrc/time_profile.hip): the velocity profile and the timed
+trajectory of a whole batch, on the device.  The rule is stated in include/nfopp_hip.h; nothing here synchronises when the
+inputs are device tensors."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# slots of TimedPaths.profile [B, N + 2, 4] (NFOPP_TIME_SLOT_*) and TimedPaths.summary [B, 4] (NFOPP_TIME_SUMMARY_*)
+TIME_SLOT_S, TIME_SLOT_T, TIME_SLOT_V, TIME_SLOT_V_PEAK = range(_lib.NUM_TIME_SLOTS)
+TIME_SUMMARY_TIME, TIME_SUMMARY_LENGTH, TIME_SUMMARY_STOPS, TIME_SUMMARY_STATUS = range(_lib.NUM_TIME_SUMMARY)
+# bits of the status slot (NFOPP_TIME_*)
+TIME_START_TOO_FAST, TIME_GOAL_UNREACHABLE, TIME_OUT_OF_RANGE = 1, 2, 4
+
+
+class MotionLimits(collections.namedtuple("MotionLimits", "v_max a_max d_max a_lat w_max cusp_angle")):
+    """What the robot may do along a path: top speed [m/s], acceleration and deceleration [m/s^2], lateral acceleration
+    v^2 * kappa and turn rate v * kappa (inf = no such limit), and the cusp rule of `BatchPlanner.path_stats`: the robot
+    stops at a vertex where the path folds back to within `cusp_angle` of the way it came (None = no cusp stops)."""
+    __slots__ = ()
+
+    def __new__(cls, v_max, a_max, d_max=None, a_lat=float("inf"), w_max=float("inf"), cusp_angle=np.pi / 3):
+        return super().__new__(cls, float(v_max), float(a_max), float(a_max if d_max is None else d_max), float(a_lat),
+                               float(w_max), None if cusp_angle is None else float(cusp_angle))
+
+    @property
+    def cos_cusp(self):
+        return -1.0 if self.cusp_angle is None else float(np.cos(np.pi - self.cusp_angle))
+
+    def to_c(self):
+        return _lib.MotionLimitsC(self.v_max, self.a_max, self.d_max, self.a_lat, self.w_max, self.cos_cusp)
+
+
+def _speeds(v, batch, device):
+    """None, a number, an array or a tensor -> None or a [B] fp32 device tensor (a tensor is not copied to the host)."""
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        v = v.to(device=device, dtype=torch.float32).reshape(-1)
+    else:
+        v = torch.from_numpy(np.array(v, np.float32).reshape(-1)).to(device)
+    if v.numel() not in (1, batch):
+        raise ValueError("a start / goal speed must be a number or [B] = [%d], got %d values" % (batch, v.numel()))
+    return v.expand(batch).contiguous()
+
+
+def _check_paths(traj, start, goal):
+    """traj [B, N, D] with N >= 1 and D = 2 or 3, start / goal [B, D]: what the kernels index by."""
+    if not all(isinstance(x, torch.Tensor) for x in (traj, start, goal)):
+        raise TypeError("traj, start and goal must be tensors")
+    if traj.dim() != 3 or traj.shape[1] < 1 or traj.shape[2] not in (2, 3):
+        raise ValueError("traj must be [B, N, D] with N >= 1 and D = 2 or 3, got %s" % (tuple(traj.shape),))
+    b, _, d = traj.shape
+    if tuple(start.shape) != (b, d) or tuple(goal.shape) != (b, d):
+        raise ValueError("start and goal must be [B, D] = [%d, %d], got %s and %s" % (b, d, tuple(start.shape), tuple(goal.shape)))
+
+
+class TimedPaths(object):
+    """The velocity profile of a batch of paths.  Device tensors: `profile` [B, N + 2, 4] float64 (TIME_SLOT_*: arc length
+    s, time t, speed v at every vertex, and the peak speed of the segment that starts there), `gear` [B, N + 1] int8
+    (+1 forward, -1 reverse; None = forward throughout), `summary` [B, 4] float64 (TIME_SUMMARY_*: total time, length,
+    stops, status bits).  `traj`, `start`, `goal` are the poses the profile was computed for; `time_parametrize` stores its
+    own copy of them, so the object stays valid when the planner moves on."""
+
+    def __init__(self, traj, start, goal, limits, profile, gear, summary):
+        _check_paths(traj, start, goal)
+        b, n, _ = traj.shape
+        if tuple(profile.shape) != (b, n + 2, _lib.NUM_TIME_SLOTS) or tuple(summary.shape) != (b, _lib.NUM_TIME_SUMMARY):
+            raise ValueError("profile must be [B, N + 2, 4] and summary [B, 4] for traj %s, got %s and %s"
+                             % (tuple(traj.shape), tuple(profile.shape), tuple(summary.shape)))
+        if gear is not None and tuple(gear.shape) != (b, n + 1):
+            raise ValueError("gear must be [B, N + 1] = [%d, %d], got %s" % (b, n + 1, tuple(gear.shape)))
+        self.traj, self.start, self.goal, self.limits = traj, start, goal, limits
+        self.profile, self.gear, self.summary = profile, gear, summary
+
+    def sample(self, dt, count, t0=0.0, want_segment=False):
+        """[B, count, D + 1] fp32 device tensor: pose and signed speed at t0 + k * dt; with `want_segment` also the int32
+        [B, count] segment each instant falls in (-1 before the start, N + 1 from the goal on)."""
+        b, n, d = self.traj.shape
+        count = int(count)
+        states = torch.empty(b, max(count, 0), d + 1, dtype=torch.float32, device=self.traj.device)
+        segment = torch.empty(b, max(count, 0), dtype=torch.int32, device=self.traj.device) if want_segment else None
+        lim = self.limits.to_c()
+        _lib.check(_lib.load().nfopp_path_time_sample(
+            _lib.ptr(self.traj), _lib.ptr(self.start), _lib.ptr(self.goal), b, n, d, lim, _lib.ptr(self.profile, torch.float64),
+            _lib.ptr(self.gear, torch.int8), float(t0), float(dt), count, _lib.ptr(states), _lib.ptr(segment, torch.int32),
+            _lib.stream_ptr()))
+        return (states, segment) if want_segment else states
+
+
+def time_parametrize(traj, start, goal, limits, v_start=None, v_goal=None):
+    """traj [B, N, D], start / goal [B, D]: fp32 HIP tensors (D = 2 or 3).  `v_start` / `v_goal`: the speed the robot has
+    at the start and shall have at the goal -- None (rest), a number, or [B] -> `TimedPaths`.  The poses are copied on the
+    device (no synchronisation): the result does not follow later changes of `traj`, `start` or `goal`."""
+    _check_paths(traj, start, goal)
+    if not traj.is_cuda:
+        raise _lib.NfoppError("time_parametrize needs HIP tensors (there is no CPU path)")
+    if not isinstance(limits, MotionLimits):
+        raise TypeError("limits must be a MotionLimits")
+    b, n, d = traj.shape
+    v_start, v_goal = _speeds(v_start, b, traj.device), _speeds(v_goal, b, traj.device)
+    traj, start, goal = (x.clone(memory_format=torch.contiguous_format) for x in (traj, start, goal))
+    f64 = dict(dtype=torch.float64, device=traj.device)
+    profile = torch.empty(b, n + 2, _lib.NUM_TIME_SLOTS, **f64)
+    gear = torch.empty(b, n + 1, dtype=torch.int8, device=traj.device)
+    summary = torch.empty(b, _lib.NUM_TIME_SUMMARY, **f64)
+    lim = limits.to_c()
+    _lib.check(_lib.load().nfopp_path_time_profile(
+        _lib.ptr(traj), _lib.ptr(start), _lib.ptr(goal), b, n, d, lim, _lib.ptr(v_start), _lib.ptr(v_goal),
+        _lib.ptr(profile, torch.float64), _lib.ptr(gear, torch.int8), _lib.ptr(summary, torch.float64), _lib.stream_ptr()))
+    return TimedPaths(traj, start, goal, limits, profile, gear, summary)

@@ -11,7 +11,7 @@ from . import _lib
 
 TORCH_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libnfopp_torch.so")
 OPS = ("onf_fwd_bwd_input", "onf_logits", "traj_step", "traj_steps", "reparametrize", "update_endpoints", "onf_train_grad", "adam_step", "onf_train_step",
-       "grid_search_init")
+       "grid_search_init", "path_time_profile", "path_time_sample")
 _loaded = False
 
 
@@ -25,6 +25,13 @@ def load():
         torch.ops.load_library(TORCH_LIB_PATH)
         _loaded = True
     return torch.ops.nfopp
+
+
+def limits_list(limits):
+    """The 6 doubles of an nfopp.MotionLimits in nfopp_motion_limits order (the `limits` argument of
+    torch.ops.nfopp.path_time_profile / path_time_sample)."""
+    c = limits.to_c()
+    return [float(getattr(c, name)) for name, _ in c._fields_]
 
 
 def hyper_list(hyper_c):

@@ -1,0 +1,312 @@
+"""CPU: the rule of nfopp_path_time_profile / nfopp_path_time_sample as restated in tests/time_profile_ref.py -- hand
+cases, properties on random wiggly paths (tests/time_profile_cases.py), coverage of the case set -- and the interface: header,
+binding and library agree, every argument check answers without a GPU, the Python names exist."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+import nfopp
+from nfopp import _lib, torch_ops
+
+import time_profile_cases as tc
+import time_profile_ref as tr
+
+F32 = np.float32
+REST = tr.Limits(v_max=2.0, a_max=1.0, d_max=1.0)        # no lateral / turn-rate limit, no cusp stops
+TICK = 2.0 ** -32
+
+
+def test_straight_ten_metres_in_ten_segments_takes_exactly_seven_seconds():
+    r = tr.profile(tc.straight(np.arange(11.0)), REST)
+    assert r["summary"][tr.SUM_TIME] == 7.0 and r["summary"][tr.SUM_LENGTH] == 10.0
+    assert r["summary"][tr.SUM_STOPS] == 0 and r["summary"][tr.SUM_STATUS] == 0
+    want = np.array([0.0, np.sqrt(2.0)] + [2.0] * 7 + [np.sqrt(2.0), 0.0])
+    assert np.array_equal(r["profile"][:, tr.SLOT_V], want)
+    assert np.array_equal(r["profile"][:, tr.SLOT_S], np.arange(11.0))
+    assert np.array_equal(r["gear"], np.ones(10, np.int8))
+
+
+def test_one_interior_vertex_peaks_inside_the_segments():
+    r = tr.profile(tc.straight([0.0, 5.0, 10.0]), REST)
+    assert r["summary"][tr.SUM_TIME] == 7.0
+    assert np.array_equal(r["profile"][:, tr.SLOT_V], [0.0, 2.0, 0.0])
+    assert np.array_equal(r["profile"][:, tr.SLOT_VP], [2.0, 2.0, 0.0]) and r["cruise"].all()
+    # without the interior cap the same 10 m in ONE segment: the peak lies inside it
+    one = tr.profile(tc.straight([0.0, 10.0, 10.0]), REST)
+    assert one["summary"][tr.SUM_TIME] == 7.0 and one["profile"][0, tr.SLOT_VP] == 2.0 and one["profile"][1, tr.SLOT_V] == 0.0
+
+
+def test_two_metres_take_two_root_two_within_the_quantisation_bound():
+    r = tr.profile(tc.straight([0.0, 1.0, 2.0]), REST)
+    assert abs(r["summary"][tr.SUM_TIME] - 2.0 * np.sqrt(2.0)) <= 2 * 2.0 ** -33
+    assert r["profile"][1, tr.SLOT_V] == np.sqrt(2.0) and not r["cruise"].any()
+
+
+def test_a_fold_is_a_stop_and_takes_finite_time():
+    p = np.array([[0, 0], [1, 0], [2, 0], [1, 0.001], [0, 0.001]], F32)
+    r = tr.profile(p, tc.LIMITS)
+    assert r["stop_cusp"].tolist() == [False, True, False] and r["summary"][tr.SUM_STOPS] == 1
+    assert r["profile"][2, tr.SLOT_V] == 0.0 and np.isfinite(r["summary"][tr.SUM_TIME]) and r["summary"][tr.SUM_TIME] > 0
+    # cos_cusp = -1 switches cusp stops off, also for an exact fold
+    back = tr.profile(np.array([[0, 0], [1, 0], [0, 0]], F32), REST)
+    assert back["summary"][tr.SUM_STOPS] == 0
+
+
+def test_a_gear_change_without_a_cusp_is_a_stop():
+    p = tc.straight([0.0, 1.0, 2.0, 3.0], dim=3)
+    p[2:, 2] = np.pi                                      # the robot goes on along +x, now backwards
+    r = tr.profile(p, tc.LIMITS)
+    assert r["gear"].tolist() == [1, 1, -1]
+    assert r["stop_gear"].tolist() == [False, True] and not r["stop_cusp"].any()
+    assert r["profile"][2, tr.SLOT_V] == 0.0 and r["summary"][tr.SUM_STOPS] == 1
+
+
+def test_zero_signs_take_the_sign_before_else_after_else_forward():
+    p = tc.straight([0.0, 0.0, 1.0, 1.0, 2.0], dim=3)
+    p[:, 2] = np.pi
+    assert tr.gears(p).tolist() == [-1, -1, -1, -1]       # leading zero: the first sign after it
+    assert tr.gears(tc.straight([0.0, 0.0, 0.0], dim=3)).tolist() == [1, 1]
+    assert tr.gears(tc.straight([0.0, 1.0, 0.0])).tolist() == [1, 1]    # dim 2
+
+
+def test_coincident_waypoints_give_a_zero_duration_segment_and_no_nan():
+    r = tr.profile(tc.straight([0.0, 1.0, 1.0, 2.0]), REST)
+    assert r["duration"][1] == 0.0 and np.isfinite(r["profile"]).all()
+    assert r["profile"][1, tr.SLOT_T] == r["profile"][2, tr.SLOT_T]
+    states, seg, _ = tr.sample(tc.straight([0.0, 1.0, 1.0, 2.0]), r["profile"], r["gear"], REST, r["profile"][1, tr.SLOT_T], 1.0, 1)
+    assert seg[0] == 2 and np.isfinite(states).all()      # the tie goes to the largest i
+
+
+def test_status_bits_and_out_of_range_rows():
+    for dim in (2, 3):
+        for path, vs, vg, want in tc.status_cases(dim):
+            r = tr.profile(path, REST, vs, vg)
+            assert r["summary"][tr.SUM_STATUS] == want, (dim, vs, vg, want)
+            if want == 4:
+                assert np.isnan(r["profile"]).all() and np.isnan(r["summary"][:3]).all() and not r["gear"].any()
+            else:
+                assert np.isfinite(r["profile"]).all()
+    # a duration of 2^20 s or more: a bend taken at a lateral limit that allows 3e-7 m/s
+    slow = tr.profile(np.array([[0, 0], [1, 0], [2, 1], [3, 1]], F32), REST._replace(a_lat=1e-13))
+    assert slow["summary"][tr.SUM_STATUS] == 4
+
+
+def _cases():
+    for n in tc.PROPERTY_N:
+        for dim in (2, 3):
+            paths, vs, vg = tc.batch(100 * n + dim, 3, n, dim)
+            for b in range(len(paths)):
+                yield n, dim, paths[b], float(vs[b]), float(vg[b])
+
+
+@pytest.fixture(scope="module")
+def solved():
+    return [(n, dim, p, vs, vg, tr.profile(p, tc.LIMITS, vs, vg)) for n, dim, p, vs, vg in _cases()]
+
+
+def test_properties_on_wiggly_paths(solved):
+    lim = tc.LIMITS
+    worst = 0.0
+    for n, dim, p, vs, vg, r in solved:
+        assert r["summary"][tr.SUM_STATUS] in (0, 1, 2, 3), (n, dim)
+        if dim == 3:
+            assert tc.forward_margin(p) >= 0.5
+        c, u, ds, s = r["c"], r["u"], r["ds"], r["s"]
+        assert (u <= c).all()                                                        # caps, exactly
+        scale = 2.0 * max(lim.a_max, lim.d_max) * s[-1] + c[np.isfinite(c)].max()
+        bound = (n + 4) * 2.0 ** -53 * scale
+        err = np.abs(u - tr.sweeps(c, ds, lim.a_max, lim.d_max)).max()               # closed form against the two sweeps
+        worst = max(worst, err / (2.0 ** -53 * scale))
+        assert err <= bound, (n, dim, err, bound)
+        up, down = u[:-2] + (2 * lim.a_max) * ds[:-1], u[2:] + (2 * lim.d_max) * ds[1:]
+        slack = np.minimum(np.minimum(c[1:-1] - u[1:-1], np.abs(up - u[1:-1])), np.abs(down - u[1:-1]))
+        assert (slack <= bound).all(), (n, dim, slack.max())                         # tightness
+        assert (r["duration"] >= 0).all() and np.isfinite(r["duration"]).all()
+        assert np.isfinite(r["profile"]).all()
+    print("closed form vs sweeps: worst %.2f units of 2^-53 * scale" % worst)
+
+
+def test_sampled_motion_on_wiggly_paths(solved):
+    lim = tc.LIMITS
+    for n, dim, p, vs, vg, r in solved:
+        prof, gear = r["profile"], r["gear"]
+        t = prof[:, tr.SLOT_T]
+        # one tick before t_{i+1} the robot is within v_max * 2^-31 of p_{i+1} (along the segment)
+        for i in np.flatnonzero(t[1:] > t[:-1]):
+            _, seg, dist = tr.sample(p, prof, gear, lim, t[i + 1] - TICK, 1.0, 1)
+            assert seg[0] == i and r["ds"][i] - dist[0] <= lim.v_max * 2.0 ** -31, (n, dim, i)
+        # speeds and their finite differences on a 10 ms grid
+        dt = 0.01
+        count = int(t[-1] / dt) + 3
+        states, seg, _ = tr.sample(p, prof, gear, lim, 0.0, dt, count)
+        v = np.abs(states[:, dim].astype(np.float64))
+        assert (v <= F32(lim.v_max)).all() and seg[0] == np.flatnonzero(t[:n + 1] == 0.0).max() and seg[-1] == n + 1
+        # a sample errs by the fp32 rounding of the speed and by the 2^-33 s a segment's duration is rounded by
+        slack = 2.0 * (2.0 ** -24 * lim.v_max + max(lim.a_max, lim.d_max) * 2.0 ** -32) / dt
+        inside = seg[1:] <= n                       # the last step may end at the goal, after the motion
+        dv = np.diff(v)[inside[: len(v) - 1]] / dt
+        assert dv.max(initial=0.0) <= lim.a_max + slack and dv.min(initial=0.0) >= -lim.d_max - slack, (n, dim, dv.max(), dv.min())
+        if dim == 3:
+            assert np.array_equal(np.sign(states[:, 3])[(seg >= 0) & (seg <= n) & (v > 0)], gear[seg[(seg >= 0) & (seg <= n) & (v > 0)]])
+
+
+def test_case_set_covers_every_branch(solved):
+    limiters, cusp, gear_stop, cruise, no_cruise = set(), False, False, False, False
+    for n, dim, p, vs, vg, r in solved:
+        limiters |= set(r["limiter"][1:-1].tolist())
+        cusp |= bool((r["stop_cusp"] & ~r["stop_gear"]).any())
+        gear_stop |= bool((r["stop_gear"] & ~r["stop_cusp"]).any())
+        cruise |= bool(r["cruise"].any())
+        no_cruise |= bool((~r["cruise"] & (r["ds"] > 0)).any())
+    assert limiters == {tr.LIMIT_CAP, tr.LIMIT_ACCEL, tr.LIMIT_DECEL}
+    assert cusp and gear_stop and cruise and no_cruise
+    seen = {int(tr.profile(p, REST, vs, vg)["summary"][tr.SUM_STATUS]) for p, vs, vg, _ in tc.status_cases(3)}
+    assert {1, 2, 4} <= seen
+
+
+def test_sampling_before_after_and_null_gear():
+    p = tc.straight([0.0, 1.0, 2.0], dim=3)
+    p[:, 2] = [3.0, -3.0, -3.0]                           # theta runs the short way through pi
+    r = tr.profile(p, REST)
+    total = r["summary"][tr.SUM_TIME]
+    states, seg, _ = tr.sample(p, r["profile"], None, REST, -0.5, total / 2 + 0.5, 4)
+    assert seg.tolist() == [-1, 1, 2, 2]                # N = 1: segment N + 1 = 2 from the goal on
+    assert np.array_equal(states[0], [0, 0, 3, 0]) and np.array_equal(states[2], [2, 0, -3, 0])
+    assert states[1, 0] == 1.0 and abs(states[1, 3] - np.sqrt(2.0)) < 1e-6
+    half, _, _ = tr.sample(p, r["profile"], None, REST, r["profile"][1, tr.SLOT_T] * 0.5, 1.0, 1)
+    assert 3.0 < half[0, 2] < 3.2                          # not through zero
+    nan_states, nan_seg, _ = tr.sample(p, np.full((3, 4), np.nan), None, REST, 0.0, 1.0, 2)
+    assert np.isnan(nan_states).all() and nan_seg.tolist() == [-1, -1]
+
+
+# ---- interface -------------------------------------------------------------------------------------------------------------
+def test_header_binding_and_library_agree():
+    lib = nfopp.load_library()
+    header = open(os.path.join(ROOT, "include", "nfopp_hip.h")).read()
+    for name, n_args in (("nfopp_path_time_profile", 13), ("nfopp_path_time_sample", 15)):
+        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header)
+        assert decl and len(decl.group(1).split(",")) == n_args, name
+        assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
+        assert len(_lib._SIGNATURES[name][1]) == n_args and _lib._SIGNATURES[name][0] is ctypes.c_int
+    assert lib.nfopp_abi_version() == 6 and "#define NFOPP_ABI_VERSION 6" in header
+    assert ctypes.sizeof(_lib.MotionLimitsC) == 48
+    fields = re.findall(r"double (\w+);", re.search(r"typedef struct nfopp_motion_limits \{(.*?)\}", header, re.S).group(1))
+    assert fields == [f[0] for f in _lib.MotionLimitsC._fields_]
+    assert "time_profile.hip" in open(os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc", "Makefile")).read()
+
+
+def _limits(**kw):
+    base = dict(v_max=2.0, a_max=1.0, d_max=1.0, a_lat=np.inf, w_max=np.inf, cos_cusp=-0.5)
+    base.update(kw)
+    return _lib.MotionLimitsC(**base)
+
+
+def _profile_rc(lim, batch=1, n=4, dim=3, ptr=1):
+    p = ctypes.c_void_p(ptr) if ptr else None
+    return nfopp.load_library().nfopp_path_time_profile(p, p, p, batch, n, dim, lim, None, None, p, None, p, None)
+
+
+def _sample_rc(lim, batch=1, n=4, dim=3, t0=0.0, dt=0.1, count=3, ptr=1):
+    p = ctypes.c_void_p(ptr) if ptr else None
+    return nfopp.load_library().nfopp_path_time_sample(p, p, p, batch, n, dim, lim, p, None, t0, dt, count, p, None, None)
+
+
+BAD_LIMITS = [(dict(v_max=0.0), "v_max"), (dict(v_max=np.inf), "v_max"), (dict(v_max=np.nan), "v_max"),
+              (dict(a_max=0.0), "a_max"), (dict(a_max=-1.0), "a_max"), (dict(a_max=np.inf), "a_max"),
+              (dict(d_max=0.0), "d_max"), (dict(d_max=np.nan), "d_max"), (dict(d_max=np.inf), "d_max"),
+              (dict(a_lat=0.0), "a_lat"), (dict(a_lat=np.nan), "a_lat"), (dict(w_max=-2.0), "w_max"),
+              (dict(w_max=np.nan), "w_max"), (dict(cos_cusp=-1.5), "cos_cusp"), (dict(cos_cusp=1.01), "cos_cusp"),
+              (dict(cos_cusp=np.nan), "cos_cusp")]
+
+
+def test_every_argument_check_answers_without_a_gpu():
+    lib = nfopp.load_library()
+
+    def refused(rc, word):
+        assert rc == -1, word
+        assert word in lib.nfopp_last_error().decode(), (word, lib.nfopp_last_error())
+
+    for call in (_profile_rc, _sample_rc):
+        for kw, word in BAD_LIMITS:
+            refused(call(_limits(**kw)), word)
+        refused(call(_limits(), dim=4), "dim")
+        refused(call(_limits(), n=0), "waypoint")
+        refused(call(_limits(), batch=-1), "batch")
+        refused(call(None), "limits")
+        refused(call(_limits(), ptr=0), "null device pointer")
+        assert call(_limits(), batch=0, ptr=0) == 0                    # nothing to do: null pointers are fine
+        assert call(_limits(a_lat=np.inf, w_max=np.inf, cos_cusp=-1.0), batch=0, ptr=0) == 0
+    refused(_profile_rc(_limits(), n=5000), "path too long")
+    refused(_profile_rc(_limits(), n=3031), "path too long")           # N + 2 = 3033 at dim 3
+    refused(_profile_rc(_limits(), n=3274, dim=2), "path too long")
+    for dt in (0.0, -0.1, np.inf, np.nan):
+        refused(_sample_rc(_limits(), dt=dt), "dt")
+    refused(_sample_rc(_limits(), t0=np.nan), "t0")
+    refused(_sample_rc(_limits(), count=-1), "count")
+    assert _sample_rc(_limits(), count=0, ptr=0) == 0
+
+
+def test_python_names_defaults_and_torch_ops():
+    for name in ("MotionLimits", "TimedPaths", "time_parametrize", "TIME_SLOT_S", "TIME_SLOT_T", "TIME_SLOT_V",
+                 "TIME_SLOT_V_PEAK", "TIME_SUMMARY_TIME", "TIME_SUMMARY_LENGTH", "TIME_SUMMARY_STOPS", "TIME_SUMMARY_STATUS",
+                 "TIME_START_TOO_FAST", "TIME_GOAL_UNREACHABLE", "TIME_OUT_OF_RANGE"):
+        assert hasattr(nfopp, name) and name in nfopp.__all__, name
+    assert (nfopp.TIME_SLOT_S, nfopp.TIME_SLOT_T, nfopp.TIME_SLOT_V, nfopp.TIME_SLOT_V_PEAK) == (0, 1, 2, 3)
+    assert (nfopp.TIME_SUMMARY_TIME, nfopp.TIME_SUMMARY_LENGTH, nfopp.TIME_SUMMARY_STOPS, nfopp.TIME_SUMMARY_STATUS) == (0, 1, 2, 3)
+    assert (nfopp.TIME_START_TOO_FAST, nfopp.TIME_GOAL_UNREACHABLE, nfopp.TIME_OUT_OF_RANGE) == (1, 2, 4)
+    lim = nfopp.MotionLimits(2.0, 1.0)
+    assert lim.d_max == 1.0 and lim.a_lat == np.inf and lim.w_max == np.inf and lim.cusp_angle == np.pi / 3
+    assert lim.cos_cusp == float(np.cos(np.pi - np.pi / 3))            # BatchPlanner.path_stats' default cusp rule
+    assert nfopp.MotionLimits(2.0, 1.0, cusp_angle=None).cos_cusp == -1.0
+    c = nfopp.MotionLimits(2.0, 1.0, 1.5, 0.8, 1.2).to_c()
+    assert (c.v_max, c.a_max, c.d_max, c.a_lat, c.w_max) == (2.0, 1.0, 1.5, 0.8, 1.2)
+    assert torch_ops.limits_list(nfopp.MotionLimits(2.0, 1.0, 1.5, 0.8, 1.2, None)) == [2.0, 1.0, 1.5, 0.8, 1.2, -1.0]
+    import inspect
+    sig = inspect.signature(nfopp.time_parametrize)
+    assert list(sig.parameters) == ["traj", "start", "goal", "limits", "v_start", "v_goal"]
+    assert sig.parameters["v_start"].default is None and sig.parameters["v_goal"].default is None
+    assert inspect.signature(nfopp.TimedPaths.sample).parameters["t0"].default == 0.0
+    bp = inspect.signature(nfopp.BatchPlanner.timed_paths).parameters
+    assert list(bp)[1:] == ["limits", "v_start", "v_goal", "best"] and bp["best"].default is False
+    for cls in (nfopp.NERFOptPlanner, nfopp.ConstrainedNERFOptPlanner):
+        gp = inspect.signature(cls.get_timed_path).parameters
+        assert list(gp)[1:] == ["limits", "dt", "v_start"] and gp["v_start"].default == 0.0
+    import torch
+    ops = torch_ops.load()
+    assert "path_time_profile" in torch_ops.OPS and "path_time_sample" in torch_ops.OPS
+    z3, z2 = torch.zeros(1, 4, 3), torch.zeros(1, 3)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.path_time_profile(z3, z2, z2, [2.0, 1.0, 1.0, 1.0, 1.0, -0.5], None, None)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.path_time_sample(z3, z2, z2, [2.0, 1.0, 1.0, 1.0, 1.0, -0.5], torch.zeros(1, 6, 4, dtype=torch.float64), None, 0.0, 0.1, 3)
+    with pytest.raises(nfopp.NfoppError, match="no CPU path"):
+        nfopp.time_parametrize(z3, z2, z2, lim)
+
+
+def test_python_entries_refuse_shapes_the_kernels_would_index_past():
+    import torch
+    lim = nfopp.MotionLimits(2.0, 1.0)
+    traj, end = torch.zeros(3, 4, 3), torch.zeros(3, 3)
+    for bad_traj, start, goal in ((torch.zeros(3, 4), end, end), (torch.zeros(3, 0, 3), end, end), (torch.zeros(3, 4, 4), end, end),
+                                  (traj, torch.zeros(3, 2), end), (traj, end, torch.zeros(2, 3)), (traj, torch.zeros(3), end)):
+        with pytest.raises(ValueError, match="must be"):
+            nfopp.time_parametrize(bad_traj, start, goal, lim)
+    from nfopp.time_profile import _speeds
+    assert _speeds(None, 3, "cpu") is None
+    assert _speeds(0.5, 3, "cpu").tolist() == [0.5] * 3 and _speeds(torch.tensor([0.25]), 3, "cpu").tolist() == [0.25] * 3
+    assert _speeds(np.array([1.0, 2.0, 3.0]), 3, "cpu").tolist() == [1.0, 2.0, 3.0]
+    for v in (torch.zeros(2), np.zeros(4), [1.0, 2.0]):
+        with pytest.raises(ValueError, match="speed"):
+            _speeds(v, 3, "cpu")
+    prof, gear, summary = torch.zeros(3, 6, 4, dtype=torch.float64), torch.zeros(3, 5, dtype=torch.int8), torch.zeros(3, 4, dtype=torch.float64)
+    assert nfopp.TimedPaths(traj, end, end, lim, prof, None, summary).gear is None
+    for p, g, s in ((prof[:, :5], gear, summary), (prof, gear[:, :4], summary), (prof, gear, summary[:2]), (prof[:2], gear, summary)):
+        with pytest.raises(ValueError, match="must be"):
+            nfopp.TimedPaths(traj, end, end, lim, p, g, s)
+    with pytest.raises(ValueError, match="must be"):
+        nfopp.TimedPaths(traj, end[:, :2], end, lim, prof, gear, summary)
