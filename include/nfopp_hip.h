@@ -767,6 +767,75 @@ int nfopp_path_time_sample(const float* traj_dev, const float* start_dev, const 
                            const int8_t* gear_dev, double t0, double dt, int32_t count, float* states_dev,
                            int32_t* segment_dev, void* stream);
 
+/* ---- conflicts between timed tracks (csrc/track_conflict.hip), additive under ABI 6 -----------------------------------------
+ * The entries above compare a path with a static map.  This one compares tracks with tracks: the B paths of a batch as B
+ * robots on one floor (self mode), or a set of timed paths against M predicted tracks of moving obstacles -- who comes closer
+ * than the radii allow, when first, and with whom, all pairs on the device.  Float64 throughout, every operation rounded on
+ * its own; the reductions are lexicographic minima on (value, index) and an integer count, which do not depend on the order:
+ * no float atomics, the same bits run after run, and the device is compared bit for bit with the numpy restatement in
+ * tests/track_conflict_ref.py.
+ *
+ * Inputs.  A track is k >= 1 positions at t_n = t0 + n * dt (n * dt rounded, then the sum, as nfopp_path_time_sample forms
+ *   its instants), read as fp32 and widened.  tracks_a_dev [ba, k, stride_a] fp32, tracks_b_dev [bb, k, stride_b]: x, y are
+ *   the first two floats of a row, stride >= 2 -- the [B, count, dim + 1] states of nfopp_path_time_sample are consumed as
+ *   they are.  Between two instants a track is LINEAR IN TIME (this check's own rule; see "what linearity costs").
+ *   tracks_b_dev == null is SELF MODE: the partners of track i are all j != i of set A (bb, stride_b, radius_b_dev are not
+ *   read).  A non-null tracks_b_dev with bb == 0 is a set of no obstacles.  radius_a_dev [ba], radius_b_dev [bb] fp32, null
+ *   = 0; self mode uses radius_a_dev for both sides.  R_ij = (ra_i + rb_j) + margin, R2_ij = R_ij * R_ij (float64; R_ij is
+ *   meant to be >= 0: the test below is on squares).  A box robot takes the radius of its circumscribed disc.
+ * Pair (i, j), interval n = 0 .. k - 2, componentwise d0 = pa_n - pb_n, d1 = pa_{n+1} - pb_{n+1}, w = d1 - d0:
+ *     c = d0x * d0x + d0y * d0y,  a = wx * wx + wy * wy,  b = d0x * wx + d0y * wy
+ *     a == 0 or b >= 0:  s = 0,         m = c
+ *     else -b >= a:      s = 1,         m = d1x * d1x + d1y * d1y
+ *     else:              s = (-b) / a,  p = d0 + s * w,  m = px * px + py * py
+ *   and one more term for the last instant: n = k - 1, s = 0, m = |d_{k-1}|^2 (the whole check when k = 1).
+ *   M_ij = min_n m_n, attained first at n*;  t*_ij = t_{n*} + s_{n*} * dt;  the gap g_ij = sqrt(M_ij) - R_ij.
+ * Conflict.  Pair (i, j) is in conflict when some m_n < R2_ij (strict, like the circle checker's dist < radius).  At the
+ *   smallest such n: s_in = 0 when c < R2, else disc = max(b * b - a * (c - R2), 0),
+ *   s_in = min(max(((-b) - sqrt(disc)) / a, 0), s);  tc_ij = t_n + s_in * dt.  A pair without conflict has tc_ij = +inf.
+ * Bad tracks.  A track with a non-finite coordinate (or radius) is BAD: as a partner it is skipped by everyone, its own
+ *   summary row is NaN with status NFOPP_CONFLICT_BAD_TRACK, its pair-matrix rows and columns are NaN (its diagonal entry in
+ *   self mode included).
+ * summary_dev [ba, NFOPP_NUM_CONFLICT_SLOTS] float64, over the good partners j of track i:
+ *     MIN_GAP        min_j g_ij; ties: the smaller j (the lexicographic minimum on (g, j));  +inf without a partner
+ *     MIN_PARTNER    j of that minimum, -1 without a partner
+ *     MIN_TIME       t* of that pair, NaN without a partner
+ *     FIRST_TIME     min_j tc_ij, +inf if none; ties: the smaller j
+ *     FIRST_PARTNER  j of that minimum, -1 if none
+ *     CONFLICTS      number of partners in conflict
+ *     STATUS         0, NFOPP_CONFLICT_BAD_TRACK, or NFOPP_CONFLICT_NO_PARTNER (no good partner: one robot alone, no
+ *                    obstacles, or every partner bad)
+ *   summary_b_dev [bb, NFOPP_NUM_CONFLICT_SLOTS] (may be null; not read in self mode): the same from set B's side, partners i.
+ * pair_gap_dev, pair_first_dev [ba, bb] float64 (each may be null): g_ij and tc_ij; in self mode [ba, ba] with +inf on the
+ *   diagonal.  In self mode every quantity above is even in the sign of d: swapping i and j negates d0, d1 and w exactly, and
+ *   every product is of two negated factors -- so the matrices are BITWISE SYMMETRIC, and the kernel evaluates the tiles of
+ *   the upper triangle only and serves both rows from them.
+ * What linearity costs.  A point moving at speed <= v stays within v * dt / 2 of the chord between its positions dt apart:
+ *   at time tau into the interval, with lambda = tau / dt, its distance from the chord point is at most
+ *   (1 - lambda) * v * tau + lambda * v * (dt - tau) = 2 * v * tau * (dt - tau) / dt <= v * dt / 2.  Two robots timed under
+ *   v_max therefore never get closer than gap - v_max * dt; `margin` is where the caller puts (va_max + vb_max) * dt / 2.
+ * workspace_dev: nfopp_track_conflicts_workspace_bytes(ba, bb, k) bytes (bb = 0 in self mode), rewritten by every call.
+ * Everything runs on `stream`; nothing synchronises.  Argument errors: a negative batch size, k < 1, a stride < 2, dt not
+ *   positive and finite, t0 or margin not finite, null tracks_a_dev / summary_dev with ba > 0, more tiles of 32 x 32 pairs than
+ *   a grid holds (2^31 - 1), a workspace that is null or too small.  ba == 0 returns 0 with null pointers and writes nothing;
+ *   self mode with ba == 1 writes the "no partner" row. */
+#define NFOPP_NUM_CONFLICT_SLOTS 7
+#define NFOPP_CONFLICT_SLOT_MIN_GAP 0
+#define NFOPP_CONFLICT_SLOT_MIN_PARTNER 1
+#define NFOPP_CONFLICT_SLOT_MIN_TIME 2
+#define NFOPP_CONFLICT_SLOT_FIRST_TIME 3
+#define NFOPP_CONFLICT_SLOT_FIRST_PARTNER 4
+#define NFOPP_CONFLICT_SLOT_CONFLICTS 5
+#define NFOPP_CONFLICT_SLOT_STATUS 6
+#define NFOPP_CONFLICT_BAD_TRACK 1
+#define NFOPP_CONFLICT_NO_PARTNER 2
+size_t nfopp_track_conflicts_workspace_bytes(int64_t ba, int64_t bb, int32_t k);
+int nfopp_track_conflicts(const float* tracks_a_dev, int64_t ba, int32_t stride_a, const float* tracks_b_dev, int64_t bb,
+                          int32_t stride_b, int32_t k, double t0, double dt, const float* radius_a_dev,
+                          const float* radius_b_dev, double margin, double* summary_dev, double* summary_b_dev,
+                          double* pair_gap_dev, double* pair_first_dev, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>       // guard / stream types that accept that device type
 #include <torch/library.h>
 
+#include <limits>
+
 #include "nfopp_hip.h"
 
 namespace {
@@ -376,6 +378,50 @@ std::tuple<Tensor, Tensor> path_time_sample(const Tensor& traj, const Tensor& st
   return std::make_tuple(states, segment);
 }
 
+// conflicts between timed tracks (nfopp_track_conflicts): tracks_a [Ba, K, Sa], tracks_b [Bb, K, Sb] or None (self mode), radii
+// [Ba] / [Bb] fp32 or None (0) -> (summary [Ba, 7], summary_b [Bb, 7], pair_gap, pair_first [Ba, Bb]) float64; summary_b is
+// empty in self mode, the pair matrices are empty without want_pairs.
+std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_a, const OptTensor& tracks_b, double dt, double t0,
+                                                           const OptTensor& radius_a, const OptTensor& radius_b, double margin,
+                                                           bool want_pairs) {
+  check_tensor(tracks_a, "tracks_a");
+  TORCH_CHECK(tracks_a.dim() == 3 && tracks_a.size(1) >= 1 && tracks_a.size(2) >= 2, "nfopp: tracks_a must be [B, K, >= 2] with K >= 1");
+  const int64_t ba = tracks_a.size(0), k = tracks_a.size(1);
+  const bool self = !tracks_b.has_value();
+  int64_t bb = ba;
+  if (!self) {
+    check_tensor(*tracks_b, "tracks_b");
+    same_device(tracks_a, *tracks_b, "tracks_b");
+    TORCH_CHECK(tracks_b->dim() == 3 && tracks_b->size(1) == k && tracks_b->size(2) >= 2,
+                "nfopp: tracks_b must be [Bb, K, >= 2] with the K of tracks_a (", k, ")");
+    bb = tracks_b->size(0);
+  }
+  TORCH_CHECK(k <= 0x7fffffffLL && tracks_a.size(2) <= 0x7fffffffLL && (self || tracks_b->size(2) <= 0x7fffffffLL),
+              "nfopp: tracks must have fewer than 2^31 instants and floats per row");
+  if (radius_a.has_value()) need(tracks_a, *radius_a, "radius_a", {ba});
+  if (!self && radius_b.has_value()) need(tracks_a, *radius_b, "radius_b", {bb});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks_a.device());
+  const auto f64 = tracks_a.options().dtype(at::kDouble);
+  Tensor summary = at::empty({ba, NFOPP_NUM_CONFLICT_SLOTS}, f64);
+  Tensor summary_b = at::empty({self ? 0 : bb, NFOPP_NUM_CONFLICT_SLOTS}, f64);
+  Tensor pair_gap = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, f64), pair_first = at::empty_like(pair_gap);
+  const size_t bytes = nfopp_track_conflicts_workspace_bytes(ba, self ? 0 : bb, (int32_t)k);
+  Tensor workspace = at::empty({(int64_t)bytes}, tracks_a.options().dtype(at::kByte));
+  auto dptr = [](Tensor& t) { return t.numel() ? t.data_ptr<double>() : nullptr; };
+  // a set of no obstacles still needs a non-null tracks_b pointer (null selects self mode); it is never read
+  const float* b_ptr = self ? nullptr : (bb > 0 ? tracks_b->data_ptr<float>() : tracks_a.data_ptr<float>());
+  check_status(nfopp_track_conflicts(ba ? tracks_a.data_ptr<float>() : nullptr, ba, (int32_t)tracks_a.size(2), ba ? b_ptr : nullptr, bb,
+                                     self ? 2 : (int32_t)tracks_b->size(2), (int32_t)k, t0, dt, opt_ptr<float>(radius_a),
+                                     self ? nullptr : opt_ptr<float>(radius_b), margin, dptr(summary), dptr(summary_b),
+                                     dptr(pair_gap), dptr(pair_first), bytes ? workspace.data_ptr() : nullptr, bytes,
+                                     stream_of(tracks_a)));
+  if (ba == 0 && summary_b.numel()) {   // the entry writes nothing for an empty set A: every obstacle is without a partner
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    summary_b.copy_(at::tensor({inf, -1.0, nan, inf, -1.0, 0.0, (double)NFOPP_CONFLICT_NO_PARTNER}, at::kDouble).expand_as(summary_b));
+  }
+  return std::make_tuple(summary, summary_b, pair_gap, pair_first);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nfopp, lib) {
@@ -409,6 +455,8 @@ TORCH_LIBRARY(nfopp, lib) {
           "(Tensor, Tensor, Tensor)");
   lib.def("path_time_sample(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor profile, Tensor? gear, float t0, "
           "float dt, int count) -> (Tensor, Tensor)");
+  lib.def("track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor? radius_a, Tensor? radius_b, float margin, "
+          "bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -426,4 +474,5 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("grid_search_init", &grid_search_init);
   lib.impl("path_time_profile", &path_time_profile);
   lib.impl("path_time_sample", &path_time_sample);
+  lib.impl("track_conflicts", &track_conflicts);
 }

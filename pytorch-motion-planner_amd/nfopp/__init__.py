@@ -5,6 +5,9 @@ Host-side mirror of the reference's planner interface over libnfopp_hip.so (C AB
 from ._lib import LIB_PATH, NUM_PATH_STATS, PATH_STAT_NAMES, NfoppError, load as load_library
 from .batch import BatchPlanner, OnfFitter, shard_range, straight_line_init
 from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
+from .conflicts import (CONFLICT_BAD_TRACK, CONFLICT_COUNT, CONFLICT_FIRST_PARTNER, CONFLICT_FIRST_TIME, CONFLICT_MIN_GAP,
+                        CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_NO_PARTNER, CONFLICT_STATUS, TrackConflicts,
+                        constant_velocity_tracks, track_conflicts)
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
 from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fields, grid_search_init, grid_search_paths,
                           margin_cells2, seed_polylines, seed_trajectories, shorten_paths)
@@ -35,4 +38,7 @@ __all__ = [
     "MotionLimits", "TimedPaths", "time_parametrize", "TIME_SLOT_S", "TIME_SLOT_T", "TIME_SLOT_V", "TIME_SLOT_V_PEAK",
     "TIME_SUMMARY_TIME", "TIME_SUMMARY_LENGTH", "TIME_SUMMARY_STOPS", "TIME_SUMMARY_STATUS", "TIME_START_TOO_FAST",
     "TIME_GOAL_UNREACHABLE", "TIME_OUT_OF_RANGE",
+    "TrackConflicts", "track_conflicts", "constant_velocity_tracks", "CONFLICT_MIN_GAP", "CONFLICT_MIN_PARTNER",
+    "CONFLICT_MIN_TIME", "CONFLICT_FIRST_TIME", "CONFLICT_FIRST_PARTNER", "CONFLICT_COUNT", "CONFLICT_STATUS",
+    "CONFLICT_BAD_TRACK", "CONFLICT_NO_PARTNER",
 ]

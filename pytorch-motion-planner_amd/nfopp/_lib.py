@@ -17,6 +17,7 @@ PATH_STAT_NAMES = ("length", "max_curvature", "curvature_at", "cusps", "reversal
                    "mean_clearance")
 NUM_TIME_SLOTS = 4      # NFOPP_NUM_TIME_SLOTS: s, t, v, peak v of the segment that starts at the vertex
 NUM_TIME_SUMMARY = 4    # NFOPP_NUM_TIME_SUMMARY: total time, length, stops, status
+NUM_CONFLICT_SLOTS = 7  # NFOPP_NUM_CONFLICT_SLOTS: min gap, its partner, its time, first conflict time, its partner, conflicts, status
 TERM_NAMES = ("total", "distance", "softplus_sum", "lambda_dot_c", "c_squared", "boundary", "cm_tanh", "direction")
 
 
@@ -174,6 +175,10 @@ _SIGNATURES = {
     "nfopp_path_time_sample": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.POINTER(MotionLimitsC), _P, _P, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_int32, _P, _P, _P]),
+    "nfopp_track_conflicts_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "nfopp_track_conflicts": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, ctypes.c_double,
+                                             _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -459,3 +459,18 @@ class BatchPlanner(object):
         eng = self.engine
         traj = self._best_traj() if best else eng.traj.view(eng.B, eng.N, eng.D)
         return time_parametrize(traj, eng.start, eng.goal, limits, v_start, v_goal)
+
+    def fleet_conflicts(self, limits, dt, count, radius, margin="chord", v_start=None, v_goal=None, best=False, obstacles=None,
+                        obstacle_radius=None, obstacle_v_max=None, want_pairs=False):
+        """The B paths as B robots that start together on one floor: time-parametrise under `limits`, sample at k * dt
+        (k < count) and check every robot against every other (nfopp.TrackConflicts: `.summary` [B, 7]).  `radius`: a
+        number or [B]; `margin="chord"` covers what a robot can do between two instants.  With `obstacles` [M, count, >= 2]
+        (predicted tracks on the same grid, e.g. `nfopp.constant_velocity_tracks`) the paths are also checked against
+        those, and the result is the pair (fleet, against obstacles); the chord margin then needs `obstacle_v_max`.
+        Nothing here synchronises with device-tensor arguments."""
+        timed = self.timed_paths(limits, v_start=v_start, v_goal=v_goal, best=best)
+        fleet = timed.conflicts(dt, count, radius=radius, margin=margin, want_pairs=want_pairs)
+        if obstacles is None:
+            return fleet
+        return fleet, timed.conflicts(dt, count, other=obstacles, radius=radius, other_radius=obstacle_radius, margin=margin,
+                                      other_v_max=obstacle_v_max, want_pairs=want_pairs)

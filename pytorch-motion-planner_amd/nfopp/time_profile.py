@@ -89,6 +89,32 @@ class TimedPaths(object):
             _lib.stream_ptr()))
         return (states, segment) if want_segment else states
 
+    def conflicts(self, dt, count, other=None, radius=0.0, other_radius=None, margin=0.0, t0=0.0, want_pairs=False,
+                  other_v_max=None):
+        """The B timed paths as B robots on one floor, sampled at t0 + k * dt (k < count): who comes closer to whom than
+        the radii allow, and when first (`nfopp.track_conflicts`, self mode) -> `nfopp.TrackConflicts`.  With `other` -- a
+        `TimedPaths`, sampled on the same grid, or a tracks tensor [M, count, >= 2] such as `constant_velocity_tracks`
+        returns -- the paths are checked against those tracks instead.  `radius` / `other_radius`: a number or one per track.
+        `margin="chord"` is (v_max + the other side's v_max) * dt / 2, what the straight line between two instants can
+        hide; for a tracks tensor it needs `other_v_max`."""
+        from .conflicts import chord_margin, track_conflicts
+        tracks_b, vb = None, self.limits.v_max
+        if isinstance(other, TimedPaths):
+            tracks_b, vb = other.sample(dt, count, t0=t0), other.limits.v_max
+        elif other is not None:
+            tracks_b, vb = other, other_v_max
+        if isinstance(margin, str):
+            if margin != "chord":
+                raise ValueError("margin must be a number or \"chord\", got %r" % (margin,))
+            if vb is None:
+                raise ValueError("margin=\"chord\" against a tracks tensor needs other_v_max, the top speed of those tracks")
+            margin = chord_margin(self.limits.v_max, vb, dt)
+        if other is None:
+            return track_conflicts(self.sample(dt, count, t0=t0), dt=dt, t0=t0, radius_a=radius, margin=margin,
+                                   want_pairs=want_pairs)
+        return track_conflicts(self.sample(dt, count, t0=t0), tracks_b, dt=dt, t0=t0, radius_a=radius, radius_b=other_radius,
+                               margin=margin, want_pairs=want_pairs)
+
 
 def time_parametrize(traj, start, goal, limits, v_start=None, v_goal=None):
     """traj [B, N, D], start / goal [B, D]: fp32 HIP tensors (D = 2 or 3).  `v_start` / `v_goal`: the speed the robot has
