@@ -10,6 +10,7 @@
 // query and the checkers cannot disagree about a pose.  No atomics; every minimum is the lexicographic minimum of
 // (distance, index), which does not depend on the order the points are visited in: the two entries, the two work
 // distributions of the indexed one and any two runs give the same bits.
+#include "block_collectives.h"
 #include "common.h"
 #include "point_cloud.h"
 
@@ -108,8 +109,8 @@ __device__ __forceinline__ void nearest_in_cells(const NearArgs& a, const Pose& 
       if (cx + r <= nx - 1) scan_cells<MODE, WAVE>(a, q, yy, cx + r, cx + r, &best, &bestk);
     }
     if (WAVE) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) take_min(__shfl_xor(best, o), __shfl_xor(bestk, o), &best, &bestk);
+      const Indexed<float> m = wave_reduce(Indexed<float>{best, bestk}, TakeMin());
+      best = m.v; bestk = m.i;
     }
     const bool closed = cx - r <= 0 && cx + r >= nx - 1 && cy - r <= 0 && cy + r >= ny - 1;
     const float lower = __builtin_fmaf(((float)r - 0.0625f) * a.cloud.index.size, 1.0f - 3.814697265625e-06f, -a.robot.reach);
@@ -170,19 +171,7 @@ struct StatsArgs {
 constexpr int PS_THREADS = 256;
 constexpr int PS_WAVES = PS_THREADS / 64;
 
-// workgroup sum in a fixed order: xor tree inside each wave, then the waves one after the other (path_interpolate_kernel's)
-__device__ __forceinline__ double block_sum(double v, double* red /* LDS [PS_WAVES] */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-  __syncthreads();   // `red` may still be read by a previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < PS_WAVES; ++w) s = s + red[w];
-  return s;
-}
-
-// workgroup extremum with the first index attaining it: SIGN = +1 maximum, -1 minimum; index -1 = no candidate
+// extremum with the first index attaining it: SIGN = +1 maximum, -1 minimum; index -1 = no candidate
 template <int SIGN>
 __device__ __forceinline__ bool better(double v, int i, double o, int oi) {
   if (i < 0) return false;
@@ -190,22 +179,11 @@ __device__ __forceinline__ bool better(double v, int i, double o, int oi) {
   return (SIGN > 0 ? v > o : v < o) || (v == o && i < oi);
 }
 template <int SIGN>
-__device__ __forceinline__ void block_extremum(double* v, int* i, double* red, int* redi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(*v, o);
-    const int oi = __shfl_xor(*i, o);
-    if (better<SIGN>(ov, oi, *v, *i)) { *v = ov; *i = oi; }
+struct Better {
+  __device__ __forceinline__ Indexed<double> operator()(Indexed<double> a, Indexed<double> b) const {
+    return better<SIGN>(b.v, b.i, a.v, a.i) ? b : a;
   }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = *v; redi[threadIdx.x >> 6] = *i; }
-  __syncthreads();
-  double bv = red[0];
-  int bi = redi[0];
-  for (int w = 1; w < PS_WAVES; ++w)
-    if (better<SIGN>(red[w], redi[w], bv, bi)) { bv = red[w]; bi = redi[w]; }
-  *v = bv; *i = bi;
-}
+};
 
 template <int D>
 __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs a) {
@@ -214,10 +192,11 @@ __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs 
   __shared__ int redi[PS_WAVES];
   const long long b = blockIdx.x;
   const int N = a.n;
-  const float* tr = a.traj + b * N * D;
-  auto point = [&](int f, int d) {  // full trajectory index 0..N+1, widened
-    return (double)(f == 0 ? a.start[b * D + d] : (f == N + 1 ? a.goal[b * D + d] : tr[(long long)(f - 1) * D + d]));
-  };
+  auto point = [&](int f, int d) { return (double)path_entry<D>(a.traj, a.start, a.goal, N, b, f * D + d); };
+  // the collectives of this kernel: sums from 0, extrema from "no candidate" (which loses to every candidate)
+  auto block_sum = [&](double v) { return block_reduce<PS_WAVES>(v, 0.0, Plus(), red); };
+  const Indexed<double> none = {0.0, -1};
+  const IndexedScratch<double> red2 = {red, redi};
   // segments i = 0..N: length, forward sign
   double len = 0.0;
   for (int i = threadIdx.x; i <= N; i += PS_THREADS) {
@@ -229,7 +208,7 @@ __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs 
       sgn[i] = fwd > 0.0 ? 1 : (fwd < 0.0 ? -1 : 0);
     }
   }
-  len = block_sum(len, red);   // its barriers also publish sgn[]
+  len = block_sum(len);   // its barriers also publish sgn[]
   // interior vertices i = 1..N between segments i - 1 and i
   double kmax = 0.0;
   int kidx = -1, cusps = 0, reversals = 0;
@@ -251,8 +230,8 @@ __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs 
       if (j >= 0 && sgn[j] != sgn[i]) ++reversals;
     }
   }
-  block_extremum<+1>(&kmax, &kidx, red, redi);
-  const double n_cusps = block_sum((double)cusps, red), n_rev = block_sum((double)reversals, red);   // integers: exact
+  const Indexed<double> sharpest = block_reduce<PS_WAVES>(Indexed<double>{kmax, kidx}, none, Better<+1>(), red2);
+  const double n_cusps = block_sum((double)cusps), n_rev = block_sum((double)reversals);   // integers: exact
   // clearance along the densified path
   double dmin = (double)__builtin_inff(), dmean = (double)__builtin_inff();
   int didx = -1;
@@ -265,13 +244,13 @@ __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs 
       sum = sum + v;
       if (mi < 0 || v < m) { m = v; mi = k; }
     }
-    block_extremum<-1>(&m, &mi, red, redi);
-    sum = block_sum(sum, red);
-    dmin = m; didx = mi; dmean = sum / (double)a.poses;
+    const Indexed<double> nearest = block_reduce<PS_WAVES>(Indexed<double>{m, mi}, none, Better<-1>(), red2);
+    sum = block_sum(sum);
+    dmin = nearest.v; didx = nearest.i; dmean = sum / (double)a.poses;
   }
   if (threadIdx.x == 0) {
     double* o = a.stats + b * NFOPP_NUM_PATH_STATS;
-    o[0] = len; o[1] = kidx < 0 ? 0.0 : kmax; o[2] = (double)kidx; o[3] = n_cusps; o[4] = n_rev;
+    o[0] = len; o[1] = sharpest.i < 0 ? 0.0 : sharpest.v; o[2] = (double)sharpest.i; o[3] = n_cusps; o[4] = n_rev;
     o[5] = dmin; o[6] = (double)didx; o[7] = dmean;
   }
 }

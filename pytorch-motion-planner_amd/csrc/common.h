@@ -186,6 +186,16 @@ __device__ __forceinline__ float wrap_angle(float a) {
   return r - NFOPP_PI_F;
 }
 
+// Entry k = f * D + d of the polyline  start | traj | goal  of batch row b: component d of vertex f, where vertex 0 is the
+// start, 1 .. N the waypoints and N + 1 the goal (start, goal [B, D]; traj [B, N, D]).  fp32 as stored: the caller widens.
+template <int D>
+__device__ __forceinline__ float path_entry(const float* traj, const float* start, const float* goal, int N, long long b,
+                                            int k) {
+  if (k < D) return start[b * D + k];
+  if (k >= (N + 1) * D) return goal[b * D + (k - (N + 1) * D)];
+  return traj[b * N * D + (k - D)];
+}
+
 // a + b * c and p * a + q * b with every product and sum rounded on its own, as a chain of separate torch ops is on the
 // CPU (hipcc would contract the plain expressions to fused multiply-adds)
 // (HIP's __fmul_rn / __fadd_rn are plain * and + and contract like them: the pragma is what holds)

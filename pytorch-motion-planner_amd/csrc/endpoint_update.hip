@@ -27,6 +27,11 @@ __device__ __forceinline__ bool argmin_before(float ka, int ia, float kb, int ib
   if (ka != ka) return (kb != kb) ? ia < ib : true;
   return ka == kb ? ia < ib : ka < kb;
 }
+struct ArgminFirst {
+  __device__ __forceinline__ Indexed<float> operator()(Indexed<float> a, Indexed<float> b) const {
+    return argmin_before(b.v, b.i, a.v, a.i) ? b : a;
+  }
+};
 
 struct EndpointArgs {
   int n, which;                 // which: 0 = start, 1 = goal
@@ -57,31 +62,17 @@ __global__ __launch_bounds__(RP_THREADS) void endpoint_update_kernel(const Endpo
   if (tid < D) (is_goal ? a.goal : a.start)[b * D + tid] = point[tid];
   __syncthreads();
 
-  // nearest waypoint: per-thread scan in rising index order, xor butterfly inside the wave, the four waves through LDS
+  // nearest waypoint: per-thread scan in rising index order, then the workgroup's reduction under the same order
   float* Q = L.Q;
   const float* P = Q + (is_goal ? (N + 1) * D : 0);   // the new endpoint's row of the image
   const float px = P[0], py = P[1];
-  float key = __builtin_inff();
-  int idx = INT_MAX;                                 // a thread without waypoints loses to every waypoint, inf keys included
-  for (int w = tid; w < N; w += RP_THREADS) {
-    const float k = sq_dist_unfused(Q[(w + 1) * D] - px, Q[(w + 1) * D + 1] - py);
-    if (argmin_before(k, w, key, idx)) { key = k; idx = w; }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ok = __shfl_xor(key, o);
-    const int oi = __shfl_xor(idx, o);
-    if (argmin_before(ok, oi, key, idx)) { key = ok; idx = oi; }
-  }
+  const Indexed<float> none = {__builtin_inff(), INT_MAX};   // loses to every waypoint, inf keys included
+  Indexed<float> nearest = none;
+  for (int w = tid; w < N; w += RP_THREADS)
+    nearest = ArgminFirst()(nearest, {sq_dist_unfused(Q[(w + 1) * D] - px, Q[(w + 1) * D + 1] - py), w});
   constexpr int WAVES = RP_THREADS / 64;
-  float* wkey = L.red;                               // `red` is idle until the reparametrisation's sum
-  int* widx = reinterpret_cast<int*>(L.red + WAVES);
-  if ((tid & 63) == 0) { wkey[tid >> 6] = key; widx[tid >> 6] = idx; }
-  __syncthreads();
-  key = wkey[0]; idx = widx[0];
-#pragma unroll
-  for (int w2 = 1; w2 < WAVES; ++w2)
-    if (argmin_before(wkey[w2], widx[w2], key, idx)) { key = wkey[w2]; idx = widx[w2]; }
+  const IndexedScratch<float> wred = {L.red, reinterpret_cast<int*>(L.red + WAVES)};   // idle until the reparametrisation's sum
+  const int idx = block_reduce<WAVES>(nearest, none, ArgminFirst(), wred).i;
   const int m = D == 3 ? min(idx + 1, N) : idx;       // constrained:182,190 vs nerf:206,214
   if (tid == 0 && a.min_index) a.min_index[b] = m;
 

@@ -6,6 +6,7 @@
 //   * the index `DeviceCircleChecker` used to build on the host (np.argsort(kind="stable") + np.searchsorted)
 // Everything here is integer counting plus per-element arithmetic: no atomics, every sum in a fixed order, so both
 // results are bit-identical from run to run.  All kernels are latency-bound helpers that run at map rate.
+#include "block_collectives.h"
 #include "common.h"
 #include "point_cloud.h"
 
@@ -13,29 +14,6 @@ namespace nfopp {
 
 constexpr int OM_THREADS = 256;             // 4 waves of 64
 constexpr int OM_WAVES = OM_THREADS / 64;
-
-// Exclusive prefix sum of one int per thread over the workgroup, in thread order; *total = the workgroup's sum.
-__device__ __forceinline__ int block_exclusive_scan(int v, int* wave_sums /* LDS [OM_WAVES] */, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();   // wave_sums may still be read by a previous call
-  if (lane == 63) wave_sums[wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < OM_WAVES; ++w) {
-    const int t = wave_sums[w];
-    before += w < wave ? t : 0;
-    all += t;
-  }
-  *total = all;
-  return before + inc - v;
-}
 
 // ---- grid -> point cloud -----------------------------------------------------------------------------------------
 // Order-preserving compaction in three launches: (1) occupied cells per chunk of GP_CHUNK cells (ballot + popcount),
@@ -101,7 +79,7 @@ __global__ __launch_bounds__(OM_THREADS) void grid_scan_kernel(const GridArgs a)
     const int i = base + threadIdx.x;
     const int v = i < a.n_chunks ? a.counts[i] : 0;
     int total;
-    const int ex = block_exclusive_scan(v, wave_sums, &total);
+    const int ex = block_exclusive_scan<OM_WAVES>(v, 0, Plus(), wave_sums, &total);
     if (i < a.n_chunks) a.counts[i] = carry + ex;
     carry += total;
   }
@@ -217,8 +195,7 @@ __global__ __launch_bounds__(OM_THREADS) void index_scan_kernel(const IndexArgs 
   int* row = a.table + (long long)threadIdx.x * a.n_seg;
   int sum = 0;
   for (int s = 0; s < a.n_seg; ++s) sum += row[s];
-  int total;
-  int run = block_exclusive_scan(sum, wave_sums, &total);
+  int run = block_exclusive_scan<OM_WAVES>(sum, 0, Plus(), wave_sums);
   for (int s = 0; s < a.n_seg; ++s) {
     const int t = row[s];
     row[s] = run;

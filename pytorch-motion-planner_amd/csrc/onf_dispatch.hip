@@ -9,6 +9,7 @@
 
 #include <atomic>
 
+#include "block_collectives.h"
 #include "onf_kernel.h"
 
 namespace nfopp {
@@ -48,28 +49,14 @@ int onf_route(const OnfGeom& g, OnfRoute* r) {
 constexpr int CP_THREADS = 1024;
 __global__ __launch_bounds__(CP_THREADS) void compact_live_kernel(const unsigned char* active, long long batch, int* live) {
   __shared__ int wave_sum[CP_THREADS / 64];
-  __shared__ int wave_off[CP_THREADS / 64 + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long long per = (batch + CP_THREADS - 1) / CP_THREADS;
   const long long lo = tid * per, hi = lo + per < batch ? lo + per : batch;
   int mine = 0;
   for (long long b = lo; b < hi; ++b) mine += active[b] != 0;
-  int scan = mine;   // inclusive scan over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(scan, o);
-    if (lane >= o) scan += up;
-  }
-  if (lane == 63) wave_sum[wave] = scan;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int w = 0; w < CP_THREADS / 64; ++w) { wave_off[w] = run; run += wave_sum[w]; }
-    wave_off[CP_THREADS / 64] = run;
-    live[0] = run;
-  }
-  __syncthreads();
-  int pos = wave_off[wave] + scan - mine;
+  int count;
+  int pos = block_exclusive_scan<CP_THREADS / 64>(mine, 0, Plus(), wave_sum, &count);
+  if (tid == 0) live[0] = count;
   for (long long b = lo; b < hi; ++b)
     if (active[b] != 0) live[1 + pos++] = (int)b;
 }

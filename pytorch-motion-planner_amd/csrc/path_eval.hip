@@ -8,6 +8,7 @@
 // PathLengthMetric), which is not available; the semantics here are the generic ones: `sub` equally spaced poses per
 // segment (theta along the wrapped difference), Euclidean xy length of the waypoint polyline.  Parity with bench-mr's
 // numbers is therefore unpinned; parity with the oracle restatement is exact.
+#include "block_collectives.h"
 #include "common.h"
 
 namespace nfopp {
@@ -26,11 +27,8 @@ __global__ __launch_bounds__(PE_THREADS) void path_interpolate_kernel(const Inte
   __shared__ float red[PE_THREADS / 64];
   const long long b = blockIdx.x;
   const int N = a.n, M = (N + 1) * a.sub + 1;
-  const float* tr = a.traj + b * N * D;
   float* out = a.poses + b * M * D;
-  auto point = [&](int f, int d) {  // full trajectory index 0..N+1
-    return f == 0 ? a.start[b * D + d] : (f == N + 1 ? a.goal[b * D + d] : tr[(f - 1) * D + d]);
-  };
+  auto point = [&](int f, int d) { return path_entry<D>(a.traj, a.start, a.goal, N, b, f * D + d); };
   float part = 0.f;
   for (int s = threadIdx.x; s <= N; s += PE_THREADS) {
     float p0[D], p1[D];
@@ -52,15 +50,8 @@ __global__ __launch_bounds__(PE_THREADS) void path_interpolate_kernel(const Inte
 #pragma unroll
     for (int d = 0; d < D; ++d) out[(M - 1) * D + d] = a.goal[b * D + d];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int w = 0; w < PE_THREADS / 64; ++w) s += red[w];
-    a.length[b] = s;
-  }
+  const float length = block_reduce<PE_THREADS / 64>(part, 0.f, Plus(), red);
+  if (threadIdx.x == 0) a.length[b] = length;
 }
 
 struct SelectArgs {

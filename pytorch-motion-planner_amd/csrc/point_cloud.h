@@ -8,6 +8,7 @@
 // csrc/sampling.hip does not, so a product feeding a plain add or subtract would be one fma in one file and two roundings in
 // the other.  Every multiply-add is an explicit __builtin_fmaf; everything else is one operation per statement.
 #pragma once
+#include "block_collectives.h"
 #include "common.h"
 
 namespace nfopp {
@@ -96,6 +97,12 @@ struct Robot {
 __device__ __forceinline__ void take_min(float d, int k, float* best, int* bestk) {
   if (d < *best || (d == *best && k < *bestk)) { *best = d; *bestk = k; }
 }
+struct TakeMin {   // take_min as the op of a reduction over (distance, index) pairs
+  __device__ __forceinline__ Indexed<float> operator()(Indexed<float> a, Indexed<float> b) const {
+    take_min(b.v, b.i, &a.v, &a.i);
+    return a;
+  }
+};
 
 // All pairs: f(ox, oy, k) for every point k of the cloud in ascending k.  The points pass through the workgroup's LDS arrays
 // ox, oy [THREADS] a tile at a time between two barriers, so every thread has to call this, one without a pose included.

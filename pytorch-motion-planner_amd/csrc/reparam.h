@@ -14,6 +14,7 @@
 //     interleaved accumulator chains per lane folded every 16 rows, then the scalar tail, then the lanes in order
 //   * torch.cumsum accumulates in float64 (at::acc_type<float, false>) and rounds every partial sum to fp32
 #pragma once
+#include "block_collectives.h"
 #include "common.h"
 
 namespace nfopp {
@@ -163,22 +164,11 @@ __device__ __forceinline__ void reparam_from_lds(const ReparamLds& L, int N, int
   if (exact) {
     double part = 0.0;
     for (int s2 = lo_s; s2 < hi_s; ++s2) part += (double)cdf[s2];
-    // exclusive offsets of the per-thread sums: wave scan, then the wave totals through LDS (as doubles in `red2`)
-    double incl = part;
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
+    // exclusive offsets of the per-thread sums (exact, like every sum here); the wave totals go through `red2`
     float* r8 = red + 9;
     if (reinterpret_cast<size_t>(r8) & 7) r8 += 1;        // 8-byte aligned slot for the four wave sums
     double* red2 = reinterpret_cast<double*>(r8);
-    if (lane == 63) red2[wave] = incl;
-    __syncthreads();
-    double off = incl - part;
-    for (int w2 = 0; w2 < wave; ++w2) off += red2[w2];
-    double run = off;
+    double run = block_exclusive_scan<RP_THREADS / 64>(part, 0.0, Plus(), red2);
     for (int s2 = lo_s; s2 < hi_s; ++s2) {
       run += (double)cdf[s2];
       cdf[s2] = (float)run;

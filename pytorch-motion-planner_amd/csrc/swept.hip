@@ -11,6 +11,7 @@
 // The per-point terms are the fp32 expressions of csrc/point_cloud.h that the checkers and the nearest-obstacle query
 // evaluate.  No atomics; every minimum is the lexicographic minimum of (value, index), which does not depend on the order
 // the points are visited in: both entries and any two runs give the same bits.
+#include "block_collectives.h"
 #include "common.h"
 #include "point_cloud.h"
 
@@ -185,45 +186,40 @@ struct SweptLabelArgs {
 constexpr int SL_THREADS = 256;
 constexpr int SL_WAVES = SL_THREADS / 64;
 
+// what a path's threads reduce: the smallest (value, segment) under take_min's order, and the OR of their flags
+struct WorstSegment { Indexed<float> seg; int flags; };
+__device__ __forceinline__ WorstSegment lane_xor(WorstSegment a, int o) { return {lane_xor(a.seg, o), lane_xor(a.flags, o)}; }
+struct WorstOp {
+  __device__ __forceinline__ WorstSegment operator()(WorstSegment a, WorstSegment b) const {
+    return {TakeMin()(a.seg, b.seg), a.flags | b.flags};
+  }
+};
+
 __global__ __launch_bounds__(SL_THREADS) void path_swept_labels_kernel(const SweptLabelArgs g) {
-  __shared__ float red[SL_WAVES];
-  __shared__ int redi[SL_WAVES], redf[SL_WAVES];
+  __shared__ WorstSegment red[SL_WAVES];
   const long long b = blockIdx.x;
   const int m = g.m, D = g.dim;
   const float* poses = g.poses + b * m * D;
   const float* value = g.value + b * (m - 1);
   float* labels = g.labels + b * m;
   const int used = g.box ? 3 : 2;   // the components the segment kernels' `finite` looks at
-  float best = __builtin_inff();
-  int bestj = 0x7fffffff, flags = 0;   // bit 0: a pose in collision, bit 1: a segment not certified
+  const WorstSegment none = {{__builtin_inff(), 0x7fffffff}, 0};
+  WorstSegment mine = none;   // flags bit 0: a pose in collision, bit 1: a segment not certified
   for (int j = threadIdx.x; j < m; j += SL_THREADS) {
-    if (labels[j] != 0.0f) flags |= 1;
+    if (labels[j] != 0.0f) mine.flags |= 1;
     if (j == m - 1) break;            // the last pose keeps its label
     const float v = value[j];
     bool finite = true;
     for (int d = 0; d < used; ++d) finite = finite && isfinite(poses[j * D + d]) && isfinite(poses[(j + 1) * D + d]);
     const bool certified = finite && (g.box ? v > g.threshold : v >= g.threshold);
-    if (!certified) { flags |= 2; labels[j] = 1.0f; }
-    if (v < best || (v == best && j < bestj)) { best = v; bestj = j; }
+    if (!certified) { mine.flags |= 2; labels[j] = 1.0f; }
+    take_min(v, j, &mine.seg.v, &mine.seg.i);
   }
-  // fixed order: xor tree inside each wave, then the waves one after the other
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int oj = __shfl_xor(bestj, o);
-    flags |= __shfl_xor(flags, o);
-    if (ov < best || (ov == best && oj < bestj)) { best = ov; bestj = oj; }
-  }
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = best; redi[threadIdx.x >> 6] = bestj; redf[threadIdx.x >> 6] = flags; }
-  __syncthreads();
+  const WorstSegment all = block_reduce<SL_WAVES>(mine, none, WorstOp(), red);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < SL_WAVES; ++w) {
-      flags |= redf[w];
-      if (red[w] < best || (red[w] == best && redi[w] < bestj)) { best = red[w]; bestj = redi[w]; }
-    }
     // a disc segment that is not certified IS a collision; a box segment is only undecided
-    if (g.status) g.status[b] = (flags & 1) || (!g.box && (flags & 2)) ? 1 : ((flags & 2) ? 2 : 0);
-    if (g.worst) { g.worst[2 * b] = best; g.worst[2 * b + 1] = (float)bestj; }
+    if (g.status) g.status[b] = (all.flags & 1) || (!g.box && (all.flags & 2)) ? 1 : ((all.flags & 2) ? 2 : 0);
+    if (g.worst) { g.worst[2 * b] = all.seg.v; g.worst[2 * b + 1] = (float)all.seg.i; }
   }
 }
 
@@ -435,8 +431,7 @@ __global__ __launch_bounds__(64) void refine_walk_kernel(const RefineArgs g) {
           for_candidates<CELLS>(cloud, c, lane, [&](float px, float py) {
             best = fminf(best, segment_term<1>(g.seg, piece, px, py));
           });
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) best = fminf(best, __shfl_xor(best, o));
+          best = wave_reduce(best, [](float x, float y) { return fminf(x, y); });
           certified = piece_certified(g.seg, piece, best);
         }
         root_node = false;
@@ -482,32 +477,35 @@ struct RefinedLabelArgs {
   unsigned char* status; float* first;
 };
 
+// the first segment that is not free, and the OR of the flags
+struct FirstSegment { int j, flags; };
+__device__ __forceinline__ FirstSegment lane_xor(FirstSegment a, int o) { return {lane_xor(a.j, o), lane_xor(a.flags, o)}; }
+struct FirstOp {
+  __device__ __forceinline__ FirstSegment operator()(FirstSegment a, FirstSegment b) const {
+    return {min(a.j, b.j), a.flags | b.flags};
+  }
+};
+
 __global__ __launch_bounds__(SL_THREADS) void path_refined_labels_kernel(const RefinedLabelArgs g) {
-  __shared__ int redi[SL_WAVES], redf[SL_WAVES];
+  __shared__ FirstSegment red[SL_WAVES];
   const long long b = blockIdx.x;
   const int m = g.m;
   const unsigned char* seg = g.seg_status + b * (m - 1);
   float* labels = g.labels + b * m;
-  int firstj = 0x7fffffff, flags = 0;   // bit 0: a pose or a segment in collision, bit 1: a segment undecided
+  const FirstSegment none = {0x7fffffff, 0};
+  FirstSegment mine = none;   // flags bit 0: a pose or a segment in collision, bit 1: a segment undecided
   for (int j = threadIdx.x; j < m; j += SL_THREADS) {
-    if (labels[j] != 0.0f) flags |= 1;
+    if (labels[j] != 0.0f) mine.flags |= 1;
     if (j == m - 1) break;            // the last pose keeps its label
     const unsigned char st = seg[j];
     if (st == RF_FREE) continue;
-    flags |= st == RF_HIT ? 1 : 2;
+    mine.flags |= st == RF_HIT ? 1 : 2;
     labels[j] = 1.0f;
-    firstj = min(firstj, j);
+    mine.j = min(mine.j, j);
   }
-  // fixed order: xor tree inside each wave, then the waves one after the other
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    firstj = min(firstj, __shfl_xor(firstj, o));
-    flags |= __shfl_xor(flags, o);
-  }
-  if ((threadIdx.x & 63) == 0) { redi[threadIdx.x >> 6] = firstj; redf[threadIdx.x >> 6] = flags; }
-  __syncthreads();
+  const FirstSegment all = block_reduce<SL_WAVES>(mine, none, FirstOp(), red);
+  const int firstj = all.j, flags = all.flags;
   if (threadIdx.x == 0) {
-    for (int w = 1; w < SL_WAVES; ++w) { flags |= redf[w]; firstj = min(firstj, redi[w]); }
     if (g.status) g.status[b] = (flags & 1) ? 1 : ((flags & 2) ? 2 : 0);
     if (g.first) {
       const bool any = firstj != 0x7fffffff;

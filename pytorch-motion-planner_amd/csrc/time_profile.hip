@@ -43,6 +43,7 @@
 //
 // No atomics, no static LDS (every byte of LDS is dynamic and follows the path length; a static array would come off the
 // 160 KiB as reparam.h notes for __syncthreads_and).  The same bits run after run.
+#include "block_collectives.h"
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -70,45 +71,9 @@ inline size_t tp_lds_bytes(long long m, int dim) {
   return (size_t)(TP_WAVES * 16 + m * 40 + ((m * dim * 4 + 7) & ~7LL) + ((2 * m + 15) & ~15LL));
 }
 
-struct SumOp {
-  __device__ __forceinline__ u64 operator()(u64 a, u64 b) const { return a + b; }
-};
 struct MinOp {
   __device__ __forceinline__ double operator()(double a, double b) const { return b < a ? b : a; }
 };
-
-// Exclusive scan of one value per thread in thread order: __shfl_up over the 64 lanes, then the wave totals through LDS
-// (reparam.h's float64 scan).  `red` [TP_WAVES] may still be read by a previous call: the first barrier covers that.
-template <class T, class Op>
-__device__ __forceinline__ T block_exclusive(T part, T identity, Op op, T* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T incl = part;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T up = __shfl_up(incl, o);
-    if (lane >= o) incl = op(up, incl);
-  }
-  T excl = __shfl_up(incl, 1);
-  if (lane == 0) excl = identity;
-  __syncthreads();
-  if (lane == 63) red[wave] = incl;
-  __syncthreads();
-  T off = identity;
-  for (int w = 0; w < wave; ++w) off = op(off, red[w]);
-  return op(off, excl);
-}
-
-// workgroup total of small integer counts (exact in any order)
-__device__ __forceinline__ u64 block_total(u64 v, u64* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  u64 s = 0;
-  for (int w = 0; w < TP_WAVES; ++w) s += red[w];
-  return s;
-}
 
 template <int D>
 __global__ __launch_bounds__(TP_THREADS) void time_profile_kernel(const ProfileArgs a) {
@@ -131,9 +96,8 @@ __global__ __launch_bounds__(TP_THREADS) void time_profile_kernel(const ProfileA
 
   // the path's image
   int bad = 0;
-  const float* tr = a.traj + b * N * D;
   for (int k = tid; k < M * D; k += TP_THREADS) {
-    const float v = k < D ? a.start[b * D + k] : (k >= (N + 1) * D ? a.goal[b * D + (k - (N + 1) * D)] : tr[k - D]);
+    const float v = path_entry<D>(a.traj, a.start, a.goal, N, b, k);
     P[k] = v;
     if (!(fabsf(v) < __builtin_inff())) bad = 1;
   }
@@ -167,7 +131,7 @@ __global__ __launch_bounds__(TP_THREADS) void time_profile_kernel(const ProfileA
   {
     u64 part = 0;
     for (int i = lo; i < hi; ++i) part += S[i];
-    u64 run = block_exclusive(part, (u64)0, SumOp(), redu);
+    u64 run = block_exclusive_scan<TP_WAVES>(part, (u64)0, Plus(), redu);
     for (int i = lo; i < hi; ++i) { const u64 l = S[i]; S[i] = run; run += l; }
   }
   // gear of each segment (S and gr are published by the barriers of the next scan)
@@ -218,7 +182,7 @@ __global__ __launch_bounds__(TP_THREADS) void time_profile_kernel(const ProfileA
   {
     double part = inf;
     for (int i = lo; i < hi; ++i) { const double v = C[i] - A * s_of(i); part = v < part ? v : part; }
-    double run = block_exclusive(part, inf, MinOp(), redd);
+    double run = block_exclusive_scan<TP_WAVES>(part, inf, MinOp(), redd);
     for (int i = lo; i < hi; ++i) {
       const double As = A * s_of(i), v = C[i] - As;
       run = v < run ? v : run;
@@ -231,7 +195,7 @@ __global__ __launch_bounds__(TP_THREADS) void time_profile_kernel(const ProfileA
     const int rlo = M - hi, rhi = M - lo;   // this thread owns indices M - 1 - r for r in [lo, hi) = [rlo, rhi)
     double part = inf;
     for (int i = rhi - 1; i >= rlo; --i) { const double v = C[i] + Dd * s_of(i); part = v < part ? v : part; }
-    double run = block_exclusive(part, inf, MinOp(), redd);
+    double run = block_exclusive_scan<TP_WAVES>(part, inf, MinOp(), redd);
     for (int i = rhi - 1; i >= rlo; --i) {
       const double Ds = Dd * s_of(i), v = C[i] + Ds;
       run = v < run ? v : run;
@@ -270,11 +234,12 @@ __global__ __launch_bounds__(TP_THREADS) void time_profile_kernel(const ProfileA
   {
     u64 part = 0;
     for (int i = lo; i < hi; ++i) part += T[i];
-    u64 run = block_exclusive(part, (u64)0, SumOp(), redu);
+    u64 run = block_exclusive_scan<TP_WAVES>(part, (u64)0, Plus(), redu);
     for (int i = lo; i < hi; ++i) { const u64 q = T[i]; T[i] = run; run += q; }
   }
-  const u64 n_stops = block_total((u64)stops, redu);   // its barriers publish T
-  const bool out_of_range = block_total((u64)bad, redu) != 0;
+  // workgroup totals of small integer counts (exact in any order); their barriers publish T
+  const u64 n_stops = block_reduce<TP_WAVES>((u64)stops, (u64)0, Plus(), redu);
+  const bool out_of_range = block_reduce<TP_WAVES>((u64)bad, (u64)0, Plus(), redu) != 0;
 
   for (int i = tid; i < M; i += TP_THREADS) {
     double* o = prof + i * 4;
@@ -316,8 +281,7 @@ __global__ __launch_bounds__(TP_THREADS) void time_sample_kernel(const SampleArg
   for (int i = threadIdx.x; i < M; i += TP_THREADS) tc[i] = prof[i * 4 + 1];
   __syncthreads();
   if (k >= a.count) return;
-  const float* tr = a.traj + b * N * D;
-  auto pose = [&](int f, int d) { return f == 0 ? a.start[b * D + d] : (f == N + 1 ? a.goal[b * D + d] : tr[(long long)(f - 1) * D + d]); };
+  auto pose = [&](int f, int d) { return path_entry<D>(a.traj, a.start, a.goal, N, b, f * D + d); };
   float* o = a.states + (b * a.count + k) * (D + 1);
   const double t = a.t0 + (double)k * a.dt;
   const double t_end = tc[N + 1];

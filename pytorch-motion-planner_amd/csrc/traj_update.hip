@@ -8,6 +8,7 @@
 // Every waypoint's gradient is assembled in registers from its two adjacent segments (3-point stencil) and its
 // two adjacent collision samples, parked once in LDS for the banded H^-1 product, and the state
 // (traj, m, v, lambda, cm) is read once and written once: 92 B + 16 B (ONF record) per waypoint-step.
+#include "block_collectives.h"
 #include "common.h"
 
 namespace nfopp {
@@ -38,31 +39,6 @@ struct TrajUpdateArgs {
   float* terms;
   const unsigned char* active;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// sums K per-thread values over the workgroup (all threads get the result); scratch >= K * (threads / 64) floats
-template <int K>
-__device__ void block_sum(float (&v)[K], float* scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = wave_sum(v[k]);
-    if (lane == 0) scratch[wave * K + k] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += scratch[w * K + k];
-    v[k] = s;
-  }
-}
 
 struct SegOut {  // contribution of one segment to its head (q_{s+1}) and tail (q_s) waypoint, plus its loss terms
   float hx, hy, hth, tx, ty, tth;
@@ -131,7 +107,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
   float* CM = LAM + (N + 1);        // N collision multipliers
   float* COEF = CM + N;             // 2W+1 interior band coefficients (Toeplitz interior: one column for all)
   float* BND = COEF + (2 * W + 1);  // NB * (2W+1): the band columns of the waypoints near the two ends
-  float* scratch = BND + NB * (2 * W + 1);  // block reductions
+  float* scratch = BND + NB * (2 * W + 1);  // block reductions: NFOPP_NUM_TERMS per wave
   const nfopp_traj_hyper& hp = a.hp;
   const int tid = threadIdx.x;
 
@@ -190,7 +166,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
     // winding constant C = sum_s wrap(dtheta_s) - theta_goal + theta_start (constrained:124-125)
     float part[1] = {0.f};
     for (int s = tid; s <= N; s += TU_THREADS) part[0] += wrap_angle(Q[(s + 1) * 3 + 2] - Q[s * 3 + 2]);
-    block_sum<1>(part, scratch);
+    block_reduce<WAVES_FROM_BLOCKDIM>(part, 0.f, Plus(), scratch);
     const float C = part[0] - Q[(N + 1) * 3 + 2] + Q[2];
     const float* lam = LAM;
     const float* cm = CM;
@@ -324,7 +300,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
   }
 
   if (a.terms) {
-    block_sum<NFOPP_NUM_TERMS>(terms, scratch);
+    block_reduce<WAVES_FROM_BLOCKDIM>(terms, 0.f, Plus(), scratch);
     if (tid == 0) {
       float* o = a.terms + b * NFOPP_NUM_TERMS;
       const float total = terms[1] + hp.collision_weight * terms[2] + terms[3] +

@@ -244,6 +244,33 @@ def test_retired_trajectories_leave_the_onf_kernel():
     # (that the kernel time follows the live fraction is a timing property: tools/early_stop_timing.py, not this suite)
 
 
+@pytest.mark.parametrize("B", [1, 1024, 1025, 2049])
+def test_the_live_list_across_thread_and_wave_boundaries(B):
+    """The compaction behind the early stop is one workgroup of 1024 threads that scans the mask: one trajectory in all, one
+    per thread, one thread with a second one, more than two per thread.  The list itself (count, then the live indices in
+    rising order) and, as above, live rows bit-identical to an unmasked run and retired rows untouched."""
+    z = load_golden("traj_benchmr_n256.npz")
+    onf, cfg = gc.make_onf(z["cfg"], z["params"])
+    hp = orc.Hyper.from_npz(z)
+    s = gc.state_of(z, "s0_", reps=B)
+    s["traj"] = s["traj"] + np.linspace(0, 0.5, B, dtype=F32)[:, None, None] * np.asarray([1, -1, 0.01], F32)
+    mask = (np.random.default_rng(B).uniform(size=B) < 0.5).astype(np.uint8)
+    mask[0], mask[-1] = 0, 1           # (B = 1: the one trajectory is live)
+    ref = gc.engine_from_state(onf, s, hp)
+    eng = gc.engine_from_state(onf, s, hp)
+    eng.active = torch.tensor(mask, device="cuda")
+    for e in (ref, eng):
+        e.seed = 77
+        e.optimize_trajectory(want_terms=False)
+    torch.cuda.synchronize()
+    live = np.flatnonzero(mask)
+    got = eng._live.cpu().numpy()
+    assert got[0] == len(live) and np.array_equal(got[1:1 + len(live)], live)
+    for name in ("traj", "lam", "cm", "adam_m", "adam_v", "t", "onf_out"):
+        assert np.array_equal(getattr(eng, name).cpu().numpy()[live], getattr(ref, name).cpu().numpy()[live]), name
+    assert np.array_equal(eng.traj.cpu().numpy()[mask == 0], s["traj"][mask == 0])
+
+
 def test_continuous_learning_full_size_and_two_shard_gradient():
     """BASELINE configs[4] per GPU at its real size: 4096 trajectories x 512 waypoints, forward-only constraints,
     continuous ONF learning on 4096 x 621 = 2 543 616 device-sampled poses per step (bench-mr hyper block, disc map).

@@ -113,6 +113,30 @@ def test_batch_planner_learns_the_field_while_planning():
     assert logit[0] > 0 > logit[1] and logit[2] < 0
 
 
+@pytest.mark.parametrize("N", [129, 300])
+def test_path_length_beyond_one_wave_and_one_stride_vs_oracle(N):
+    """The length of nfopp_path_interpolate is a workgroup sum over the N + 1 segments: 130 of them end inside the third
+    wave, 301 are more than one per thread (the evaluation test below has 34).  The oracle and the bounds of that test.  They
+    hold here by count: either fp32 sum rounds at most 45 times (numpy: 8 chains of 38 terms, then 3 and a few levels; the
+    kernel: 2 per thread, 6 in the wave, 4 waves), every term is within 2 ulp, so the two differ by less than
+    60 * 2^-24 * length = 9e-6 for a length below 2.5."""
+    from nfopp import _lib
+    rng = np.random.default_rng(N)
+    B, D, sub = 5, 3, 2
+    starts = np.concatenate([rng.uniform(0.2, 0.6, (B, 1)), rng.uniform(0.3, 1.3, (B, 1)), rng.uniform(-3, 3, (B, 1))], 1).astype(F32)
+    goals = np.concatenate([rng.uniform(1.6, 2.0, (B, 1)), rng.uniform(0.3, 1.3, (B, 1)), rng.uniform(-3, 3, (B, 1))], 1).astype(F32)
+    traj = nfopp.straight_line_init(starts, goals, N) + rng.uniform(-2e-4, 2e-4, (B, N, D)).astype(F32)
+    m = (N + 1) * sub + 1
+    d_traj, d_start, d_goal = (torch.tensor(a, device="cuda") for a in (traj, starts, goals))
+    poses, length = torch.empty(B, m, D, device="cuda"), torch.empty(B, device="cuda")
+    _lib.check(_lib.load().nfopp_path_interpolate(_lib.ptr(d_traj), _lib.ptr(d_start), _lib.ptr(d_goal), B, N, D, sub,
+                                                  _lib.ptr(poses), _lib.ptr(length), _lib.stream_ptr()))
+    ref_poses, ref_len = orc.path_interpolate(traj, starts, goals, sub)
+    assert 1.0 < ref_len.min() and ref_len.max() < 2.5
+    assert max_abs(poses.cpu().numpy(), ref_poses) < 1e-6
+    assert max_abs(length.cpu().numpy(), ref_len) < 1e-5
+
+
 @pytest.mark.parametrize("D", [3, 2])
 def test_path_evaluation_and_early_stop_vs_oracle(D):
     z = load_golden("g1_onf.npz")

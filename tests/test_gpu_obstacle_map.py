@@ -70,6 +70,7 @@ COMPACTION_SHAPES = {
     "one_cell_more_than_a_chunk": (3, 683),                 # 2049 cells: GP_CHUNK + 1
     "exactly_one_chunk": (32, 64),                          # 2048 cells
     "more_chunks_than_one_scan_pass": (725, 725),           # 525625 cells: 257 chunks > GP_SCAN_PASS
+    "chunk_counts_end_inside_the_third_wave": (260, 1024),  # 266240 cells: 130 chunks, one per thread of the scan
 }
 
 
@@ -79,7 +80,8 @@ def test_point_cloud_across_compaction_boundaries(shape_name, fill):
     rows, cols = COMPACTION_SHAPES[shape_name]
     cells = rows * cols
     assert {"one_cell_more_than_a_chunk": cells == GP_CHUNK + 1, "exactly_one_chunk": cells == GP_CHUNK,
-            "more_chunks_than_one_scan_pass": -(-cells // GP_CHUNK) > GP_SCAN_PASS}[shape_name]
+            "more_chunks_than_one_scan_pass": -(-cells // GP_CHUNK) > GP_SCAN_PASS,
+            "chunk_counts_end_inside_the_third_wave": 128 < -(-cells // GP_CHUNK) <= 192}[shape_name]
     rng = np.random.default_rng(cells)
     if fill == "random":
         data = rng.uniform(0, 0.72, (rows, cols)).astype(F32)

@@ -378,6 +378,37 @@ def test_path_reduction_equals_the_restatement(box):
                                        threshold, 1, None, None, _lib.stream_ptr()) == -1
 
 
+@pytest.mark.parametrize("m", [2, 65, 257, 600])
+@pytest.mark.parametrize("box", [False, True])
+def test_path_reduction_across_wave_and_stride_boundaries(box, m):
+    """The same reduction with fewer poses than one wave, a count that ends inside the second wave, one pose beyond a stride
+    of the workgroup and more than two strides: the worst value tied in the middle and in the last segment, the only segment
+    that is not certified at the far end, only the last pose in collision."""
+    rng = np.random.default_rng(47 + m)
+    B, D = 4, 3 if box else 2
+    threshold = 0.25
+    poses = rng.uniform(-1, 1, (B, m, D)).astype(F32)
+    values = rng.uniform(0.3, 2.0, (B, m - 1)).astype(F32)
+    labels = np.zeros((B, m), F32)
+    values[1, m - 2], values[1, (m - 2) // 2] = 0.1, 0.1
+    values[2, m - 2] = 0.2
+    labels[3, m - 1] = 1.0
+    lib = _lib.load()
+    d_poses, d_values = dev(poses), dev(values)
+    got = dev(labels.reshape(-1))
+    status = torch.full((B,), 9, dtype=torch.uint8, device="cuda")
+    worst = torch.full((B, 2), -7.0, device="cuda")
+    _lib.check(lib.nfopp_path_swept_labels(_lib.ptr(d_poses), _lib.ptr(d_values), _lib.ptr(got), B, m, D, threshold,
+                                           int(box), _lib.ptr(status, torch.uint8), _lib.ptr(worst), _lib.stream_ptr()))
+    got, status, worst = got.cpu().numpy().reshape(B, m), status.cpu().numpy(), worst.cpu().numpy()
+    for p in range(B):
+        want, st, wv, wj = sr.path_reduction(poses[p], values[p], labels[p], threshold, box)
+        assert np.array_equal(got[p], want) and status[p] == st and worst[p, 1] == wj, p
+        assert np.array_equal(bits(worst[p, :1]), bits(np.array([wv], F32)))
+    assert list(status) == ([0, 2, 2, 1] if box else [0, 1, 1, 1])
+    assert worst[1, 1] == (m - 2) // 2 and worst[2, 1] == m - 2
+
+
 # ---- 9 - 12: the planner and the wall ------------------------------------------------------------------------------------
 RADIUS = 0.3
 SMALL_BOX = (-0.25, 0.25, -0.15, 0.15)            # reach 0.292: the poses, 1 apart, are inside the certificate's domain

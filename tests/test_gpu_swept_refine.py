@@ -302,6 +302,38 @@ def test_path_reduction_equals_the_restatement():
     assert np.array_equal(again.cpu().numpy().reshape(B, m), got)
 
 
+@pytest.mark.parametrize("m", [2, 65, 257, 600])
+def test_path_reduction_across_wave_and_stride_boundaries(m):
+    """The same reduction with fewer poses than one wave, a count that ends inside the second wave, one pose beyond a stride
+    of the workgroup and more than two strides: the only segment that is not free at the far end, a hit there behind an
+    undecided segment in the middle, only the last pose in collision, a random mix."""
+    rng = np.random.default_rng(53 + m)
+    B = 5
+    seg = np.zeros((B, m - 1), np.uint8)
+    s = np.full((B, m - 1), -1.0, F32)
+    labels = np.zeros((B, m), F32)
+    seg[1, m - 2] = UNDECIDED
+    seg[2, (m - 2) // 2] = UNDECIDED
+    seg[2, m - 2], s[2, m - 2] = HIT, 0.375
+    labels[3, m - 1] = 1.0
+    seg[4] = rng.integers(0, 3, m - 1)
+    s[4][seg[4] == HIT] = rng.integers(0, 257, (seg[4] == HIT).sum()) / F32(256)
+    lib = _lib.load()
+    d_seg, d_s = dev(seg, np.uint8), dev(s)
+    got = dev(labels.reshape(-1))
+    status = torch.full((B,), 9, dtype=torch.uint8, device="cuda")
+    first = torch.full((B, 2), -7.0, device="cuda")
+    _lib.check(lib.nfopp_path_refined_labels(_lib.ptr(d_seg, torch.uint8), _lib.ptr(d_s), _lib.ptr(got), B, m,
+                                             _lib.ptr(status, torch.uint8), _lib.ptr(first), _lib.stream_ptr()))
+    got, status, first = got.cpu().numpy().reshape(B, m), status.cpu().numpy(), first.cpu().numpy()
+    for p in range(B):
+        want, st, fs = rr.path_reduction(seg[p], s[p], labels[p])
+        assert np.array_equal(got[p], want) and status[p] == st and tuple(first[p]) == fs, p
+    assert status.tolist()[:4] == [0, 2, 1, 1]
+    assert first[0].tolist() == [-1, -1] and first[1].tolist() == [m - 2, -1] and first[3].tolist() == [-1, -1]
+    assert first[2].tolist() == ([0, 0.375] if m == 2 else [(m - 2) // 2, -1])
+
+
 # ---- the planner and the wall ------------------------------------------------------------------------------------------
 def wall_planner():
     """DESIGN 14's wall with the box robot: B = 4 straight paths of N = 8 waypoints, 10 poses 1 apart along x from -4.5 to 4.5
