@@ -836,6 +836,62 @@ int nfopp_track_conflicts(const float* tracks_a_dev, int64_t ba, int32_t stride_
                           double* pair_gap_dev, double* pair_first_dev, void* workspace_dev, size_t workspace_bytes,
                           void* stream);
 
+/* ---- prioritised start-delay scheduling of a fleet (csrc/fleet_schedule.hip), additive under ABI 6 ---------------------------
+ * nfopp_track_conflicts tells which robots of a fleet are in conflict.  These two entries are the outer step: every robot
+ * keeps its path and only WHEN it leaves changes.  In priority order each robot takes the smallest start delay, in steps of
+ * the common time grid, that keeps it clear of every robot scheduled before it and of every predicted obstacle.  Predicates,
+ * integer ORs and a count-trailing-zeros: no atomics, the same bits run after run, and the device is compared bit for bit
+ * with the numpy restatement in tests/fleet_schedule_ref.py.
+ *
+ * Tracks.  tracks_dev [b, k, stride] fp32 on a common grid, x, y the first two floats of a row, stride >= 2 -- what
+ *   nfopp_path_time_sample writes.  There are D = max_delay + 1 candidate delays 0 .. max_delay grid steps,
+ *   0 <= max_delay <= NFOPP_SCHEDULE_MAX_DELAY.
+ * A delayed robot.  Robot i delayed by q is at track_i[clamp(h - q, 0, k - 1)] at instant h: it waits at its first sample and
+ *   stays parked at its last.  The caller chooses k so that the last sample is the goal.
+ * Pair predicate C_ij(r) for a relative shift r = q_i - q_j in [-max_delay, max_delay]: the conflict predicate of
+ *   nfopp_track_conflicts -- some m_n < R2_ij (strict), the last-instant term included, R_ij = (r_i + r_j) + margin, the same
+ *   float64 arithmetic -- applied to robot i delayed by max(r, 0) and robot j delayed by max(-r, 0), over k + |r| instants.
+ *   Later instants add nothing: both robots are parked there and the last-instant term already holds that value, so the
+ *   definition is independent of any horizon.  One of the two robots is never delayed: the assignment uses bit d - q_j for
+ *   robot i at delay d against robot j at delay q_j, and in absolute time that pair only has min(d, q_j) more intervals in
+ *   front, in which both wait at |d_0|^2, the c interval 0 starts from -- the predicate depends on the two delays through their
+ *   difference
+ *   alone.  By the evenness in the sign of d stated above, C_ji(-r) has the same bit as C_ij(r).
+ * pair_mask_dev [b, b, 2] uint64, both triangles: the mask of a pair is 128 bits in two little-endian words, bit
+ *   r + max_delay is C_ij(r), unused high bits are 0.  The diagonal is 0, a pair with a bad robot is 0, and mask_ji is mask_ij
+ *   with its 2 * max_delay + 1 bits reversed (the kernel evaluates the upper triangle only and mirrors it).
+ * Obstacles (optional: obstacles_dev null or m == 0).  obstacles_dev [m, k + max_delay, obstacle_stride] fp32 with
+ *   obstacle_radius_dev [m] (null = 0), in absolute time, never shifted.  Bit d of base_mask_dev[i] is the same predicate for
+ *   robot i delayed by d against obstacle j over all k + max_delay instants, ORed over the good obstacles j.
+ * Bad tracks.  A robot or obstacle with a non-finite coordinate or radius is bad.  A bad obstacle is skipped by everyone.  A
+ *   bad robot has bad_dev[i] = 1 (else 0), base 0, gets NFOPP_SCHEDULE_BAD_TRACK and delay -1, and is invisible to the others.
+ * Assignment (nfopp_fleet_assign_delays, one workgroup).  order_dev [b] int32 (null: 0 .. b - 1) is visited front to back.  An
+ *   entry out of range, or a robot already visited, is skipped (any int32 content is safe).  A robot never visited ends with
+ *   NFOPP_SCHEDULE_NOT_ORDERED, delay -1, forbidden 0.  For robot i
+ *     forbidden_i = (base_i | OR over the robots j scheduled before it of (mask_ij >> (max_delay - q_j))) & (2^D - 1),
+ *   q_i = its lowest clear bit, status 0.  No clear bit: NFOPP_SCHEDULE_UNRESOLVED, delay -1; the robot is not on the floor for
+ *   those after it and the schedule promises nothing about it (a caller can pass it back as a parked obstacle).
+ *   delay_dev [b] int32, status_dev [b] int32, forbidden_dev [b] uint64 (may be null).
+ * The two-step form lets a caller retry other priority orders -- the standard cure for an unresolved robot -- on the same
+ *   masks at the cost of the assignment pass alone.
+ * workspace_dev: nfopp_fleet_shift_masks_workspace_bytes(b, m) bytes (0 without obstacles), rewritten by every call.
+ * Everything runs on `stream`; nothing synchronises.  Argument errors: a negative batch size or one above 2^31 - 1, max_delay
+ *   outside 0 .. 63, k < 1 or too large for an index, a stride < 2, margin not finite, a null pointer where one is read or
+ *   written, more tiles of 8 x 8 pairs than a grid holds (2^31 - 1), a workspace that is null or too small, more robots than
+ *   the assignment pass can keep in one workgroup's LDS (one byte each in 160 KiB).  b == 0 returns 0 with null pointers. */
+#define NFOPP_SCHEDULE_MAX_DELAY 63
+#define NFOPP_SCHEDULE_BAD_TRACK 1
+#define NFOPP_SCHEDULE_UNRESOLVED 2
+#define NFOPP_SCHEDULE_NOT_ORDERED 3
+size_t nfopp_fleet_shift_masks_workspace_bytes(int64_t b, int64_t m);
+int nfopp_fleet_shift_masks(const float* tracks_dev, int64_t b, int32_t stride, int32_t k, const float* radius_dev,
+                            double margin, int32_t max_delay, const float* obstacles_dev, int64_t m, int32_t obstacle_stride,
+                            const float* obstacle_radius_dev, uint64_t* pair_mask_dev, uint64_t* base_mask_dev,
+                            int32_t* bad_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int nfopp_fleet_assign_delays(const uint64_t* pair_mask_dev, const uint64_t* base_mask_dev, const int32_t* bad_dev,
+                              const int32_t* order_dev, int64_t b, int32_t max_delay, int32_t* delay_dev, int32_t* status_dev,
+                              uint64_t* forbidden_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,12 @@ struct Plus {
   }
 };
 
+// a | b on integers: the union of bit sets, which no order can change
+struct BitOr {
+  template <class T>
+  __device__ __forceinline__ T operator()(T a, T b) const { return a | b; }
+};
+
 // ---- what moves between lanes: scalars, and (value, index) pairs for "the extremum and where it is" -----------------
 // The order on pairs (ties, NaN, "no candidate") is the caller's op and stays beside its kernel.
 template <class V>

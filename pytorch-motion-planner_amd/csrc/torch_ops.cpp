@@ -422,6 +422,64 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_
   return std::make_tuple(summary, summary_b, pair_gap, pair_first);
 }
 
+// the shift masks of a fleet (nfopp_fleet_shift_masks): tracks [B, K, S], radius [B] fp32 or None (0), obstacles
+// [M, K + max_delay, So] or None with obstacle_radius [M] or None -> (pair [B, B, 2], base [B]) int64 holding the uint64 words,
+// bad [B] int32
+std::tuple<Tensor, Tensor, Tensor> fleet_shift_masks(const Tensor& tracks, int64_t max_delay, const OptTensor& radius, double margin,
+                                                     const OptTensor& obstacles, const OptTensor& obstacle_radius) {
+  check_tensor(tracks, "tracks");
+  TORCH_CHECK(tracks.dim() == 3 && tracks.size(1) >= 1 && tracks.size(2) >= 2, "nfopp: tracks must be [B, K, >= 2] with K >= 1");
+  TORCH_CHECK(max_delay >= 0 && max_delay <= NFOPP_SCHEDULE_MAX_DELAY, "nfopp: max_delay must be in 0 .. ", NFOPP_SCHEDULE_MAX_DELAY);
+  const int64_t b = tracks.size(0), k = tracks.size(1);
+  TORCH_CHECK(k <= 0x7fffffffLL && tracks.size(2) <= 0x7fffffffLL, "nfopp: tracks must have fewer than 2^31 instants and floats per row");
+  if (radius.has_value()) need(tracks, *radius, "radius", {b});
+  int64_t m = 0;
+  if (obstacles.has_value()) {
+    check_tensor(*obstacles, "obstacles");
+    same_device(tracks, *obstacles, "obstacles");
+    TORCH_CHECK(obstacles->dim() == 3 && obstacles->size(1) == k + max_delay && obstacles->size(2) >= 2 &&
+                    obstacles->size(2) <= 0x7fffffffLL,
+                "nfopp: obstacles must be [M, K + max_delay, >= 2] = [M, ", k + max_delay, ", >= 2]");
+    m = obstacles->size(0);
+    if (obstacle_radius.has_value()) need(tracks, *obstacle_radius, "obstacle_radius", {m});
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks.device());
+  const auto i64 = tracks.options().dtype(at::kLong);
+  Tensor pair = at::empty({b, b, 2}, i64), base = at::empty({b}, i64), bad = at::empty({b}, tracks.options().dtype(at::kInt));
+  const size_t bytes = nfopp_fleet_shift_masks_workspace_bytes(b, m);
+  Tensor workspace = at::empty({(int64_t)bytes}, tracks.options().dtype(at::kByte));
+  auto u64 = [](Tensor& t) { return t.numel() ? reinterpret_cast<uint64_t*>(t.data_ptr<int64_t>()) : nullptr; };
+  check_status(nfopp_fleet_shift_masks(b ? tracks.data_ptr<float>() : nullptr, b, (int32_t)tracks.size(2), (int32_t)k, opt_ptr<float>(radius),
+                                       margin, (int32_t)max_delay, m ? obstacles->data_ptr<float>() : nullptr, m,
+                                       m ? (int32_t)obstacles->size(2) : 2, m ? opt_ptr<float>(obstacle_radius) : nullptr, u64(pair),
+                                       u64(base), b ? bad.data_ptr<int32_t>() : nullptr, bytes ? workspace.data_ptr() : nullptr, bytes,
+                                       stream_of(tracks)));
+  return std::make_tuple(pair, base, bad);
+}
+
+// the assignment pass (nfopp_fleet_assign_delays) on masks as written above; order [B] int32 or None (0 .. B - 1)
+// -> (delay [B] int32, status [B] int32, forbidden [B] int64 holding the uint64 word)
+std::tuple<Tensor, Tensor, Tensor> fleet_assign_delays(const Tensor& pair, const Tensor& base, const Tensor& bad, const OptTensor& order,
+                                                       int64_t max_delay) {
+  check_tensor(pair, "pair", at::kLong);
+  TORCH_CHECK(pair.dim() == 3 && pair.size(0) == pair.size(1) && pair.size(2) == 2, "nfopp: pair must be [B, B, 2]");
+  TORCH_CHECK(max_delay >= 0 && max_delay <= NFOPP_SCHEDULE_MAX_DELAY, "nfopp: max_delay must be in 0 .. ", NFOPP_SCHEDULE_MAX_DELAY);
+  const int64_t b = pair.size(0);
+  need(pair, base, "base", {b}, at::kLong);
+  need(pair, bad, "bad", {b}, at::kInt);
+  if (order.has_value()) need(pair, *order, "order", {b}, at::kInt);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(pair.device());
+  const auto i32 = pair.options().dtype(at::kInt);
+  Tensor delay = at::empty({b}, i32), status = at::empty({b}, i32), forbidden = at::empty({b}, pair.options());
+  if (b > 0)
+    check_status(nfopp_fleet_assign_delays(reinterpret_cast<const uint64_t*>(pair.data_ptr<int64_t>()),
+                                           reinterpret_cast<const uint64_t*>(base.data_ptr<int64_t>()), bad.data_ptr<int32_t>(),
+                                           opt_ptr<int32_t>(order), b, (int32_t)max_delay, delay.data_ptr<int32_t>(),
+                                           status.data_ptr<int32_t>(), reinterpret_cast<uint64_t*>(forbidden.data_ptr<int64_t>()),
+                                           stream_of(pair)));
+  return std::make_tuple(delay, status, forbidden);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nfopp, lib) {
@@ -457,6 +515,9 @@ TORCH_LIBRARY(nfopp, lib) {
           "float dt, int count) -> (Tensor, Tensor)");
   lib.def("track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor? radius_a, Tensor? radius_b, float margin, "
           "bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor)");
+  lib.def("fleet_shift_masks(Tensor tracks, int max_delay, Tensor? radius, float margin, Tensor? obstacles, Tensor? obstacle_radius) -> "
+          "(Tensor, Tensor, Tensor)");
+  lib.def("fleet_assign_delays(Tensor pair, Tensor base, Tensor bad, Tensor? order, int max_delay) -> (Tensor, Tensor, Tensor)");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -475,4 +536,6 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("path_time_profile", &path_time_profile);
   lib.impl("path_time_sample", &path_time_sample);
   lib.impl("track_conflicts", &track_conflicts);
+  lib.impl("fleet_shift_masks", &fleet_shift_masks);
+  lib.impl("fleet_assign_delays", &fleet_assign_delays);
 }

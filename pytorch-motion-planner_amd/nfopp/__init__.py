@@ -8,6 +8,8 @@ from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
 from .conflicts import (CONFLICT_BAD_TRACK, CONFLICT_COUNT, CONFLICT_FIRST_PARTNER, CONFLICT_FIRST_TIME, CONFLICT_MIN_GAP,
                         CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_NO_PARTNER, CONFLICT_STATUS, TrackConflicts,
                         constant_velocity_tracks, track_conflicts)
+from .schedule import (SCHEDULE_BAD_TRACK, SCHEDULE_MAX_DELAY, SCHEDULE_NOT_ORDERED, SCHEDULE_OK, SCHEDULE_UNRESOLVED, FleetMasks,
+                       FleetSchedule, delay_tracks, fleet_shift_masks, schedule_delays)
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
 from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fields, grid_search_init, grid_search_paths,
                           margin_cells2, seed_polylines, seed_trajectories, shorten_paths)
@@ -41,4 +43,6 @@ __all__ = [
     "TrackConflicts", "track_conflicts", "constant_velocity_tracks", "CONFLICT_MIN_GAP", "CONFLICT_MIN_PARTNER",
     "CONFLICT_MIN_TIME", "CONFLICT_FIRST_TIME", "CONFLICT_FIRST_PARTNER", "CONFLICT_COUNT", "CONFLICT_STATUS",
     "CONFLICT_BAD_TRACK", "CONFLICT_NO_PARTNER",
+    "FleetMasks", "FleetSchedule", "fleet_shift_masks", "schedule_delays", "delay_tracks", "SCHEDULE_OK", "SCHEDULE_BAD_TRACK",
+    "SCHEDULE_UNRESOLVED", "SCHEDULE_NOT_ORDERED", "SCHEDULE_MAX_DELAY",
 ]

@@ -474,3 +474,14 @@ class BatchPlanner(object):
             return fleet
         return fleet, timed.conflicts(dt, count, other=obstacles, radius=radius, other_radius=obstacle_radius, margin=margin,
                                       other_v_max=obstacle_v_max, want_pairs=want_pairs)
+
+    def fleet_schedule(self, limits, dt, count, radius, max_delay, margin="chord", order=None, best=False, obstacles=None,
+                       obstacle_radius=None, obstacle_v_max=None, v_start=None, v_goal=None):
+        """The B paths as B robots on one floor that may leave late: time-parametrise under `limits`, sample at k * dt
+        (k < count) and give every robot, in priority `order` (None: robot 0 first; "longest_first"; or [B] indices), the
+        smallest start delay of 0 .. max_delay grid steps that keeps it clear of the robots scheduled before it and of
+        `obstacles` -- a `TimedPaths`, or predicted tracks [M, count + max_delay, >= 2] (then the chord margin needs
+        `obstacle_v_max`) -> nfopp.FleetSchedule.  Nothing here synchronises with device-tensor arguments."""
+        timed = self.timed_paths(limits, v_start=v_start, v_goal=v_goal, best=best)
+        return timed.schedule(dt, count, max_delay, radius, margin=margin, order=order, other=obstacles,
+                              other_radius=obstacle_radius, other_v_max=obstacle_v_max)

@@ -115,6 +115,42 @@ class TimedPaths(object):
         return track_conflicts(self.sample(dt, count, t0=t0), tracks_b, dt=dt, t0=t0, radius_a=radius, radius_b=other_radius,
                                margin=margin, want_pairs=want_pairs)
 
+    def schedule(self, dt, count, max_delay, radius, margin="chord", order=None, other=None, other_radius=None, other_v_max=None):
+        """The B timed paths as B robots that may leave late: sampled at k * dt (k < count), every robot gets, in priority
+        `order`, the smallest start delay of 0 .. max_delay grid steps that keeps it clear of the robots scheduled before it
+        (`nfopp.schedule_delays`) -> `nfopp.FleetSchedule` with `delay_seconds` and `complete`.  `order`: None (robot 0
+        first), "longest_first" (a stable device argsort of the total time, descending), or [B] indices.  `other`: a
+        `TimedPaths`, sampled at count + max_delay instants, or a tracks tensor [M, count + max_delay, >= 2] of predicted
+        obstacles in absolute time.  `margin="chord"` is (v_max + the larger of v_max and the other side's v_max) * dt / 2:
+        one margin serves robot pairs and obstacle pairs alike; for a tracks tensor it needs `other_v_max`.  A robot is
+        `complete` when its total time fits the sampled instants, so that its last sample is its goal."""
+        from .conflicts import chord_margin
+        from .schedule import fleet_shift_masks
+        count, max_delay = int(count), int(max_delay)
+        obstacles, vb = None, self.limits.v_max
+        if isinstance(other, TimedPaths):
+            obstacles, vb = other.sample(dt, count + max_delay), max(vb, other.limits.v_max)
+        elif other is not None:
+            obstacles, vb = other, None if other_v_max is None else max(vb, float(other_v_max))
+        if isinstance(margin, str):
+            if margin != "chord":
+                raise ValueError("margin must be a number or \"chord\", got %r" % (margin,))
+            if vb is None:
+                raise ValueError("margin=\"chord\" against a tracks tensor needs other_v_max, the top speed of those tracks")
+            margin = chord_margin(self.limits.v_max, vb, dt)
+        total = self.summary[:, TIME_SUMMARY_TIME]
+        if isinstance(order, str):
+            if order != "longest_first":
+                raise ValueError("order must be None, \"longest_first\" or [B] indices, got %r" % (order,))
+            order = torch.argsort(total, descending=True, stable=True)
+        masks = fleet_shift_masks(self.sample(dt, count), max_delay=max_delay, radius=radius, margin=margin, obstacles=obstacles,
+                                  obstacle_radius=other_radius)
+        out = masks.assign(order)
+        step = torch.tensor(float(dt), dtype=torch.float64, device=out.delay.device)
+        out.delay_seconds = torch.where(out.delay >= 0, out.delay.double() * step, torch.full_like(step, float("nan")))
+        out.complete = total <= (count - 1) * float(dt)
+        return out
+
 
 def time_parametrize(traj, start, goal, limits, v_start=None, v_goal=None):
     """traj [B, N, D], start / goal [B, D]: fp32 HIP tensors (D = 2 or 3).  `v_start` / `v_goal`: the speed the robot has
