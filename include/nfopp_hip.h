@@ -850,7 +850,8 @@ int nfopp_track_conflicts(const float* tracks_a_dev, int64_t ba, int32_t stride_
  *   stays parked at its last.  The caller chooses k so that the last sample is the goal.
  * Pair predicate C_ij(r) for a relative shift r = q_i - q_j in [-max_delay, max_delay]: the conflict predicate of
  *   nfopp_track_conflicts -- some m_n < R2_ij (strict), the last-instant term included, R_ij = (r_i + r_j) + margin, the same
- *   float64 arithmetic -- applied to robot i delayed by max(r, 0) and robot j delayed by max(-r, 0), over k + |r| instants.
+ *   float64 arithmetic (one set of device functions, csrc/track_pairs.h, which both kernel files call and which also owns
+ *   the map from a workgroup to its tile of pairs) -- applied to robot i delayed by max(r, 0) and robot j delayed by max(-r, 0), over k + |r| instants.
  *   Later instants add nothing: both robots are parked there and the last-instant term already holds that value, so the
  *   definition is independent of any horizon.  One of the two robots is never delayed: the assignment uses bit d - q_j for
  *   robot i at delay d against robot j at delay q_j, and in absolute time that pair only has min(d, q_j) more intervals in

@@ -17,8 +17,8 @@
 //  A delayed robot.  Robot i delayed by q is at track_i[clamp(h - q, 0, K - 1)] at instant h: it waits at its first sample and
 //    stays parked at its last.
 //  Pair predicate C_ij(r), r = q_i - q_j in [-max_delay, max_delay]: the conflict predicate of track_conflict.hip -- some
-//    m_k < R2_ij (strict), over the intervals k = 0 .. n - 2 and the last-instant term m = |d_{n-1}|^2, the same float64
-//    arithmetic, R_ij = (r_i + r_j) + margin, R2_ij = R_ij * R_ij -- on robot i delayed by max(r, 0) and robot j delayed by
+//    m_k < R2_ij (strict), over the intervals k = 0 .. n - 2 and the last-instant term m = |d_{n-1}|^2, the predicate of
+//    track_pairs.h, R_ij = (r_i + r_j) + margin, R2_ij = R_ij * R_ij -- on robot i delayed by max(r, 0) and robot j delayed by
 //    max(-r, 0), over n = K + |r| instants.  Later instants add nothing: both robots are parked there, every further interval has
 //    a == 0 and m = c = the last-instant term.  So the predicate does not depend on a horizon.  One of the two robots is never
 //    delayed: the assignment uses bit d - q_j for robot i at delay d against robot j at delay q_j, and in absolute time that
@@ -39,6 +39,7 @@
 // Predicates, integer ORs and a count-trailing-zeros: no atomics, nothing depends on an order, two runs give the same bits.
 #include "block_collectives.h"
 #include "common.h"
+#include "track_pairs.h"
 
 #pragma clang fp contract(off)
 
@@ -70,8 +71,6 @@ struct ShiftMaskArgs {
   unsigned long long* part;              // obstacles: [ba, ntb]
   long long nta, ntb;
 };
-
-__device__ __forceinline__ bool finite32(float v) { return fabsf(v) < __builtin_inff(); }
 
 // flags[t] <- 1 when track t has a non-finite x or y at any instant, or a non-finite radius; one wave per track
 __global__ __launch_bounds__(FS_THREADS) void fleet_bad_kernel(const float* tracks, const float* radius, long long n, int k, int stride,
@@ -107,19 +106,8 @@ __global__ __launch_bounds__(FS_THREADS) void fleet_shift_mask_kernel(const Shif
   const int tid = threadIdx.x, lane = tid & 63;
 
   long long ta, tb;
-  if (p.self) {   // tile `t` of the upper triangle, row by row: row r starts at r * n - r * (r - 1) / 2
-    const long long n = p.nta, t = blockIdx.x, q = 2 * n + 1;
-    long long r = (long long)(((double)q - sqrt((double)(q * q - 8 * t))) * 0.5);
-    if (r < 0) r = 0;
-    if (r > n - 1) r = n - 1;
-    while (r > 0 && r * n - r * (r - 1) / 2 > t) --r;
-    while (r + 1 < n && (r + 1) * n - (r + 1) * r / 2 <= t) ++r;
-    ta = r;
-    tb = r + (t - (r * n - r * (r - 1) / 2));
-  } else {
-    ta = blockIdx.x / p.ntb;
-    tb = blockIdx.x % p.ntb;
-  }
+  if (p.self) upper_triangle_tile(blockIdx.x, p.nta, &ta, &tb);
+  else pair_tile(blockIdx.x, p.ntb, &ta, &tb);
   const long long a0 = ta * FS_TILE, b0 = tb * FS_TILE;
   const long long row_a = (long long)p.k * p.stride_a, row_b = (long long)p.kb * p.stride_b;
 
@@ -151,7 +139,8 @@ __global__ __launch_bounds__(FS_THREADS) void fleet_shift_mask_kernel(const Shif
     const bool on = sidx < n_shift && !sBad[li] && !sBad[FS_TILE + lj] && (!diagonal || li < lj);
     if (!on) continue;
     live |= 1u << s;
-    const double R = (sRad[li] + sRad[FS_TILE + lj]) + p.margin, R2 = R * R;
+    double R, R2;
+    pair_radius(sRad[li], sRad[FS_TILE + lj], p.margin, &R, &R2);
     const double x = (double)sLast[li].x - (double)sLast[FS_TILE + lj].x, y = (double)sLast[li].y - (double)sLast[FS_TILE + lj].y;
     const double m = x * x + y * y;
     if (m < R2) done |= 1u << s;
@@ -185,7 +174,8 @@ __global__ __launch_bounds__(FS_THREADS) void fleet_shift_mask_kernel(const Shif
       const int n_inst = p.self ? p.k + (r < 0 ? -r : r) : h_all;
       const int lo = h0 > 1 ? h0 : 1, hi = min(h0 + FS_CHUNK - 1, n_inst - 1);   // intervals h - 1 -> h of this trip
       if (lo > hi) continue;
-      const double R = (sRad[li] + sRad[FS_TILE + lj]) + p.margin, R2 = R * R;
+      double R, R2;
+      pair_radius(sRad[li], sRad[FS_TILE + lj], p.margin, &R, &R2);
       const float2* rowA = sA + li * FS_WINDOW + (lo - 1 - da - wbase);
       const float2* rowB = sB + lj * FS_WINDOW + (lo - 1 - db - wbase);
       float2 pa = rowA[0], pb = rowB[0];
@@ -196,16 +186,7 @@ __global__ __launch_bounds__(FS_THREADS) void fleet_shift_mask_kernel(const Shif
         pa = rowA[n]; pb = rowB[n];
         const double d1x = (double)pa.x - (double)pb.x, d1y = (double)pa.y - (double)pb.y;
         const double e = d1x * d1x + d1y * d1y;
-        const double wx = d1x - x0, wy = d1y - y0;
-        const double a = wx * wx + wy * wy, b = x0 * wx + y0 * wy;
-        double m;
-        if (a == 0.0 || b >= 0.0) m = cc;
-        else if (-b >= a) m = e;
-        else {
-          const double sc = (-b) / a;
-          const double px = x0 + sc * wx, py = y0 + sc * wy;
-          m = px * px + py * py;
-        }
+        const double m = closest_approach(x0, y0, cc, d1x, d1y, e).m;
         if (m < R2) { hit = true; break; }   // an OR: the remaining intervals cannot change the bit
         x0 = d1x; y0 = d1y; cc = e;          // d1 of this interval is d0 of the next
       }

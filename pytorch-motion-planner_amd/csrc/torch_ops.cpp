@@ -378,26 +378,34 @@ std::tuple<Tensor, Tensor> path_time_sample(const Tensor& traj, const Tensor& st
   return std::make_tuple(states, segment);
 }
 
+// a tracks tensor of the conflict check and the scheduler: [B, K, S] fp32 with K >= 1 instants and S >= 2 floats per row, K
+// and S an int32 -> (B, K, S)
+std::tuple<int64_t, int64_t, int32_t> check_tracks(const Tensor& t, const char* name) {
+  check_tensor(t, name);
+  TORCH_CHECK(t.dim() == 3 && t.size(1) >= 1 && t.size(2) >= 2, "nfopp: ", name, " must be [B, K, >= 2] with K >= 1");
+  TORCH_CHECK(t.size(1) <= 0x7fffffffLL && t.size(2) <= 0x7fffffffLL, "nfopp: ", name,
+              " must have fewer than 2^31 instants and floats per row");
+  return std::make_tuple(t.size(0), t.size(1), (int32_t)t.size(2));
+}
+// the workspace of such an op: `bytes` bytes on the device of `like`
+Tensor byte_workspace(const Tensor& like, size_t bytes) { return at::empty({(int64_t)bytes}, like.options().dtype(at::kByte)); }
+
 // conflicts between timed tracks (nfopp_track_conflicts): tracks_a [Ba, K, Sa], tracks_b [Bb, K, Sb] or None (self mode), radii
 // [Ba] / [Bb] fp32 or None (0) -> (summary [Ba, 7], summary_b [Bb, 7], pair_gap, pair_first [Ba, Bb]) float64; summary_b is
 // empty in self mode, the pair matrices are empty without want_pairs.
 std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_a, const OptTensor& tracks_b, double dt, double t0,
                                                            const OptTensor& radius_a, const OptTensor& radius_b, double margin,
                                                            bool want_pairs) {
-  check_tensor(tracks_a, "tracks_a");
-  TORCH_CHECK(tracks_a.dim() == 3 && tracks_a.size(1) >= 1 && tracks_a.size(2) >= 2, "nfopp: tracks_a must be [B, K, >= 2] with K >= 1");
-  const int64_t ba = tracks_a.size(0), k = tracks_a.size(1);
+  const auto [ba, k, stride_a] = check_tracks(tracks_a, "tracks_a");
   const bool self = !tracks_b.has_value();
   int64_t bb = ba;
+  int32_t stride_b = 2;
   if (!self) {
-    check_tensor(*tracks_b, "tracks_b");
+    int64_t kb;
+    std::tie(bb, kb, stride_b) = check_tracks(*tracks_b, "tracks_b");
     same_device(tracks_a, *tracks_b, "tracks_b");
-    TORCH_CHECK(tracks_b->dim() == 3 && tracks_b->size(1) == k && tracks_b->size(2) >= 2,
-                "nfopp: tracks_b must be [Bb, K, >= 2] with the K of tracks_a (", k, ")");
-    bb = tracks_b->size(0);
+    TORCH_CHECK(kb == k, "nfopp: tracks_b must be [Bb, K, >= 2] with the K of tracks_a (", k, ")");
   }
-  TORCH_CHECK(k <= 0x7fffffffLL && tracks_a.size(2) <= 0x7fffffffLL && (self || tracks_b->size(2) <= 0x7fffffffLL),
-              "nfopp: tracks must have fewer than 2^31 instants and floats per row");
   if (radius_a.has_value()) need(tracks_a, *radius_a, "radius_a", {ba});
   if (!self && radius_b.has_value()) need(tracks_a, *radius_b, "radius_b", {bb});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks_a.device());
@@ -406,13 +414,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_
   Tensor summary_b = at::empty({self ? 0 : bb, NFOPP_NUM_CONFLICT_SLOTS}, f64);
   Tensor pair_gap = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, f64), pair_first = at::empty_like(pair_gap);
   const size_t bytes = nfopp_track_conflicts_workspace_bytes(ba, self ? 0 : bb, (int32_t)k);
-  Tensor workspace = at::empty({(int64_t)bytes}, tracks_a.options().dtype(at::kByte));
+  Tensor workspace = byte_workspace(tracks_a, bytes);
   auto dptr = [](Tensor& t) { return t.numel() ? t.data_ptr<double>() : nullptr; };
   // a set of no obstacles still needs a non-null tracks_b pointer (null selects self mode); it is never read
   const float* b_ptr = self ? nullptr : (bb > 0 ? tracks_b->data_ptr<float>() : tracks_a.data_ptr<float>());
-  check_status(nfopp_track_conflicts(ba ? tracks_a.data_ptr<float>() : nullptr, ba, (int32_t)tracks_a.size(2), ba ? b_ptr : nullptr, bb,
-                                     self ? 2 : (int32_t)tracks_b->size(2), (int32_t)k, t0, dt, opt_ptr<float>(radius_a),
-                                     self ? nullptr : opt_ptr<float>(radius_b), margin, dptr(summary), dptr(summary_b),
+  check_status(nfopp_track_conflicts(ba ? tracks_a.data_ptr<float>() : nullptr, ba, stride_a, ba ? b_ptr : nullptr, bb, stride_b,
+                                     (int32_t)k, t0, dt, opt_ptr<float>(radius_a), self ? nullptr : opt_ptr<float>(radius_b), margin, dptr(summary), dptr(summary_b),
                                      dptr(pair_gap), dptr(pair_first), bytes ? workspace.data_ptr() : nullptr, bytes,
                                      stream_of(tracks_a)));
   if (ba == 0 && summary_b.numel()) {   // the entry writes nothing for an empty set A: every obstacle is without a partner
@@ -427,31 +434,27 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_
 // bad [B] int32
 std::tuple<Tensor, Tensor, Tensor> fleet_shift_masks(const Tensor& tracks, int64_t max_delay, const OptTensor& radius, double margin,
                                                      const OptTensor& obstacles, const OptTensor& obstacle_radius) {
-  check_tensor(tracks, "tracks");
-  TORCH_CHECK(tracks.dim() == 3 && tracks.size(1) >= 1 && tracks.size(2) >= 2, "nfopp: tracks must be [B, K, >= 2] with K >= 1");
+  const auto [b, k, stride] = check_tracks(tracks, "tracks");
   TORCH_CHECK(max_delay >= 0 && max_delay <= NFOPP_SCHEDULE_MAX_DELAY, "nfopp: max_delay must be in 0 .. ", NFOPP_SCHEDULE_MAX_DELAY);
-  const int64_t b = tracks.size(0), k = tracks.size(1);
-  TORCH_CHECK(k <= 0x7fffffffLL && tracks.size(2) <= 0x7fffffffLL, "nfopp: tracks must have fewer than 2^31 instants and floats per row");
   if (radius.has_value()) need(tracks, *radius, "radius", {b});
   int64_t m = 0;
+  int32_t obstacle_stride = 2;
   if (obstacles.has_value()) {
-    check_tensor(*obstacles, "obstacles");
+    int64_t ko;
+    std::tie(m, ko, obstacle_stride) = check_tracks(*obstacles, "obstacles");
     same_device(tracks, *obstacles, "obstacles");
-    TORCH_CHECK(obstacles->dim() == 3 && obstacles->size(1) == k + max_delay && obstacles->size(2) >= 2 &&
-                    obstacles->size(2) <= 0x7fffffffLL,
-                "nfopp: obstacles must be [M, K + max_delay, >= 2] = [M, ", k + max_delay, ", >= 2]");
-    m = obstacles->size(0);
+    TORCH_CHECK(ko == k + max_delay, "nfopp: obstacles must be [M, K + max_delay, >= 2] = [M, ", k + max_delay, ", >= 2]");
     if (obstacle_radius.has_value()) need(tracks, *obstacle_radius, "obstacle_radius", {m});
   }
   c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks.device());
   const auto i64 = tracks.options().dtype(at::kLong);
   Tensor pair = at::empty({b, b, 2}, i64), base = at::empty({b}, i64), bad = at::empty({b}, tracks.options().dtype(at::kInt));
   const size_t bytes = nfopp_fleet_shift_masks_workspace_bytes(b, m);
-  Tensor workspace = at::empty({(int64_t)bytes}, tracks.options().dtype(at::kByte));
+  Tensor workspace = byte_workspace(tracks, bytes);
   auto u64 = [](Tensor& t) { return t.numel() ? reinterpret_cast<uint64_t*>(t.data_ptr<int64_t>()) : nullptr; };
-  check_status(nfopp_fleet_shift_masks(b ? tracks.data_ptr<float>() : nullptr, b, (int32_t)tracks.size(2), (int32_t)k, opt_ptr<float>(radius),
+  check_status(nfopp_fleet_shift_masks(b ? tracks.data_ptr<float>() : nullptr, b, stride, (int32_t)k, opt_ptr<float>(radius),
                                        margin, (int32_t)max_delay, m ? obstacles->data_ptr<float>() : nullptr, m,
-                                       m ? (int32_t)obstacles->size(2) : 2, m ? opt_ptr<float>(obstacle_radius) : nullptr, u64(pair),
+                                       obstacle_stride, m ? opt_ptr<float>(obstacle_radius) : nullptr, u64(pair),
                                        u64(base), b ? bad.data_ptr<int32_t>() : nullptr, bytes ? workspace.data_ptr() : nullptr, bytes,
                                        stream_of(tracks)));
   return std::make_tuple(pair, base, bad);

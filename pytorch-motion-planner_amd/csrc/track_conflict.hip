@@ -7,30 +7,19 @@
 //                                   staged in LDS per trip, 2 x 2 pairs per thread; per-tile partials of every row (and column)
 //   * track_conflict_reduce_kernel  one thread per track: the lexicographic minima and the count over its tiles' partials
 //
-// The rule (restated in numpy in tests/track_conflict_ref.py; include/nfopp_hip.h repeats it for callers).  Everything is
-// float64 with every operation rounded on its own.  A track is K >= 1 positions at t_k = t0 + k * dt (k * dt rounded, then
-// the sum, as nfopp_path_time_sample forms its instants), read as fp32 and widened; x, y are the first two floats of a row
-// of `stride` floats.  Between two instants a track is linear in time.  R_ij = (ra_i + rb_j) + margin, R2_ij = R_ij * R_ij.
-//  Pair (i, j), interval k = 0 .. K - 2, componentwise d0 = pa_k - pb_k, d1 = pa_{k+1} - pb_{k+1}, w = d1 - d0:
-//    c = d0x * d0x + d0y * d0y,  a = wx * wx + wy * wy,  b = d0x * wx + d0y * wy
-//    a == 0 or b >= 0:  s = 0,         m = c
-//    else -b >= a:      s = 1,         m = d1x * d1x + d1y * d1y
-//    else:              s = (-b) / a,  p = d0 + s * w,  m = px * px + py * py
-//  and one more term for the last instant: k = K - 1, s = 0, m = |d_{K-1}|^2 (the whole check when K = 1).
-//  M_ij = min_k m_k, attained first at k*;  t*_ij = t_{k*} + s_{k*} * dt;  gap g_ij = sqrt(M_ij) - R_ij.
-//  Conflict: some m_k < R2_ij (strict, like the circle checker's dist < radius).  At the smallest such k: s_in = 0 when
-//    c < R2, else disc = max(b * b - a * (c - R2), 0), s_in = min(max(((-b) - sqrt(disc)) / a, 0), s);  tc_ij = t_k + s_in * dt
-//    (the last-instant term: tc = t_{K-1} + 0 * dt).  No conflict: tc_ij = +inf.
+// The pair rule -- the closest approach of an interval, R and R2, the strict conflict test, the first-contact fraction -- and
+// the map from a workgroup to its tile of pairs are those of track_pairs.h, which states them.  What is this file's own:
 //  A track with a non-finite coordinate or radius is BAD: skipped as a partner by everyone, its own summary row NaN with
 //    status NFOPP_CONFLICT_BAD_TRACK, its pair-matrix rows and columns NaN (the diagonal entry included).
 //  Summary row of track i: lexicographic minima over the good partners j on (g_ij, j) and on (tc_ij, j) -- the smaller j wins
 //    a tie -- and the number of partners in conflict.
-//  Self mode (no set B): partners are all j != i.  Swapping i and j negates d0, d1 and w exactly, and every product above is
-//    of two negated factors, so every quantity is even in the sign of d: the pair matrices are bitwise symmetric.  The
-//    kernel evaluates the tiles of the upper triangle only and serves both rows from them.
+//  Self mode (no set B): partners are all j != i.  Swapping i and j negates d0, d1 and w exactly, and every product of the
+//    rule is of two negated factors, so every quantity is even in the sign of d: the pair matrices are bitwise symmetric.
+//    The kernel evaluates the tiles of the upper triangle only and serves both rows from them.
 //
 // No atomics and no float sums: minima are order-free and the count is an integer, so two runs give the same bits.
 #include "common.h"
+#include "track_pairs.h"
 
 #pragma clang fp contract(off)
 
@@ -79,19 +68,8 @@ __global__ __launch_bounds__(TC_THREADS) void track_conflict_tile_kernel(const C
   const double inf = (double)__builtin_inff(), qnan = (double)__builtin_nanf("");
 
   long long ta, tb;
-  if (p.self) {   // tile `t` of the upper triangle, row by row: row r starts at r * n - r * (r - 1) / 2
-    const long long n = p.nta, t = blockIdx.x, q = 2 * n + 1;
-    long long r = (long long)(((double)q - sqrt((double)(q * q - 8 * t))) * 0.5);
-    if (r < 0) r = 0;
-    if (r > n - 1) r = n - 1;
-    while (r > 0 && r * n - r * (r - 1) / 2 > t) --r;
-    while (r + 1 < n && (r + 1) * n - (r + 1) * r / 2 <= t) ++r;
-    ta = r;
-    tb = r + (t - (r * n - r * (r - 1) / 2));
-  } else {
-    ta = blockIdx.x / p.ntb;
-    tb = blockIdx.x % p.ntb;
-  }
+  if (p.self) upper_triangle_tile(blockIdx.x, p.nta, &ta, &tb);
+  else pair_tile(blockIdx.x, p.ntb, &ta, &tb);
   const long long a0 = ta * TC_TILE_A, b0 = tb * TC_TILE_B;
 
   // radii; a non-finite one makes the track bad, as a non-finite coordinate does below
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(TC_THREADS) void track_conflict_tile_kernel(const C
     const long long g = is_a ? a0 + tid : b0 + (tid - TC_TILE_A);
     const float* rad = is_a ? p.ra : p.rb;
     const float r = (rad && g < (is_a ? p.ba : p.bb)) ? rad[g] : 0.f;
-    sbad[tid] = fabsf(r) < __builtin_inff() ? 0 : 1;
+    sbad[tid] = finite32(r) ? 0 : 1;
   }
   double R[2][2], R2[2][2];
 #pragma unroll
@@ -109,8 +87,7 @@ __global__ __launch_bounds__(TC_THREADS) void track_conflict_tile_kernel(const C
     for (int c = 0; c < 2; ++c) {
       const long long gi = a0 + ty + 16 * r, gj = b0 + tx + 16 * c;
       const double ra = (p.ra && gi < p.ba) ? (double)p.ra[gi] : 0.0, rb = (p.rb && gj < p.bb) ? (double)p.rb[gj] : 0.0;
-      R[r][c] = (ra + rb) + p.margin;
-      R2[r][c] = R[r][c] * R[r][c];
+      pair_radius(ra, rb, p.margin, &R[r][c], &R2[r][c]);
     }
 
   double M[2][2], ss[2][2], tc[2][2], d0x[2][2], d0y[2][2], c0[2][2];
@@ -135,7 +112,7 @@ __global__ __launch_bounds__(TC_THREADS) void track_conflict_tile_kernel(const C
         const float* src = is_a ? p.a + g * row_a + (long long)(k0 + kk) * p.stride_a
                                 : p.b + g * row_b + (long long)(k0 + kk) * p.stride_b;
         v.x = src[0]; v.y = src[1];
-        if (!(fabsf(v.x) < __builtin_inff() && fabsf(v.y) < __builtin_inff())) sbad[tr] = 1;   // every writer writes 1
+        if (!(finite32(v.x) && finite32(v.y))) sbad[tr] = 1;   // every writer writes 1
       }
       (is_a ? sA : sB)[kk * TC_PITCH + lt] = v;
     }
@@ -152,30 +129,10 @@ __global__ __launch_bounds__(TC_THREADS) void track_conflict_tile_kernel(const C
           const double d1x = (double)pa[r].x - (double)pb[c].x, d1y = (double)pa[r].y - (double)pb[c].y;
           const double e = d1x * d1x + d1y * d1y;
           if (k > 0) {   // interval k - 1: d1 of the previous instant is d0 of this one, across chunk boundaries too
-            const double x0 = d0x[r][c], y0 = d0y[r][c], cc = c0[r][c];
-            const double wx = d1x - x0, wy = d1y - y0;
-            const double a = wx * wx + wy * wy, b = x0 * wx + y0 * wy;
-            double s, m;
-            if (a == 0.0 || b >= 0.0) { s = 0.0; m = cc; }
-            else if (-b >= a) { s = 1.0; m = e; }
-            else {
-              s = (-b) / a;
-              const double px = x0 + s * wx, py = y0 + s * wy;
-              m = px * px + py * py;
-            }
-            if (m < M[r][c]) { M[r][c] = m; ks[r][c] = k - 1; ss[r][c] = s; }
-            if (m < R2[r][c] && !(tc[r][c] < inf)) {
-              double s_in = 0.0;
-              if (!(cc < R2[r][c])) {
-                const double bb = b * b, cr = cc - R2[r][c], acr = a * cr;
-                double disc = bb - acr;
-                disc = disc > 0.0 ? disc : 0.0;
-                s_in = ((-b) - sqrt(disc)) / a;
-                s_in = s_in > 0.0 ? s_in : 0.0;
-                s_in = s_in < s ? s_in : s;
-              }
-              tc[r][c] = (p.t0 + (double)(k - 1) * p.dt) + s_in * p.dt;
-            }
+            const Approach q = closest_approach(d0x[r][c], d0y[r][c], c0[r][c], d1x, d1y, e);
+            if (q.m < M[r][c]) { M[r][c] = q.m; ks[r][c] = k - 1; ss[r][c] = q.s; }
+            if (q.m < R2[r][c] && !(tc[r][c] < inf))
+              tc[r][c] = (p.t0 + (double)(k - 1) * p.dt) + entry_fraction(q.a, q.b, c0[r][c], R2[r][c], q.s) * p.dt;
           }
           d0x[r][c] = d1x; d0y[r][c] = d1y; c0[r][c] = e;
         }

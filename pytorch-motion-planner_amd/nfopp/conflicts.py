@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tracks import check_tracks, hip_device, per_row, raw_ptr
 
 # slots of TrackConflicts.summary [B, 7] (NFOPP_CONFLICT_SLOT_*)
 (CONFLICT_MIN_GAP, CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_FIRST_TIME, CONFLICT_FIRST_PARTNER, CONFLICT_COUNT,
@@ -31,68 +32,22 @@ class TrackConflicts(object):
         return self.summary[:, CONFLICT_COUNT] > 0
 
 
-def _check_tracks(t, name):
-    """[B, K, >= 2] fp32 with K >= 1 whose last two dimensions are contiguous and whose tracks follow each other without a
-    gap: what the kernel indexes by.  -> (B, K, row stride in floats)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a tensor" % name)
-    if t.dim() != 3 or t.shape[1] < 1 or t.shape[2] < 2:
-        raise ValueError("%s must be [B, K, >= 2] with K >= 1, got %s" % (name, tuple(t.shape)))
-    if t.dtype != torch.float32:
-        raise ValueError("%s must be float32, got %s" % (name, t.dtype))
-    b, k, _ = t.shape
-    sb, sk, sx = t.stride()
-    row = sk if k > 1 else (sb if b > 1 else t.shape[2])      # the stride of a dimension of size 1 says nothing
-    if b > 0 and (sx != 1 or row < 2 or (k > 1 and b > 1 and sb != k * sk)):
-        raise ValueError("%s must be laid out as rows of x, y, ... that follow each other (strides (K * S, S, 1) with S >= 2), "
-                         "got strides %s for shape %s" % (name, tuple(t.stride()), tuple(t.shape)))
-    return b, k, int(row)
-
-
-def _radii(r, batch, device, name):
-    """None, a number, an array or a tensor -> None (all zero) or a [B] fp32 device tensor (a tensor is not copied to the
-    host)."""
-    if r is None:
-        return None
-    if isinstance(r, torch.Tensor):
-        r = r.to(device=device, dtype=torch.float32).reshape(-1)
-    else:
-        r = torch.from_numpy(np.array(r, np.float32).reshape(-1)).to(device)
-    if r.numel() not in (1, batch):
-        raise ValueError("%s must be a number or [B] = [%d], got %d values" % (name, batch, r.numel()))
-    return r.expand(batch).contiguous()
-
-
-def _raw_ptr(t):
-    """Device pointer of a track tensor `_check_tracks` accepted (it may be a strided view, which `_lib.ptr` refuses)."""
-    if not t.is_cuda:
-        raise _lib.NfoppError("track_conflicts needs HIP tensors (there is no CPU path)")
-    dev = _lib._current_device()
-    if t.device.index != dev:
-        _lib.require_current_device(t.device.index, dev)
-    return t.data_ptr() or None
-
-
 def track_conflicts(tracks_a, tracks_b=None, *, dt, t0=0.0, radius_a=0.0, radius_b=None, margin=0.0, want_pairs=False):
     """tracks_a [Ba, K, >= 2], tracks_b [Bb, K, >= 2] or None: fp32 HIP tensors of positions at t0 + k * dt, x and y first in a
     row (`TimedPaths.sample` returns such a tensor).  Without `tracks_b` the tracks of A are checked against each other.
     `radius_a` / `radius_b`: a number or [B] (metres; a box robot takes its circumscribed disc); `margin` is added to every
     sum of radii -- put (va_max + vb_max) * dt / 2 there to cover what the robots do between two instants.
     -> `TrackConflicts`."""
-    ba, k, stride_a = _check_tracks(tracks_a, "tracks_a")
+    ba, k, stride_a = check_tracks(tracks_a, "tracks_a")
     self_mode = tracks_b is None
     bb, stride_b = 0, 2
     if not self_mode:
-        bb, kb, stride_b = _check_tracks(tracks_b, "tracks_b")
+        bb, kb, stride_b = check_tracks(tracks_b, "tracks_b")
         if kb != k:
             raise ValueError("tracks_a and tracks_b must share the time grid: K = %d and %d" % (k, kb))
-    if not tracks_a.is_cuda or (not self_mode and not tracks_b.is_cuda):
-        raise _lib.NfoppError("track_conflicts needs HIP tensors (there is no CPU path)")
-    device = tracks_a.device
-    if not self_mode and tracks_b.device != device:
-        raise _lib.NfoppError("tracks_b lives on %s, tracks_a on %s" % (tracks_b.device, device))
-    radius_a = _radii(radius_a, ba, device, "radius_a")
-    radius_b = None if self_mode else _radii(radius_b, bb, device, "radius_b")
+    device = hip_device("track_conflicts", "tracks_a", tracks_a, "tracks_b", tracks_b)
+    radius_a = per_row(radius_a, ba, device, "radius_a")
+    radius_b = None if self_mode else per_row(radius_b, bb, device, "radius_b")
     lib = _lib.load()
     f64 = dict(dtype=torch.float64, device=device)
     cols = ba if self_mode else bb
@@ -103,9 +58,9 @@ def track_conflicts(tracks_a, tracks_b=None, *, dt, t0=0.0, radius_a=0.0, radius
     nbytes = int(lib.nfopp_track_conflicts_workspace_bytes(ba, bb, k))
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
     # a set of no obstacles still needs a non-null pointer (null selects self mode); it is never read
-    b_ptr = None if self_mode else (_raw_ptr(tracks_b) or _raw_ptr(tracks_a))
+    b_ptr = None if self_mode else (raw_ptr(tracks_b) or raw_ptr(tracks_a))
     _lib.check(lib.nfopp_track_conflicts(
-        _raw_ptr(tracks_a), ba, stride_a, b_ptr, bb, stride_b, k, float(t0), float(dt), _lib.ptr(radius_a), _lib.ptr(radius_b),
+        raw_ptr(tracks_a), ba, stride_a, b_ptr, bb, stride_b, k, float(t0), float(dt), _lib.ptr(radius_a), _lib.ptr(radius_b),
         float(margin), _lib.ptr(summary, torch.float64), _lib.ptr(summary_b, torch.float64), _lib.ptr(pair_gap, torch.float64),
         _lib.ptr(pair_first, torch.float64), _lib.ptr(workspace, torch.uint8), nbytes, _lib.stream_ptr()))
     if ba == 0 and bb > 0:      # the entry writes nothing for an empty set A: every obstacle is without a partner

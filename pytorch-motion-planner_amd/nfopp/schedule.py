@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .conflicts import _check_tracks, _radii, _raw_ptr
+from ._tracks import check_tracks, hip_device, per_row, raw_ptr
 
 # values of FleetSchedule.status (NFOPP_SCHEDULE_*)
 SCHEDULE_OK, SCHEDULE_BAD_TRACK, SCHEDULE_UNRESOLVED, SCHEDULE_NOT_ORDERED = 0, 1, 2, 3
@@ -74,19 +74,15 @@ def fleet_shift_masks(tracks, *, max_delay, radius=0.0, margin=0.0, obstacles=No
     per track; `margin` is added to every sum of radii.  `obstacles` [M, K + max_delay, >= 2]: predicted tracks in absolute
     time, never shifted -> `FleetMasks`."""
     max_delay = _check_max_delay(max_delay)
-    b, k, stride = _check_tracks(tracks, "tracks")
+    b, k, stride = check_tracks(tracks, "tracks")
     m, stride_o = 0, 2
     if obstacles is not None:
-        m, ko, stride_o = _check_tracks(obstacles, "obstacles")
+        m, ko, stride_o = check_tracks(obstacles, "obstacles")
         if ko != k + max_delay:
             raise ValueError("obstacles must cover K + max_delay = %d instants, got %d" % (k + max_delay, ko))
-    if not tracks.is_cuda or (obstacles is not None and not obstacles.is_cuda):
-        raise _lib.NfoppError("fleet_shift_masks needs HIP tensors (there is no CPU path)")
-    device = tracks.device
-    if obstacles is not None and obstacles.device != device:
-        raise _lib.NfoppError("obstacles live on %s, tracks on %s" % (obstacles.device, device))
-    radius = _radii(radius, b, device, "radius")
-    obstacle_radius = None if obstacles is None else _radii(obstacle_radius, m, device, "obstacle_radius")
+    device = hip_device("fleet_shift_masks", "tracks", tracks, "obstacles", obstacles)
+    radius = per_row(radius, b, device, "radius")
+    obstacle_radius = None if obstacles is None else per_row(obstacle_radius, m, device, "obstacle_radius")
     lib = _lib.load()
     pair = torch.empty(b, b, 2, dtype=torch.int64, device=device)
     base = torch.empty(b, dtype=torch.int64, device=device)
@@ -94,7 +90,7 @@ def fleet_shift_masks(tracks, *, max_delay, radius=0.0, margin=0.0, obstacles=No
     nbytes = int(lib.nfopp_fleet_shift_masks_workspace_bytes(b, m))
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
     _lib.check(lib.nfopp_fleet_shift_masks(
-        _raw_ptr(tracks), b, stride, k, _lib.ptr(radius), float(margin), max_delay, _raw_ptr(obstacles) if m else None, m, stride_o,
+        raw_ptr(tracks), b, stride, k, _lib.ptr(radius), float(margin), max_delay, raw_ptr(obstacles) if m else None, m, stride_o,
         _lib.ptr(obstacle_radius) if m else None, _lib.ptr(pair, torch.int64), _lib.ptr(base, torch.int64), _lib.ptr(bad, torch.int32),
         _lib.ptr(workspace, torch.uint8), nbytes, _lib.stream_ptr()))
     return FleetMasks(pair, base, bad, max_delay)

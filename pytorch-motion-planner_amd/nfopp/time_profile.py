@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tracks import per_row
 
 # slots of TimedPaths.profile [B, N + 2, 4] (NFOPP_TIME_SLOT_*) and TimedPaths.summary [B, 4] (NFOPP_TIME_SUMMARY_*)
 TIME_SLOT_S, TIME_SLOT_T, TIME_SLOT_V, TIME_SLOT_V_PEAK = range(_lib.NUM_TIME_SLOTS)
@@ -33,17 +34,17 @@ class MotionLimits(collections.namedtuple("MotionLimits", "v_max a_max d_max a_l
         return _lib.MotionLimitsC(self.v_max, self.a_max, self.d_max, self.a_lat, self.w_max, self.cos_cusp)
 
 
-def _speeds(v, batch, device):
-    """None, a number, an array or a tensor -> None or a [B] fp32 device tensor (a tensor is not copied to the host)."""
-    if v is None:
-        return None
-    if isinstance(v, torch.Tensor):
-        v = v.to(device=device, dtype=torch.float32).reshape(-1)
-    else:
-        v = torch.from_numpy(np.array(v, np.float32).reshape(-1)).to(device)
-    if v.numel() not in (1, batch):
-        raise ValueError("a start / goal speed must be a number or [B] = [%d], got %d values" % (batch, v.numel()))
-    return v.expand(batch).contiguous()
+def _chord_margin_or_number(margin, v_self, v_other, dt):
+    """`margin` of `TimedPaths.conflicts` / `.schedule`: a number as it is, "chord" -> `chord_margin` of the two top speeds
+    (v_other None: the other side is a tracks tensor whose top speed was not given)."""
+    if not isinstance(margin, str):
+        return margin
+    if margin != "chord":
+        raise ValueError("margin must be a number or \"chord\", got %r" % (margin,))
+    if v_other is None:
+        raise ValueError("margin=\"chord\" against a tracks tensor needs other_v_max, the top speed of those tracks")
+    from .conflicts import chord_margin
+    return chord_margin(v_self, v_other, dt)
 
 
 def _check_paths(traj, start, goal):
@@ -97,18 +98,13 @@ class TimedPaths(object):
         returns -- the paths are checked against those tracks instead.  `radius` / `other_radius`: a number or one per track.
         `margin="chord"` is (v_max + the other side's v_max) * dt / 2, what the straight line between two instants can
         hide; for a tracks tensor it needs `other_v_max`."""
-        from .conflicts import chord_margin, track_conflicts
+        from .conflicts import track_conflicts
         tracks_b, vb = None, self.limits.v_max
         if isinstance(other, TimedPaths):
             tracks_b, vb = other.sample(dt, count, t0=t0), other.limits.v_max
         elif other is not None:
             tracks_b, vb = other, other_v_max
-        if isinstance(margin, str):
-            if margin != "chord":
-                raise ValueError("margin must be a number or \"chord\", got %r" % (margin,))
-            if vb is None:
-                raise ValueError("margin=\"chord\" against a tracks tensor needs other_v_max, the top speed of those tracks")
-            margin = chord_margin(self.limits.v_max, vb, dt)
+        margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt)
         if other is None:
             return track_conflicts(self.sample(dt, count, t0=t0), dt=dt, t0=t0, radius_a=radius, margin=margin,
                                    want_pairs=want_pairs)
@@ -124,7 +120,6 @@ class TimedPaths(object):
         obstacles in absolute time.  `margin="chord"` is (v_max + the larger of v_max and the other side's v_max) * dt / 2:
         one margin serves robot pairs and obstacle pairs alike; for a tracks tensor it needs `other_v_max`.  A robot is
         `complete` when its total time fits the sampled instants, so that its last sample is its goal."""
-        from .conflicts import chord_margin
         from .schedule import fleet_shift_masks
         count, max_delay = int(count), int(max_delay)
         obstacles, vb = None, self.limits.v_max
@@ -132,12 +127,7 @@ class TimedPaths(object):
             obstacles, vb = other.sample(dt, count + max_delay), max(vb, other.limits.v_max)
         elif other is not None:
             obstacles, vb = other, None if other_v_max is None else max(vb, float(other_v_max))
-        if isinstance(margin, str):
-            if margin != "chord":
-                raise ValueError("margin must be a number or \"chord\", got %r" % (margin,))
-            if vb is None:
-                raise ValueError("margin=\"chord\" against a tracks tensor needs other_v_max, the top speed of those tracks")
-            margin = chord_margin(self.limits.v_max, vb, dt)
+        margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt)
         total = self.summary[:, TIME_SUMMARY_TIME]
         if isinstance(order, str):
             if order != "longest_first":
@@ -162,7 +152,7 @@ def time_parametrize(traj, start, goal, limits, v_start=None, v_goal=None):
     if not isinstance(limits, MotionLimits):
         raise TypeError("limits must be a MotionLimits")
     b, n, d = traj.shape
-    v_start, v_goal = _speeds(v_start, b, traj.device), _speeds(v_goal, b, traj.device)
+    v_start, v_goal = (per_row(v, b, traj.device, "a start / goal speed") for v in (v_start, v_goal))
     traj, start, goal = (x.clone(memory_format=torch.contiguous_format) for x in (traj, start, goal))
     f64 = dict(dtype=torch.float64, device=traj.device)
     profile = torch.empty(b, n + 2, _lib.NUM_TIME_SLOTS, **f64)

@@ -174,6 +174,43 @@ def test_the_schedule_is_clear_by_the_conflict_check_and_orders_reuse_the_masks(
     assert np.array_equal(_u64(one.pair), want["pair"]) and not one.base.any()
 
 
+def one_predicate_case(b, k):
+    """B straight drives across a square floor that take all K instants, radii and floor sized so that some pairs conflict
+    and some do not, and (B > 1) a NaN coordinate in track B // 2 -> (tracks [B, K, 2], radius [B], margin)."""
+    rng = np.random.default_rng(100 * b + k)
+    ends = rng.uniform(0.0, 0.5 * np.sqrt(b), (2, b, 1, 2))
+    lam = (np.arange(k) / max(k - 1, 1))[None, :, None]
+    tracks = (ends[0] * (1 - lam) + ends[1] * lam).astype(F32)
+    if b > 1:
+        tracks[b // 2, k // 2, 1] = np.nan
+    return tracks, rng.uniform(0.05, 0.2, b).astype(F32), 0.03125
+
+
+# (1, 1): one pair; (9, 5): two 8-tiles of the scheduler; (33, 5): across a 32-tile of the conflict kernel; (9, 70) with
+# max_delay 3: K + max_delay across the 64-instant chunk of one kernel and the 32-instant chunk of the other
+@pytest.mark.parametrize("b,k,md", ((1, 1, 0), (9, 5, 2), (33, 5, 2), (9, 70, 3)), ids=lambda v: str(v))
+def test_one_predicate_on_the_device(b, k, md):
+    """Bit max_delay (r = 0) of every pair mask is `pair_first < inf` of the conflict check in self mode: device against
+    device over the whole matrix, the diagonal and the bad track's row and column included (there pair_first is +inf or NaN
+    and the mask is 0).  Both kernels take the predicate from csrc/track_pairs.h."""
+    tracks, radius, margin = one_predicate_case(b, k)
+    t, r = _dev(tracks), _dev(radius)
+    masks = nfopp.fleet_shift_masks(t, max_delay=md, radius=r, margin=margin)
+    found = nfopp.track_conflicts(t, dt=1.0, radius_a=r, margin=margin, want_pairs=True)
+    bit = ((masks.pair[:, :, md // 64] >> (md % 64)) & 1).bool()
+    want = found.pair_first < float("inf")
+    assert torch.equal(bit, want), torch.nonzero(bit != want)[:6].tolist()
+    bad = masks.bad.bool()
+    assert bad.tolist() == [b > 1 and i == b // 2 for i in range(b)]
+    assert torch.isnan(found.pair_first[bad]).all() and torch.isnan(found.pair_first[:, bad]).all()
+    assert not masks.pair[bad].any() and not masks.pair[:, bad].any() and not masks.pair.diagonal().any()
+    if b > 1:
+        good = ~(bad[:, None] | bad[None, :] | torch.eye(b, dtype=torch.bool, device="cuda"))
+        assert want[good].any() and (~want)[good].any()
+    if k > 64:      # a first contact in the last chunk of instants of either kernel
+        assert (found.pair_first[want] > 64.0).any()
+
+
 def test_the_torch_ops_equal_the_raw_calls():
     ops = torch_ops.load()
     for c in (fc.sized_case(9, 7, 5, m=3, stride=3), fc.sized_case(10, 6, 40, m=0, stride=2)):

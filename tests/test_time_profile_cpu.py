@@ -296,7 +296,10 @@ def test_python_entries_refuse_shapes_the_kernels_would_index_past():
                                   (traj, torch.zeros(3, 2), end), (traj, end, torch.zeros(2, 3)), (traj, torch.zeros(3), end)):
         with pytest.raises(ValueError, match="must be"):
             nfopp.time_parametrize(bad_traj, start, goal, lim)
-    from nfopp.time_profile import _speeds
+    from nfopp._tracks import per_row
+
+    def _speeds(v, batch, device):
+        return per_row(v, batch, device, "a start / goal speed")
     assert _speeds(None, 3, "cpu") is None
     assert _speeds(0.5, 3, "cpu").tolist() == [0.5] * 3 and _speeds(torch.tensor([0.25]), 3, "cpu").tolist() == [0.25] * 3
     assert _speeds(np.array([1.0, 2.0, 3.0]), 3, "cpu").tolist() == [1.0, 2.0, 3.0]

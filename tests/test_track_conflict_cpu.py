@@ -264,6 +264,22 @@ def kernel_constants():
     return tuple(int(re.search(r"constexpr int %s = (\d+);" % n, src).group(1)) for n in ("TC_TILE_A", "TC_TILE_B", "TC_CHUNK"))
 
 
+def test_the_pair_arithmetic_has_one_owner_and_the_makefile_knows_every_header():
+    csrc = os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc")
+    rule = re.search(r"^\$\(OBJ\)/%\.o:(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len([f for f in sources if f.endswith(".hip")]) > 20
+    for f in sources:                                                   # a header edit rebuilds its users, through headers too
+        for h in re.findall(r'^#include "([^"]+)"', open(os.path.join(csrc, f)).read(), re.M):
+            assert h in rule or (h == "nfopp_hip.h" and "$(ROOT)/include/nfopp_hip.h" in rule), (f, h)
+    assert "track_pairs.h" in rule
+    assert "#pragma clang fp contract(off)" in open(os.path.join(csrc, "track_pairs.h")).read()
+    for f in ("track_conflict.hip", "fleet_schedule.hip"):
+        src = open(os.path.join(csrc, f)).read()
+        assert '#include "track_pairs.h"' in src, f
+        assert "q * q - 8 * t" not in src, f                            # the tile map exists once
+
+
 def _rc(ba=3, bb=2, stride_a=2, stride_b=2, k=4, t0=0.0, dt=0.1, margin=0.0, ptr=1, self_mode=False, summary=1, workspace=1,
         workspace_bytes=1 << 20):
     P = lambda v: ctypes.c_void_p(v) if v else None
@@ -344,7 +360,8 @@ def test_python_names_and_signatures():
 
 def test_constant_velocity_tracks_and_the_python_shape_checks():
     import torch
-    from nfopp.conflicts import _check_tracks, _radii, chord_margin
+    from nfopp._tracks import check_tracks as _check_tracks, per_row as _radii
+    from nfopp.conflicts import chord_margin
     tracks = nfopp.constant_velocity_tracks(torch.tensor([[1.0, 2.0], [0.0, 0.0]]), torch.tensor([[0.5, -1.0], [0.0, 2.0]]), 0.25, 5, t0=1.0)
     assert tracks.dtype == torch.float32 and tuple(tracks.shape) == (2, 5, 2)
     assert tracks[0].tolist() == [[1.5 + 0.125 * k, 1.0 - 0.25 * k] for k in range(5)]
