@@ -893,6 +893,82 @@ int nfopp_fleet_assign_delays(const uint64_t* pair_mask_dev, const uint64_t* bas
                               const int32_t* order_dev, int64_t b, int32_t max_delay, int32_t* delay_dev, int32_t* status_dev,
                               uint64_t* forbidden_dev, void* stream);
 
+/* ---- space-time grid search for the robots a schedule cannot place (csrc/spacetime_search.hip), additive under ABI 6 ---------
+ * nfopp_fleet_assign_delays ends with robots it cannot place: a robot placed before them waits on their path, crosses it at the
+ * wrong time or parks on it for good, and no re-timing of a fixed path gets round that.  These entries give such a robot
+ * another path, chosen with time in it: an earliest-arrival search on an occupancy grid against what is already reserved.
+ * Predicates and integer ORs only, the same bits run after run; the device is compared bit for bit with the numpy restatement
+ * in tests/spacetime_ref.py.
+ *
+ * Grid.  occupancy_dev [rows, cols] uint8, non-zero = wall, with the geometry of the grid search above: the float64 centre of
+ *   cell (row, col) is  col * res + res / 2 + b0  (x) and  row * res + res / 2 + b2  (y), every operation rounded on its own,
+ *   left to right.  The centre used everywhere is that value rounded to fp32: it is what the output tracks hold and, widened,
+ *   what the predicate reads.  The caller inflates the image for the robot's footprint.
+ * Time.  t >= 1 instants on the callers' common time grid.  dt does not enter: everything is per tick.
+ * Moves.  In one tick a robot stays or moves to one of its 8 neighbours (the move set of the grid search with no corner rule;
+ *   cells outside the image are walls).  A move takes one tick whatever its length: the caller chooses
+ *   dt >= sqrt(2) * res / v_max.  Directions d = 0 .. 8 as (drow, dcol):
+ *     (0,+1) (0,-1) (+1,0) (-1,0) (+1,+1) (+1,-1) (-1,+1) (-1,-1) (0,0) -- the wait is last.
+ * Movers.  tracks_dev [m, t, stride >= 2] fp32 in absolute time, never shifted, radius_dev [m] (null = 0) and visible_dev [m]
+ *   uint8 (null = all visible).  A track with a non-finite coordinate or radius is bad and skipped.
+ * Edge predicate.  Edge (u, d, h) is the robot going from cell u at instant h to v = u + d at h + 1.  It is blocked if v is
+ *   outside the image or a wall, or if some visible good mover j gives the conflict predicate of nfopp_track_conflicts on this
+ *   one interval: d0 = centre(u) - p_j[h], d1 = centre(v) - p_j[h + 1], m the closest approach of the interval, blocked when
+ *   m < R2_j (strict), R_j = (robot_radius + r_j) + margin, R2_j = R_j * R_j -- the same float64 arithmetic, the same device
+ *   functions (csrc/track_pairs.h).  last[u] is the last-instant term: |centre(u) - p_j[t - 1]|^2 < R2_j for some such j.
+ *   There is one robot_radius (an fp32 value) for the whole planned fleet: the reservation then does not depend on which robot
+ *   is being planned and can be accumulated.
+ * Reservation.  uint64 words, W = (cols + 63) / 64 words a row, bit c % 64 of word c / 64 is column c:
+ *     blocked [t - 1][9][rows][W]   bit = edge (u, d, h) is blocked, indexed by the source cell u
+ *     last    [rows][W]             follows it
+ *   nfopp_spacetime_reservation_bytes(rows, cols, t) bytes in all (0: not an image and t an int32 indexes).  The padding bits of
+ *   a row (columns >= cols) are 1 in blocked and 0 in last.  nfopp_spacetime_reservation_init writes the static part (walls,
+ *   the image edge, the padding) and clears last; nfopp_spacetime_reserve ORs the movers' bits in -- OR is order-free, so
+ *   reserving a set of tracks in two calls gives the bits of one call.  Its workspace: nfopp_spacetime_reserve_workspace_bytes(m).
+ * Search of one robot, start cell s, goal cell g.  reach_0 = {s}; reach_{h+1}[v] = OR over d of (reach_h[v - d] and edge
+ *   (v - d, d, h) not blocked).  park[t - 1] = !last[g]; park[h] = park[h + 1] and wait edge (g, 8, h) not blocked.  Arrival
+ *   h* = the smallest h with reach_h[g] and park[h].  Path: cell[h] = g for h >= h*; backwards from (g, h*) the predecessor
+ *   of (v, h) is v - d for the lowest d with reach_{h-1}[v - d] and edge (v - d, d, h - 1) not blocked; it ends at (s, 0) by
+ *   construction.
+ * Statuses.  0 planned; NFOPP_SPACETIME_BAD_CELL: start or goal outside the image or on a wall; NFOPP_SPACETIME_UNREACHED: no
+ *   such h*; NFOPP_SPACETIME_NOT_ORDERED: never visited.  A robot that is not planned has arrival -1, cells all -1 and NaN track
+ *   rows, and reserves nothing: it is not on the floor for those after it, as an unresolved robot of the schedule is not.
+ * Fleet (nfopp_spacetime_plan_fleet).  start_cells_dev / goal_cells_dev [robots, 2] int32 (row, col).  order_dev [robots] int32
+ *   (null: 0 .. robots - 1) is visited front to back; an entry out of range or a robot already visited is skipped on the
+ *   device, before anything is indexed by it (any int32 content is safe).  Each planned robot's output track (fp32 centres,
+ *   radius robot_radius) is reserved before the next robot is searched, so robot k's predicate against robot k' < k is the
+ *   predicate of nfopp_track_conflicts on the two output tracks, bit for bit: "nobody planned is in conflict, by
+ *   nfopp_track_conflicts itself" holds by construction, not by tolerance.  reservation_dev is read and written: the caller
+ *   initialises it and reserves the movers first.  Outputs: cells_dev [robots, t] int32 flat index row * cols + col,
+ *   arrival_dev [robots], status_dev [robots], tracks_dev [robots, t, 2] fp32.  workspace_dev:
+ *   nfopp_spacetime_plan_workspace_bytes(rows, cols, t, robots) bytes (reach of every instant, t * rows * W * 8, and a word
+ *   of state per robot).  One search launch (one workgroup, both frontiers in LDS) and one reserve launch per order position,
+ *   all on `stream`; nothing synchronises, no kernel waits on another workgroup.
+ * The snap.  A planned track starts at the centre of the robot's start cell, up to res / sqrt(2) from where the robot stands:
+ *   the caller adds that to margin.  Grid tracks are seeds and timetables, not smooth trajectories.
+ * Argument errors, nothing is clamped: t < 1, an empty image, an image and t whose bitmaps overflow an int32 index, a frontier
+ *   larger than one workgroup's LDS (2 * rows * W * 8 + 64 bytes in 160 KiB), a reservation or workspace that is null or too
+ *   small, a null pointer where one is read or written, a stride < 2, a negative batch size, a geometry value, robot_radius or
+ *   margin that is not finite, a resolution <= 0.  robots == 0 and m == 0 return 0. */
+#define NFOPP_SPACETIME_BAD_CELL 1
+#define NFOPP_SPACETIME_UNREACHED 2
+#define NFOPP_SPACETIME_NOT_ORDERED 3
+size_t nfopp_spacetime_reservation_bytes(int32_t rows, int32_t cols, int32_t t);
+int nfopp_spacetime_reservation_init(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, int32_t t,
+                                     uint64_t* reservation_dev, size_t reservation_bytes, void* stream);
+size_t nfopp_spacetime_reserve_workspace_bytes(int64_t m);
+int nfopp_spacetime_reserve(int32_t rows, int32_t cols, int32_t t, double b0, double b2, double resolution, float robot_radius,
+                            double margin, const float* tracks_dev, int64_t m, int32_t stride, const float* radius_dev,
+                            const uint8_t* visible_dev, uint64_t* reservation_dev, size_t reservation_bytes,
+                            void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t nfopp_spacetime_plan_workspace_bytes(int32_t rows, int32_t cols, int32_t t, int64_t robots);
+int nfopp_spacetime_plan_fleet(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, int32_t t, double b0, double b2,
+                               double resolution, float robot_radius, double margin, const int32_t* start_cells_dev,
+                               const int32_t* goal_cells_dev, const int32_t* order_dev, int64_t robots,
+                               uint64_t* reservation_dev, size_t reservation_bytes, int32_t* cells_dev, int32_t* arrival_dev,
+                               int32_t* status_dev, float* tracks_dev, void* workspace_dev, size_t workspace_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

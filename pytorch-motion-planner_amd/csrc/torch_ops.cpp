@@ -483,6 +483,82 @@ std::tuple<Tensor, Tensor, Tensor> fleet_assign_delays(const Tensor& pair, const
   return std::make_tuple(delay, status, forbidden);
 }
 
+// an occupancy image [rows, cols] uint8 and the instants of a reservation -> its size in int64 words
+int64_t spacetime_words(const Tensor& occupancy, int64_t count) {
+  check_tensor(occupancy, "occupancy", at::kByte);
+  TORCH_CHECK(occupancy.dim() == 2 && occupancy.numel() > 0, "nfopp: occupancy must be a non-empty [rows, cols] image");
+  TORCH_CHECK(count >= 1 && count <= 0x7fffffffLL, "nfopp: count must be >= 1");
+  TORCH_CHECK(occupancy.size(0) <= 0x7fffffffLL && occupancy.size(1) <= 0x7fffffffLL, "nfopp: image too large for an index");
+  const size_t bytes = nfopp_spacetime_reservation_bytes((int32_t)occupancy.size(0), (int32_t)occupancy.size(1), (int32_t)count);
+  TORCH_CHECK(bytes > 0, "nfopp: image and count too large for an index");
+  return (int64_t)(bytes / 8);
+}
+
+// a space-time reservation with tracks ORed in (nfopp_spacetime_reservation_init / nfopp_spacetime_reserve): reservation None
+// = a fresh one from the occupancy image, else a copy of the given one; tracks [M, count, S] or None with radius [M] fp32 or
+// None (0) and visible [M] uint8 or None (all) -> the reservation's words [n] int64 (layout: include/nfopp_hip.h)
+Tensor spacetime_reserve(const Tensor& occupancy, int64_t count, double b0, double b2, double resolution, double robot_radius, double margin,
+                         const OptTensor& reservation, const OptTensor& tracks, const OptTensor& radius, const OptTensor& visible) {
+  const int64_t n = spacetime_words(occupancy, count);
+  const int32_t rows = (int32_t)occupancy.size(0), cols = (int32_t)occupancy.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(occupancy.device());
+  Tensor words;
+  if (reservation.has_value()) {
+    need(occupancy, *reservation, "reservation", {n}, at::kLong);
+    words = reservation->clone();
+  } else {
+    words = at::empty({n}, occupancy.options().dtype(at::kLong));
+    check_status(nfopp_spacetime_reservation_init(occupancy.data_ptr<uint8_t>(), rows, cols, (int32_t)count,
+                                                  reinterpret_cast<uint64_t*>(words.data_ptr<int64_t>()), (size_t)n * 8, stream_of(occupancy)));
+  }
+  if (!tracks.has_value()) {
+    TORCH_CHECK(!radius.has_value() && !visible.has_value(), "nfopp: radius and visible belong to tracks");
+    return words;
+  }
+  const auto [m, k, stride] = check_tracks(*tracks, "tracks");
+  same_device(occupancy, *tracks, "tracks");
+  TORCH_CHECK(k == count, "nfopp: tracks must be [M, count, >= 2] = [M, ", count, ", >= 2]");
+  if (radius.has_value()) need(occupancy, *radius, "radius", {m});
+  if (visible.has_value()) need(occupancy, *visible, "visible", {m}, at::kByte);
+  const size_t bytes = nfopp_spacetime_reserve_workspace_bytes(m);
+  Tensor workspace = byte_workspace(occupancy, bytes);
+  check_status(nfopp_spacetime_reserve(rows, cols, (int32_t)count, b0, b2, resolution, (float)robot_radius, margin,
+                                       m ? tracks->data_ptr<float>() : nullptr, m, stride, opt_ptr<float>(radius), opt_ptr<uint8_t>(visible),
+                                       reinterpret_cast<uint64_t*>(words.data_ptr<int64_t>()), (size_t)n * 8,
+                                       bytes ? workspace.data_ptr() : nullptr, bytes, stream_of(occupancy)));
+  return words;
+}
+
+// the fleet pass (nfopp_spacetime_plan_fleet): start_cells / goal_cells [R, 2] int32 (row, col), order [R] int32 or None; the
+// reservation is read and WRITTEN (every planned robot is reserved) -> (cells [R, count] int32, arrival [R] int32, status [R]
+// int32, tracks [R, count, 2] fp32)
+std::tuple<Tensor, Tensor, Tensor, Tensor> spacetime_plan_fleet(const Tensor& occupancy, int64_t count, double b0, double b2, double resolution,
+                                                                double robot_radius, double margin, const Tensor& start_cells,
+                                                                const Tensor& goal_cells, const OptTensor& order, Tensor reservation) {
+  const int64_t n = spacetime_words(occupancy, count);
+  const int32_t rows = (int32_t)occupancy.size(0), cols = (int32_t)occupancy.size(1);
+  need(occupancy, reservation, "reservation", {n}, at::kLong);
+  check_tensor(start_cells, "start_cells", at::kInt);
+  TORCH_CHECK(start_cells.dim() == 2 && start_cells.size(1) == 2, "nfopp: start_cells must be [R, 2] (row, col)");
+  const int64_t r = start_cells.size(0);
+  same_device(occupancy, start_cells, "start_cells");
+  need(occupancy, goal_cells, "goal_cells", {r, 2}, at::kInt);
+  if (order.has_value()) need(occupancy, *order, "order", {r}, at::kInt);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(occupancy.device());
+  const auto i32 = occupancy.options().dtype(at::kInt);
+  Tensor cells = at::empty({r, count}, i32), arrival = at::empty({r}, i32), status = at::empty({r}, i32);
+  Tensor tracks = at::empty({r, count, 2}, occupancy.options().dtype(at::kFloat));
+  const size_t bytes = nfopp_spacetime_plan_workspace_bytes(rows, cols, (int32_t)count, r);
+  Tensor workspace = byte_workspace(occupancy, bytes);
+  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
+  check_status(nfopp_spacetime_plan_fleet(occupancy.data_ptr<uint8_t>(), rows, cols, (int32_t)count, b0, b2, resolution, (float)robot_radius,
+                                          margin, i32p(start_cells), i32p(goal_cells), opt_ptr<int32_t>(order), r,
+                                          reinterpret_cast<uint64_t*>(reservation.data_ptr<int64_t>()), (size_t)n * 8, i32p(cells),
+                                          i32p(arrival), i32p(status), r ? tracks.data_ptr<float>() : nullptr,
+                                          bytes ? workspace.data_ptr() : nullptr, bytes, stream_of(occupancy)));
+  return std::make_tuple(cells, arrival, status, tracks);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nfopp, lib) {
@@ -521,6 +597,10 @@ TORCH_LIBRARY(nfopp, lib) {
   lib.def("fleet_shift_masks(Tensor tracks, int max_delay, Tensor? radius, float margin, Tensor? obstacles, Tensor? obstacle_radius) -> "
           "(Tensor, Tensor, Tensor)");
   lib.def("fleet_assign_delays(Tensor pair, Tensor base, Tensor bad, Tensor? order, int max_delay) -> (Tensor, Tensor, Tensor)");
+  lib.def("spacetime_reserve(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
+          "Tensor? reservation, Tensor? tracks, Tensor? radius, Tensor? visible) -> Tensor");
+  lib.def("spacetime_plan_fleet(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
+          "Tensor start_cells, Tensor goal_cells, Tensor? order, Tensor(a!) reservation) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -541,4 +621,6 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("track_conflicts", &track_conflicts);
   lib.impl("fleet_shift_masks", &fleet_shift_masks);
   lib.impl("fleet_assign_delays", &fleet_assign_delays);
+  lib.impl("spacetime_reserve", &spacetime_reserve);
+  lib.impl("spacetime_plan_fleet", &spacetime_plan_fleet);
 }

@@ -10,6 +10,8 @@ from .conflicts import (CONFLICT_BAD_TRACK, CONFLICT_COUNT, CONFLICT_FIRST_PARTN
                         constant_velocity_tracks, track_conflicts)
 from .schedule import (SCHEDULE_BAD_TRACK, SCHEDULE_MAX_DELAY, SCHEDULE_NOT_ORDERED, SCHEDULE_OK, SCHEDULE_UNRESOLVED, FleetMasks,
                        FleetSchedule, delay_tracks, fleet_shift_masks, schedule_delays)
+from .spacetime import (SPACETIME_BAD_CELL, SPACETIME_DIRECTIONS, SPACETIME_NOT_ORDERED, SPACETIME_OK, SPACETIME_UNREACHED,
+                        SpaceTimePlan, SpaceTimeReservation, spacetime_plan)
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
 from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fields, grid_search_init, grid_search_paths,
                           margin_cells2, seed_polylines, seed_trajectories, shorten_paths)
@@ -45,4 +47,6 @@ __all__ = [
     "CONFLICT_BAD_TRACK", "CONFLICT_NO_PARTNER",
     "FleetMasks", "FleetSchedule", "fleet_shift_masks", "schedule_delays", "delay_tracks", "SCHEDULE_OK", "SCHEDULE_BAD_TRACK",
     "SCHEDULE_UNRESOLVED", "SCHEDULE_NOT_ORDERED", "SCHEDULE_MAX_DELAY",
+    "SpaceTimePlan", "SpaceTimeReservation", "spacetime_plan", "SPACETIME_OK", "SPACETIME_BAD_CELL", "SPACETIME_UNREACHED",
+    "SPACETIME_NOT_ORDERED", "SPACETIME_DIRECTIONS",
 ]

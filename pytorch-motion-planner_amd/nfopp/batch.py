@@ -476,12 +476,24 @@ class BatchPlanner(object):
                                       other_v_max=obstacle_v_max, want_pairs=want_pairs)
 
     def fleet_schedule(self, limits, dt, count, radius, max_delay, margin="chord", order=None, best=False, obstacles=None,
-                       obstacle_radius=None, obstacle_v_max=None, v_start=None, v_goal=None):
+                       obstacle_radius=None, obstacle_v_max=None, v_start=None, v_goal=None, replan=None):
         """The B paths as B robots on one floor that may leave late: time-parametrise under `limits`, sample at k * dt
         (k < count) and give every robot, in priority `order` (None: robot 0 first; "longest_first"; or [B] indices), the
         smallest start delay of 0 .. max_delay grid steps that keeps it clear of the robots scheduled before it and of
         `obstacles` -- a `TimedPaths`, or predicted tracks [M, count + max_delay, >= 2] (then the chord margin needs
-        `obstacle_v_max`) -> nfopp.FleetSchedule.  Nothing here synchronises with device-tensor arguments."""
+        `obstacle_v_max`) -> nfopp.FleetSchedule.  Nothing here synchronises with device-tensor arguments.
+
+        `replan`: an OccupancyGrid (inflated for the robot's footprint).  The robots the schedule could not place are then
+        searched on it in space-time over count + max_delay instants (`FleetSchedule.replan`, with the snap added to the
+        schedule's margin; `radius` must be one number); the schedule comes back with `plan` (an nfopp.SpaceTimePlan) and
+        `merged` [B, count + max_delay, 2].  Without it nothing changes."""
         timed = self.timed_paths(limits, v_start=v_start, v_goal=v_goal, best=best)
-        return timed.schedule(dt, count, max_delay, radius, margin=margin, order=order, other=obstacles,
-                              other_radius=obstacle_radius, other_v_max=obstacle_v_max)
+        sched = timed.schedule(dt, count, max_delay, radius, margin=margin, order=order, other=obstacles,
+                               other_radius=obstacle_radius, other_v_max=obstacle_v_max)
+        if replan is not None:
+            if isinstance(radius, torch.Tensor) or np.ndim(radius) != 0:
+                raise ValueError("replan plans a fleet of one robot radius: radius must be a number")
+            sched.plan, sched.merged = sched.replan(sched.tracks, replan, int(count) + int(max_delay), robot_radius=radius,
+                                                    base_margin=sched.margin, obstacles=sched.obstacles,
+                                                    obstacle_radius=sched.obstacle_radius)
+        return sched

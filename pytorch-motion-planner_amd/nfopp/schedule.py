@@ -31,11 +31,53 @@ class FleetSchedule(object):
     def __init__(self, delay, status, forbidden, max_delay, delay_seconds=None, complete=None):
         self.delay, self.status, self.forbidden, self.max_delay = delay, status, forbidden, max_delay
         self.delay_seconds, self.complete = delay_seconds, complete
+        # set by `TimedPaths.schedule`, for `replan`: the sampled tracks, the margin as a number, the sampled obstacles
+        self.tracks = self.margin = self.obstacles = self.obstacle_radius = None
 
     @property
     def scheduled(self):
         """[B] bool device tensor: the robots that got a delay."""
         return self.status == SCHEDULE_OK
+
+    def replan(self, tracks, grid, count, *, robot_radius, margin="snap", base_margin=0.0, obstacles=None, obstacle_radius=None):
+        """Another path, chosen with time in it, for every robot this schedule left SCHEDULE_UNRESOLVED (`nfopp.spacetime_plan`).
+        `tracks` [B, K, >= 2] are the tracks the schedule was made from.  The scheduled robots' `delay_tracks` over `count`
+        instants become the visible movers (radius `robot_radius`); every unresolved robot is searched on `grid` (an
+        OccupancyGrid, inflated by the caller for the robot's footprint) from the cell of its first sample to the cell of its
+        last, in index order, each against the movers, `obstacles` [M, count, >= 2] and the robots re-planned before it.  A
+        robot with a bad track (SCHEDULE_BAD_TRACK: its samples are not finite, so it has no cells) or one the schedule never
+        visited (SCHEDULE_NOT_ORDERED) is not searched: it comes back SPACETIME_NOT_ORDERED and is not on the floor, as in
+        the schedule.  A re-planned track starts at the centre of its start cell, up to res / sqrt(2) from where the robot
+        stands: `margin="snap"` is `base_margin` (the margin of the schedule) plus that, a number is taken as it is.
+        Everything is built from torch operations on device tensors: nothing synchronises.
+        -> (`SpaceTimePlan`, merged [B, count, 2] fp32: the delayed track of a scheduled robot, the planned track of a
+        re-planned one, NaN rows for every other robot -- it still has no place -- ready for `track_conflicts`)."""
+        from .spacetime import spacetime_plan
+        if isinstance(margin, str):
+            if margin != "snap":
+                raise ValueError("margin must be \"snap\" or a number, got %r" % (margin,))
+            margin = float(base_margin) + grid.resolution / np.sqrt(2.0)
+        b = tracks.shape[0]
+        if self.status.numel() != b:
+            raise ValueError("tracks must be the [B] = [%d] tracks of this schedule, got %d" % (self.status.numel(), b))
+        on = self.scheduled
+        moved = delay_tracks(tracks[:, :, :2], self.delay, count)
+        order = torch.where(self.status == SCHEDULE_UNRESOLVED, torch.arange(b, dtype=torch.int32, device=self.status.device),
+                            torch.full_like(self.status, -1))
+        radius = torch.full((b,), float(np.float32(robot_radius)), dtype=torch.float32, device=moved.device)
+        visible = on
+        if obstacles is not None:
+            m = obstacles.shape[0]
+            moved_all = torch.cat([moved, obstacles[:, :, :2].to(torch.float32)], 0).contiguous()
+            radius = torch.cat([radius, per_row(0.0 if obstacle_radius is None else obstacle_radius, m, moved.device, "obstacle_radius")])
+            visible = torch.cat([on, torch.ones(m, dtype=torch.bool, device=on.device)])
+        else:
+            moved_all = moved
+        plan = spacetime_plan(grid, tracks[:, 0, :2], tracks[:, -1, :2], count, robot_radius=robot_radius, margin=margin, tracks=moved_all,
+                              track_radius=radius, visible=visible, order=order)
+        merged = torch.where(plan.planned[:, None, None], plan.tracks,
+                             torch.where(on[:, None, None], moved, torch.full_like(moved, float("nan"))))
+        return plan, merged
 
 
 class FleetMasks(object):

@@ -133,12 +133,15 @@ class TimedPaths(object):
             if order != "longest_first":
                 raise ValueError("order must be None, \"longest_first\" or [B] indices, got %r" % (order,))
             order = torch.argsort(total, descending=True, stable=True)
-        masks = fleet_shift_masks(self.sample(dt, count), max_delay=max_delay, radius=radius, margin=margin, obstacles=obstacles,
+        states = self.sample(dt, count)
+        masks = fleet_shift_masks(states, max_delay=max_delay, radius=radius, margin=margin, obstacles=obstacles,
                                   obstacle_radius=other_radius)
         out = masks.assign(order)
         step = torch.tensor(float(dt), dtype=torch.float64, device=out.delay.device)
         out.delay_seconds = torch.where(out.delay >= 0, out.delay.double() * step, torch.full_like(step, float("nan")))
         out.complete = total <= (count - 1) * float(dt)
+        # what FleetSchedule.replan goes on from: the sampled tracks, the margin as a number, the obstacles as sampled
+        out.tracks, out.margin, out.obstacles, out.obstacle_radius = states, margin, obstacles, other_radius
         return out
 
 

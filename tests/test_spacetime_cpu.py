@@ -1,0 +1,514 @@
+"""CPU: the rule of nfopp_spacetime_reserve / nfopp_spacetime_plan_fleet as restated in tests/spacetime_ref.py -- hand cases on
+dyadic geometry with exact expectations, minimality against an enumeration of all move sequences, the tie-break against a
+second (recursive) statement, the end-to-end statement through tests/track_conflict_ref.py, the circle fleet of the schedule
+tests re-planned, coverage of the case set computed from the restatement -- and the interface: header, binding and library
+agree, every argument check answers without a GPU, the Python names and their checks exist."""
+import ctypes
+import functools
+import inspect
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+
+import nfopp
+from nfopp import _lib, torch_ops
+from nfopp import spacetime as ns
+
+import fleet_schedule_cases as fc
+import fleet_schedule_ref as fr
+import spacetime_cases as sc
+import spacetime_ref as sr
+import track_conflict_ref as tr
+
+F32 = np.float32
+INF = np.inf
+
+
+# ---- hand cases ------------------------------------------------------------------------------------------------------------
+def test_corridor_with_a_bay():
+    _, _, p = sc.solve(sc.corridor())
+    assert p["status"].tolist() == [0, 0] and p["arrival"][0] == 6
+    assert p["cells"][0].tolist() == [7, 8, 9, 10, 11, 12] + [13] * 6            # robot 0 goes straight along row 1
+    assert 3 in p["cells"][1].tolist() and p["cells"][1][0] == 13 and p["cells"][1][-1] == 7     # robot 1 takes the bay (0, 3)
+    for T in (7, 12, 20):                                                        # the bay walled: no way past, whatever T
+        _, _, q = sc.solve(sc.corridor(T, bay=False))
+        assert q["status"].tolist() == [0, sr.STATUS_UNREACHED] and q["arrival"].tolist() == [6, -1]
+        assert (q["cells"][1] == -1).all() and np.isnan(q["tracks"][1]).all()
+    _, _, r = sc.solve(sc.corridor(order=[1, 0]))                                # reversed: robot 0 is the one that gives way
+    assert r["status"].tolist() == [0, 0] and r["cells"][1].tolist() == [13, 12, 11, 10, 9, 8] + [7] * 6 and 3 in r["cells"][0].tolist()
+
+
+def test_gate_costs_exactly_the_ticks_of_the_hand_count_and_the_waits_are_where_the_tie_break_puts_them():
+    """An open 1 x 8 corridor, a mover on cell 4 during instants 2 .. 6.  Unobstructed the robot arrives at 7.  It is on cell 3
+    at instant 3 and may enter cell 4 over the interval 6 -> 7 at the earliest (the mover leaves sideways then, closest approach
+    just under 1): three ticks lost, arrival 10.  Backwards from the goal the lowest direction that holds is a move (0, +1) down
+    to (cell 0, instant 3); there (0, -1) from cell 1 holds before the wait does, and so on: the slack is spent at the start."""
+    c = sc.gate()
+    _, _, p = sc.solve(c)
+    free = sc.solve(dict(c, tracks=None))[2]
+    assert free["arrival"].tolist() == [7] and p["arrival"].tolist() == [7 + 3]
+    assert p["cells"][0].tolist() == [0, 0, 1, 0, 1, 2, 3, 4, 5, 6, 7, 7]
+
+
+def test_a_mover_parked_on_the_goal_and_one_that_leaves():
+    _, _, p = sc.solve(sc.parked_on_goal())
+    assert p["status"].tolist() == [sr.STATUS_UNREACHED]
+    for leaves in (5, 6, 8):                                                     # away from instant `leaves` on: park holds from there
+        res, _, p = sc.solve(sc.parked_on_goal(leaves=leaves))
+        assert p["status"].tolist() == [0] and p["arrival"].tolist() == [leaves]
+        assert res.blocked[leaves - 1, sr.WAIT, 0, 3] and not res.blocked[leaves:, sr.WAIT, 0, 3].any() and not res.last[0, 3]
+
+
+def test_a_single_instant():
+    assert sc.solve(sc.single_instant((0, 0), False))[2]["status"].tolist() == [0]
+    res, _, p = sc.solve(sc.single_instant((0, 0), True))                        # only `last` can say so
+    assert p["status"].tolist() == [sr.STATUS_UNREACHED] and res.last[0, 0] and res.blocked.size == 0
+    assert sc.solve(sc.single_instant((0, 1), False))[2]["status"].tolist() == [sr.STATUS_UNREACHED]
+
+
+def test_strictness_and_bad_cells():
+    res, _, p = sc.solve(sc.strict(False))                                       # exactly R from two cell centres: standing there is free
+    mover = mover_only(sc.strict(False))
+    assert not mover[0][:, sr.WAIT].any() and not mover[1].any() and p["status"].tolist() == [0]
+    assert mover[0][:, 0, 0, 0].all() and mover[0][:, 1, 0, 1].all()             # while a move between the two cells runs it over
+    res, _, p = sc.solve(sc.strict(True))                                        # one fp32 step closer to cell 0
+    mover = mover_only(sc.strict(True))
+    assert mover[1].tolist() == [[True, False, False]] and mover[0][:, sr.WAIT, 0].tolist() == [[True, False, False]] * 2
+    assert p["status"].tolist() == [sr.STATUS_UNREACHED]
+    occ = np.zeros((2, 3), np.uint8)
+    occ[1, 1] = 1
+    for start, goal in (((1, 1), (0, 0)), ((0, 0), (1, 1)), ((-1, 0), (0, 0)), ((0, 3), (0, 0)), ((0, 0), (2, 0)), ((0, 0), (0, -1))):
+        _, _, p = sc.solve(sc.case(occ, 4, [start], [goal]))
+        assert p["status"].tolist() == [sr.STATUS_BAD_CELL] and p["arrival"].tolist() == [-1], (start, goal)
+
+
+def mover_only(c):
+    return sr.mover_bits(c["geo"], c["T"], c["tracks"], c["radius"], c["visible"], c["robot_radius"], c["margin"])
+
+
+# ---- minimality, independently of the restatement's own search -------------------------------------------------------------
+def small_cases():
+    """Images up to 3 x 4 with walls, T <= 5, a mover that wanders over the floor."""
+    rng = np.random.default_rng(5)
+    for k in range(40):
+        rows, cols, T = rng.integers(1, 4), rng.integers(1, 5), int(rng.integers(1, 6))
+        occ = (rng.uniform(size=(rows, cols)) < 0.2).astype(np.uint8)
+        free = np.argwhere(occ == 0)
+        if len(free) == 0:
+            continue
+        s, g = free[rng.integers(len(free))], free[rng.integers(len(free))]
+        walk = np.cumsum(rng.integers(-1, 2, (T, 2)), axis=0) + rng.integers(0, 3, 2) + 0.5
+        tracks = None if k % 4 == 0 else [walk.astype(F32)]
+        yield sc.case(occ, T, [s], [g], tracks=tracks)
+
+
+def enumerated_arrival(res, start, goal):
+    """The earliest instant from which some sequence of T - 1 moves stands on the goal to the end, over ALL 9^(T-1) sequences."""
+    best = None
+    for moves in itertools.product(range(9), repeat=res.T - 1):
+        v, path = tuple(start), [tuple(start)]
+        for h, d in enumerate(moves):
+            if res.blocked[h, d, v[0], v[1]]:
+                break
+            v = (v[0] + sr.DIRS[d][0], v[1] + sr.DIRS[d][1])
+            path.append(v)
+        else:
+            if v != tuple(goal) or res.last[v]:
+                continue
+            h = res.T - 1
+            while h > 0 and path[h - 1] == tuple(goal) and moves[h - 1] == sr.WAIT:
+                h -= 1
+            best = h if best is None else min(best, h)
+    return best
+
+
+def test_arrival_is_minimal_over_all_move_sequences():
+    reached = missed = 0
+    for c in small_cases():
+        res, _, p = sc.solve(c)
+        want = enumerated_arrival(res, c["starts"][0], c["goals"][0])
+        if want is None:
+            assert p["status"].tolist() == [sr.STATUS_UNREACHED], c
+            missed += 1
+        else:
+            assert p["status"].tolist() == [0] and p["arrival"].tolist() == [want], (c, want)
+            reached += 1
+    assert reached >= 10 and missed >= 3
+
+
+# ---- the tie-break, by a second statement -----------------------------------------------------------------------------------
+def recursive_path(res, start, goal, arrival):
+    """reach and the predecessor as recursive functions of (cell, instant), without the restatement's arrays."""
+    geo = res.geo
+
+    @functools.lru_cache(maxsize=None)
+    def reach(v, h):
+        if h == 0:
+            return v == start
+        return any(edge(v, d, h) for d in range(9))
+
+    def edge(v, d, h):                                                           # (v - d, d, h - 1) is open and its source reached
+        u = (v[0] - sr.DIRS[d][0], v[1] - sr.DIRS[d][1])
+        return sr.inside(geo, u) and not res.blocked[h - 1, d, u[0], u[1]] and reach(u, h - 1)
+
+    def back(v, h):
+        if h == 0:
+            return [v]
+        d = next(d for d in range(9) if edge(v, d, h))
+        return back((v[0] - sr.DIRS[d][0], v[1] - sr.DIRS[d][1]), h - 1) + [v]
+
+    return back(goal, arrival) + [goal] * (res.T - 1 - arrival)
+
+
+def test_the_returned_path_is_the_one_the_lowest_direction_rule_defines(solved):
+    seen = 0
+    for name, c, before, after, p in solved:
+        if c["geo"].rows * c["geo"].cols > 700:
+            continue
+        res = before.copy()
+        for i in np.flatnonzero(p["status"] >= 0) if c["order"] is None else []:
+            if p["status"][i] == 0:
+                path = recursive_path(res, tuple(int(x) for x in c["starts"][i]), tuple(int(x) for x in c["goals"][i]), int(p["arrival"][i]))
+                assert [r * c["geo"].cols + q for r, q in path] == p["cells"][i].tolist(), (name, i)
+                res.add(p["tracks"][i:i + 1], radius=res.robot_radius)
+                seen += 1
+    assert seen >= 12
+
+
+# ---- the families -----------------------------------------------------------------------------------------------------------
+def _families():
+    for n in range(len(sc.SIZES)):
+        yield "sized_%d" % n, sc.sized_case(n)
+    yield "sized_6_odd", dict(sc.sized_case(6), order=sc.orders(8, seed=6)["odd"])
+    yield "sized_6_perm", dict(sc.sized_case(6), order=sc.orders(8, seed=6)["permutation"])
+    for name, c in (("corridor", sc.corridor()), ("corridor_reversed", sc.corridor(order=[1, 0])), ("no_bay", sc.corridor(bay=False)),
+                    ("gate", sc.gate()), ("parked", sc.parked_on_goal()), ("leaves", sc.parked_on_goal(leaves=6)),
+                    ("single", sc.single_instant((0, 0), True)), ("strict", sc.strict(True))):
+        yield name, c
+
+
+@pytest.fixture(scope="module")
+def solved():
+    return [(name, c) + sc.solve(c) for name, c in _families()]
+
+
+def test_nobody_planned_is_in_conflict_by_the_conflict_check(solved):
+    seen = 0
+    for name, c, before, after, p in solved:
+        on = np.flatnonzero(p["status"] == 0)
+        if not len(on):
+            continue
+        rr = np.full(len(on), c["robot_radius"], F32)
+        fleet = tr.conflicts(p["tracks"][on], None, dt=1.0, radius_a=rr, margin=c["margin"])
+        assert not (fleet["pair_first"] < INF).any(), name
+        seen += int(len(on) >= 2)
+        if c["tracks"] is not None:
+            good = sr.good_tracks(c["tracks"], c["radius"], c["visible"])
+            floor = tr.conflicts(p["tracks"][on], c["tracks"][good][:, :, :2], dt=1.0, radius_a=rr, radius_b=c["radius"][good], margin=c["margin"])
+            assert not (floor["pair_first"] < INF).any(), name
+    assert seen >= 6
+
+
+def test_blocked_and_last_are_the_conflict_check_on_two_sample_tracks(solved):
+    """Sampled (u, d, h, j): the bit a mover sets is `pair_first < inf` of the robot's move over that one interval against the
+    mover's, as two-sample tracks; `last` is the same on one-sample tracks."""
+    rng = np.random.default_rng(11)
+    hits = misses = 0
+    for name, c, before, after, p in solved:
+        if c["tracks"] is None or c["T"] < 2:
+            continue
+        geo, T = c["geo"], c["T"]
+        good = np.flatnonzero(sr.good_tracks(c["tracks"], c["radius"], c["visible"]))
+        if not len(good):
+            continue
+        mover = mover_only(c)
+        set_bits = np.argwhere(mover[0])
+        for k in range(60):                                                      # half anywhere, half where a mover set a bit
+            h, d, r, q = rng.integers(T - 1), rng.integers(9), rng.integers(geo.rows), rng.integers(geo.cols)
+            if k % 2 and len(set_bits):
+                h, d, r, q = set_bits[rng.integers(len(set_bits))]
+            v = (r + sr.DIRS[d][0], q + sr.DIRS[d][1])
+            if not sr.inside(geo, v):
+                continue
+            a = np.stack([geo.centre_of(r, q), geo.centre_of(*v)])[None]
+            b = c["tracks"][good][:, h:h + 2, :2]
+            two = tr.conflicts(a, b, dt=1.0, radius_a=c["robot_radius"], radius_b=c["radius"][good], margin=c["margin"])
+            assert bool((two["pair_first"] < INF).any()) == bool(mover[0][h, d, r, q]), (name, h, d, r, q)
+            hits += int(mover[0][h, d, r, q])
+            misses += int(not mover[0][h, d, r, q])
+            one = tr.conflicts(a[:, :1], c["tracks"][good][:, -1:, :2], dt=1.0, radius_a=c["robot_radius"], radius_b=c["radius"][good],
+                               margin=c["margin"])
+            assert bool((one["pair_first"] < INF).any()) == bool(mover[1][r, q]), (name, r, q)
+    assert hits >= 20 and misses >= 100
+
+
+def test_the_circle_fleet_the_schedule_cannot_place_is_replanned_and_clear():
+    """fleet_schedule_cases.circle(16, 18, 7) -- D = 8 candidate delays: 8 of 16 unresolved.  On a wall-free 24 x 24 grid of
+    0.25 m over 41 instants, with the snap added to the schedule's margin, all 8 are placed; the 16 tracks are clear."""
+    case, geo, count = sc.circle_replan()
+    _, s = fc.solve(case)
+    assert (s["status"] == fr.STATUS_UNRESOLVED).sum() == 8 and (s["status"] == 0).sum() == 8
+    c, plan, merged = sc.replan_ref(case, s, geo, count)
+    off = s["status"] != 0
+    assert (plan["status"][off] == 0).all() and (plan["status"][~off] == sr.STATUS_NOT_ORDERED).all()
+    assert not np.isnan(merged).any() and (plan["arrival"][off] < count - 1).all()
+    found = tr.conflicts(merged, None, dt=1.0, radius_a=case["radius"], margin=case["margin"])
+    assert not (found["pair_first"] < INF).any()
+    # a re-planned track starts within the snap of where the robot stands and ends in the cell of its goal
+    d0 = np.linalg.norm(merged[off, 0] - case["tracks"][off, 0, :2], axis=1)
+    assert (d0 <= geo.res / np.sqrt(2.0) + 1e-6).all() and (d0 > 0).any()
+    d1 = np.abs(merged[off, -1] - case["tracks"][off, -1, :2]).max()
+    assert d1 <= geo.res / 2 + 1e-6
+
+
+def test_replan_searches_the_unresolved_robots_only():
+    """A robot with a bad track (its samples are NaN: it has no cells) and robots the schedule never visited are not searched:
+    NOT_ORDERED from the plan, NaN rows in the merged tracks, nothing reserved -- not a phantom robot on some corner cell."""
+    case, geo, count = sc.circle_replan_odd()
+    _, s = fc.solve(case)
+    st = s["status"]
+    assert set(st.tolist()) == {0, fr.STATUS_BAD_TRACK, fr.STATUS_UNRESOLVED, fr.STATUS_NOT_ORDERED} and st[5] == fr.STATUS_BAD_TRACK
+    c, plan, merged = sc.replan_ref(case, s, geo, count)
+    unresolved, on = st == fr.STATUS_UNRESOLVED, st == 0
+    assert (c["order"][unresolved] == np.flatnonzero(unresolved)).all() and (c["order"][~unresolved] == -1).all()
+    assert (plan["status"][~unresolved] == sr.STATUS_NOT_ORDERED).all() and (plan["status"][unresolved] != sr.STATUS_NOT_ORDERED).all()
+    assert (plan["status"][unresolved] == 0).any()
+    off = ~on & (plan["status"] != 0)
+    assert off[5] and off[st == fr.STATUS_NOT_ORDERED].all() and np.isnan(merged[off]).all() and not np.isnan(merged[~off]).any()
+    assert (plan["cells"][off] == -1).all() and (plan["arrival"][off] == -1).all()
+    floor = np.flatnonzero(~off)
+    found = tr.conflicts(merged[floor], None, dt=1.0, radius_a=case["radius"][floor], margin=case["margin"])
+    assert not (found["pair_first"] < INF).any()
+
+
+def test_reordering_is_relabelling_and_odd_orders_skip(solved):
+    by = {name: (c, p) for name, c, before, after, p in solved}
+    c, ident = by["sized_6"]
+    _, perm_plan = by["sized_6_perm"]
+    perm = sc.orders(8, seed=6)["permutation"]
+    moved = dict(c, starts=c["starts"][perm], goals=c["goals"][perm], order=None)
+    want = sc.solve(moved)[2]
+    for key in ("status", "arrival", "cells"):
+        assert np.array_equal(perm_plan[key][perm], want[key]), key
+    assert not np.array_equal(by["corridor"][1]["cells"], by["corridor_reversed"][1]["cells"])      # an order that matters
+    _, odd_plan = by["sized_6_odd"]
+    odd = sc.orders(8, seed=6)["odd"]
+    visited = [i for n, i in enumerate(odd) if 0 <= i < 8 and i not in odd[:n].tolist()]
+    missing = sorted(set(range(8)) - set(visited))
+    assert len(missing) >= 2 and (odd_plan["status"][missing] == sr.STATUS_NOT_ORDERED).all() and (odd_plan["arrival"][missing] == -1).all()
+    assert (odd_plan["cells"][missing] == -1).all() and np.isnan(odd_plan["tracks"][missing]).all()
+    keep = np.array(visited)
+    sub = sc.solve(dict(c, starts=c["starts"][keep], goals=c["goals"][keep], order=None))[2]
+    for key in ("status", "arrival", "cells"):
+        assert np.array_equal(odd_plan[key][keep], sub[key]), key
+
+
+# ---- coverage, computed from the restatement ---------------------------------------------------------------------------------
+def test_case_set_covers_what_it_claims(solved):
+    statuses, dirs = set(), set()
+    for name, c, before, after, p in solved:
+        statuses |= set(p["status"].tolist())
+        for i in np.flatnonzero(p["status"] == 0):
+            dirs |= set(p["dirs"][i])
+    assert statuses == {0, sr.STATUS_BAD_CELL, sr.STATUS_UNREACHED, sr.STATUS_NOT_ORDERED}
+    assert dirs == set(range(9))                                                 # every direction in some returned path
+    c = sc.sized_case(6)
+    _, _, br = sr.mover_bits(c["geo"], c["T"], c["tracks"], c["radius"], c["visible"], c["robot_radius"], c["margin"], want_branches=True)
+    assert br["start"].any() and br["end"].any() and br["interior"].any()        # a blocked bit from each closest_approach branch
+    single = mover_only(sc.single_instant((0, 0), True))                         # a last-only block: nothing else exists at T = 1
+    assert single[1].any() and single[0].size == 0
+    c = sc.sized_case(7)                                                         # three words a row: bits in the first and the last
+    blocked, last = mover_only(c)
+    wb, wl = sr.pack_rows(blocked, False), sr.pack_rows(last, False)
+    assert wb.shape[-1] == 3 and wb[..., 0].any() and wb[..., 2].any() and wl[..., 0].any() and wl[..., 2].any()
+    # the planted bad mover, NaN radius and invisible mover are skipped, and each would have set bits
+    good = sr.good_tracks(c["tracks"], c["radius"], c["visible"])
+    assert (~good).sum() == 3 and good[1] and good[2]
+    seen = dict(c, tracks=np.where(np.isfinite(c["tracks"][:, :, :2]), c["tracks"][:, :, :2], 0).astype(F32), visible=None,
+                radius=np.where(np.isfinite(c["radius"]), c["radius"], F32(0.05)))
+    assert (sr.pack_rows(mover_only(seen)[0], False) != wb).any()
+
+
+def test_pack_rows_layout():
+    bits = np.zeros((2, 65), bool)
+    bits[0, [0, 63, 64]] = True
+    w = sr.pack_rows(bits, True)
+    assert w.shape == (2, 2) and [int(x) for x in w[0]] == [1 | 1 << 63, 2 ** 64 - 1] and [int(x) for x in w[1]] == [0, 2 ** 64 - 2]
+    assert [int(x) for x in sr.pack_rows(bits, False)[0]] == [1 | 1 << 63, 1]
+    assert np.array_equal(sr.unpack_rows(w, 65), bits)
+    geo = sr.Geometry(2, 3, -0.3, 0.2, 0.1)
+    x, y = geo.centres()
+    assert x.dtype == F32 and np.array_equal(x, (np.arange(3) * 0.1 + 0.1 / 2 + -0.3).astype(F32)) and np.array_equal(geo.centre_of(1, 2), [x[2], y[1]])
+    gx, gy, _, _ = nfopp.grid_search._cell_centres((-0.3, 0.0, 0.2, 0.4), 0.1)
+    assert np.array_equal(gx[:3].astype(F32), x)
+
+
+# ---- interface -------------------------------------------------------------------------------------------------------------
+ENTRIES = (("nfopp_spacetime_reservation_bytes", 3, "size_t", ctypes.c_size_t), ("nfopp_spacetime_reservation_init", 7, "int", ctypes.c_int),
+           ("nfopp_spacetime_reserve_workspace_bytes", 1, "size_t", ctypes.c_size_t), ("nfopp_spacetime_reserve", 18, "int", ctypes.c_int),
+           ("nfopp_spacetime_plan_workspace_bytes", 4, "size_t", ctypes.c_size_t), ("nfopp_spacetime_plan_fleet", 22, "int", ctypes.c_int))
+
+
+def test_header_binding_and_library_agree():
+    lib = nfopp.load_library()
+    header = open(os.path.join(ROOT, "include", "nfopp_hip.h")).read()
+    for name, n_args, res, ctype in ENTRIES:
+        decl = re.search(r"\b%s %s\(([^;]*)\);" % (res, name), header)
+        assert decl and len(decl.group(1).split(",")) == n_args, name
+        assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
+        assert len(_lib._SIGNATURES[name][1]) == n_args and _lib._SIGNATURES[name][0] is ctype
+    assert lib.nfopp_abi_version() == 6
+    for name, value in (("BAD_CELL", sr.STATUS_BAD_CELL), ("UNREACHED", sr.STATUS_UNREACHED), ("NOT_ORDERED", sr.STATUS_NOT_ORDERED)):
+        assert "#define NFOPP_SPACETIME_%s %d" % (name, value) in header, name
+        assert getattr(nfopp, "SPACETIME_" + name) == value
+    assert nfopp.SPACETIME_DIRECTIONS == sr.DIRS
+    csrc = os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc")
+    assert "spacetime_search.hip" in open(os.path.join(csrc, "Makefile")).read()
+    src = open(os.path.join(csrc, "spacetime_search.hip")).read()
+    assert "#pragma clang fp contract(off)" in src and '#include "track_pairs.h"' in src and '#include "block_collectives.h"' in src
+    table = re.search(r"ST_DROW\[ST_DIRS\] = \{([^}]*)\};\s*constexpr int ST_DCOL\[ST_DIRS\] = \{([^}]*)\};", src)
+    assert tuple(zip(*[[int(x) for x in g.split(",")] for g in table.groups()])) == sr.DIRS
+    for word in ("the wait is last", "lowest d", "source cell", "padding bits", "by construction"):
+        assert word in header, word
+
+
+def _P(v):
+    return ctypes.c_void_p(v) if v else None
+
+
+def _init_rc(rows=3, cols=7, t=4, occ=1, res=1, nbytes=1 << 20):
+    return nfopp.load_library().nfopp_spacetime_reservation_init(_P(occ), rows, cols, t, _P(res), nbytes, None)
+
+
+def _reserve_rc(rows=3, cols=7, t=4, b0=0.0, b2=0.0, resolution=1.0, robot_radius=0.25, margin=0.0, tracks=1, m=2, stride=2, res=1,
+                nbytes=1 << 20, ws=1, ws_bytes=1 << 10):
+    return nfopp.load_library().nfopp_spacetime_reserve(rows, cols, t, b0, b2, resolution, robot_radius, margin, _P(tracks), m, stride, None,
+                                                        None, _P(res), nbytes, _P(ws), ws_bytes, None)
+
+
+def _plan_rc(rows=3, cols=7, t=4, b0=0.0, b2=0.0, resolution=1.0, robot_radius=0.25, margin=0.0, robots=2, nbytes=1 << 20, ws=1,
+             ws_bytes=1 << 20, **null):
+    p = dict(occ=1, starts=1, goals=1, res=1, cells=1, arrival=1, status=1, tracks=1)
+    p.update(null)
+    return nfopp.load_library().nfopp_spacetime_plan_fleet(_P(p["occ"]), rows, cols, t, b0, b2, resolution, robot_radius, margin,
+                                                           _P(p["starts"]), _P(p["goals"]), None, robots, _P(p["res"]), nbytes, _P(p["cells"]),
+                                                           _P(p["arrival"]), _P(p["status"]), _P(p["tracks"]), _P(ws), ws_bytes, None)
+
+
+def test_every_argument_check_answers_without_a_gpu():
+    lib = nfopp.load_library()
+
+    def refused(rc, word):
+        assert rc == -1, word
+        assert word in lib.nfopp_last_error().decode(), (word, lib.nfopp_last_error())
+
+    for call in (_init_rc, _reserve_rc, _plan_rc):
+        refused(call(t=0), "T >= 1")
+        refused(call(rows=0), "at least one cell")
+        refused(call(cols=-1), "at least one cell")
+        refused(call(rows=2 ** 16, cols=2 ** 16), "too large for an index")
+        refused(call(rows=1024, cols=1024, t=2 ** 15), "too large for an index")
+        refused(call(nbytes=((4 - 1) * 9 + 1) * 3 * 8 - 1), "reservation too small")
+    for call in (_reserve_rc, _plan_rc):
+        for bad in (np.nan, np.inf):
+            refused(call(b0=bad), "resolution")
+            refused(call(b2=bad), "resolution")
+            refused(call(resolution=bad), "resolution")
+            refused(call(robot_radius=bad), "robot_radius")
+            refused(call(margin=bad), "margin")
+        refused(call(resolution=0.0), "resolution")
+        refused(call(resolution=-1.0), "resolution")
+    refused(_init_rc(occ=0), "null device pointer")
+    refused(_init_rc(res=0), "null device pointer")
+    refused(_reserve_rc(m=-1), "batch")
+    refused(_reserve_rc(m=2 ** 31), "batch")
+    refused(_reserve_rc(stride=1), "stride")
+    refused(_reserve_rc(res=0), "null device pointer")
+    refused(_reserve_rc(tracks=0), "null device pointer")
+    assert _reserve_rc(m=0, tracks=0, ws=0, ws_bytes=0) == 0                     # nothing to do
+    assert lib.nfopp_spacetime_reserve_workspace_bytes(0) == 0
+    for m in (1, 2, 17):
+        need = lib.nfopp_spacetime_reserve_workspace_bytes(m)
+        assert need >= 4 * m and need % 8 == 0
+        refused(_reserve_rc(m=m, ws_bytes=need - 1), "workspace")
+        refused(_reserve_rc(m=m, ws=0, ws_bytes=need), "workspace")
+    refused(_plan_rc(robots=-1), "batch")
+    refused(_plan_rc(robots=2 ** 31), "batch")
+    for null in ("occ", "starts", "goals", "res", "cells", "arrival", "status", "tracks"):
+        refused(_plan_rc(**{null: 0}), "null device pointer")
+    assert _plan_rc(robots=0, occ=0, starts=0, goals=0, res=0, cells=0, arrival=0, status=0, tracks=0, ws=0, ws_bytes=0) == 0
+    # both frontiers of a search sit in one workgroup's LDS: 2 * rows * W * 8 + 64 bytes in 160 KiB
+    assert _plan_rc(rows=10236, cols=64, t=1, robots=0) == 0
+    refused(_plan_rc(rows=10237, cols=64, t=1, robots=0), "frontier too large")
+    refused(_plan_rc(rows=1024, cols=1024, t=2), "frontier too large")
+    # the workspace: reach of every instant and a word of state per robot
+    for rows, cols, t, robots in ((3, 7, 4, 2), (5, 65, 9, 3), (1, 1, 1, 1)):
+        need = lib.nfopp_spacetime_plan_workspace_bytes(rows, cols, t, robots)
+        assert need >= t * rows * -(-cols // 64) * 8 + 4 * robots
+        refused(_plan_rc(rows=rows, cols=cols, t=t, robots=robots, ws_bytes=need - 1), "workspace")
+        refused(_plan_rc(rows=rows, cols=cols, t=t, robots=robots, ws=0, ws_bytes=need), "workspace")
+    assert lib.nfopp_spacetime_plan_workspace_bytes(3, 7, 0, 2) == 0 == lib.nfopp_spacetime_plan_workspace_bytes(3, 7, 4, 0)
+    assert lib.nfopp_spacetime_reservation_bytes(3, 7, 4) == ((4 - 1) * 9 + 1) * 3 * 8 and lib.nfopp_spacetime_reservation_bytes(3, 7, 0) == 0
+    assert lib.nfopp_spacetime_reservation_bytes(5, 65, 1) == 5 * 2 * 8 and lib.nfopp_spacetime_reservation_bytes(2 ** 16, 2 ** 16, 2) == 0
+
+
+def test_python_names_signatures_and_checks():
+    for name in ("SpaceTimePlan", "SpaceTimeReservation", "spacetime_plan", "SPACETIME_OK", "SPACETIME_BAD_CELL", "SPACETIME_UNREACHED",
+                 "SPACETIME_NOT_ORDERED", "SPACETIME_DIRECTIONS"):
+        assert hasattr(nfopp, name) and name in nfopp.__all__, name
+    assert (nfopp.SpaceTimePlan.OK, nfopp.SpaceTimePlan.BAD_CELL, nfopp.SpaceTimePlan.UNREACHED, nfopp.SpaceTimePlan.NOT_ORDERED) == (0, 1, 2, 3)
+    sig = inspect.signature(nfopp.spacetime_plan).parameters
+    assert list(sig) == ["grid", "starts", "goals", "count", "robot_radius", "margin", "tracks", "track_radius", "visible", "order", "reservation"]
+    assert sig["robot_radius"].kind is inspect.Parameter.KEYWORD_ONLY and sig["robot_radius"].default is inspect.Parameter.empty
+    assert list(inspect.signature(nfopp.SpaceTimeReservation.__init__).parameters) == ["self", "grid", "count", "robot_radius", "margin"]
+    assert list(inspect.signature(nfopp.SpaceTimeReservation.add).parameters) == ["self", "tracks", "radius", "visible"]
+    rp = inspect.signature(nfopp.FleetSchedule.replan).parameters
+    assert list(rp)[:4] == ["self", "tracks", "grid", "count"] and rp["robot_radius"].kind is inspect.Parameter.KEYWORD_ONLY
+    assert rp["margin"].default == "snap"
+    fs = inspect.signature(nfopp.BatchPlanner.fleet_schedule).parameters
+    assert fs["replan"].default is None and list(fs)[-1] == "replan"
+    plan = nfopp.SpaceTimePlan(torch.zeros(2, 3, dtype=torch.int32), torch.tensor([1, -1]), torch.tensor([0, 2]), torch.zeros(2, 3, 2), None)
+    assert plan.planned.tolist() == [True, False]
+    grid = nfopp.OccupancyGrid(np.zeros((3, 7), np.uint8), (0.0, 7.0, 0.0, 3.0), 1.0)
+    for count in (0, -1, 2.5):
+        with pytest.raises(ValueError, match="count"):
+            nfopp.SpaceTimeReservation(grid, count, 0.25)
+        with pytest.raises(ValueError, match="count"):
+            nfopp.spacetime_plan(grid, [(0, 0)], [(0, 1)], count, robot_radius=0.25)
+    with pytest.raises(ValueError, match="robot_radius"):
+        nfopp.SpaceTimeReservation(grid, 4, np.nan)
+    with pytest.raises(ValueError, match="margin"):
+        nfopp.SpaceTimeReservation(grid, 4, 0.25, np.inf)
+    with pytest.raises(ValueError, match="int32"):
+        nfopp.SpaceTimeReservation(nfopp.OccupancyGrid(np.zeros((1024, 1024), np.uint8), (0, 1, 0, 1), 1.0), 2 ** 15, 0.25)
+    assert ns._cells(grid, [(0, 0), (2, 6)], "starts", "cpu").tolist() == [[0, 0], [2, 6]]
+    assert ns._cells(grid, [(0.5, 2.5), (6.5, 0.25)], "starts", "cpu").tolist() == [[2, 0], [0, 6]]      # points are (x, y)
+    for bad in (np.zeros(3), np.zeros((2, 4)), np.zeros((2, 3), np.int64)):
+        with pytest.raises(ValueError, match="starts"):
+            ns._cells(grid, bad, "starts", "cpu")
+    sched = nfopp.FleetSchedule(torch.tensor([0, -1]), torch.tensor([0, 2]), torch.tensor([0, 3]), 1)
+    assert sched.tracks is None and sched.margin is None
+    with pytest.raises(ValueError, match="snap"):
+        sched.replan(torch.zeros(2, 3, 2), grid, 4, robot_radius=0.25, margin="snip")
+    with pytest.raises(ValueError, match="tracks of this schedule"):
+        sched.replan(torch.zeros(3, 3, 2), grid, 4, robot_radius=0.25)
+
+
+def test_the_torch_ops_are_registered_and_refuse_cpu_tensors():
+    assert "spacetime_reserve" in torch_ops.OPS and "spacetime_plan_fleet" in torch_ops.OPS
+    ops = torch_ops.load()
+    assert "Tensor(a!) reservation" in str(torch.ops.nfopp.spacetime_plan_fleet.default._schema)
+    occ = torch.zeros(3, 7, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.spacetime_reserve(occ, 4, 0.0, 0.0, 1.0, 0.25, 0.0, None, None, None, None)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ops.spacetime_plan_fleet(occ, 4, 0.0, 0.0, 1.0, 0.25, 0.0, torch.zeros(1, 2, dtype=torch.int32), torch.zeros(1, 2, dtype=torch.int32),
+                                 None, torch.zeros(84, dtype=torch.int64))
+    with pytest.raises(nfopp.NfoppError, match="no HIP device|no CPU path|HIP"):
+        nfopp.SpaceTimeReservation(nfopp.OccupancyGrid(np.zeros((3, 7), np.uint8), (0.0, 7.0, 0.0, 3.0), 1.0), 4, 0.25)
