@@ -686,6 +686,59 @@ int nfopp_grid_seed_polylines(const float* points_dev, const int32_t* count_dev,
                               int32_t dim, int32_t angles_with_direction, float* traj_dev, void* workspace_dev,
                               size_t workspace_bytes, void* stream);
 
+/* ---- heading-aware lattice search for car-like seeds (csrc/lattice_search.hip), additive under ABI 6 ---------------------
+ * A search over (cell, heading) states whose cell paths go through nfopp_grid_seed_trajectories unchanged
+ * (nfopp/lattice.py: LatticeGrid, lattice_fields, lattice_search_paths, lattice_search_init).  The rule is this library's
+ * own; the reference has no such search.  tests/lattice_ref.py restates it in numpy and the device is compared with ==.
+ *
+ * State: (cell (row, col), heading h in 0 .. 7); heading h stands for the angle h * pi / 4.
+ * Directions dir(h) as (d row, d col), row = y and col = x as in the occupancy grid:
+ *   h      0       1       2       3       4        5        6       7
+ *   dir  (0,+1)  (+1,+1)  (+1,0)  (+1,-1)  (0,-1)  (-1,-1)  (-1,0)  (-1,+1)
+ * Occupancy: layers_dev uint8 [L, rows, cols] with L = 1 or 8, non-zero = blocked.  State (c, h) reads layer h mod L.  Cells
+ *   outside the image are blocked.  There is no corner rule between states.
+ * Moves are forward only: from (c, h) to (c + dir(h'), h') with h' in {h, h + 1, h - 1} mod 8.  The move is along the heading
+ *   the robot has AFTER it; that heading differs from the one before by at most one step.  The target state must be free.
+ * Cost: an integer pair (a, b), ordered exactly as a + b * sqrt 2.  A move to an even h' adds (1, 0), a move to an odd h'
+ *   adds (0, 1), a move with h' != h adds a further (turn_cost, 0), turn_cost an integer 0 .. 255.  Equal cost means equal
+ *   pair, so the field is the unique fixed point of the relaxation: the same bits from run to run, compared with ==.
+ * Goal: goal state g = (goal cell, goal heading); with goal heading -1 it is the goal cell at every heading.  Goal states
+ *   have cost (0, 0) and are forced free.
+ * Field: d_g(c, h) = the minimum cost from (c, h) to g.  The sentinel (-1, -1) marks blocked states, states that cannot
+ *   reach g, every state of a goal whose cell is outside the grid and every state of a goal whose heading is outside -1 .. 7.
+ * Trace: problem p starts in (start cell, start heading); the start state is NOT tested for occupancy.  At a state with a
+ *   cost the next state is the first successor, tried in the order h' = h, h + 1, h - 1, whose cost plus the move equals
+ *   the current cost exactly; the trace ends at the first state with cost (0, 0).  At a blocked start state, whose own value
+ *   is the sentinel, the first step goes to the successor with the smallest d + move, ties broken by the same order; the
+ *   path's cost is that sum; if no successor has a cost the status is 1.
+ * Status: 0 ok; 1 unreachable; 2 the start or goal cell is outside the grid, or the start heading is outside 0 .. 7.
+ * Refused before launch (argument error, nothing is clamped): turn_cost outside 0 .. 255, L not 1 or 8,
+ *   8 * rows * cols * (1 + turn_cost) >= 2^21 (the bound under which the float64 key orders pairs exactly), a short
+ *   workspace, null required pointers.
+ *
+ * nfopp_lattice_distance_fields: goal_states_dev int32 [G, 3] (row, col, heading or -1), callers pass each goal state once;
+ *   fields_dev int32 [G, 8, rows, cols, 2] <- d_g.  One workgroup per goal state.  While the padded 8-layer field fits 144 KiB
+ *   of LDS and 8 * rows * cols * (1 + turn_cost) <= 65535 the counts are packed 16 + 16 bits in LDS (no count can wrap);
+ *   otherwise 32 + 32 bits in `workspace` (nfopp_lattice_fields_workspace_bytes, 0 for the LDS form and for a refused
+ *   shape), 8-byte aligned.  No float atomics.
+ * nfopp_lattice_trace_paths: one thread per problem.  start_states_dev int32 [B, 3] (row, col, heading), goal_states_dev
+ *   int32 [B, 3], field_index_dev int32 [B] = the problem's field among n_total; fields_dev holds the n_fields fields
+ *   field_first .. field_first + n_fields - 1 of them (a caller that cannot hold all fields at once calls once per chunk).
+ *   A field_index outside 0 .. n_total - 1 gives status 2, like an off-grid cell or a bad start heading: all are tested
+ *   before anything is indexed by them.  A problem whose field is not among the ones passed is not touched by the call.
+ *   cells_dev int32 [B, max_len, 2] (row, col), headings_dev int32 [B, max_len] (first and last state included), count_dev [B]
+ *   = states the path has (max_len = 0 sizes the buffers: nothing is written to cells / headings, which may be null),
+ *   status_dev [B], cost_dev [B, 2] (may be null) = (a, b) of the path, (-1, -1) and count 0 where status != 0. */
+size_t nfopp_lattice_fields_workspace_bytes(int32_t rows, int32_t cols, int32_t turn_cost, int64_t n_goals);
+int nfopp_lattice_distance_fields(const uint8_t* layers_dev, int32_t n_layers, int32_t rows, int32_t cols,
+                                  const int32_t* goal_states_dev, int64_t n_goals, int32_t turn_cost, int32_t* fields_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream);
+int nfopp_lattice_trace_paths(const int32_t* fields_dev, int64_t field_first, int64_t n_fields, int64_t n_total,
+                              int32_t rows, int32_t cols, int32_t turn_cost, const int32_t* start_states_dev,
+                              const int32_t* goal_states_dev, const int32_t* field_index_dev, int64_t batch, int32_t max_len,
+                              int32_t* cells_dev, int32_t* headings_dev, int32_t* count_dev, int32_t* status_dev,
+                              int32_t* cost_dev, void* stream);
+
 /* ---- time parametrisation under motion limits (csrc/time_profile.hip), additive under ABI 6 --------------------------------
  * Everything above is geometry; these two entries say WHEN the robot is where and how fast it may go, for a whole batch,
  * without a host round trip.  Float64 throughout, every operation rounded on its own; the two prefix sums are integers, so

@@ -559,6 +559,56 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> spacetime_plan_fleet(const Tensor& oc
   return std::make_tuple(cells, arrival, status, tracks);
 }
 
+// the lattice search over (cell, heading) states (nfopp_lattice_distance_fields): layers uint8 [L, rows, cols], goal_states int32
+// [G, 3] (row, col, heading or -1) -> fields int32 [G, 8, rows, cols, 2]
+Tensor lattice_fields(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost) {
+  check_tensor(layers, "layers", at::kByte);
+  check_tensor(goal_states, "goal_states", at::kInt);
+  same_device(layers, goal_states, "goal_states");
+  TORCH_CHECK(layers.dim() == 3, "nfopp: layers must be [L, rows, cols] uint8");
+  TORCH_CHECK(goal_states.dim() == 2 && goal_states.size(1) == 3, "nfopp: goal_states must be [G, 3] (row, col, heading)");
+  TORCH_CHECK(turn_cost >= 0 && turn_cost <= 255, "nfopp: turn_cost must be 0..255");
+  const int64_t L = layers.size(0), rows = layers.size(1), cols = layers.size(2), G = goal_states.size(0);
+  TORCH_CHECK(rows >= 1 && cols >= 1 && rows <= 32768 && cols <= 32768, "nfopp: grid must be 1..32768 cells a side");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(layers.device());
+  Tensor fields = at::empty({G, 8, rows, cols, 2}, layers.options().dtype(at::kInt));
+  const size_t bytes = nfopp_lattice_fields_workspace_bytes((int32_t)rows, (int32_t)cols, (int32_t)turn_cost, G);
+  Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, layers.options().dtype(at::kLong));
+  check_status(nfopp_lattice_distance_fields(layers.data_ptr<uint8_t>(), (int32_t)L, (int32_t)rows, (int32_t)cols,
+                                             G ? goal_states.data_ptr<int32_t>() : nullptr, G, (int32_t)turn_cost,
+                                             G ? fields.data_ptr<int32_t>() : nullptr, bytes ? work.data_ptr() : nullptr, bytes,
+                                             stream_of(layers)));
+  return fields;
+}
+
+// the descent (nfopp_lattice_trace_paths) through fields [n_fields, 8, rows, cols, 2] = the fields field_first .. of n_total:
+// start_states / goal_states int32 [B, 3], field_index int32 [B] -> (cells [B, max_len, 2], headings [B, max_len], count [B],
+// status [B], cost [B, 2]) int32.  Outputs start as zeros, so a problem of another chunk reads count 0, status 0.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> lattice_trace_paths(const Tensor& fields, int64_t field_first, int64_t n_total,
+                                                                       const Tensor& start_states, const Tensor& goal_states,
+                                                                       const Tensor& field_index, int64_t turn_cost, int64_t max_len) {
+  check_tensor(fields, "fields", at::kInt);
+  TORCH_CHECK(fields.dim() == 5 && fields.size(1) == 8 && fields.size(4) == 2, "nfopp: fields must be [G, 8, rows, cols, 2]");
+  check_tensor(start_states, "start_states", at::kInt);
+  TORCH_CHECK(start_states.dim() == 2 && start_states.size(1) == 3, "nfopp: start_states must be [B, 3] (row, col, heading)");
+  same_device(fields, start_states, "start_states");
+  const int64_t B = start_states.size(0), G = fields.size(0), rows = fields.size(2), cols = fields.size(3);
+  need(fields, goal_states, "goal_states", {B, 3}, at::kInt);
+  need(fields, field_index, "field_index", {B}, at::kInt);
+  TORCH_CHECK(max_len >= 0 && max_len <= std::numeric_limits<int32_t>::max(), "nfopp: bad max_len");
+  TORCH_CHECK(turn_cost >= 0 && turn_cost <= 255, "nfopp: turn_cost must be 0..255");
+  TORCH_CHECK(rows >= 1 && cols >= 1, "nfopp: fields of an empty grid");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(fields.device());
+  const auto i32 = fields.options().dtype(at::kInt);
+  Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32);
+  Tensor count = at::zeros({B}, i32), status = at::zeros({B}, i32), cost = at::zeros({B, 2}, i32);
+  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
+  check_status(nfopp_lattice_trace_paths(i32p(fields), field_first, G, n_total, (int32_t)rows, (int32_t)cols, (int32_t)turn_cost,
+                                         i32p(start_states), i32p(goal_states), i32p(field_index), B, (int32_t)max_len, i32p(cells),
+                                         i32p(headings), i32p(count), i32p(status), i32p(cost), stream_of(fields)));
+  return std::make_tuple(cells, headings, count, status, cost);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nfopp, lib) {
@@ -601,6 +651,9 @@ TORCH_LIBRARY(nfopp, lib) {
           "Tensor? reservation, Tensor? tracks, Tensor? radius, Tensor? visible) -> Tensor");
   lib.def("spacetime_plan_fleet(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
           "Tensor start_cells, Tensor goal_cells, Tensor? order, Tensor(a!) reservation) -> (Tensor, Tensor, Tensor, Tensor)");
+  lib.def("lattice_fields(Tensor layers, Tensor goal_states, int turn_cost) -> Tensor");
+  lib.def("lattice_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
+          "Tensor field_index, int turn_cost, int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -623,4 +676,6 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("fleet_assign_delays", &fleet_assign_delays);
   lib.impl("spacetime_reserve", &spacetime_reserve);
   lib.impl("spacetime_plan_fleet", &spacetime_plan_fleet);
+  lib.impl("lattice_fields", &lattice_fields);
+  lib.impl("lattice_trace_paths", &lattice_trace_paths);
 }

@@ -18,6 +18,7 @@ from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fi
 from .host_utils import (AttributeDict, CircleCollisionChecker,
                          CircleDirectedCollisionChecker, CollisionChecker, Position2, RectangleCollisionChecker,
                          TrajectoryInitializer)
+from .lattice import LatticeGrid, heading_index, lattice_fields, lattice_search_init, lattice_search_paths
 from .learning import BatchSampler, DeviceCircleChecker, DeviceGridChecker, DeviceGridMap, DeviceRectangleChecker
 from .onf_model import ONF
 from .path_tools import PathPostprocessor, init_trajectories
@@ -49,4 +50,5 @@ __all__ = [
     "SCHEDULE_UNRESOLVED", "SCHEDULE_NOT_ORDERED", "SCHEDULE_MAX_DELAY",
     "SpaceTimePlan", "SpaceTimeReservation", "spacetime_plan", "SPACETIME_OK", "SPACETIME_BAD_CELL", "SPACETIME_UNREACHED",
     "SPACETIME_NOT_ORDERED", "SPACETIME_DIRECTIONS",
+    "LatticeGrid", "heading_index", "lattice_fields", "lattice_search_paths", "lattice_search_init",
 ]

@@ -139,6 +139,12 @@ _SIGNATURES = {
                                                 ctypes.c_double, ctypes.c_int32, _P, _P, _P]),
     "nfopp_grid_seed_polylines": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int32,
                                                  ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_size_t, _P]),
+    "nfopp_lattice_fields_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
+    "nfopp_lattice_distance_fields": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64,
+                                                     ctypes.c_int32, _P, _P, ctypes.c_size_t, _P]),
+    "nfopp_lattice_trace_paths": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64, ctypes.c_int32,
+                                                 _P, _P, _P, _P, _P, _P]),
     "nfopp_grid_to_points": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P]),

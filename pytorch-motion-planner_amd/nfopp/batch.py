@@ -16,6 +16,7 @@ import torch
 from . import _lib
 from .engine import TrajectoryEngine
 from .grid_search import AstarTrajectoryInitializer, OccupancyGrid, grid_search_init
+from .lattice import LatticeGrid, lattice_search_init
 from .path_tools import init_trajectories
 
 
@@ -166,13 +167,23 @@ class BatchPlanner(object):
     seed_status = None   # per-problem status of the last grid-search seeding (nfopp/grid_search.py), else None
     seed_margin = None   # the clearance margin each problem was seeded at (all zero without one); None without grid seeding
 
-    def init(self, starts, goals, boundaries, trajectories=None, initializer=None, seed_clearance=None, seed_any_angle=False):
+    def init(self, starts, goals, boundaries, trajectories=None, initializer=None, seed_clearance=None, seed_any_angle=False,
+             seed_turn_cost=0):
         """`seed_clearance` / `seed_any_angle`: grid_search_init's `clearance` / `any_angle` for an OccupancyGrid initializer
-        (an AstarTrajectoryInitializer carries its own)."""
+        (an AstarTrajectoryInitializer carries its own).  A LatticeGrid initializer seeds SE(2) batches through
+        lattice_search_init with `seed_turn_cost`; it takes neither of the two: shortening by line of sight would undo the
+        heading constraint, and a margin is built into the lattice (LatticeGrid.from_grid(grid.inflated(m)))."""
         eng = self.engine
         eng.set_endpoints(starts, goals)
         eng.hyper = eng.hyper.replace(bounds=boundaries)
         self.seed_status = self.seed_margin = None
+        if isinstance(initializer, LatticeGrid):
+            if seed_clearance is not None or seed_any_angle:
+                raise ValueError("seed_clearance / seed_any_angle do not go with a LatticeGrid: build it from grid.inflated(m)")
+            if eng.D != 3:
+                raise ValueError("a LatticeGrid seeds SE(2) trajectories (D = 3) only")
+        elif seed_turn_cost != 0:
+            raise ValueError("seed_turn_cost goes with a LatticeGrid initializer")
         if seed_clearance is not None and not isinstance(initializer, OccupancyGrid):
             raise ValueError("seed_clearance goes with an OccupancyGrid initializer")
         if seed_any_angle and not isinstance(initializer, OccupancyGrid):
@@ -185,11 +196,15 @@ class BatchPlanner(object):
                 _, self.seed_status, self.seed_margin = grid_search_init(
                     initializer, eng.start, eng.goal, eng.N, self.init_angles_with_trajectory and eng.D == 3, out=eng.traj,
                     clearance=() if seed_clearance is None else seed_clearance, any_angle=bool(seed_any_angle))
+            elif isinstance(initializer, LatticeGrid):
+                _, self.seed_status = lattice_search_init(initializer, eng.start, eng.goal, eng.N,
+                                                          self.init_angles_with_trajectory, out=eng.traj,
+                                                          turn_cost=seed_turn_cost)
             elif isinstance(initializer, AstarTrajectoryInitializer):
                 initializer.initialize_batch(eng.start, eng.goal, eng.N, out=eng.traj, boundaries=boundaries)
                 self.seed_status, self.seed_margin = initializer.status, initializer.seed_margin
             else:
-                raise TypeError("initializer must be an OccupancyGrid or an AstarTrajectoryInitializer")
+                raise TypeError("initializer must be an OccupancyGrid, a LatticeGrid or an AstarTrajectoryInitializer")
         elif trajectories is None:
             # device initialiser (trajectory_initializer.py:12-45); eng.start / eng.goal were uploaded just above
             init_trajectories(eng.start, eng.goal, eng.N, self.init_angles_with_trajectory and eng.D == 3, out=eng.traj)

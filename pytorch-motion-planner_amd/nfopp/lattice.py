@@ -1,0 +1,231 @@
+"""Heading-aware lattice search for car-like trajectory seeds (csrc/lattice_search.hip; the rule: include/nfopp_hip.h).
+
+The state of the search is (cell, heading), heading h in 0 .. 7 standing for h * pi / 4; moves are forward only, along the
+heading the robot has after the move, which differs from the one before by at most one step.  A seed therefore leaves the
+start along the start heading and reaches the goal along the goal heading, and with eight occupancy layers
+(`LatticeGrid.from_checker`) it threads only the gaps the robot fits through at the heading it has there.  The traced cells
+go through the seeding stage of the 8-connected search (`seed_trajectories`) unchanged."""
+
+import numpy as np
+import torch
+
+from . import _lib
+from .grid_search import OccupancyGrid, _as_device_points, _cell_centres, seed_trajectories
+
+HEADINGS = 8
+GOAL_HEADING_MODES = ("fixed", "free")
+
+
+def heading_index(theta):
+    """theta (radians, any float tensor) -> int32 heading index: round(theta / (pi / 4)) in float64 with torch's
+    half-to-even, then mod 8; -1 (which the search refuses with status 2) where theta is not finite."""
+    t = theta.double()
+    idx = torch.remainder(torch.round(t / (np.pi / 4)), HEADINGS)
+    return torch.where(torch.isfinite(t), idx, torch.full_like(idx, -1.0)).to(torch.int32)
+
+
+class LatticeGrid(object):
+    """uint8 occupancy layers [L, rows = y cells, cols = x cells] with L = 1 or 8 (non-zero = blocked; state (cell, h) reads
+    layer h mod L) and the geometry of OccupancyGrid: cell of a point = floor((x - b0) / resolution), cell centre =
+    j * resolution + resolution / 2 + b0."""
+
+    def __init__(self, layers, boundaries, resolution, device="cuda"):
+        if torch.is_tensor(layers) and not layers.is_cuda:
+            layers = layers.numpy()
+        if torch.is_tensor(layers):
+            if layers.dtype != torch.uint8:
+                raise ValueError("layers must be uint8")
+            host, dev_layers = None, layers
+            shape = tuple(layers.shape)
+        else:
+            host = np.ascontiguousarray(np.asarray(layers) != 0, dtype=np.uint8)
+            dev_layers, shape = None, host.shape
+        if len(shape) != 3 or shape[0] not in (1, HEADINGS) or shape[1] < 1 or shape[2] < 1:
+            raise ValueError("layers must be a non-empty [L, rows, cols] array with L = 1 or 8")
+        self.boundaries = tuple(float(b) for b in boundaries)
+        if len(self.boundaries) != 4:
+            raise ValueError("boundaries must be (x0, x1, y0, y1)")
+        self.resolution = float(resolution)
+        if not self.resolution > 0:
+            raise ValueError("resolution must be positive")
+        self._layers_host, self._layers_dev = host, None
+        self.device = device
+        if dev_layers is not None:
+            self._layers_dev = (dev_layers != 0).to(torch.uint8).contiguous()
+            self.device = dev_layers.device
+        self._shape = shape
+
+    @property
+    def shape(self):
+        """(rows, cols)"""
+        return self._shape[1:]
+
+    @property
+    def n_layers(self):
+        return self._shape[0]
+
+    @property
+    def layers(self):
+        """The device copy (uploaded on first use)."""
+        if self._layers_dev is None:
+            _lib.require_gpu()
+            self._layers_dev = torch.tensor(self._layers_host, device=self.device)
+        return self._layers_dev
+
+    @property
+    def layers_host(self):
+        if self._layers_host is None:
+            self._layers_host = self._layers_dev.cpu().numpy()
+        return self._layers_host
+
+    @classmethod
+    def from_grid(cls, grid):
+        """One layer: the OccupancyGrid's image at every heading."""
+        if grid._occupancy_dev is not None:
+            return cls(grid._occupancy_dev[None], grid.boundaries, grid.resolution)
+        return cls(grid.occupancy_host[None], grid.boundaries, grid.resolution, grid.device)
+
+    @classmethod
+    def from_checker(cls, checker, resolution, boundaries=None, device=None):
+        """Eight layers from one `labels` call of a device checker over 8 * cells poses (cell centre, float32(h * pi / 4)):
+        the box robot gets its footprint per heading from the checker's own kernels."""
+        if resolution is None:
+            raise TypeError("from_checker() needs a resolution")
+        if not hasattr(checker, "labels"):
+            raise TypeError("LatticeGrid.from_checker needs a device checker (one with `labels`)")
+        if boundaries is None:
+            boundaries = checker.get_boundaries() if hasattr(checker, "get_boundaries") else getattr(checker, "boundaries", None)
+        if boundaries is None:
+            raise ValueError("the checker carries no boundaries: pass boundaries=(x0, x1, y0, y1)")
+        boundaries = tuple(float(b) for b in boundaries)
+        x, y, x_cells, y_cells = _cell_centres(boundaries, resolution)
+        dev = device or getattr(getattr(checker, "grid", None), "device", None) or \
+            getattr(getattr(checker, "obstacles", None), "device", None) or "cuda"
+        xy = np.stack([x, y], 1).astype(np.float32)
+        poses = np.concatenate([np.concatenate([xy, np.full((len(xy), 1), np.float32(h * np.pi / 4), np.float32)], 1)
+                                for h in range(HEADINGS)], 0)
+        labels = checker.labels(torch.tensor(poses, device=dev))
+        return cls((labels > 0).to(torch.uint8).reshape(HEADINGS, y_cells, x_cells), boundaries, resolution)
+
+    cells_of = OccupancyGrid.cells_of
+
+    def states_of(self, points, free_heading=False):
+        """[B, 3] device poses -> int32 [B, 3] (row, col, heading index); heading -1 everywhere with `free_heading`."""
+        cells = self.cells_of(points)
+        h = torch.full_like(cells[:, 0], -1) if free_heading else heading_index(points[:, 2])
+        return torch.cat([cells, h[:, None]], 1).contiguous()
+
+
+def _turn_cost(turn_cost):
+    if int(turn_cost) != turn_cost or not 0 <= int(turn_cost) <= 255:
+        raise ValueError("turn_cost must be an integer 0 .. 255")
+    return int(turn_cost)
+
+
+def _check_bound(lgrid, turn_cost):
+    rows, cols = lgrid.shape
+    if HEADINGS * rows * cols * (1 + turn_cost) >= 2 ** 21:
+        raise ValueError("8 * rows * cols * (1 + turn_cost) must stay below 2^21 (%d x %d, turn_cost %d)" % (rows, cols, turn_cost))
+
+
+def lattice_fields(lgrid, goal_states, turn_cost=0):
+    """goal_states int32 [G, 3] (row, col, heading or -1) on the device -> int32 [G, 8, rows, cols, 2]: the exact cost (a, b)
+    from every state to the goal state; (-1, -1) = blocked or unreachable."""
+    lib = _lib.load()
+    turn_cost = _turn_cost(turn_cost)
+    _check_bound(lgrid, turn_cost)
+    layers = lgrid.layers
+    rows, cols = lgrid.shape
+    goal_states = torch.as_tensor(goal_states, device=layers.device).to(torch.int32).contiguous()
+    if goal_states.dim() != 2 or goal_states.shape[1] != 3:
+        raise ValueError("goal_states must be [G, 3] (row, col, heading)")
+    g = goal_states.shape[0]
+    fields = torch.empty(g, HEADINGS, rows, cols, 2, dtype=torch.int32, device=layers.device)
+    ws_bytes = lib.nfopp_lattice_fields_workspace_bytes(rows, cols, turn_cost, g)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=layers.device) if ws_bytes else None
+    _lib.check(lib.nfopp_lattice_distance_fields(_lib.ptr(layers, torch.uint8), lgrid.n_layers, rows, cols,
+                                                 _lib.ptr(goal_states, torch.int32), g, turn_cost, _lib.ptr(fields, torch.int32),
+                                                 _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
+                                                 _lib.stream_ptr()))
+    return fields
+
+
+def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes):
+    """-> (cells, headings, count, status, cost, starts, goals), all on the device."""
+    lib = _lib.load()
+    if not isinstance(lgrid, LatticeGrid):
+        raise TypeError("the lattice search needs a LatticeGrid")
+    if goal_heading not in GOAL_HEADING_MODES:
+        raise ValueError("goal_heading must be 'fixed' or 'free'")
+    turn_cost = _turn_cost(turn_cost)
+    _check_bound(lgrid, turn_cost)
+    starts, goals = _as_device_points(lgrid, starts), _as_device_points(lgrid, goals)
+    if starts.shape != goals.shape or starts.shape[1] != 3:
+        raise ValueError("starts and goals must both be [B, 3] poses (x, y, theta)")
+    rows, cols = lgrid.shape
+    b = starts.shape[0]
+    dev = starts.device
+    i32 = torch.int32
+    start_states = lgrid.states_of(starts)
+    goal_states = lgrid.states_of(goals, free_heading=goal_heading == "free")
+    # problems that share a goal state share a field
+    gr, gc, gh = goal_states[:, 0].long(), goal_states[:, 1].long(), goal_states[:, 2].long()
+    inside = (gr >= 0) & (gr < rows) & (gc >= 0) & (gc < cols)
+    key = torch.where(inside, (gr * cols + gc) * (HEADINGS + 1) + gh + 1, torch.full_like(gr, -1))
+    uniq, inverse = torch.unique(key, return_inverse=True)
+    if uniq.numel() and int(uniq[0]) < 0:
+        uniq, inverse = uniq[1:], inverse - 1
+    field_index = inverse.to(i32).contiguous()
+    cell = uniq // (HEADINGS + 1)
+    unique_states = torch.stack([cell // cols, cell % cols, uniq % (HEADINGS + 1) - 1], 1).to(i32).contiguous()
+    n_total = unique_states.shape[0]
+    per_field = HEADINGS * rows * cols * 8
+    chunk = max(1, int(max_field_bytes) // per_field)
+    count = torch.zeros(b, dtype=i32, device=dev)
+    status = torch.zeros(b, dtype=i32, device=dev)
+    cost = torch.zeros(b, 2, dtype=i32, device=dev)
+    cells = torch.zeros(b, 1, 2, dtype=i32, device=dev)
+    headings = torch.zeros(b, 1, dtype=i32, device=dev)
+
+    def trace(fields, first, max_len):
+        n = 0 if fields is None else fields.shape[0]
+        _lib.check(lib.nfopp_lattice_trace_paths(
+            _lib.ptr(fields, i32) if n else None, first, n, n_total, rows, cols, turn_cost, _lib.ptr(start_states, i32),
+            _lib.ptr(goal_states, i32), _lib.ptr(field_index, i32), b, max_len, _lib.ptr(cells, i32) if max_len else None,
+            _lib.ptr(headings, i32) if max_len else None, _lib.ptr(count, i32), _lib.ptr(status, i32), _lib.ptr(cost, i32),
+            _lib.stream_ptr()))
+
+    if b == 0:
+        return cells, headings, count, status, cost, starts, goals
+    if n_total == 0:
+        trace(None, 0, 0)   # every goal is outside the grid: status 2 throughout
+    # one sizing pass and one count.max() per chunk of fields: a single chunk (the usual case) costs the one read-back of the
+    # 8-connected search; counts of earlier chunks stay in `count`, so the maximum never falls
+    for first in range(0, n_total, chunk):
+        fields = lattice_fields(lgrid, unique_states[first:first + chunk], turn_cost)
+        trace(fields, first, 0)
+        max_len = max(int(count.max()), 1)
+        if max_len > cells.shape[1]:
+            grow = max_len - cells.shape[1]
+            cells = torch.nn.functional.pad(cells, (0, 0, 0, grow)).contiguous()
+            headings = torch.nn.functional.pad(headings, (0, grow)).contiguous()
+        trace(fields, first, cells.shape[1])
+    return cells, headings, count, status, cost, starts, goals
+
+
+def lattice_search_paths(lgrid, starts, goals, turn_cost=0, goal_heading="fixed", max_field_bytes=2 ** 30):
+    """starts, goals [B, 3] poses -> (cells int32 [B, max_len, 2] (row, col), headings int32 [B, max_len], counts [B], status
+    [B], costs [B, 2] = (a, b)), on the device; what lies behind a row's count is zero.  goal_heading "fixed": the goal state
+    is (goal cell, heading_index(goal theta)); "free": the goal cell at any heading.  Distinct goal states are searched once,
+    in chunks whose fields stay within `max_field_bytes` (at least one field per chunk)."""
+    return _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes)[:5]
+
+
+def lattice_search_init(lgrid, starts, goals, n_waypoints, init_angles_with_trajectory=True, out=None, turn_cost=0,
+                        goal_heading="fixed"):
+    """-> (traj [B, N, 3] fp32, status [B] int32) on the device: the lattice path's cells through seed_trajectories.  status 0
+    = seeded along a minimum-cost lattice path; 1 = goal state unreachable, 2 = start or goal outside the grid (or a start
+    heading that is not finite): those problems get the straight line of `init_trajectories`."""
+    cells, _, count, status, _, starts, goals = _search(lgrid, starts, goals, turn_cost, goal_heading, 2 ** 30)
+    traj = seed_trajectories(lgrid, cells, count, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
+    return traj, status
