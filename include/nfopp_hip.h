@@ -10,6 +10,13 @@
  * Every function returns 0 on success and a negative nfopp_status otherwise; nfopp_last_error() describes the
  * last failure of the calling thread.  No torch types, no ownership transfer: buffers are borrowed for the call.
  *
+ * Buffer contract: a call stores nothing outside the arrays it is given, at the sizes stated here; an array declared `const`
+ * is not written; a pure output and a workspace need no initialisation -- no element of either is read before the call has
+ * written it, so results do not depend on what the memory held; and where an entry says that elements are left alone (rows
+ * of retired trajectories, slots that belong to another entry) they keep their bytes.  Each entry says which elements of its
+ * pure outputs it writes.  tests/test_gpu_buffer_contracts.py pins all of this on bits and bytes for the entries of the step
+ * and fit pipeline and for every entry that takes a workspace_dev.
+ *
  * A batch of B trajectories is B independent reference problems that share one ONF (occupancy neural field).
  */
 #ifndef NFOPP_HIP_H
@@ -77,12 +84,15 @@ int64_t nfopp_onf_param_count(const nfopp_onf_config* cfg);
 /* ONF forward + input gradient at explicit points.  Replaces `ONF.forward` (nfop/onf_model.py:33-50,
  * nfop/angle_encoder.py:15-18) followed by autograd w.r.t. the input.
  *   points_dev [P, point_dim]  point_dim = 3 (x, y, theta) when angle_dim > 0, else 2
- *   out4_dev   [P, 4]          logit, dlogit/dx, dlogit/dy, dlogit/dtheta (0 for 2-D fields) */
+ *   out4_dev   [P, 4]          logit, dlogit/dx, dlogit/dy, dlogit/dtheta (0 for 2-D fields); all 4 P floats are written,
+ *                              on every matrix path and at every P (the tiles of the last, partly filled chunk store no row
+ *                              past P) */
 int nfopp_onf_eval_points(const nfopp_onf_config* cfg, const float* params_dev, const float* points_dev,
                           int64_t n_points, float* out4_dev, void* stream);
 
 /* Forward only (the backward half of the kernel is skipped): out4_dev [P, 4] = logit, 0, 0, 0.  Used where the
- * reference evaluates the field without gradients (nfop/nerf_opt_planner.py:98-99,122-125, plotting). */
+ * reference evaluates the field without gradients (nfop/nerf_opt_planner.py:98-99,122-125, plotting).  The three zeros of
+ * every row are written too. */
 int nfopp_onf_eval_logits(const nfopp_onf_config* cfg, const float* params_dev, const float* points_dev,
                           int64_t n_points, float* out4_dev, void* stream);
 
@@ -91,14 +101,18 @@ int nfopp_onf_eval_logits(const nfopp_onf_config* cfg, const float* params_dev, 
  *   traj_dev [B, N, D]   interior waypoints;  sample j of trajectory b lies between waypoints j and j+1
  *   t_dev    [B, N-1]    t_mode 0: read (injected draws);  t_mode 1: drawn here with Philox4x32-10
  *                        (key = seed, counter = (global sample index, rng_offset)) and WRITTEN for the
- *                        update kernel;  traj_index_offset = global index of trajectory 0 (multi-GPU shards
+ *                        update kernel (t_mode 0 never writes t_dev);  traj_index_offset = global index of
+ *                        trajectory 0 (multi-GPU shards
  *                        draw the same numbers as a single-GPU run)
  *   out4_dev [B, N-1, 4] as nfopp_onf_eval_points
  *   active_dev [B] uint8 or NULL (ABI 4): early stop, the reference's `break` (scripts/run_bench_mr.py:121-126).
  *                        Trajectories with active == 0 are compacted OUT of the sample stream, so the kernel's
  *                        work is proportional to the live ones; their t / out4 rows are left untouched and the
  *                        rows of live trajectories are bit-identical to a launch without the mask.
- *   live_ws_dev [B + 1] int32 workspace for the live list (required with active_dev, else may be NULL) */
+ *   live_ws_dev [B + 1] int32 workspace for the live list (required with active_dev, else may be NULL).  Needs no
+ *                        initialisation: the call writes the live count to [0] and the live indices behind it, reads no
+ *                        other element and leaves the slots behind the last live index alone.  With every trajectory
+ *                        retired nothing of t / out4 is written. */
 int nfopp_traj_collision_eval(const nfopp_onf_config* cfg, const float* params_dev, const float* traj_dev,
                               int64_t batch, int32_t n_waypoints, int32_t dim, float* t_dev, int32_t t_mode,
                               uint64_t seed, uint64_t rng_offset, int64_t traj_index_offset, float* out4_dev,
@@ -115,7 +129,8 @@ int nfopp_traj_collision_eval(const nfopp_onf_config* cfg, const float* params_d
  *       tridiagonal Toeplitz matrix is Toeplitz away from the ends); their coefficients are broadcast from LDS.
  *       Pass lo = hi = 0 to disable.
  *   terms_dev [B, 8] or NULL: total, distance, sum softplus, sum lam*c, sum c^2, boundary, sum cm*tanh, sum relu(d)^2
- *   active_dev [B] uint8 or NULL: trajectories with 0 are left untouched (early stop, see nfopp_path_select_best) */
+ *   active_dev [B] uint8 or NULL: trajectories with 0 are left untouched (early stop, see nfopp_path_select_best): their
+ *       rows of traj, lam, cm, adam_m, adam_v AND of terms_dev keep their bytes; the 8 terms of every live row are written */
 int nfopp_traj_update(const nfopp_traj_hyper* hp, int64_t batch, int32_t n_waypoints, int32_t dim,
                       float* traj_dev, const float* start_dev, const float* goal_dev, float* lam_dev,
                       float* cm_dev, float* adam_m_dev, float* adam_v_dev, const float* t_dev,
@@ -124,7 +139,8 @@ int nfopp_traj_update(const nfopp_traj_hyper* hp, int64_t batch, int32_t n_waypo
                       void* stream);
 
 /* Arc-length reparametrisation (constrained:132-171 for D = 3 incl. multipliers; nerf:224-244 for D = 2).
- *   u_dev [N] = torch.linspace(0, 1, N+2)[1:-1] (formed by the caller so its rounding is the reference's) */
+ *   u_dev [N] = torch.linspace(0, 1, N+2)[1:-1] (formed by the caller so its rounding is the reference's)
+ *   active_dev [B] uint8 or NULL: the rows of traj, lam and cm of trajectories with 0 keep their bytes */
 int nfopp_reparametrize(int64_t batch, int32_t n_waypoints, int32_t dim, float* traj_dev,
                         const float* start_dev, const float* goal_dev, float* lam_dev, float* cm_dev,
                         const float* u_dev, const uint8_t* active_dev, void* stream);
@@ -155,7 +171,8 @@ int nfopp_update_endpoints(int64_t batch, int32_t n_waypoints, int32_t dim, int3
  *     them (step_size = lr / (1 - beta1^k), bc2_sqrt = sqrt(1 - beta2^k); hp's two fields are ignored)
  *   nfopp_reparametrize when (step_count + k) % reparam_freq == 0           (nfop/nerf_opt_planner.py:60-71)
  * Same kernels and arguments as n single-step sequences: results are bit-identical to them.  terms_dev [B, 8] (or NULL)
- * receives the loss terms of the LAST step.  The caller advances its own counters by n_steps afterwards.  Nothing
+ * receives the loss terms of the LAST step (rows of retired trajectories are left alone, as are their rows of t_dev and
+ * onf_out4_dev; t_mode 0 does not touch t_dev at all).  The caller advances its own counters by n_steps afterwards.  Nothing
  * synchronises.  Not for steps with ONF learning: the reference's fit needs the host checker between steps. */
 typedef struct nfopp_traj_buffers {
   float* traj_dev;             /* [B, N, D] */
@@ -193,7 +210,9 @@ int nfopp_traj_steps(const nfopp_onf_config* cfg, const float* params_dev, const
  * every parameter incl. the angle frequencies (nfop/nerf_opt_planner.py:83-89).
  *   samples_dev [P, point_dim], labels_dev [P] (0/1), inv_count = 1 / (global sample count)
  *   grad_dev [n_params + 2]: flat gradient in parameter order, then sum of per-sample losses * inv_count, then P
- *   workspace: nfopp_onf_train_workspace_bytes(cfg, P) bytes of device scratch
+ *   workspace: nfopp_onf_train_workspace_bytes(cfg, P) bytes of device scratch, exactly that many are enough for every P
+ *     (the last, ragged chunk of samples reads and writes no row past P); it needs no initialisation
+ *   All n_params + 2 floats of grad_dev are written (stored, not accumulated: the buffer need not be zeroed).
  * Reductions run in a fixed order (no float atomics): results are bitwise reproducible. */
 size_t nfopp_onf_train_workspace_bytes(const nfopp_onf_config* cfg, int64_t n_samples);
 int nfopp_onf_train_grad(const nfopp_onf_config* cfg, const float* params_dev, const float* samples_dev,
@@ -208,7 +227,7 @@ int nfopp_onf_train_grad_ex(const nfopp_onf_config* cfg, const float* params_dev
 
 /* ---- continuous ONF learning over a batch: ground truth and sample generation on the device --------------------
  * Ground-truth checkers (labels_dev[p] = 1.0 in collision, 0.0 free); bounds4 (host, may be NULL) = xmin,xmax,ymin,ymax
- * of nfop/collision_checker/collision_checker.py:12-19.
+ * of nfop/collision_checker/collision_checker.py:12-19.  Every one of labels_dev[0 .. n) is written, by all five entries.
  *   circle:    any |pose.xy - obstacle| < radius                 nfop/collision_checker/circle_collision_checker.py:11-14
  *   rectangle: any obstacle inside box4 = (x0,x1,y0,y1) in the robot frame   .../rectangle_collision_checker.py:11-26
  *   grid:      uint8 occupancy image, cell = int((x - origin - cell/2)/cell) in float64 like the reference's numpy
@@ -245,6 +264,9 @@ int nfopp_check_collision_grid(const float* poses_dev, int64_t n, int32_t pose_d
  * (sigma course/angle) written to samples[b][0..N-2], "fine" copies appended to the candidate list behind the
  * retained pool (pool_count = 0 on the first step, pool_cap afterwards), n_field uniform field poses written to
  * samples[b][N-1+pool_cap ...].  Layouts: cand [B, pool_cap+N-1, D], samples [B, N-1+pool_cap+n_field, D].
+ * Written: cand / cand_age slots [0, pool_count + N - 1) of every trajectory (with pool_count = 0 the last pool_cap slots are
+ * left alone), samples slots [0, N - 1) and [N - 1 + pool_cap, end); the pool_cap slots between them belong to
+ * nfopp_resample_pool and are left alone.  pool_dev / pool_age_dev are only read (not at all with pool_count = 0).
  * Draws: Philox4x32-10 keyed by seed, counter (index, stream, trajectory, rng_offset). */
 int nfopp_sample_candidates(const float* prev_traj_dev, int64_t batch, int32_t n_waypoints, int32_t dim,
                             int32_t pool_cap, int32_t pool_count, int32_t n_field, float course_sigma, float fine_sigma,
@@ -256,7 +278,9 @@ int nfopp_sample_candidates(const float* prev_traj_dev, int64_t batch, int32_t n
  * candidates kept WITHOUT replacement with probability proportional to the weights (exponential race), ages + 1.
  * The first n_candidates of cand_stride (= pool_cap + N - 1) candidate slots per trajectory are valid;
  * onf_out4_dev [B, cand_stride, 4] = nfopp_onf_eval_points on cand_dev.  The new pool is also written to
- * samples[b][sample_offset ...] (sample_stride = poses per trajectory in the samples buffer). */
+ * samples[b][sample_offset ...] (sample_stride = poses per trajectory in the samples buffer): all of pool_dev and
+ * pool_age_dev is written, of samples_dev the slots [sample_offset, sample_offset + pool_cap) of every trajectory and no
+ * other. */
 int nfopp_resample_pool(int64_t batch, int32_t n_candidates, int32_t cand_stride, int32_t pool_cap, int32_t dim,
                         int32_t sample_stride,
                         int32_t sample_offset, uint64_t seed, uint64_t rng_offset, int64_t traj_index_offset,
@@ -269,7 +293,9 @@ int nfopp_resample_pool(int64_t batch, int32_t n_candidates, int32_t cand_stride
  * The caller labels the poses with a ground-truth checker (above), then
  * nfopp_path_select_best: collides[b] = any label set; a collision-free path shorter than best_length[b] replaces
  *   best_traj[b]; a collision-free path that does not improve clears active[b] (the reference's `break`); inactive
- *   trajectories are skipped by nfopp_traj_update / nfopp_reparametrize when active_dev is passed to them. */
+ *   trajectories are skipped by nfopp_traj_update / nfopp_reparametrize when active_dev is passed to them.
+ * Written: every pose of poses_dev and every length_dev[b]; every collides_dev[b], for inactive trajectories too;
+ *   best_traj[b] and best_length[b] only where the path replaces the best one; active[b] only where it is cleared. */
 int nfopp_path_interpolate(const float* traj_dev, const float* start_dev, const float* goal_dev, int64_t batch,
                            int32_t n_waypoints, int32_t dim, int32_t sub, float* poses_dev, float* length_dev,
                            void* stream);
@@ -304,7 +330,8 @@ int nfopp_get_matrix_path(void);
  * nfopp_init_trajectories: TrajectoryInitializer.initialize_trajectory (+ initialize_angle and, with
  *   angles_with_direction != 0, initialize_angle_with_trajectory_direction; nfop/trajectory_initializer.py:12-45) for
  *   a batch: traj_dev [B, N, D] <- straight line start -> goal with torch.linspace's fp32 rounding, theta along the
- *   wrapped shortest rotation, optionally pulled towards the travel direction by a 0 -> 1 -> 0 ramp.
+ *   wrapped shortest rotation, optionally pulled towards the travel direction by a 0 -> 1 -> 0 ramp.  All B * N * D
+ *   floats are written.
  * nfopp_path_postprocess: PathPostprocessor.process (nfop/ros/path_postprocessor.py:13-69) for a batch of fp32 paths
  *   path_dev [B, n_points, 3] (3 <= n_points <= 1026): near-duplicate filter, quadratic-spline re-sampling every
  *   distance_step metres over the chord-length parameter (float64), leading direction flip trimmed.  count_dev[b] =
@@ -316,7 +343,8 @@ int nfopp_init_trajectories(const float* start_dev, const float* goal_dev, int64
 int nfopp_path_postprocess(const float* path_dev, int64_t batch, int32_t n_points, float minimal_distance,
                            float distance_step, int32_t max_out, double* out_dev, int32_t* count_dev, void* stream);
 /* torch.optim.Adam single-tensor update on a flat buffer (used for the ONF weights after the gradient
- * all-reduce): m.lerp_(g, 1-b1); v = b2 v + (1-b2) g^2; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps). */
+ * all-reduce): m.lerp_(g, 1-b1); v = b2 v + (1-b2) g^2; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps).  param, m and v are
+ * updated in place over [0, n) at every n (a grid-stride loop beyond 2048 * 256 elements); grad_dev is only read. */
 int nfopp_adam_step(float* param_dev, const float* grad_dev, float* m_dev, float* v_dev, int64_t n, float beta2,
                     float omb1, float omb2, float eps, float step_size, float bc2_sqrt, void* stream);
 
@@ -332,7 +360,7 @@ int nfopp_adam_step(float* param_dev, const float* grad_dev, float* m_dev, float
  *   grid hold the sentinel (-1, -1).  The result is the unique fixed point of the relaxation: bit-identical from run to
  *   run.  Grids whose padded field fits 144 KiB of LDS with 16 + 16-bit counts (at most 65535 cells) are relaxed in
  *   LDS; larger ones, up to 2^21 cells, in `workspace` (nfopp_grid_fields_workspace_bytes, 0 for the LDS form) with
- *   32 + 32-bit counts, so no count can wrap.
+ *   32 + 32-bit counts, so no count can wrap.  The workspace needs no initialisation; all of fields_dev is written.
  * nfopp_grid_trace_paths (find_path's parent walk, jps.py:56-66): problem p starts in start_cells_dev[p], ends in
  *   goal_cells_dev[p] and reads field field_index_dev[p].  From the start cell it steps to the first neighbour, in
  *   the order N, W, S, E, NW, NE, SW, SE of (row, col), whose cost plus the move equals the current cost exactly.
@@ -345,7 +373,8 @@ int nfopp_adam_step(float* param_dev, const float* grad_dev, float* m_dev, float
  *   re-sampled to n_waypoints + 2 points by the quadratic spline over the normalised chord length and the interior
  *   points are stored as fp32 in traj_dev [B, N, D]; headings as nfopp_init_trajectories writes them, the
  *   travel-direction pull along the seeded path.  A problem with status != 0 gets exactly nfopp_init_trajectories'
- *   trajectory.  Paths longer than 64 KiB of LDS allow need `workspace` (nfopp_grid_seed_workspace_bytes, else 0). */
+ *   trajectory.  Paths longer than 64 KiB of LDS allow need `workspace` (nfopp_grid_seed_workspace_bytes, else 0), which
+ *   needs no initialisation. */
 size_t nfopp_grid_fields_workspace_bytes(int32_t rows, int32_t cols, int64_t n_goals);
 int nfopp_grid_distance_fields(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, const int32_t* goal_cells_dev,
                                int64_t n_goals, int32_t* fields_dev, void* workspace_dev, size_t workspace_bytes,
@@ -386,7 +415,7 @@ int nfopp_grid_seed_trajectories(const int32_t* cells_dev, const int32_t* count_
  *   cells, and the 3 x 3 search of the check kernels stays exhaustive: clamping to an interval is monotone and
  *   non-expansive, so a point whose true cell is within one cell of a pose's true cell (in x and in y) is still within
  *   one after both are clamped.  n_obstacles = 0 is valid: cell_start_dev <- zeros, nothing else is touched.
- *   workspace: nfopp_cell_index_workspace_bytes(n_obstacles) bytes of device scratch. */
+ *   workspace: nfopp_cell_index_workspace_bytes(n_obstacles) bytes of device scratch; it needs no initialisation. */
 int nfopp_grid_to_points(const void* grid_dev, int32_t is_int8, int32_t rows, int32_t cols, float threshold,
                          double resolution, double origin_x, double origin_y, double origin_cos, double origin_sin,
                          int32_t max_points, float* points_dev, double* points64_dev, int32_t* count_dev, void* stream);
@@ -626,7 +655,8 @@ int nfopp_path_refined_labels(const uint8_t* seg_status_dev, const float* seg_s_
  *   outward from the cell over a copy of the row of g in LDS until (col - col')^2 alone exceeds the best distance.
  *   Integer arithmetic throughout, no atomics: the same bytes from run to run.
  *   Limits: 1 <= rows, cols <= 4096 and rows * cols <= 2^24 (the limit of nfopp_grid_to_points); larger input is an
- *   argument error.  workspace: nfopp_grid_edt_workspace_bytes(rows, cols) bytes of device scratch (0 = bad shape). */
+ *   argument error.  workspace: nfopp_grid_edt_workspace_bytes(rows, cols) bytes of device scratch (0 = bad shape); it
+ *   needs no initialisation. */
 size_t nfopp_grid_edt_workspace_bytes(int32_t rows, int32_t cols);
 int nfopp_grid_edt(const uint8_t* occupancy_dev, int32_t rows, int32_t cols, int32_t border, int32_t* dist2_dev,
                    int32_t* nearest_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
@@ -720,7 +750,7 @@ int nfopp_grid_seed_polylines(const float* points_dev, const int32_t* count_dev,
  *   fields_dev int32 [G, 8, rows, cols, 2] <- d_g.  One workgroup per goal state.  While the padded 8-layer field fits 144 KiB
  *   of LDS and 8 * rows * cols * (1 + turn_cost) <= 65535 the counts are packed 16 + 16 bits in LDS (no count can wrap);
  *   otherwise 32 + 32 bits in `workspace` (nfopp_lattice_fields_workspace_bytes, 0 for the LDS form and for a refused
- *   shape), 8-byte aligned.  No float atomics.
+ *   shape), 8-byte aligned, no initialisation needed.  No float atomics.
  * nfopp_lattice_trace_paths: one thread per problem.  start_states_dev int32 [B, 3] (row, col, heading), goal_states_dev
  *   int32 [B, 3], field_index_dev int32 [B] = the problem's field among n_total; fields_dev holds the n_fields fields
  *   field_first .. field_first + n_fields - 1 of them (a caller that cannot hold all fields at once calls once per chunk).
@@ -928,7 +958,8 @@ int nfopp_track_conflicts(const float* tracks_a_dev, int64_t ba, int32_t stride_
  *   delay_dev [b] int32, status_dev [b] int32, forbidden_dev [b] uint64 (may be null).
  * The two-step form lets a caller retry other priority orders -- the standard cure for an unresolved robot -- on the same
  *   masks at the cost of the assignment pass alone.
- * workspace_dev: nfopp_fleet_shift_masks_workspace_bytes(b, m) bytes (0 without obstacles), rewritten by every call.
+ * workspace_dev: nfopp_fleet_shift_masks_workspace_bytes(b, m) bytes (0 without obstacles), rewritten by every call (no
+ *   initialisation needed).  All of pair_mask_dev, base_mask_dev and bad_dev is written.
  * Everything runs on `stream`; nothing synchronises.  Argument errors: a negative batch size or one above 2^31 - 1, max_delay
  *   outside 0 .. 63, k < 1 or too large for an index, a stride < 2, margin not finite, a null pointer where one is read or
  *   written, more tiles of 8 x 8 pairs than a grid holds (2^31 - 1), a workspace that is null or too small, more robots than
@@ -976,8 +1007,10 @@ int nfopp_fleet_assign_delays(const uint64_t* pair_mask_dev, const uint64_t* bas
  *     last    [rows][W]             follows it
  *   nfopp_spacetime_reservation_bytes(rows, cols, t) bytes in all (0: not an image and t an int32 indexes).  The padding bits of
  *   a row (columns >= cols) are 1 in blocked and 0 in last.  nfopp_spacetime_reservation_init writes the static part (walls,
- *   the image edge, the padding) and clears last; nfopp_spacetime_reserve ORs the movers' bits in -- OR is order-free, so
- *   reserving a set of tracks in two calls gives the bits of one call.  Its workspace: nfopp_spacetime_reserve_workspace_bytes(m).
+ *   the image edge, the padding) and clears last -- every word of the reservation is written, for t = 1 (no blocked part)
+ *   too, so the buffer needs no initialisation; nfopp_spacetime_reserve ORs the movers' bits in -- OR is order-free, so
+ *   reserving a set of tracks in two calls gives the bits of one call.  Its workspace: nfopp_spacetime_reserve_workspace_bytes(m),
+ *   no initialisation needed.
  * Search of one robot, start cell s, goal cell g.  reach_0 = {s}; reach_{h+1}[v] = OR over d of (reach_h[v - d] and edge
  *   (v - d, d, h) not blocked).  park[t - 1] = !last[g]; park[h] = park[h + 1] and wait edge (g, 8, h) not blocked.  Arrival
  *   h* = the smallest h with reach_h[g] and park[h].  Path: cell[h] = g for h >= h*; backwards from (g, h*) the predecessor
@@ -995,7 +1028,8 @@ int nfopp_fleet_assign_delays(const uint64_t* pair_mask_dev, const uint64_t* bas
  *   initialises it and reserves the movers first.  Outputs: cells_dev [robots, t] int32 flat index row * cols + col,
  *   arrival_dev [robots], status_dev [robots], tracks_dev [robots, t, 2] fp32.  workspace_dev:
  *   nfopp_spacetime_plan_workspace_bytes(rows, cols, t, robots) bytes (reach of every instant, t * rows * W * 8, and a word
- *   of state per robot).  One search launch (one workgroup, both frontiers in LDS) and one reserve launch per order position,
+ *   of state per robot; no initialisation needed).  Every element of the four outputs is written.  One search launch (one
+ *   workgroup, both frontiers in LDS) and one reserve launch per order position,
  *   all on `stream`; nothing synchronises, no kernel waits on another workgroup.
  * The snap.  A planned track starts at the centre of the robot's start cell, up to res / sqrt(2) from where the robot stands:
  *   the caller adds that to margin.  Grid tracks are seeds and timetables, not smooth trajectories.
