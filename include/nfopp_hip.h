@@ -477,7 +477,8 @@ int nfopp_build_cell_index(const float* obstacles_dev, int32_t n_obstacles, floa
  *     7 NFOPP_PATH_STAT_MEAN_CLEARANCE sum / poses_per_path                           (+inf)
  *   pose_dist_dev [B, poses_per_path] (may be null) is whatever the caller measured along the densified path
  *   (nfopp_path_interpolate, then a nearest-obstacle query).  active_dev (may be null) is accepted for symmetry with the
- *   other per-path calls and NOT consulted: rows with active == 0 are written too, statistics are wanted for retired paths. */
+ *   other per-path calls and NOT consulted: rows with active == 0 are written too, statistics are wanted for retired paths.
+ *   A sign byte per segment and the reductions' 64 bytes sit in one workgroup's LDS: N <= 163775, beyond that "path too long". */
 #define NFOPP_NUM_PATH_STATS 8
 #define NFOPP_PATH_STAT_LENGTH 0
 #define NFOPP_PATH_STAT_MAX_CURVATURE 1

@@ -170,6 +170,13 @@ struct StatsArgs {
 
 constexpr int PS_THREADS = 256;
 constexpr int PS_WAVES = PS_THREADS / 64;
+constexpr int PS_HEAD = 64;                   // bytes in front of the sign array: the reductions' scratch
+static_assert(PS_WAVES * 8 + PS_WAVES * 4 <= PS_HEAD, "the reductions' scratch fits its head");
+
+// LDS of one path of N waypoints: the head and a sign byte per segment, every byte of it dynamic (a static array would come
+// off the 160 KiB without launch_dynamic_lds seeing it, as block_collectives.h notes).  The longest path served is the largest
+// N with ps_lds_bytes(N) <= 160 KiB: N = 163775.
+inline size_t ps_lds_bytes(long long n) { return (size_t)PS_HEAD + (size_t)((n + 1 + 15) & ~15LL); }
 
 // extremum with the first index attaining it: SIGN = +1 maximum, -1 minimum; index -1 = no candidate
 template <int SIGN>
@@ -187,9 +194,10 @@ struct Better {
 
 template <int D>
 __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs a) {
-  extern __shared__ signed char sgn[];   // [N + 1]: sign of each segment's forward component (dim 3)
-  __shared__ double red[PS_WAVES];
-  __shared__ int redi[PS_WAVES];
+  extern __shared__ __attribute__((aligned(16))) unsigned char ps_smem[];
+  double* red = reinterpret_cast<double*>(ps_smem);                    // [PS_WAVES]
+  int* redi = reinterpret_cast<int*>(ps_smem + PS_WAVES * 8);          // [PS_WAVES]
+  signed char* sgn = reinterpret_cast<signed char*>(ps_smem + PS_HEAD);   // [N + 1]: sign of each segment's forward component (dim 3)
   const long long b = blockIdx.x;
   const int N = a.n;
   auto point = [&](int f, int d) { return (double)path_entry<D>(a.traj, a.start, a.goal, N, b, f * D + d); };
@@ -338,7 +346,6 @@ extern "C" int nfopp_path_stats(const float* traj_dev, const float* start_dev, c
   StatsArgs a;
   a.traj = traj_dev; a.start = start_dev; a.goal = goal_dev; a.n = n_waypoints; a.dim = dim;
   a.pose_dist = pose_dist_dev; a.poses = poses_per_path; a.cos_cusp = cos_cusp; a.stats = stats_dev;
-  const size_t lds = ((size_t)n_waypoints + 1 + 15) & ~(size_t)15;
-  return launch_dynamic_lds(dim == 3 ? path_stats_kernel<3> : path_stats_kernel<2>, batch, PS_THREADS, lds, stream, a,
-                            "path too long");
+  return launch_dynamic_lds(dim == 3 ? path_stats_kernel<3> : path_stats_kernel<2>, batch, PS_THREADS,
+                            ps_lds_bytes(n_waypoints), stream, a, "path too long");
 }

@@ -6,6 +6,8 @@ import numpy as np
 F32 = np.float32
 NUM_PATH_STATS = 8
 (LENGTH, MAX_CURVATURE, CURVATURE_AT, CUSPS, REVERSALS, MIN_CLEARANCE, CLEARANCE_AT, MEAN_CLEARANCE) = range(NUM_PATH_STATS)
+# the longest path nfopp_path_stats serves: ps_lds_bytes(N) = 64 + 16 * ceil((N + 1) / 16) <= 160 KiB (csrc/clearance.hip)
+LONGEST_PATH = 163775
 
 
 def offsets(poses, points):

@@ -36,9 +36,39 @@ SHAPES = {
     "9x65": (9, 65, 0.30, 1, (0, 255), ()),                # a row across a 64-cell boundary; 255: the wide form by counts
     "20x23": (20, 23, 0.25, 8, (0, 1, 3), ()),             # a different occupancy per heading
     "40x130": (40, 130, 0.20, 1, (1,), ()),                # the wide form by size
+    # the LDS form past one trip of its 512 threads over the lines (every shape above that relaxes in LDS has fewer): 1808 lines,
+    # 4 trips, and lines of 300 cells
+    "2x300": (2, 300, "one", 1, (0, 3), ()),
+    "300x2": (300, 2, "one", 1, (0, 3), ()),
+    # row stride 9, padded 512 x 9 = 4608 cells: 8 layers are EXACTLY the 36864 words of LS_LDS_WORDS.  Turn cost 1 relaxes in
+    # LDS (counts 57120 <= 65535), 2 is wide by counts (85680); one row more (513 x 9) is wide by size
+    "510x7": (510, 7, 0.20, 1, (1, 2), ()),
+    "511x7": (511, 7, 0.20, 1, (0,), ()),
+    "65x65": (65, 65, 0.25, 1, (0,), ()),                  # the largest square field in LDS: 8 x 67 x 67 = 35912 words
 }
-WIDE = {("9x65", 255), ("40x130", 1)}                      # every other (shape, turn cost) relaxes in LDS
-TRACE_SHAPES = (("5x5", 0), ("5x5w", 0), ("9x65", 0), ("20x23", 1))
+# every other (shape, turn cost) relaxes in LDS
+WIDE = {("9x65", 255), ("40x130", 1), ("510x7", 2), ("511x7", 0)}
+TRACE_SHAPES = (("5x5", 0), ("5x5w", 0), ("9x65", 0), ("20x23", 1), ("2x300", 0), ("510x7", 1))
+TRACE_GOALS = {"9x65": 2, "2x300": 1, "510x7": 1}         # goals traced from every state (default 3): the large maps take fewer
+# 510 x 7 has 28560 states with paths of up to 439 cells, 24 s of restated traces: every 17th state (17 is coprime to the 7
+# columns and the 3570 cells of a heading, so every column and heading, and rows all along the map, still start paths) keeps
+# it under 2 s
+TRACE_EVERY = {"510x7": 17}
+# restated from csrc/lattice_search.hip (tests/test_lattice_cpu.py reads them back from the source)
+LS_THREADS = 512             # `constexpr int LS_THREADS = 512;`: the stride of lattice_field_body over the lines
+LS_LDS_WORDS = 36864         # `constexpr int LS_LDS_WORDS = 36864;`: the packed 8-layer field one workgroup's LDS holds
+
+
+def n_lines(name):
+    """The lines lattice_field_body shares among its threads: rows and columns twice, the diagonals four times."""
+    rows, cols = SHAPES[name][:2]
+    return 2 * rows + 2 * cols + 4 * (rows + cols - 1)
+
+
+def lds_words(name):
+    """Words of the padded 8-layer field: (rows + 2) rows of odd stride (cols + 2) | 1."""
+    rows, cols = SHAPES[name][:2]
+    return 8 * (rows + 2) * ((cols + 2) | 1)
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,13 +116,15 @@ def fields_of(name, turn_cost):
     return out
 
 
-def trace_problems(name, max_goals=3):
-    """Starts at every state of the map (blocked ones included) towards the first goals of the shape -> (starts [B, 3],
-    goal states [B, 3], field_index [B]) with B a multiple of the state count."""
+def trace_problems(name, max_goals=None):
+    """Starts at every state of the map (blocked ones included; every TRACE_EVERY-th where the map has an entry there) towards
+    the first goals of the shape (TRACE_GOALS of them unless `max_goals` says otherwise) -> (starts [B, 3], goal states
+    [B, 3], field_index [B]) with B a multiple of the number of start states."""
     rows, cols = SHAPES[name][:2]
     goals = goals_of(name)
+    max_goals = TRACE_GOALS.get(name, 3) if max_goals is None else max_goals
     n = min(max_goals, 4 if SHAPES[name][2] is not None else 2)
-    states = np.asarray([(r, c, h) for h in range(8) for r in range(rows) for c in range(cols)], np.int32)
+    states = np.asarray([(r, c, h) for h in range(8) for r in range(rows) for c in range(cols)], np.int32)[::TRACE_EVERY.get(name, 1)]
     starts = np.concatenate([states] * n)
     fidx = np.repeat(np.arange(n, dtype=np.int32), len(states))
     return starts, goals[fidx], fidx

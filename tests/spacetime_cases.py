@@ -76,7 +76,8 @@ def strict(closer, T=3):
 
 # rows x cols x T x movers x robots of the device comparison: the smallest cases, a row of 63 / 64 / 65 cells (one word and the
 # word boundary), the size of the re-planning example, and three words a row with more movers than the reserve kernel stages
-# per trip (16) and more cells than the search kernel has threads
+# per trip (16).  The last has more CELLS (5200) than the search kernel has threads, but only rows * words = 120 WORDS, which is
+# what that kernel's loops run over: the sizes past one trip of it are EDGES, below
 SIZES = ((1, 1, 1, 0, 1), (1, 2, 2, 1, 1), (3, 7, 8, 0, 2), (5, 63, 9, 2, 3), (5, 64, 9, 3, 3), (5, 65, 9, 3, 3), (24, 24, 41, 8, 8),
          (40, 130, 33, 17, 17))
 STRIDES = (2, 3, 4, 2, 3, 4, 3, 2)
@@ -131,6 +132,72 @@ def sized_case(n, seed=0):
 
 def orders(r, seed=0):
     return fc.orders(r, seed)
+
+
+# ---- the sizes past one trip of the plan kernels' loops, and the largest frontier ----------------------------------------------
+# The constants of csrc/spacetime_search.hip these cases are sized by, restated (tests/test_spacetime_cpu.py reads them back
+# from the source and computes what each case reaches): a constant that moves there names the case to replace here.
+SEARCH_THREADS = 1024            # `constexpr int ST_SEARCH_THREADS = 1024;`: the stride of st_search_kernel over words and instants
+INIT_GRID, INIT_THREADS = 2048, 256   # `init_blocks < 2048 ? init_blocks : 2048` in nfopp_spacetime_plan_fleet, `ST_THREADS = 256`
+LDS_BYTES = 160 * 1024           # `NFOPP_REQUIRE(lds <= 160 * 1024, "frontier too large ...` in nfopp_spacetime_plan_fleet
+SEARCH_HEAD = 64                 # `constexpr int ST_SEARCH_HEAD = 64;`: lds = ST_SEARCH_HEAD + 2 * rows * words * 8
+LARGEST_RW = (LDS_BYTES - SEARCH_HEAD) // 16   # 10236 words: exactly 160 KiB
+
+
+def words_past_one_trip():
+    """1040 x 3, T = 24: one word a row, rows * words = 1040 > 1024 -- the word loop of the search takes a second trip.  A mover
+    stands on (1030, 1) throughout; robot 0 goes down column 1 past it, robot 1 comes up from the last row."""
+    T = 24
+    return case(np.zeros((1040, 3)), T, [(1018, 1), (1039, 0)], [(1036, 1), (1025, 2)], tracks=[standing((1030, 1), range(T), T)])
+
+
+def carry_past_one_trip():
+    """513 x 65, T = 6: two words a row, rows * words = 1026.  The one robot crosses from column 63 to column 64 in the last rows:
+    the bit arrives in word 1025 from word 1024, the neighbour-word carry of a second trip."""
+    return case(np.zeros((513, 65)), 6, [(510, 60)], [(512, 64)])
+
+
+def visited_goal(T=1100, comes=1030, leaves=1041):
+    """1 x 4: the robot stands on its goal from instant 3 on, until a mover comes to stand there during comes .. leaves - 1; it
+    steps aside and is back at `leaves`.  In the parked_on_goal cases the goal is not REACHED before the mover has left, so the
+    arrival does not depend on the park scan; here reach holds at the goal from instant 3 on, and only a park scan that
+    finds the blocked wait edge at leaves - 1 >= 1024 -- in its second trip -- keeps the arrival from being 3."""
+    return case(np.zeros((1, 4)), T, [(0, 0)], [(0, 3)], tracks=[standing((0, 3), range(comes, leaves), T)])
+
+
+def many_robots(robots=513, T=1025):
+    """1 x 4, T = 1025, 513 robots: robots * T = 525825 entries for st_plan_init_kernel's 524288 threads.  `order` visits three
+    robots (the last, one of the first, one in the middle), at positions 0, 7 and the last; everyone else keeps what the init
+    kernel wrote."""
+    starts, goals = np.zeros((robots, 2), np.int32), np.zeros((robots, 2), np.int32)
+    visited = [robots - 1, 5, robots // 2]
+    starts[visited, 1], goals[visited, 1] = (0, 3, 2), (1, 3, 2)
+    order = np.full(robots, -1, np.int32)
+    order[[0, 7, robots - 1]] = visited
+    return case(np.zeros((1, 4)), T, starts, goals, order=order)
+
+
+def largest_frontier(rows=LARGEST_RW):
+    """rows x 1, T = 3: at 10236 rows both frontiers and the head are exactly 160 KiB of dynamic LDS.  One robot goes from the
+    last row but one to the last."""
+    return case(np.zeros((rows, 1)), 3, [(rows - 2, 0)], [(rows - 1, 0)])
+
+
+# name -> (the case, statuses, arrivals of the robots `order` visits, in index order)
+EDGES = {
+    "1040x3": (words_past_one_trip, [0, 0], [18, 14]),
+    "513x65": (carry_past_one_trip, [0], [4]),
+    "T=1025": (lambda: parked_on_goal(T=1025, leaves=1024), [0], [1024]),      # hb = 1023 in the first trip, ha = 1024 in the second
+    "T=1026": (lambda: parked_on_goal(T=1026, leaves=1025), [0], [1025]),      # hb = 1024: both in the second
+    "T=1100": (lambda: parked_on_goal(T=1100, leaves=1060), [0], [1060]),
+    "T=1100-back":(visited_goal, [0], [1041]),                               # reached at 3; hb = 1040 is what delays the arrival
+    "R=513": (many_robots, [0, 0, 0], [0, 0, 1]),
+    "10236x1": (largest_frontier, [0], [1]),
+}
+
+
+def edge_case(name):
+    return EDGES[name][0]()
 
 
 def circle_replan_odd():

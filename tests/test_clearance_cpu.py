@@ -1,6 +1,7 @@
 """CPU-only tests of the clearance feature: the numpy restatement (tests/clearance_ref.py) against hand-computed cases,
 the argument checks of the three C-ABI entries without a device, and the slot constants."""
 import ctypes
+import os
 
 import numpy as np
 
@@ -126,3 +127,16 @@ def test_c_abi_argument_checks():
     assert stats(poses=0) == -1 and stats(poses=-1, dist=None) == -1 and b"pose count" in err()
     assert stats(cos_cusp=float("nan")) == -1
     assert stats(n=200000) == -1 and b"too long" in err()              # the sign array must fit one workgroup's LDS
+    # with the reductions' 64-byte head in front of it, all of it dynamic: 64 + 16 * ceil((N + 1) / 16) bytes in 160 KiB.  The
+    # last N served (cr.LONGEST_PATH, run on the device in tests/test_gpu_clearance.py) asks for exactly 163840 bytes, the first
+    # one refused for 16 more -- the message carries the request.  N = 163792 .. 163839 fit while the head was static LDS
+    # that the check did not count
+    assert 64 + (cr.LONGEST_PATH + 1 + 15) // 16 * 16 == 160 * 1024 == 163840
+    for dim in (2, 3):
+        assert stats(n=cr.LONGEST_PATH + 1, dim=dim) == -1 and b"too long" in err() and b"(163856 bytes)" in err()
+        assert stats(n=163792, dim=dim) == -1 and stats(n=163839, dim=dim) == -1 and b"too long" in err()
+    kernel = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pytorch-motion-planner_amd", "csrc",
+                               "clearance.hip")).read()
+    stats_kernel = kernel[kernel.index("void path_stats_kernel("):kernel.index("static void launch_nearest(")]
+    assert "extern __shared__" in stats_kernel and stats_kernel.count("__shared__") == 1      # no static array beside the dynamic block
+    assert "constexpr int PS_HEAD = 64;" in kernel and "N = %d" % cr.LONGEST_PATH in kernel

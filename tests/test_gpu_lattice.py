@@ -2,7 +2,10 @@
 tests/lattice_ref.py (test_lattice_cpu.py checks the restatement and the cases without a GPU).
 
 Everything compared here is an integer (fields, cells, headings, counts, costs, status) or comes from the same kernel on
-the same input (seeded trajectories, checker labels): every comparison is `==` on the bits."""
+the same input (seeded trajectories, checker labels): every comparison is `==` on the bits.
+
+Measured on an MI355X: the whole file takes 6.6 s.  The shapes at the LDS form's stride and capacity edges (2x300, 300x2,
+510x7, 511x7, 65x65: lattice_cases.SHAPES) take 2.2 s of it, mostly their restated fields and traces, none more than 0.6 s."""
 import functools
 
 import numpy as np
@@ -91,7 +94,7 @@ def _trace(fields, first, n_total, rows, cols, tc, starts, goals, fidx, max_len)
 def _trace_case(name, tc):
     """Every state of the map as a start (blocked ones included) towards the first goals, then the refused problems."""
     rows, cols = lc.SHAPES[name][:2]
-    starts, goals, fidx = lc.trace_problems(name, max_goals=2 if name == "9x65" else 3)
+    starts, goals, fidx = lc.trace_problems(name)
     g0 = lc.goals_of(name)[0]
     n_goals = len(lc.goals_of(name))
     bad_starts = [(0, 0, 0), (0, 0, 0), (-1, 0, 0), (rows, 0, 0), (0, cols, 0), (0, -1, 0), (0, 0, -1), (0, 0, 8), (0, 0, 0)]

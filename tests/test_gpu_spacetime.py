@@ -1,11 +1,16 @@
 """GPU: nfopp_spacetime_reservation_init, nfopp_spacetime_reserve and nfopp_spacetime_plan_fleet (csrc/spacetime_search.hip)
 against the numpy restatement (tests/spacetime_ref.py), bit for bit: the blocked and last bitmaps, cells, arrivals, statuses and
 tracks (NaN rows as bits), at the sizes where the kernels take another path (one cell, a row of 63 / 64 / 65 cells -- one word
-and the word boundary --, three words a row, more movers than the reserve kernel stages per trip, more words than the search
-kernel has threads); then the device's own end-to-end check through nfopp.track_conflicts and the Python interface.
+and the word boundary --, three words a row, more movers than the reserve kernel stages per trip); at the sizes past one trip
+of the plan kernels' strided loops (spacetime_cases.EDGES: more than 1024 words, with one and with two words a row; more than
+1024 instants on either side of the trip boundary; more robots x instants than the init kernel has threads) and at the largest
+frontier one workgroup's LDS holds; then the device's own end-to-end check through nfopp.track_conflicts and the Python
+interface.  The 40 x 130 case has more cells than the search kernel has threads but only 120 words, which is what its loops
+run over: it never took them past one trip.
 
-Measured on an MI355X: the whole file takes about 9 s; about 4 s of it are the numpy restatement of the movers of the 40 x 130 x 33
-case, which is computed once and shared, never written to."""
+Measured on an MI355X: the whole file takes 8.4 s; about 4 s of it are the numpy restatement of the movers of the 40 x 130 x 33
+case, which is computed once and shared, never written to.  The eight EDGES cases and the refusal take 0.6 s together, none
+more than 0.2 s."""
 import functools
 
 import numpy as np
@@ -72,6 +77,13 @@ def _raw_reserve(c, words, lo=0, hi=None):
 
 
 def _raw_plan(c, words, order="case"):
+    rc, out = _plan_call(c, words, order)
+    _lib.check(rc)
+    return out
+
+
+def _plan_call(c, words, order="case"):
+    """-> (the entry's return value, (cells, arrival, status, tracks) poisoned with -7 / 7.0 before the call)."""
     lib, L = _lib.load(), _lib
     g, T = c["geo"], c["T"]
     r = len(c["starts"])
@@ -83,11 +95,11 @@ def _raw_plan(c, words, order="case"):
     tracks = torch.full((r, T, 2), 7.0, dtype=torch.float32, device="cuda")
     nbytes = lib.nfopp_spacetime_plan_workspace_bytes(g.rows, g.cols, T, r)
     ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    L.check(lib.nfopp_spacetime_plan_fleet(L.ptr(occ, torch.uint8), *_geometry(c), L.ptr(starts, torch.int32), L.ptr(goals, torch.int32),
-                                           L.ptr(order, torch.int32), r, L.ptr(words, torch.int64), words.numel() * 8,
-                                           L.ptr(cells, torch.int32), L.ptr(arrival, torch.int32), L.ptr(status, torch.int32),
-                                           L.ptr(tracks), L.ptr(ws, torch.uint8), nbytes, L.stream_ptr()))
-    return cells, arrival, status, tracks
+    rc = lib.nfopp_spacetime_plan_fleet(L.ptr(occ, torch.uint8), *_geometry(c), L.ptr(starts, torch.int32), L.ptr(goals, torch.int32),
+                                        L.ptr(order, torch.int32), r, L.ptr(words, torch.int64), words.numel() * 8,
+                                        L.ptr(cells, torch.int32), L.ptr(arrival, torch.int32), L.ptr(status, torch.int32),
+                                        L.ptr(tracks), L.ptr(ws, torch.uint8), nbytes, L.stream_ptr())
+    return rc, (cells, arrival, status, tracks)
 
 
 def _split(c, words):
@@ -172,6 +184,34 @@ def test_hand_cases():
             assert 3 in cells[0].tolist() and 3 not in cells[1].tolist()
         if label == "gate":
             assert cells[0].tolist() == [0, 0, 1, 0, 1, 2, 3, 4, 5, 6, 7, 7]
+
+
+@pytest.mark.parametrize("name", list(sc.EDGES))
+def test_sizes_past_one_trip_and_the_largest_frontier_equal_the_restatement_bit_for_bit(name):
+    """spacetime_cases.EDGES through init, reserve, plan, the reservation after the fleet, and a second run on fresh poisoned
+    buffers; what each case reaches is computed in tests/test_spacetime_cpu.py."""
+    c = sc.edge_case(name)
+    _, status, arrival = sc.EDGES[name]
+    (cells, arr, st, tracks), words, want, _ = _run(c, name)
+    visited = np.flatnonzero(want["status"] != sr.STATUS_NOT_ORDERED)
+    assert st.cpu().numpy()[visited].tolist() == status and arr.cpu().numpy()[visited].tolist() == arrival, (name, visited)
+    again = _raw_plan(c, _raw_reserve(c, _raw_init(c)))
+    assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip((cells, arr, st, tracks), again))
+    if name == "R=513":       # everyone `order` leaves out holds what the init kernel wrote, past its grid's one trip too
+        off = torch.tensor(want["status"] == sr.STATUS_NOT_ORDERED, device="cuda")
+        assert int(off.sum()) == len(c["starts"]) - 3 and len(c["starts"]) * c["T"] > sc.INIT_GRID * sc.INIT_THREADS
+        assert (cells[off] == -1).all() and (arr[off] == -1).all() and torch.isnan(tracks[off]).all()
+
+
+def test_a_frontier_one_row_past_the_largest_is_refused_and_nothing_is_written():
+    c = sc.largest_frontier(sc.LARGEST_RW + 1)
+    words = _raw_init(c)
+    before = words.clone()
+    rc, (cells, arrival, status, tracks) = _plan_call(c, words)
+    assert rc == -1 and "frontier too large" in _lib.load().nfopp_last_error().decode()
+    torch.cuda.synchronize()
+    assert (cells == -7).all() and (arrival == -7).all() and (status == -7).all() and (tracks == 7.0).all()
+    assert torch.equal(words, before)
 
 
 def _grid(c):

@@ -1,7 +1,10 @@
 """GPU: nfopp_path_time_profile / nfopp_path_time_sample (csrc/time_profile.hip) against the numpy restatement
 (tests/time_profile_ref.py), bit for bit: profile, gear, summary, states and segment, at the sizes where the kernel takes
-another path (one interior vertex, the wave boundary at N + 2 = 64 / 65 / 66, the 256-thread stride, several trips); then
-the Python interface and the torch ops against the raw calls."""
+another path (one interior vertex, the wave boundary at N + 2 = 64 / 65 / 66, the 256-thread stride, several trips, the
+longest path whose image fits one workgroup's LDS and the refusal one waypoint past it); then the Python interface and the
+torch ops against the raw calls.
+
+Measured on an MI355X: the whole file takes 4.0 s; the two longest-path cases take 0.06 s each."""
 import numpy as np
 import pytest
 import torch
@@ -73,6 +76,46 @@ def test_profile_and_samples_equal_the_restatement_bit_for_bit(b, n, dim):
         states, segment = tr.sample_batch(paths, prof, gear, tc.LIMITS, 0.0, 0.01, 700)
         got_states, got_segment = got.sample(0.01, 700, want_segment=True)
         assert _same_bits(got_segment, segment) and _same_bits(got_states, states)
+
+
+@pytest.mark.parametrize("dim,n", tc.LONGEST)
+def test_the_longest_path_served_equals_the_restatement_and_one_waypoint_more_is_refused(dim, n):
+    """N + 2 = 3032 (dim 3) / 3275 (dim 2): the largest LDS image the entry accepts, every thread 12 or 13 trips over the
+    vertices.  Profile, gear, summary and samples bit for bit; at N + 1 the call answers "path too long" and writes nothing."""
+    b = tc.LONGEST_B
+    paths, vs, vg = tc.batch(tc.LONGEST_SEED, b, n, dim)
+    assert tc.lds_bytes(n + 2, dim) <= 160 * 1024 < tc.lds_bytes(n + 3, dim)
+    if dim == 3:
+        assert min(tc.forward_margin(p) for p in paths) >= 1e-6
+    prof, gear, summary = tr.profile_batch(paths, tc.LIMITS, vs, vg)
+    assert (summary[:, tr.SUM_STATUS] != 4).all()
+    got = _timed(paths, vs=vs, vg=vg)
+    assert _same_bits(got.gear, gear)
+    assert _same_bits(got.summary, summary), (got.summary.cpu().numpy(), summary)
+    assert _same_bits(got.profile, prof), np.argwhere(got.profile.cpu().numpy() != prof)[:8]
+    again = _timed(paths, vs=vs, vg=vg)
+    assert torch.equal(again.profile, got.profile) and torch.equal(again.gear, got.gear) and torch.equal(again.summary, got.summary)
+    # 61 instants from before the start to past the end, and 700 on a finer grid that ends past the slowest path's goal
+    total = float(np.nanmax(prof[:, -1, tr.SLOT_T]))
+    for t0, dt, count in (_instants(prof), (0.0, total / 650, 700)):
+        states, segment = tr.sample_batch(paths, prof, gear, tc.LIMITS, t0, dt, count)
+        got_states, got_segment = got.sample(dt, count, t0=t0, want_segment=True)
+        assert segment.max() == n + 1 and len(np.unique(segment)) > count // 2      # all along the path, and past its end
+        assert _same_bits(got_segment, segment)
+        assert _same_bits(got_states, states), np.argwhere(got_states.cpu().numpy() != states)[:8]
+    # one waypoint more: refused before anything is launched, the poisoned outputs stay as they were
+    lib, L = _lib.load(), _lib
+    traj = torch.zeros(1, n + 1, dim, device="cuda")
+    start, goal = torch.zeros(1, dim, device="cuda"), torch.ones(1, dim, device="cuda")
+    profile_dev = torch.full((1, n + 3, 4), -7.0, dtype=torch.float64, device="cuda")
+    gear_dev = torch.full((1, n + 2), -7, dtype=torch.int8, device="cuda")
+    summary_dev = torch.full((1, 4), -7.0, dtype=torch.float64, device="cuda")
+    rc = lib.nfopp_path_time_profile(L.ptr(traj), L.ptr(start), L.ptr(goal), 1, n + 1, dim, LIMITS.to_c(), None, None,
+                                     L.ptr(profile_dev, torch.float64), L.ptr(gear_dev, torch.int8), L.ptr(summary_dev, torch.float64),
+                                     L.stream_ptr())
+    assert rc == -1 and "path too long" in lib.nfopp_last_error().decode()
+    torch.cuda.synchronize()
+    assert (profile_dev == -7.0).all() and (gear_dev == -7).all() and (summary_dev == -7.0).all()
 
 
 def test_out_of_range_rows_are_nan_and_the_others_untouched():

@@ -101,7 +101,7 @@ def test_what_the_device_cases_cover():
     for name, tc in lc.TRACE_SHAPES:
         layers, fields = lc.layers_of(name), lc.fields_of(name, tc)
         rows, cols = layers.shape[1:]
-        starts, goal_states, fidx = lc.trace_problems(name, max_goals=2 if name == "9x65" else 3)
+        starts, goal_states, fidx = lc.trace_problems(name)
         step = max(1, len(starts) // 1500)
         cells, heads, count, status, _ = lr.search(fields, (rows, cols), starts[::step], goal_states[::step], fidx[::step], tc)
         statuses |= set(int(s) for s in status)
@@ -123,6 +123,23 @@ def test_what_the_device_cases_cover():
     assert statuses == {0, 1, 2}
     assert headings_seen == set(range(8)) and {1, 7} <= turns
     assert layer_dependent and wall_goal and blocked_start
+    # the LDS form at its stride and capacity edges, against the kernel's constants as its source states them: some shape that
+    # relaxes in LDS has more lines than the kernel has threads (2x300 / 300x2: 1808, four trips), one fills LS_LDS_WORDS
+    # exactly (510x7), and the shapes on the other side of each dispatch edge are wide
+    kernel = open(os.path.join(CSRC, "lattice_search.hip")).read()
+    for text in ("constexpr int LS_THREADS = %d;" % lc.LS_THREADS, "constexpr int LS_LDS_WORDS = %d;" % lc.LS_LDS_WORDS,
+                 "for (int q = threadIdx.x; q < n_lines; q += LS_THREADS)", "const int n_lines = 2 * rows + 2 * cols + 4 * n_diag;",
+                 "*stride = (cols + 2) | 1;", "LS_HEADINGS * *padded <= LS_LDS_WORDS && counts <= 65535"):
+        assert text in kernel, (text, "the kernel's constant or loop moved: replace the shape sized by it")
+    in_lds = [(n, tc) for n, s in lc.SHAPES.items() for tc in s[4] if (n, tc) not in lc.WIDE]
+    assert all(lc.lds_words(n) <= lc.LS_LDS_WORDS and 8 * lc.SHAPES[n][0] * lc.SHAPES[n][1] * (1 + tc) <= 65535 for n, tc in in_lds)
+    assert max(lc.n_lines(n) for n, _ in in_lds) > 3 * lc.LS_THREADS
+    assert lc.n_lines("2x300") == lc.n_lines("300x2") == 1808 and ("2x300", 3) in in_lds and ("300x2", 3) in in_lds
+    assert any(lc.lds_words(n) == lc.LS_LDS_WORDS for n, _ in in_lds) and lc.lds_words("510x7") == 8 * 512 * 9 == lc.LS_LDS_WORDS
+    assert ("510x7", 1) in in_lds and 8 * 510 * 7 * 2 == 57120 <= 65535 < 8 * 510 * 7 * 3 and ("510x7", 2) in lc.WIDE
+    assert lc.lds_words("511x7") == 8 * 513 * 9 > lc.LS_LDS_WORDS and ("511x7", 0) in lc.WIDE
+    assert lc.lds_words("65x65") == 35912 and ("65x65", 0) in in_lds
+    assert {("2x300", 0), ("510x7", 1)} <= set(lc.TRACE_SHAPES)
     layers, goal = lc.approach_case()
     fixed, free = lr.lattice_field(layers, goal, 0), lr.lattice_field(layers, goal[:2] + (-1,), 0)
     assert tuple(fixed[0, 1, 0]) == (-1, -1) and len(lr.trace_path(fixed, (1, 0, 0))[0]) == 0      # status 1

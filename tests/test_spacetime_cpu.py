@@ -310,7 +310,8 @@ def test_reordering_is_relabelling_and_odd_orders_skip(solved):
 
 
 # ---- coverage, computed from the restatement ---------------------------------------------------------------------------------
-def test_case_set_covers_what_it_claims(solved):
+def test_case_set_covers_what_it_claims(solved, solved_edges):
+    _edge_claims(solved_edges)
     statuses, dirs = set(), set()
     for name, c, before, after, p in solved:
         statuses |= set(p["status"].tolist())
@@ -333,6 +334,81 @@ def test_case_set_covers_what_it_claims(solved):
     seen = dict(c, tracks=np.where(np.isfinite(c["tracks"][:, :, :2]), c["tracks"][:, :, :2], 0).astype(F32), visible=None,
                 radius=np.where(np.isfinite(c["radius"]), c["radius"], F32(0.05)))
     assert (sr.pack_rows(mover_only(seen)[0], False) != wb).any()
+
+
+@pytest.fixture(scope="module")
+def solved_edges():
+    return {name: (sc.edge_case(name),) + sc.solve(sc.edge_case(name)) for name in sc.EDGES}
+
+
+def _word_index(c, cells):
+    """rows * words index of the word each flat cell index sits in."""
+    cells = np.asarray(cells)
+    return cells // c["geo"].cols * c["geo"].words + cells % c["geo"].cols // 64
+
+
+def _edge_claims(solved_edges):
+    """The second half of test_case_set_covers_what_it_claims.  What each case of spacetime_cases.EDGES reaches in csrc/spacetime_search.hip, computed from the restatement against the
+    kernel's constants as that file states them: a case shrunk below its stride or capacity edge fails here."""
+    src = open(os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc", "spacetime_search.hip")).read()
+    for text in ("constexpr int ST_SEARCH_THREADS = %d;" % sc.SEARCH_THREADS, "constexpr int ST_THREADS = %d;" % sc.INIT_THREADS,
+                 "init_blocks < %d ? init_blocks : %d" % (sc.INIT_GRID, sc.INIT_GRID), "constexpr int ST_SEARCH_HEAD = %d;" % sc.SEARCH_HEAD,
+                 "NFOPP_REQUIRE(lds <= 160 * 1024", "for (int q = tid; q < rw; q += ST_SEARCH_THREADS)",
+                 "for (int h = tid; h + 1 < p.T; h += ST_SEARCH_THREADS)", "for (int h = tid; h < p.T; h += ST_SEARCH_THREADS)",
+                 "k += (long long)gridDim.x * ST_THREADS"):
+        assert text in src, (text, "the kernel's constant or loop moved: replace the case sized by it")
+    assert sc.LDS_BYTES == 160 * 1024 and sc.LARGEST_RW == 10236
+    trip = sc.SEARCH_THREADS
+    for name, (c, before, after, p) in solved_edges.items():
+        _, status, arrival = sc.EDGES[name]
+        visited = np.flatnonzero(p["status"] != sr.STATUS_NOT_ORDERED)
+        assert p["status"][visited].tolist() == status and p["arrival"][visited].tolist() == arrival, name
+    # more words than one trip of the word loop: a path and a frontier with cells in words on either side of the trip boundary
+    for name in ("1040x3", "513x65"):
+        c, before, after, p = solved_edges[name]
+        assert c["geo"].rows * c["geo"].words > trip, name
+        on = np.flatnonzero(p["status"] == 0)
+        assert any((_word_index(c, p["cells"][i]) < trip).any() and (_word_index(c, p["cells"][i]) >= trip).any() for i in on), name
+        reach = sr.reach_sets(before, tuple(int(x) for x in c["starts"][on[0]]))
+        flat = reach.reshape(c["T"], -1)
+        word = _word_index(c, np.arange(flat.shape[1]))
+        assert ((flat & (word < trip)).any(axis=1) & (flat & (word >= trip)).any(axis=1)).any(), name
+    assert solved_edges["1040x3"][0]["geo"].words == 1 and solved_edges["513x65"][0]["geo"].words == 2
+    # the carry between neighbouring words in the second trip: a move of the path between two words of one row, both past it
+    c, _, _, p = solved_edges["513x65"]
+    cells = p["cells"][0]
+    rows_, cols_ = cells // c["geo"].cols, cells % c["geo"].cols
+    crossing = (rows_[1:] == rows_[:-1]) & (cols_[1:] // 64 != cols_[:-1] // 64)
+    assert (crossing & (_word_index(c, cells[1:]) >= trip) & (_word_index(c, cells[:-1]) >= trip)).any()
+    # more instants than one trip: the last blocked wait edge at the goal (hb) and the arrival (ha) relative to the trip boundary
+    for name, hb_second, ha in (("T=1025", False, 1024), ("T=1026", True, 1025), ("T=1100", True, 1060)):
+        c, before, _, p = solved_edges[name]
+        gr, gc = (int(x) for x in c["goals"][0])
+        hb = int(np.flatnonzero(before.blocked[:, sr.WAIT, gr, gc]).max())
+        assert c["T"] > trip and (hb >= trip) == hb_second and hb == ha - 1 and p["arrival"].tolist() == [ha] and ha >= trip, (name, hb)
+    assert [int(np.flatnonzero(solved_edges[n][1].blocked[:, sr.WAIT, 0, 3]).max()) for n in ("T=1025", "T=1026")] == [trip - 1, trip]
+    # in those three the goal is first reached at the arrival, whatever the park scan finds; in this one it is reached in the
+    # first trip and the arrival is one past a blocked wait edge in the second: a park scan of one trip would answer 3
+    c, before, _, p = solved_edges["T=1100-back"]
+    at_goal = sr.reach_sets(before, (0, 0))[:, 0, 3]
+    hb = int(np.flatnonzero(before.blocked[:, sr.WAIT, 0, 3]).max())
+    assert at_goal[3] and not at_goal[:3].any() and hb >= trip and p["arrival"].tolist() == [hb + 1] and at_goal[hb + 1]
+    assert not before.blocked[:trip, sr.WAIT, 0, 3].any()
+    for name in ("T=1025", "T=1026", "T=1100"):
+        c, before, _, p = solved_edges[name]
+        assert not sr.reach_sets(before, (0, 0))[:p["arrival"][0], 0, 3].any(), name
+    # more robots x instants than the init kernel's capped grid has threads; three robots visited, distinct goals
+    c, _, _, p = solved_edges["R=513"]
+    r = len(c["starts"])
+    assert r * c["T"] > sc.INIT_GRID * sc.INIT_THREADS == 524288 and r > 2 * sc.INIT_THREADS    # robots' own rows past a workgroup too
+    visited = np.flatnonzero(p["status"] != sr.STATUS_NOT_ORDERED)
+    assert len(visited) == 3 and (c["order"] >= 0).sum() == 3 and len({tuple(g) for g in c["goals"][visited]}) == 3
+    assert visited.min() < 256 and visited.max() == r - 1
+    # the largest frontier: exactly the 160 KiB the entry accepts, one row more is over
+    c = solved_edges["10236x1"][0]
+    rw = c["geo"].rows * c["geo"].words
+    assert sc.SEARCH_HEAD + 2 * rw * 8 == sc.LDS_BYTES and c["starts"][0, 0] == rw - 2 and c["goals"][0, 0] == rw - 1
+    assert _plan_rc(rows=rw, cols=1, t=3, robots=0) == 0 and _plan_rc(rows=rw + 1, cols=1, t=3, robots=0) == -1
 
 
 def test_pack_rows_layout():

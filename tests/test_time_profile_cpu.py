@@ -244,6 +244,18 @@ def test_every_argument_check_answers_without_a_gpu():
     refused(_profile_rc(_limits(), n=5000), "path too long")
     refused(_profile_rc(_limits(), n=3031), "path too long")           # N + 2 = 3033 at dim 3
     refused(_profile_rc(_limits(), n=3274, dim=2), "path too long")
+    # tests/test_gpu_time_profile.py runs the device at time_profile_cases.LONGEST: the last N whose image fits, by the source's
+    # own formula; its paths keep the forward component the gears are read from away from zero
+    src = open(os.path.join(ROOT, "pytorch-motion-planner_amd", "csrc", "time_profile.hip")).read()
+    assert "return (size_t)(TP_WAVES * 16 + m * 40 + ((m * dim * 4 + 7) & ~7LL) + ((2 * m + 15) & ~15LL));" in src
+    assert "constexpr int TP_THREADS = 256;" in src and dict(tc.LONGEST) == {3: 3030, 2: 3273}
+    for dim, n in tc.LONGEST:
+        assert tc.lds_bytes(n + 2, dim) <= 160 * 1024 < tc.lds_bytes(n + 3, dim)
+        refused(_profile_rc(_limits(), n=n + 1, dim=dim), "path too long")
+        paths, _, _ = tc.batch(tc.LONGEST_SEED, tc.LONGEST_B, n, dim)
+        assert paths.shape == (tc.LONGEST_B, n + 2, dim)
+        if dim == 3:
+            assert min(tc.forward_margin(p) for p in paths) >= 1e-6
     for dt in (0.0, -0.1, np.inf, np.nan):
         refused(_sample_rc(_limits(), dt=dt), "dt")
     refused(_sample_rc(_limits(), t0=np.nan), "t0")

@@ -10,6 +10,15 @@ F32 = np.float32
 LIMITS = tr.Limits(v_max=2.0, a_max=1.0, d_max=1.5, a_lat=1.0, w_max=1.5, cos_cusp=float(np.cos(np.pi - np.pi / 3)))
 SIZES = ((1, 1), (3, 2), (2, 62), (2, 63), (2, 64), (3, 255), (1, 600))    # B x N of the device comparison
 PROPERTY_N = (1, 2, 5, 62, 63, 64, 255, 600)
+# (dim, N) of the longest path nfopp_path_time_profile serves: the largest m = N + 2 whose LDS image (lds_bytes below, the
+# `tp_lds_bytes` of csrc/time_profile.hip restated) fits 160 KiB -- 3032 at dim 3, 3275 at dim 2
+LONGEST = ((3, 3030), (2, 3273))
+LONGEST_B, LONGEST_SEED = 2, 77
+
+
+def lds_bytes(m, dim):
+    """TP_WAVES * 16 + m * 40 + ((m * dim * 4 + 7) & ~7) + ((2 * m + 15) & ~15) with TP_WAVES = 4."""
+    return 4 * 16 + m * 40 + ((m * dim * 4 + 7) & ~7) + ((2 * m + 15) & ~15)
 
 
 def straight(xs, dim=2):
