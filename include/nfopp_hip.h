@@ -770,6 +770,82 @@ int nfopp_lattice_trace_paths(const int32_t* fields_dev, int64_t field_first, in
                               int32_t* cells_dev, int32_t* headings_dev, int32_t* count_dev, int32_t* status_dev,
                               int32_t* cost_dev, void* stream);
 
+/* ---- lattice search with reverse moves and gear changes (csrc/lattice_gears.hip), additive under ABI 6 --------------------
+ * The search above over (cell, heading, gear) states, so that a seed may back out of a dead end or make a three-point turn,
+ * a trace that reports the gear of every move, and a seeding entry that takes the body heading from the lattice states
+ * (nfopp/lattice.py: lattice_gear_fields, lattice_gear_search_paths, seed_lattice_trajectories, lattice_gear_search_init,
+ * GearLattice).  The rule is this library's own; tests/lattice_gears_ref.py restates it in numpy and the device is compared
+ * with ==.  Directions, headings, occupancy layers and the pair order are those of the section above, unchanged.
+ *
+ * State: (cell c, heading h in 0 .. 7, gear s in {0 forward, 1 reverse}).  s is the gear of the move that entered the state.
+ *   Occupancy does not depend on s: state (c, h, s) reads layer h mod L, cells outside the image are blocked, no corner rule.
+ * Moves.  Forward, gear 0: from (c, h) to (c + dir(h'), h').  Reverse, gear 1: from (c, h) to (c - dir(h), h'): a forward move
+ *   run backwards in time, so the robot backs along the heading it had BEFORE the move.  In both h' in {h, h + 1, h - 1} mod
+ *   8, and the target state must be free.
+ * Cost: an integer pair (a, b), ordered exactly as a + b * sqrt 2.  A forward move adds (1, 0) for even h' and (0, 1) for odd
+ *   h'.  A reverse move adds (1, 0) for even h and (0, 1) for odd h: the parity of the direction it moves along.  Either adds
+ *   (turn_cost, 0) where h' != h.  A reverse move adds a further (reverse_cost, 0).  A move whose gear differs from s adds
+ *   (cusp_cost, 0).  All three costs are integers 0 .. 255.
+ * Goal: (goal cell, goal heading or -1 for every heading), at both gears.  Cost (0, 0), forced free.
+ * Field: d_g(s, h, c) = the minimum cost from the state to the goal, int32 [G, 2, 8, rows, cols, 2].  (-1, -1) marks blocked
+ *   states, states that cannot reach the goal, and every state of a goal whose cell is outside the grid or whose heading is
+ *   outside -1 .. 7.
+ * Trace: the start has no gear: its first move is charged no cusp cost.  The start state is NOT tested for occupancy.  A start
+ *   that is a goal state gives the one-state path with cost (0, 0).  Otherwise the first move is the one of the six successors
+ *   with the smallest d(successor) + move cost without the cusp term.  The order is forward h, h + 1, h - 1, then reverse h,
+ *   h + 1, h - 1; ties go to the first in that order; the path's cost is that sum; if no successor has a cost the status is 1.
+ *   After the first move the next state is the first successor in the same order whose cost plus the move (with the cusp
+ *   term) equals the current cost exactly.  The trace ends at the first state with cost (0, 0).  This one rule covers blocked
+ *   starts too.
+ * Status: 0 ok; 1 unreachable; 2 the start or goal cell is outside the grid, or the start heading is outside 0 .. 7.
+ * Refused before launch (argument error, nothing is clamped): a cost outside 0 .. 255, L not 1 or 8,
+ *   16 * rows * cols * (1 + turn_cost + reverse_cost + cusp_cost) >= 2^21 (the bound under which the float64 key orders pairs
+ *   exactly, on the largest count a path over 16 * rows * cols states can reach), a short or misaligned workspace, null
+ *   required pointers.
+ *
+ * nfopp_lattice_gear_distance_fields: goal_states_dev int32 [G, 3]; fields_dev int32 [G, 2, 8, rows, cols, 2] <- d_g, every
+ *   element written.  One workgroup per goal state.  While the padded 16-layer field fits 144 KiB of LDS and the count above
+ *   is <= 65535 the pairs are packed 16 + 16 bits in LDS; otherwise 32 + 32 bits in `workspace`
+ *   (nfopp_lattice_gear_fields_workspace_bytes, 0 for the LDS form and for a refused shape), 8-byte aligned, no initialisation
+ *   needed; of it only the queried number of bytes is written.  No atomics; the same bits run after run.
+ * nfopp_lattice_gear_trace_paths: one thread per problem; arguments as nfopp_lattice_trace_paths, every index tested before
+ *   anything is indexed by it, a problem whose field is not among the ones passed is not touched.  Writes count_dev [B],
+ *   status_dev [B], cost_dev [B, 2] (may be null) of every other problem; (-1, -1) and count 0 where status != 0.  Of
+ *   cells_dev [B, max_len, 2], headings_dev [B, max_len] and gears_dev [B, max_len] it writes the first min(count, max_len)
+ *   entries of a problem with status 0 and nothing else (max_len = 0 sizes the buffers; the three may then be null).
+ *   gears[k] is the gear of the move into state k; gears[0] is the gear of the first move, or 0 for a one-state path.
+ *   fields_dev is the caller's: on a field that is no fixed point of the rule a walk that finds no fitting successor, or
+ *   does not end within 16 * rows * cols moves, gives status 1 (entries of its row may then have been written).
+ * nfopp_lattice_seed_trajectories: SE(2) only, traj_dev fp32 [B, N, 3], every element written.  xy is bit for bit what
+ *   nfopp_grid_seed_trajectories writes for the same cells (one code path).  theta is the body heading of the lattice path,
+ *   unwound, interpolated over the parameter the spline already has.  With m = count + 2 knots in float64: A[0] = theta_start;
+ *   the first cell knot is a1 = theta_start + wrap(h_0 * (pi / 4) - theta_start); cell knot k is a1 + u_k * (pi / 4) with
+ *   u_0 = 0 and u_k = u_(k-1) + the signed heading step ((h_k - h_(k-1) + 4) mod 8) - 4, which is -1, 0 or +1 on a lattice
+ *   path; the goal knot is the last cell knot + wrap(theta_goal - it); wrap(x) = x - 2 pi * rint(x / (2 pi)).  Waypoint i has
+ *   q = (i + 1) * (1 / (N + 1)), the product the xy spline is evaluated at; k is the largest index in 0 .. m - 2 with
+ *   PAR_k <= q, PAR the spline's normalised chord-length parameter; theta = A_k + (A_(k+1) - A_k) * ((q - PAR_k) /
+ *   (PAR_(k+1) - PAR_k)), rounded to fp32.  Every operation is rounded on its own; no atan2, sin or cos.  A problem with
+ *   status != 0 or a count outside 1 .. max_len gets the trajectory of nfopp_init_trajectories with angles_with_direction = 0.
+ *   Workspace as nfopp_grid_seed_workspace_bytes (nfopp_lattice_seed_workspace_bytes returns the same number). */
+size_t nfopp_lattice_gear_fields_workspace_bytes(int32_t rows, int32_t cols, int32_t turn_cost, int32_t reverse_cost,
+                                                 int32_t cusp_cost, int64_t n_goals);
+int nfopp_lattice_gear_distance_fields(const uint8_t* layers_dev, int32_t n_layers, int32_t rows, int32_t cols,
+                                       const int32_t* goal_states_dev, int64_t n_goals, int32_t turn_cost, int32_t reverse_cost,
+                                       int32_t cusp_cost, int32_t* fields_dev, void* workspace_dev, size_t workspace_bytes,
+                                       void* stream);
+int nfopp_lattice_gear_trace_paths(const int32_t* fields_dev, int64_t field_first, int64_t n_fields, int64_t n_total,
+                                   int32_t rows, int32_t cols, int32_t turn_cost, int32_t reverse_cost, int32_t cusp_cost,
+                                   const int32_t* start_states_dev, const int32_t* goal_states_dev,
+                                   const int32_t* field_index_dev, int64_t batch, int32_t max_len, int32_t* cells_dev,
+                                   int32_t* headings_dev, int32_t* gears_dev, int32_t* count_dev, int32_t* status_dev,
+                                   int32_t* cost_dev, void* stream);
+size_t nfopp_lattice_seed_workspace_bytes(int64_t batch, int32_t max_len);
+int nfopp_lattice_seed_trajectories(const int32_t* cells_dev, const int32_t* headings_dev, const int32_t* count_dev,
+                                    const int32_t* status_dev, int64_t batch, int32_t max_len, const float* start_dev,
+                                    const float* goal_dev, int32_t n_waypoints, double origin_x, double origin_y,
+                                    double resolution, float* traj_dev, void* workspace_dev, size_t workspace_bytes,
+                                    void* stream);
+
 /* ---- time parametrisation under motion limits (csrc/time_profile.hip), additive under ABI 6 --------------------------------
  * Everything above is geometry; these two entries say WHEN the robot is where and how fast it may go, for a whole batch,
  * without a host round trip.  Float64 throughout, every operation rounded on its own; the two prefix sums are integers, so

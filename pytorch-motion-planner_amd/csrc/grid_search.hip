@@ -239,10 +239,12 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs a) {
 
 // ---- stage 3: polyline -> spline -> waypoints ------------------------------------------------------------------------
 constexpr int SD_THREADS = 256;
+constexpr double SD_PI = 3.141592653589793;
 
 struct SeedArgs {
   const int* cells; const int* count; const int* status;
   const float* points;      // [B, max_len, 2] fp32 xy: the interior of the polyline as given (cells is then null), else null
+  const int* headings = nullptr;   // [B, max_len] lattice headings of the cells: theta is then the body heading of the path
   int max_len, n, directed;
   const float* start; const float* goal;
   double ox, oy, res;
@@ -338,7 +340,41 @@ __device__ __forceinline__ void seed_body(const SeedArgs& a, double* W, long lon
     out[i * D + 0] = (float)p[0];
     out[i * D + 1] = (float)p[1];
   }
-  if (D == 3) {
+  if (D == 3 && a.headings) {
+    // The body heading of a lattice path (nfopp_lattice_seed_trajectories), unwound and interpolated over the spline's own
+    // parameter; float64, every operation rounded on its own, no atan2 / sin / cos.  Knots A[0 .. m - 1]: the start angle,
+    // the cells' headings as a1 + u_k * (pi / 4) with u the running sum of the signed heading steps, the goal angle; a1 and
+    // the goal knot are the nearest turn to the knot before them, wrap(x) = x - 2 pi * rint(x / 2 pi).
+    double* A = DD;   // the pivots are done with
+    if (threadIdx.x == 0) {
+      const int* heads = a.headings + b * (long long)a.max_len;
+      const double quarter = SD_PI / 4.0, two_pi = 2.0 * SD_PI;
+      const double ths = (double)s[2];
+      double x = (double)heads[0] * quarter - ths;
+      const double a1 = ths + (x - two_pi * rint(x / two_pi));
+      int u = 0;
+      A[0] = ths;
+      A[1] = a1 + (double)u * quarter;
+      for (int k = 1; k < cnt; ++k) {
+        u += ((heads[k] - heads[k - 1] + 4) & 7) - 4;   // -1, 0 or +1 between the states of a lattice path
+        A[k + 1] = a1 + (double)u * quarter;
+      }
+      x = (double)g[2] - A[cnt];
+      A[m - 1] = A[cnt] + (x - two_pi * rint(x / two_pi));
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int i = threadIdx.x; i < N; i += SD_THREADS) {
+      const double q = (double)(i + 1) * step;   // the parameter the xy spline is evaluated at
+      int lo = 0, hi = m - 2;                    // largest k in [0, m - 2] with PAR[k] <= q: PAR[k + 1] > q, as q < 1
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (PAR[mid] <= q) lo = mid; else hi = mid - 1;
+      }
+      const double w = (q - PAR[lo]) / (PAR[lo + 1] - PAR[lo]);
+      out[i * D + 2] = (float)(A[lo] + (A[lo + 1] - A[lo]) * w);
+    }
+  } else if (D == 3) {
     __threadfence_block();
     __syncthreads();
     // initialize_angle / initialize_angle_with_trajectory_direction (trajectory_initializer.py:23-45) on the seeded xy
@@ -491,4 +527,23 @@ extern "C" int nfopp_grid_seed_polylines(const float* points_dev, const int32_t*
   a.cells = nullptr; a.points = points_dev; a.ox = a.oy = 0.0; a.res = 1.0;   // the geometry is in the points already
   return seed_launch(a, count_dev, status_dev, batch, max_len, start_dev, goal_dev, n_waypoints, dim, angles_with_direction,
                      traj_dev, workspace_dev, workspace_bytes, stream);
+}
+
+// The seeding stage for lattice paths (lattice_search.hip, lattice_gears.hip): xy as nfopp_grid_seed_trajectories writes it for
+// the same cells, theta from the headings of the lattice states, so a reverse run keeps the body heading it is driven at.
+extern "C" size_t nfopp_lattice_seed_workspace_bytes(int64_t batch, int32_t max_len) {
+  return nfopp_grid_seed_workspace_bytes(batch, max_len);
+}
+
+extern "C" int nfopp_lattice_seed_trajectories(const int32_t* cells_dev, const int32_t* headings_dev, const int32_t* count_dev,
+                                               const int32_t* status_dev, int64_t batch, int32_t max_len, const float* start_dev,
+                                               const float* goal_dev, int32_t n_waypoints, double origin_x, double origin_y,
+                                               double resolution, float* traj_dev, void* workspace_dev, size_t workspace_bytes,
+                                               void* stream) {
+  NFOPP_REQUIRE(resolution > 0.0, "bad resolution");
+  NFOPP_REQUIRE(batch <= 0 || max_len <= 0 || (cells_dev && headings_dev), "null device pointer");
+  SeedArgs a;
+  a.cells = cells_dev; a.points = nullptr; a.headings = headings_dev; a.ox = origin_x; a.oy = origin_y; a.res = resolution;
+  return seed_launch(a, count_dev, status_dev, batch, max_len, start_dev, goal_dev, n_waypoints, 3, 0, traj_dev, workspace_dev,
+                     workspace_bytes, stream);
 }

@@ -609,6 +609,93 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> lattice_trace_paths(const Ten
   return std::make_tuple(cells, headings, count, status, cost);
 }
 
+static void check_gear_costs(int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost) {
+  TORCH_CHECK(turn_cost >= 0 && turn_cost <= 255, "nfopp: turn_cost must be 0..255");
+  TORCH_CHECK(reverse_cost >= 0 && reverse_cost <= 255, "nfopp: reverse_cost must be 0..255");
+  TORCH_CHECK(cusp_cost >= 0 && cusp_cost <= 255, "nfopp: cusp_cost must be 0..255");
+}
+
+// the lattice search over (cell, heading, gear) states (nfopp_lattice_gear_distance_fields): layers uint8 [L, rows, cols],
+// goal_states int32 [G, 3] (row, col, heading or -1) -> fields int32 [G, 2, 8, rows, cols, 2]
+Tensor lattice_gear_fields(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost) {
+  check_tensor(layers, "layers", at::kByte);
+  check_tensor(goal_states, "goal_states", at::kInt);
+  same_device(layers, goal_states, "goal_states");
+  TORCH_CHECK(layers.dim() == 3, "nfopp: layers must be [L, rows, cols] uint8");
+  TORCH_CHECK(goal_states.dim() == 2 && goal_states.size(1) == 3, "nfopp: goal_states must be [G, 3] (row, col, heading)");
+  check_gear_costs(turn_cost, reverse_cost, cusp_cost);
+  const int64_t L = layers.size(0), rows = layers.size(1), cols = layers.size(2), G = goal_states.size(0);
+  TORCH_CHECK(rows >= 1 && cols >= 1 && rows <= 32768 && cols <= 32768, "nfopp: grid must be 1..32768 cells a side");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(layers.device());
+  Tensor fields = at::empty({G, 2, 8, rows, cols, 2}, layers.options().dtype(at::kInt));
+  const size_t bytes = nfopp_lattice_gear_fields_workspace_bytes((int32_t)rows, (int32_t)cols, (int32_t)turn_cost,
+                                                                 (int32_t)reverse_cost, (int32_t)cusp_cost, G);
+  Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, layers.options().dtype(at::kLong));
+  check_status(nfopp_lattice_gear_distance_fields(layers.data_ptr<uint8_t>(), (int32_t)L, (int32_t)rows, (int32_t)cols,
+                                                  G ? goal_states.data_ptr<int32_t>() : nullptr, G, (int32_t)turn_cost,
+                                                  (int32_t)reverse_cost, (int32_t)cusp_cost, G ? fields.data_ptr<int32_t>() : nullptr,
+                                                  bytes ? work.data_ptr() : nullptr, bytes, stream_of(layers)));
+  return fields;
+}
+
+// the descent (nfopp_lattice_gear_trace_paths) through fields [n_fields, 2, 8, rows, cols, 2] = the fields field_first .. of
+// n_total -> (cells [B, max_len, 2], headings [B, max_len], gears [B, max_len], count [B], status [B], cost [B, 2]) int32.
+// Outputs start as zeros, so a problem of another chunk reads count 0, status 0.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> lattice_gear_trace_paths(
+    const Tensor& fields, int64_t field_first, int64_t n_total, const Tensor& start_states, const Tensor& goal_states,
+    const Tensor& field_index, int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost, int64_t max_len) {
+  check_tensor(fields, "fields", at::kInt);
+  TORCH_CHECK(fields.dim() == 6 && fields.size(1) == 2 && fields.size(2) == 8 && fields.size(5) == 2,
+              "nfopp: fields must be [G, 2, 8, rows, cols, 2]");
+  check_tensor(start_states, "start_states", at::kInt);
+  TORCH_CHECK(start_states.dim() == 2 && start_states.size(1) == 3, "nfopp: start_states must be [B, 3] (row, col, heading)");
+  same_device(fields, start_states, "start_states");
+  const int64_t B = start_states.size(0), G = fields.size(0), rows = fields.size(3), cols = fields.size(4);
+  need(fields, goal_states, "goal_states", {B, 3}, at::kInt);
+  need(fields, field_index, "field_index", {B}, at::kInt);
+  TORCH_CHECK(max_len >= 0 && max_len <= std::numeric_limits<int32_t>::max(), "nfopp: bad max_len");
+  check_gear_costs(turn_cost, reverse_cost, cusp_cost);
+  TORCH_CHECK(rows >= 1 && cols >= 1, "nfopp: fields of an empty grid");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(fields.device());
+  const auto i32 = fields.options().dtype(at::kInt);
+  Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32), gears = at::zeros({B, max_len}, i32);
+  Tensor count = at::zeros({B}, i32), status = at::zeros({B}, i32), cost = at::zeros({B, 2}, i32);
+  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
+  check_status(nfopp_lattice_gear_trace_paths(i32p(fields), field_first, G, n_total, (int32_t)rows, (int32_t)cols, (int32_t)turn_cost,
+                                              (int32_t)reverse_cost, (int32_t)cusp_cost, i32p(start_states), i32p(goal_states),
+                                              i32p(field_index), B, (int32_t)max_len, i32p(cells), i32p(headings), i32p(gears),
+                                              i32p(count), i32p(status), i32p(cost), stream_of(fields)));
+  return std::make_tuple(cells, headings, gears, count, status, cost);
+}
+
+// nfopp_lattice_seed_trajectories: cells int32 [B, max_len, 2], headings int32 [B, max_len], count / status int32 [B], start /
+// goal fp32 [B, 3] -> traj fp32 [B, n_waypoints, 3]
+Tensor lattice_seed_trajectories(const Tensor& cells, const Tensor& headings, const Tensor& count, const Tensor& status,
+                                 const Tensor& start, const Tensor& goal, int64_t n_waypoints, double origin_x, double origin_y,
+                                 double resolution) {
+  check_tensor(cells, "cells", at::kInt);
+  TORCH_CHECK(cells.dim() == 3 && cells.size(2) == 2, "nfopp: cells must be [B, max_len, 2] (row, col)");
+  const int64_t B = cells.size(0), max_len = cells.size(1);
+  need(cells, headings, "headings", {B, max_len}, at::kInt);
+  need(cells, count, "count", {B}, at::kInt);
+  need(cells, status, "status", {B}, at::kInt);
+  need(cells, start, "start", {B, 3}, at::kFloat);
+  need(cells, goal, "goal", {B, 3}, at::kFloat);
+  TORCH_CHECK(n_waypoints >= 1 && n_waypoints <= std::numeric_limits<int32_t>::max(), "nfopp: bad n_waypoints");
+  TORCH_CHECK(resolution > 0.0, "nfopp: bad resolution");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(cells.device());
+  Tensor traj = at::empty({B, n_waypoints, 3}, cells.options().dtype(at::kFloat));
+  const size_t bytes = nfopp_lattice_seed_workspace_bytes(B, (int32_t)max_len);
+  Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, cells.options().dtype(at::kLong));
+  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
+  check_status(nfopp_lattice_seed_trajectories(i32p(cells), i32p(headings), i32p(count), i32p(status), B, (int32_t)max_len,
+                                               B ? start.data_ptr<float>() : nullptr, B ? goal.data_ptr<float>() : nullptr,
+                                               (int32_t)n_waypoints, origin_x, origin_y, resolution,
+                                               B ? traj.data_ptr<float>() : nullptr, bytes ? work.data_ptr() : nullptr, bytes,
+                                               stream_of(cells)));
+  return traj;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nfopp, lib) {
@@ -654,6 +741,12 @@ TORCH_LIBRARY(nfopp, lib) {
   lib.def("lattice_fields(Tensor layers, Tensor goal_states, int turn_cost) -> Tensor");
   lib.def("lattice_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
           "Tensor field_index, int turn_cost, int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  lib.def("lattice_gear_fields(Tensor layers, Tensor goal_states, int turn_cost, int reverse_cost, int cusp_cost) -> Tensor");
+  lib.def("lattice_gear_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
+          "Tensor field_index, int turn_cost, int reverse_cost, int cusp_cost, int max_len) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  lib.def("lattice_seed_trajectories(Tensor cells, Tensor headings, Tensor count, Tensor status, Tensor start, Tensor goal, "
+          "int n_waypoints, float origin_x, float origin_y, float resolution) -> Tensor");
 }
 
 // The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
@@ -678,4 +771,7 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("spacetime_plan_fleet", &spacetime_plan_fleet);
   lib.impl("lattice_fields", &lattice_fields);
   lib.impl("lattice_trace_paths", &lattice_trace_paths);
+  lib.impl("lattice_gear_fields", &lattice_gear_fields);
+  lib.impl("lattice_gear_trace_paths", &lattice_gear_trace_paths);
+  lib.impl("lattice_seed_trajectories", &lattice_seed_trajectories);
 }

@@ -18,7 +18,8 @@ from .grid_search import (AstarTrajectoryInitializer, OccupancyGrid, distance_fi
 from .host_utils import (AttributeDict, CircleCollisionChecker,
                          CircleDirectedCollisionChecker, CollisionChecker, Position2, RectangleCollisionChecker,
                          TrajectoryInitializer)
-from .lattice import LatticeGrid, heading_index, lattice_fields, lattice_search_init, lattice_search_paths
+from .lattice import (GearLattice, LatticeGrid, heading_index, lattice_fields, lattice_gear_fields, lattice_gear_search_init,
+                      lattice_gear_search_paths, lattice_search_init, lattice_search_paths, seed_lattice_trajectories)
 from .learning import BatchSampler, DeviceCircleChecker, DeviceGridChecker, DeviceGridMap, DeviceRectangleChecker
 from .onf_model import ONF
 from .path_tools import PathPostprocessor, init_trajectories
@@ -51,4 +52,5 @@ __all__ = [
     "SpaceTimePlan", "SpaceTimeReservation", "spacetime_plan", "SPACETIME_OK", "SPACETIME_BAD_CELL", "SPACETIME_UNREACHED",
     "SPACETIME_NOT_ORDERED", "SPACETIME_DIRECTIONS",
     "LatticeGrid", "heading_index", "lattice_fields", "lattice_search_paths", "lattice_search_init",
+    "GearLattice", "lattice_gear_fields", "lattice_gear_search_paths", "lattice_gear_search_init", "seed_lattice_trajectories",
 ]

@@ -145,6 +145,18 @@ _SIGNATURES = {
     "nfopp_lattice_trace_paths": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                                  ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64, ctypes.c_int32,
                                                  _P, _P, _P, _P, _P, _P]),
+    "nfopp_lattice_gear_fields_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                                    ctypes.c_int32, ctypes.c_int64]),
+    "nfopp_lattice_gear_distance_fields": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64,
+                                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_size_t,
+                                                          _P]),
+    "nfopp_lattice_gear_trace_paths": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                                      ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "nfopp_lattice_seed_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32]),
+    "nfopp_lattice_seed_trajectories": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int32,
+                                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P,
+                                                       ctypes.c_size_t, _P]),
     "nfopp_grid_to_points": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_int32, _P, _P, _P, _P]),

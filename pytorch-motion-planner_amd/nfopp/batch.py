@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .engine import TrajectoryEngine
 from .grid_search import AstarTrajectoryInitializer, OccupancyGrid, grid_search_init
-from .lattice import LatticeGrid, lattice_search_init
+from .lattice import GearLattice, LatticeGrid, lattice_gear_search_init, lattice_search_init
 from .path_tools import init_trajectories
 
 
@@ -165,6 +165,7 @@ class BatchPlanner(object):
             self.fitter = OnfFitter(onf, fit_lr, fit_betas, group=group)
 
     seed_status = None   # per-problem status of the last grid-search seeding (nfopp/grid_search.py), else None
+    seed_gear_changes = None   # gear changes of each problem's seed after a GearLattice initializer, else None
     seed_margin = None   # the clearance margin each problem was seeded at (all zero without one); None without grid seeding
 
     def init(self, starts, goals, boundaries, trajectories=None, initializer=None, seed_clearance=None, seed_any_angle=False,
@@ -172,12 +173,14 @@ class BatchPlanner(object):
         """`seed_clearance` / `seed_any_angle`: grid_search_init's `clearance` / `any_angle` for an OccupancyGrid initializer
         (an AstarTrajectoryInitializer carries its own).  A LatticeGrid initializer seeds SE(2) batches through
         lattice_search_init with `seed_turn_cost`; it takes neither of the two: shortening by line of sight would undo the
-        heading constraint, and a margin is built into the lattice (LatticeGrid.from_grid(grid.inflated(m)))."""
+        heading constraint, and a margin is built into the lattice (LatticeGrid.from_grid(grid.inflated(m))).  A GearLattice
+        initializer does the same through lattice_gear_search_init, with reverse moves at its costs, and sets
+        `seed_gear_changes`."""
         eng = self.engine
         eng.set_endpoints(starts, goals)
         eng.hyper = eng.hyper.replace(bounds=boundaries)
-        self.seed_status = self.seed_margin = None
-        if isinstance(initializer, LatticeGrid):
+        self.seed_status = self.seed_margin = self.seed_gear_changes = None
+        if isinstance(initializer, (LatticeGrid, GearLattice)):
             if seed_clearance is not None or seed_any_angle:
                 raise ValueError("seed_clearance / seed_any_angle do not go with a LatticeGrid: build it from grid.inflated(m)")
             if eng.D != 3:
@@ -200,11 +203,15 @@ class BatchPlanner(object):
                 _, self.seed_status = lattice_search_init(initializer, eng.start, eng.goal, eng.N,
                                                           self.init_angles_with_trajectory, out=eng.traj,
                                                           turn_cost=seed_turn_cost)
+            elif isinstance(initializer, GearLattice):
+                _, self.seed_status, self.seed_gear_changes = lattice_gear_search_init(
+                    initializer.lgrid, eng.start, eng.goal, eng.N, out=eng.traj, turn_cost=seed_turn_cost,
+                    reverse_cost=initializer.reverse_cost, cusp_cost=initializer.cusp_cost)
             elif isinstance(initializer, AstarTrajectoryInitializer):
                 initializer.initialize_batch(eng.start, eng.goal, eng.N, out=eng.traj, boundaries=boundaries)
                 self.seed_status, self.seed_margin = initializer.status, initializer.seed_margin
             else:
-                raise TypeError("initializer must be an OccupancyGrid, a LatticeGrid or an AstarTrajectoryInitializer")
+                raise TypeError("initializer must be an OccupancyGrid, a LatticeGrid, a GearLattice or an AstarTrajectoryInitializer")
         elif trajectories is None:
             # device initialiser (trajectory_initializer.py:12-45); eng.start / eng.goal were uploaded just above
             init_trajectories(eng.start, eng.goal, eng.N, self.init_angles_with_trajectory and eng.D == 3, out=eng.traj)

@@ -4,13 +4,18 @@ The state of the search is (cell, heading), heading h in 0 .. 7 standing for h *
 heading the robot has after the move, which differs from the one before by at most one step.  A seed therefore leaves the
 start along the start heading and reaches the goal along the goal heading, and with eight occupancy layers
 (`LatticeGrid.from_checker`) it threads only the gaps the robot fits through at the heading it has there.  The traced cells
-go through the seeding stage of the 8-connected search (`seed_trajectories`) unchanged."""
+go through the seeding stage of the 8-connected search (`seed_trajectories`) unchanged.
+
+The `lattice_gear_*` functions (csrc/lattice_gears.hip) search (cell, heading, gear) states: a reverse move backs along the
+heading the robot had before it, `reverse_cost` is charged per reverse move and `cusp_cost` per gear change.  Their seeds go
+through `seed_lattice_trajectories`, which takes theta from the headings of the lattice states, so a reverse run keeps the
+body heading it is driven at."""
 
 import numpy as np
 import torch
 
 from . import _lib
-from .grid_search import OccupancyGrid, _as_device_points, _cell_centres, seed_trajectories
+from .grid_search import OccupancyGrid, _as_device_points, _cell_centres, _seed_out, seed_trajectories
 
 HEADINGS = 8
 GOAL_HEADING_MODES = ("fixed", "free")
@@ -116,10 +121,21 @@ class LatticeGrid(object):
         return torch.cat([cells, h[:, None]], 1).contiguous()
 
 
-def _turn_cost(turn_cost):
-    if int(turn_cost) != turn_cost or not 0 <= int(turn_cost) <= 255:
-        raise ValueError("turn_cost must be an integer 0 .. 255")
-    return int(turn_cost)
+def _cost(value, name="turn_cost"):
+    if int(value) != value or not 0 <= int(value) <= 255:
+        raise ValueError("%s must be an integer 0 .. 255" % name)
+    return int(value)
+
+
+def _gear_costs(turn_cost, reverse_cost, cusp_cost):
+    return _cost(turn_cost), _cost(reverse_cost, "reverse_cost"), _cost(cusp_cost, "cusp_cost")
+
+
+def _check_gear_bound(lgrid, costs):
+    rows, cols = lgrid.shape
+    if 2 * HEADINGS * rows * cols * (1 + sum(costs)) >= 2 ** 21:
+        raise ValueError("16 * rows * cols * (1 + turn_cost + reverse_cost + cusp_cost) must stay below 2^21 (%d x %d, costs %s)"
+                         % (rows, cols, costs))
 
 
 def _check_bound(lgrid, turn_cost):
@@ -132,7 +148,7 @@ def lattice_fields(lgrid, goal_states, turn_cost=0):
     """goal_states int32 [G, 3] (row, col, heading or -1) on the device -> int32 [G, 8, rows, cols, 2]: the exact cost (a, b)
     from every state to the goal state; (-1, -1) = blocked or unreachable."""
     lib = _lib.load()
-    turn_cost = _turn_cost(turn_cost)
+    turn_cost = _cost(turn_cost)
     _check_bound(lgrid, turn_cost)
     layers = lgrid.layers
     rows, cols = lgrid.shape
@@ -150,15 +166,46 @@ def lattice_fields(lgrid, goal_states, turn_cost=0):
     return fields
 
 
-def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes):
-    """-> (cells, headings, count, status, cost, starts, goals), all on the device."""
+def lattice_gear_fields(lgrid, goal_states, turn_cost=0, reverse_cost=0, cusp_cost=0):
+    """goal_states int32 [G, 3] (row, col, heading or -1) on the device -> int32 [G, 2, 8, rows, cols, 2]: the exact cost (a, b)
+    from every state (gear, heading, cell) to the goal state with reverse moves allowed; (-1, -1) = blocked or unreachable."""
+    lib = _lib.load()
+    costs = _gear_costs(turn_cost, reverse_cost, cusp_cost)
+    _check_gear_bound(lgrid, costs)
+    layers = lgrid.layers
+    rows, cols = lgrid.shape
+    goal_states = torch.as_tensor(goal_states, device=layers.device).to(torch.int32).contiguous()
+    if goal_states.dim() != 2 or goal_states.shape[1] != 3:
+        raise ValueError("goal_states must be [G, 3] (row, col, heading)")
+    g = goal_states.shape[0]
+    fields = torch.empty(g, 2, HEADINGS, rows, cols, 2, dtype=torch.int32, device=layers.device)
+    ws_bytes = lib.nfopp_lattice_gear_fields_workspace_bytes(rows, cols, costs[0], costs[1], costs[2], g)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=layers.device) if ws_bytes else None
+    _lib.check(lib.nfopp_lattice_gear_distance_fields(
+        _lib.ptr(layers, torch.uint8), lgrid.n_layers, rows, cols, _lib.ptr(goal_states, torch.int32), g, costs[0], costs[1],
+        costs[2], _lib.ptr(fields, torch.int32), _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
+        _lib.stream_ptr()))
+    return fields
+
+
+def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes, gear_costs=None):
+    """-> (cells, headings, count, status, cost, starts, goals), all on the device; with `gear_costs` = (reverse_cost,
+    cusp_cost) the search over (cell, heading, gear) states, and `gears` [B, max_len] behind the seven."""
     lib = _lib.load()
     if not isinstance(lgrid, LatticeGrid):
         raise TypeError("the lattice search needs a LatticeGrid")
     if goal_heading not in GOAL_HEADING_MODES:
         raise ValueError("goal_heading must be 'fixed' or 'free'")
-    turn_cost = _turn_cost(turn_cost)
-    _check_bound(lgrid, turn_cost)
+    # the two searches differ in their costs, their field and trace entries, and the gear layer of the field; nothing below
+    # this block asks which one runs
+    if gear_costs is None:
+        costs = (_cost(turn_cost),)
+        _check_bound(lgrid, costs[0])
+        fields_fn, trace_entry, gear_layers = lattice_fields, lib.nfopp_lattice_trace_paths, 1
+    else:
+        costs = _gear_costs(turn_cost, *gear_costs)
+        _check_gear_bound(lgrid, costs)
+        fields_fn, trace_entry, gear_layers = lattice_gear_fields, lib.nfopp_lattice_gear_trace_paths, 2
     starts, goals = _as_device_points(lgrid, starts), _as_device_points(lgrid, goals)
     if starts.shape != goals.shape or starts.shape[1] != 3:
         raise ValueError("starts and goals must both be [B, 3] poses (x, y, theta)")
@@ -179,38 +226,44 @@ def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes):
     cell = uniq // (HEADINGS + 1)
     unique_states = torch.stack([cell // cols, cell % cols, uniq % (HEADINGS + 1) - 1], 1).to(i32).contiguous()
     n_total = unique_states.shape[0]
-    per_field = HEADINGS * rows * cols * 8
+    per_field = gear_layers * HEADINGS * rows * cols * 8
     chunk = max(1, int(max_field_bytes) // per_field)
     count = torch.zeros(b, dtype=i32, device=dev)
     status = torch.zeros(b, dtype=i32, device=dev)
     cost = torch.zeros(b, 2, dtype=i32, device=dev)
     cells = torch.zeros(b, 1, 2, dtype=i32, device=dev)
     headings = torch.zeros(b, 1, dtype=i32, device=dev)
+    gears = torch.zeros(b, 1, dtype=i32, device=dev)
 
     def trace(fields, first, max_len):
         n = 0 if fields is None else fields.shape[0]
-        _lib.check(lib.nfopp_lattice_trace_paths(
-            _lib.ptr(fields, i32) if n else None, first, n, n_total, rows, cols, turn_cost, _lib.ptr(start_states, i32),
-            _lib.ptr(goal_states, i32), _lib.ptr(field_index, i32), b, max_len, _lib.ptr(cells, i32) if max_len else None,
-            _lib.ptr(headings, i32) if max_len else None, _lib.ptr(count, i32), _lib.ptr(status, i32), _lib.ptr(cost, i32),
-            _lib.stream_ptr()))
+        paths = [cells, headings] + ([gears] if gear_layers == 2 else [])   # the gear trace writes `gears` behind the headings
+        _lib.check(trace_entry(
+            _lib.ptr(fields, i32) if n else None, first, n, n_total, rows, cols, *costs, _lib.ptr(start_states, i32),
+            _lib.ptr(goal_states, i32), _lib.ptr(field_index, i32), b, max_len,
+            *[_lib.ptr(t, i32) if max_len else None for t in paths], _lib.ptr(count, i32), _lib.ptr(status, i32),
+            _lib.ptr(cost, i32), _lib.stream_ptr()))
+
+    def result():
+        return (cells, headings, count, status, cost, starts, goals) + ((gears,) if gear_layers == 2 else ())
 
     if b == 0:
-        return cells, headings, count, status, cost, starts, goals
+        return result()
     if n_total == 0:
         trace(None, 0, 0)   # every goal is outside the grid: status 2 throughout
     # one sizing pass and one count.max() per chunk of fields: a single chunk (the usual case) costs the one read-back of the
     # 8-connected search; counts of earlier chunks stay in `count`, so the maximum never falls
     for first in range(0, n_total, chunk):
-        fields = lattice_fields(lgrid, unique_states[first:first + chunk], turn_cost)
+        fields = fields_fn(lgrid, unique_states[first:first + chunk], *costs)
         trace(fields, first, 0)
         max_len = max(int(count.max()), 1)
         if max_len > cells.shape[1]:
             grow = max_len - cells.shape[1]
             cells = torch.nn.functional.pad(cells, (0, 0, 0, grow)).contiguous()
             headings = torch.nn.functional.pad(headings, (0, grow)).contiguous()
+            gears = torch.nn.functional.pad(gears, (0, grow)).contiguous()
         trace(fields, first, cells.shape[1])
-    return cells, headings, count, status, cost, starts, goals
+    return result()
 
 
 def lattice_search_paths(lgrid, starts, goals, turn_cost=0, goal_heading="fixed", max_field_bytes=2 ** 30):
@@ -229,3 +282,73 @@ def lattice_search_init(lgrid, starts, goals, n_waypoints, init_angles_with_traj
     cells, _, count, status, _, starts, goals = _search(lgrid, starts, goals, turn_cost, goal_heading, 2 ** 30)
     traj = seed_trajectories(lgrid, cells, count, status, starts, goals, n_waypoints, init_angles_with_trajectory, out)
     return traj, status
+
+
+def lattice_gear_search_paths(lgrid, starts, goals, turn_cost=0, reverse_cost=0, cusp_cost=0, goal_heading="fixed",
+                              max_field_bytes=2 ** 30):
+    """lattice_search_paths with reverse moves: -> (cells int32 [B, max_len, 2], headings int32 [B, max_len], gears int32
+    [B, max_len], counts [B], status [B], costs [B, 2]) on the device.  gears[k] is the gear (0 forward, 1 reverse) of the move
+    into state k, gears[0] the gear of the first move.  `reverse_cost` is charged per reverse move, `cusp_cost` per change of
+    gear after the first move.  Goal states are shared and chunked as in lattice_search_paths."""
+    cells, headings, count, status, cost, _, _, gears = _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes,
+                                                                (reverse_cost, cusp_cost))
+    return cells, headings, gears, count, status, cost
+
+
+def seed_lattice_trajectories(lgrid, cells, headings, count, status, starts, goals, n_waypoints, out=None):
+    """Lattice paths -> [B, N, 3] fp32 trajectories (nfopp_lattice_seed_trajectories): xy as `seed_trajectories` gives for the
+    same cells, theta the body heading of the lattice states, unwound and interpolated over the spline's parameter.  A
+    problem with status != 0 gets the straight line of `init_trajectories(..., False)`."""
+    lib = _lib.load()
+    starts, goals = _as_device_points(lgrid, starts), _as_device_points(lgrid, goals)
+    if starts.shape != goals.shape or starts.shape[1] != 3:
+        raise ValueError("starts and goals must both be [B, 3] poses (x, y, theta)")
+    b = starts.shape[0]
+    dev = starts.device
+    i32 = torch.int32
+    cells = torch.as_tensor(cells, dtype=i32, device=dev).contiguous()
+    headings = torch.as_tensor(headings, dtype=i32, device=dev).contiguous()
+    count = torch.as_tensor(count, dtype=i32, device=dev).contiguous()
+    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
+    if cells.dim() != 3 or cells.shape[0] != b or cells.shape[2] != 2 or headings.shape != cells.shape[:2] or \
+            count.shape != (b,) or status.shape != (b,):
+        raise ValueError("cells [B, max_len, 2], headings [B, max_len], count [B] and status [B] must agree with the poses")
+    max_len = cells.shape[1]
+    out = _seed_out(b, n_waypoints, 3, dev, out)
+    ws_bytes = lib.nfopp_lattice_seed_workspace_bytes(b, max_len)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+    bd = lgrid.boundaries
+    _lib.check(lib.nfopp_lattice_seed_trajectories(
+        _lib.ptr(cells, i32), _lib.ptr(headings, i32), _lib.ptr(count, i32), _lib.ptr(status, i32), b, max_len, _lib.ptr(starts),
+        _lib.ptr(goals), int(n_waypoints), bd[0], bd[2], lgrid.resolution, _lib.ptr(out),
+        _lib.ptr(ws, torch.float64) if ws is not None else None, ws_bytes, _lib.stream_ptr()))
+    return out.view(b, int(n_waypoints), 3)
+
+
+def gear_changes(gears, count, status):
+    """int32 [B] on the device: the moves of each traced path whose gear differs from the one before (0 where status != 0)."""
+    k = torch.arange(gears.shape[1], device=gears.device)[None, :]
+    differ = (gears[:, 1:] != gears[:, :-1]) & (k[:, 1:] >= 2) & (k[:, 1:] < count[:, None]) & (status[:, None] == 0)
+    return differ.sum(1).to(torch.int32)
+
+
+def lattice_gear_search_init(lgrid, starts, goals, n_waypoints, out=None, turn_cost=0, reverse_cost=0, cusp_cost=0,
+                             goal_heading="fixed"):
+    """-> (traj [B, N, 3] fp32, status [B] int32, gear_changes [B] int32) on the device: the minimum-cost path over forward
+    and reverse moves through seed_lattice_trajectories.  status as lattice_search_init; gear_changes counts the cusps of the
+    seed (0 where status != 0)."""
+    cells, headings, count, status, _, starts, goals, gears = _search(lgrid, starts, goals, turn_cost, goal_heading, 2 ** 30,
+                                                                      (reverse_cost, cusp_cost))
+    traj = seed_lattice_trajectories(lgrid, cells, headings, count, status, starts, goals, n_waypoints, out)
+    return traj, status, gear_changes(gears, count, status)
+
+
+class GearLattice(object):
+    """Initializer for BatchPlanner.init: a LatticeGrid searched with reverse moves at the given costs."""
+
+    def __init__(self, lgrid, reverse_cost=0, cusp_cost=0):
+        if not isinstance(lgrid, LatticeGrid):
+            raise TypeError("GearLattice needs a LatticeGrid")
+        self.lgrid = lgrid
+        self.reverse_cost = _cost(reverse_cost, "reverse_cost")
+        self.cusp_cost = _cost(cusp_cost, "cusp_cost")

@@ -6,9 +6,11 @@ The same 256 problems (bench.py's generator, the same random stream) are planned
 frozen pre-fitted field.  Per row: the collision-free share at the seed and after the steps (BatchPlanner.evaluate), the
 cusps per path at the seed and after the steps (BatchPlanner.path_stats), and the angle between the start heading and the
 seed's first segment (start -> first waypoint), and the same angle to the first waypoint two cells away, mean and 90th
-percentile in degrees.  Information, not a gate.
+percentile in degrees.  With --gears the lattice search with reverse moves (nfopp.GearLattice) adds a row per gear setting,
+with the gear changes and reversals of its seeds and how many of the problems the forward-only lattice leaves unseeded
+(status 1) it seeds.  Information, not a gate.
 
-Usage:  python tools/lattice_seed_quality.py [--problems 256] [--steps 500] [--out profiles/lattice_search.txt]
+Usage:  python tools/lattice_seed_quality.py [--problems 256] [--steps 500] [--gears] [--out profiles/lattice_search.txt]
 """
 import argparse
 import json
@@ -48,6 +50,7 @@ def main():
     ap.add_argument("--problems", type=int, default=256)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--fit-iters", type=int, default=300)
+    ap.add_argument("--gears", action="store_true", help="add the rows of the search with reverse moves")
     ap.add_argument("--out", default=None, help="append the result line to this file as well")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
@@ -63,16 +66,22 @@ def main():
     N, B = 256, args.problems
     result = {"map": env.name, "problems": B, "steps": args.steps, "waypoints": N, "onf_fit_loss": fit_loss}
     rows = [("straight_line", None, 0), ("grid_search", grid, 0), ("lattice_turn_cost_0", lgrid, 0), ("lattice_turn_cost_2", lgrid, 2)]
+    if args.gears:   # (turn, reverse, cusp)
+        rows += [("lattice_gears_%d_%d_%d" % (tc, rc, cc), nfopp.GearLattice(lgrid, rc, cc), tc)
+                 for tc, rc, cc in ((0, 0, 0), (0, 1, 3), (2, 1, 3), (2, 2, 6))]   # 16 * 100 * 100 * (1 + costs) < 2^21: a cost sum of at most 12
+    unseeded = None
     for name, ini, tc in rows:
         planner = nfopp.BatchPlanner(onf, B, N, bench.bench_hyper(), velocity_hessian_weight=0.5, device=device, seed=bench.SEED)
         planner.init(starts[:B], goals[:B], bench.BOUNDS, initializer=ini, seed_turn_cost=tc)
         angle, angle_far = departure_angles(planner)
         collides0, _ = planner.evaluate(truth)
         free0 = 1.0 - float(collides0.float().mean())      # read now: evaluate() returns the planner's own buffer
-        cusps0 = planner.path_stats()[:, nfopp.PATH_STAT_CUSPS]
+        stats0 = planner.path_stats().clone()
+        cusps0 = stats0[:, nfopp.PATH_STAT_CUSPS]
         planner.step(n=args.steps)
         collides, length = planner.evaluate(truth)
-        cusps = planner.path_stats()[:, nfopp.PATH_STAT_CUSPS]
+        stats = planner.path_stats()
+        cusps = stats[:, nfopp.PATH_STAT_CUSPS]
         free = collides == 0
         result[name] = {"collision_free_at_seed": free0,
                         "collision_free_after_steps": float(free.float().mean()),
@@ -82,6 +91,16 @@ def main():
                         "mean_length_of_free_paths": float(length[free].mean()) if bool(free.any()) else None}
         if ini is not None:
             result[name]["seed_status_counts"] = np.bincount(planner.seed_status.cpu().numpy(), minlength=3).tolist()
+        if name == "lattice_turn_cost_0":
+            unseeded = planner.seed_status == 1
+        if isinstance(ini, nfopp.GearLattice):
+            ok = planner.seed_status == 0
+            result[name].update(
+                gear_changes_per_seeded_path=float(planner.seed_gear_changes[ok].float().mean()),
+                seeds_with_a_gear_change=int((planner.seed_gear_changes[ok] > 0).sum()),
+                reversals_per_path_at_seed=float(stats0[:, nfopp.PATH_STAT_REVERSALS].mean()),
+                reversals_per_path_after_steps=float(stats[:, nfopp.PATH_STAT_REVERSALS].mean()),
+                seeded_of_the_forward_lattice_unreachable="%d of %d" % (int((ok & unseeded).sum()), int(unseeded.sum())))
     line = json.dumps(result)
     print(line)
     if args.out:
