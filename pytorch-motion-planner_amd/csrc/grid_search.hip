@@ -16,6 +16,7 @@
 // additions made on it inside one sweep) stays below 3e-9, so the order of DIFFERENT pairs is exact; whether a cell
 // changed is decided on the integer pair itself.
 #include "common.h"
+#include "lattice_field.h"
 #include "pair_cost.h"
 #include "spline2.h"
 #include "traj_init.h"
@@ -55,15 +56,8 @@ __device__ __forceinline__ void field_body(const FieldArgs& a, T* F, int g) {
   const int rows = a.rows, cols = a.cols, stride = a.stride;
   const int gr = a.goals[2 * g], gc = a.goals[2 * g + 1];
   const bool goal_ok = gr >= 0 && gr < rows && gc >= 0 && gc < cols;
-  for (long long k = threadIdx.x; k < a.padded; k += GS_THREADS) {
-    const int r = (int)(k / stride) - 1, c = (int)(k % stride) - 1;
-    T v = P::WALL;
-    if (r >= 0 && r < rows && c >= 0 && c < cols) {
-      if (a.occ[(long long)r * cols + c] == 0) v = P::UNREACHED;
-      if (r == gr && c == gc) v = 0;   // the goal cell is forced free (astar_trajectory_initializer.py:40)
-    }
-    F[k] = v;
-  }
+  // the padded field of lattice_field.h, one layer; the goal cell is forced free (astar_trajectory_initializer.py:40)
+  lattice_fill_layer<T, GS_THREADS>(F, a.occ, rows, cols, stride, a.padded, gr, gc, true);
   if (sizeof(T) == 8) __threadfence();
   __syncthreads();
   const int runs_per_row = a.cols_p / GS_RUN;
@@ -131,14 +125,8 @@ __device__ __forceinline__ void field_body(const FieldArgs& a, T* F, int g) {
     if (sizeof(T) == 8) __threadfence();   // wide path: the field lives in global memory, the next sweep must not read stale lines
     if (!__syncthreads_or(changed)) break;
   }
-  int* out = a.out + (long long)g * rows * cols * 2;
-  for (long long k = threadIdx.x; k < (long long)rows * cols; k += GS_THREADS) {
-    const int r = (int)(k / cols), c = (int)(k % cols);
-    const T v = F[(long long)(r + 1) * stride + c + 1];
-    int2 pr;
-    if (v >= P::WALL) { pr.x = -1; pr.y = -1; } else { pr.x = P::a(v); pr.y = P::b(v); }
-    reinterpret_cast<int2*>(out)[k] = pr;
-  }
+  lattice_store_layer<T, GS_THREADS>(F, 0, reinterpret_cast<int2*>(a.out + (long long)g * rows * cols * 2), 0, (long long)rows * cols, cols,
+                                     stride);
 }
 
 __global__ __launch_bounds__(GS_THREADS) void field_lds_kernel(const FieldArgs a) {

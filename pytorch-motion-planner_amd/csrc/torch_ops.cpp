@@ -559,113 +559,104 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> spacetime_plan_fleet(const Tensor& oc
   return std::make_tuple(cells, arrival, status, tracks);
 }
 
-// the lattice search over (cell, heading) states (nfopp_lattice_distance_fields): layers uint8 [L, rows, cols], goal_states int32
-// [G, 3] (row, col, heading or -1) -> fields int32 [G, 8, rows, cols, 2]
-Tensor lattice_fields(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost) {
-  check_tensor(layers, "layers", at::kByte);
-  check_tensor(goal_states, "goal_states", at::kInt);
-  same_device(layers, goal_states, "goal_states");
-  TORCH_CHECK(layers.dim() == 3, "nfopp: layers must be [L, rows, cols] uint8");
-  TORCH_CHECK(goal_states.dim() == 2 && goal_states.size(1) == 3, "nfopp: goal_states must be [G, 3] (row, col, heading)");
-  TORCH_CHECK(turn_cost >= 0 && turn_cost <= 255, "nfopp: turn_cost must be 0..255");
-  const int64_t L = layers.size(0), rows = layers.size(1), cols = layers.size(2), G = goal_states.size(0);
-  TORCH_CHECK(rows >= 1 && cols >= 1 && rows <= 32768 && cols <= 32768, "nfopp: grid must be 1..32768 cells a side");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(layers.device());
-  Tensor fields = at::empty({G, 8, rows, cols, 2}, layers.options().dtype(at::kInt));
-  const size_t bytes = nfopp_lattice_fields_workspace_bytes((int32_t)rows, (int32_t)cols, (int32_t)turn_cost, G);
-  Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, layers.options().dtype(at::kLong));
-  check_status(nfopp_lattice_distance_fields(layers.data_ptr<uint8_t>(), (int32_t)L, (int32_t)rows, (int32_t)cols,
-                                             G ? goal_states.data_ptr<int32_t>() : nullptr, G, (int32_t)turn_cost,
-                                             G ? fields.data_ptr<int32_t>() : nullptr, bytes ? work.data_ptr() : nullptr, bytes,
-                                             stream_of(layers)));
-  return fields;
-}
-
-// the descent (nfopp_lattice_trace_paths) through fields [n_fields, 8, rows, cols, 2] = the fields field_first .. of n_total:
-// start_states / goal_states int32 [B, 3], field_index int32 [B] -> (cells [B, max_len, 2], headings [B, max_len], count [B],
-// status [B], cost [B, 2]) int32.  Outputs start as zeros, so a problem of another chunk reads count 0, status 0.
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> lattice_trace_paths(const Tensor& fields, int64_t field_first, int64_t n_total,
-                                                                       const Tensor& start_states, const Tensor& goal_states,
-                                                                       const Tensor& field_index, int64_t turn_cost, int64_t max_len) {
-  check_tensor(fields, "fields", at::kInt);
-  TORCH_CHECK(fields.dim() == 5 && fields.size(1) == 8 && fields.size(4) == 2, "nfopp: fields must be [G, 8, rows, cols, 2]");
-  check_tensor(start_states, "start_states", at::kInt);
-  TORCH_CHECK(start_states.dim() == 2 && start_states.size(1) == 3, "nfopp: start_states must be [B, 3] (row, col, heading)");
-  same_device(fields, start_states, "start_states");
-  const int64_t B = start_states.size(0), G = fields.size(0), rows = fields.size(2), cols = fields.size(3);
-  need(fields, goal_states, "goal_states", {B, 3}, at::kInt);
-  need(fields, field_index, "field_index", {B}, at::kInt);
-  TORCH_CHECK(max_len >= 0 && max_len <= std::numeric_limits<int32_t>::max(), "nfopp: bad max_len");
-  TORCH_CHECK(turn_cost >= 0 && turn_cost <= 255, "nfopp: turn_cost must be 0..255");
-  TORCH_CHECK(rows >= 1 && cols >= 1, "nfopp: fields of an empty grid");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(fields.device());
-  const auto i32 = fields.options().dtype(at::kInt);
-  Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32);
-  Tensor count = at::zeros({B}, i32), status = at::zeros({B}, i32), cost = at::zeros({B, 2}, i32);
-  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
-  check_status(nfopp_lattice_trace_paths(i32p(fields), field_first, G, n_total, (int32_t)rows, (int32_t)cols, (int32_t)turn_cost,
-                                         i32p(start_states), i32p(goal_states), i32p(field_index), B, (int32_t)max_len, i32p(cells),
-                                         i32p(headings), i32p(count), i32p(status), i32p(cost), stream_of(fields)));
-  return std::make_tuple(cells, headings, count, status, cost);
-}
-
-static void check_gear_costs(int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost) {
+static void check_lattice_costs(int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost) {
   TORCH_CHECK(turn_cost >= 0 && turn_cost <= 255, "nfopp: turn_cost must be 0..255");
   TORCH_CHECK(reverse_cost >= 0 && reverse_cost <= 255, "nfopp: reverse_cost must be 0..255");
   TORCH_CHECK(cusp_cost >= 0 && cusp_cost <= 255, "nfopp: cusp_cost must be 0..255");
 }
 
-// the lattice search over (cell, heading, gear) states (nfopp_lattice_gear_distance_fields): layers uint8 [L, rows, cols],
-// goal_states int32 [G, 3] (row, col, heading or -1) -> fields int32 [G, 2, 8, rows, cols, 2]
-Tensor lattice_gear_fields(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost) {
+// What the two lattice field ops share: layers uint8 [L, rows, cols], goal_states int32 [G, 3] (row, col, heading or -1) ->
+// fields int32 [G, 8, rows, cols, 2] from nfopp_lattice_distance_fields, with `gears` [G, 2, 8, rows, cols, 2] from
+// nfopp_lattice_gear_distance_fields; the forward-only search has reverse_cost = cusp_cost = 0.
+static Tensor lattice_fields_impl(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost, int64_t reverse_cost,
+                                  int64_t cusp_cost, bool gears) {
   check_tensor(layers, "layers", at::kByte);
   check_tensor(goal_states, "goal_states", at::kInt);
   same_device(layers, goal_states, "goal_states");
   TORCH_CHECK(layers.dim() == 3, "nfopp: layers must be [L, rows, cols] uint8");
   TORCH_CHECK(goal_states.dim() == 2 && goal_states.size(1) == 3, "nfopp: goal_states must be [G, 3] (row, col, heading)");
-  check_gear_costs(turn_cost, reverse_cost, cusp_cost);
-  const int64_t L = layers.size(0), rows = layers.size(1), cols = layers.size(2), G = goal_states.size(0);
-  TORCH_CHECK(rows >= 1 && cols >= 1 && rows <= 32768 && cols <= 32768, "nfopp: grid must be 1..32768 cells a side");
+  check_lattice_costs(turn_cost, reverse_cost, cusp_cost);
+  const int64_t G = goal_states.size(0);
+  const int32_t L = (int32_t)layers.size(0), tc = (int32_t)turn_cost, rc = (int32_t)reverse_cost, cc = (int32_t)cusp_cost;
+  TORCH_CHECK(layers.size(1) >= 1 && layers.size(2) >= 1 && layers.size(1) <= 32768 && layers.size(2) <= 32768,
+              "nfopp: grid must be 1..32768 cells a side");
+  const int32_t rows = (int32_t)layers.size(1), cols = (int32_t)layers.size(2);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(layers.device());
-  Tensor fields = at::empty({G, 2, 8, rows, cols, 2}, layers.options().dtype(at::kInt));
-  const size_t bytes = nfopp_lattice_gear_fields_workspace_bytes((int32_t)rows, (int32_t)cols, (int32_t)turn_cost,
-                                                                 (int32_t)reverse_cost, (int32_t)cusp_cost, G);
+  const auto i32 = layers.options().dtype(at::kInt);
+  Tensor fields = gears ? at::empty({G, 2, 8, rows, cols, 2}, i32) : at::empty({G, 8, rows, cols, 2}, i32);
+  const size_t bytes = gears ? nfopp_lattice_gear_fields_workspace_bytes(rows, cols, tc, rc, cc, G)
+                             : nfopp_lattice_fields_workspace_bytes(rows, cols, tc, G);
   Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, layers.options().dtype(at::kLong));
-  check_status(nfopp_lattice_gear_distance_fields(layers.data_ptr<uint8_t>(), (int32_t)L, (int32_t)rows, (int32_t)cols,
-                                                  G ? goal_states.data_ptr<int32_t>() : nullptr, G, (int32_t)turn_cost,
-                                                  (int32_t)reverse_cost, (int32_t)cusp_cost, G ? fields.data_ptr<int32_t>() : nullptr,
-                                                  bytes ? work.data_ptr() : nullptr, bytes, stream_of(layers)));
+  const uint8_t* occ = layers.data_ptr<uint8_t>();
+  const int32_t* goals = G ? goal_states.data_ptr<int32_t>() : nullptr;
+  int32_t* out = G ? fields.data_ptr<int32_t>() : nullptr;
+  void* ws = bytes ? work.data_ptr() : nullptr;
+  check_status(gears ? nfopp_lattice_gear_distance_fields(occ, L, rows, cols, goals, G, tc, rc, cc, out, ws, bytes, stream_of(layers))
+                     : nfopp_lattice_distance_fields(occ, L, rows, cols, goals, G, tc, out, ws, bytes, stream_of(layers)));
   return fields;
 }
 
-// the descent (nfopp_lattice_gear_trace_paths) through fields [n_fields, 2, 8, rows, cols, 2] = the fields field_first .. of
-// n_total -> (cells [B, max_len, 2], headings [B, max_len], gears [B, max_len], count [B], status [B], cost [B, 2]) int32.
-// Outputs start as zeros, so a problem of another chunk reads count 0, status 0.
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> lattice_gear_trace_paths(
-    const Tensor& fields, int64_t field_first, int64_t n_total, const Tensor& start_states, const Tensor& goal_states,
-    const Tensor& field_index, int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost, int64_t max_len) {
+// What the two lattice trace ops share: the descent through fields [n_fields, 8, rows, cols, 2] (nfopp_lattice_trace_paths), with
+// `gears` [n_fields, 2, 8, rows, cols, 2] (nfopp_lattice_gear_trace_paths), = the fields field_first .. of n_total; start_states /
+// goal_states int32 [B, 3], field_index int32 [B] -> {cells [B, max_len, 2], headings [B, max_len], gears [B, max_len] (with
+// `gears` only), count [B], status [B], cost [B, 2]} int32.  Outputs start as zeros, so a problem of another chunk reads count
+// 0, status 0.
+static std::vector<Tensor> lattice_trace_impl(const Tensor& fields, int64_t field_first, int64_t n_total, const Tensor& start_states,
+                                              const Tensor& goal_states, const Tensor& field_index, int64_t turn_cost,
+                                              int64_t reverse_cost, int64_t cusp_cost, int64_t max_len, bool gears) {
   check_tensor(fields, "fields", at::kInt);
-  TORCH_CHECK(fields.dim() == 6 && fields.size(1) == 2 && fields.size(2) == 8 && fields.size(5) == 2,
-              "nfopp: fields must be [G, 2, 8, rows, cols, 2]");
+  if (gears) {
+    TORCH_CHECK(fields.dim() == 6 && fields.size(1) == 2 && fields.size(2) == 8 && fields.size(5) == 2,
+                "nfopp: fields must be [G, 2, 8, rows, cols, 2]");
+  } else {
+    TORCH_CHECK(fields.dim() == 5 && fields.size(1) == 8 && fields.size(4) == 2, "nfopp: fields must be [G, 8, rows, cols, 2]");
+  }
   check_tensor(start_states, "start_states", at::kInt);
   TORCH_CHECK(start_states.dim() == 2 && start_states.size(1) == 3, "nfopp: start_states must be [B, 3] (row, col, heading)");
   same_device(fields, start_states, "start_states");
-  const int64_t B = start_states.size(0), G = fields.size(0), rows = fields.size(3), cols = fields.size(4);
+  const int64_t B = start_states.size(0), G = fields.size(0), rows = fields.size(gears ? 3 : 2), cols = fields.size(gears ? 4 : 3);
   need(fields, goal_states, "goal_states", {B, 3}, at::kInt);
   need(fields, field_index, "field_index", {B}, at::kInt);
   TORCH_CHECK(max_len >= 0 && max_len <= std::numeric_limits<int32_t>::max(), "nfopp: bad max_len");
-  check_gear_costs(turn_cost, reverse_cost, cusp_cost);
+  check_lattice_costs(turn_cost, reverse_cost, cusp_cost);
   TORCH_CHECK(rows >= 1 && cols >= 1, "nfopp: fields of an empty grid");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(fields.device());
   const auto i32 = fields.options().dtype(at::kInt);
-  Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32), gears = at::zeros({B, max_len}, i32);
+  Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32), gear = at::zeros({gears ? B : 0, max_len}, i32);
   Tensor count = at::zeros({B}, i32), status = at::zeros({B}, i32), cost = at::zeros({B, 2}, i32);
   auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
-  check_status(nfopp_lattice_gear_trace_paths(i32p(fields), field_first, G, n_total, (int32_t)rows, (int32_t)cols, (int32_t)turn_cost,
-                                              (int32_t)reverse_cost, (int32_t)cusp_cost, i32p(start_states), i32p(goal_states),
-                                              i32p(field_index), B, (int32_t)max_len, i32p(cells), i32p(headings), i32p(gears),
-                                              i32p(count), i32p(status), i32p(cost), stream_of(fields)));
-  return std::make_tuple(cells, headings, gears, count, status, cost);
+  const int32_t r = (int32_t)rows, c = (int32_t)cols, tc = (int32_t)turn_cost, ml = (int32_t)max_len;
+  check_status(gears ? nfopp_lattice_gear_trace_paths(i32p(fields), field_first, G, n_total, r, c, tc, (int32_t)reverse_cost,
+                                                      (int32_t)cusp_cost, i32p(start_states), i32p(goal_states), i32p(field_index), B, ml,
+                                                      i32p(cells), i32p(headings), i32p(gear), i32p(count), i32p(status), i32p(cost),
+                                                      stream_of(fields))
+                     : nfopp_lattice_trace_paths(i32p(fields), field_first, G, n_total, r, c, tc, i32p(start_states), i32p(goal_states),
+                                                 i32p(field_index), B, ml, i32p(cells), i32p(headings), i32p(count), i32p(status),
+                                                 i32p(cost), stream_of(fields)));
+  return {cells, headings, gear, count, status, cost};
+}
+
+Tensor lattice_fields(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost) {
+  return lattice_fields_impl(layers, goal_states, turn_cost, 0, 0, false);
+}
+
+Tensor lattice_gear_fields(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost) {
+  return lattice_fields_impl(layers, goal_states, turn_cost, reverse_cost, cusp_cost, true);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> lattice_trace_paths(const Tensor& fields, int64_t field_first, int64_t n_total,
+                                                                       const Tensor& start_states, const Tensor& goal_states,
+                                                                       const Tensor& field_index, int64_t turn_cost, int64_t max_len) {
+  const auto t = lattice_trace_impl(fields, field_first, n_total, start_states, goal_states, field_index, turn_cost, 0, 0, max_len, false);
+  return std::make_tuple(t[0], t[1], t[3], t[4], t[5]);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> lattice_gear_trace_paths(
+    const Tensor& fields, int64_t field_first, int64_t n_total, const Tensor& start_states, const Tensor& goal_states,
+    const Tensor& field_index, int64_t turn_cost, int64_t reverse_cost, int64_t cusp_cost, int64_t max_len) {
+  const auto t = lattice_trace_impl(fields, field_first, n_total, start_states, goal_states, field_index, turn_cost, reverse_cost,
+                                    cusp_cost, max_len, true);
+  return std::make_tuple(t[0], t[1], t[2], t[3], t[4], t[5]);
 }
 
 // nfopp_lattice_seed_trajectories: cells int32 [B, max_len, 2], headings int32 [B, max_len], count / status int32 [B], start /

@@ -131,61 +131,47 @@ def _gear_costs(turn_cost, reverse_cost, cusp_cost):
     return _cost(turn_cost), _cost(reverse_cost, "reverse_cost"), _cost(cusp_cost, "cusp_cost")
 
 
-def _check_gear_bound(lgrid, costs):
+def _check_bound(lgrid, costs, gear_layers):
+    """costs: (turn_cost,) with gear_layers 1, (turn_cost, reverse_cost, cusp_cost) with gear_layers 2."""
     rows, cols = lgrid.shape
-    if 2 * HEADINGS * rows * cols * (1 + sum(costs)) >= 2 ** 21:
-        raise ValueError("16 * rows * cols * (1 + turn_cost + reverse_cost + cusp_cost) must stay below 2^21 (%d x %d, costs %s)"
-                         % (rows, cols, costs))
+    if gear_layers * HEADINGS * rows * cols * (1 + sum(costs)) >= 2 ** 21:
+        if gear_layers == 2:
+            raise ValueError("16 * rows * cols * (1 + turn_cost + reverse_cost + cusp_cost) must stay below 2^21 (%d x %d, costs %s)"
+                             % (rows, cols, costs))
+        raise ValueError("8 * rows * cols * (1 + turn_cost) must stay below 2^21 (%d x %d, turn_cost %d)" % (rows, cols, costs[0]))
 
 
-def _check_bound(lgrid, turn_cost):
+def _fields(lgrid, goal_states, costs, gear_layers):
+    """The fields of either search: [G, 8, rows, cols, 2] with gear_layers 1, [G, 2, 8, rows, cols, 2] with gear_layers 2."""
+    lib = _lib.load()
+    _check_bound(lgrid, costs, gear_layers)
+    layers = lgrid.layers
     rows, cols = lgrid.shape
-    if HEADINGS * rows * cols * (1 + turn_cost) >= 2 ** 21:
-        raise ValueError("8 * rows * cols * (1 + turn_cost) must stay below 2^21 (%d x %d, turn_cost %d)" % (rows, cols, turn_cost))
+    goal_states = torch.as_tensor(goal_states, device=layers.device).to(torch.int32).contiguous()
+    if goal_states.dim() != 2 or goal_states.shape[1] != 3:
+        raise ValueError("goal_states must be [G, 3] (row, col, heading)")
+    g = goal_states.shape[0]
+    fields = torch.empty((g,) + (2,) * (gear_layers - 1) + (HEADINGS, rows, cols, 2), dtype=torch.int32, device=layers.device)
+    query, entry = ((lib.nfopp_lattice_fields_workspace_bytes, lib.nfopp_lattice_distance_fields) if gear_layers == 1 else
+                    (lib.nfopp_lattice_gear_fields_workspace_bytes, lib.nfopp_lattice_gear_distance_fields))
+    ws_bytes = query(rows, cols, *costs, g)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=layers.device) if ws_bytes else None
+    _lib.check(entry(_lib.ptr(layers, torch.uint8), lgrid.n_layers, rows, cols, _lib.ptr(goal_states, torch.int32), g, *costs,
+                     _lib.ptr(fields, torch.int32), _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
+                     _lib.stream_ptr()))
+    return fields
 
 
 def lattice_fields(lgrid, goal_states, turn_cost=0):
     """goal_states int32 [G, 3] (row, col, heading or -1) on the device -> int32 [G, 8, rows, cols, 2]: the exact cost (a, b)
     from every state to the goal state; (-1, -1) = blocked or unreachable."""
-    lib = _lib.load()
-    turn_cost = _cost(turn_cost)
-    _check_bound(lgrid, turn_cost)
-    layers = lgrid.layers
-    rows, cols = lgrid.shape
-    goal_states = torch.as_tensor(goal_states, device=layers.device).to(torch.int32).contiguous()
-    if goal_states.dim() != 2 or goal_states.shape[1] != 3:
-        raise ValueError("goal_states must be [G, 3] (row, col, heading)")
-    g = goal_states.shape[0]
-    fields = torch.empty(g, HEADINGS, rows, cols, 2, dtype=torch.int32, device=layers.device)
-    ws_bytes = lib.nfopp_lattice_fields_workspace_bytes(rows, cols, turn_cost, g)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=layers.device) if ws_bytes else None
-    _lib.check(lib.nfopp_lattice_distance_fields(_lib.ptr(layers, torch.uint8), lgrid.n_layers, rows, cols,
-                                                 _lib.ptr(goal_states, torch.int32), g, turn_cost, _lib.ptr(fields, torch.int32),
-                                                 _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
-                                                 _lib.stream_ptr()))
-    return fields
+    return _fields(lgrid, goal_states, (_cost(turn_cost),), 1)
 
 
 def lattice_gear_fields(lgrid, goal_states, turn_cost=0, reverse_cost=0, cusp_cost=0):
     """goal_states int32 [G, 3] (row, col, heading or -1) on the device -> int32 [G, 2, 8, rows, cols, 2]: the exact cost (a, b)
     from every state (gear, heading, cell) to the goal state with reverse moves allowed; (-1, -1) = blocked or unreachable."""
-    lib = _lib.load()
-    costs = _gear_costs(turn_cost, reverse_cost, cusp_cost)
-    _check_gear_bound(lgrid, costs)
-    layers = lgrid.layers
-    rows, cols = lgrid.shape
-    goal_states = torch.as_tensor(goal_states, device=layers.device).to(torch.int32).contiguous()
-    if goal_states.dim() != 2 or goal_states.shape[1] != 3:
-        raise ValueError("goal_states must be [G, 3] (row, col, heading)")
-    g = goal_states.shape[0]
-    fields = torch.empty(g, 2, HEADINGS, rows, cols, 2, dtype=torch.int32, device=layers.device)
-    ws_bytes = lib.nfopp_lattice_gear_fields_workspace_bytes(rows, cols, costs[0], costs[1], costs[2], g)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=layers.device) if ws_bytes else None
-    _lib.check(lib.nfopp_lattice_gear_distance_fields(
-        _lib.ptr(layers, torch.uint8), lgrid.n_layers, rows, cols, _lib.ptr(goal_states, torch.int32), g, costs[0], costs[1],
-        costs[2], _lib.ptr(fields, torch.int32), _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
-        _lib.stream_ptr()))
-    return fields
+    return _fields(lgrid, goal_states, _gear_costs(turn_cost, reverse_cost, cusp_cost), 2)
 
 
 def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes, gear_costs=None):
@@ -199,13 +185,10 @@ def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes, gear
     # the two searches differ in their costs, their field and trace entries, and the gear layer of the field; nothing below
     # this block asks which one runs
     if gear_costs is None:
-        costs = (_cost(turn_cost),)
-        _check_bound(lgrid, costs[0])
-        fields_fn, trace_entry, gear_layers = lattice_fields, lib.nfopp_lattice_trace_paths, 1
+        costs, trace_entry, gear_layers = (_cost(turn_cost),), lib.nfopp_lattice_trace_paths, 1
     else:
-        costs = _gear_costs(turn_cost, *gear_costs)
-        _check_gear_bound(lgrid, costs)
-        fields_fn, trace_entry, gear_layers = lattice_gear_fields, lib.nfopp_lattice_gear_trace_paths, 2
+        costs, trace_entry, gear_layers = _gear_costs(turn_cost, *gear_costs), lib.nfopp_lattice_gear_trace_paths, 2
+    _check_bound(lgrid, costs, gear_layers)
     starts, goals = _as_device_points(lgrid, starts), _as_device_points(lgrid, goals)
     if starts.shape != goals.shape or starts.shape[1] != 3:
         raise ValueError("starts and goals must both be [B, 3] poses (x, y, theta)")
@@ -254,7 +237,7 @@ def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes, gear
     # one sizing pass and one count.max() per chunk of fields: a single chunk (the usual case) costs the one read-back of the
     # 8-connected search; counts of earlier chunks stay in `count`, so the maximum never falls
     for first in range(0, n_total, chunk):
-        fields = fields_fn(lgrid, unique_states[first:first + chunk], *costs)
+        fields = _fields(lgrid, unique_states[first:first + chunk], costs, gear_layers)
         trace(fields, first, 0)
         max_len = max(int(count.max()), 1)
         if max_len > cells.shape[1]:

@@ -55,12 +55,12 @@ TRACE_GOALS = {"9x65": 2, "2x300": 1, "510x7": 1}         # goals traced from ev
 # it under 2 s
 TRACE_EVERY = {"510x7": 17}
 # restated from csrc/lattice_search.hip (tests/test_lattice_cpu.py reads them back from the source)
-LS_THREADS = 512             # `constexpr int LS_THREADS = 512;`: the stride of lattice_field_body over the lines
-LS_LDS_WORDS = 36864         # `constexpr int LS_LDS_WORDS = 36864;`: the packed 8-layer field one workgroup's LDS holds
+LS_THREADS = 512             # `constexpr int LATTICE_THREADS = 512;` (csrc/lattice_field.h): the stride of the field kernels over the lines
+LS_LDS_WORDS = 36864         # `constexpr int LATTICE_LDS_WORDS = 36864;`: the packed 8-layer field one workgroup's LDS holds
 
 
 def n_lines(name):
-    """The lines lattice_field_body shares among its threads: rows and columns twice, the diagonals four times."""
+    """The lines a field kernel shares among its threads: rows and columns twice, the diagonals four times."""
     rows, cols = SHAPES[name][:2]
     return 2 * rows + 2 * cols + 4 * (rows + cols - 1)
 

@@ -26,8 +26,8 @@ HAND_PATH = ((0, 3, 4, None), (0, 2, 4, 0), (0, 3, 5, 1), (1, 4, 6, 1), (0, 5, 7
 HAND_PATH_MOVES = ((1, 0), (1 + 1 + 3, 0), (1, 1), (3, 1), (1, 0))
 
 # restated from csrc/lattice_gears.hip (tests/test_lattice_gears_cpu.py reads them back from the source)
-LG_THREADS = 512             # `constexpr int LG_THREADS = 512;`: the stride of gear_field_body over the lines
-LG_LDS_WORDS = 36864         # `constexpr int LG_LDS_WORDS = 36864;`: the packed 16-layer field one workgroup's LDS holds
+LG_THREADS = 512             # `constexpr int LATTICE_THREADS = 512;` (csrc/lattice_field.h): the stride of the field kernels over the lines
+LG_LDS_WORDS = 36864         # `constexpr int LATTICE_LDS_WORDS = 36864;`: the packed 16-layer field one workgroup's LDS holds
 
 # ---- the shapes of the device tests: name -> (rows, cols, wall share or "one" / None, layers, cost sets, extra goals) ---------
 SHAPES = {
@@ -63,7 +63,7 @@ TRACE_SHAPES = (("5x5w", (1, 2, 1)), ("3x7", (0, 1, 3)), ("2x7", (0, 0, 0)), ("2
 
 
 def n_lines(name):
-    """The lines gear_field_body shares among its threads: rows and columns twice, the diagonals four times."""
+    """The lines a field kernel shares among its threads: rows and columns twice, the diagonals four times."""
     rows, cols = SHAPES[name][:2]
     return 2 * rows + 2 * cols + 4 * (rows + cols - 1)
 

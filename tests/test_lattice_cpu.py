@@ -123,14 +123,18 @@ def test_what_the_device_cases_cover():
     assert statuses == {0, 1, 2}
     assert headings_seen == set(range(8)) and {1, 7} <= turns
     assert layer_dependent and wall_goal and blocked_start
-    # the LDS form at its stride and capacity edges, against the kernel's constants as its source states them: some shape that
-    # relaxes in LDS has more lines than the kernel has threads (2x300 / 300x2: 1808, four trips), one fills LS_LDS_WORDS
-    # exactly (510x7), and the shapes on the other side of each dispatch edge are wide
+    # the LDS form at its stride and capacity edges, against the kernel's constants as the shared frame (csrc/lattice_field.h)
+    # states them: some shape that relaxes in LDS has more lines than the kernel has threads (2x300 / 300x2: 1808, four trips),
+    # one fills LATTICE_LDS_WORDS exactly (510x7), and the shapes on the other side of each dispatch edge are wide
+    frame = open(os.path.join(CSRC, "lattice_field.h")).read()
+    for text in ("constexpr int LATTICE_THREADS = %d;" % lc.LS_THREADS, "constexpr int LATTICE_LDS_WORDS = %d;" % lc.LS_LDS_WORDS,
+                 "{ return 2 * rows + 2 * cols + 4 * (rows + cols - 1); }", "*stride = (cols + 2) | 1;",
+                 "n_state_layers * *padded <= LATTICE_LDS_WORDS && counts <= 65535", "constexpr int LATTICE_HEADINGS = 8;"):
+        assert text in frame, (text, "the kernel's constant or loop moved: replace the shape sized by it")
     kernel = open(os.path.join(CSRC, "lattice_search.hip")).read()
-    for text in ("constexpr int LS_THREADS = %d;" % lc.LS_THREADS, "constexpr int LS_LDS_WORDS = %d;" % lc.LS_LDS_WORDS,
-                 "for (int q = threadIdx.x; q < n_lines; q += LS_THREADS)", "const int n_lines = 2 * rows + 2 * cols + 4 * n_diag;",
-                 "*stride = (cols + 2) | 1;", "LS_HEADINGS * *padded <= LS_LDS_WORDS && counts <= 65535"):
-        assert text in kernel, (text, "the kernel's constant or loop moved: replace the shape sized by it")
+    for text in ("constexpr int LS_STATES = LATTICE_HEADINGS;", "const int n_lines = lattice_n_lines(rows, cols);",   # 8 state layers
+                 "for (int q = threadIdx.x; q < n_lines; q += LATTICE_THREADS)", "LS_STATES, \"8 * rows * cols * (1 + turn_cost) reaches"):
+        assert text in kernel, (text, "the kernel's layer count or loop moved: replace the shape sized by it")
     in_lds = [(n, tc) for n, s in lc.SHAPES.items() for tc in s[4] if (n, tc) not in lc.WIDE]
     assert all(lc.lds_words(n) <= lc.LS_LDS_WORDS and 8 * lc.SHAPES[n][0] * lc.SHAPES[n][1] * (1 + tc) <= 65535 for n, tc in in_lds)
     assert max(lc.n_lines(n) for n, _ in in_lds) > 3 * lc.LS_THREADS
@@ -279,9 +283,13 @@ def test_header_binding_library_and_build_agree():
     assert lib.nfopp_abi_version() == 6 and _lib.ABI_VERSION == 6
     assert "lattice_search.hip" in open(os.path.join(CSRC, "Makefile")).read()
     kernel = open(os.path.join(CSRC, "lattice_search.hip")).read()
-    dirs = re.search(r"LS_DR\[LS_HEADINGS\] = \{([^}]*)\};\s*__constant__ int LS_DC\[LS_HEADINGS\] = \{([^}]*)\};", kernel)
+    frame = open(os.path.join(CSRC, "lattice_field.h")).read()
+    dirs = re.search(r"LATTICE_DR\[LATTICE_HEADINGS\] = \{([^}]*)\};\s*inline __constant__ int LATTICE_DC\[LATTICE_HEADINGS\] = "
+                     r"\{([^}]*)\};", frame)
     got = tuple(zip(*[[int(v) for v in g.split(",")] for g in dirs.groups()]))
-    assert got == lr.DIRS                                                   # the direction table, kernel against restatement
+    assert got == lr.DIRS                                                   # the one direction table against the restatement
+    assert '#include "lattice_field.h"' in kernel and "__constant__" not in kernel and "lattice_field.h" in \
+        open(os.path.join(CSRC, "Makefile")).read()
     for text in (header, kernel, open(os.path.join(ROOT, "tests", "lattice_ref.py")).read()):
         for word in ("h' in {h, h + 1, h - 1}", "forced free", "turn_cost", "AFTER"):
             assert word in text, word

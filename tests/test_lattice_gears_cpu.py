@@ -194,8 +194,10 @@ def test_the_device_shapes_sit_where_their_names_say():
     assert _fields_rc(rows=9, cols=65, cc=255) != 0 and "2^21" in lib.nfopp_last_error().decode()
     for bad in ((0, 5, 0, 0, 0, 1), (5, 5, 256, 0, 0, 1), (5, 5, 0, 256, 0, 1), (5, 5, 0, 0, -1, 1), (5, 5, 0, 0, 0, 0), (256, 512, 0, 0, 0, 1)):
         assert lib.nfopp_lattice_gear_fields_workspace_bytes(*bad) == 0
+    frame = open(os.path.join(CSRC, "lattice_field.h")).read()
+    assert "constexpr int LATTICE_THREADS = %d;" % gc.LG_THREADS in frame and "constexpr int LATTICE_LDS_WORDS = %d;" % gc.LG_LDS_WORDS in frame
     src = open(os.path.join(CSRC, "lattice_gears.hip")).read()
-    assert "constexpr int LG_THREADS = %d;" % gc.LG_THREADS in src and "constexpr int LG_LDS_WORDS = %d;" % gc.LG_LDS_WORDS in src
+    assert "constexpr int LG_STATES = 2 * LATTICE_HEADINGS;" in src and "for (int q = threadIdx.x; q < n_lines; q += LATTICE_THREADS)" in src
 
 
 def test_the_seeding_knots_unwind_the_heading():
@@ -368,9 +370,17 @@ def test_header_binding_library_and_build_agree():
     assert lib.nfopp_abi_version() == 6 and _lib.ABI_VERSION == 6
     assert "lattice_gears.hip" in open(os.path.join(CSRC, "Makefile")).read()
     kernel = open(os.path.join(CSRC, "lattice_gears.hip")).read()
-    dirs = re.search(r"LG_DR\[LG_HEADINGS\] = \{([^}]*)\};\s*__constant__ int LG_DC\[LG_HEADINGS\] = \{([^}]*)\};", kernel)
-    got = tuple(zip(*[[int(v) for v in g.split(",")] for g in dirs.groups()]))
-    assert got == lr.DIRS                                                   # the direction table, kernel against restatement
+    # the direction table is the one of csrc/lattice_field.h, pinned against the restatement in test_lattice_cpu.py
+    frame = open(os.path.join(CSRC, "lattice_field.h")).read()
+    line_map = re.compile(r"int h = 0, i = q;.*?len = len_r < len_c \? len_r : len_c;", re.S)
+    own, shared = line_map.search(kernel).group(0), line_map.search(frame).group(0)
+    assert [t.strip() for t in own.split("\n")] == [t.strip() for t in shared.split("\n")]    # the gear file's own line map, kept for
+    assert "const int n_lines = lattice_n_lines(rows, cols);" in kernel                          # its kernels' time, is the header's text
+    assert '#include "lattice_field.h"' in kernel and "LATTICE_DR[" in kernel and "__constant__" not in kernel
+    sources = "".join(open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h")))
+    for once in ("{0, 1, 1, 1, 0, -1, -1, -1}", "{1, 1, 0, -1, -1, -1, 0, 1}", "2 * rows + 2 * cols + 4 * (rows + cols - 1)",
+                 "(cols + 2) | 1"):
+        assert sources.count(once) == 1, once                               # one table, one n_lines formula, one odd stride
     assert '#include "pair_cost.h"' in kernel and "struct Packed" not in kernel and "pair_key(T v)" not in kernel
     for text in (header, kernel, open(os.path.join(ROOT, "tests", "lattice_gears_ref.py")).read()):
         for word in ("h' in {h, h + 1, h - 1}", "forced free", "BEFORE", "reverse_cost", "cusp_cost", "forward h, h + 1, h - 1",
