@@ -10,6 +10,7 @@
 // Everything that decides an anchor is int32 arithmetic, so the result does not depend on the schedule; the points are
 // float64 with every operation rounded on its own, stored fp32.
 #include "common.h"
+#include "grid_frame.h"
 
 namespace nfopp {
 
@@ -57,10 +58,9 @@ __device__ __forceinline__ bool sees(const int* __restrict__ dist2, int cols, in
   return true;
 }
 
-// the centre of a (possibly fractional) cell coordinate in metres; for an integer u the very expression of the seeding
-// stage (grid_search.hip: seed_body), so a path with nothing to shorten gives that stage's polyline bit for bit
+// the fractional cell coordinates below are float64 with every operation rounded on its own; their centres in metres are
+// grid_cell_centre's (grid_frame.h), the seeding stage's too
 #pragma clang fp contract(off)
-__device__ __forceinline__ float centre(double u, double res, double origin) { return (float)((u * res + res / 2.0) + origin); }
 
 __global__ __launch_bounds__(AA_THREADS) void shorten_kernel(const ShortenArgs a) {
   const int lane = threadIdx.x & 63;
@@ -116,8 +116,8 @@ __global__ __launch_bounds__(AA_THREADS) void shorten_kernel(const ShortenArgs a
         const double ur = (double)A.x + (double)(dr * t) / (double)m;
         const double uc = (double)A.y + (double)(dc * t) / (double)m;
         float* q = pts + (n_points + t) * 2;
-        q[0] = centre(uc, a.res, a.ox);
-        q[1] = centre(ur, a.res, a.oy);
+        q[0] = grid_cell_centre(uc, a.res, a.ox);
+        q[1] = grid_cell_centre(ur, a.res, a.oy);
       }
     }
     n_points += m;
@@ -126,8 +126,8 @@ __global__ __launch_bounds__(AA_THREADS) void shorten_kernel(const ShortenArgs a
   if (lane == 0) {
     if (pts && n_points < a.max_points) {
       const int2 E = cells[n - 1];
-      pts[n_points * 2] = centre((double)E.y, a.res, a.ox);
-      pts[n_points * 2 + 1] = centre((double)E.x, a.res, a.oy);
+      pts[n_points * 2] = grid_cell_centre((double)E.y, a.res, a.ox);
+      pts[n_points * 2 + 1] = grid_cell_centre((double)E.x, a.res, a.oy);
     }
     a.anchor_count[p] = n_anchors;
     a.point_count[p] = (int)min(n_points + 1, (long long)INT32_MAX);

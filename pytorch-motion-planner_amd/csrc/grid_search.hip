@@ -16,6 +16,7 @@
 // additions made on it inside one sweep) stays below 3e-9, so the order of DIFFERENT pairs is exact; whether a cell
 // changed is decided on the integer pair itself.
 #include "common.h"
+#include "grid_frame.h"
 #include "lattice_field.h"
 #include "pair_cost.h"
 #include "spline2.h"
@@ -276,8 +277,8 @@ __device__ __forceinline__ void seed_body(const SeedArgs& a, double* W, long lon
     else if (points) { x = points[2 * (k - 1)]; y = points[2 * (k - 1) + 1]; }
     else {
       const int2 rc = cells[k - 1];
-      x = (float)(((double)rc.y * a.res + a.res / 2.0) + a.ox);
-      y = (float)(((double)rc.x * a.res + a.res / 2.0) + a.oy);
+      x = grid_cell_centre((double)rc.y, a.res, a.ox);
+      y = grid_cell_centre((double)rc.x, a.res, a.oy);
     }
     P[2 * k] = x; P[2 * k + 1] = y;
     C[2 * k] = (double)x; C[2 * k + 1] = (double)y;

@@ -58,6 +58,7 @@
 
 #include "block_collectives.h"
 #include "common.h"
+#include "grid_frame.h"
 #include "track_pairs.h"
 
 #pragma clang fp contract(off)
@@ -90,15 +91,6 @@ __host__ __device__ __forceinline__ int st_dcol(int d) { return (int)((ST_DCOL_B
 
 struct IntMax { __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; } };
 struct IntMin { __device__ __forceinline__ int operator()(int a, int b) const { return a < b ? a : b; } };
-
-// the fp32 centre of column / row n: (n * res + res / 2) + origin in float64, rounded once
-__device__ __forceinline__ float st_centre(int n, double res, double origin) {
-#pragma clang fp contract(off)
-  const double scaled = (double)n * res;
-  const double half = res / 2.0;
-  const double mid = scaled + half;
-  return (float)(mid + origin);
-}
 
 __device__ __forceinline__ bool st_wall(const unsigned char* occ, int rows, int cols, int r, int c) {
   return r < 0 || r >= rows || c < 0 || c >= cols || occ[(long long)r * cols + c] != 0;
@@ -175,8 +167,8 @@ __global__ __launch_bounds__(ST_THREADS) void st_reserve_kernel(const ReserveArg
   double xs[3], ys[3];   // the centres of the columns col - 1 .. col + 1 and the rows r - 1 .. r + 1, widened
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    xs[k] = (double)st_centre(col + k - 1, p.res, p.b0);
-    ys[k] = (double)st_centre(r + k - 1, p.res, p.b2);
+    xs[k] = (double)grid_cell_centre((double)(col + k - 1), p.res, p.b0);
+    ys[k] = (double)grid_cell_centre((double)(r + k - 1), p.res, p.b2);
   }
   unsigned bits = 0u;   // bit d: edge (this cell, d, h) meets a mover; bit 0 alone for the last-instant term
   for (long long j0 = 0; j0 < p.m; j0 += ST_TRACKS) {
@@ -356,8 +348,8 @@ __global__ __launch_bounds__(ST_SEARCH_THREADS) void st_search_kernel(const Sear
   for (int h = tid; h < p.T; h += ST_SEARCH_THREADS) {
     const int cell = h >= ha ? gr * p.cols + gc : cells[h];
     if (h > ha) cells[h] = cell;
-    track[2 * h] = st_centre(cell % p.cols, p.res, p.b0);
-    track[2 * h + 1] = st_centre(cell / p.cols, p.res, p.b2);
+    track[2 * h] = grid_cell_centre((double)(cell % p.cols), p.res, p.b0);
+    track[2 * h + 1] = grid_cell_centre((double)(cell / p.cols), p.res, p.b2);
   }
   if (tid == 0) { p.arrival[i] = ha; p.status[i] = 0; }
 }

@@ -33,6 +33,10 @@ template <class T>
 T* opt_ptr(const OptTensor& t) {
   return (t.has_value() && t->defined() && t->numel() > 0) ? t->data_ptr<T>() : nullptr;
 }
+// an int32 tensor that may be empty: its pointer, or null
+int32_t* i32p(const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; }
+// the workspace of an op: `bytes` bytes on the device of `like` (the entries' 8-byte alignment is the device allocator's)
+Tensor byte_workspace(const Tensor& like, size_t bytes) { return at::empty({(int64_t)bytes}, like.options().dtype(at::kByte)); }
 void check_status(int rc) { TORCH_CHECK(rc == 0, "nfopp call failed (", rc, "): ", nfopp_last_error()); }
 
 nfopp_onf_config make_cfg(double mean, double sigma, bool use_cos, bool has_bias, int64_t angle_dim) {
@@ -266,7 +270,7 @@ Tensor grid_search_init(Tensor traj, const Tensor& start, const Tensor& goal, co
   const auto i32 = traj.options().dtype(at::kInt);
   Tensor fields = at::empty({G, rows, cols, 2}, i32);
   const size_t fws = nfopp_grid_fields_workspace_bytes((int32_t)rows, (int32_t)cols, G);
-  Tensor fwork = at::empty({(int64_t)((fws + 7) / 8)}, traj.options().dtype(at::kLong));
+  Tensor fwork = byte_workspace(traj, fws);
   check_status(nfopp_grid_distance_fields(occupancy.data_ptr<uint8_t>(), (int32_t)rows, (int32_t)cols,
                                           unique_goal_cells.data_ptr<int32_t>(), G, fields.data_ptr<int32_t>(),
                                           fws ? fwork.data_ptr() : nullptr, fws, stream_of(traj)));
@@ -282,7 +286,7 @@ Tensor grid_search_init(Tensor traj, const Tensor& start, const Tensor& goal, co
   Tensor cells = at::zeros({B, max_len, 2}, i32);
   trace((int32_t)max_len, cells.data_ptr<int32_t>());
   const size_t sws = nfopp_grid_seed_workspace_bytes(B, (int32_t)max_len);
-  Tensor swork = at::empty({(int64_t)((sws + 7) / 8)}, traj.options().dtype(at::kDouble));
+  Tensor swork = byte_workspace(traj, sws);
   check_status(nfopp_grid_seed_trajectories(cells.data_ptr<int32_t>(), count.data_ptr<int32_t>(), status.data_ptr<int32_t>(), B,
                                             (int32_t)max_len, b.start, b.goal, (int32_t)N, (int32_t)D,
                                             angles_with_direction ? 1 : 0, origin_x, origin_y, resolution, b.traj, sws ? swork.data_ptr() : nullptr, sws, stream_of(traj)));
@@ -387,8 +391,6 @@ std::tuple<int64_t, int64_t, int32_t> check_tracks(const Tensor& t, const char* 
               " must have fewer than 2^31 instants and floats per row");
   return std::make_tuple(t.size(0), t.size(1), (int32_t)t.size(2));
 }
-// the workspace of such an op: `bytes` bytes on the device of `like`
-Tensor byte_workspace(const Tensor& like, size_t bytes) { return at::empty({(int64_t)bytes}, like.options().dtype(at::kByte)); }
 
 // conflicts between timed tracks (nfopp_track_conflicts): tracks_a [Ba, K, Sa], tracks_b [Bb, K, Sb] or None (self mode), radii
 // [Ba] / [Bb] fp32 or None (0) -> (summary [Ba, 7], summary_b [Bb, 7], pair_gap, pair_first [Ba, Bb]) float64; summary_b is
@@ -550,7 +552,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> spacetime_plan_fleet(const Tensor& oc
   Tensor tracks = at::empty({r, count, 2}, occupancy.options().dtype(at::kFloat));
   const size_t bytes = nfopp_spacetime_plan_workspace_bytes(rows, cols, (int32_t)count, r);
   Tensor workspace = byte_workspace(occupancy, bytes);
-  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
   check_status(nfopp_spacetime_plan_fleet(occupancy.data_ptr<uint8_t>(), rows, cols, (int32_t)count, b0, b2, resolution, (float)robot_radius,
                                           margin, i32p(start_cells), i32p(goal_cells), opt_ptr<int32_t>(order), r,
                                           reinterpret_cast<uint64_t*>(reservation.data_ptr<int64_t>()), (size_t)n * 8, i32p(cells),
@@ -586,7 +587,7 @@ static Tensor lattice_fields_impl(const Tensor& layers, const Tensor& goal_state
   Tensor fields = gears ? at::empty({G, 2, 8, rows, cols, 2}, i32) : at::empty({G, 8, rows, cols, 2}, i32);
   const size_t bytes = gears ? nfopp_lattice_gear_fields_workspace_bytes(rows, cols, tc, rc, cc, G)
                              : nfopp_lattice_fields_workspace_bytes(rows, cols, tc, G);
-  Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, layers.options().dtype(at::kLong));
+  Tensor work = byte_workspace(layers, bytes);
   const uint8_t* occ = layers.data_ptr<uint8_t>();
   const int32_t* goals = G ? goal_states.data_ptr<int32_t>() : nullptr;
   int32_t* out = G ? fields.data_ptr<int32_t>() : nullptr;
@@ -624,7 +625,6 @@ static std::vector<Tensor> lattice_trace_impl(const Tensor& fields, int64_t fiel
   const auto i32 = fields.options().dtype(at::kInt);
   Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32), gear = at::zeros({gears ? B : 0, max_len}, i32);
   Tensor count = at::zeros({B}, i32), status = at::zeros({B}, i32), cost = at::zeros({B, 2}, i32);
-  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
   const int32_t r = (int32_t)rows, c = (int32_t)cols, tc = (int32_t)turn_cost, ml = (int32_t)max_len;
   check_status(gears ? nfopp_lattice_gear_trace_paths(i32p(fields), field_first, G, n_total, r, c, tc, (int32_t)reverse_cost,
                                                       (int32_t)cusp_cost, i32p(start_states), i32p(goal_states), i32p(field_index), B, ml,
@@ -677,8 +677,7 @@ Tensor lattice_seed_trajectories(const Tensor& cells, const Tensor& headings, co
   c10::hip::HIPGuardMasqueradingAsCUDA guard(cells.device());
   Tensor traj = at::empty({B, n_waypoints, 3}, cells.options().dtype(at::kFloat));
   const size_t bytes = nfopp_lattice_seed_workspace_bytes(B, (int32_t)max_len);
-  Tensor work = at::empty({(int64_t)((bytes + 7) / 8)}, cells.options().dtype(at::kLong));
-  auto i32p = [](const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; };
+  Tensor work = byte_workspace(cells, bytes);
   check_status(nfopp_lattice_seed_trajectories(i32p(cells), i32p(headings), i32p(count), i32p(status), B, (int32_t)max_len,
                                                B ? start.data_ptr<float>() : nullptr, B ? goal.data_ptr<float>() : nullptr,
                                                (int32_t)n_waypoints, origin_x, origin_y, resolution,

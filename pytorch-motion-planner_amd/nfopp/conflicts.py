@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import workspace
 from ._tracks import check_tracks, hip_device, per_row, raw_ptr
 
 # slots of TrackConflicts.summary [B, 7] (NFOPP_CONFLICT_SLOT_*)
@@ -55,14 +56,13 @@ def track_conflicts(tracks_a, tracks_b=None, *, dt, t0=0.0, radius_a=0.0, radius
     summary_b = None if self_mode else torch.empty(bb, _lib.NUM_CONFLICT_SLOTS, **f64)
     pair_gap = torch.empty(ba, cols, **f64) if want_pairs else None
     pair_first = torch.empty(ba, cols, **f64) if want_pairs else None
-    nbytes = int(lib.nfopp_track_conflicts_workspace_bytes(ba, bb, k))
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    ws = workspace(lib.nfopp_track_conflicts_workspace_bytes(ba, bb, k), device)
     # a set of no obstacles still needs a non-null pointer (null selects self mode); it is never read
     b_ptr = None if self_mode else (raw_ptr(tracks_b) or raw_ptr(tracks_a))
     _lib.check(lib.nfopp_track_conflicts(
         raw_ptr(tracks_a), ba, stride_a, b_ptr, bb, stride_b, k, float(t0), float(dt), _lib.ptr(radius_a), _lib.ptr(radius_b),
         float(margin), _lib.ptr(summary, torch.float64), _lib.ptr(summary_b, torch.float64), _lib.ptr(pair_gap, torch.float64),
-        _lib.ptr(pair_first, torch.float64), _lib.ptr(workspace, torch.uint8), nbytes, _lib.stream_ptr()))
+        _lib.ptr(pair_first, torch.float64), ws.ptr, ws.nbytes, _lib.stream_ptr()))
     if ba == 0 and bb > 0:      # the entry writes nothing for an empty set A: every obstacle is without a partner
         summary_b[:] = torch.tensor([np.inf, -1.0, np.nan, np.inf, -1.0, 0.0, CONFLICT_NO_PARTNER], **f64)
     return TrackConflicts(summary, summary_b, pair_gap, pair_first)

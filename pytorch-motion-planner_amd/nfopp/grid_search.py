@@ -10,6 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import (GridFrame, as_device_points, cell_centres, cell_keys, checker_boundaries, checker_device, goal_table, int32_on,
+                    seed_launch, traced_search, workspace)
 from .host_utils import Position2
 
 STATUS_OK, STATUS_UNREACHABLE, STATUS_OUTSIDE = 0, 1, 2
@@ -17,25 +19,9 @@ RASTER_HEADING = 3 * np.pi / 4   # astar_trajectory_initializer.py:37
 _MISSING = object()
 
 
-def _cell_counts(boundaries, resolution):
-    # astar_trajectory_initializer.py:29-30
-    x_cells = int((boundaries[1] - boundaries[0]) // resolution) + 1
-    y_cells = int((boundaries[3] - boundaries[2]) // resolution) + 1
-    return x_cells, y_cells
-
-
-def _cell_centres(boundaries, resolution):
-    # astar_trajectory_initializer.py:35-37 (float64, x fastest)
-    x_cells, y_cells = _cell_counts(boundaries, resolution)
-    x, y = np.meshgrid(range(x_cells), range(y_cells))
-    x = x.reshape(-1) * resolution + resolution / 2 + boundaries[0]
-    y = y.reshape(-1) * resolution + resolution / 2 + boundaries[2]
-    return x, y, x_cells, y_cells
-
-
-class OccupancyGrid(object):
-    """uint8 occupancy [rows = y cells, cols = x cells] (non-zero = wall) with the geometry of the reference's raster:
-    cell of a point = int((x - b0) // resolution), cell centre = j * resolution + resolution / 2 + b0.
+class OccupancyGrid(GridFrame):
+    """uint8 occupancy [rows = y cells, cols = x cells] (non-zero = wall) with the geometry of the reference's raster
+    (GridFrame: `cells_of`, `cell_centres`).
 
     The occupancy of a grid never changes after construction, so its distance transform (csrc/grid_edt.hip) and the images
     inflated from it are computed once and kept."""
@@ -46,10 +32,7 @@ class OccupancyGrid(object):
             raise ValueError("occupancy must be a non-empty [rows, cols] array")
         self._occupancy_host = occ
         self._shape = occ.shape
-        self.boundaries = tuple(float(b) for b in boundaries)
-        self.resolution = float(resolution)
-        if not self.resolution > 0:
-            raise ValueError("resolution must be positive")
+        GridFrame.__init__(self, boundaries, resolution)
         self.device = device
         self._occupancy_dev = None
         self._edt = {}        # border -> (dist2, nearest)
@@ -91,18 +74,10 @@ class OccupancyGrid(object):
         (`check_collision`) once on the host."""
         if resolution is None:
             raise TypeError("from_checker() needs a resolution")
-        if boundaries is None:
-            if hasattr(checker, "get_boundaries"):
-                boundaries = checker.get_boundaries()
-            else:
-                boundaries = getattr(checker, "boundaries", None)
-        if boundaries is None:
-            raise ValueError("the checker carries no boundaries: pass boundaries=(x0, x1, y0, y1)")
-        boundaries = tuple(float(b) for b in boundaries)
-        x, y, x_cells, y_cells = _cell_centres(boundaries, resolution)
+        boundaries = checker_boundaries(checker, boundaries)
+        x, y, x_cells, y_cells = cell_centres(boundaries, resolution)
         if hasattr(checker, "labels") and not hasattr(checker, "check_collision"):
-            dev = device or getattr(getattr(checker, "grid", None), "device", None) or \
-                getattr(getattr(checker, "obstacles", None), "device", None) or "cuda"
+            dev = checker_device(checker, device)
             poses = torch.tensor(np.stack([x, y, np.full_like(x, RASTER_HEADING)], 1).astype(np.float32), device=dev)
             occ = (checker.labels(poses) > 0).to(torch.uint8).reshape(y_cells, x_cells)
             grid = cls(occ.cpu().numpy(), boundaries, resolution, dev)
@@ -112,15 +87,6 @@ class OccupancyGrid(object):
             raise TypeError("the checker offers neither check_collision nor labels")
         hit = np.asarray(checker.check_collision(Position2(x, y, np.ones_like(x) * RASTER_HEADING)))
         return cls(hit.reshape(y_cells, x_cells), boundaries, resolution, device or "cuda")
-
-    def cells_of(self, points):
-        """[B, >= 2] device points -> int32 [B, 2] (row, col); float64 floor division as the reference's `//`."""
-        b = self.boundaries
-        xy = points[:, :2].double()
-        col = torch.floor((xy[:, 0] - b[0]) / self.resolution)
-        row = torch.floor((xy[:, 1] - b[2]) / self.resolution)
-        lim = float(2 ** 30)
-        return torch.stack([row, col], 1).clamp_(-lim, lim).to(torch.int32).contiguous()
 
     def distance_transform(self, border=False):
         """-> (dist2, nearest), int32 [rows, cols] on the device (nfopp_grid_edt): the squared Euclidean distance, in cells,
@@ -134,10 +100,9 @@ class OccupancyGrid(object):
             rows, cols = self.shape
             dist2 = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
             nearest = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
-            ws_bytes = lib.nfopp_grid_edt_workspace_bytes(rows, cols)
-            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=occ.device) if ws_bytes else None
+            ws = workspace(lib.nfopp_grid_edt_workspace_bytes(rows, cols), occ.device)
             _lib.check(lib.nfopp_grid_edt(_lib.ptr(occ, torch.uint8), rows, cols, int(border), _lib.ptr(dist2, torch.int32),
-                                          _lib.ptr(nearest, torch.int32), _lib.ptr(ws, torch.int32), ws_bytes, _lib.stream_ptr()))
+                                          _lib.ptr(nearest, torch.int32), ws.ptr, ws.nbytes, _lib.stream_ptr()))
             self._edt[border] = (dist2, nearest)
         return self._edt[border]
 
@@ -178,18 +143,6 @@ def margin_cells2(margin, resolution):
     return int(np.floor(q * q * (1.0 + 1e-9)))
 
 
-def _as_device_points(grid, pts):
-    if not torch.is_tensor(pts):
-        pts = torch.as_tensor(np.asarray(pts, np.float32))
-    if not pts.is_cuda:
-        _lib.require_gpu()
-        pts = pts.to(grid.device)
-    pts = pts.detach().float().contiguous()
-    if pts.dim() != 2 or pts.shape[1] not in (2, 3):
-        raise ValueError("starts / goals must be [B, 2] or [B, 3]")
-    return pts
-
-
 def distance_fields(grid, goal_cells):
     """goal_cells int32 [G, 2] (row, col) on the device -> int32 [G, rows, cols, 2] exact costs-to-goal (a, b);
     (-1, -1) = wall or unreachable."""
@@ -199,49 +152,37 @@ def distance_fields(grid, goal_cells):
     goal_cells = goal_cells.to(torch.int32).contiguous()
     g = goal_cells.shape[0]
     fields = torch.empty(g, rows, cols, 2, dtype=torch.int32, device=occ.device)
-    ws_bytes = lib.nfopp_grid_fields_workspace_bytes(rows, cols, g)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=occ.device) if ws_bytes else None
+    ws = workspace(lib.nfopp_grid_fields_workspace_bytes(rows, cols, g), occ.device)
     _lib.check(lib.nfopp_grid_distance_fields(_lib.ptr(occ, torch.uint8), rows, cols, _lib.ptr(goal_cells, torch.int32), g,
-                                              _lib.ptr(fields, torch.int32),
-                                              _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
-                                              _lib.stream_ptr()))
+                                              _lib.ptr(fields, torch.int32), ws.ptr, ws.nbytes, _lib.stream_ptr()))
     return fields
 
 
 def _search(grid, starts, goals):
     """-> (cells [B, max_len, 2], count, status, cost, starts, goals), all on the device."""
     lib = _lib.load()
-    starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
+    starts, goals = as_device_points(grid, starts), as_device_points(grid, goals)
     if starts.shape != goals.shape:
         raise ValueError("starts and goals must have the same shape")
     rows, cols = grid.shape
     b = starts.shape[0]
-    dev = starts.device
-    start_cells, goal_cells = grid.cells_of(starts), grid.cells_of(goals)
-    # problems that share a goal cell share a field
-    inside = (goal_cells[:, 0] >= 0) & (goal_cells[:, 0] < rows) & (goal_cells[:, 1] >= 0) & (goal_cells[:, 1] < cols)
-    key = torch.where(inside, goal_cells[:, 0].long() * cols + goal_cells[:, 1].long(), torch.full_like(inside, -1, dtype=torch.long))
-    uniq, inverse = torch.unique(key, return_inverse=True)
-    if uniq.numel() and int(uniq[0]) < 0:
-        uniq, inverse = uniq[1:], inverse - 1
-    field_index = inverse.to(torch.int32).contiguous()
-    unique_cells = torch.stack([uniq // cols, uniq % cols], 1).to(torch.int32).contiguous()
-    fields = distance_fields(grid, unique_cells) if uniq.numel() else torch.empty(0, rows, cols, 2, dtype=torch.int32, device=dev)
-    count = torch.empty(b, dtype=torch.int32, device=dev)
-    status = torch.empty(b, dtype=torch.int32, device=dev)
-    cost = torch.empty(b, 2, dtype=torch.int32, device=dev)
     i32 = torch.int32
+    start_cells, goal_cells = grid.cells_of(starts), grid.cells_of(goals)
+    # the key of a goal: its flat cell index
+    inside, flat = cell_keys(goal_cells, grid.shape)
+    uniq, field_index = goal_table(torch.where(inside, flat, torch.full_like(flat, -1)))
+    unique_cells = torch.stack([uniq // cols, uniq % cols], 1).to(i32).contiguous()
 
-    def trace(max_len, cells):
-        _lib.check(lib.nfopp_grid_trace_paths(_lib.ptr(fields, i32) if fields.numel() else None, fields.shape[0], rows, cols,
-                                              _lib.ptr(start_cells, i32), _lib.ptr(goal_cells, i32), _lib.ptr(field_index, i32),
-                                              b, max_len, _lib.ptr(cells, i32) if cells is not None else None,
-                                              _lib.ptr(count, i32), _lib.ptr(status, i32), _lib.ptr(cost, i32), _lib.stream_ptr()))
+    def trace(fields, first, paths, count, status, cost):
+        _lib.check(lib.nfopp_grid_trace_paths(
+            _lib.ptr(fields, i32), 0 if fields is None else fields.shape[0], rows, cols, _lib.ptr(start_cells, i32),
+            _lib.ptr(goal_cells, i32), _lib.ptr(field_index, i32), b, paths[0].shape[1] if paths else 0,
+            _lib.ptr(paths[0], i32) if paths else None, _lib.ptr(count, i32), _lib.ptr(status, i32), _lib.ptr(cost, i32),
+            _lib.stream_ptr()))
 
-    trace(0, None)
-    max_len = max(int(count.max()) if b else 0, 1)
-    cells = torch.zeros(b, max_len, 2, dtype=i32, device=dev)
-    trace(max_len, cells)
+    n = unique_cells.shape[0]   # every field at once: one chunk
+    (cells,), count, status, cost = traced_search(b, starts.device, n, max(n, 1), ((2,),),
+                                                  lambda first, last: distance_fields(grid, unique_cells), trace)
     return cells, count, status, cost, starts, goals
 
 
@@ -261,7 +202,7 @@ def _search_with_clearance(grid, starts, goals, clearance):
     margin at which its search returns status 0, else the plain grid's (with its status 1 / 2).  The levels are merged on
     the device.  -> (cells, count, status, cost, starts, goals, seed_margin fp32 [B], seed_cells2 int32 [B]): the margin each
     problem was seeded at and the threshold on dist2 of that level, both 0 for the plain grid."""
-    starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
+    starts, goals = as_device_points(grid, starts), as_device_points(grid, goals)
     cells, count, status, cost = _search(grid, starts, goals)[:4]
     seed_margin = torch.zeros(count.shape[0], dtype=torch.float32, device=count.device)
     seed_cells2 = torch.zeros(count.shape[0], dtype=torch.int32, device=count.device)
@@ -297,34 +238,14 @@ def grid_search_paths(grid, starts, goals, clearance=None):
     return r[:4] + r[6:7]
 
 
-def _seed_out(b, n_waypoints, d, dev, out):
-    if out is None:
-        return torch.empty(b, int(n_waypoints), d, dtype=torch.float32, device=dev)
-    if out.numel() != b * int(n_waypoints) * d or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous fp32 tensor of B * N * D elements")
-    return out
-
-
 def seed_trajectories(grid, cells, counts, status, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None):
     """The seeding stage alone: cell paths -> [B, N, D] trajectories (reparametrize_path + initialize_angle)."""
     lib = _lib.load()
-    starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
-    b, d = starts.shape
-    dev = starts.device
-    i32 = torch.int32
-    cells = torch.as_tensor(cells, dtype=i32, device=dev).contiguous()
-    counts = torch.as_tensor(counts, dtype=i32, device=dev).contiguous()
-    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
-    max_len = cells.shape[1]
-    out = _seed_out(b, n_waypoints, d, dev, out)
-    ws_bytes = lib.nfopp_grid_seed_workspace_bytes(b, max_len)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
-    bd = grid.boundaries
-    _lib.check(lib.nfopp_grid_seed_trajectories(
-        _lib.ptr(cells, i32), _lib.ptr(counts, i32), _lib.ptr(status, i32), b, max_len, _lib.ptr(starts), _lib.ptr(goals),
-        int(n_waypoints), d, 1 if (init_angles_with_trajectory and d == 3) else 0, bd[0], bd[2], grid.resolution,
-        _lib.ptr(out), _lib.ptr(ws, torch.float64) if ws is not None else None, ws_bytes, _lib.stream_ptr()))
-    return out.view(b, int(n_waypoints), d)
+    starts, goals = as_device_points(grid, starts), as_device_points(grid, goals)
+    cells, counts, status = int32_on(starts.device, cells, counts, status)
+    directed = 1 if (init_angles_with_trajectory and starts.shape[1] == 3) else 0
+    return seed_launch(lib.nfopp_grid_seed_workspace_bytes, lib.nfopp_grid_seed_trajectories, [cells], counts, status, starts, goals,
+                       n_waypoints, (starts.shape[1], directed) + grid.origin_resolution, out)
 
 
 def _shorten_paths(grid, cells, counts, status, cells2, lookahead, max_points=None):
@@ -340,11 +261,10 @@ def _shorten_paths(grid, cells, counts, status, cells2, lookahead, max_points=No
     anchor_counts = torch.zeros(b, dtype=i32, device=dev)
     points = torch.zeros(b, max_points, 2, dtype=torch.float32, device=dev)
     point_counts = torch.zeros(b, dtype=i32, device=dev)
-    bd = grid.boundaries
     _lib.check(lib.nfopp_grid_shorten_paths(
         _lib.ptr(dist2, i32), rows, cols, _lib.ptr(cells, i32), _lib.ptr(counts, i32), _lib.ptr(status, i32),
-        _lib.ptr(cells2, i32), b, max_len, int(lookahead), _lib.ptr(anchors, i32), _lib.ptr(anchor_counts, i32), bd[0], bd[2],
-        grid.resolution, max_points, _lib.ptr(points), _lib.ptr(point_counts, i32), _lib.stream_ptr()))
+        _lib.ptr(cells2, i32), b, max_len, int(lookahead), _lib.ptr(anchors, i32), _lib.ptr(anchor_counts, i32),
+        *grid.origin_resolution, max_points, _lib.ptr(points), _lib.ptr(point_counts, i32), _lib.stream_ptr()))
     return points, point_counts, anchors, anchor_counts
 
 
@@ -359,15 +279,12 @@ def shorten_paths(grid, cells, counts, status, cells2=None, lookahead=256, max_p
     which is computed once per grid."""
     if int(lookahead) < 1:
         raise ValueError("lookahead must be at least 1")
-    i32 = torch.int32
     dev = grid.occupancy.device
-    cells = torch.as_tensor(cells, dtype=i32, device=dev).contiguous()
-    counts = torch.as_tensor(counts, dtype=i32, device=dev).contiguous()
-    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
+    cells, counts, status = int32_on(dev, cells, counts, status)
     if cells.dim() != 3 or cells.shape[2] != 2 or counts.shape != (cells.shape[0],) or status.shape != counts.shape:
         raise ValueError("cells must be [B, max_len, 2], counts and status [B]")
     if cells2 is not None:
-        cells2 = torch.as_tensor(cells2, dtype=i32, device=dev).contiguous()
+        cells2, = int32_on(dev, cells2)
         if cells2.shape != counts.shape:
             raise ValueError("cells2 must be [B]")
         if bool((cells2 < 0).any()):
@@ -380,24 +297,14 @@ def seed_polylines(grid, points, point_counts, status, starts, goals, n_waypoint
     trajectories, with the arithmetic of seed_trajectories (which forms the points from cell centres).  points fp32
     [B, max_len, 2] xy in metres; rows with status != 0 or a count outside 1..max_len get the straight line."""
     lib = _lib.load()
-    starts, goals = _as_device_points(grid, starts), _as_device_points(grid, goals)
-    b, d = starts.shape
-    dev = starts.device
-    i32 = torch.int32
-    points = torch.as_tensor(points, dtype=torch.float32, device=dev).contiguous()
-    point_counts = torch.as_tensor(point_counts, dtype=i32, device=dev).contiguous()
-    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
-    if points.dim() != 3 or points.shape[0] != b or points.shape[2] != 2:
+    starts, goals = as_device_points(grid, starts), as_device_points(grid, goals)
+    points = torch.as_tensor(points, dtype=torch.float32, device=starts.device).contiguous()
+    point_counts, status = int32_on(starts.device, point_counts, status)
+    if points.dim() != 3 or points.shape[0] != starts.shape[0] or points.shape[2] != 2:
         raise ValueError("points must be [B, max_len, 2]")
-    max_len = points.shape[1]
-    out = _seed_out(b, n_waypoints, d, dev, out)
-    ws_bytes = lib.nfopp_grid_seed_workspace_bytes(b, max_len)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
-    _lib.check(lib.nfopp_grid_seed_polylines(
-        _lib.ptr(points), _lib.ptr(point_counts, i32), _lib.ptr(status, i32), b, max_len, _lib.ptr(starts), _lib.ptr(goals),
-        int(n_waypoints), d, 1 if (init_angles_with_trajectory and d == 3) else 0, _lib.ptr(out),
-        _lib.ptr(ws, torch.float64) if ws is not None else None, ws_bytes, _lib.stream_ptr()))
-    return out.view(b, int(n_waypoints), d)
+    directed = 1 if (init_angles_with_trajectory and starts.shape[1] == 3) else 0
+    return seed_launch(lib.nfopp_grid_seed_workspace_bytes, lib.nfopp_grid_seed_polylines, [points], point_counts, status, starts,
+                       goals, n_waypoints, (starts.shape[1], directed), out)
 
 
 def grid_search_init(grid, starts, goals, n_waypoints, init_angles_with_trajectory=False, out=None, clearance=None,

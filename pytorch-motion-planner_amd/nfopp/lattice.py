@@ -15,7 +15,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grid_search import OccupancyGrid, _as_device_points, _cell_centres, _seed_out, seed_trajectories
+from ._grid import (GridFrame, as_device_points, cell_centres, cell_keys, checker_boundaries, checker_device, goal_table, int32_on,
+                    seed_launch, traced_search, workspace)
+from .grid_search import seed_trajectories
 
 HEADINGS = 8
 GOAL_HEADING_MODES = ("fixed", "free")
@@ -29,10 +31,9 @@ def heading_index(theta):
     return torch.where(torch.isfinite(t), idx, torch.full_like(idx, -1.0)).to(torch.int32)
 
 
-class LatticeGrid(object):
+class LatticeGrid(GridFrame):
     """uint8 occupancy layers [L, rows = y cells, cols = x cells] with L = 1 or 8 (non-zero = blocked; state (cell, h) reads
-    layer h mod L) and the geometry of OccupancyGrid: cell of a point = floor((x - b0) / resolution), cell centre =
-    j * resolution + resolution / 2 + b0."""
+    layer h mod L) and the geometry of OccupancyGrid (GridFrame: `cells_of`, `cell_centres`)."""
 
     def __init__(self, layers, boundaries, resolution, device="cuda"):
         if torch.is_tensor(layers) and not layers.is_cuda:
@@ -47,12 +48,7 @@ class LatticeGrid(object):
             dev_layers, shape = None, host.shape
         if len(shape) != 3 or shape[0] not in (1, HEADINGS) or shape[1] < 1 or shape[2] < 1:
             raise ValueError("layers must be a non-empty [L, rows, cols] array with L = 1 or 8")
-        self.boundaries = tuple(float(b) for b in boundaries)
-        if len(self.boundaries) != 4:
-            raise ValueError("boundaries must be (x0, x1, y0, y1)")
-        self.resolution = float(resolution)
-        if not self.resolution > 0:
-            raise ValueError("resolution must be positive")
+        GridFrame.__init__(self, boundaries, resolution, four_sides=True)
         self._layers_host, self._layers_dev = host, None
         self.device = device
         if dev_layers is not None:
@@ -98,21 +94,14 @@ class LatticeGrid(object):
             raise TypeError("from_checker() needs a resolution")
         if not hasattr(checker, "labels"):
             raise TypeError("LatticeGrid.from_checker needs a device checker (one with `labels`)")
-        if boundaries is None:
-            boundaries = checker.get_boundaries() if hasattr(checker, "get_boundaries") else getattr(checker, "boundaries", None)
-        if boundaries is None:
-            raise ValueError("the checker carries no boundaries: pass boundaries=(x0, x1, y0, y1)")
-        boundaries = tuple(float(b) for b in boundaries)
-        x, y, x_cells, y_cells = _cell_centres(boundaries, resolution)
-        dev = device or getattr(getattr(checker, "grid", None), "device", None) or \
-            getattr(getattr(checker, "obstacles", None), "device", None) or "cuda"
+        boundaries = checker_boundaries(checker, boundaries)
+        x, y, x_cells, y_cells = cell_centres(boundaries, resolution)
+        dev = checker_device(checker, device)
         xy = np.stack([x, y], 1).astype(np.float32)
         poses = np.concatenate([np.concatenate([xy, np.full((len(xy), 1), np.float32(h * np.pi / 4), np.float32)], 1)
                                 for h in range(HEADINGS)], 0)
         labels = checker.labels(torch.tensor(poses, device=dev))
         return cls((labels > 0).to(torch.uint8).reshape(HEADINGS, y_cells, x_cells), boundaries, resolution)
-
-    cells_of = OccupancyGrid.cells_of
 
     def states_of(self, points, free_heading=False):
         """[B, 3] device poses -> int32 [B, 3] (row, col, heading index); heading -1 everywhere with `free_heading`."""
@@ -147,18 +136,16 @@ def _fields(lgrid, goal_states, costs, gear_layers):
     _check_bound(lgrid, costs, gear_layers)
     layers = lgrid.layers
     rows, cols = lgrid.shape
-    goal_states = torch.as_tensor(goal_states, device=layers.device).to(torch.int32).contiguous()
+    goal_states, = int32_on(layers.device, goal_states)
     if goal_states.dim() != 2 or goal_states.shape[1] != 3:
         raise ValueError("goal_states must be [G, 3] (row, col, heading)")
     g = goal_states.shape[0]
     fields = torch.empty((g,) + (2,) * (gear_layers - 1) + (HEADINGS, rows, cols, 2), dtype=torch.int32, device=layers.device)
     query, entry = ((lib.nfopp_lattice_fields_workspace_bytes, lib.nfopp_lattice_distance_fields) if gear_layers == 1 else
                     (lib.nfopp_lattice_gear_fields_workspace_bytes, lib.nfopp_lattice_gear_distance_fields))
-    ws_bytes = query(rows, cols, *costs, g)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=layers.device) if ws_bytes else None
+    ws = workspace(query(rows, cols, *costs, g), layers.device)
     _lib.check(entry(_lib.ptr(layers, torch.uint8), lgrid.n_layers, rows, cols, _lib.ptr(goal_states, torch.int32), g, *costs,
-                     _lib.ptr(fields, torch.int32), _lib.ptr(ws, torch.int64) if ws is not None else None, ws_bytes,
-                     _lib.stream_ptr()))
+                     _lib.ptr(fields, torch.int32), ws.ptr, ws.nbytes, _lib.stream_ptr()))
     return fields
 
 
@@ -189,64 +176,35 @@ def _search(lgrid, starts, goals, turn_cost, goal_heading, max_field_bytes, gear
     else:
         costs, trace_entry, gear_layers = _gear_costs(turn_cost, *gear_costs), lib.nfopp_lattice_gear_trace_paths, 2
     _check_bound(lgrid, costs, gear_layers)
-    starts, goals = _as_device_points(lgrid, starts), _as_device_points(lgrid, goals)
+    starts, goals = as_device_points(lgrid, starts), as_device_points(lgrid, goals)
     if starts.shape != goals.shape or starts.shape[1] != 3:
         raise ValueError("starts and goals must both be [B, 3] poses (x, y, theta)")
     rows, cols = lgrid.shape
     b = starts.shape[0]
-    dev = starts.device
     i32 = torch.int32
     start_states = lgrid.states_of(starts)
     goal_states = lgrid.states_of(goals, free_heading=goal_heading == "free")
-    # problems that share a goal state share a field
-    gr, gc, gh = goal_states[:, 0].long(), goal_states[:, 1].long(), goal_states[:, 2].long()
-    inside = (gr >= 0) & (gr < rows) & (gc >= 0) & (gc < cols)
-    key = torch.where(inside, (gr * cols + gc) * (HEADINGS + 1) + gh + 1, torch.full_like(gr, -1))
-    uniq, inverse = torch.unique(key, return_inverse=True)
-    if uniq.numel() and int(uniq[0]) < 0:
-        uniq, inverse = uniq[1:], inverse - 1
-    field_index = inverse.to(i32).contiguous()
+    # the key of a goal: (flat cell index, heading + 1), the heading -1 .. 7 in the low digit
+    inside, flat = cell_keys(goal_states, lgrid.shape)
+    key = flat * (HEADINGS + 1) + goal_states[:, 2].long() + 1
+    uniq, field_index = goal_table(torch.where(inside, key, torch.full_like(key, -1)))
     cell = uniq // (HEADINGS + 1)
     unique_states = torch.stack([cell // cols, cell % cols, uniq % (HEADINGS + 1) - 1], 1).to(i32).contiguous()
     n_total = unique_states.shape[0]
     per_field = gear_layers * HEADINGS * rows * cols * 8
-    chunk = max(1, int(max_field_bytes) // per_field)
-    count = torch.zeros(b, dtype=i32, device=dev)
-    status = torch.zeros(b, dtype=i32, device=dev)
-    cost = torch.zeros(b, 2, dtype=i32, device=dev)
-    cells = torch.zeros(b, 1, 2, dtype=i32, device=dev)
-    headings = torch.zeros(b, 1, dtype=i32, device=dev)
-    gears = torch.zeros(b, 1, dtype=i32, device=dev)
 
-    def trace(fields, first, max_len):
-        n = 0 if fields is None else fields.shape[0]
-        paths = [cells, headings] + ([gears] if gear_layers == 2 else [])   # the gear trace writes `gears` behind the headings
+    def trace(fields, first, paths, count, status, cost):
+        # the gear trace writes `gears` behind the headings: its third path tensor
         _lib.check(trace_entry(
-            _lib.ptr(fields, i32) if n else None, first, n, n_total, rows, cols, *costs, _lib.ptr(start_states, i32),
-            _lib.ptr(goal_states, i32), _lib.ptr(field_index, i32), b, max_len,
-            *[_lib.ptr(t, i32) if max_len else None for t in paths], _lib.ptr(count, i32), _lib.ptr(status, i32),
+            _lib.ptr(fields, i32), first, 0 if fields is None else fields.shape[0], n_total, rows, cols, *costs,
+            _lib.ptr(start_states, i32), _lib.ptr(goal_states, i32), _lib.ptr(field_index, i32), b, paths[0].shape[1] if paths else 0,
+            *[_lib.ptr(t, i32) for t in paths or (None,) * (1 + gear_layers)], _lib.ptr(count, i32), _lib.ptr(status, i32),
             _lib.ptr(cost, i32), _lib.stream_ptr()))
 
-    def result():
-        return (cells, headings, count, status, cost, starts, goals) + ((gears,) if gear_layers == 2 else ())
-
-    if b == 0:
-        return result()
-    if n_total == 0:
-        trace(None, 0, 0)   # every goal is outside the grid: status 2 throughout
-    # one sizing pass and one count.max() per chunk of fields: a single chunk (the usual case) costs the one read-back of the
-    # 8-connected search; counts of earlier chunks stay in `count`, so the maximum never falls
-    for first in range(0, n_total, chunk):
-        fields = _fields(lgrid, unique_states[first:first + chunk], costs, gear_layers)
-        trace(fields, first, 0)
-        max_len = max(int(count.max()), 1)
-        if max_len > cells.shape[1]:
-            grow = max_len - cells.shape[1]
-            cells = torch.nn.functional.pad(cells, (0, 0, 0, grow)).contiguous()
-            headings = torch.nn.functional.pad(headings, (0, grow)).contiguous()
-            gears = torch.nn.functional.pad(gears, (0, grow)).contiguous()
-        trace(fields, first, cells.shape[1])
-    return result()
+    paths, count, status, cost = traced_search(
+        b, starts.device, n_total, max(1, int(max_field_bytes) // per_field), ((2,), ()) + ((),) * (gear_layers - 1),
+        lambda first, last: _fields(lgrid, unique_states[first:last], costs, gear_layers), trace)
+    return (paths[0], paths[1], count, status, cost, starts, goals) + tuple(paths[2:])
 
 
 def lattice_search_paths(lgrid, starts, goals, turn_cost=0, goal_heading="fixed", max_field_bytes=2 ** 30):
@@ -283,29 +241,16 @@ def seed_lattice_trajectories(lgrid, cells, headings, count, status, starts, goa
     same cells, theta the body heading of the lattice states, unwound and interpolated over the spline's parameter.  A
     problem with status != 0 gets the straight line of `init_trajectories(..., False)`."""
     lib = _lib.load()
-    starts, goals = _as_device_points(lgrid, starts), _as_device_points(lgrid, goals)
+    starts, goals = as_device_points(lgrid, starts), as_device_points(lgrid, goals)
     if starts.shape != goals.shape or starts.shape[1] != 3:
         raise ValueError("starts and goals must both be [B, 3] poses (x, y, theta)")
     b = starts.shape[0]
-    dev = starts.device
-    i32 = torch.int32
-    cells = torch.as_tensor(cells, dtype=i32, device=dev).contiguous()
-    headings = torch.as_tensor(headings, dtype=i32, device=dev).contiguous()
-    count = torch.as_tensor(count, dtype=i32, device=dev).contiguous()
-    status = torch.as_tensor(status, dtype=i32, device=dev).contiguous()
+    cells, headings, count, status = int32_on(starts.device, cells, headings, count, status)
     if cells.dim() != 3 or cells.shape[0] != b or cells.shape[2] != 2 or headings.shape != cells.shape[:2] or \
             count.shape != (b,) or status.shape != (b,):
         raise ValueError("cells [B, max_len, 2], headings [B, max_len], count [B] and status [B] must agree with the poses")
-    max_len = cells.shape[1]
-    out = _seed_out(b, n_waypoints, 3, dev, out)
-    ws_bytes = lib.nfopp_lattice_seed_workspace_bytes(b, max_len)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev) if ws_bytes else None
-    bd = lgrid.boundaries
-    _lib.check(lib.nfopp_lattice_seed_trajectories(
-        _lib.ptr(cells, i32), _lib.ptr(headings, i32), _lib.ptr(count, i32), _lib.ptr(status, i32), b, max_len, _lib.ptr(starts),
-        _lib.ptr(goals), int(n_waypoints), bd[0], bd[2], lgrid.resolution, _lib.ptr(out),
-        _lib.ptr(ws, torch.float64) if ws is not None else None, ws_bytes, _lib.stream_ptr()))
-    return out.view(b, int(n_waypoints), 3)
+    return seed_launch(lib.nfopp_lattice_seed_workspace_bytes, lib.nfopp_lattice_seed_trajectories, [cells, headings], count, status,
+                       starts, goals, n_waypoints, lgrid.origin_resolution, out)
 
 
 def gear_changes(gears, count, status):

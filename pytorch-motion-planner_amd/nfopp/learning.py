@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import workspace
 
 
 def _f4(values):
@@ -112,13 +113,12 @@ class _PointCloudChecker(object):
         size = np.float32(max(reach * 1.001, float((hi - lo).max()) / 64.0))
         nx, ny = (int(np.floor((hi[k] - lo[k]) / size)) + 1 for k in (0, 1))
         lib = _lib.load()
-        nbytes = lib.nfopp_cell_index_workspace_bytes(n)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+        ws = workspace(lib.nfopp_cell_index_workspace_bytes(n), pts.device)
         ordered = torch.empty_like(pts)
         start = torch.empty(nx * ny + 1, dtype=torch.int32, device=pts.device)
         _lib.check(lib.nfopp_build_cell_index(_lib.ptr(pts), n, float(lo[0]), float(lo[1]), float(size), nx, ny,
-                                              _lib.ptr(ordered), _lib.ptr(start, torch.int32), _lib.ptr(work, torch.uint8),
-                                              nbytes, _lib.stream_ptr()))
+                                              _lib.ptr(ordered), _lib.ptr(start, torch.int32), ws.ptr, ws.nbytes,
+                                              _lib.stream_ptr()))
         self.obstacles = ordered
         self.cells = (start, nx, ny, float(lo[0]), float(lo[1]), float(size))
 

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import workspace
 from ._tracks import check_tracks, hip_device, per_row, raw_ptr
 
 # values of FleetSchedule.status (NFOPP_SCHEDULE_*)
@@ -129,12 +130,11 @@ def fleet_shift_masks(tracks, *, max_delay, radius=0.0, margin=0.0, obstacles=No
     pair = torch.empty(b, b, 2, dtype=torch.int64, device=device)
     base = torch.empty(b, dtype=torch.int64, device=device)
     bad = torch.empty(b, dtype=torch.int32, device=device)
-    nbytes = int(lib.nfopp_fleet_shift_masks_workspace_bytes(b, m))
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    ws = workspace(lib.nfopp_fleet_shift_masks_workspace_bytes(b, m), device)
     _lib.check(lib.nfopp_fleet_shift_masks(
         raw_ptr(tracks), b, stride, k, _lib.ptr(radius), float(margin), max_delay, raw_ptr(obstacles) if m else None, m, stride_o,
         _lib.ptr(obstacle_radius) if m else None, _lib.ptr(pair, torch.int64), _lib.ptr(base, torch.int64), _lib.ptr(bad, torch.int32),
-        _lib.ptr(workspace, torch.uint8), nbytes, _lib.stream_ptr()))
+        ws.ptr, ws.nbytes, _lib.stream_ptr()))
     return FleetMasks(pair, base, bad, max_delay)
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import int32_on, workspace
 from ._tracks import check_tracks, per_row, raw_ptr
 
 # values of SpaceTimePlan.status (NFOPP_SPACETIME_*)
@@ -88,13 +89,11 @@ class SpaceTimeReservation(object):
                 raise ValueError("visible must be [M] = [%d], got %d values" % (m, visible.numel()))
         lib = _lib.load()
         rows, cols = self.grid.shape
-        b = self.grid.boundaries
-        nbytes = int(lib.nfopp_spacetime_reserve_workspace_bytes(m))
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        ws = workspace(lib.nfopp_spacetime_reserve_workspace_bytes(m), device)
         _lib.check(lib.nfopp_spacetime_reserve(
-            rows, cols, self.count, b[0], b[2], self.grid.resolution, self.robot_radius, self.margin, raw_ptr(tracks) if m else None, m,
+            rows, cols, self.count, *self.grid.origin_resolution, self.robot_radius, self.margin, raw_ptr(tracks) if m else None, m,
             stride, _lib.ptr(radius), _lib.ptr(visible, torch.uint8), _lib.ptr(self.words, torch.int64), self.words.numel() * 8,
-            _lib.ptr(workspace, torch.uint8), nbytes, _lib.stream_ptr()))
+            ws.ptr, ws.nbytes, _lib.stream_ptr()))
         return self
 
 
@@ -126,7 +125,7 @@ def _cells(grid, v, name, device):
         return grid.cells_of(v)
     if v.shape[1] != 2:
         raise ValueError("%s: integer cells are [R, 2] (row, col), got %s" % (name, tuple(v.shape)))
-    return v.to(torch.int32).contiguous()
+    return int32_on(device, v)[0]
 
 
 def spacetime_plan(grid, starts, goals, count, *, robot_radius, margin=0.0, tracks=None, track_radius=None, visible=None, order=None,
@@ -159,19 +158,16 @@ def spacetime_plan(grid, starts, goals, count, *, robot_radius, margin=0.0, trac
             order = torch.from_numpy(np.array(order, np.int64).reshape(-1))
         if order.dim() != 1 or order.numel() != r or order.is_floating_point():
             raise ValueError("order must be [R] = [%d] integers, got %s %s" % (r, tuple(order.shape), order.dtype))
-        order = order.to(device=device, dtype=torch.int32).contiguous()
+        order, = int32_on(device, order)
     lib = _lib.load()
     rows, cols = grid.shape
-    b = grid.boundaries
     i32 = dict(dtype=torch.int32, device=device)
     cells, arrival, status = torch.empty(r, count, **i32), torch.empty(r, **i32), torch.empty(r, **i32)
     out = torch.empty(r, count, 2, dtype=torch.float32, device=device)
-    nbytes = int(lib.nfopp_spacetime_plan_workspace_bytes(rows, cols, count, r))
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    ws = workspace(lib.nfopp_spacetime_plan_workspace_bytes(rows, cols, count, r), device)
     _lib.check(lib.nfopp_spacetime_plan_fleet(
-        _lib.ptr(grid.occupancy, torch.uint8), rows, cols, count, b[0], b[2], grid.resolution, reservation.robot_radius,
+        _lib.ptr(grid.occupancy, torch.uint8), rows, cols, count, *grid.origin_resolution, reservation.robot_radius,
         reservation.margin, _lib.ptr(starts, torch.int32), _lib.ptr(goals, torch.int32), _lib.ptr(order, torch.int32), r,
         _lib.ptr(reservation.words, torch.int64), reservation.words.numel() * 8, _lib.ptr(cells, torch.int32),
-        _lib.ptr(arrival, torch.int32), _lib.ptr(status, torch.int32), _lib.ptr(out), _lib.ptr(workspace, torch.uint8), nbytes,
-        _lib.stream_ptr()))
+        _lib.ptr(arrival, torch.int32), _lib.ptr(status, torch.int32), _lib.ptr(out), ws.ptr, ws.nbytes, _lib.stream_ptr()))
     return SpaceTimePlan(cells, arrival, status, out, reservation)

@@ -25,7 +25,7 @@ class Geometry(object):
         return (self.cols + 63) // 64
 
     def centres(self):
-        """-> (x [cols], y [rows]) fp32: _cell_centres' float64 expression, rounded once."""
+        """-> (x [cols], y [rows]) fp32: cell_centres' float64 expression (nfopp/_grid.py), rounded once."""
         x = np.arange(self.cols) * self.res + self.res / 2 + self.b0
         y = np.arange(self.rows) * self.res + self.res / 2 + self.b2
         return x.astype(F32), y.astype(F32)

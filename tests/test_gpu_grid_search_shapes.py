@@ -407,3 +407,46 @@ def test_end_to_end_on_a_grid_beyond_the_lds_kernel(D):
                 clear = np.abs(np.abs(ang) - np.pi) > 1e-3             # waypoints on the wrap may flip by 2 pi w
                 assert np.abs(traj[i][:, 2].astype(np.float64) - want)[clear].max() < 1e-6, i
         print("D=%d directed=%d: worst xy err / bound %.3f" % (D, directed, worst))
+
+
+# ---- one cell centre for the seeding stage, the any-angle shortening and the space-time search -------------------------------
+def test_the_kernels_share_one_cell_centre():
+    """A free 3 x 65 grid (65 columns: the last cell lies in the second 64-bit word of a reservation row) with boundaries
+    (-0.3, 6.2, 0.2, 0.4) and resolution 0.1; a robot of radius 0 goes from cell (1, 0) to (1, 64) over 65 instants.  Its
+    planned track, the any-angle points of the same 65 cells with lookahead 1 (every cell stays an anchor) and fp32 of the host
+    frame's float64 centres are the same bits, and seeding those points gives what seeding the cells gives: the three kernels
+    and the host form a centre one way (csrc/grid_frame.h, nfopp/_grid.py).
+
+    This pins the sharing, not the `fp contract(off)` pragma of the shared function: a search on the CPU over 6 resolutions x
+    5 origins x 4096 columns found no geometry where a fused multiply-add changes the fp32 centre.  The pragma stays because
+    fractional coordinates and other geometries are not covered by that search."""
+    import spacetime_ref as sr
+    rows, cols, T = 3, 65, 65
+    boundaries, res = (-0.3, 6.2, 0.2, 0.4), 0.1
+    occ = np.zeros((rows, cols), np.uint8)
+    grid = nfopp.OccupancyGrid(occ, boundaries, res, device="cuda")
+    assert grid.cell_counts() == (cols, rows)
+    path = np.stack([np.ones(T, np.int32), np.arange(T, dtype=np.int32)], 1)                # (row, col): (1, h)
+    # the restated rule plans exactly these cells
+    ref = sr.plan_fleet(sr.Reservation(occ, sr.Geometry(rows, cols, boundaries[0], boundaries[2], res), T, 0.0), [[1, 0]], [[1, 64]])
+    assert ref["status"].tolist() == [0] and ref["arrival"].tolist() == [64]
+    assert np.array_equal(ref["cells"][0], path[:, 0] * cols + path[:, 1])
+    plan = nfopp.spacetime_plan(grid, _dev([[1, 0]], I32), _dev([[1, 64]], I32), T, robot_radius=0.0)
+    assert plan.status.tolist() == [0] and np.array_equal(plan.cells[0].cpu().numpy(), ref["cells"][0])
+    tracks = plan.tracks[0].cpu().numpy()
+    cells, count, status = _dev(path[None], I32), _dev([T], I32), _dev([0], I32)
+    points, point_counts, anchors, anchor_counts = nfopp.shorten_paths(grid, cells, count, status, lookahead=1)
+    assert point_counts.tolist() == [T] and anchor_counts.tolist() == [T] and anchors[0].tolist() == list(range(T))
+    x, y, x_cells, _ = grid.cell_centres()
+    flat = path[:, 0] * x_cells + path[:, 1]
+    want = np.stack([x[flat], y[flat]], 1).astype(F32)
+    assert tracks.dtype == F32 and tracks.shape == (T, 2)
+    assert tracks.tobytes() == want.tobytes()
+    assert points[0].cpu().numpy().tobytes() == want.tobytes()
+    assert np.array_equal(tracks, ref["tracks"][0])
+    starts, goals = _dev([[-0.27, 0.33]]), _dev([[6.13, 0.31]])
+    assert grid.cells_of(starts).tolist() == [[1, 0]] and grid.cells_of(goals).tolist() == [[1, 64]]
+    from_points = nfopp.seed_polylines(grid, points, point_counts, status, starts, goals, 8)
+    from_cells = nfopp.seed_trajectories(grid, cells, count, status, starts, goals, 8)
+    assert from_cells.shape == (1, 8, 2) and torch.isfinite(from_cells).all()
+    assert from_points.cpu().numpy().tobytes() == from_cells.cpu().numpy().tobytes()

@@ -421,7 +421,7 @@ def test_pack_rows_layout():
     geo = sr.Geometry(2, 3, -0.3, 0.2, 0.1)
     x, y = geo.centres()
     assert x.dtype == F32 and np.array_equal(x, (np.arange(3) * 0.1 + 0.1 / 2 + -0.3).astype(F32)) and np.array_equal(geo.centre_of(1, 2), [x[2], y[1]])
-    gx, gy, _, _ = nfopp.grid_search._cell_centres((-0.3, 0.0, 0.2, 0.4), 0.1)
+    gx, gy, _, _ = nfopp._grid.cell_centres((-0.3, 0.0, 0.2, 0.4), 0.1)
     assert np.array_equal(gx[:3].astype(F32), x)
 
 

@@ -23,13 +23,13 @@ for p in (ROOT, os.path.join(ROOT, "pytorch-motion-planner_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 import nfopp  # noqa: E402
-from nfopp import grid_search as gs  # noqa: E402
+from nfopp import _grid, grid_search as gs  # noqa: E402
 import bench  # noqa: E402
 
 
 def stage_times(grid, starts, goals, n, repeats=5):
     """Median ms of (fields, trace, seeding) by events; the goal-cell bookkeeping in torch is outside the three."""
-    starts, goals = gs._as_device_points(grid, starts), gs._as_device_points(grid, goals)
+    starts, goals = _grid.as_device_points(grid, starts), _grid.as_device_points(grid, goals)
     rows, cols = grid.shape
     goal_cells = grid.cells_of(goals)
     uniq = torch.unique(goal_cells[:, 0].long() * cols + goal_cells[:, 1].long())
