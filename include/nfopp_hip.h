@@ -996,6 +996,102 @@ int nfopp_track_conflicts(const float* tracks_a_dev, int64_t ba, int32_t stride_
                           double* pair_gap_dev, double* pair_first_dev, void* workspace_dev, size_t workspace_bytes,
                           void* stream);
 
+/* ---- conflicts between timed SE(2) tracks of oriented boxes (csrc/box_conflict.hip), additive under ABI 6 --------------------
+ * nfopp_track_conflicts sees every robot as a disc; a car is a box that drives along its heading, and two of them pass in
+ * neighbouring lanes long before their circumscribed discs do.  These entries check box against box over time: the separation
+ * of the boxes at the instants, a Lipschitz certificate for what lies between two instants (the form of the static swept
+ * check), and bisection of what the certificate leaves undecided.  Float64 with every operation rounded on its own; after the
+ * headings pass only +, -, *, /, sqrt and comparisons, so the device is compared bit for bit with the numpy restatement in
+ * tests/box_conflict_ref.py when that is given the device's unit vectors.  No float atomics, no float sums: the same bits run
+ * after run.
+ *
+ * nfopp_track_headings.  tracks_dev [batch, k, stride >= 3] fp32, x, y, theta first in a row (the states of
+ *   nfopp_path_time_sample for SE(2) as they are) -> heading_dev [batch, k, 2] float64 (cos theta, sin theta) of the widened
+ *   theta, NaN for a theta that is not finite.  The only transcendental step of the check; the pair kernel never reads theta.
+ * Tracks.  Instants t_n = t0 + n * dt as for nfopp_track_conflicts.  Between two instants the position is LINEAR IN TIME and the
+ *   heading turns the shorter way at a constant rate.  tracks_b_dev == null is SELF MODE (heading_b_dev, box_b_dev,
+ *   radius_b_dev, bb, stride_b are not read); a non-null tracks_b_dev with bb == 0 is a set of no obstacles.
+ * Shape.  box_a_dev [ba, 4], box_b_dev [bb, 4] fp32: x0, x1, y0, y1 of each track's box in its body frame, x0 < x1, y0 < y1 (a
+ *   zero-size box is not allowed: a disc is a small box plus a rounding radius, or goes to nfopp_track_conflicts).
+ *   radius_a_dev [ba], radius_b_dev [bb] fp32, null = 0: the rounding radius r >= 0.  reach = fl32(fl32(sqrt(mx * mx + my * my))
+ *   * 1.000001f) with mx = max(|x0|, |x1|), my = max(|y0|, |y1|) widened to float64: box_reach of the static checkers with
+ *   hypotf written as the rounded float64 root.  R_ij = (r_i + r_j) + margin as for nfopp_track_conflicts;
+ *   D_ij = (reach_i + reach_j) + R_ij, D2_ij = D_ij * D_ij.
+ * Bad tracks.  A non-finite x, y, unit vector, box entry or radius, x0 >= x1, y0 >= y1 or r < 0 make a track BAD: nobody's
+ *   partner, its summary row NaN with status NFOPP_CONFLICT_BAD_TRACK, its pair rows and columns NFOPP_BOX_PAIR_BAD / NaN (the
+ *   diagonal entry in self mode included).
+ * Separation at an instant, poses P_i = (p_i, u_i), P_j = (p_j, u_j), u = (c, s):
+ *     d = p_j - p_i;  cr = ci * cj + si * sj,  sr = ci * sj - si * cj
+ *     xi = dx * ci + dy * si,  yi = dy * ci - dx * si;  xj = -(dx * cj + dy * sj),  yj = -(dy * cj - dx * sj)
+ *     gap(t, box, cx, cy, s0, s1):  a0 = box.x0 * cx, a1 = box.x1 * cx, b0 = box.y0 * cy, b1 = box.y1 * cy,
+ *       lo = (t + min(a0, a1)) + min(b0, b1),  hi = (t + max(a0, a1)) + max(b0, b1),  max(lo - s1, s0 - hi)
+ *     g1 = gap(xi, box_j, cr, -sr, x0_i, x1_i),  g2 = gap(yi, box_j, sr, cr, y0_i, y1_i)
+ *     g3 = gap(xj, box_i, cr, sr, x0_j, x1_j),   g4 = gap(yj, box_i, -sr, cr, y0_j, y1_j)
+ *     sep = max(max(g1, g2), max(g3, g4))        with max(a, b) = a > b ? a : b and min(a, b) = a < b ? a : b
+ *   -- the largest gap over the four face axes (the separating-axis test): sep < 0 iff the open boxes intersect, and sep never
+ *   exceeds the distance between the boxes.
+ * A sub-interval [a, b] -- an interval of the grid or a dyadic part of one -- with poses P at a and Q at b.  In this order:
+ *     1. d0 = p_i - p_j at a, d1 at b, c = |d0|^2, e = |d1|^2, and (a, b, s, m) the closest approach of nfopp_track_conflicts'
+ *        rule on them.  m >= D2: FREE (the discs of radius reach cover the boxes at every heading; this step is part of the
+ *        rule: it decides cases step 3 cannot).
+ *     2. sa = sep at a.  sa - R < 0: CONFLICT at a (strict).
+ *     3. sb = sep at b;  ni = sqrt(|Q_i.u - P_i.u|^2), nj likewise;  mot = sqrt(a) + H * (reach_i * ni + reach_j * nj) with H
+ *        the float64 next above pi / 2 (0x1.921fb54442d19p+0).  ((sa + sb) - mot) * 0.5 - R >= 0: FREE.  The certificate: the
+ *        distance f between the rounded boxes changes no faster than the relative position moves plus reach times the angle
+ *        each box turns; an angle phi <= pi is at most (pi / 2) * 2 sin(phi / 2), its chord; so over the sub-interval
+ *        f >= max(f_a - lambda * mot, f_b - (1 - lambda) * mot) >= (f_a + f_b - mot) / 2, and f >= sep.
+ *     4. depth < refine, and li = sqrt(|P_i.u + Q_i.u|^2) != 0 and lj != 0: split at the mid pose, p = (p_a + p_b) * 0.5 and
+ *        u = (P.u + Q.u) / l (the exact middle of the shorter turn); the left half first, then the right half.  A zero sum is
+ *        a turn of exactly pi, whose direction is not defined.
+ *     5. Otherwise UNDECIDED at a.
+ * A pair.  The intervals in time order, then one term for the last instant: with d = p_i - p_j there, unless |d|^2 >= D2 (the
+ *   discs, as in step 1), sep_{k-1} - R < 0 is a CONFLICT at t_{k-1} (the whole check when k = 1).  The walk stops at the first CONFLICT: first_ij is its time, +inf if none; undecided_ij is the
+ *   time of the first UNDECIDED met before it, +inf if none.  The node at depth d and position pos of interval n has the time
+ *   t_n + (pos / 2^d) * dt, an exact dyadic fraction.  Status: NFOPP_BOX_PAIR_CONFLICT when first < inf, else
+ *   NFOPP_BOX_PAIR_UNDECIDED when undecided < inf, else NFOPP_BOX_PAIR_FREE.  Raising `refine` only splits what was UNDECIDED.
+ *   FREE says that the rounded boxes stay R apart between the instants under the motion model above; CONFLICT says sep < R at
+ *   the reported time; continuous-time exactness beyond the certificate is not claimed.
+ * Self mode evaluates i < j with i as the first box and COPIES the result to (j, i): the arithmetic is not even in the order of
+ *   the boxes, the matrices are symmetric because they are copied.
+ * summary_dev [ba, NFOPP_NUM_BOX_CONFLICT_SLOTS] float64, over the good partners j of track i:
+ *     FIRST_TIME, FIRST_PARTNER          the lexicographic minimum on (first_ij, j); +inf, -1 if none
+ *     CONFLICTS                          number of partners whose status is CONFLICT
+ *     UNDECIDED_TIME, UNDECIDED_PARTNER  the lexicographic minimum on (undecided_ij, j) over all partners; +inf, -1 if none
+ *     UNDECIDED                          number of partners whose status is UNDECIDED
+ *     STATUS                             0, NFOPP_CONFLICT_BAD_TRACK or NFOPP_CONFLICT_NO_PARTNER
+ *   summary_b_dev [bb, ...] (may be null; not read in self mode): the same from set B's side.
+ * pair_status_dev [ba, bb] int32, pair_first_dev, pair_undecided_dev [ba, bb] float64 (each may be null; self mode: [ba, ba],
+ *   the diagonal FREE, +inf, +inf).
+ * What the motion model costs.  For margin: a point of a box at distance <= reach from its origin, on a robot with speed <= v
+ *   and turn rate <= w, moves at speed <= v + reach * w, so by the bound of nfopp_track_conflicts it stays within
+ *   (v + reach * w) * dt / 2 of where the model puts it: (va + vb) * dt / 2 + (reach_a * wa + reach_b * wb) * dt / 2 in all.
+ * workspace_dev: nfopp_box_track_conflicts_workspace_bytes(ba, bb, k) bytes (bb = 0 in self mode), rewritten by every call.
+ * Everything runs on `stream`; nothing synchronises.  Argument errors, refused before any launch and never clamped: a negative
+ *   batch size or one past 2^31 - 1, k < 1, a stride < 3, refine outside 0 .. NFOPP_BOX_CONFLICT_MAX_REFINE, dt not positive
+ *   and finite, t0 or margin not finite, a null tracks / heading / box / summary pointer with tracks to read, more tiles of
+ *   32 x 32 pairs than a grid holds, a workspace that is null or too small.  ba == 0 returns 0 and writes nothing. */
+#define NFOPP_BOX_CONFLICT_MAX_REFINE 8
+#define NFOPP_BOX_PAIR_BAD (-1)
+#define NFOPP_BOX_PAIR_FREE 0
+#define NFOPP_BOX_PAIR_CONFLICT 1
+#define NFOPP_BOX_PAIR_UNDECIDED 2
+#define NFOPP_NUM_BOX_CONFLICT_SLOTS 7
+#define NFOPP_BOX_CONFLICT_SLOT_FIRST_TIME 0
+#define NFOPP_BOX_CONFLICT_SLOT_FIRST_PARTNER 1
+#define NFOPP_BOX_CONFLICT_SLOT_CONFLICTS 2
+#define NFOPP_BOX_CONFLICT_SLOT_UNDECIDED_TIME 3
+#define NFOPP_BOX_CONFLICT_SLOT_UNDECIDED_PARTNER 4
+#define NFOPP_BOX_CONFLICT_SLOT_UNDECIDED 5
+#define NFOPP_BOX_CONFLICT_SLOT_STATUS 6
+int nfopp_track_headings(const float* tracks_dev, int64_t batch, int32_t stride, int32_t k, double* heading_dev, void* stream);
+size_t nfopp_box_track_conflicts_workspace_bytes(int64_t ba, int64_t bb, int32_t k);
+int nfopp_box_track_conflicts(const float* tracks_a_dev, const double* heading_a_dev, int64_t ba, int32_t stride_a,
+                              const float* tracks_b_dev, const double* heading_b_dev, int64_t bb, int32_t stride_b, int32_t k,
+                              double t0, double dt, const float* box_a_dev, const float* box_b_dev, const float* radius_a_dev,
+                              const float* radius_b_dev, double margin, int32_t refine, double* summary_dev,
+                              double* summary_b_dev, int32_t* pair_status_dev, double* pair_first_dev,
+                              double* pair_undecided_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- prioritised start-delay scheduling of a fleet (csrc/fleet_schedule.hip), additive under ABI 6 ---------------------------
  * nfopp_track_conflicts tells which robots of a fleet are in conflict.  These two entries are the outer step: every robot
  * keeps its path and only WHEN it leaves changes.  In priority order each robot takes the smallest start delay, in steps of

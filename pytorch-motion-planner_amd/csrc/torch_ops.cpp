@@ -431,6 +431,67 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_
   return std::make_tuple(summary, summary_b, pair_gap, pair_first);
 }
 
+// the headings pass of the box check (nfopp_track_headings): tracks [B, K, S >= 3] -> [B, K, 2] float64 (cos theta, sin theta)
+Tensor track_headings(const Tensor& tracks) {
+  const auto [b, k, stride] = check_tracks(tracks, "tracks");
+  TORCH_CHECK(stride >= 3, "nfopp: tracks must be [B, K, >= 3] (x, y, theta)");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks.device());
+  Tensor out = at::empty({b, k, 2}, tracks.options().dtype(at::kDouble));
+  check_status(nfopp_track_headings(b ? tracks.data_ptr<float>() : nullptr, b, stride, (int32_t)k, b ? out.data_ptr<double>() : nullptr,
+                                    stream_of(tracks)));
+  return out;
+}
+
+// conflicts between timed tracks of oriented boxes (nfopp_track_headings, then nfopp_box_track_conflicts): tracks [B, K, S >= 3],
+// box [B, 4] fp32, radius [B] fp32 or None (0) -> (summary [Ba, 7], summary_b [Bb, 7] float64, pair_status [Ba, Bb] int32,
+// pair_first, pair_undecided [Ba, Bb] float64); summary_b is empty in self mode, the pair matrices without want_pairs.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> box_track_conflicts(const Tensor& tracks_a, const OptTensor& tracks_b, double dt,
+                                                                       double t0, const Tensor& box_a, const OptTensor& box_b,
+                                                                       const OptTensor& radius_a, const OptTensor& radius_b,
+                                                                       double margin, int64_t refine, bool want_pairs) {
+  const auto [ba, k, stride_a] = check_tracks(tracks_a, "tracks_a");
+  const bool self = !tracks_b.has_value();
+  int64_t bb = ba;
+  int32_t stride_b = 3;
+  if (!self) {
+    int64_t kb;
+    std::tie(bb, kb, stride_b) = check_tracks(*tracks_b, "tracks_b");
+    same_device(tracks_a, *tracks_b, "tracks_b");
+    TORCH_CHECK(kb == k, "nfopp: tracks_b must be [Bb, K, >= 3] with the K of tracks_a (", k, ")");
+    TORCH_CHECK(box_b.has_value(), "nfopp: tracks_b needs box_b");
+    need(tracks_a, *box_b, "box_b", {bb, 4});
+  }
+  TORCH_CHECK(stride_a >= 3 && stride_b >= 3, "nfopp: box tracks must be [B, K, >= 3] (x, y, theta)");
+  TORCH_CHECK(refine >= 0 && refine <= NFOPP_BOX_CONFLICT_MAX_REFINE, "nfopp: refine must be 0 .. ", NFOPP_BOX_CONFLICT_MAX_REFINE);
+  need(tracks_a, box_a, "box_a", {ba, 4});
+  if (radius_a.has_value()) need(tracks_a, *radius_a, "radius_a", {ba});
+  if (!self && radius_b.has_value()) need(tracks_a, *radius_b, "radius_b", {bb});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks_a.device());
+  const auto f64 = tracks_a.options().dtype(at::kDouble);
+  Tensor heading_a = track_headings(tracks_a);
+  Tensor heading_b = self ? at::empty({0, k, 2}, f64) : track_headings(*tracks_b);
+  Tensor summary = at::empty({ba, NFOPP_NUM_BOX_CONFLICT_SLOTS}, f64);
+  Tensor summary_b = at::empty({self ? 0 : bb, NFOPP_NUM_BOX_CONFLICT_SLOTS}, f64);
+  Tensor pair_status = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, tracks_a.options().dtype(at::kInt));
+  Tensor pair_first = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, f64), pair_undecided = at::empty_like(pair_first);
+  const size_t bytes = nfopp_box_track_conflicts_workspace_bytes(ba, self ? 0 : bb, (int32_t)k);
+  Tensor workspace = byte_workspace(tracks_a, bytes);
+  auto dptr = [](Tensor& t) { return t.numel() ? t.data_ptr<double>() : nullptr; };
+  // a set of no obstacles still needs a non-null tracks_b pointer (null selects self mode); it is never read
+  const float* b_ptr = self ? nullptr : (bb > 0 ? tracks_b->data_ptr<float>() : tracks_a.data_ptr<float>());
+  check_status(nfopp_box_track_conflicts(
+      ba ? tracks_a.data_ptr<float>() : nullptr, dptr(heading_a), ba, stride_a, ba ? b_ptr : nullptr, dptr(heading_b), bb, stride_b,
+      (int32_t)k, t0, dt, ba ? box_a.data_ptr<float>() : nullptr, (!self && bb) ? box_b->data_ptr<float>() : nullptr,
+      opt_ptr<float>(radius_a), self ? nullptr : opt_ptr<float>(radius_b), margin, (int32_t)refine, dptr(summary), dptr(summary_b),
+      pair_status.numel() ? pair_status.data_ptr<int32_t>() : nullptr, dptr(pair_first), dptr(pair_undecided),
+      bytes ? workspace.data_ptr() : nullptr, bytes, stream_of(tracks_a)));
+  if (ba == 0 && summary_b.numel()) {   // the entry writes nothing for an empty set A: every obstacle is without a partner
+    const double inf = std::numeric_limits<double>::infinity();
+    summary_b.copy_(at::tensor({inf, -1.0, 0.0, inf, -1.0, 0.0, (double)NFOPP_CONFLICT_NO_PARTNER}, at::kDouble).expand_as(summary_b));
+  }
+  return std::make_tuple(summary, summary_b, pair_status, pair_first, pair_undecided);
+}
+
 // the shift masks of a fleet (nfopp_fleet_shift_masks): tracks [B, K, S], radius [B] fp32 or None (0), obstacles
 // [M, K + max_delay, So] or None with obstacle_radius [M] or None -> (pair [B, B, 2], base [B]) int64 holding the uint64 words,
 // bad [B] int32
@@ -721,6 +782,9 @@ TORCH_LIBRARY(nfopp, lib) {
           "float dt, int count) -> (Tensor, Tensor)");
   lib.def("track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor? radius_a, Tensor? radius_b, float margin, "
           "bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor)");
+  lib.def("track_headings(Tensor tracks) -> Tensor");
+  lib.def("box_track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor box_a, Tensor? box_b, Tensor? radius_a, "
+          "Tensor? radius_b, float margin, int refine, bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   lib.def("fleet_shift_masks(Tensor tracks, int max_delay, Tensor? radius, float margin, Tensor? obstacles, Tensor? obstacle_radius) -> "
           "(Tensor, Tensor, Tensor)");
   lib.def("fleet_assign_delays(Tensor pair, Tensor base, Tensor bad, Tensor? order, int max_delay) -> (Tensor, Tensor, Tensor)");
@@ -755,6 +819,8 @@ TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
   lib.impl("path_time_profile", &path_time_profile);
   lib.impl("path_time_sample", &path_time_sample);
   lib.impl("track_conflicts", &track_conflicts);
+  lib.impl("track_headings", &track_headings);
+  lib.impl("box_track_conflicts", &box_track_conflicts);
   lib.impl("fleet_shift_masks", &fleet_shift_masks);
   lib.impl("fleet_assign_delays", &fleet_assign_delays);
   lib.impl("spacetime_reserve", &spacetime_reserve);

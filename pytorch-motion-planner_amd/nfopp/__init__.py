@@ -6,8 +6,8 @@ from ._lib import LIB_PATH, NUM_PATH_STATS, PATH_STAT_NAMES, NfoppError, load as
 from .batch import BatchPlanner, OnfFitter, shard_range, straight_line_init
 from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
 from .conflicts import (CONFLICT_BAD_TRACK, CONFLICT_COUNT, CONFLICT_FIRST_PARTNER, CONFLICT_FIRST_TIME, CONFLICT_MIN_GAP,
-                        CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_NO_PARTNER, CONFLICT_STATUS, TrackConflicts,
-                        constant_velocity_tracks, track_conflicts)
+                        CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_NO_PARTNER, CONFLICT_STATUS, BoxTrackConflicts,
+                        TrackConflicts, box_track_conflicts, constant_velocity_tracks, track_conflicts, track_headings)
 from .schedule import (SCHEDULE_BAD_TRACK, SCHEDULE_MAX_DELAY, SCHEDULE_NOT_ORDERED, SCHEDULE_OK, SCHEDULE_UNRESOLVED, FleetMasks,
                        FleetSchedule, delay_tracks, fleet_shift_masks, schedule_delays)
 from .spacetime import (SPACETIME_BAD_CELL, SPACETIME_DIRECTIONS, SPACETIME_NOT_ORDERED, SPACETIME_OK, SPACETIME_UNREACHED,
@@ -46,7 +46,7 @@ __all__ = [
     "TIME_GOAL_UNREACHABLE", "TIME_OUT_OF_RANGE",
     "TrackConflicts", "track_conflicts", "constant_velocity_tracks", "CONFLICT_MIN_GAP", "CONFLICT_MIN_PARTNER",
     "CONFLICT_MIN_TIME", "CONFLICT_FIRST_TIME", "CONFLICT_FIRST_PARTNER", "CONFLICT_COUNT", "CONFLICT_STATUS",
-    "CONFLICT_BAD_TRACK", "CONFLICT_NO_PARTNER",
+    "CONFLICT_BAD_TRACK", "CONFLICT_NO_PARTNER", "BoxTrackConflicts", "box_track_conflicts", "track_headings",
     "FleetMasks", "FleetSchedule", "fleet_shift_masks", "schedule_delays", "delay_tracks", "SCHEDULE_OK", "SCHEDULE_BAD_TRACK",
     "SCHEDULE_UNRESOLVED", "SCHEDULE_NOT_ORDERED", "SCHEDULE_MAX_DELAY",
     "SpaceTimePlan", "SpaceTimeReservation", "spacetime_plan", "SPACETIME_OK", "SPACETIME_BAD_CELL", "SPACETIME_UNREACHED",

@@ -18,6 +18,8 @@ PATH_STAT_NAMES = ("length", "max_curvature", "curvature_at", "cusps", "reversal
 NUM_TIME_SLOTS = 4      # NFOPP_NUM_TIME_SLOTS: s, t, v, peak v of the segment that starts at the vertex
 NUM_TIME_SUMMARY = 4    # NFOPP_NUM_TIME_SUMMARY: total time, length, stops, status
 NUM_CONFLICT_SLOTS = 7  # NFOPP_NUM_CONFLICT_SLOTS: min gap, its partner, its time, first conflict time, its partner, conflicts, status
+NUM_BOX_CONFLICT_SLOTS = 7  # NFOPP_NUM_BOX_CONFLICT_SLOTS: first conflict, its partner, conflicts, first undecided, its partner, undecided, status
+BOX_CONFLICT_MAX_REFINE = 8  # NFOPP_BOX_CONFLICT_MAX_REFINE
 SCHEDULE_MAX_DELAY = 63  # NFOPP_SCHEDULE_MAX_DELAY: candidate start delays are 0 .. max_delay <= 63 grid steps
 TERM_NAMES = ("total", "distance", "softplus_sum", "lambda_dot_c", "c_squared", "boundary", "cm_tanh", "direction")
 
@@ -198,6 +200,11 @@ _SIGNATURES = {
     "nfopp_track_conflicts": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, ctypes.c_double,
                                              _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "nfopp_track_headings": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P]),
+    "nfopp_box_track_conflicts_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "nfopp_box_track_conflicts": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int64, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, ctypes.c_double,
+                                                 ctypes.c_int32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "nfopp_fleet_shift_masks_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
     "nfopp_fleet_shift_masks": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_double,
                                                ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P,

@@ -483,19 +483,25 @@ class BatchPlanner(object):
         return time_parametrize(traj, eng.start, eng.goal, limits, v_start, v_goal)
 
     def fleet_conflicts(self, limits, dt, count, radius, margin="chord", v_start=None, v_goal=None, best=False, obstacles=None,
-                        obstacle_radius=None, obstacle_v_max=None, want_pairs=False):
+                        obstacle_radius=None, obstacle_v_max=None, want_pairs=False, box=None, refine=0, obstacle_box=None,
+                        obstacle_w_max=None):
         """The B paths as B robots that start together on one floor: time-parametrise under `limits`, sample at k * dt
         (k < count) and check every robot against every other (nfopp.TrackConflicts: `.summary` [B, 7]).  `radius`: a
         number or [B]; `margin="chord"` covers what a robot can do between two instants.  With `obstacles` [M, count, >= 2]
         (predicted tracks on the same grid, e.g. `nfopp.constant_velocity_tracks`) the paths are also checked against
         those, and the result is the pair (fleet, against obstacles); the chord margin then needs `obstacle_v_max`.
-        Nothing here synchronises with device-tensor arguments."""
+        With `box` (x0, x1, y0, y1) the robots are oriented boxes (nfopp.BoxTrackConflicts; `radius` rounds them, `refine`
+        halves undecided intervals, obstacles carry x, y, theta and take `obstacle_box` / `obstacle_w_max`): see
+        `TimedPaths.conflicts`.  Nothing here synchronises with device-tensor arguments."""
         timed = self.timed_paths(limits, v_start=v_start, v_goal=v_goal, best=best)
-        fleet = timed.conflicts(dt, count, radius=radius, margin=margin, want_pairs=want_pairs)
+        shape = {} if box is None and refine == 0 and obstacle_box is None else dict(box=box, refine=refine)
+        fleet = timed.conflicts(dt, count, radius=radius, margin=margin, want_pairs=want_pairs, **shape)
         if obstacles is None:
             return fleet
+        if shape:
+            shape.update(other_box=obstacle_box, other_w_max=obstacle_w_max)
         return fleet, timed.conflicts(dt, count, other=obstacles, radius=radius, other_radius=obstacle_radius, margin=margin,
-                                      other_v_max=obstacle_v_max, want_pairs=want_pairs)
+                                      other_v_max=obstacle_v_max, want_pairs=want_pairs, **shape)
 
     def fleet_schedule(self, limits, dt, count, radius, max_delay, margin="chord", order=None, best=False, obstacles=None,
                        obstacle_radius=None, obstacle_v_max=None, v_start=None, v_goal=None, replan=None):

@@ -47,6 +47,18 @@ def _chord_margin_or_number(margin, v_self, v_other, dt):
     return chord_margin(v_self, v_other, dt)
 
 
+def _box_turn_margin(box, w_max, dt):
+    """The rotation term of the chord margin for one side: reach * w_max * dt / 2, reach the farthest corner of the largest
+    of the side's boxes (host values: one box or [B, 4])."""
+    from .conflicts import box_reach
+    if isinstance(box, torch.Tensor):
+        raise ValueError("margin=\"chord\" needs the boxes as host values; give a number for boxes held on the device")
+    if w_max is None or not np.isfinite(w_max):
+        raise ValueError("margin=\"chord\" for boxes needs a finite turn-rate limit (MotionLimits.w_max / other_w_max)")
+    reach = max(box_reach(b) for b in np.asarray(box, np.float64).reshape(-1, 4))
+    return reach * float(w_max) * float(dt) / 2.0
+
+
 def _check_paths(traj, start, goal):
     """traj [B, N, D] with N >= 1 and D = 2 or 3, start / goal [B, D]: what the kernels index by."""
     if not all(isinstance(x, torch.Tensor) for x in (traj, start, goal)):
@@ -91,25 +103,47 @@ class TimedPaths(object):
         return (states, segment) if want_segment else states
 
     def conflicts(self, dt, count, other=None, radius=0.0, other_radius=None, margin=0.0, t0=0.0, want_pairs=False,
-                  other_v_max=None):
+                  other_v_max=None, box=None, refine=0, other_box=None, other_w_max=None):
         """The B timed paths as B robots on one floor, sampled at t0 + k * dt (k < count): who comes closer to whom than
         the radii allow, and when first (`nfopp.track_conflicts`, self mode) -> `nfopp.TrackConflicts`.  With `other` -- a
         `TimedPaths`, sampled on the same grid, or a tracks tensor [M, count, >= 2] such as `constant_velocity_tracks`
         returns -- the paths are checked against those tracks instead.  `radius` / `other_radius`: a number or one per track.
         `margin="chord"` is (v_max + the other side's v_max) * dt / 2, what the straight line between two instants can
-        hide; for a tracks tensor it needs `other_v_max`."""
-        from .conflicts import track_conflicts
-        tracks_b, vb = None, self.limits.v_max
+        hide; for a tracks tensor it needs `other_v_max`.
+
+        With `box` -- (x0, x1, y0, y1) in the body frame, or one per path -- the robots are oriented boxes on SE(2) paths
+        (`nfopp.box_track_conflicts` -> `nfopp.BoxTrackConflicts`): `radius` is then the rounding radius, `refine` (0 .. 8)
+        how often an undecided interval is halved, `other_box` the boxes of `other` (default: `box`, which must then be one
+        box), whose tracks carry x, y, theta.  `margin="chord"` gains reach * w_max * dt / 2 per side (reach: the farthest
+        corner of the side's largest box; w_max from the limits, `other_w_max` for a tracks tensor)."""
+        from .conflicts import box_track_conflicts, track_conflicts
+        tracks_b, vb, wb = None, self.limits.v_max, self.limits.w_max
         if isinstance(other, TimedPaths):
-            tracks_b, vb = other.sample(dt, count, t0=t0), other.limits.v_max
+            tracks_b, vb, wb = other.sample(dt, count, t0=t0), other.limits.v_max, other.limits.w_max
         elif other is not None:
-            tracks_b, vb = other, other_v_max
-        margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt)
+            tracks_b, vb, wb = other, other_v_max, other_w_max
+        if box is None:
+            if refine != 0 or other_box is not None:
+                raise ValueError("refine and other_box belong to the box check: give box")
+            margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt)
+            if other is None:
+                return track_conflicts(self.sample(dt, count, t0=t0), dt=dt, t0=t0, radius_a=radius, margin=margin,
+                                       want_pairs=want_pairs)
+            return track_conflicts(self.sample(dt, count, t0=t0), tracks_b, dt=dt, t0=t0, radius_a=radius, radius_b=other_radius,
+                                   margin=margin, want_pairs=want_pairs)
+        if self.traj.shape[2] != 3:
+            raise ValueError("the box check needs SE(2) paths (x, y, theta)")
+        if other is not None and other_box is None:
+            other_box = box
+        if isinstance(margin, str):
+            margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt) + _box_turn_margin(box, self.limits.w_max, dt) + \
+                _box_turn_margin(box if other is None else other_box, wb, dt)
         if other is None:
-            return track_conflicts(self.sample(dt, count, t0=t0), dt=dt, t0=t0, radius_a=radius, margin=margin,
-                                   want_pairs=want_pairs)
-        return track_conflicts(self.sample(dt, count, t0=t0), tracks_b, dt=dt, t0=t0, radius_a=radius, radius_b=other_radius,
-                               margin=margin, want_pairs=want_pairs)
+            return box_track_conflicts(self.sample(dt, count, t0=t0), dt=dt, t0=t0, box_a=box, radius_a=radius, margin=margin,
+                                       refine=refine, want_pairs=want_pairs)
+        return box_track_conflicts(self.sample(dt, count, t0=t0), tracks_b, dt=dt, t0=t0, box_a=box, box_b=other_box,
+                                   radius_a=radius, radius_b=0.0 if other_radius is None else other_radius, margin=margin,
+                                   refine=refine, want_pairs=want_pairs)
 
     def schedule(self, dt, count, max_delay, radius, margin="chord", order=None, other=None, other_radius=None, other_v_max=None):
         """The B timed paths as B robots that may leave late: sampled at k * dt (k < count), every robot gets, in priority

@@ -11,7 +11,7 @@ from . import _lib
 
 TORCH_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libnfopp_torch.so")
 OPS = ("onf_fwd_bwd_input", "onf_logits", "traj_step", "traj_steps", "reparametrize", "update_endpoints", "onf_train_grad", "adam_step", "onf_train_step",
-       "grid_search_init", "path_time_profile", "path_time_sample", "track_conflicts", "fleet_shift_masks", "fleet_assign_delays",
+       "grid_search_init", "path_time_profile", "path_time_sample", "track_conflicts", "track_headings", "box_track_conflicts", "fleet_shift_masks", "fleet_assign_delays",
        "spacetime_reserve", "spacetime_plan_fleet", "lattice_fields", "lattice_trace_paths",
        "lattice_gear_fields", "lattice_gear_trace_paths", "lattice_seed_trajectories")
 _loaded = False
