@@ -31,6 +31,7 @@
 // feature / hidden-unit index ("x32 order": the accumulator layout gives every lane four consecutive positions per
 // register quad, i.e. one 16-byte store) plus the 48-byte record (u, 1, theta | rho | sign words of a2).  dW3[:100] =
 // sum_p rho_p relu(a2_p) is NOT accumulated here: it falls out of G2 in the gather kernel (GatherArgs::x32_order).
+#include <stdint.h>
 #include <string.h>
 
 #include <type_traits>
@@ -74,6 +75,10 @@ constexpr int O_W3A = O_ISA + 224 * 4;         // [128] fp32 W3[:100] by hidden 
 constexpr int O_W3L = O_W3A + 128 * 4;         // [7 kb][2 g][3 levels][4 words]: W3[:100] pre-split in B-fragment order
 constexpr int IMG_BYTES = O_W3L + HK * 2 * 3 * 16;
 static_assert(IMG_BYTES % 16 == 0 && IMG_BYTES <= 160 * 1024, "LDS image");
+// hi -> mid distance of the W2 images: with the largest tile offset of either W2 GEMM it fits the 16-bit offset of a DS read
+constexpr int W2_MID = O_W2M - O_W2H;
+static_assert(O_W2H % 256 == 0 && W2_MID % 256 == 0, "the XOR addressing of the W2 reads passes the image offsets by");
+static_assert(W2_MID + 64 * RS2 + 255 < 65536 && W2_MID + 16 * RS2 * 5 + 255 < 65536, "W2 mid reads: base + immediate");
 
 __host__ __device__ constexpr int pos_of_slot(int s) {
   return 16 * (s >> 4) + 8 * ((s >> 2) & 1) + 4 * ((s >> 3) & 1) + (s & 3);
@@ -187,21 +192,47 @@ __global__ __launch_bounds__(256) void x32_prep_kernel(const OnfGeom geo, const 
   img[idx] = out;
 }
 
+// ---- the pad positions 104 .. 111 ------------------------------------------------------------------------------------
+// Pairs p = 2, 3 of hidden block 6 are positions 104 + 4 g + {0, 1} and 106 + 4 g + {0, 1}: past the last extended row in
+// BOTH lane halves (pair 1 -- 98, 99 | 102, 103 -- is a pad only in the upper half and is computed like any other).  Their
+// level words are the constant 0 and are written as such; what the kernel computed there, and why the bits are the same:
+//  * a1 / a2 at these rows: every A fragment comes from the zero row of the image (row31 / row32 clamp to W1_ZERO /
+//    W2_ZERO) and a zero third level (w1ext / w2ext return 0 past their last row), the accumulator starts from the
+//    literal +0 of the first product, and (+0) + (+-0) = +0 under round-to-nearest: exactly +0 for finite operands.  (A
+//    non-finite pose or weight turns every real position, the logit and the gradient into NaN either way; only the
+//    fit's stored pads h1[104..111] of such a sample would read 0 where they read NaN.)
+//  * h1_item: relu1 is an integer max, relu1(+0) = +0; the mask pushes shift in the top bit of 0 - 0 = 0, i.e. four
+//    pushes are `m1w <<= 4`; the split of (+0, +0) is perm(0, 0) = 0 and 0 - 0 = +0 at every level.  TRAIN stores +0.
+//  * dh2_item: hv = +0, mk = (0 - 0) >> 31 = 0, so the level words w3c & mk are 0 and the sign words take no bit.  The
+//    logit terms are fmaf(w3f, +0, lgs) with w3f = +0 (O_W3A is zero past H): lgs + (+0), which changes lgs only from -0
+//    to +0.  That cannot reach the logit: in the upper lane half pair 1 (positions 102, 103: w3f = +0, hv = +0) has
+//    already run the same two terms on both chains, and the lower half adds the literal +0.0f (`g == 1 ? skipv : 0.0f`)
+//    to lgs[0] + lgs[1], which maps -0 to +0 whichever of the two was -0.
+//  * dh1_item: dv = accd & (mask bit) with the mask bits 0 (pushed as zeros above), so dv = +0 whatever accd holds, and
+//    its split is 0.  TRAIN stores rho * dv, and (+0) * rho is -0 for rho < 0: that product is still formed.
+constexpr bool pad_pair(int kb, int p) { return kb == HK - 1 && p >= 2; }
+static_assert(16 * (HK - 1) + 8 >= W1_ZERO && 16 * (HK - 1) + 8 >= W2_ZERO && 16 * (HK - 1) + 8 >= H, "pairs 2, 3 of the last block are pads");
+
 // ---- device helpers ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ f32x16 mfma32(const u32x4& a, const u32x4& b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ u32x4 lds128(const unsigned char* lds, int byte) {
-  return *reinterpret_cast<const u32x4*>(lds + byte);
+// LDS reads take the BYTE ADDRESS as an integer.  The image is the kernel's only LDS (no static __shared__; launch_shape
+// checks the code object), so it starts at LDS address 0 and an image offset IS the address.  Going through the `lds`
+// symbol instead costs a `v_add_u32 v, 0, v` wherever a lane base is kept for several reads: the symbol's value is only
+// known to the assembler, so the compiler cannot fold the addition away.
+template <class T>
+__device__ __forceinline__ T lds_at(int byte) {
+  typedef __attribute__((address_space(3))) const T lds_t;
+  return *(lds_t*)(uintptr_t)(unsigned)byte;
 }
-__device__ __forceinline__ f32x4 lds128f(const unsigned char* lds, int byte) {
-  return *reinterpret_cast<const f32x4*>(lds + byte);
-}
+__device__ __forceinline__ u32x4 lds128(int byte) { return lds_at<u32x4>(byte); }
+__device__ __forceinline__ f32x4 lds128f(int byte) { return lds_at<f32x4>(byte); }
 // two transposing reads = the 8 k values of a transposed A fragment (rows 8 apart in k: byte distance `d8`)
-__device__ __forceinline__ u32x4 lds_tr(const unsigned char* lds, int byte0, int byte1) {
+__device__ __forceinline__ u32x4 lds_tr(int byte0, int byte1) {
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + byte0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + byte1));
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(unsigned)byte0);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(unsigned)byte1);
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   return __builtin_bit_cast(u32x4, s16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w});
 }
@@ -355,11 +386,15 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     const int lowE = 16 * ((gg ^ xs) & 3), lowO = 16 * (((2 | gg) ^ xs) & 3), row31 = min(96 + jj, W1_ZERO);
     w1f[0][0] = jj * RS1 + lowE; w1f[0][1] = row31 * RS1 + lowE; w1f[1][0] = jj * RS1 + lowO; w1f[1][1] = row31 * RS1 + lowO;
   };
-  // forward W2: (base ^ (kb << 5)) + 32 * RS2 * mt; [tile 3 ?]
+  // forward W2: (base ^ (kb << 5)) + 32 * RS2 * mt; [tile 3 ?].  The bases hold the hi image's offset (a multiple of 256: the
+  // XORs on the low 8 bits pass it by) and are opaque once FINISHED, so that every hi read is base + immediate and every
+  // mid read base + W2_MID + immediate -- with the image offsets added per read, hipcc formed each address with a
+  // v_add_u32 of a literal past the 16-bit offset of a DS instruction.
   auto bases_w2f = [&](int (&w2f)[2]) __attribute__((always_inline)) {
     asm volatile("" : "+v"(lane_v));
     const int jj = lane_v & 31, gg = lane_v >> 5, sw2 = 16 * swz2(jj), row32 = min(96 + jj, W2_ZERO);
-    w2f[0] = (jj * RS2 + sw2) ^ (gg << 4); w2f[1] = (row32 * RS2 + sw2) ^ (gg << 4);
+    w2f[0] = O_W2H + ((jj * RS2 + sw2) ^ (gg << 4)); w2f[1] = O_W2H + ((row32 * RS2 + sw2) ^ (gg << 4));
+    asm volatile("" : "+v"(w2f[0]), "+v"(w2f[1]));
   };
   // transposed reads: lane = (g, a, q, p); [eh][kb == 6 ?]
   //   W2: (base ^ (mt << 6)) + 16 * RS2 * kb;   W1: base + 16 * RS1 * kb + 64 * mt
@@ -371,9 +406,10 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     for (int eh = 0; eh < 2; ++eh) {
       const int low = 16 * (((2 * ta + (tp & 1)) ^ (2 * eh + gg)) & 3) + 8 * (tp >> 1);
       const int r = 8 * eh + 4 * gg + tq;
-      if (W1) { t[eh][0] = r * RS1 + low; t[eh][1] = min(96 + r, W1_ZERO) * RS1 + low; }
-      else { t[eh][0] = r * RS2 + 64 * tq + low; t[eh][1] = min(96 + r, W2_ZERO) * RS2 + 64 * tq + low; }
+      if (W1) { t[eh][0] = O_W1H + r * RS1 + low; t[eh][1] = O_W1H + min(96 + r, W1_ZERO) * RS1 + low; }
+      else { t[eh][0] = O_W2H + r * RS2 + 64 * tq + low; t[eh][1] = O_W2H + min(96 + r, W2_ZERO) * RS2 + 64 * tq + low; }
     }
+    X32_OPAQUE2(t);   // (finished bases, image offset included: see bases_w2f)
   };
   int ftl = O_FT + 64 * g, ftdl = O_FTD + 64 * g, isl = O_ISA + 16 * g, w3al = O_W3A + 16 * g, w3ll = O_W3L + 48 * g;
   int fin_rel = geo.fin - 4 * g;   // position == fin  <=>  16 kb + 8 (e >> 2) + (e & 3) == fin_rel
@@ -477,10 +513,10 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     auto feature_any = [&](auto special_c, int T, int kb, int e) __attribute__((always_inline)) {
       constexpr bool SPECIAL = decltype(special_c)::value;   // the block may hold angle / ones / pad positions
       const int off = 256 * kb + 128 * (e >> 2) + 16 * (e & 3);
-      const f32x4 tw = lds128f(lds, ftl + off);
+      const f32x4 tw = lds128f(ftl + off);
       float arg = fmaf(tw.x, ux[T], fmaf(tw.y, uy[T], tw.z));
       if constexpr (SPECIAL) {
-        const float isa = *reinterpret_cast<const float*>(lds + isl + (off >> 2));
+        const float isa = lds_at<float>(isl + (off >> 2));
         const float za = (th[T] + tw.z) * tw.x;
         arg = isa != 0.0f ? za : arg;
       }
@@ -516,8 +552,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       int nxt_ft = 0;   // table byte address of the block being prepared
       auto load_pair = [&](int p) __attribute__((always_inline)) {
         const int off = nxt_ft + 128 * ((2 * p) >> 2) + 16 * ((2 * p) & 3);
-        tw[p & 1][0] = lds128f(lds, off);
-        tw[p & 1][1] = lds128f(lds, off + 16);
+        tw[p & 1][0] = lds128f(off);
+        tw[p & 1][1] = lds128f(off + 16);
       };
       auto l1_item = [&](auto wc, u32x4 (&out)[NT][3]) __attribute__((always_inline)) {
         constexpr int T = decltype(wc)::value % NT, w = decltype(wc)::value / NT;
@@ -543,7 +579,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       auto load_pair_any = [&](int p) __attribute__((always_inline)) {
         load_pair(p);
         const int off = nxt_is + 32 * ((2 * p) >> 2) + 4 * ((2 * p) & 3);
-        const f32x2 fl2 = *reinterpret_cast<const f32x2*>(lds + off);
+        const f32x2 fl2 = lds_at<f32x2>(off);
         isa2[p & 1][0] = fl2.x; isa2[p & 1][1] = fl2.y;
       };
       auto l1_item_any = [&](auto wc, u32x4 (&out)[NT][3]) __attribute__((always_inline)) {
@@ -577,11 +613,11 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           // in-image read)
           if constexpr (mt < 3) {
             const int off = kq + (mt + 1 < 3 ? 32 * RS1 * (mt + 1) : 0);
-            fh[(mt + 1) & 1] = lds128(lds, O_W1H + w1f[PAR][mt + 1 == 3] + off);
-            fm[(mt + 1) & 1] = lds128(lds, w1m[PAR][mt + 1 == 3] + off);
+            fh[(mt + 1) & 1] = lds128(O_W1H + w1f[PAR][mt + 1 == 3] + off);
+            fm[(mt + 1) & 1] = lds128(w1m[PAR][mt + 1 == 3] + off);
           } else {
             const int off = 64 * ((kb + 1) >> 1);
-            fh[0] = lds128(lds, O_W1H + w1f[PAR ^ 1][0] + off); fm[0] = lds128(lds, w1m[PAR ^ 1][0] + off);
+            fh[0] = lds128(O_W1H + w1f[PAR ^ 1][0] + off); fm[0] = lds128(w1m[PAR ^ 1][0] + off);
           }
           fl[(4 * PAR + mt + LOOK) & (RL - 1)] = lo_frag(C::S_L1 + 4 * kb + mt + LOOK);
           __builtin_amdgcn_sched_barrier(0);
@@ -592,7 +628,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         });
       };
       constexpr int FS = C::FS;
-      fh[0] = lds128(lds, O_W1H + w1f[0][0]); fm[0] = lds128(lds, w1m[0][0]);
+      fh[0] = lds128(O_W1H + w1f[0][0]); fm[0] = lds128(w1m[0][0]);
       l1_block(ic<1>{}, ic<0>{}, 0, bA, bB, std::true_type{});
       l1_block(ic<1>{}, ic<1>{}, 1, bB, bA, std::false_type{});
 #pragma unroll 1
@@ -631,6 +667,12 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         constexpr int kb = decltype(kbc)::value, T = decltype(wc)::value % NT, w = decltype(wc)::value / NT;
         if constexpr (w < 68) {
           constexpr int p = w / 17, u = w % 17, t = kb >> 1, r0 = 8 * (kb & 1) + 2 * p, h0 = TRAIN ? 2 * (p & 1) : 0;
+          if constexpr (pad_pair(kb, p)) {   // constant +0 (see "the pad positions" above)
+            if constexpr (u == 0) out[T][0][p] = out[T][1][p] = out[T][2][p] = 0u;
+            if constexpr (u == 2 && p == 2) m1w[T][kb >> 2] <<= 4;   // the four mask pushes of pairs 2, 3
+            if constexpr (TRAIN && u == 15 && p == 3) st4(r_h1, vo_h + 64 * kb + 32 * (p >> 1), 0.0f, 0.0f, 0.0f, 0.0f);
+            return;
+          }
           if constexpr (u == 0) hv[T][h0] = relu1(acc1[t][T][r0]);
           if constexpr (u == 1) hv[T][h0 + 1] = relu1(acc1[t][T][r0 + 1]);
           if constexpr (u == 2) m1w[T][kb >> 2] = __builtin_amdgcn_alignbit(m1w[T][kb >> 2], 0u - __float_as_uint(hv[T][h0]), 31);
@@ -646,14 +688,14 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         sfor<0, 4>([&](auto mtc) {
           constexpr int mt = decltype(mtc)::value;
           if constexpr (mt == 0 && kb == 0) {
-            fh[0] = lds128(lds, O_W2H + w2f[0]); fm[0] = lds128(lds, O_W2M + w2f[0]);
+            fh[0] = lds128(w2f[0]); fm[0] = lds128(W2_MID + w2f[0]);
           }
           if constexpr (mt < 3) {
             const int ad = (w2f[mt + 1 == 3] ^ kx) + (mt + 1 < 3 ? 32 * RS2 * (mt + 1) : 0);
-            fh[(mt + 1) & 1] = lds128(lds, O_W2H + ad); fm[(mt + 1) & 1] = lds128(lds, O_W2M + ad);
+            fh[(mt + 1) & 1] = lds128(ad); fm[(mt + 1) & 1] = lds128(W2_MID + ad);
           } else if constexpr (kb + 1 < HK) {
             const int ad = w2f[0] ^ ((kb + 1) << 5);
-            fh[0] = lds128(lds, O_W2H + ad); fm[0] = lds128(lds, O_W2M + ad);
+            fh[0] = lds128(ad); fm[0] = lds128(W2_MID + ad);
           }
           fl[(C::S_L2 + 4 * kb + mt + LOOK) & (RL - 1)] = lo_frag(C::S_L2 + 4 * kb + mt + LOOK);
           __builtin_amdgcn_sched_barrier(0);
@@ -672,7 +714,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         float lgs[2] = {0.0f, 0.0f};
         sfor<0, HK>([&](auto kbc) {
           constexpr int kb = decltype(kbc)::value;
-          const f32x4 w3f[2] = {lds128f(lds, w3al + 64 * kb), lds128f(lds, w3al + 64 * kb + 32)};
+          const f32x4 w3f[2] = {lds128f(w3al + 64 * kb), lds128f(w3al + 64 * kb + 32)};
 #pragma unroll
           for (int e = 0; e < 8; ++e) lgs[e & 1] = fmaf(w3f[e >> 2][e & 3], relu1(acc2[kb >> 1][T][8 * (kb & 1) + e]), lgs[e & 1]);
         });
@@ -701,8 +743,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       float hv[NT][2];
       unsigned mk[NT][2];
       auto dh2_load = [&](int kb) __attribute__((always_inline)) {
-        w3f[0] = lds128f(lds, w3al + 64 * kb); w3f[1] = lds128f(lds, w3al + 64 * kb + 32);
-        w3c[0] = lds128(lds, w3ll + 96 * kb); w3c[1] = lds128(lds, w3ll + 96 * kb + 16); w3c[2] = lds128(lds, w3ll + 96 * kb + 32);
+        w3f[0] = lds128f(w3al + 64 * kb); w3f[1] = lds128f(w3al + 64 * kb + 32);
+        w3c[0] = lds128(w3ll + 96 * kb); w3c[1] = lds128(w3ll + 96 * kb + 16); w3c[2] = lds128(w3ll + 96 * kb + 32);
       };
       // one pair of block kb: relu, sign mask, logit terms, masked level words: 12 instructions per tile, tiles alternating
       // (TRAIN: + 2, the sign bits of a2 for the record, in front of the mask merge)
@@ -711,6 +753,10 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         if constexpr (w < 4 * DH2_IP) {
           constexpr int p = w / DH2_IP, u0 = w % DH2_IP, t = kb >> 1, r0 = 8 * (kb & 1) + 2 * p, e0 = 2 * p;
           constexpr int u = !TRAIN ? u0 : (u0 < 8 ? u0 : (u0 < 10 ? 92 + u0 : u0 - 2));
+          if constexpr (pad_pair(kb, p)) {   // constant 0, no logit term, no sign bit (see "the pad positions" above)
+            if constexpr (u == 0) out[T][0][p] = out[T][1][p] = out[T][2][p] = 0u;
+            return;
+          }
           // (the 28 bit constants live in scalar registers and push a few of those into spill lanes; pushing the bits in with
           // v_alignbit instead frees them but moves the pressure to the vector file: 51 instead of 35 spilled registers, +3 %)
           if constexpr (u == 100) sgn[T][p >> 1] |= mk[T][0] & (1u << (4 * kb + (e0 & 3)));
@@ -740,8 +786,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           auto fetch = [&](int kbn, int mtn, int zn, int slot) __attribute__((always_inline)) {
             const int a0 = (t2[0][zn] ^ (mtn << 6)) + (zn ? 0 : 16 * RS2 * kbn);
             const int a1 = (t2[1][zn] ^ (mtn << 6)) + (zn ? 0 : 16 * RS2 * kbn);
-            fh[slot] = lds_tr(lds, O_W2H + a0, O_W2H + a1);
-            fm[slot] = lds_tr(lds, O_W2M + a0, O_W2M + a1);
+            fh[slot] = lds_tr(a0, a1);
+            fm[slot] = lds_tr(W2_MID + a0, W2_MID + a1);
           };
           if constexpr (mt == 0 && kb == 0) fetch(0, 0, 0, 0);
           if constexpr (mt < 3) fetch(kb, mt + 1, Z, (mt + 1) & 1);
@@ -792,17 +838,19 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       constexpr int kb = decltype(kbc)::value, T = decltype(wc)::value % NT, w = decltype(wc)::value / NT;
       if constexpr (w < 4 * DH1_IP) {
         constexpr int p = w / DH1_IP, u = w % DH1_IP, t = kb >> 1, e0 = 2 * p;
+        constexpr bool PAD = pad_pair(kb, p);   // dv = +0 (see "the pad positions" above); TRAIN keeps the products with rho
+        if constexpr (PAD && u == 0) { dv[T][0] = dv[T][1] = 0.0f; dhl[kb][T][0][p] = dhl[kb][T][1][p] = dhl[kb][T][2][p] = 0u; }
         if constexpr (TRAIN && u == 16) dq[T][2 * (p & 1)] = dv[T][0] * rho[T];
         if constexpr (TRAIN && u == 17) dq[T][2 * (p & 1) + 1] = dv[T][1] * rho[T];
         if constexpr (TRAIN && u == 18 && (p & 1)) st4(r_dh1, vo_h + 64 * kb + 32 * (p >> 1), dq[T][0], dq[T][1], dq[T][2], dq[T][3]);
         constexpr int nbits = (kb >> 2) == 0 ? 32 : 8 * (HK - 4);   // pushes into this mask word
         constexpr int k0 = 8 * (kb & 3) + e0;
-        if constexpr (u == 0) dv[T][0] = __uint_as_float((unsigned)__builtin_amdgcn_sbfe((int)m1w[T][kb >> 2], nbits - 1 - k0, 1));
-        if constexpr (u == 1) dv[T][1] = __uint_as_float((unsigned)__builtin_amdgcn_sbfe((int)m1w[T][kb >> 2], nbits - 2 - k0, 1));
-        if constexpr (u == 2) dv[T][0] = __uint_as_float(__float_as_uint(accd[t][T][8 * (kb & 1) + e0]) & __float_as_uint(dv[T][0]));
-        if constexpr (u == 3) dv[T][1] = __uint_as_float(__float_as_uint(accd[t][T][8 * (kb & 1) + e0 + 1]) & __float_as_uint(dv[T][1]));
+        if constexpr (!PAD && u == 0) dv[T][0] = __uint_as_float((unsigned)__builtin_amdgcn_sbfe((int)m1w[T][kb >> 2], nbits - 1 - k0, 1));
+        if constexpr (!PAD && u == 1) dv[T][1] = __uint_as_float((unsigned)__builtin_amdgcn_sbfe((int)m1w[T][kb >> 2], nbits - 2 - k0, 1));
+        if constexpr (!PAD && u == 2) dv[T][0] = __uint_as_float(__float_as_uint(accd[t][T][8 * (kb & 1) + e0]) & __float_as_uint(dv[T][0]));
+        if constexpr (!PAD && u == 3) dv[T][1] = __uint_as_float(__float_as_uint(accd[t][T][8 * (kb & 1) + e0 + 1]) & __float_as_uint(dv[T][1]));
         if constexpr (u == 4 && kb == 6 && p == 0) dv[T][0] = g == 1 ? 1.0f : dv[T][0];   // position 100: d logit / d skip
-        if constexpr (u >= 5 && u < 16) split_item<u - 5>(dss[T], dv[T][0], dv[T][1], dhl[kb][T], p);
+        if constexpr (!PAD && u >= 5 && u < 16) split_item<u - 5>(dss[T], dv[T][0], dv[T][1], dhl[kb][T], p);
       }
     };
     sfor<0, 4 * DH1_IP * NT>([&](auto w) { dh1_item(ic<0>{}, w); });
@@ -827,8 +875,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       int ep_ft = 0, ep_vo = 0;   // (TRAIN: byte offset of the epilogue tile in the sample's row of de)
       auto ep_load = [&](int pr) __attribute__((always_inline)) {   // pair pr = registers 2 pr, 2 pr + 1
         const int off = ep_ft + 128 * ((2 * pr) >> 2) + 16 * ((2 * pr) & 3);
-        tw[pr & 1][0] = lds128f(lds, off);
-        tw[pr & 1][1] = lds128f(lds, off + 16);
+        tw[pr & 1][0] = lds128f(off);
+        tw[pr & 1][1] = lds128f(off + 16);
       };
       // chain-rule epilogue of the previous tile (plain positional features): per point tile 8 pairs x 22 instructions, 5 per
       // slot, the point tiles' items alternating (the table entries are shared)
@@ -854,8 +902,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         if constexpr (HOOK == 1) { ep_ft = ftdl + 512 * (mt - 1); ep_vo = vo_de + 128 * (mt - 1); ep_load(0); }
         auto fetch = [&](int kbn, int mtn, int zn, u32x4& oh, u32x4& om) __attribute__((always_inline)) {
           const int off = 64 * mtn + (zn ? 0 : 16 * RS1 * kbn);
-          oh = lds_tr(lds, O_W1H + t1[0][zn] + off, O_W1H + t1[1][zn] + off);
-          om = lds_tr(lds, t1m[0][zn] + off, t1m[1][zn] + off);
+          oh = lds_tr(t1[0][zn] + off, t1[1][zn] + off);
+          om = lds_tr(t1m[0][zn] + off, t1m[1][zn] + off);
         };
         fh[0] = fhn; fm[0] = fmn;   // fetched during the previous tile's last step
         sfor<0, HK>([&](auto kbc) {
@@ -881,8 +929,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int off = 512 * mt + 128 * (r >> 2) + 16 * (r & 3);
-            const f32x4 e = lds128f(lds, ftdl + off);
-            const float isa = *reinterpret_cast<const float*>(lds + isl + (off >> 2));
+            const f32x4 e = lds128f(ftdl + off);
+            const float isa = lds_at<float>(isl + (off >> 2));
             float arg = fmaf(e.x, ux[T], fmaf(e.y, uy[T], e.z));
             const float za = (th[T] + e.z) * e.x;
             arg = isa != 0.0f ? za : arg;
@@ -899,8 +947,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           }
       };
       {
-        fhn = lds_tr(lds, O_W1H + t1[0][0], O_W1H + t1[1][0]);
-        fmn = lds_tr(lds, t1m[0][0], t1m[1][0]);
+        fhn = lds_tr(t1[0][0], t1[1][0]);
+        fmn = lds_tr(t1m[0][0], t1m[1][0]);
       }
       l1t_tile(ic<2>{}, 0, accp);
       if constexpr (TRAIN) { train_offsets(); r_de = train_rsrc(a.ws_de, 16 * NKB); }
@@ -959,6 +1007,17 @@ static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_ou
     hipLaunchKernelGGL(x32_prep_kernel<NKB>, dim3((N_PIECES + 255) / 256), dim3(256), 0, stream, a.geom, a.params, img, blob);
     NFOPP_HIP(hipGetLastError());
     g_images.set_tag(slot, stream, ImageTag{a.params, ver, a.geom});
+  }
+  // the kernel reads the image at absolute LDS addresses (lds_at): it must own no LDS in front of the dynamic block
+  static bool lds_checked[MAX_DEVICES] = {};
+  const int dev = current_device();
+  if (dev < 0) return NFOPP_ERR_HIP;
+  if (!lds_checked[dev]) {
+    hipFuncAttributes fa;
+    NFOPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(onf_x32_kernel<NKB, MODE, XT, 1>)));
+    NFOPP_REQUIRE(fa.sharedSizeBytes == 0, "onf_x32_kernel holds %zu bytes of static LDS: its image would not start at LDS address 0",
+                  (size_t)fa.sharedSizeBytes);
+    lds_checked[dev] = true;
   }
   return launch_persistent<onf_x32_kernel<NKB, MODE, XT, 1>>(IMG_BYTES, XT, (a.n_points + CH - 1) / CH, stream, grid_out, a,
                                                              (const u32x4*)img, (const u32x4*)blob);
