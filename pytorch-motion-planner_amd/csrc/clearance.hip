@@ -25,7 +25,7 @@ constexpr int NR_WAVE_POSES = 4;              // poses one wave searches one aft
 
 struct NearArgs {   // a pose that load_pose flags as not finite is answered +inf / -1
   const float* poses; long long n; int dim;
-  PointCloud cloud; Robot robot;
+  Scene scene;
   float* dist; int* index;
 };
 
@@ -33,6 +33,15 @@ __device__ __forceinline__ void store_result(const NearArgs& a, long long p, boo
   a.dist[p] = finite ? best : __builtin_inff();
   if (a.index) a.index[p] = finite ? bestk : -1;
 }
+
+// what every form does with a point: the nearest one to the robot at pose q so far, the smallest index among equals
+template <int MODE>
+struct Nearest {
+  const Robot& robot; const Pose& q; float best; int bestk;
+  __device__ __forceinline__ void operator()(float px, float py, int k, int) {
+    take_min(robot.point_distance<MODE>(q, px, py), k, &best, &bestk);
+  }
+};
 
 // ---- all pairs ------------------------------------------------------------------------------------------------------
 template <int MODE>
@@ -42,12 +51,9 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_kernel(const NearArgs a) {
   const bool valid = p < a.n;
   Pose q = {0.f, 0.f, 1.f, 0.f, false};
   if (valid) q = load_pose<MODE>(a.poses, a.dim, p);
-  float best = __builtin_inff();
-  int bestk = -1;
-  for_all_points<NR_THREADS>(a.cloud, ox, oy, [&](float px, float py, int k) {
-    take_min(a.robot.point_distance<MODE>(q, px, py), k, &best, &bestk);
-  });
-  if (valid) store_result(a, p, q.finite, best, bestk);
+  Nearest<MODE> near = {a.scene.robot, q, __builtin_inff(), -1};
+  for_all_points<NR_THREADS>(a.scene.cloud, ox, oy, near);
+  if (valid) store_result(a, p, q.finite, near.best, near.bestk);
 }
 
 // ---- cell index: search in rings, and when it may stop -----------------------------------------------------------------
@@ -76,48 +82,39 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_kernel(const NearArgs a) {
 //      The factor 1 - 2^-18 (64 * 2^-24) covers both cases and the roundings of forming L(r) itself.
 //  (4) Ties: a point at exactly the best distance with a smaller index must still be found, hence the strict L(r) > best.
 // L(0) < 0: ring 1 is always searched, unless the index is a single cell.
-// the points of cells x_lo..x_hi of row yy.  WAVE = false: the calling thread visits every one.  WAVE = true: the 64 lanes
-// of a wave hold the same pose and split the run among them.
+// WAVE = false: the calling thread visits every point.  WAVE = true: the 64 lanes of a wave hold the same pose, split each
+// run of points among them (for_row_points) and combine their minima after every ring.  *rings (may be null) <- rings
+// searched.  The minimum lives in a functor of this function's own and leaves through the pointers: carried in from the
+// kernels, across their `if (q.finite)` and the wave form's loop over poses, it cost that kernel 23 instructions more.
 template <int MODE, bool WAVE>
-__device__ __forceinline__ void scan_cells(const NearArgs& a, const Pose& q, int yy, int x_lo, int x_hi, float* best,
-                                           int* bestk) {
-  int k, k1;
-  a.cloud.index.row_range(yy, x_lo, x_hi, &k, &k1);
-  const float* pt = a.cloud.points;
-  for (k += WAVE ? (int)(threadIdx.x & 63) : 0; k < k1; k += WAVE ? 64 : 1)
-    take_min(a.robot.point_distance<MODE>(q, pt[2 * (long long)k], pt[2 * (long long)k + 1]), k, best, bestk);
-}
-
-// In the wave form the lanes combine their minima after every ring.  *rings (may be null) <- rings searched.
-template <int MODE, bool WAVE>
-__device__ __forceinline__ void nearest_in_cells(const NearArgs& a, const Pose& q, float* best_out, int* bestk_out,
-                                                 int* rings) {
-  const int nx = a.cloud.index.cells_x, ny = a.cloud.index.cells_y;
+__device__ __forceinline__ void nearest_in_cells(const Scene& scene, const Pose& q, float* best, int* bestk, int* rings) {
+  const PointCloud& cloud = scene.cloud;
+  Nearest<MODE> near = {scene.robot, q, __builtin_inff(), -1};
+  const int nx = cloud.index.cells_x, ny = cloud.index.cells_y;
   int cx, cy;
-  a.cloud.index.cell(q.x, q.y, &cx, &cy);
-  float best = __builtin_inff();
-  int bestk = -1, r = 0;
+  cloud.index.cell(q.x, q.y, &cx, &cy);
+  int r = 0;
   const int r_end = max(nx, ny);
   for (; r < r_end; ++r) {
     const int x_lo = max(cx - r, 0), x_hi = min(cx + r, nx - 1);
     // the two rows of the ring
-    if (cy - r >= 0) scan_cells<MODE, WAVE>(a, q, cy - r, x_lo, x_hi, &best, &bestk);
-    if (r > 0 && cy + r <= ny - 1) scan_cells<MODE, WAVE>(a, q, cy + r, x_lo, x_hi, &best, &bestk);
+    if (cy - r >= 0) for_row_points<WAVE>(cloud, cy - r, x_lo, x_hi, near);
+    if (r > 0 && cy + r <= ny - 1) for_row_points<WAVE>(cloud, cy + r, x_lo, x_hi, near);
     // the two columns between them, a cell at a time
     for (int yy = max(cy - r + 1, 0); yy <= min(cy + r - 1, ny - 1); ++yy) {
-      if (cx - r >= 0) scan_cells<MODE, WAVE>(a, q, yy, cx - r, cx - r, &best, &bestk);
-      if (cx + r <= nx - 1) scan_cells<MODE, WAVE>(a, q, yy, cx + r, cx + r, &best, &bestk);
+      if (cx - r >= 0) for_row_points<WAVE>(cloud, yy, cx - r, cx - r, near);
+      if (cx + r <= nx - 1) for_row_points<WAVE>(cloud, yy, cx + r, cx + r, near);
     }
     if (WAVE) {
-      const Indexed<float> m = wave_reduce(Indexed<float>{best, bestk}, TakeMin());
-      best = m.v; bestk = m.i;
+      const Indexed<float> m = wave_reduce(Indexed<float>{near.best, near.bestk}, TakeMin());
+      near.best = m.v; near.bestk = m.i;
     }
     const bool closed = cx - r <= 0 && cx + r >= nx - 1 && cy - r <= 0 && cy + r >= ny - 1;
-    const float lower = __builtin_fmaf(((float)r - 0.0625f) * a.cloud.index.size, 1.0f - 3.814697265625e-06f, -a.robot.reach);
-    if (closed || lower > best) { ++r; break; }
+    const float lower = __builtin_fmaf(((float)r - 0.0625f) * cloud.index.size, 1.0f - 3.814697265625e-06f, -scene.robot.reach);
+    if (closed || lower > near.best) { ++r; break; }
   }
-  *best_out = best;
-  *bestk_out = bestk;
+  *best = near.best;
+  *bestk = near.bestk;
   if (rings) *rings = r;
 }
 
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_cells_kernel(const NearArg
   const Pose q = load_pose<MODE>(a.poses, a.dim, p);
   float best = __builtin_inff();
   int bestk = -1;
-  if (q.finite) nearest_in_cells<MODE, false>(a, q, &best, &bestk, nullptr);
+  if (q.finite) nearest_in_cells<MODE, false>(a.scene, q, &best, &bestk, nullptr);
   store_result(a, p, q.finite, best, bestk);
 }
 
@@ -142,7 +139,7 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_cells_wave_kernel(const Ne
     const Pose q = load_pose<MODE>(a.poses, a.dim, p);
     float best = __builtin_inff();
     int bestk = -1;
-    if (q.finite) nearest_in_cells<MODE, true>(a, q, &best, &bestk, nullptr);
+    if (q.finite) nearest_in_cells<MODE, true>(a.scene, q, &best, &bestk, nullptr);
     if ((threadIdx.x & 63) == 0) store_result(a, p, q.finite, best, bestk);
   }
 }
@@ -155,7 +152,7 @@ __global__ __launch_bounds__(NR_THREADS) void nearest_rings_kernel(const NearArg
   const Pose q = load_pose<MODE>(a.poses, a.dim, p);
   float best;
   int bestk, rings = 0;
-  if (q.finite) nearest_in_cells<MODE, false>(a, q, &best, &bestk, &rings);
+  if (q.finite) nearest_in_cells<MODE, false>(a.scene, q, &best, &bestk, &rings);
   a.index[p] = rings;
 }
 
@@ -264,16 +261,19 @@ __global__ __launch_bounds__(PS_THREADS) void path_stats_kernel(const StatsArgs 
 }
 
 template <int MODE>
-static void launch_nearest(const NearArgs& a, int form, hipStream_t st) {
-  const unsigned grid = (unsigned)((a.n + NR_THREADS - 1) / NR_THREADS);
-  if (form == 0) hipLaunchKernelGGL(nearest_kernel<MODE>, dim3(grid), dim3(NR_THREADS), 0, st, a);
-  else if (form == 1) hipLaunchKernelGGL(nearest_cells_kernel<MODE>, dim3(grid), dim3(NR_THREADS), 0, st, a);
-  else if (form == 3) hipLaunchKernelGGL(nearest_rings_kernel<MODE>, dim3(grid), dim3(NR_THREADS), 0, st, a);
-  else {
-    const long long per_group = (long long)(NR_THREADS / 64) * NR_WAVE_POSES;
-    hipLaunchKernelGGL(nearest_cells_wave_kernel<MODE>, dim3((unsigned)((a.n + per_group - 1) / per_group)),
-                       dim3(NR_THREADS), 0, st, a);
-  }
+static void launch_nearest(const NearArgs& a, void* stream) {   // the wave form: the one launch with a grid of its own
+  const long long per_group = (long long)(NR_THREADS / 64) * NR_WAVE_POSES;
+  hipLaunchKernelGGL(nearest_cells_wave_kernel<MODE>, dim3((unsigned)((a.n + per_group - 1) / per_group)), dim3(NR_THREADS),
+                     0, (hipStream_t)stream, a);
+}
+
+template <int MODE>
+static int launch_form(const NearArgs& a, int form, void* stream) {
+  const auto per_pose = form == 0 ? nearest_kernel<MODE> : (form == 1 ? nearest_cells_kernel<MODE> : nearest_rings_kernel<MODE>);
+  if (form != 2) return launch_per_item<NR_THREADS>(per_pose, a.n, stream, a);
+  launch_nearest<MODE>(a, stream);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
 }
 
 // form: 0 all pairs, 1 cell index with one thread per pose, 2 cell index with one wave per group of poses, 3 ring counts
@@ -282,25 +282,17 @@ static int nearest(int form, const float* poses_dev, int64_t n, int32_t pose_dim
                    float cell_y0, float cell_size, const float* box4, float* dist_dev, int32_t* index_dev, void* stream) {
   NFOPP_REQUIRE(n >= 0 && (pose_dim == 2 || pose_dim == 3), "need n >= 0 and pose_dim 2 or 3");
   NFOPP_REQUIRE(n <= (int64_t)0x7fffffff * NR_WAVE_POSES, "too many poses for one call");
-  NFOPP_REQUIRE(!box4 || pose_dim == 3, "the box robot needs poses with a heading (pose_dim 3)");
-  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
   NearArgs a = {};
-  if (form != 0) {
-    const int rc = fill_cell_index(&a.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size,
-                                   n_obstacles > 0 || form == 3);
-    if (rc) return rc;
-    NFOPP_REQUIRE((long long)cells_x * cells_y <= MAX_INDEX_CELLS, "the index holds between 1 and 65536 cells");
-  }
+  bool all_pairs;
+  const int rc = fill_scene(&a.scene, &all_pairs, form == 0 ? SCENE_ALL_PAIRS : (form == 3 ? SCENE_CELLS_ALWAYS : SCENE_CELLS),
+                            obstacles_dev, n_obstacles, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size, box4,
+                            0.f, pose_dim);
+  if (rc) return rc;
   if (n == 0) return NFOPP_OK;
   NFOPP_REQUIRE(poses_dev && dist_dev && (form != 3 || index_dev), "null device pointer");
-  a.poses = poses_dev; a.n = n; a.dim = pose_dim; a.cloud.points = obstacles_dev; a.cloud.n = n_obstacles;
-  a.dist = dist_dev; a.index = index_dev;
-  if (box4) set_box(&a.robot, box4);
-  if (n_obstacles == 0 && form != 3) form = 0;   // nothing to search: the all-pairs kernel writes +inf / -1
-  if (box4) launch_nearest<1>(a, form, (hipStream_t)stream);
-  else launch_nearest<0>(a, form, (hipStream_t)stream);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  a.poses = poses_dev; a.n = n; a.dim = pose_dim; a.dist = dist_dev; a.index = index_dev;
+  if (all_pairs) form = 0;   // nothing to search: the all-pairs kernel writes +inf / -1
+  return box4 ? launch_form<1>(a, form, stream) : launch_form<0>(a, form, stream);
 }
 
 }  // namespace nfopp

@@ -74,6 +74,15 @@ int launch_dynamic_lds(void (*kernel)(Args), long long grid, int threads, size_t
   return NFOPP_OK;
 }
 
+// kernel(args) with one thread per item: ceil(n / THREADS) workgroups of THREADS, no launch for n == 0; -> the launch's status
+template <int THREADS, class Args>
+int launch_per_item(void (*kernel)(Args), long long n, void* stream, const Args& args) {
+  if (n == 0) return NFOPP_OK;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, args);
+  NFOPP_HIP(hipGetLastError());
+  return NFOPP_OK;
+}
+
 // A scratch device buffer per (device, stream), for kernels that rewrite their scratch on the launch stream in front of
 // every launch: launches of one stream are ordered by the stream itself, and two streams (two planners with different
 // fields) never share a buffer.  16 buffers per device -- a handful of streams is the realistic case, though PyTorch's

@@ -1,8 +1,11 @@
-// What every kernel over the obstacle point cloud shares: the uniform cell index (built by csrc/obstacle_map.hip, searched
-// by the *_cells checkers of csrc/sampling.hip, the nearest-obstacle query of csrc/clearance.hip and the swept check of
-// csrc/swept.hip), the robot's shape and
-// the all-pairs visit.  The index is sound only if all three form a cell number the same way, and `dist < radius` of the
-// query is the circle checker's obstacle term only if both evaluate one expression: each is written once, here.
+// What every kernel over the obstacle point cloud shares: the uniform cell index, the robot's shape, the visits of the points
+// (all pairs; the sorted points of a window of cells) and the host's side of an entry that takes a cloud and a robot.
+// Users: csrc/obstacle_map.hip builds the index (CellIndex::cell); the checkers of csrc/sampling.hip, the nearest-obstacle
+// query of csrc/clearance.hip and the swept check and its refinement of csrc/swept.hip search it (for_row_points,
+// for_window_points), visit every point (for_all_points) and open their entries with fill_scene.  The index is sound only
+// if all of them form a cell number the same way, `dist < radius` of the query is the circle checker's obstacle term only
+// if both evaluate one expression, and an indexed entry writes its all-pairs partner's bytes only if each visit is one loop:
+// every one of these is written once, here.
 //
 // RULE for the fp32 arithmetic of this header: csrc/clearance.hip compiles under `#pragma clang fp contract(off)`,
 // csrc/sampling.hip does not, so a product feeding a plain add or subtract would be one fma in one file and two roundings in
@@ -14,6 +17,12 @@
 namespace nfopp {
 
 constexpr int MAX_INDEX_CELLS = 65536;   // cell numbers are the build's 16-bit sort key and enter the ring search's bound
+
+struct CellWindow { int x_lo, y_lo, x_hi, y_hi; };   // a rectangle of cells, both ends included, inside the index
+
+__device__ __forceinline__ float outward(float w, float sign) {   // w moved by 4 * 2^-24 |w| towards sign * inf
+  return __builtin_fmaf(fabsf(w), sign * 2.384185791015625e-07f, w);
+}
 
 // cells_x * cells_y cells of `size` from (x0, y0), row-major; cell_start[c] .. cell_start[c + 1]: the sorted points of cell c
 struct CellIndex {
@@ -32,6 +41,28 @@ struct CellIndex {
   __device__ __forceinline__ void row_range(int yy, int x_lo, int x_hi, int* k0, int* k1) const {
     *k0 = cell_start[yy * cells_x + x_lo];
     *k1 = cell_start[yy * cells_x + x_hi + 1];
+  }
+  // the cell of (x, y) grown by r cells per side
+  __device__ __forceinline__ CellWindow window_around(float x, float y, int r) const {
+    int cx, cy;
+    cell(x, y, &cx, &cy);
+    return {max(cx - r, 0), max(cy - r, 0), min(cx + r, cells_x - 1), min(cy + r, cells_y - 1)};
+  }
+  // The cells of the bounding box of (ax, ay) and (bx, by) inflated by r, and one further cell per side: every cell that can
+  // hold a point within r of the segment between the two.  From coordinates to cells: each bound w = min - r or max + r is
+  // formed in fp32 and then moved outward by 4 * 2^-24 |w|, more than the rounding of its own two operations, so the fp32
+  // bound encloses the exact one.  axis_cell is a chain of monotone operations (correctly rounded subtraction and division,
+  // floor, clamp), and points and bounds go through that one function: lo <= ox <= hi implies
+  // cell(lo) <= cell(ox) <= cell(hi), for a point clamped into a border cell too.  One further cell is visited on each side:
+  // it costs a few points per segment and keeps the coverage from resting on the last bit of this argument and of the one
+  // that gave r (csrc/swept.hip, (1) and (2)).
+  __device__ __forceinline__ CellWindow window_of_box(float ax, float ay, float bx, float by, float r) const {
+    const float lox = outward(fminf(ax, bx) - r, -1.f), hix = outward(fmaxf(ax, bx) + r, 1.f);
+    const float loy = outward(fminf(ay, by) - r, -1.f), hiy = outward(fmaxf(ay, by) + r, 1.f);
+    int x_lo, y_lo, x_hi, y_hi;
+    cell(lox, loy, &x_lo, &y_lo);
+    cell(hix, hiy, &x_hi, &y_hi);
+    return {max(x_lo - 1, 0), max(y_lo - 1, 0), min(x_hi + 1, cells_x - 1), min(y_hi + 1, cells_y - 1)};
   }
 };
 
@@ -104,7 +135,9 @@ struct TakeMin {   // take_min as the op of a reduction over (distance, index) p
   }
 };
 
-// All pairs: f(ox, oy, k) for every point k of the cloud in ascending k.  The points pass through the workgroup's LDS arrays
+// The two visits of the points.  Both call f(ox, oy, k, j): point k of the cloud, the jth the visit comes to.  A query passes
+// one functor to either, so its all-pairs and its indexed kernel differ in the visit alone.
+// All pairs: every point k of the cloud in ascending k (j = k).  The points pass through the workgroup's LDS arrays
 // ox, oy [THREADS] a tile at a time between two barriers, so every thread has to call this, one without a pose included.
 template <int THREADS, class F>
 __device__ __forceinline__ void for_all_points(const PointCloud& cloud, float* ox, float* oy, F&& f) {
@@ -116,8 +149,32 @@ __device__ __forceinline__ void for_all_points(const PointCloud& cloud, float* o
     }
     __syncthreads();
     const int m = min(THREADS, cloud.n - base);
-    for (int k = 0; k < m; ++k) f(ox[k], oy[k], base + k);
+    for (int k = 0; k < m; ++k) f(ox[k], oy[k], base + k, base + k);
   }
+}
+
+// The index: the sorted points k of cells x_lo..x_hi of row yy in ascending k, j = before, before + 1, ... counting along
+// the run, only those with FIRST <= j < LAST; -> the run's length.  WAVE = false: the calling thread visits every point.
+// WAVE = true: the 64 lanes of a wave call this with the same arguments and split the points, the first going to lane 0.
+// Cells are formed only through CellIndex::cell and read only through row_range, here.
+template <bool WAVE, int FIRST = 0, int LAST = 0x7fffffff, class F>
+__device__ __forceinline__ int for_row_points(const PointCloud& cloud, int yy, int x_lo, int x_hi, F&& f, int before = 0) {
+  int k0, k1;
+  cloud.index.row_range(yy, x_lo, x_hi, &k0, &k1);
+  const int from = FIRST > 0 ? min(max(FIRST - before, 0), k1 - k0) : 0;
+  const int to = LAST < 0x7fffffff ? min(max(LAST - before, 0), k1 - k0) : k1 - k0;
+  for (int k = k0 + from + (WAVE ? (int)(threadIdx.x & 63) : 0); k < k0 + to; k += WAVE ? 64 : 1)
+    f(cloud.points[2 * (long long)k], cloud.points[2 * (long long)k + 1], k, before + (k - k0));
+  return k1 - k0;
+}
+
+// ... and the points of a window, row after row: j is the point's ordinal among the window's; -> their number.  The loop
+// runs over at most cells_y rows of the index.
+template <bool WAVE, int FIRST = 0, int LAST = 0x7fffffff, class F>
+__device__ __forceinline__ int for_window_points(const PointCloud& cloud, const CellWindow& w, F&& f) {
+  int total = 0;
+  for (int yy = w.y_lo; yy <= w.y_hi; ++yy) total += for_row_points<WAVE, FIRST, LAST>(cloud, yy, w.x_lo, w.x_hi, f, total);
+  return total;
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
@@ -142,6 +199,40 @@ static inline float box_reach(const float* box4) { return box_corner(box4) * 1.0
 static inline void set_box(Robot* r, const float* box4) {
   for (int k = 0; k < 4; ++k) r->box[k] = box4[k];
   r->reach = box_reach(box4);
+}
+
+struct Scene { PointCloud cloud; Robot robot; };   // what an entry judges its poses against: in every argument struct
+
+enum SceneLookup {      // how an entry finds the points of a pose, as far as its arguments are concerned
+  SCENE_ALL_PAIRS,      // no index: the six index arguments are not looked at
+  SCENE_CELLS,          // an index of at most MAX_INDEX_CELLS cells; without points nothing reads it and cell_start may be null
+  SCENE_CELLS_ALWAYS,   // the same, read even without points (the ring counts of csrc/clearance.hip)
+  SCENE_CHECKER_CELLS,  // the *_cells checkers: at least one point, any number of cells (they search 3 x 3 cells, no rings)
+};
+
+// The part of every entry's prologue that is about the scene, in the order the requirements have always fired in; then
+// *scene is filled (box4 null: the disc of `radius`) and *all_pairs says which kernel to launch -- the all-pairs one also
+// where an indexed entry has no points, so that nothing reads an index over nothing.  What only some entries ask (a cell no
+// smaller than the reach, a box at all) and what is about their own arrays (counts, null pointers) stays with them.
+static inline int fill_scene(Scene* scene, bool* all_pairs, SceneLookup lookup, const float* obstacles_dev,
+                             int32_t n_obstacles, const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y,
+                             float cell_x0, float cell_y0, float cell_size, const float* box4, float radius,
+                             int32_t pose_dim) {
+  NFOPP_REQUIRE(!box4 || pose_dim == 3, "the box robot needs poses with a heading (pose_dim 3)");
+  if (lookup == SCENE_CHECKER_CELLS) NFOPP_REQUIRE(n_obstacles > 0 && obstacles_dev, "bad obstacle index");
+  else NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
+  if (lookup != SCENE_ALL_PAIRS) {
+    const int rc = fill_cell_index(&scene->cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size,
+                                   n_obstacles > 0 || lookup == SCENE_CELLS_ALWAYS);
+    if (rc) return rc;
+    NFOPP_REQUIRE(lookup == SCENE_CHECKER_CELLS || (long long)cells_x * cells_y <= MAX_INDEX_CELLS,
+                  "the index holds between 1 and 65536 cells");
+  }
+  scene->cloud.points = obstacles_dev; scene->cloud.n = n_obstacles;
+  if (box4) set_box(&scene->robot, box4);
+  else scene->robot.radius = radius;
+  *all_pairs = lookup == SCENE_ALL_PAIRS || (n_obstacles == 0 && lookup != SCENE_CELLS_ALWAYS);
+  return NFOPP_OK;
 }
 
 }  // namespace nfopp

@@ -143,10 +143,10 @@ __global__ __launch_bounds__(SM_THREADS) void resample_pool_kernel(const Resampl
 }
 
 // ---- ground-truth checkers ------------------------------------------------------------------------------------
-// The cell index, the robot's predicate (Robot::hits<MODE>) and the all-pairs visit are those of csrc/point_cloud.h.
+// The cell index, the robot's predicate (Robot::hits<MODE>) and both visits of the points are those of csrc/point_cloud.h.
 struct CheckArgs {
   const float* poses; long long n; int dim;
-  PointCloud cloud; Robot robot;
+  Scene scene;
   int has_bounds; float bounds[4];
   float* labels;
 };
@@ -156,7 +156,14 @@ __device__ __forceinline__ bool out_of_bounds(const CheckArgs& a, float x, float
   return a.has_bounds && (x > a.bounds[1] || x < a.bounds[0] || y > a.bounds[3] || y < a.bounds[2]);
 }
 
-// MODE 0: disc robot, MODE 1: box robot against every point of the cloud
+// what both kernels do with a point: MODE 0 the disc robot, MODE 1 the box robot at pose q
+template <int MODE>
+struct HitsAny {
+  const Robot& robot; const Pose& q; bool hit;
+  __device__ __forceinline__ void operator()(float px, float py, int, int) { hit |= robot.hits<MODE>(q, px, py); }
+};
+
+// against every point of the cloud
 template <int MODE>
 __global__ __launch_bounds__(SM_THREADS) void check_points_kernel(const CheckArgs a) {
   __shared__ float ox[SM_THREADS], oy[SM_THREADS];
@@ -164,9 +171,9 @@ __global__ __launch_bounds__(SM_THREADS) void check_points_kernel(const CheckArg
   const bool valid = p < a.n;
   Pose q = {0.f, 0.f, 1.f, 0.f, false};
   if (valid) q = load_pose<MODE>(a.poses, a.dim, p);
-  bool hit = false;
-  for_all_points<SM_THREADS>(a.cloud, ox, oy, [&](float px, float py, int) { hit |= a.robot.hits<MODE>(q, px, py); });
-  if (valid) a.labels[p] = (hit || out_of_bounds(a, q.x, q.y)) ? 1.0f : 0.0f;
+  HitsAny<MODE> any = {a.scene.robot, q, false};
+  for_all_points<SM_THREADS>(a.scene.cloud, ox, oy, any);
+  if (valid) a.labels[p] = (any.hit || out_of_bounds(a, q.x, q.y)) ? 1.0f : 0.0f;
 }
 
 // The same with the cell index: the cell size is at least the robot's reach (the disc's radius; the largest distance from
@@ -177,16 +184,9 @@ __global__ __launch_bounds__(SM_THREADS) void check_points_cells_kernel(const Ch
   const long long p = blockIdx.x * (long long)SM_THREADS + threadIdx.x;
   if (p >= a.n) return;
   const Pose q = load_pose<MODE>(a.poses, a.dim, p);
-  const CellIndex& ix = a.cloud.index;
-  int cx, cy;
-  ix.cell(q.x, q.y, &cx, &cy);
-  bool hit = false;
-  for (int yy = max(cy - 1, 0); yy <= min(cy + 1, ix.cells_y - 1); ++yy) {
-    int k, k1;
-    ix.row_range(yy, max(cx - 1, 0), min(cx + 1, ix.cells_x - 1), &k, &k1);
-    for (; k < k1; ++k) hit |= a.robot.hits<MODE>(q, a.cloud.points[2 * k], a.cloud.points[2 * k + 1]);
-  }
-  a.labels[p] = (hit || out_of_bounds(a, q.x, q.y)) ? 1.0f : 0.0f;
+  HitsAny<MODE> any = {a.scene.robot, q, false};
+  for_window_points<false>(a.scene.cloud, a.scene.cloud.index.window_around(q.x, q.y, 1), any);
+  a.labels[p] = (any.hit || out_of_bounds(a, q.x, q.y)) ? 1.0f : 0.0f;
 }
 
 // occupancy grid (onf_planner_image_map.ipynb cell 2): cell = int((x - origin - cell/2) / cell) truncated toward zero,
@@ -210,14 +210,6 @@ __global__ __launch_bounds__(SM_THREADS) void check_grid_kernel(const GridCheckA
   a.labels[p] = hit ? 1.0f : 0.0f;
 }
 
-template <class Args>
-static int launch_check(void (*kernel)(Args), const Args& a, hipStream_t st) {
-  if (a.n == 0) return NFOPP_OK;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n + SM_THREADS - 1) / SM_THREADS)), dim3(SM_THREADS), 0, st, a);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
-}
-
 }  // namespace nfopp
 
 using namespace nfopp;
@@ -237,15 +229,33 @@ static int fill_common(CheckArgs* a, const float* poses_dev, int64_t n, int32_t 
   return fill_poses(a, poses_dev, n, pose_dim, labels_dev);
 }
 
-extern "C" int nfopp_check_collision_circle(const float* poses_dev, int64_t n, int32_t pose_dim,
-                                            const float* obstacles_dev, int32_t n_obstacles, float radius,
-                                            const float* bounds4, float* labels_dev, void* stream) {
+// The four point-cloud checkers: MODE 0 the disc of `radius`, MODE 1 the box; `reach` is looked at by the indexed box entry
+template <int MODE>
+static int check_points(SceneLookup lookup, const float* poses_dev, int64_t n, int32_t pose_dim, const float* obstacles_dev,
+                        int32_t n_obstacles, const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y, float cell_x0,
+                        float cell_y0, float cell_size, const float* box4, float radius, float reach, const float* bounds4,
+                        float* labels_dev, void* stream) {
   CheckArgs a = {};
   int rc = fill_common(&a, poses_dev, n, pose_dim, bounds4, labels_dev);
   if (rc) return rc;
-  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
-  a.cloud.points = obstacles_dev; a.cloud.n = n_obstacles; a.robot.radius = radius;
-  return launch_check(check_points_kernel<0>, a, (hipStream_t)stream);
+  NFOPP_REQUIRE(MODE == 0 || box4, "null box");
+  bool all_pairs;
+  rc = fill_scene(&a.scene, &all_pairs, lookup, obstacles_dev, n_obstacles, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0,
+                  cell_size, box4, radius, pose_dim);
+  if (rc) return rc;
+  if (lookup != SCENE_ALL_PAIRS && MODE == 0)
+    NFOPP_REQUIRE(cell_size >= radius && radius > 0.f, "the cell size must be at least the robot radius");
+  if (lookup != SCENE_ALL_PAIRS && MODE == 1)   // the reach the caller states must cover every corner of the box (up to its fp32 rounding)
+    NFOPP_REQUIRE(reach > 0.f && reach * 1.00001f >= box_corner(box4) && cell_size >= reach,
+                  "the cell size must be at least the robot's reach, and the reach must cover the corners of the box");
+  return launch_per_item<SM_THREADS>(all_pairs ? check_points_kernel<MODE> : check_points_cells_kernel<MODE>, n, stream, a);
+}
+
+extern "C" int nfopp_check_collision_circle(const float* poses_dev, int64_t n, int32_t pose_dim,
+                                            const float* obstacles_dev, int32_t n_obstacles, float radius,
+                                            const float* bounds4, float* labels_dev, void* stream) {
+  return check_points<0>(SCENE_ALL_PAIRS, poses_dev, n, pose_dim, obstacles_dev, n_obstacles, nullptr, 0, 0, 0.f, 0.f, 0.f,
+                         nullptr, radius, 0.f, bounds4, labels_dev, stream);
 }
 
 extern "C" int nfopp_check_collision_circle_cells(const float* poses_dev, int64_t n, int32_t pose_dim,
@@ -253,28 +263,15 @@ extern "C" int nfopp_check_collision_circle_cells(const float* poses_dev, int64_
                                                   const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y,
                                                   float cell_x0, float cell_y0, float cell_size, float radius,
                                                   const float* bounds4, float* labels_dev, void* stream) {
-  CheckArgs a = {};
-  int rc = fill_common(&a, poses_dev, n, pose_dim, bounds4, labels_dev);
-  if (rc) return rc;
-  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev, "bad obstacle index");
-  rc = fill_cell_index(&a.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size);
-  if (rc) return rc;
-  NFOPP_REQUIRE(cell_size >= radius && radius > 0.f, "the cell size must be at least the robot radius");
-  a.cloud.points = obstacles_sorted_dev; a.cloud.n = n_obstacles; a.robot.radius = radius;
-  return launch_check(check_points_cells_kernel<0>, a, (hipStream_t)stream);
+  return check_points<0>(SCENE_CHECKER_CELLS, poses_dev, n, pose_dim, obstacles_sorted_dev, n_obstacles, cell_start_dev,
+                         cells_x, cells_y, cell_x0, cell_y0, cell_size, nullptr, radius, 0.f, bounds4, labels_dev, stream);
 }
 
 extern "C" int nfopp_check_collision_rectangle(const float* poses_dev, int64_t n, const float* obstacles_dev,
                                                int32_t n_obstacles, const float* box4, const float* bounds4,
                                                float* labels_dev, void* stream) {
-  CheckArgs a = {};
-  int rc = fill_common(&a, poses_dev, n, 3, bounds4, labels_dev);
-  if (rc) return rc;
-  NFOPP_REQUIRE(box4, "null box");
-  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
-  a.cloud.points = obstacles_dev; a.cloud.n = n_obstacles;
-  set_box(&a.robot, box4);
-  return launch_check(check_points_kernel<1>, a, (hipStream_t)stream);
+  return check_points<1>(SCENE_ALL_PAIRS, poses_dev, n, 3, obstacles_dev, n_obstacles, nullptr, 0, 0, 0.f, 0.f, 0.f, box4,
+                         0.f, 0.f, bounds4, labels_dev, stream);
 }
 
 extern "C" int nfopp_check_collision_rectangle_cells(const float* poses_dev, int64_t n,
@@ -282,19 +279,8 @@ extern "C" int nfopp_check_collision_rectangle_cells(const float* poses_dev, int
                                                      const int32_t* cell_start_dev, int32_t cells_x, int32_t cells_y,
                                                      float cell_x0, float cell_y0, float cell_size, const float* box4,
                                                      float reach, const float* bounds4, float* labels_dev, void* stream) {
-  CheckArgs a = {};
-  int rc = fill_common(&a, poses_dev, n, 3, bounds4, labels_dev);
-  if (rc) return rc;
-  NFOPP_REQUIRE(box4, "null box");
-  NFOPP_REQUIRE(n_obstacles > 0 && obstacles_sorted_dev, "bad obstacle index");
-  rc = fill_cell_index(&a.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size);
-  if (rc) return rc;
-  // the reach the caller states must cover every corner of the box (up to its fp32 rounding)
-  NFOPP_REQUIRE(reach > 0.f && reach * 1.00001f >= box_corner(box4) && cell_size >= reach,
-                "the cell size must be at least the robot's reach, and the reach must cover the corners of the box");
-  a.cloud.points = obstacles_sorted_dev; a.cloud.n = n_obstacles;
-  set_box(&a.robot, box4);
-  return launch_check(check_points_cells_kernel<1>, a, (hipStream_t)stream);
+  return check_points<1>(SCENE_CHECKER_CELLS, poses_dev, n, 3, obstacles_sorted_dev, n_obstacles, cell_start_dev, cells_x,
+                         cells_y, cell_x0, cell_y0, cell_size, box4, 0.f, reach, bounds4, labels_dev, stream);
 }
 
 extern "C" int nfopp_check_collision_grid(const float* poses_dev, int64_t n, int32_t pose_dim, const uint8_t* grid_dev,
@@ -305,7 +291,7 @@ extern "C" int nfopp_check_collision_grid(const float* poses_dev, int64_t n, int
   if (rc) return rc;
   NFOPP_REQUIRE(grid_dev && rows > 1 && cols > 1 && cell_size > 0.0, "bad occupancy grid");
   a.grid = grid_dev; a.rows = rows; a.cols = cols; a.origin_x = origin_x; a.origin_y = origin_y; a.cell = cell_size;
-  return launch_check(check_grid_kernel, a, (hipStream_t)stream);
+  return launch_per_item<SM_THREADS>(check_grid_kernel, n, stream, a);
 }
 
 extern "C" int nfopp_sample_candidates(const float* prev_traj_dev, int64_t batch, int32_t n_waypoints, int32_t dim,

@@ -34,7 +34,7 @@ struct Segment {
 
 struct SweptArgs {
   const float* a; const float* b; long long n; int dim;
-  PointCloud cloud; Robot robot;
+  Scene scene;
   float horizon;
   float* value; int* index;
 };
@@ -55,8 +55,8 @@ __device__ __forceinline__ Segment load_segment(const SweptArgs& g, long long p)
   if (MODE == 1) {
     const float turn = g.b[p * g.dim + 2] - g.a[p * g.dim + 2];
     const float dth = fabsf(wrap_angle(turn));
-    s.delta = __builtin_fmaf(g.robot.reach, dth, s.len);
-    const float limit = 4.f * g.robot.reach;
+    s.delta = __builtin_fmaf(g.scene.robot.reach, dth, s.len);
+    const float limit = 4.f * g.scene.robot.reach;
     s.in_domain = s.delta <= limit && fabsf(turn) <= SW_MAX_TURN;
   }
   return s;
@@ -68,7 +68,7 @@ __device__ __forceinline__ Segment load_segment(const SweptArgs& g, long long p)
 // one subtraction of a per-segment constant is monotone, so it does not change which point wins).
 template <int MODE>
 __device__ __forceinline__ float segment_term(const SweptArgs& g, const Segment& s, float ox, float oy) {
-  if (MODE == 1) return g.robot.point_distance<1>(s.a, ox, oy) + g.robot.point_distance<1>(s.b, ox, oy);
+  if (MODE == 1) return g.scene.robot.point_distance<1>(s.a, ox, oy) + g.scene.robot.point_distance<1>(s.b, ox, oy);
   const float ax = ox - s.a.x, ay = oy - s.a.y;
   const float bx = ox - s.b.x, by = oy - s.b.y;
   float v = fminf(disc_distance(ax, ay), disc_distance(bx, by));
@@ -89,12 +89,21 @@ __device__ __forceinline__ void store_segment(const SweptArgs& g, long long p, c
   float v = best;
   int k = bestk;
   if (MODE == 1 && bestk >= 0) v = best - s.delta;
-  if (!s.finite || g.cloud.n == 0) { v = __builtin_inff(); k = -1; }
+  if (!s.finite || g.scene.cloud.n == 0) { v = __builtin_inff(); k = -1; }
   else if (!s.in_domain) { v = -__builtin_inff(); k = -1; }
   else if (!(v <= g.horizon)) { v = __builtin_inff(); k = -1; }
   g.value[p] = v;
   if (g.index) g.index[p] = k;
 }
+
+// what both entries do with a point: the smallest term of segment s so far, the smallest index among equals
+template <int MODE>
+struct SegmentMin {
+  const SweptArgs& g; const Segment& s; float best; int bestk;
+  __device__ __forceinline__ void operator()(float px, float py, int k, int) {
+    take_min(segment_term<MODE>(g, s, px, py), k, &best, &bestk);
+  }
+};
 
 // ---- all pairs ------------------------------------------------------------------------------------------------------
 template <int MODE>
@@ -104,12 +113,9 @@ __global__ __launch_bounds__(SW_THREADS) void swept_kernel(const SweptArgs g) {
   const bool valid = p < g.n;
   Segment s = {};
   if (valid) s = load_segment<MODE>(g, p);
-  float best = __builtin_inff();
-  int bestk = -1;
-  for_all_points<SW_THREADS>(g.cloud, ox, oy, [&](float px, float py, int k) {
-    take_min(segment_term<MODE>(g, s, px, py), k, &best, &bestk);
-  });
-  if (valid) store_segment<MODE>(g, p, s, best, bestk);
+  SegmentMin<MODE> least = {g, s, __builtin_inff(), -1};
+  for_all_points<SW_THREADS>(g.scene.cloud, ox, oy, least);
+  if (valid) store_segment<MODE>(g, p, s, least.best, least.bestk);
 }
 
 // ---- cell index: which cells a segment has to look at --------------------------------------------------------------------
@@ -127,23 +133,19 @@ __global__ __launch_bounds__(SW_THREADS) void swept_kernel(const SweptArgs g) {
 //      15 * 2^-24 |o - a| (csrc/clearance.hip, (3)), so |o - a| (1 - 15 * 2^-24) <= reach + (delta + h)(1 + 2 * 2^-24): the point
 //      lies within  R = (reach + delta + h)(1 + 2^-18)  of a's origin, a fortiori inside the bounding box of a and b
 //      inflated by R (the same holds about b; one rectangle serves both shapes).
-//  (3) From coordinates to cells.  Each bound w = min - R or max + R is formed in fp32 and then moved outward by
-//      4 * 2^-24 |w|, more than the rounding of its own two operations, so the fp32 bound encloses the exact one.
-//      CellIndex::axis_cell is a chain of monotone operations (correctly rounded subtraction and division, floor, clamp),
-//      and points and bounds go through that one function: lo <= ox <= hi implies cell(lo) <= cell(ox) <= cell(hi), for a
-//      point clamped into a border cell too.  One further cell is visited on each side: it costs a few points per segment
-//      and keeps the coverage from resting on the last bit of (1) to (3).
-//  Cells are formed only through CellIndex::cell and row_range; the loops run over at most cells_y rows of the index.
+//  (3) From coordinates to cells: CellIndex::window_of_box of csrc/point_cloud.h, where the rectangle is formed and the
+//      argument stands -- bounds moved outward, monotone cell numbers, one further cell per side.
 template <int MODE>
 __device__ __forceinline__ float cover_radius(const SweptArgs& g, const Segment& s) {
   if (MODE == 0) return __builtin_fmaf(3.814697265625e-06f, g.horizon + s.len, g.horizon);
-  const float reach_delta = g.robot.reach + s.delta;
+  const float reach_delta = g.scene.robot.reach + s.delta;
   const float r = reach_delta + g.horizon;
   return r * SW_COVER;
 }
 
-__device__ __forceinline__ float outward(float w, float sign) {   // w moved by 4 * 2^-24 |w| towards sign * inf
-  return __builtin_fmaf(fabsf(w), sign * 2.384185791015625e-07f, w);
+template <int MODE>
+__device__ __forceinline__ CellWindow cover_window(const SweptArgs& g, const Segment& s) {
+  return g.scene.cloud.index.window_of_box(s.a.x, s.a.y, s.b.x, s.b.y, cover_radius<MODE>(g, s));
 }
 
 template <int MODE>
@@ -151,26 +153,9 @@ __global__ __launch_bounds__(SW_THREADS) void swept_cells_kernel(const SweptArgs
   const long long p = blockIdx.x * (long long)SW_THREADS + threadIdx.x;
   if (p >= g.n) return;
   const Segment s = load_segment<MODE>(g, p);
-  float best = __builtin_inff();
-  int bestk = -1;
-  if (s.finite && s.in_domain) {
-    const float r = cover_radius<MODE>(g, s);
-    const float lox = outward(fminf(s.a.x, s.b.x) - r, -1.f), hix = outward(fmaxf(s.a.x, s.b.x) + r, 1.f);
-    const float loy = outward(fminf(s.a.y, s.b.y) - r, -1.f), hiy = outward(fmaxf(s.a.y, s.b.y) + r, 1.f);
-    int x_lo, y_lo, x_hi, y_hi;
-    g.cloud.index.cell(lox, loy, &x_lo, &y_lo);
-    g.cloud.index.cell(hix, hiy, &x_hi, &y_hi);
-    x_lo = max(x_lo - 1, 0); x_hi = min(x_hi + 1, g.cloud.index.cells_x - 1);
-    y_lo = max(y_lo - 1, 0); y_hi = min(y_hi + 1, g.cloud.index.cells_y - 1);
-    const float* pt = g.cloud.points;
-    for (int yy = y_lo; yy <= y_hi; ++yy) {
-      int k, k1;
-      g.cloud.index.row_range(yy, x_lo, x_hi, &k, &k1);
-      for (; k < k1; ++k)
-        take_min(segment_term<MODE>(g, s, pt[2 * (long long)k], pt[2 * (long long)k + 1]), k, &best, &bestk);
-    }
-  }
-  store_segment<MODE>(g, p, s, best, bestk);
+  SegmentMin<MODE> least = {g, s, __builtin_inff(), -1};
+  if (s.finite && s.in_domain) for_window_points<false>(g.scene.cloud, cover_window<MODE>(g, s), least);
+  store_segment<MODE>(g, p, s, least.best, least.bestk);
 }
 
 // ---- path reduction -------------------------------------------------------------------------------------------------
@@ -265,20 +250,10 @@ struct RefineArgs {
 // the comparison store_segment<1> leaves to its reader: the written value is > slack.  `best` = +inf without a point.
 __device__ __forceinline__ bool piece_certified(const SweptArgs& g, const Segment& s, float best) {
   if (!s.finite) return false;              // not reached below: sub-poses of finite ends are finite (|coordinates| < 2^60)
-  if (g.cloud.n == 0) return true;
+  if (g.scene.cloud.n == 0) return true;
   if (!s.in_domain) return false;
   const float v = best - s.delta;
   return v > g.horizon;
-}
-
-__device__ __forceinline__ void cover_cells(const SweptArgs& g, const Segment& s, int* x_lo, int* y_lo, int* x_hi, int* y_hi) {
-  const float r = cover_radius<1>(g, s);
-  const float lox = outward(fminf(s.a.x, s.b.x) - r, -1.f), hix = outward(fmaxf(s.a.x, s.b.x) + r, 1.f);
-  const float loy = outward(fminf(s.a.y, s.b.y) - r, -1.f), hiy = outward(fmaxf(s.a.y, s.b.y) + r, 1.f);
-  g.cloud.index.cell(lox, loy, x_lo, y_lo);
-  g.cloud.index.cell(hix, hiy, x_hi, y_hi);
-  *x_lo = max(*x_lo - 1, 0); *x_hi = min(*x_hi + 1, g.cloud.index.cells_x - 1);
-  *y_lo = max(*y_lo - 1, 0); *y_hi = min(*y_hi + 1, g.cloud.index.cells_y - 1);
 }
 
 __device__ __forceinline__ void store_root(const RefineArgs& g, long long p, const Segment& s, bool hit_a, bool hit_b, float best) {
@@ -294,71 +269,53 @@ __device__ __forceinline__ void store_root(const RefineArgs& g, long long p, con
   if (g.depth) g.depth[p] = 0;
 }
 
+// what both root kernels do with a point: steps 1 and 2 of the definition and the root piece's minimum
+struct RootTerms {
+  const SweptArgs& g; const Segment& s; float best; bool hit_a, hit_b;
+  __device__ __forceinline__ void operator()(float px, float py, int, int) {
+    best = fminf(best, segment_term<1>(g, s, px, py));
+    hit_a |= g.scene.robot.hits<1>(s.a, px, py);
+    hit_b |= g.scene.robot.hits<1>(s.b, px, py);
+  }
+};
+
 __global__ __launch_bounds__(SW_THREADS) void refine_root_kernel(const RefineArgs g) {
   __shared__ float ox[SW_THREADS], oy[SW_THREADS];
   const long long p = blockIdx.x * (long long)SW_THREADS + threadIdx.x;
   const bool valid = p < g.seg.n;
   Segment s = {};
   if (valid) s = load_segment<1>(g.seg, p);
-  float best = __builtin_inff();
-  bool hit_a = false, hit_b = false;
-  for_all_points<SW_THREADS>(g.seg.cloud, ox, oy, [&](float px, float py, int) {
-    best = fminf(best, segment_term<1>(g.seg, s, px, py));
-    hit_a |= g.seg.robot.hits<1>(s.a, px, py);
-    hit_b |= g.seg.robot.hits<1>(s.b, px, py);
-  });
-  if (valid) store_root(g, p, s, hit_a, hit_b, best);
+  RootTerms root = {g.seg, s, __builtin_inff(), false, false};
+  for_all_points<SW_THREADS>(g.seg.scene.cloud, ox, oy, root);
+  if (valid) store_root(g, p, s, root.hit_a, root.hit_b, root.best);
 }
 
 __global__ __launch_bounds__(SW_THREADS) void refine_root_cells_kernel(const RefineArgs g) {
   const long long p = blockIdx.x * (long long)SW_THREADS + threadIdx.x;
   if (p >= g.seg.n) return;
   const Segment s = load_segment<1>(g.seg, p);
-  float best = __builtin_inff();
-  bool hit_a = false, hit_b = false;
-  if (s.finite) {
-    int x_lo, y_lo, x_hi, y_hi;
-    cover_cells(g.seg, s, &x_lo, &y_lo, &x_hi, &y_hi);
-    const float* pt = g.seg.cloud.points;
-    for (int yy = y_lo; yy <= y_hi; ++yy) {
-      int k, k1;
-      g.seg.cloud.index.row_range(yy, x_lo, x_hi, &k, &k1);
-      for (; k < k1; ++k) {
-        const float px = pt[2 * (long long)k], py = pt[2 * (long long)k + 1];
-        best = fminf(best, segment_term<1>(g.seg, s, px, py));
-        hit_a |= g.seg.robot.hits<1>(s.a, px, py);
-        hit_b |= g.seg.robot.hits<1>(s.b, px, py);
-      }
-    }
-  }
-  store_root(g, p, s, hit_a, hit_b, best);
+  RootTerms root = {g.seg, s, __builtin_inff(), false, false};
+  if (s.finite) for_window_points<false>(g.seg.scene.cloud, cover_window<1>(g.seg, s), root);
+  store_root(g, p, s, root.hit_a, root.hit_b, root.best);
 }
 
-// the candidate points of one segment as a wave sees them: f(ox, oy) for each, the 64 lanes taking them in turn
+// The candidate points of one segment as a wave sees them.  CELLS: candidate j is the jth point for_window_points comes to
+// in the segment's window; else it is point j of the cloud.  Candidates j < RF_STAGE are kept in LDS, the others are read
+// from global memory at every visit.
 struct Candidates {
-  const float* lx; const float* ly;   // the first min(total, RF_STAGE) of them, in LDS
+  const float* lx; const float* ly;   // the first min(total, RF_STAGE) of them
   int total;
-  int x_lo, y_lo, x_hi, y_hi;         // CELLS: the rows they come from
+  CellWindow window;      // CELLS
 };
 
+// f(ox, oy) for each candidate, the 64 lanes taking them in turn
 template <bool CELLS, class F>
 __device__ __forceinline__ void for_candidates(const PointCloud& cloud, const Candidates& c, int lane, F&& f) {
-  const int staged = min(c.total, RF_STAGE);
-  for (int k = lane; k < staged; k += 64) f(c.lx[k], c.ly[k]);
+  for (int k = lane; k < min(c.total, RF_STAGE); k += 64) f(c.lx[k], c.ly[k]);
   if (c.total <= RF_STAGE) return;
   const float* pt = cloud.points;
-  if (!CELLS) {
-    for (int k = RF_STAGE + lane; k < c.total; k += 64) f(pt[2 * (long long)k], pt[2 * (long long)k + 1]);
-    return;
-  }
-  int base = 0;                        // candidates in front of this row
-  for (int yy = c.y_lo; yy <= c.y_hi; ++yy) {
-    int k0, k1;
-    cloud.index.row_range(yy, c.x_lo, c.x_hi, &k0, &k1);
-    const int skip = min(max(RF_STAGE - base, 0), k1 - k0);   // of this row, already visited in LDS
-    for (int k = k0 + skip + lane; k < k1; k += 64) f(pt[2 * (long long)k], pt[2 * (long long)k + 1]);
-    base += k1 - k0;
-  }
+  if (CELLS) for_window_points<true, RF_STAGE>(cloud, c.window, [&](float px, float py, int, int) { f(px, py); });
+  else for (int k = RF_STAGE + lane; k < c.total; k += 64) f(pt[2 * (long long)k], pt[2 * (long long)k + 1]);
 }
 
 // sub-pose i * 2^-d of the motion from a to b, as three floats: the ends as loaded, the others by one fma per component
@@ -377,7 +334,7 @@ __global__ __launch_bounds__(64) void refine_walk_kernel(const RefineArgs g) {
   __shared__ float lx[RF_STAGE], ly[RF_STAGE];
   const int lane = threadIdx.x;
   const long long waves = gridDim.x;
-  const PointCloud& cloud = g.seg.cloud;
+  const PointCloud& cloud = g.seg.scene.cloud;
   // wave w owns the segments p = w (mod waves): neighbours along a path, which tend to be hard together, go to different waves
   for (long long base = blockIdx.x; base < g.seg.n; base += 64 * waves) {
     const long long mine = base + lane * waves;
@@ -389,26 +346,12 @@ __global__ __launch_bounds__(64) void refine_walk_kernel(const RefineArgs g) {
       for (int k = 0; k < 3; ++k) { a3[k] = g.seg.a[p * 3 + k]; b3[k] = g.seg.b[p * 3 + k]; }
       const Segment root = load_segment<1>(g.seg, p);
       const float dth = wrap_angle(b3[2] - a3[2]);
-      Candidates c = {lx, ly, cloud.n, 0, 0, 0, 0};
+      Candidates c = {lx, ly, cloud.n, {}};
+      if (CELLS) c.window = cover_window<1>(g.seg, root);
+      const auto keep = [&](float px, float py, int, int j) { lx[j] = px; ly[j] = py; };
       __syncthreads();                 // the previous segment's reads of lx, ly are done (one wave: a wait, no stall)
-      if (CELLS) {
-        cover_cells(g.seg, root, &c.x_lo, &c.y_lo, &c.x_hi, &c.y_hi);
-        c.total = 0;
-        for (int yy = c.y_lo; yy <= c.y_hi; ++yy) {
-          int k0, k1;
-          cloud.index.row_range(yy, c.x_lo, c.x_hi, &k0, &k1);
-          for (int k = k0 + lane; k < k1 && c.total + (k - k0) < RF_STAGE; k += 64) {
-            lx[c.total + (k - k0)] = cloud.points[2 * (long long)k];
-            ly[c.total + (k - k0)] = cloud.points[2 * (long long)k + 1];
-          }
-          c.total += k1 - k0;
-        }
-      } else {
-        for (int k = lane; k < min(c.total, RF_STAGE); k += 64) {
-          lx[k] = cloud.points[2 * (long long)k];
-          ly[k] = cloud.points[2 * (long long)k + 1];
-        }
-      }
+      if (CELLS) c.total = for_window_points<true, 0, RF_STAGE>(cloud, c.window, keep);
+      else for (int k = lane; k < min(c.total, RF_STAGE); k += 64) keep(cloud.points[2 * k], cloud.points[2 * k + 1], k, k);
       __syncthreads();
       // the pre-order walk; the root piece was evaluated, and found wanting, in pass 1
       int d = 0, deepest = 0, evals = 1;
@@ -444,7 +387,7 @@ __global__ __launch_bounds__(64) void refine_walk_kernel(const RefineArgs g) {
             sub_pose(a3, b3, root.ex, root.ey, dth, 2 * i + 1, d + 1, pm);
             const Pose mid = load_pose<1>(pm, 3, 0);
             bool inside = false;
-            for_candidates<CELLS>(cloud, c, lane, [&](float px, float py) { inside |= g.seg.robot.hits<1>(mid, px, py); });
+            for_candidates<CELLS>(cloud, c, lane, [&](float px, float py) { inside |= g.seg.scene.robot.hits<1>(mid, px, py); });
             if (__ballot(inside)) {
               hit = true;
               at = (float)(2 * i + 1) * __int_as_float((127 - (d + 1)) << 23);
@@ -524,42 +467,27 @@ static int swept_refine(bool cells, const float* a_dev, const float* b_dev, int6
   NFOPP_REQUIRE(n <= (int64_t)0x7fffffff * SW_THREADS, "too many segments for one call");
   NFOPP_REQUIRE(max_depth >= 0 && max_depth <= 20, "max_depth must be between 0 and 20");
   NFOPP_REQUIRE(node_budget >= 1, "node_budget must be >= 1");
-  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
   RefineArgs g = {};
-  if (cells) {
-    const int rc = fill_cell_index(&g.seg.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size,
-                                   n_obstacles > 0);
-    if (rc) return rc;
-    NFOPP_REQUIRE((long long)cells_x * cells_y <= MAX_INDEX_CELLS, "the index holds between 1 and 65536 cells");
-  }
+  bool all_pairs;   // also where there is nothing to search: every finite segment is certified at its root
+  int rc = fill_scene(&g.seg.scene, &all_pairs, cells ? SCENE_CELLS : SCENE_ALL_PAIRS, obstacles_dev, n_obstacles,
+                      cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size, box4, 0.f, pose_dim);
+  if (rc) return rc;
   if (n == 0) return NFOPP_OK;
   NFOPP_REQUIRE(a_dev && b_dev && status_dev, "null device pointer");
-  g.seg.a = a_dev; g.seg.b = b_dev; g.seg.n = n; g.seg.dim = 3; g.seg.cloud.points = obstacles_dev; g.seg.cloud.n = n_obstacles;
-  set_box(&g.seg.robot, box4);
+  g.seg.a = a_dev; g.seg.b = b_dev; g.seg.n = n; g.seg.dim = 3;
   g.seg.horizon = nfopp_swept_slack(box4);
   g.max_depth = max_depth; g.budget = node_budget;
   g.status = status_dev; g.s = s_dev; g.depth = depth_dev;
-  if (n_obstacles == 0) cells = false;   // nothing to search: every finite segment is certified at its root
-  const hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((n + SW_THREADS - 1) / SW_THREADS);
-  if (cells) hipLaunchKernelGGL(refine_root_cells_kernel, dim3(grid), dim3(SW_THREADS), 0, st, g);
-  else hipLaunchKernelGGL(refine_root_kernel, dim3(grid), dim3(SW_THREADS), 0, st, g);
-  NFOPP_HIP(hipGetLastError());
+  rc = launch_per_item<SW_THREADS>(all_pairs ? refine_root_kernel : refine_root_cells_kernel, n, stream, g);
+  if (rc) return rc;
   if (max_depth == 0 || node_budget == 1 || n_obstacles == 0) return NFOPP_OK;   // pass 1 left nothing PENDING
   const long long groups = (n + 63) / 64;
   const long long waves = (long long)query_cus() * 16;
   const unsigned wgrid = (unsigned)(groups < waves ? groups : waves);
-  if (cells) hipLaunchKernelGGL(refine_walk_kernel<true>, dim3(wgrid), dim3(64), 0, st, g);
-  else hipLaunchKernelGGL(refine_walk_kernel<false>, dim3(wgrid), dim3(64), 0, st, g);
+  if (all_pairs) hipLaunchKernelGGL(refine_walk_kernel<false>, dim3(wgrid), dim3(64), 0, (hipStream_t)stream, g);
+  else hipLaunchKernelGGL(refine_walk_kernel<true>, dim3(wgrid), dim3(64), 0, (hipStream_t)stream, g);
   NFOPP_HIP(hipGetLastError());
   return NFOPP_OK;
-}
-
-template <int MODE>
-static void launch_swept(const SweptArgs& g, bool cells, hipStream_t st) {
-  const unsigned grid = (unsigned)((g.n + SW_THREADS - 1) / SW_THREADS);
-  if (cells) hipLaunchKernelGGL(swept_cells_kernel<MODE>, dim3(grid), dim3(SW_THREADS), 0, st, g);
-  else hipLaunchKernelGGL(swept_kernel<MODE>, dim3(grid), dim3(SW_THREADS), 0, st, g);
 }
 
 static int swept(bool cells, const float* a_dev, const float* b_dev, int64_t n, int32_t pose_dim,
@@ -568,26 +496,19 @@ static int swept(bool cells, const float* a_dev, const float* b_dev, int64_t n, 
                  float* value_dev, int32_t* index_dev, void* stream) {
   NFOPP_REQUIRE(n >= 0 && (pose_dim == 2 || pose_dim == 3), "need n >= 0 and pose_dim 2 or 3");
   NFOPP_REQUIRE(n <= (int64_t)0x7fffffff * SW_THREADS, "too many segments for one call");
+  // fill_scene asks this too; here it has always been asked in front of the horizon, and stays there
   NFOPP_REQUIRE(!box4 || pose_dim == 3, "the box robot needs poses with a heading (pose_dim 3)");
   NFOPP_REQUIRE(horizon >= 0.f, "the horizon must be >= 0");   // false for a NaN too
-  NFOPP_REQUIRE(n_obstacles >= 0 && (n_obstacles == 0 || obstacles_dev), "bad obstacle array");
   SweptArgs g = {};
-  if (cells) {
-    const int rc = fill_cell_index(&g.cloud.index, cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size,
-                                   n_obstacles > 0);
-    if (rc) return rc;
-    NFOPP_REQUIRE((long long)cells_x * cells_y <= MAX_INDEX_CELLS, "the index holds between 1 and 65536 cells");
-  }
+  bool all_pairs;   // also where there is nothing to search: the all-pairs kernel writes +inf / -1
+  const int rc = fill_scene(&g.scene, &all_pairs, cells ? SCENE_CELLS : SCENE_ALL_PAIRS, obstacles_dev, n_obstacles,
+                            cell_start_dev, cells_x, cells_y, cell_x0, cell_y0, cell_size, box4, 0.f, pose_dim);
+  if (rc) return rc;
   if (n == 0) return NFOPP_OK;
   NFOPP_REQUIRE(a_dev && b_dev && value_dev, "null device pointer");
-  g.a = a_dev; g.b = b_dev; g.n = n; g.dim = pose_dim; g.cloud.points = obstacles_dev; g.cloud.n = n_obstacles;
-  g.horizon = horizon; g.value = value_dev; g.index = index_dev;
-  if (box4) set_box(&g.robot, box4);
-  if (n_obstacles == 0) cells = false;   // nothing to search: the all-pairs kernel writes +inf / -1
-  if (box4) launch_swept<1>(g, cells, (hipStream_t)stream);
-  else launch_swept<0>(g, cells, (hipStream_t)stream);
-  NFOPP_HIP(hipGetLastError());
-  return NFOPP_OK;
+  g.a = a_dev; g.b = b_dev; g.n = n; g.dim = pose_dim; g.horizon = horizon; g.value = value_dev; g.index = index_dev;
+  if (box4) return launch_per_item<SW_THREADS>(all_pairs ? swept_kernel<1> : swept_cells_kernel<1>, n, stream, g);
+  return launch_per_item<SW_THREADS>(all_pairs ? swept_kernel<0> : swept_cells_kernel<0>, n, stream, g);
 }
 
 }  // namespace nfopp

@@ -174,6 +174,31 @@ def test_max_depth_0_is_the_existing_certificate(name, kind):
         assert same([t[decided] for t in deeper], [t[decided] for t in runs[0][0]])
 
 
+@pytest.mark.parametrize("rows", cases.BEYOND, ids=lambda rows: "%d_%d_%d" % rows)
+def test_indexed_walk_beyond_the_staged_candidates(rows):
+    """Every segment's window is the whole 3 x 3 index, which holds more than the 1024 candidates a wave keeps in LDS, and
+    the points that decide the segments are candidates beyond them: the indexed walk reads them from global memory, row by
+    row, from where the staged ones end -- between two rows, inside the last row, inside the first (the preconditions are
+    swept_refine_cases.beyond_the_stage's)."""
+    name, points, geom, box, a, b, refs = cases.beyond_the_stage(rows)
+    tgc.CLOUDS[name] = (points, geom)          # Entries reads the cloud by name
+    try:
+        entries = Entries(name)
+    finally:
+        del tgc.CLOUDS[name]
+    assert entries.box == box and entries.cloud.n == sum(rows)
+    da, db = dev(a), dev(b)
+    for max_depth in DEPTHS:
+        brute, cells = entries.run(False, da, db, max_depth), entries.run(True, da, db, max_depth)
+        assert same(brute, cells), max_depth
+        status, s, depth = brute
+        want_status, want_s, want_depth, ambiguous = refs[max_depth]
+        differ = ~ambiguous & ((status != want_status) | (s != want_s) | (depth != want_depth))
+        print("%s depth %d: ambiguous %d, device free / hit / undecided %s, differing %d"
+              % (name, max_depth, ambiguous.sum(), np.bincount(status, minlength=3).tolist(), differ.sum()))
+        assert not differ.any(), (max_depth, np.flatnonzero(differ)[:8])
+
+
 # ---- against the restatement -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("name", NAMES)
