@@ -80,21 +80,52 @@ __device__ __forceinline__ SegOut segment_terms(const nfopp_traj_hyper& hp, floa
   return o;
 }
 
-// collision sample j of this trajectory: returns gamma (upstream on the logit), tanh(logit), softplus value
+// collision sample j of this trajectory: returns gamma (upstream on the logit), tanh(logit), softplus value (a loss term only:
+// not formed without TERMS)
+template <bool TERMS>
 __device__ __forceinline__ void collision_terms(const nfopp_traj_hyper& hp, float logit, float cm_i, float* gamma,
                                                 float* th_l, float* sp) {
   const float beta = hp.collision_beta;
   const float bl = logit * beta;
   const float z = expf(bl);
   const bool lin = bl > 20.0f;  // torch softplus threshold
-  *sp = lin ? logit : log1pf(z) / beta;
+  *sp = !TERMS ? 0.0f : lin ? logit : log1pf(z) / beta;
   const float dsp = lin ? 1.0f : z / (z + 1.0f);
   const float th = tanhf(logit);
   *th_l = th;
   *gamma = hp.collision_weight * dsp + cm_i * (1.0f - th * th);
 }
 
-template <int D>
+// Staging of the boundary waypoints' band columns: one flight = K2_BND_FLIGHT taps k0, k0 + TU_WAVES, ... of one column per
+// lane, held in registers between the loads and the LDS writes (12 x 4 waves covers 2W+1 = 43 at the benchmark's weight and
+// every interior shape with up to 64 boundary columns; larger tables take further flights).
+constexpr int TU_WAVES = TU_THREADS / 64;
+constexpr int K2_BND_FLIGHT = 12;
+
+// waypoint of staged column c: the NB_LO waypoints in front of the interior, then those behind it
+__device__ __forceinline__ int bnd_waypoint(int c, int nb_lo, int interior_hi) {
+  return c < nb_lo ? c : interior_hi + (c - nb_lo);
+}
+
+__device__ __forceinline__ void bnd_load(float (&r)[K2_BND_FLIGHT], const float* band, int w, int k0, int taps, int N) {
+#pragma unroll
+  for (int j = 0; j < K2_BND_FLIGHT; ++j) {
+    const int k = min(k0 + TU_WAVES * j, taps - 1);  // past the last tap: a load inside the table, not written below
+    r[j] = band[k * N + w];
+  }
+}
+
+__device__ __forceinline__ void bnd_store(const float (&r)[K2_BND_FLIGHT], float* column, int k0, int taps, bool in_table) {
+#pragma unroll
+  for (int j = 0; j < K2_BND_FLIGHT; ++j) {
+    const int k = k0 + TU_WAVES * j;
+    if (in_table && k < taps) column[k] = r[j];
+  }
+}
+
+// TERMS: the per-trajectory loss terms are asked for (a.terms is set).  The planner's own step does not ask: the softplus
+// values, the squared terms and the final block reduction form no part of the state and are not computed then.
+template <int D, bool TERMS>
 __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUpdateArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int N = a.n;
@@ -111,26 +142,30 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
   const nfopp_traj_hyper& hp = a.hp;
   const int tid = threadIdx.x;
 
-  // once per workgroup: preconditioner coefficients (the boundary waves used to fetch their 2W+1 coefficients from global
-  // memory inside the band loop, 4 in flight: 27 % of the kernel) and the zero rows around the gradient
-  if (a.interior_hi > a.interior_lo)
-    for (int k = tid; k <= 2 * W; k += TU_THREADS) COEF[k] = a.hinv_band[(long long)k * N + a.interior_lo];
-  for (int idx = tid; idx < NB * (2 * W + 1); idx += TU_THREADS) {
-    const int k = idx / NB, c = idx - k * NB;                 // consecutive threads: consecutive columns of one band row
-    const int w = c < NB_LO ? c : a.interior_hi + (c - NB_LO);
-    BND[c * (2 * W + 1) + k] = a.hinv_band[(long long)k * N + w];
-  }
-  for (int k = tid; k < W * D; k += TU_THREADS) { GP[k] = 0.0f; GP[(N + W) * D + k] = 0.0f; }
-
   // one trajectory per workgroup (walking several in a row measured slower: nothing overlaps between a workgroup's
   // trajectories, and the loop costs 36 VGPRs = one wave per SIMD)
   const long long b = blockIdx.x;
-  if (a.active && !a.active[b]) return;  // retired trajectory (uniform per workgroup)
+  if (a.active && !a.active[b]) return;  // retired trajectory (uniform per workgroup, before any barrier)
+
+  // Everything this workgroup reads before its first barrier is ISSUED here, into registers, and written to LDS below: the
+  // interior coefficients, the boundary band columns, this thread's prefetch and the state.  One exposure to the memory
+  // latency for all of them when the boundary table is one flight (NB <= 64 columns, 2W+1 <= 4 * K2_BND_FLIGHT taps) and
+  // N <= 256; what lies beyond goes in further trips after the LDS writes.
+  const int taps = 2 * W + 1;
+  const bool has_interior = a.interior_hi > a.interior_lo;
+  // Boundary columns (the boundary waves used to fetch their 2W+1 coefficients from global memory inside the band loop, 4 in
+  // flight: 27 % of the kernel).  Taps by wave (k = wave, wave + 4, ...: scalar, and so is k * N), columns by lane; 32-bit
+  // indexing: N * (2W+1) words are at most a few MB.  Loads beyond the table are clamped into it and not written.
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  float bnd_r[K2_BND_FLIGHT];
+  if (NB > 0) bnd_load(bnd_r, a.hinv_band, bnd_waypoint(lane < NB ? lane : NB - 1, NB_LO, a.interior_hi), wave, taps, N);
+  float coef_r = 0.f;
+  if (has_interior && tid < taps) coef_r = a.hinv_band[tid * N + a.interior_lo];
 
   float* traj = a.traj + b * N * D;
   // This thread's first waypoint (w = tid) needs two draws, two ONF records and its Adam moments from global memory.  Issued
-  // here, with the state loads, they cost ONE exposure to the memory latency instead of one per phase (the loads cannot
-  // move across the barriers by themselves).  Waypoints beyond the first pass (N > 256) load where they are used.
+  // here, with the state loads, they cost no exposure to the memory latency of their own (the loads cannot move across the
+  // barriers by themselves).  Waypoints beyond the first pass (N > 256) load where they are used.
   const float* tb = a.t + b * (N - 1);
   const float* onf = a.onf + b * (N - 1) * 4;
   float* am = a.adam_m + b * N * D;
@@ -145,15 +180,42 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
 #pragma unroll
     for (int d = 0; d < D; ++d) { pf_m[d] = am[tid * D + d]; pf_v[d] = av[tid * D + d]; }
   }
-  for (int k = tid; k < N * D; k += TU_THREADS) Q[D + k] = traj[k];
-  if (tid < D) {
-    Q[tid] = a.start[b * D + tid];
-    Q[(N + 1) * D + tid] = a.goal[b * D + tid];
-  }
+  // state: the first D trips of the trajectory, two of lambda (N + 1 = 257 at the benchmark shape) and one of cm
+  float st_q[D], st_lam0 = 0.f, st_lam1 = 0.f, st_cm = 0.f, st_start = 0.f, st_goal = 0.f;
+#pragma unroll
+  for (int d = 0; d < D; ++d) { const int k = tid + d * TU_THREADS; st_q[d] = k < N * D ? traj[k] : 0.f; }
+  if (tid < D) { st_start = a.start[b * D + tid]; st_goal = a.goal[b * D + tid]; }
   if (D == 3) {
-    for (int k = tid; k <= N; k += TU_THREADS) LAM[k] = a.lam[b * (N + 1) + k];
-    for (int k = tid; k < N; k += TU_THREADS) CM[k] = a.cm[b * N + k];
+    if (tid <= N) st_lam0 = a.lam[b * (N + 1) + tid];
+    if (tid + TU_THREADS <= N) st_lam1 = a.lam[b * (N + 1) + tid + TU_THREADS];
+    if (tid < N) st_cm = a.cm[b * N + tid];
   }
+
+  // the LDS writes, in the order of issue; then what did not fit the first flight, and the zero rows around the gradient
+  if (NB > 0) bnd_store(bnd_r, BND + lane * taps, wave, taps, lane < NB);
+  if (has_interior && tid < taps) COEF[tid] = coef_r;
+#pragma unroll
+  for (int d = 0; d < D; ++d) { const int k = tid + d * TU_THREADS; if (k < N * D) Q[D + k] = st_q[d]; }
+  if (tid < D) { Q[tid] = st_start; Q[(N + 1) * D + tid] = st_goal; }
+  if (D == 3) {
+    if (tid <= N) LAM[tid] = st_lam0;
+    if (tid + TU_THREADS <= N) LAM[tid + TU_THREADS] = st_lam1;
+    if (tid < N) CM[tid] = st_cm;
+  }
+  for (int c0 = 0; c0 < NB; c0 += 64)
+    for (int k0 = wave + (c0 == 0 ? TU_WAVES * K2_BND_FLIGHT : 0); k0 < taps; k0 += TU_WAVES * K2_BND_FLIGHT) {
+      const int c = c0 + lane;
+      bnd_load(bnd_r, a.hinv_band, bnd_waypoint(c < NB ? c : NB - 1, NB_LO, a.interior_hi), k0, taps, N);
+      bnd_store(bnd_r, BND + c * taps, k0, taps, c < NB);
+    }
+  if (has_interior)
+    for (int k = tid + TU_THREADS; k < taps; k += TU_THREADS) COEF[k] = a.hinv_band[k * N + a.interior_lo];
+  for (int k = tid + D * TU_THREADS; k < N * D; k += TU_THREADS) Q[D + k] = traj[k];
+  if (D == 3) {
+    for (int k = tid + 2 * TU_THREADS; k <= N; k += TU_THREADS) LAM[k] = a.lam[b * (N + 1) + k];
+    for (int k = tid + TU_THREADS; k < N; k += TU_THREADS) CM[k] = a.cm[b * N + k];
+  }
+  for (int k = tid; k < W * D; k += TU_THREADS) { GP[k] = 0.0f; GP[(N + W) * D + k] = 0.0f; }
   __syncthreads();
 
   // (staging t / the ONF records in LDS with the state loads measured slower, twice: round 1 and round 2; round 3 keeps
@@ -198,7 +260,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
         const float4 o = first ? pf_o0 : reinterpret_cast<const float4*>(onf)[w];
         const float cm_i = cm[w + 1] * (1.0f - tj) + cm_c * tj;
         float gamma, thl, sp;
-        collision_terms(hp, o.x, cm_i, &gamma, &thl, &sp);
+        collision_terms<TERMS>(hp, o.x, cm_i, &gamma, &thl, &sp);
         terms[2] += sp; terms[6] += cm_i * thl;
         gx += tj * (gamma * o.y); gy += tj * (gamma * o.z); gth += tj * (gamma * o.w);
         g_cm += tj * thl;
@@ -209,7 +271,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
         const float4 o = first ? pf_o1 : reinterpret_cast<const float4*>(onf)[w - 1];
         const float cm_i = cm_c * (1.0f - tj) + cm[w - 1] * tj;
         float gamma, thl, sp;
-        collision_terms(hp, o.x, cm_i, &gamma, &thl, &sp);
+        collision_terms<TERMS>(hp, o.x, cm_i, &gamma, &thl, &sp);
         const float omt = 1.0f - tj;
         gx += omt * (gamma * o.y); gy += omt * (gamma * o.z); gth += omt * (gamma * o.w);
         g_cm += omt * thl;
@@ -237,7 +299,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
         const float tj = first ? pf_t0 : tb[w];
         const float4 o = first ? pf_o0 : reinterpret_cast<const float4*>(onf)[w];
         float gamma, thl, sp;
-        collision_terms(hp, o.x, 0.0f, &gamma, &thl, &sp);
+        collision_terms<TERMS>(hp, o.x, 0.0f, &gamma, &thl, &sp);
         terms[2] += sp;
         gx += tj * (gamma * o.y); gy += tj * (gamma * o.z);
       }
@@ -246,7 +308,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
         const float tj = first ? pf_t1 : tb[w - 1];
         const float4 o = first ? pf_o1 : reinterpret_cast<const float4*>(onf)[w - 1];
         float gamma, thl, sp;
-        collision_terms(hp, o.x, 0.0f, &gamma, &thl, &sp);
+        collision_terms<TERMS>(hp, o.x, 0.0f, &gamma, &thl, &sp);
         const float omt = 1.0f - tj;
         gx += omt * (gamma * o.y); gy += omt * (gamma * o.z);
       }
@@ -299,7 +361,7 @@ __global__ __launch_bounds__(TU_THREADS, 1) void traj_update_kernel(const TrajUp
     }
   }
 
-  if (a.terms) {
+  if (TERMS) {
     block_reduce<WAVES_FROM_BLOCKDIM>(terms, 0.f, Plus(), scratch);
     if (tid == 0) {
       float* o = a.terms + b * NFOPP_NUM_TERMS;
@@ -346,6 +408,8 @@ extern "C" int nfopp_traj_update(const nfopp_traj_hyper* hp, int64_t batch, int3
   const size_t lds = (size_t)((n_waypoints + 2) * dim + (n_waypoints + 2 * half_width) * dim + 2 * n_waypoints + 1 +
                               (n_boundary + 1) * (2 * half_width + 1) + NFOPP_NUM_TERMS * (TU_THREADS / 64)) * 4;
   NFOPP_REQUIRE(batch <= 0x7fffffffLL, "batch too large for one launch");
-  return launch_dynamic_lds(dim == 3 ? traj_update_kernel<3> : traj_update_kernel<2>, batch, TU_THREADS, lds, stream, a,
+  const auto kernel = dim == 3 ? (terms_dev ? traj_update_kernel<3, true> : traj_update_kernel<3, false>)
+                               : (terms_dev ? traj_update_kernel<2, true> : traj_update_kernel<2, false>);
+  return launch_dynamic_lds(kernel, batch, TU_THREADS, lds, stream, a,
                             "trajectory too long");
 }

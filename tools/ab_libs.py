@@ -1,5 +1,6 @@
 """Dev tool: A/B two builds of libnfopp_hip.so IN ONE PROCESS, interleaved rounds (guide rule 24): the fused ONF kernel on
-the cfg3 shape.  Usage: python tools/ab_libs.py build/<variant>/libnfopp_hip.so   (compared with the product build)"""
+the cfg3 shape.  Usage: python tools/ab_libs.py build/<variant>/libnfopp_hip.so [k1|k2|k3] [rounds]   (compared with the product
+build; a null pair -- a copy of the product library as the variant -- gives the tool's own spread)"""
 import ctypes
 import os
 import sys
@@ -80,8 +81,11 @@ if KERNEL == "k3":      # arc-length reparametrisation
     out = {k: engs[k].traj for k in libs}
 
 times = {k: [] for k in libs}
-for rnd in range(8):
-    for k, lib in libs.items():
+ROUNDS = int(sys.argv[3]) if len(sys.argv) > 3 else 8
+for rnd in range(ROUNDS):
+    # the library that goes second in a round meets warmer clocks and caches: the order alternates, so that a null pair
+    # (the same library loaded from two paths) has no side that is always second
+    for k, lib in (list(libs.items()) if rnd % 2 == 0 else list(libs.items())[::-1]):
         for _ in range(3):
             run(lib, out[k])
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
