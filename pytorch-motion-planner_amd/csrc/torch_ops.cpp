@@ -29,14 +29,41 @@ void check_tensor(const Tensor& t, const char* name, at::ScalarType dtype = at::
 void same_device(const Tensor& a, const Tensor& b, const char* name) {
   TORCH_CHECK(a.device() == b.device(), "nfopp: ", name, " lives on ", b.device(), ", expected ", a.device());
 }
-template <class T>
-T* opt_ptr(const OptTensor& t) {
-  return (t.has_value() && t->defined() && t->numel() > 0) ? t->data_ptr<T>() : nullptr;
+// x belongs beside `first`: of `dtype`, contiguous, on its device
+void beside(const Tensor& first, const Tensor& x, const char* name, at::ScalarType dtype = at::kFloat) {
+  check_tensor(x, name, dtype);
+  same_device(first, x, name);
 }
-// an int32 tensor that may be empty: its pointer, or null
-int32_t* i32p(const Tensor& t) { return t.numel() ? t.data_ptr<int32_t>() : nullptr; }
+// ... and of exactly this shape
+void need(const Tensor& first, const Tensor& x, const char* name, at::IntArrayRef shape, at::ScalarType dtype = at::kFloat) {
+  beside(first, x, name, dtype);
+  TORCH_CHECK(x.sizes() == shape, "nfopp: ", name, " must have shape ", shape, ", got ", x.sizes());
+}
+void need_if_given(const Tensor& first, const OptTensor& x, const char* name, at::IntArrayRef shape, at::ScalarType dtype = at::kFloat) {
+  if (x.has_value()) need(first, *x, name, shape, dtype);
+}
+// The one statement of "pointer, or null when there is nothing": a tensor that is absent, undefined or empty gives null.  Every
+// pointer an entry may receive as null comes from here; a site whose null follows another rule says so ("own condition").
+template <class T>
+T* ptr(const Tensor& t) { return (t.defined() && t.numel() > 0) ? t.data_ptr<T>() : nullptr; }
+template <class T>
+T* ptr(const OptTensor& t) { return t.has_value() ? ptr<T>(*t) : nullptr; }
+// the uint64 words an int64 tensor holds
+uint64_t* words_ptr(const Tensor& t) { return reinterpret_cast<uint64_t*>(ptr<int64_t>(t)); }
 // the workspace of an op: `bytes` bytes on the device of `like` (the entries' 8-byte alignment is the device allocator's)
-Tensor byte_workspace(const Tensor& like, size_t bytes) { return at::empty({(int64_t)bytes}, like.options().dtype(at::kByte)); }
+struct Workspace {
+  Tensor buffer;
+  size_t bytes;
+  Workspace(const Tensor& like, size_t n) : buffer(at::empty({(int64_t)n}, like.options().dtype(at::kByte))), bytes(n) {}
+  void* ptr() const { return bytes ? buffer.data_ptr() : nullptr; }
+};
+// what an op holds while it launches: the device of its tensors made current, and the CURRENT HIP stream of that device
+struct Launch {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard;
+  void* stream;
+  explicit Launch(const Tensor& t)
+      : guard(t.device()), stream((void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.get_device()).stream()) {}
+};
 void check_status(int rc) { TORCH_CHECK(rc == 0, "nfopp call failed (", rc, "): ", nfopp_last_error()); }
 
 nfopp_onf_config make_cfg(double mean, double sigma, bool use_cos, bool has_bias, int64_t angle_dim) {
@@ -50,7 +77,11 @@ void check_params(const Tensor& params, const nfopp_onf_config& c) {
   TORCH_CHECK(want > 0, "nfopp: bad ONF configuration");
   TORCH_CHECK(params.numel() == want, "nfopp: params has ", params.numel(), " elements, this ONF configuration has ", want);
 }
-void* stream_of(const Tensor& t) { return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.get_device()).stream(); }
+// x is [P, 2] or, for an ONF with angle features, [P, 3]
+void check_point_rows(const Tensor& x, const char* name, int64_t angle_dim) {
+  const int64_t dim = angle_dim > 0 ? 3 : 2;
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "nfopp: ", name, " must be [P, ", dim, "]");
+}
 
 // the 18 floats of nfopp_traj_hyper in declaration order
 nfopp_traj_hyper make_hyper(at::ArrayRef<double> h) {
@@ -62,43 +93,29 @@ nfopp_traj_hyper make_hyper(at::ArrayRef<double> h) {
   return o;
 }
 
+// What onf_fwd_bwd_input and onf_logits share: params and points [P, dim] through `entry` -> its [P, 4] rows
+using OnfPointsEntry = int (*)(const nfopp_onf_config*, const float*, const float*, int64_t, float*, void*);
+Tensor onf_points(OnfPointsEntry entry, const Tensor& params, const Tensor& points, const nfopp_onf_config& c, int64_t angle_dim) {
+  check_params(params, c);
+  beside(params, points, "points");
+  check_point_rows(points, "points", angle_dim);
+  const Launch on(params);
+  Tensor out = at::empty({points.size(0), 4}, points.options());
+  check_status(entry(&c, params.data_ptr<float>(), points.data_ptr<float>(), points.size(0), out.data_ptr<float>(), on.stream));
+  return out;
+}
+
 // ONF.forward + autograd w.r.t. the input (nfop/onf_model.py:33-50): out [P, 4] = logit, d/dx, d/dy, d/dtheta
 Tensor onf_fwd_bwd_input(const Tensor& params, const Tensor& points, double mean, double sigma, bool use_cos, bool has_bias,
                          int64_t angle_dim) {
-  const nfopp_onf_config c = make_cfg(mean, sigma, use_cos, has_bias, angle_dim);
-  check_params(params, c);
-  check_tensor(points, "points");
-  same_device(params, points, "points");
-  const int64_t dim = angle_dim > 0 ? 3 : 2;
-  TORCH_CHECK(points.dim() == 2 && points.size(1) == dim, "nfopp: points must be [P, ", dim, "]");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
-  Tensor out = at::empty({points.size(0), 4}, points.options());
-  check_status(nfopp_onf_eval_points(&c, params.data_ptr<float>(), points.data_ptr<float>(), points.size(0),
-                                     out.data_ptr<float>(), stream_of(params)));
-  return out;
+  return onf_points(nfopp_onf_eval_points, params, points, make_cfg(mean, sigma, use_cos, has_bias, angle_dim), angle_dim);
 }
 
 // forward only (nfop/nerf_opt_planner.py:98-99,122-125): out [P, 1]
 Tensor onf_logits(const Tensor& params, const Tensor& points, double mean, double sigma, bool use_cos, bool has_bias,
                   int64_t angle_dim) {
-  const nfopp_onf_config c = make_cfg(mean, sigma, use_cos, has_bias, angle_dim);
-  check_params(params, c);
-  check_tensor(points, "points");
-  same_device(params, points, "points");
-  const int64_t dim = angle_dim > 0 ? 3 : 2;
-  TORCH_CHECK(points.dim() == 2 && points.size(1) == dim, "nfopp: points must be [P, ", dim, "]");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
-  Tensor out = at::empty({points.size(0), 4}, points.options());
-  check_status(nfopp_onf_eval_logits(&c, params.data_ptr<float>(), points.data_ptr<float>(), points.size(0),
-                                     out.data_ptr<float>(), stream_of(params)));
-  return out.narrow(1, 0, 1);
-}
-
-// x belongs to the batch of `traj`: fp32 (or `dtype`), contiguous, on traj's device, of exactly this shape
-void need(const Tensor& traj, const Tensor& x, const char* name, at::IntArrayRef shape, at::ScalarType dtype = at::kFloat) {
-  check_tensor(x, name, dtype);
-  same_device(traj, x, name);
-  TORCH_CHECK(x.sizes() == shape, "nfopp: ", name, " must have shape ", shape, ", got ", x.sizes());
+  return onf_points(nfopp_onf_eval_logits, params, points, make_cfg(mean, sigma, use_cos, has_bias, angle_dim), angle_dim)
+      .narrow(1, 0, 1);
 }
 
 // The state tensors of a batch of B trajectories, stated once for every op that takes them: traj [B, N, D], start / goal
@@ -147,8 +164,7 @@ Batch batch_state(const Tensor& traj, const Tensor& start, const Tensor& goal, c
   }
   if (live_ws && masked) {
     TORCH_CHECK(live_ws->has_value(), "nfopp: an active mask needs the live-list workspace (B + 1 int32)");
-    check_tensor(**live_ws, "live_ws", at::kInt);
-    same_device(traj, **live_ws, "live_ws");
+    beside(traj, **live_ws, "live_ws", at::kInt);
     TORCH_CHECK((*live_ws)->numel() >= b.B + 1, "nfopp: live_ws must hold B + 1 int32");
     b.live_ws = (*live_ws)->data_ptr<int32_t>();
   } else if (live_ws) {
@@ -169,7 +185,7 @@ Batch step_state(const Tensor& params, const nfopp_onf_config& c, int64_t angle_
   need(traj, adam_m, "adam_m", {b.B, b.N, b.D}); need(traj, adam_v, "adam_v", {b.B, b.N, b.D});
   need(traj, t, "t", {b.B, b.N - 1}); need(traj, onf_out, "onf_out", {b.B, b.N - 1, 4});
   need(traj, hinv_band, "hinv_band", {2 * half_width + 1, b.N});
-  if (terms.has_value()) need(traj, *terms, "terms", {b.B, NFOPP_NUM_TERMS});
+  need_if_given(traj, terms, "terms", {b.B, NFOPP_NUM_TERMS});
   return b;
 }
 
@@ -184,15 +200,14 @@ void traj_step(const Tensor& params, double mean, double sigma, bool use_cos, bo
   const Batch b = step_state(params, c, angle_dim, traj, start, goal, lam, cm, adam_m, adam_v, t, onf_out, hinv_band, half_width,
                              nullptr, terms, active, live_ws);
   const nfopp_traj_hyper hp = make_hyper(hyper);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
-  void* st = stream_of(traj);
+  const Launch on(traj);
   check_status(nfopp_traj_collision_eval(&c, params.data_ptr<float>(), b.traj, b.B, (int32_t)b.N, (int32_t)b.D,
                                          t.data_ptr<float>(), (int32_t)t_mode, (uint64_t)seed, (uint64_t)rng_offset,
-                                         traj_index_offset, onf_out.data_ptr<float>(), b.mask, b.live_ws, st));
+                                         traj_index_offset, onf_out.data_ptr<float>(), b.mask, b.live_ws, on.stream));
   check_status(nfopp_traj_update(&hp, b.B, (int32_t)b.N, (int32_t)b.D, b.traj, b.start, b.goal, b.lam, b.cm,
                                  adam_m.data_ptr<float>(), adam_v.data_ptr<float>(), t.data_ptr<float>(),
                                  onf_out.data_ptr<float>(), hinv_band.data_ptr<float>(), (int32_t)half_width,
-                                 (int32_t)interior_lo, (int32_t)interior_hi, opt_ptr<float>(terms), b.mask, st));
+                                 (int32_t)interior_lo, (int32_t)interior_hi, ptr<float>(terms), b.mask, on.stream));
 }
 
 // n frozen-field planner steps from one call (nfopp_traj_steps, ABI 6): the callers' step loops
@@ -209,7 +224,7 @@ void traj_steps(const Tensor& params, double mean, double sigma, bool use_cos, b
   const Batch b = step_state(params, c, angle_dim, traj, start, goal, lam, cm, adam_m, adam_v, t, onf_out, hinv_band, half_width,
                              &u, terms, active, live_ws);
   TORCH_CHECK(n_steps >= 0 && reparam_freq >= 1 && adam_steps_done >= 0 && step_count >= 0, "nfopp: bad step schedule");
-  if (t_steps.has_value()) need(traj, *t_steps, "t_steps", {n_steps, b.B, b.N - 1});
+  need_if_given(traj, t_steps, "t_steps", {n_steps, b.B, b.N - 1});
   const nfopp_traj_hyper hp = make_hyper(hyper);
   const nfopp_traj_buffers buf = {b.traj, b.start, b.goal, b.lam, b.cm, adam_m.data_ptr<float>(), adam_v.data_ptr<float>(),
                                   t.data_ptr<float>(), onf_out.data_ptr<float>(), hinv_band.data_ptr<float>(), b.u, b.mask,
@@ -220,18 +235,17 @@ void traj_steps(const Tensor& params, double mean, double sigma, bool use_cos, b
   sc.adam_steps_done = adam_steps_done; sc.step_count = step_count; sc.traj_index_offset = traj_index_offset;
   sc.seed = (uint64_t)seed; sc.rng_offset = (uint64_t)rng_offset; sc.reparam_freq = (int32_t)reparam_freq;
   sc.t_mode = t_steps.has_value() ? 0 : 1;
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
-  check_status(nfopp_traj_steps(&c, params.data_ptr<float>(), &hp, &buf, &sc, (int32_t)n_steps, opt_ptr<float>(t_steps),
-                                opt_ptr<float>(terms), stream_of(traj)));
+  const Launch on(traj);
+  check_status(nfopp_traj_steps(&c, params.data_ptr<float>(), &hp, &buf, &sc, (int32_t)n_steps, ptr<float>(t_steps),
+                                ptr<float>(terms), on.stream));
 }
 
 // arc-length reparametrisation (constrained:132-171 / nerf:224-244), in place
 void reparametrize(Tensor traj, const Tensor& start, const Tensor& goal, const OptTensor& lam, const OptTensor& cm,
                    const Tensor& u, const OptTensor& active) {
   const Batch b = batch_state(traj, start, goal, lam, cm, &u, &active, "active", nullptr);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
-  check_status(nfopp_reparametrize(b.B, (int32_t)b.N, (int32_t)b.D, b.traj, b.start, b.goal, b.lam, b.cm, b.u, b.mask,
-                                   stream_of(traj)));
+  const Launch on(traj);
+  check_status(nfopp_reparametrize(b.B, (int32_t)b.N, (int32_t)b.D, b.traj, b.start, b.goal, b.lam, b.cm, b.u, b.mask, on.stream));
 }
 
 // start (which = 0) / goal (which = 1) update of a batch (constrained:178-194 / nerf:202-218), in place: nearest waypoint,
@@ -241,10 +255,10 @@ void update_endpoints(Tensor traj, Tensor start, Tensor goal, const OptTensor& l
   const Batch b = batch_state(traj, start, goal, lam, cm, &u, &moved, "moved", nullptr);
   TORCH_CHECK(which == 0 || which == 1, "nfopp: which must be 0 (start) or 1 (goal)");
   need(traj, points, "points", {b.B, b.D});
-  if (min_index.has_value()) need(traj, *min_index, "min_index", {b.B}, at::kInt);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  need_if_given(traj, min_index, "min_index", {b.B}, at::kInt);
+  const Launch on(traj);
   check_status(nfopp_update_endpoints(b.B, (int32_t)b.N, (int32_t)b.D, (int32_t)which, points.data_ptr<float>(), b.mask, b.traj,
-                                      b.start, b.goal, b.lam, b.cm, b.u, opt_ptr<int32_t>(min_index), stream_of(traj)));
+                                      b.start, b.goal, b.lam, b.cm, b.u, ptr<int32_t>(min_index), on.stream));
 }
 
 // grid-search (A*) seeding of a batch (astar_trajectory_initializer.py:15-48): traj [B, N, D] in place, returns status [B].
@@ -255,41 +269,38 @@ Tensor grid_search_init(Tensor traj, const Tensor& start, const Tensor& goal, co
                         double origin_y, double resolution, bool angles_with_direction) {
   const Batch b = batch_endpoints(traj, start, goal);
   const int64_t B = b.B, N = b.N, D = b.D;
-  check_tensor(occupancy, "occupancy", at::kByte);
-  check_tensor(start_cells, "start_cells", at::kInt); check_tensor(goal_cells, "goal_cells", at::kInt);
-  check_tensor(unique_goal_cells, "unique_goal_cells", at::kInt); check_tensor(field_index, "field_index", at::kInt);
-  same_device(traj, occupancy, "occupancy");
-  same_device(traj, start_cells, "start_cells"); same_device(traj, goal_cells, "goal_cells");
-  same_device(traj, unique_goal_cells, "unique_goal_cells"); same_device(traj, field_index, "field_index");
+  beside(traj, occupancy, "occupancy", at::kByte);
+  beside(traj, start_cells, "start_cells", at::kInt); beside(traj, goal_cells, "goal_cells", at::kInt);
+  beside(traj, unique_goal_cells, "unique_goal_cells", at::kInt); beside(traj, field_index, "field_index", at::kInt);
   TORCH_CHECK(occupancy.dim() == 2, "nfopp: occupancy must be [rows, cols] uint8");
+  // the cells and the index are taken by their element counts (a flat [2 B] start_cells passes), so `need` does not state them
   TORCH_CHECK(start_cells.numel() == 2 * B && goal_cells.numel() == 2 * B && field_index.numel() == B,
               "nfopp: start_cells / goal_cells must be [B, 2], field_index [B]");
   TORCH_CHECK(unique_goal_cells.dim() == 2 && unique_goal_cells.size(1) == 2, "nfopp: unique_goal_cells must be [G, 2]");
   const int64_t rows = occupancy.size(0), cols = occupancy.size(1), G = unique_goal_cells.size(0);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  const Launch on(traj);
   const auto i32 = traj.options().dtype(at::kInt);
   Tensor fields = at::empty({G, rows, cols, 2}, i32);
-  const size_t fws = nfopp_grid_fields_workspace_bytes((int32_t)rows, (int32_t)cols, G);
-  Tensor fwork = byte_workspace(traj, fws);
+  const Workspace fwork(traj, nfopp_grid_fields_workspace_bytes((int32_t)rows, (int32_t)cols, G));
   check_status(nfopp_grid_distance_fields(occupancy.data_ptr<uint8_t>(), (int32_t)rows, (int32_t)cols,
-                                          unique_goal_cells.data_ptr<int32_t>(), G, fields.data_ptr<int32_t>(),
-                                          fws ? fwork.data_ptr() : nullptr, fws, stream_of(traj)));
+                                          unique_goal_cells.data_ptr<int32_t>(), G, fields.data_ptr<int32_t>(), fwork.ptr(),
+                                          fwork.bytes, on.stream));
   Tensor count = at::empty({B}, i32), status = at::empty({B}, i32);
   auto trace = [&](int32_t max_len, int32_t* cells) {
-    check_status(nfopp_grid_trace_paths(G ? fields.data_ptr<int32_t>() : nullptr, G, (int32_t)rows, (int32_t)cols,
+    check_status(nfopp_grid_trace_paths(ptr<int32_t>(fields), G, (int32_t)rows, (int32_t)cols,
                                         start_cells.data_ptr<int32_t>(), goal_cells.data_ptr<int32_t>(),
                                         field_index.data_ptr<int32_t>(), B, max_len, cells, count.data_ptr<int32_t>(),
-                                        status.data_ptr<int32_t>(), nullptr, stream_of(traj)));
+                                        status.data_ptr<int32_t>(), nullptr, on.stream));
   };
   trace(0, nullptr);
   const int64_t max_len = B ? std::max<int64_t>(count.max().item<int64_t>(), 1) : 1;
   Tensor cells = at::zeros({B, max_len, 2}, i32);
   trace((int32_t)max_len, cells.data_ptr<int32_t>());
-  const size_t sws = nfopp_grid_seed_workspace_bytes(B, (int32_t)max_len);
-  Tensor swork = byte_workspace(traj, sws);
+  const Workspace swork(traj, nfopp_grid_seed_workspace_bytes(B, (int32_t)max_len));
   check_status(nfopp_grid_seed_trajectories(cells.data_ptr<int32_t>(), count.data_ptr<int32_t>(), status.data_ptr<int32_t>(), B,
                                             (int32_t)max_len, b.start, b.goal, (int32_t)N, (int32_t)D,
-                                            angles_with_direction ? 1 : 0, origin_x, origin_y, resolution, b.traj, sws ? swork.data_ptr() : nullptr, sws, stream_of(traj)));
+                                            angles_with_direction ? 1 : 0, origin_x, origin_y, resolution, b.traj, swork.ptr(),
+                                            swork.bytes, on.stream));
   return status;
 }
 
@@ -298,32 +309,29 @@ Tensor onf_train_grad(const Tensor& params, const Tensor& samples, const Tensor&
                       double sigma, bool use_cos, bool has_bias, int64_t angle_dim) {
   const nfopp_onf_config c = make_cfg(mean, sigma, use_cos, has_bias, angle_dim);
   check_params(params, c);
-  check_tensor(samples, "samples"); check_tensor(labels, "labels");
-  same_device(params, samples, "samples"); same_device(params, labels, "labels");
-  const int64_t dim = angle_dim > 0 ? 3 : 2;
-  TORCH_CHECK(samples.dim() == 2 && samples.size(1) == dim, "nfopp: samples must be [P, ", dim, "]");
+  beside(params, samples, "samples"); beside(params, labels, "labels");
+  check_point_rows(samples, "samples", angle_dim);
   TORCH_CHECK(labels.numel() == samples.size(0), "nfopp: labels must be [P]");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+  const Launch on(params);
   const int64_t P = samples.size(0);
   const size_t ws_bytes = nfopp_onf_train_workspace_bytes(&c, P);
   Tensor ws = at::empty({(int64_t)((ws_bytes + 3) / 4)}, params.options());
   Tensor grad = at::empty({params.numel() + 2}, params.options());
   check_status(nfopp_onf_train_grad(&c, params.data_ptr<float>(), samples.data_ptr<float>(), labels.data_ptr<float>(), P,
-                                    (float)inv_count, grad.data_ptr<float>(), ws.data_ptr<float>(), ws_bytes, stream_of(params)));
+                                    (float)inv_count, grad.data_ptr<float>(), ws.data_ptr<float>(), ws_bytes, on.stream));
   return grad;
 }
 
 // torch.optim.Adam single-tensor update on the flat parameter buffer (nerf:90), in place
 void adam_step(Tensor param, const Tensor& grad, Tensor m, Tensor v, double beta2, double omb1, double omb2, double eps,
                double step_size, double bc2_sqrt) {
-  check_tensor(param, "param"); check_tensor(grad, "grad"); check_tensor(m, "m"); check_tensor(v, "v");
-  same_device(param, grad, "grad"); same_device(param, m, "m"); same_device(param, v, "v");
+  check_tensor(param, "param");
+  beside(param, grad, "grad"); beside(param, m, "m"); beside(param, v, "v");
   const int64_t n = param.numel();
   TORCH_CHECK(grad.numel() >= n && m.numel() == n && v.numel() == n, "nfopp: grad / m / v must cover the ", n, " parameters");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(param.device());
+  const Launch on(param);
   check_status(nfopp_adam_step(param.data_ptr<float>(), grad.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), n,
-                               (float)beta2, (float)omb1, (float)omb2, (float)eps, (float)step_size, (float)bc2_sqrt,
-                               stream_of(param)));
+                               (float)beta2, (float)omb1, (float)omb2, (float)eps, (float)step_size, (float)bc2_sqrt, on.stream));
 }
 
 // one `_optimize_collision_model` step on one GPU: gradient + Adam (multi-GPU callers all-reduce the gradient in between:
@@ -351,15 +359,15 @@ std::tuple<Tensor, Tensor, Tensor> path_time_profile(const Tensor& traj, const T
                                                      const OptTensor& v_goal) {
   const Batch b = batch_endpoints(traj, start, goal);
   const nfopp_motion_limits lim = make_limits(limits);
-  if (v_start.has_value()) need(traj, *v_start, "v_start", {b.B});
-  if (v_goal.has_value()) need(traj, *v_goal, "v_goal", {b.B});
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  need_if_given(traj, v_start, "v_start", {b.B});
+  need_if_given(traj, v_goal, "v_goal", {b.B});
+  const Launch on(traj);
   const auto f64 = traj.options().dtype(at::kDouble);
   Tensor profile = at::empty({b.B, b.N + 2, NFOPP_NUM_TIME_SLOTS}, f64), summary = at::empty({b.B, NFOPP_NUM_TIME_SUMMARY}, f64);
   Tensor gear = at::empty({b.B, b.N + 1}, traj.options().dtype(at::kChar));
-  check_status(nfopp_path_time_profile(b.traj, b.start, b.goal, b.B, (int32_t)b.N, (int32_t)b.D, &lim, opt_ptr<float>(v_start),
-                                       opt_ptr<float>(v_goal), profile.data_ptr<double>(), gear.data_ptr<int8_t>(),
-                                       summary.data_ptr<double>(), stream_of(traj)));
+  check_status(nfopp_path_time_profile(b.traj, b.start, b.goal, b.B, (int32_t)b.N, (int32_t)b.D, &lim, ptr<float>(v_start),
+                                       ptr<float>(v_goal), profile.data_ptr<double>(), gear.data_ptr<int8_t>(),
+                                       summary.data_ptr<double>(), on.stream));
   return std::make_tuple(profile, gear, summary);
 }
 
@@ -371,14 +379,13 @@ std::tuple<Tensor, Tensor> path_time_sample(const Tensor& traj, const Tensor& st
   const Batch b = batch_endpoints(traj, start, goal);
   const nfopp_motion_limits lim = make_limits(limits);
   need(traj, profile, "profile", {b.B, b.N + 2, NFOPP_NUM_TIME_SLOTS}, at::kDouble);
-  if (gear.has_value()) need(traj, *gear, "gear", {b.B, b.N + 1}, at::kChar);
+  need_if_given(traj, gear, "gear", {b.B, b.N + 1}, at::kChar);
   TORCH_CHECK(count >= 0 && count <= 0x7fffffffLL, "nfopp: count must lie in [0, 2^31)");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(traj.device());
+  const Launch on(traj);
   Tensor states = at::empty({b.B, count, b.D + 1}, traj.options());
   Tensor segment = at::empty({b.B, count}, traj.options().dtype(at::kInt));
   check_status(nfopp_path_time_sample(b.traj, b.start, b.goal, b.B, (int32_t)b.N, (int32_t)b.D, &lim, profile.data_ptr<double>(),
-                                      opt_ptr<int8_t>(gear), t0, dt, (int32_t)count, states.numel() ? states.data_ptr<float>() : nullptr,
-                                      segment.numel() ? segment.data_ptr<int32_t>() : nullptr, stream_of(traj)));
+                                      ptr<int8_t>(gear), t0, dt, (int32_t)count, ptr<float>(states), ptr<int32_t>(segment), on.stream));
   return std::make_tuple(states, segment);
 }
 
@@ -391,6 +398,56 @@ std::tuple<int64_t, int64_t, int32_t> check_tracks(const Tensor& t, const char* 
               " must have fewer than 2^31 instants and floats per row");
   return std::make_tuple(t.size(0), t.size(1), (int32_t)t.size(2));
 }
+// ... of a second set, which lives beside the op's first tensor
+std::tuple<int64_t, int64_t, int32_t> check_tracks_beside(const Tensor& first, const Tensor& t, const char* name) {
+  const auto shape = check_tracks(t, name);
+  same_device(first, t, name);
+  return shape;
+}
+
+// The two sets of a conflict check, stated once for track_conflicts and box_track_conflicts: tracks_a [Ba, K, Sa] against
+// tracks_b [Bb, K, Sb], or against itself when tracks_b is None (self mode: the entries take a null tracks_b for it, and
+// Bb = 0 where they count B's rows).  `least_stride` is the S both sets need at least, and what stride_b reads in self mode.
+struct TwoSets {
+  int64_t ba = 0, bb = 0, k = 0;   // bb = ba in self mode: the width of the pair matrices
+  int32_t stride_a = 0, stride_b = 0;
+  bool self = true;
+  const float *a = nullptr, *b = nullptr, *radius_a = nullptr, *radius_b = nullptr;   // what the entry receives
+  at::TensorOptions f64;
+
+  TwoSets(const Tensor& tracks_a, const OptTensor& tracks_b, int32_t least_stride) : f64(tracks_a.options().dtype(at::kDouble)) {
+    std::tie(ba, k, stride_a) = check_tracks(tracks_a, "tracks_a");
+    self = !tracks_b.has_value();
+    bb = ba;
+    stride_b = least_stride;
+    if (!self) {
+      int64_t kb;
+      std::tie(bb, kb, stride_b) = check_tracks_beside(tracks_a, *tracks_b, "tracks_b");
+      TORCH_CHECK(kb == k, "nfopp: tracks_b must be [Bb, K, >= ", least_stride, "] with the K of tracks_a (", k, ")");
+    }
+    a = ptr<float>(tracks_a);
+    // own condition: null selects self mode, so a set of no obstacles still needs a non-null tracks_b pointer (it is never
+    // read), and an empty set A, for which the entries do nothing, gives null on both sides
+    b = (self || ba == 0) ? nullptr : (bb > 0 ? tracks_b->data_ptr<float>() : a);
+  }
+  // radius_a [Ba], radius_b [Bb] fp32 or None (0)
+  void radii(const Tensor& tracks_a, const OptTensor& ra, const OptTensor& rb) {
+    need_if_given(tracks_a, ra, "radius_a", {ba});
+    if (!self) need_if_given(tracks_a, rb, "radius_b", {bb});
+    radius_a = ptr<float>(ra);
+    radius_b = self ? nullptr : ptr<float>(rb);   // own condition: self mode neither checks nor reads radius_b
+  }
+  int64_t rows_b() const { return self ? 0 : bb; }   // B's rows as the entries and summary_b count them
+  Tensor summary_a(int64_t slots) const { return at::empty({ba, slots}, f64); }
+  Tensor summary_b(int64_t slots) const { return at::empty({rows_b(), slots}, f64); }
+  Tensor pair_matrix(bool want_pairs, const at::TensorOptions& options) const {
+    return at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, options);
+  }
+  // the entries write nothing for an empty set A: every obstacle is without a partner, which reads `row`
+  void fill_b_of_empty_a(Tensor& summary_b, at::ArrayRef<double> row) const {
+    if (ba == 0 && summary_b.numel()) summary_b.copy_(at::tensor(row, at::kDouble).expand_as(summary_b));
+  }
+};
 
 // conflicts between timed tracks (nfopp_track_conflicts): tracks_a [Ba, K, Sa], tracks_b [Bb, K, Sb] or None (self mode), radii
 // [Ba] / [Bb] fp32 or None (0) -> (summary [Ba, 7], summary_b [Bb, 7], pair_gap, pair_first [Ba, Bb]) float64; summary_b is
@@ -398,36 +455,17 @@ std::tuple<int64_t, int64_t, int32_t> check_tracks(const Tensor& t, const char* 
 std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_a, const OptTensor& tracks_b, double dt, double t0,
                                                            const OptTensor& radius_a, const OptTensor& radius_b, double margin,
                                                            bool want_pairs) {
-  const auto [ba, k, stride_a] = check_tracks(tracks_a, "tracks_a");
-  const bool self = !tracks_b.has_value();
-  int64_t bb = ba;
-  int32_t stride_b = 2;
-  if (!self) {
-    int64_t kb;
-    std::tie(bb, kb, stride_b) = check_tracks(*tracks_b, "tracks_b");
-    same_device(tracks_a, *tracks_b, "tracks_b");
-    TORCH_CHECK(kb == k, "nfopp: tracks_b must be [Bb, K, >= 2] with the K of tracks_a (", k, ")");
-  }
-  if (radius_a.has_value()) need(tracks_a, *radius_a, "radius_a", {ba});
-  if (!self && radius_b.has_value()) need(tracks_a, *radius_b, "radius_b", {bb});
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks_a.device());
-  const auto f64 = tracks_a.options().dtype(at::kDouble);
-  Tensor summary = at::empty({ba, NFOPP_NUM_CONFLICT_SLOTS}, f64);
-  Tensor summary_b = at::empty({self ? 0 : bb, NFOPP_NUM_CONFLICT_SLOTS}, f64);
-  Tensor pair_gap = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, f64), pair_first = at::empty_like(pair_gap);
-  const size_t bytes = nfopp_track_conflicts_workspace_bytes(ba, self ? 0 : bb, (int32_t)k);
-  Tensor workspace = byte_workspace(tracks_a, bytes);
-  auto dptr = [](Tensor& t) { return t.numel() ? t.data_ptr<double>() : nullptr; };
-  // a set of no obstacles still needs a non-null tracks_b pointer (null selects self mode); it is never read
-  const float* b_ptr = self ? nullptr : (bb > 0 ? tracks_b->data_ptr<float>() : tracks_a.data_ptr<float>());
-  check_status(nfopp_track_conflicts(ba ? tracks_a.data_ptr<float>() : nullptr, ba, stride_a, ba ? b_ptr : nullptr, bb, stride_b,
-                                     (int32_t)k, t0, dt, opt_ptr<float>(radius_a), self ? nullptr : opt_ptr<float>(radius_b), margin, dptr(summary), dptr(summary_b),
-                                     dptr(pair_gap), dptr(pair_first), bytes ? workspace.data_ptr() : nullptr, bytes,
-                                     stream_of(tracks_a)));
-  if (ba == 0 && summary_b.numel()) {   // the entry writes nothing for an empty set A: every obstacle is without a partner
-    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
-    summary_b.copy_(at::tensor({inf, -1.0, nan, inf, -1.0, 0.0, (double)NFOPP_CONFLICT_NO_PARTNER}, at::kDouble).expand_as(summary_b));
-  }
+  TwoSets s(tracks_a, tracks_b, 2);
+  s.radii(tracks_a, radius_a, radius_b);
+  const Launch on(tracks_a);
+  Tensor summary = s.summary_a(NFOPP_NUM_CONFLICT_SLOTS), summary_b = s.summary_b(NFOPP_NUM_CONFLICT_SLOTS);
+  Tensor pair_gap = s.pair_matrix(want_pairs, s.f64), pair_first = at::empty_like(pair_gap);
+  const Workspace work(tracks_a, nfopp_track_conflicts_workspace_bytes(s.ba, s.rows_b(), (int32_t)s.k));
+  check_status(nfopp_track_conflicts(s.a, s.ba, s.stride_a, s.b, s.bb, s.stride_b, (int32_t)s.k, t0, dt, s.radius_a, s.radius_b, margin,
+                                     ptr<double>(summary), ptr<double>(summary_b), ptr<double>(pair_gap), ptr<double>(pair_first),
+                                     work.ptr(), work.bytes, on.stream));
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+  s.fill_b_of_empty_a(summary_b, {inf, -1.0, nan, inf, -1.0, 0.0, (double)NFOPP_CONFLICT_NO_PARTNER});
   return std::make_tuple(summary, summary_b, pair_gap, pair_first);
 }
 
@@ -435,10 +473,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> track_conflicts(const Tensor& tracks_
 Tensor track_headings(const Tensor& tracks) {
   const auto [b, k, stride] = check_tracks(tracks, "tracks");
   TORCH_CHECK(stride >= 3, "nfopp: tracks must be [B, K, >= 3] (x, y, theta)");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks.device());
+  const Launch on(tracks);
   Tensor out = at::empty({b, k, 2}, tracks.options().dtype(at::kDouble));
-  check_status(nfopp_track_headings(b ? tracks.data_ptr<float>() : nullptr, b, stride, (int32_t)k, b ? out.data_ptr<double>() : nullptr,
-                                    stream_of(tracks)));
+  check_status(nfopp_track_headings(ptr<float>(tracks), b, stride, (int32_t)k, ptr<double>(out), on.stream));
   return out;
 }
 
@@ -449,46 +486,29 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> box_track_conflicts(const Ten
                                                                        double t0, const Tensor& box_a, const OptTensor& box_b,
                                                                        const OptTensor& radius_a, const OptTensor& radius_b,
                                                                        double margin, int64_t refine, bool want_pairs) {
-  const auto [ba, k, stride_a] = check_tracks(tracks_a, "tracks_a");
-  const bool self = !tracks_b.has_value();
-  int64_t bb = ba;
-  int32_t stride_b = 3;
-  if (!self) {
-    int64_t kb;
-    std::tie(bb, kb, stride_b) = check_tracks(*tracks_b, "tracks_b");
-    same_device(tracks_a, *tracks_b, "tracks_b");
-    TORCH_CHECK(kb == k, "nfopp: tracks_b must be [Bb, K, >= 3] with the K of tracks_a (", k, ")");
+  TwoSets s(tracks_a, tracks_b, 3);
+  if (!s.self) {
     TORCH_CHECK(box_b.has_value(), "nfopp: tracks_b needs box_b");
-    need(tracks_a, *box_b, "box_b", {bb, 4});
+    need(tracks_a, *box_b, "box_b", {s.bb, 4});
   }
-  TORCH_CHECK(stride_a >= 3 && stride_b >= 3, "nfopp: box tracks must be [B, K, >= 3] (x, y, theta)");
+  TORCH_CHECK(s.stride_a >= 3 && s.stride_b >= 3, "nfopp: box tracks must be [B, K, >= 3] (x, y, theta)");
   TORCH_CHECK(refine >= 0 && refine <= NFOPP_BOX_CONFLICT_MAX_REFINE, "nfopp: refine must be 0 .. ", NFOPP_BOX_CONFLICT_MAX_REFINE);
-  need(tracks_a, box_a, "box_a", {ba, 4});
-  if (radius_a.has_value()) need(tracks_a, *radius_a, "radius_a", {ba});
-  if (!self && radius_b.has_value()) need(tracks_a, *radius_b, "radius_b", {bb});
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks_a.device());
-  const auto f64 = tracks_a.options().dtype(at::kDouble);
+  need(tracks_a, box_a, "box_a", {s.ba, 4});
+  s.radii(tracks_a, radius_a, radius_b);
+  const Launch on(tracks_a);
   Tensor heading_a = track_headings(tracks_a);
-  Tensor heading_b = self ? at::empty({0, k, 2}, f64) : track_headings(*tracks_b);
-  Tensor summary = at::empty({ba, NFOPP_NUM_BOX_CONFLICT_SLOTS}, f64);
-  Tensor summary_b = at::empty({self ? 0 : bb, NFOPP_NUM_BOX_CONFLICT_SLOTS}, f64);
-  Tensor pair_status = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, tracks_a.options().dtype(at::kInt));
-  Tensor pair_first = at::empty({want_pairs ? ba : 0, want_pairs ? bb : 0}, f64), pair_undecided = at::empty_like(pair_first);
-  const size_t bytes = nfopp_box_track_conflicts_workspace_bytes(ba, self ? 0 : bb, (int32_t)k);
-  Tensor workspace = byte_workspace(tracks_a, bytes);
-  auto dptr = [](Tensor& t) { return t.numel() ? t.data_ptr<double>() : nullptr; };
-  // a set of no obstacles still needs a non-null tracks_b pointer (null selects self mode); it is never read
-  const float* b_ptr = self ? nullptr : (bb > 0 ? tracks_b->data_ptr<float>() : tracks_a.data_ptr<float>());
-  check_status(nfopp_box_track_conflicts(
-      ba ? tracks_a.data_ptr<float>() : nullptr, dptr(heading_a), ba, stride_a, ba ? b_ptr : nullptr, dptr(heading_b), bb, stride_b,
-      (int32_t)k, t0, dt, ba ? box_a.data_ptr<float>() : nullptr, (!self && bb) ? box_b->data_ptr<float>() : nullptr,
-      opt_ptr<float>(radius_a), self ? nullptr : opt_ptr<float>(radius_b), margin, (int32_t)refine, dptr(summary), dptr(summary_b),
-      pair_status.numel() ? pair_status.data_ptr<int32_t>() : nullptr, dptr(pair_first), dptr(pair_undecided),
-      bytes ? workspace.data_ptr() : nullptr, bytes, stream_of(tracks_a)));
-  if (ba == 0 && summary_b.numel()) {   // the entry writes nothing for an empty set A: every obstacle is without a partner
-    const double inf = std::numeric_limits<double>::infinity();
-    summary_b.copy_(at::tensor({inf, -1.0, 0.0, inf, -1.0, 0.0, (double)NFOPP_CONFLICT_NO_PARTNER}, at::kDouble).expand_as(summary_b));
-  }
+  Tensor heading_b = s.self ? at::empty({0, s.k, 2}, s.f64) : track_headings(*tracks_b);
+  Tensor summary = s.summary_a(NFOPP_NUM_BOX_CONFLICT_SLOTS), summary_b = s.summary_b(NFOPP_NUM_BOX_CONFLICT_SLOTS);
+  Tensor pair_status = s.pair_matrix(want_pairs, tracks_a.options().dtype(at::kInt));
+  Tensor pair_first = s.pair_matrix(want_pairs, s.f64), pair_undecided = at::empty_like(pair_first);
+  const Workspace work(tracks_a, nfopp_box_track_conflicts_workspace_bytes(s.ba, s.rows_b(), (int32_t)s.k));
+  const float* box_b_ptr = s.self ? nullptr : ptr<float>(box_b);   // own condition: self mode neither checks nor reads box_b
+  check_status(nfopp_box_track_conflicts(s.a, ptr<double>(heading_a), s.ba, s.stride_a, s.b, ptr<double>(heading_b), s.bb, s.stride_b,
+                                         (int32_t)s.k, t0, dt, ptr<float>(box_a), box_b_ptr, s.radius_a, s.radius_b, margin,
+                                         (int32_t)refine, ptr<double>(summary), ptr<double>(summary_b), ptr<int32_t>(pair_status),
+                                         ptr<double>(pair_first), ptr<double>(pair_undecided), work.ptr(), work.bytes, on.stream));
+  const double inf = std::numeric_limits<double>::infinity();
+  s.fill_b_of_empty_a(summary_b, {inf, -1.0, 0.0, inf, -1.0, 0.0, (double)NFOPP_CONFLICT_NO_PARTNER});
   return std::make_tuple(summary, summary_b, pair_status, pair_first, pair_undecided);
 }
 
@@ -499,27 +519,24 @@ std::tuple<Tensor, Tensor, Tensor> fleet_shift_masks(const Tensor& tracks, int64
                                                      const OptTensor& obstacles, const OptTensor& obstacle_radius) {
   const auto [b, k, stride] = check_tracks(tracks, "tracks");
   TORCH_CHECK(max_delay >= 0 && max_delay <= NFOPP_SCHEDULE_MAX_DELAY, "nfopp: max_delay must be in 0 .. ", NFOPP_SCHEDULE_MAX_DELAY);
-  if (radius.has_value()) need(tracks, *radius, "radius", {b});
+  need_if_given(tracks, radius, "radius", {b});
   int64_t m = 0;
   int32_t obstacle_stride = 2;
   if (obstacles.has_value()) {
     int64_t ko;
-    std::tie(m, ko, obstacle_stride) = check_tracks(*obstacles, "obstacles");
-    same_device(tracks, *obstacles, "obstacles");
+    std::tie(m, ko, obstacle_stride) = check_tracks_beside(tracks, *obstacles, "obstacles");
     TORCH_CHECK(ko == k + max_delay, "nfopp: obstacles must be [M, K + max_delay, >= 2] = [M, ", k + max_delay, ", >= 2]");
-    if (obstacle_radius.has_value()) need(tracks, *obstacle_radius, "obstacle_radius", {m});
+    need_if_given(tracks, obstacle_radius, "obstacle_radius", {m});
   }
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(tracks.device());
+  const Launch on(tracks);
   const auto i64 = tracks.options().dtype(at::kLong);
   Tensor pair = at::empty({b, b, 2}, i64), base = at::empty({b}, i64), bad = at::empty({b}, tracks.options().dtype(at::kInt));
-  const size_t bytes = nfopp_fleet_shift_masks_workspace_bytes(b, m);
-  Tensor workspace = byte_workspace(tracks, bytes);
-  auto u64 = [](Tensor& t) { return t.numel() ? reinterpret_cast<uint64_t*>(t.data_ptr<int64_t>()) : nullptr; };
-  check_status(nfopp_fleet_shift_masks(b ? tracks.data_ptr<float>() : nullptr, b, stride, (int32_t)k, opt_ptr<float>(radius),
-                                       margin, (int32_t)max_delay, m ? obstacles->data_ptr<float>() : nullptr, m,
-                                       obstacle_stride, m ? opt_ptr<float>(obstacle_radius) : nullptr, u64(pair),
-                                       u64(base), b ? bad.data_ptr<int32_t>() : nullptr, bytes ? workspace.data_ptr() : nullptr, bytes,
-                                       stream_of(tracks)));
+  const Workspace work(tracks, nfopp_fleet_shift_masks_workspace_bytes(b, m));
+  // own condition: without obstacles, obstacle_radius is neither checked nor read
+  const float* obstacle_radius_ptr = obstacles.has_value() ? ptr<float>(obstacle_radius) : nullptr;
+  check_status(nfopp_fleet_shift_masks(ptr<float>(tracks), b, stride, (int32_t)k, ptr<float>(radius), margin, (int32_t)max_delay,
+                                       ptr<float>(obstacles), m, obstacle_stride, obstacle_radius_ptr, words_ptr(pair), words_ptr(base),
+                                       ptr<int32_t>(bad), work.ptr(), work.bytes, on.stream));
   return std::make_tuple(pair, base, bad);
 }
 
@@ -533,28 +550,34 @@ std::tuple<Tensor, Tensor, Tensor> fleet_assign_delays(const Tensor& pair, const
   const int64_t b = pair.size(0);
   need(pair, base, "base", {b}, at::kLong);
   need(pair, bad, "bad", {b}, at::kInt);
-  if (order.has_value()) need(pair, *order, "order", {b}, at::kInt);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(pair.device());
+  need_if_given(pair, order, "order", {b}, at::kInt);
+  const Launch on(pair);
   const auto i32 = pair.options().dtype(at::kInt);
   Tensor delay = at::empty({b}, i32), status = at::empty({b}, i32), forbidden = at::empty({b}, pair.options());
   if (b > 0)
-    check_status(nfopp_fleet_assign_delays(reinterpret_cast<const uint64_t*>(pair.data_ptr<int64_t>()),
-                                           reinterpret_cast<const uint64_t*>(base.data_ptr<int64_t>()), bad.data_ptr<int32_t>(),
-                                           opt_ptr<int32_t>(order), b, (int32_t)max_delay, delay.data_ptr<int32_t>(),
-                                           status.data_ptr<int32_t>(), reinterpret_cast<uint64_t*>(forbidden.data_ptr<int64_t>()),
-                                           stream_of(pair)));
+    check_status(nfopp_fleet_assign_delays(words_ptr(pair), words_ptr(base), bad.data_ptr<int32_t>(), ptr<int32_t>(order), b,
+                                           (int32_t)max_delay, delay.data_ptr<int32_t>(), status.data_ptr<int32_t>(),
+                                           words_ptr(forbidden), on.stream));
   return std::make_tuple(delay, status, forbidden);
 }
 
-// an occupancy image [rows, cols] uint8 and the instants of a reservation -> its size in int64 words
-int64_t spacetime_words(const Tensor& occupancy, int64_t count) {
+// What the two space-time ops share: an occupancy image [rows, cols] uint8 and the instants of a reservation on it -> the
+// frame, and the reservation's size in int64 words
+struct ImageFrame {
+  int32_t rows, cols, count;
+  int64_t words;
+  size_t bytes() const { return (size_t)words * 8; }
+};
+ImageFrame image_frame(const Tensor& occupancy, int64_t count) {
   check_tensor(occupancy, "occupancy", at::kByte);
   TORCH_CHECK(occupancy.dim() == 2 && occupancy.numel() > 0, "nfopp: occupancy must be a non-empty [rows, cols] image");
   TORCH_CHECK(count >= 1 && count <= 0x7fffffffLL, "nfopp: count must be >= 1");
   TORCH_CHECK(occupancy.size(0) <= 0x7fffffffLL && occupancy.size(1) <= 0x7fffffffLL, "nfopp: image too large for an index");
-  const size_t bytes = nfopp_spacetime_reservation_bytes((int32_t)occupancy.size(0), (int32_t)occupancy.size(1), (int32_t)count);
+  ImageFrame f = {(int32_t)occupancy.size(0), (int32_t)occupancy.size(1), (int32_t)count, 0};
+  const size_t bytes = nfopp_spacetime_reservation_bytes(f.rows, f.cols, f.count);
   TORCH_CHECK(bytes > 0, "nfopp: image and count too large for an index");
-  return (int64_t)(bytes / 8);
+  f.words = (int64_t)(bytes / 8);
+  return f;
 }
 
 // a space-time reservation with tracks ORed in (nfopp_spacetime_reservation_init / nfopp_spacetime_reserve): reservation None
@@ -562,33 +585,29 @@ int64_t spacetime_words(const Tensor& occupancy, int64_t count) {
 // None (0) and visible [M] uint8 or None (all) -> the reservation's words [n] int64 (layout: include/nfopp_hip.h)
 Tensor spacetime_reserve(const Tensor& occupancy, int64_t count, double b0, double b2, double resolution, double robot_radius, double margin,
                          const OptTensor& reservation, const OptTensor& tracks, const OptTensor& radius, const OptTensor& visible) {
-  const int64_t n = spacetime_words(occupancy, count);
-  const int32_t rows = (int32_t)occupancy.size(0), cols = (int32_t)occupancy.size(1);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(occupancy.device());
+  const ImageFrame f = image_frame(occupancy, count);
+  const Launch on(occupancy);
   Tensor words;
   if (reservation.has_value()) {
-    need(occupancy, *reservation, "reservation", {n}, at::kLong);
+    need(occupancy, *reservation, "reservation", {f.words}, at::kLong);
     words = reservation->clone();
   } else {
-    words = at::empty({n}, occupancy.options().dtype(at::kLong));
-    check_status(nfopp_spacetime_reservation_init(occupancy.data_ptr<uint8_t>(), rows, cols, (int32_t)count,
-                                                  reinterpret_cast<uint64_t*>(words.data_ptr<int64_t>()), (size_t)n * 8, stream_of(occupancy)));
+    words = at::empty({f.words}, occupancy.options().dtype(at::kLong));
+    check_status(nfopp_spacetime_reservation_init(occupancy.data_ptr<uint8_t>(), f.rows, f.cols, f.count, words_ptr(words), f.bytes(),
+                                                  on.stream));
   }
   if (!tracks.has_value()) {
     TORCH_CHECK(!radius.has_value() && !visible.has_value(), "nfopp: radius and visible belong to tracks");
     return words;
   }
-  const auto [m, k, stride] = check_tracks(*tracks, "tracks");
-  same_device(occupancy, *tracks, "tracks");
+  const auto [m, k, stride] = check_tracks_beside(occupancy, *tracks, "tracks");
   TORCH_CHECK(k == count, "nfopp: tracks must be [M, count, >= 2] = [M, ", count, ", >= 2]");
-  if (radius.has_value()) need(occupancy, *radius, "radius", {m});
-  if (visible.has_value()) need(occupancy, *visible, "visible", {m}, at::kByte);
-  const size_t bytes = nfopp_spacetime_reserve_workspace_bytes(m);
-  Tensor workspace = byte_workspace(occupancy, bytes);
-  check_status(nfopp_spacetime_reserve(rows, cols, (int32_t)count, b0, b2, resolution, (float)robot_radius, margin,
-                                       m ? tracks->data_ptr<float>() : nullptr, m, stride, opt_ptr<float>(radius), opt_ptr<uint8_t>(visible),
-                                       reinterpret_cast<uint64_t*>(words.data_ptr<int64_t>()), (size_t)n * 8,
-                                       bytes ? workspace.data_ptr() : nullptr, bytes, stream_of(occupancy)));
+  need_if_given(occupancy, radius, "radius", {m});
+  need_if_given(occupancy, visible, "visible", {m}, at::kByte);
+  const Workspace work(occupancy, nfopp_spacetime_reserve_workspace_bytes(m));
+  check_status(nfopp_spacetime_reserve(f.rows, f.cols, f.count, b0, b2, resolution, (float)robot_radius, margin, ptr<float>(tracks), m,
+                                       stride, ptr<float>(radius), ptr<uint8_t>(visible), words_ptr(words), f.bytes(), work.ptr(),
+                                       work.bytes, on.stream));
   return words;
 }
 
@@ -598,26 +617,23 @@ Tensor spacetime_reserve(const Tensor& occupancy, int64_t count, double b0, doub
 std::tuple<Tensor, Tensor, Tensor, Tensor> spacetime_plan_fleet(const Tensor& occupancy, int64_t count, double b0, double b2, double resolution,
                                                                 double robot_radius, double margin, const Tensor& start_cells,
                                                                 const Tensor& goal_cells, const OptTensor& order, Tensor reservation) {
-  const int64_t n = spacetime_words(occupancy, count);
-  const int32_t rows = (int32_t)occupancy.size(0), cols = (int32_t)occupancy.size(1);
-  need(occupancy, reservation, "reservation", {n}, at::kLong);
+  const ImageFrame f = image_frame(occupancy, count);
+  need(occupancy, reservation, "reservation", {f.words}, at::kLong);
   check_tensor(start_cells, "start_cells", at::kInt);
   TORCH_CHECK(start_cells.dim() == 2 && start_cells.size(1) == 2, "nfopp: start_cells must be [R, 2] (row, col)");
   const int64_t r = start_cells.size(0);
   same_device(occupancy, start_cells, "start_cells");
   need(occupancy, goal_cells, "goal_cells", {r, 2}, at::kInt);
-  if (order.has_value()) need(occupancy, *order, "order", {r}, at::kInt);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(occupancy.device());
+  need_if_given(occupancy, order, "order", {r}, at::kInt);
+  const Launch on(occupancy);
   const auto i32 = occupancy.options().dtype(at::kInt);
   Tensor cells = at::empty({r, count}, i32), arrival = at::empty({r}, i32), status = at::empty({r}, i32);
   Tensor tracks = at::empty({r, count, 2}, occupancy.options().dtype(at::kFloat));
-  const size_t bytes = nfopp_spacetime_plan_workspace_bytes(rows, cols, (int32_t)count, r);
-  Tensor workspace = byte_workspace(occupancy, bytes);
-  check_status(nfopp_spacetime_plan_fleet(occupancy.data_ptr<uint8_t>(), rows, cols, (int32_t)count, b0, b2, resolution, (float)robot_radius,
-                                          margin, i32p(start_cells), i32p(goal_cells), opt_ptr<int32_t>(order), r,
-                                          reinterpret_cast<uint64_t*>(reservation.data_ptr<int64_t>()), (size_t)n * 8, i32p(cells),
-                                          i32p(arrival), i32p(status), r ? tracks.data_ptr<float>() : nullptr,
-                                          bytes ? workspace.data_ptr() : nullptr, bytes, stream_of(occupancy)));
+  const Workspace work(occupancy, nfopp_spacetime_plan_workspace_bytes(f.rows, f.cols, f.count, r));
+  check_status(nfopp_spacetime_plan_fleet(occupancy.data_ptr<uint8_t>(), f.rows, f.cols, f.count, b0, b2, resolution, (float)robot_radius,
+                                          margin, ptr<int32_t>(start_cells), ptr<int32_t>(goal_cells), ptr<int32_t>(order), r,
+                                          words_ptr(reservation), f.bytes(), ptr<int32_t>(cells), ptr<int32_t>(arrival),
+                                          ptr<int32_t>(status), ptr<float>(tracks), work.ptr(), work.bytes, on.stream));
   return std::make_tuple(cells, arrival, status, tracks);
 }
 
@@ -633,8 +649,7 @@ static void check_lattice_costs(int64_t turn_cost, int64_t reverse_cost, int64_t
 static Tensor lattice_fields_impl(const Tensor& layers, const Tensor& goal_states, int64_t turn_cost, int64_t reverse_cost,
                                   int64_t cusp_cost, bool gears) {
   check_tensor(layers, "layers", at::kByte);
-  check_tensor(goal_states, "goal_states", at::kInt);
-  same_device(layers, goal_states, "goal_states");
+  beside(layers, goal_states, "goal_states", at::kInt);
   TORCH_CHECK(layers.dim() == 3, "nfopp: layers must be [L, rows, cols] uint8");
   TORCH_CHECK(goal_states.dim() == 2 && goal_states.size(1) == 3, "nfopp: goal_states must be [G, 3] (row, col, heading)");
   check_lattice_costs(turn_cost, reverse_cost, cusp_cost);
@@ -643,18 +658,16 @@ static Tensor lattice_fields_impl(const Tensor& layers, const Tensor& goal_state
   TORCH_CHECK(layers.size(1) >= 1 && layers.size(2) >= 1 && layers.size(1) <= 32768 && layers.size(2) <= 32768,
               "nfopp: grid must be 1..32768 cells a side");
   const int32_t rows = (int32_t)layers.size(1), cols = (int32_t)layers.size(2);
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(layers.device());
+  const Launch on(layers);
   const auto i32 = layers.options().dtype(at::kInt);
   Tensor fields = gears ? at::empty({G, 2, 8, rows, cols, 2}, i32) : at::empty({G, 8, rows, cols, 2}, i32);
-  const size_t bytes = gears ? nfopp_lattice_gear_fields_workspace_bytes(rows, cols, tc, rc, cc, G)
-                             : nfopp_lattice_fields_workspace_bytes(rows, cols, tc, G);
-  Tensor work = byte_workspace(layers, bytes);
+  const Workspace work(layers, gears ? nfopp_lattice_gear_fields_workspace_bytes(rows, cols, tc, rc, cc, G)
+                                     : nfopp_lattice_fields_workspace_bytes(rows, cols, tc, G));
   const uint8_t* occ = layers.data_ptr<uint8_t>();
-  const int32_t* goals = G ? goal_states.data_ptr<int32_t>() : nullptr;
-  int32_t* out = G ? fields.data_ptr<int32_t>() : nullptr;
-  void* ws = bytes ? work.data_ptr() : nullptr;
-  check_status(gears ? nfopp_lattice_gear_distance_fields(occ, L, rows, cols, goals, G, tc, rc, cc, out, ws, bytes, stream_of(layers))
-                     : nfopp_lattice_distance_fields(occ, L, rows, cols, goals, G, tc, out, ws, bytes, stream_of(layers)));
+  const int32_t* goals = ptr<int32_t>(goal_states);
+  int32_t* out = ptr<int32_t>(fields);
+  check_status(gears ? nfopp_lattice_gear_distance_fields(occ, L, rows, cols, goals, G, tc, rc, cc, out, work.ptr(), work.bytes, on.stream)
+                     : nfopp_lattice_distance_fields(occ, L, rows, cols, goals, G, tc, out, work.ptr(), work.bytes, on.stream));
   return fields;
 }
 
@@ -682,18 +695,18 @@ static std::vector<Tensor> lattice_trace_impl(const Tensor& fields, int64_t fiel
   TORCH_CHECK(max_len >= 0 && max_len <= std::numeric_limits<int32_t>::max(), "nfopp: bad max_len");
   check_lattice_costs(turn_cost, reverse_cost, cusp_cost);
   TORCH_CHECK(rows >= 1 && cols >= 1, "nfopp: fields of an empty grid");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(fields.device());
+  const Launch on(fields);
   const auto i32 = fields.options().dtype(at::kInt);
   Tensor cells = at::zeros({B, max_len, 2}, i32), headings = at::zeros({B, max_len}, i32), gear = at::zeros({gears ? B : 0, max_len}, i32);
   Tensor count = at::zeros({B}, i32), status = at::zeros({B}, i32), cost = at::zeros({B, 2}, i32);
   const int32_t r = (int32_t)rows, c = (int32_t)cols, tc = (int32_t)turn_cost, ml = (int32_t)max_len;
-  check_status(gears ? nfopp_lattice_gear_trace_paths(i32p(fields), field_first, G, n_total, r, c, tc, (int32_t)reverse_cost,
-                                                      (int32_t)cusp_cost, i32p(start_states), i32p(goal_states), i32p(field_index), B, ml,
-                                                      i32p(cells), i32p(headings), i32p(gear), i32p(count), i32p(status), i32p(cost),
-                                                      stream_of(fields))
-                     : nfopp_lattice_trace_paths(i32p(fields), field_first, G, n_total, r, c, tc, i32p(start_states), i32p(goal_states),
-                                                 i32p(field_index), B, ml, i32p(cells), i32p(headings), i32p(count), i32p(status),
-                                                 i32p(cost), stream_of(fields)));
+  const auto p = [](const Tensor& t) { return ptr<int32_t>(t); };
+  check_status(gears ? nfopp_lattice_gear_trace_paths(p(fields), field_first, G, n_total, r, c, tc, (int32_t)reverse_cost,
+                                                      (int32_t)cusp_cost, p(start_states), p(goal_states), p(field_index), B, ml,
+                                                      p(cells), p(headings), p(gear), p(count), p(status), p(cost), on.stream)
+                     : nfopp_lattice_trace_paths(p(fields), field_first, G, n_total, r, c, tc, p(start_states), p(goal_states),
+                                                 p(field_index), B, ml, p(cells), p(headings), p(count), p(status), p(cost),
+                                                 on.stream));
   return {cells, headings, gear, count, status, cost};
 }
 
@@ -735,99 +748,70 @@ Tensor lattice_seed_trajectories(const Tensor& cells, const Tensor& headings, co
   need(cells, goal, "goal", {B, 3}, at::kFloat);
   TORCH_CHECK(n_waypoints >= 1 && n_waypoints <= std::numeric_limits<int32_t>::max(), "nfopp: bad n_waypoints");
   TORCH_CHECK(resolution > 0.0, "nfopp: bad resolution");
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(cells.device());
+  const Launch on(cells);
   Tensor traj = at::empty({B, n_waypoints, 3}, cells.options().dtype(at::kFloat));
-  const size_t bytes = nfopp_lattice_seed_workspace_bytes(B, (int32_t)max_len);
-  Tensor work = byte_workspace(cells, bytes);
-  check_status(nfopp_lattice_seed_trajectories(i32p(cells), i32p(headings), i32p(count), i32p(status), B, (int32_t)max_len,
-                                               B ? start.data_ptr<float>() : nullptr, B ? goal.data_ptr<float>() : nullptr,
-                                               (int32_t)n_waypoints, origin_x, origin_y, resolution,
-                                               B ? traj.data_ptr<float>() : nullptr, bytes ? work.data_ptr() : nullptr, bytes,
-                                               stream_of(cells)));
+  const Workspace work(cells, nfopp_lattice_seed_workspace_bytes(B, (int32_t)max_len));
+  check_status(nfopp_lattice_seed_trajectories(ptr<int32_t>(cells), ptr<int32_t>(headings), ptr<int32_t>(count), ptr<int32_t>(status), B,
+                                               (int32_t)max_len, ptr<float>(start), ptr<float>(goal), (int32_t)n_waypoints, origin_x,
+                                               origin_y, resolution, ptr<float>(traj), work.ptr(), work.bytes, on.stream));
   return traj;
 }
 
 }  // namespace
 
+// One list: the schema of every op and its function.  The ops validate their arguments themselves (device included: a CPU tensor
+// gets the "no CPU path" message instead of a dispatcher "no kernel" error), so each is registered for every dispatch key.
 TORCH_LIBRARY(nfopp, lib) {
-  lib.def("onf_fwd_bwd_input(Tensor params, Tensor points, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim) -> Tensor");
-  lib.def("onf_logits(Tensor params, Tensor points, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim) -> Tensor");
-  lib.def(
-      "traj_step(Tensor params, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim, Tensor(a!) traj, Tensor start, "
-      "Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor(d!) adam_m, Tensor(e!) adam_v, Tensor(f!) t, int t_mode, int seed, "
-      "int rng_offset, int traj_index_offset, Tensor(g!) onf_out, Tensor hinv_band, int half_width, int interior_lo, int interior_hi, "
-      "float[] hyper, Tensor(h!)? terms, Tensor? active, Tensor(i!)? live_ws) -> ()");
-  lib.def(
-      "traj_steps(Tensor params, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim, Tensor(a!) traj, Tensor start, "
-      "Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor(d!) adam_m, Tensor(e!) adam_v, Tensor(f!) t, Tensor? t_steps, int seed, "
-      "int rng_offset, int traj_index_offset, Tensor(g!) onf_out, Tensor hinv_band, int half_width, int interior_lo, int interior_hi, "
-      "Tensor u, float[] hyper, float adam_lr, float adam_beta1, float adam_beta2, int adam_steps_done, int step_count, "
-      "int reparam_freq, int n_steps, Tensor(h!)? terms, Tensor? active, Tensor(i!)? live_ws) -> ()");
-  lib.def("reparametrize(Tensor(a!) traj, Tensor start, Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor u, Tensor? active) -> ()");
-  lib.def("update_endpoints(Tensor(a!) traj, Tensor(b!) start, Tensor(c!) goal, Tensor(d!)? lam, Tensor(e!)? cm, Tensor u, "
-          "Tensor points, int which, Tensor? moved, Tensor(f!)? min_index) -> ()");
-  lib.def("onf_train_grad(Tensor params, Tensor samples, Tensor labels, float inv_count, float mean, float sigma, bool use_cos, "
-          "bool has_bias, int angle_dim) -> Tensor");
-  lib.def("adam_step(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float beta2, float omb1, float omb2, float eps, "
-          "float step_size, float bc2_sqrt) -> ()");
-  lib.def("onf_train_step(Tensor(a!) params, Tensor(b!) m, Tensor(c!) v, Tensor samples, Tensor labels, float mean, float sigma, "
-          "bool use_cos, bool has_bias, int angle_dim, float beta2, float omb1, float omb2, float eps, float step_size, "
-          "float bc2_sqrt) -> Tensor");
-  lib.def("grid_search_init(Tensor(a!) traj, Tensor start, Tensor goal, Tensor occupancy, Tensor start_cells, Tensor goal_cells, "
-          "Tensor unique_goal_cells, Tensor field_index, float origin_x, float origin_y, float resolution, "
-          "bool angles_with_direction) -> Tensor");
-  lib.def("path_time_profile(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor? v_start, Tensor? v_goal) -> "
-          "(Tensor, Tensor, Tensor)");
-  lib.def("path_time_sample(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor profile, Tensor? gear, float t0, "
-          "float dt, int count) -> (Tensor, Tensor)");
-  lib.def("track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor? radius_a, Tensor? radius_b, float margin, "
-          "bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor)");
-  lib.def("track_headings(Tensor tracks) -> Tensor");
-  lib.def("box_track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor box_a, Tensor? box_b, Tensor? radius_a, "
-          "Tensor? radius_b, float margin, int refine, bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
-  lib.def("fleet_shift_masks(Tensor tracks, int max_delay, Tensor? radius, float margin, Tensor? obstacles, Tensor? obstacle_radius) -> "
-          "(Tensor, Tensor, Tensor)");
-  lib.def("fleet_assign_delays(Tensor pair, Tensor base, Tensor bad, Tensor? order, int max_delay) -> (Tensor, Tensor, Tensor)");
-  lib.def("spacetime_reserve(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
-          "Tensor? reservation, Tensor? tracks, Tensor? radius, Tensor? visible) -> Tensor");
-  lib.def("spacetime_plan_fleet(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
-          "Tensor start_cells, Tensor goal_cells, Tensor? order, Tensor(a!) reservation) -> (Tensor, Tensor, Tensor, Tensor)");
-  lib.def("lattice_fields(Tensor layers, Tensor goal_states, int turn_cost) -> Tensor");
-  lib.def("lattice_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
-          "Tensor field_index, int turn_cost, int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
-  lib.def("lattice_gear_fields(Tensor layers, Tensor goal_states, int turn_cost, int reverse_cost, int cusp_cost) -> Tensor");
-  lib.def("lattice_gear_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
-          "Tensor field_index, int turn_cost, int reverse_cost, int cusp_cost, int max_len) -> "
-          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
-  lib.def("lattice_seed_trajectories(Tensor cells, Tensor headings, Tensor count, Tensor status, Tensor start, Tensor goal, "
-          "int n_waypoints, float origin_x, float origin_y, float resolution) -> Tensor");
-}
-
-// The ops validate their arguments themselves (device included: a CPU tensor gets the "no CPU path" message instead of a
-// dispatcher "no kernel" error), so they are registered for every dispatch key.
-TORCH_LIBRARY_IMPL(nfopp, CompositeExplicitAutograd, lib) {
-  lib.impl("onf_fwd_bwd_input", &onf_fwd_bwd_input);
-  lib.impl("onf_logits", &onf_logits);
-  lib.impl("traj_step", &traj_step);
-  lib.impl("traj_steps", &traj_steps);
-  lib.impl("reparametrize", &reparametrize);
-  lib.impl("update_endpoints", &update_endpoints);
-  lib.impl("onf_train_grad", &onf_train_grad);
-  lib.impl("adam_step", &adam_step);
-  lib.impl("onf_train_step", &onf_train_step);
-  lib.impl("grid_search_init", &grid_search_init);
-  lib.impl("path_time_profile", &path_time_profile);
-  lib.impl("path_time_sample", &path_time_sample);
-  lib.impl("track_conflicts", &track_conflicts);
-  lib.impl("track_headings", &track_headings);
-  lib.impl("box_track_conflicts", &box_track_conflicts);
-  lib.impl("fleet_shift_masks", &fleet_shift_masks);
-  lib.impl("fleet_assign_delays", &fleet_assign_delays);
-  lib.impl("spacetime_reserve", &spacetime_reserve);
-  lib.impl("spacetime_plan_fleet", &spacetime_plan_fleet);
-  lib.impl("lattice_fields", &lattice_fields);
-  lib.impl("lattice_trace_paths", &lattice_trace_paths);
-  lib.impl("lattice_gear_fields", &lattice_gear_fields);
-  lib.impl("lattice_gear_trace_paths", &lattice_gear_trace_paths);
-  lib.impl("lattice_seed_trajectories", &lattice_seed_trajectories);
+  const auto op = [&lib](const char* schema, auto* fn) {
+    lib.def(schema, torch::dispatch(c10::DispatchKey::CompositeExplicitAutograd, fn));
+  };
+  op("onf_fwd_bwd_input(Tensor params, Tensor points, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim) -> Tensor", &onf_fwd_bwd_input);
+  op("onf_logits(Tensor params, Tensor points, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim) -> Tensor", &onf_logits);
+  op("traj_step(Tensor params, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim, Tensor(a!) traj, Tensor start, "
+     "Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor(d!) adam_m, Tensor(e!) adam_v, Tensor(f!) t, int t_mode, int seed, "
+     "int rng_offset, int traj_index_offset, Tensor(g!) onf_out, Tensor hinv_band, int half_width, int interior_lo, int interior_hi, "
+     "float[] hyper, Tensor(h!)? terms, Tensor? active, Tensor(i!)? live_ws) -> ()", &traj_step);
+  op("traj_steps(Tensor params, float mean, float sigma, bool use_cos, bool has_bias, int angle_dim, Tensor(a!) traj, Tensor start, "
+     "Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor(d!) adam_m, Tensor(e!) adam_v, Tensor(f!) t, Tensor? t_steps, int seed, "
+     "int rng_offset, int traj_index_offset, Tensor(g!) onf_out, Tensor hinv_band, int half_width, int interior_lo, int interior_hi, "
+     "Tensor u, float[] hyper, float adam_lr, float adam_beta1, float adam_beta2, int adam_steps_done, int step_count, "
+     "int reparam_freq, int n_steps, Tensor(h!)? terms, Tensor? active, Tensor(i!)? live_ws) -> ()", &traj_steps);
+  op("reparametrize(Tensor(a!) traj, Tensor start, Tensor goal, Tensor(b!)? lam, Tensor(c!)? cm, Tensor u, Tensor? active) -> ()", &reparametrize);
+  op("update_endpoints(Tensor(a!) traj, Tensor(b!) start, Tensor(c!) goal, Tensor(d!)? lam, Tensor(e!)? cm, Tensor u, "
+     "Tensor points, int which, Tensor? moved, Tensor(f!)? min_index) -> ()", &update_endpoints);
+  op("onf_train_grad(Tensor params, Tensor samples, Tensor labels, float inv_count, float mean, float sigma, bool use_cos, "
+     "bool has_bias, int angle_dim) -> Tensor", &onf_train_grad);
+  op("adam_step(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float beta2, float omb1, float omb2, float eps, "
+     "float step_size, float bc2_sqrt) -> ()", &adam_step);
+  op("onf_train_step(Tensor(a!) params, Tensor(b!) m, Tensor(c!) v, Tensor samples, Tensor labels, float mean, float sigma, "
+     "bool use_cos, bool has_bias, int angle_dim, float beta2, float omb1, float omb2, float eps, float step_size, "
+     "float bc2_sqrt) -> Tensor", &onf_train_step);
+  op("grid_search_init(Tensor(a!) traj, Tensor start, Tensor goal, Tensor occupancy, Tensor start_cells, Tensor goal_cells, "
+     "Tensor unique_goal_cells, Tensor field_index, float origin_x, float origin_y, float resolution, "
+     "bool angles_with_direction) -> Tensor", &grid_search_init);
+  op("path_time_profile(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor? v_start, Tensor? v_goal) -> "
+     "(Tensor, Tensor, Tensor)", &path_time_profile);
+  op("path_time_sample(Tensor traj, Tensor start, Tensor goal, float[] limits, Tensor profile, Tensor? gear, float t0, "
+     "float dt, int count) -> (Tensor, Tensor)", &path_time_sample);
+  op("track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor? radius_a, Tensor? radius_b, float margin, "
+     "bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor)", &track_conflicts);
+  op("track_headings(Tensor tracks) -> Tensor", &track_headings);
+  op("box_track_conflicts(Tensor tracks_a, Tensor? tracks_b, float dt, float t0, Tensor box_a, Tensor? box_b, Tensor? radius_a, "
+     "Tensor? radius_b, float margin, int refine, bool want_pairs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", &box_track_conflicts);
+  op("fleet_shift_masks(Tensor tracks, int max_delay, Tensor? radius, float margin, Tensor? obstacles, Tensor? obstacle_radius) -> "
+     "(Tensor, Tensor, Tensor)", &fleet_shift_masks);
+  op("fleet_assign_delays(Tensor pair, Tensor base, Tensor bad, Tensor? order, int max_delay) -> (Tensor, Tensor, Tensor)", &fleet_assign_delays);
+  op("spacetime_reserve(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
+     "Tensor? reservation, Tensor? tracks, Tensor? radius, Tensor? visible) -> Tensor", &spacetime_reserve);
+  op("spacetime_plan_fleet(Tensor occupancy, int count, float b0, float b2, float resolution, float robot_radius, float margin, "
+     "Tensor start_cells, Tensor goal_cells, Tensor? order, Tensor(a!) reservation) -> (Tensor, Tensor, Tensor, Tensor)", &spacetime_plan_fleet);
+  op("lattice_fields(Tensor layers, Tensor goal_states, int turn_cost) -> Tensor", &lattice_fields);
+  op("lattice_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
+     "Tensor field_index, int turn_cost, int max_len) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", &lattice_trace_paths);
+  op("lattice_gear_fields(Tensor layers, Tensor goal_states, int turn_cost, int reverse_cost, int cusp_cost) -> Tensor", &lattice_gear_fields);
+  op("lattice_gear_trace_paths(Tensor fields, int field_first, int n_total, Tensor start_states, Tensor goal_states, "
+     "Tensor field_index, int turn_cost, int reverse_cost, int cusp_cost, int max_len) -> "
+     "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", &lattice_gear_trace_paths);
+  op("lattice_seed_trajectories(Tensor cells, Tensor headings, Tensor count, Tensor status, Tensor start, Tensor goal, "
+     "int n_waypoints, float origin_x, float origin_y, float resolution) -> Tensor", &lattice_seed_trajectories);
 }

@@ -3,6 +3,7 @@ refuses CPU tensors / wrong dtypes / wrong shapes at the op boundary (TORCH_CHEC
 import pytest
 import torch
 
+from conftest import load_golden
 from nfopp import torch_ops
 
 
@@ -12,6 +13,19 @@ def test_ops_are_registered():
         assert hasattr(ops, name), name
     schema = str(torch.ops.nfopp.traj_step.default._schema)
     assert "Tensor(a!) traj" in schema and "float[] hyper" in schema
+
+
+@pytest.mark.parametrize("name", torch_ops.OPS)
+def test_schema_and_dispatch_key_are_the_recorded_ones(name):
+    """Names, argument order, defaults, alias annotations and return types of every op are those of
+    tests/golden/torch_ops_contract.npz (tools/record_torch_ops_contract.py), and its kernel is registered once, for every
+    backend: the ops validate the device themselves."""
+    torch_ops.load()
+    z = load_golden("torch_ops_contract.npz")
+    assert sorted(k[len("schema/"):] for k in z.files if k.startswith("schema/")) == sorted(torch_ops.OPS)
+    assert str(getattr(torch.ops.nfopp, name).default._schema) == str(z["schema/" + name])
+    kernels = [line for line in torch._C._dispatch_dump("nfopp::" + name).splitlines() if "registered at" in line and ":: (" in line]
+    assert len(kernels) == 1 and kernels[0].startswith("CompositeExplicitAutograd"), kernels
 
 
 def test_cpu_tensors_are_refused_at_the_op_boundary():
