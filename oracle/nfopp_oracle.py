@@ -778,6 +778,22 @@ def _find_interval(t, m, x):
     return ell
 
 
+def filter_path(path, minimal_distance):
+    """_filter_trajectory (ros/path_postprocessor.py:35-44) on an fp32 path [n >= 3, 3]: walk backwards, keep both end poses
+    and the interior poses further than minimal_distance from the last kept one -> the kept poses, in order."""
+    tr = np.asarray(path, F32)
+    md = F32(minimal_distance)
+    keep = [len(tr) - 1]
+    prev = tr[-1]
+    for i in range(len(tr) - 2, 0, -1):
+        dx, dy = F32(prev[0] - tr[i, 0]), F32(prev[1] - tr[i, 1])
+        if np.sqrt(F32(F32(dx * dx) + F32(dy * dy))) > md:
+            keep.append(i)
+            prev = tr[i]
+    keep.append(0)
+    return tr[keep[::-1]].copy()
+
+
 def path_postprocess(path, minimal_distance=0.001, distance_step=0.05):
     """ros/path_postprocessor.py:13-69 for one fp32 path [n, 3] -> float64 [count', 3].
 
@@ -788,17 +804,7 @@ def path_postprocess(path, minimal_distance=0.001, distance_step=0.05):
     tr = np.asarray(path, F32)
     if len(tr) < 3:
         return tr.copy()
-    # _filter_trajectory (:35-44): walk backwards, keep interior poses further than minimal_distance from the last kept
-    md = F32(minimal_distance)
-    keep = [len(tr) - 1]
-    prev = tr[-1]
-    for i in range(len(tr) - 2, 0, -1):
-        dx, dy = F32(prev[0] - tr[i, 0]), F32(prev[1] - tr[i, 1])
-        if np.sqrt(F32(F32(dx * dx) + F32(dy * dy))) > md:
-            keep.append(i)
-            prev = tr[i]
-    keep.append(0)
-    tr = tr[keep[::-1]].copy()
+    tr = filter_path(tr, minimal_distance)
     m = len(tr)
     if m < 3:
         raise ValueError("path collapses to fewer than 3 poses: no quadratic spline")

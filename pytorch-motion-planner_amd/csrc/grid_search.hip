@@ -228,7 +228,6 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs a) {
 
 // ---- stage 3: polyline -> spline -> waypoints ------------------------------------------------------------------------
 constexpr int SD_THREADS = 256;
-constexpr double SD_PI = 3.141592653589793;
 
 struct SeedArgs {
   const int* cells; const int* count; const int* status;
@@ -260,13 +259,10 @@ __device__ __forceinline__ void seed_body(const SeedArgs& a, double* W, long lon
     return;
   }
   const int m = cnt + 2;
-  const int M = a.max_len + 2;
-  double* T = W;                 // m + 3 knots
-  double* C = T + (M + 3);       // 2m coefficients (right-hand side in place)
-  double* PAR = C + 2 * M;       // m parameter values
-  double* DD = PAR + M;          // m pivots
-  double* UP = DD + M;           // m super-diagonal
-  float* P = reinterpret_cast<float*>(UP + M);   // 2m polyline (fp32, as the reference builds it)
+  const SplineArea sp = spline_carve<2>(W, a.max_len + 2);
+  double* C = sp.C;
+  const double *T = sp.T, *PAR = sp.PAR;
+  float* P = reinterpret_cast<float*>(sp.end);   // 2m polyline (fp32, as the reference builds it)
   const int2* cells = reinterpret_cast<const int2*>(a.cells) + b * (long long)a.max_len;
   const float* points = a.points ? a.points + b * (long long)a.max_len * 2 : nullptr;
   // polyline = [start, cell centres, goal] (astar_trajectory_initializer.py:19-20, 45-47: centres in float64, stored fp32)
@@ -286,38 +282,9 @@ __device__ __forceinline__ void seed_body(const SeedArgs& a, double* W, long lon
   __threadfence_block();
   __syncthreads();
   if (threadIdx.x == 0) {
-    float acc = 0.f;
-    PAR[0] = 0.0;
-    for (int i = 0; i < m - 1; ++i) {
-      const float dx = P[2 * (i + 1)] - P[2 * i], dy = P[2 * (i + 1) + 1] - P[2 * i + 1];
-      const float d = sqrtf((dx * dx) + (dy * dy)) + 1e-6f;
-      acc = (acc + d);
-      PAR[i + 1] = (double)acc;
-    }
-    const double last = PAR[m - 1];
-    for (int i = 0; i < m; ++i) PAR[i] = PAR[i] / last;
-    // knots at the data-site midpoints, ends tripled; tridiagonal collocation system, eliminated without pivoting
-    T[0] = T[1] = T[2] = PAR[0];
-    for (int i = 1; i <= m - 3; ++i) T[2 + i] = (PAR[i + 1] + PAR[i]) / 2.0;
-    T[m] = T[m + 1] = T[m + 2] = PAR[m - 1];
-    DD[0] = 1.0; UP[0] = 0.0;
-    double dd_prev = 1.0, up_prev = 0.0, c_prev[2] = {C[0], C[1]};
-    for (int j = 1; j < m; ++j) {
-      double lowj = 0.0, diagj = 1.0, upj = 0.0;
-      if (j < m - 1) {
-        double h[3];
-        collocation_row(T, PAR, m, j, h);
-        lowj = h[0]; diagj = h[1]; upj = h[2];
-      }
-      const double wgt = lowj / dd_prev;
-      dd_prev = diagj - wgt * up_prev;
-      up_prev = upj;
-      DD[j] = dd_prev; UP[j] = upj;
-      for (int d = 0; d < 2; ++d) { c_prev[d] = C[2 * j + d] - wgt * c_prev[d]; C[2 * j + d] = c_prev[d]; }
-    }
-    for (int d = 0; d < 2; ++d) { c_prev[d] = c_prev[d] / dd_prev; C[2 * (m - 1) + d] = c_prev[d]; }
-    for (int j = m - 2; j >= 0; --j)
-      for (int d = 0; d < 2; ++d) { c_prev[d] = (C[2 * j + d] - UP[j] * c_prev[d]) / DD[j]; C[2 * j + d] = c_prev[d]; }
+    // whether the sites are distinct is not looked at: two equal ones give NaN waypoints with status 0 (open)
+    chord_parameter<2>(P, m, sp.PAR, nullptr);
+    spline_fit<2>(sp, m);
   }
   __threadfence_block();
   __syncthreads();
@@ -334,10 +301,10 @@ __device__ __forceinline__ void seed_body(const SeedArgs& a, double* W, long lon
     // parameter; float64, every operation rounded on its own, no atan2 / sin / cos.  Knots A[0 .. m - 1]: the start angle,
     // the cells' headings as a1 + u_k * (pi / 4) with u the running sum of the signed heading steps, the goal angle; a1 and
     // the goal knot are the nearest turn to the knot before them, wrap(x) = x - 2 pi * rint(x / 2 pi).
-    double* A = DD;   // the pivots are done with
+    double* A = sp.DD;   // the pivots are done with
     if (threadIdx.x == 0) {
       const int* heads = a.headings + b * (long long)a.max_len;
-      const double quarter = SD_PI / 4.0, two_pi = 2.0 * SD_PI;
+      const double quarter = NFOPP_PI_D / 4.0, two_pi = 2.0 * NFOPP_PI_D;
       const double ths = (double)s[2];
       double x = (double)heads[0] * quarter - ths;
       const double a1 = ths + (x - two_pi * rint(x / two_pi));
@@ -392,9 +359,8 @@ __global__ __launch_bounds__(SD_THREADS) void seed_kernel(const SeedArgs a) {
   else seed_body<D>(a, sd_lds, b);
 }
 
-// doubles one problem's spline needs: knots M + 3, coefficients 2M, parameter M, pivots M, super-diagonal M, and the
-// fp32 polyline 2M floats
-static long long seed_doubles(int max_len) { return 7LL * (max_len + 2) + 3; }
+// doubles one problem needs: the spline's area for M = max_len + 2 sites of xy, and behind it the fp32 polyline, 2M floats
+static long long seed_doubles(int max_len) { return spline_doubles(max_len + 2, 2) + (max_len + 2); }
 constexpr long long SD_LDS_BYTES = 64 * 1024;
 
 static bool field_fits_lds(int rows, int cols, int* cols_p, int* stride, long long* padded) {

@@ -7,11 +7,10 @@
 // unfolded first, and trim the leading poses that are driven in the opposite direction to the first one.
 //
 // Precision follows numpy on the fp32 path the planner returns: filter, segment lengths, their running sum and the
-// unfolded headings in fp32; parametrisation, spline and output in float64.  With midpoint knots row j of the
-// collocation matrix touches only coefficients j-1..j+1, so the system is tridiagonal and is eliminated without
-// pivoting by one lane (scipy calls LAPACK gbsv; agreement to rounding, checked against scipy's output in
-// tests/golden/g12).  The sequential parts (filter, sums, elimination: O(n)) run on lane 0; evaluation of the
-// `count` output poses is spread over the workgroup.
+// unfolded headings in fp32; parametrisation, spline and output in float64.  The parameter and the fit are spline2.h's
+// (chord_parameter, spline_fit; agreement with scipy to rounding, checked against its output in tests/golden/g12); this
+// file keeps the filter, the pairwise length, the heading unfold and the trim.  The sequential parts (filter, sums,
+// elimination: O(n)) run on lane 0; evaluation of the `count` output poses is spread over the workgroup.
 #include "common.h"
 #include "spline2.h"
 
@@ -68,12 +67,9 @@ __device__ __forceinline__ float remainder_two_pi(float x) {
 __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a) {
   extern __shared__ double lds[];
   const int n = a.n;
-  double* T = lds;              // n + 3 knots
-  double* C = T + (n + 3);      // 3n spline coefficients (right-hand side in place)
-  double* PAR = C + 3 * n;      // n parameter values
-  double* DD = PAR + n;         // n pivots
-  double* UP = DD + n;          // n super-diagonal
-  float* P = reinterpret_cast<float*>(UP + n);   // 3n filtered poses
+  const SplineArea sp = spline_carve<3>(lds, n);
+  const double *T = sp.T, *C = sp.C;             // knots and coefficients, once lane 0 has fitted the spline
+  float* P = reinterpret_cast<float*>(sp.end);   // 3n filtered poses
   float* DIST = P + 3 * n;      // n segment lengths
   __shared__ int s_m, s_count, s_first;
   const long long b = blockIdx.x;
@@ -100,27 +96,10 @@ __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a)
     const int m = n - w;
     float* Q = P + 3 * w;
     int count = -1;
-    bool spline_exists = m >= 3;
-    if (m >= 3) {
-      // ---- parametrisation (:27-33) and total length (:21-25)
-      float acc = 0.f;
-      PAR[0] = 0.0;
-      for (int i = 0; i < m - 1; ++i) {
-        const float dx = Q[3 * (i + 1)] - Q[3 * i], dy = Q[3 * (i + 1) + 1] - Q[3 * i + 1];
-        const float d = sqrtf((dx * dx) + (dy * dy)) + 1e-6f;
-        DIST[i] = d;
-        acc = (acc + d);
-        PAR[i + 1] = (double)acc;
-      }
-      const double last = PAR[m - 1];
-      for (int i = 0; i < m; ++i) PAR[i] = PAR[i] / last;
-      // scipy refuses duplicate sites ("Expect x to not have duplicates"): with minimal_distance below 1e-6 * 2^24 a
-      // segment can round away in the fp32 running sum, and the collocation matrix is then singular
-      for (int i = 1; i < m; ++i)
-        if (PAR[i] == PAR[i - 1]) spline_exists = false;
-    }
-    if (spline_exists) {
-      const float total = pairwise_sum<4>(DIST, m - 1);
+    // ---- parametrisation (:27-33).  scipy refuses duplicate sites ("Expect x to not have duplicates"): with minimal_distance
+    // below 1e-6 * 2^24 a segment can round away in the fp32 running sum; no spline goes through such a path
+    if (m >= 3 && chord_parameter<3>(Q, m, sp.PAR, DIST)) {
+      const float total = pairwise_sum<4>(DIST, m - 1);   // total length (:21-25)
       count = (int)(total / a.dist_step);
       // ---- unfold headings (utils/math.py:38-43)
       float prev = remainder_two_pi(Q[2] + NFOPP_PI_F) - NFOPP_PI_F;
@@ -136,30 +115,10 @@ __global__ __launch_bounds__(PP_THREADS) void path_post_kernel(const PostArgs a)
         prev = cur;
         Q[3 * i + 2] = (float)((double)first_angle + (double)run);
       }
-      // ---- knots and the tridiagonal collocation system
-      T[0] = T[1] = T[2] = PAR[0];
-      for (int i = 1; i <= m - 3; ++i) T[2 + i] = (PAR[i + 1] + PAR[i]) / 2.0;
-      T[m] = T[m + 1] = T[m + 2] = PAR[m - 1];
+      // ---- the spline through the kept poses (spline2.h)
       for (int i = 0; i < m; ++i)
-        for (int d = 0; d < 3; ++d) C[3 * i + d] = (double)Q[3 * i + d];
-      DD[0] = 1.0; UP[0] = 0.0;
-      for (int j = 1; j < m; ++j) {
-        double lowj = 0.0, diagj = 1.0, upj = 0.0;
-        if (j < m - 1) {
-          // x_j lies in knot interval ell = j+1 (clamped to [2, m-1]); its three basis functions are coefficients j-1..j+1
-          const int ell = j + 1 > m - 1 ? m - 1 : j + 1;
-          double h[3];
-          basis2(T, ell, PAR[j], h);
-          lowj = h[0]; diagj = h[1]; upj = h[2];
-        }
-        const double wgt = lowj / DD[j - 1];
-        DD[j] = diagj - wgt * UP[j - 1];
-        UP[j] = upj;
-        for (int d = 0; d < 3; ++d) C[3 * j + d] -= wgt * C[3 * (j - 1) + d];
-      }
-      for (int d = 0; d < 3; ++d) C[3 * (m - 1) + d] /= DD[m - 1];
-      for (int j = m - 2; j >= 0; --j)
-        for (int d = 0; d < 3; ++d) C[3 * j + d] = (C[3 * j + d] - UP[j] * C[3 * (j + 1) + d]) / DD[j];
+        for (int d = 0; d < 3; ++d) sp.C[3 * i + d] = (double)Q[3 * i + d];
+      spline_fit<3>(sp, m);
       // ---- direction of the first segments (:54-69): only the first 7 poses matter
       int first = 1;
       if (count >= 2) {
@@ -230,7 +189,7 @@ extern "C" int nfopp_path_postprocess(const float* path_dev, int64_t batch, int3
   PostArgs a;
   a.path = path_dev; a.n = n_points; a.max_out = max_out; a.min_dist = minimal_distance; a.dist_step = distance_step;
   a.out = out_dev; a.count = count_dev;
-  // doubles: knots n+3, coefficients 3n, parameter n, pivots n, super-diagonal n; floats: poses 3n, lengths n
-  const size_t lds = (size_t)(7 * n_points + 3) * 8 + (size_t)(4 * n_points) * 4;
+  // the spline's area for n poses of (x, y, heading); floats behind it: poses 3n, lengths n
+  const size_t lds = (size_t)spline_doubles(n_points, 3) * 8 + (size_t)(4 * n_points) * 4;
   return launch_dynamic_lds(path_post_kernel, batch, PP_THREADS, lds, stream, a, "path too long");   // 1026 poses: 72 KiB
 }

@@ -1,6 +1,7 @@
 """Dev tool: A/B two builds of libnfopp_hip.so IN ONE PROCESS, interleaved rounds (guide rule 24): the fused ONF kernel on
-the cfg3 shape.  Usage: python tools/ab_libs.py build/<variant>/libnfopp_hip.so [k1|k2|k3] [rounds]   (compared with the product
-build; a null pair -- a copy of the product library as the variant -- gives the tool's own spread)"""
+the cfg3 shape.  Usage: python tools/ab_libs.py build/<variant>/libnfopp_hip.so [k1|k2|k3|seed|post] [rounds] [product.so]
+(compared with the product build, or with the library named last; a null pair -- a copy of the product library as the variant --
+gives the tool's own spread)"""
 import ctypes
 import os
 import sys
@@ -23,7 +24,7 @@ def bind(path):
     return lib
 
 
-libs = {"product": bind(_lib.LIB_PATH), "variant": bind(os.path.abspath(sys.argv[1]))}
+libs = {"product": bind(os.path.abspath(sys.argv[4]) if len(sys.argv) > 4 else _lib.LIB_PATH), "variant": bind(os.path.abspath(sys.argv[1]))}
 KERNEL = sys.argv[2] if len(sys.argv) > 2 else "k1"     # k1: fused ONF kernel, k2: stencil / optimiser kernel
 torch.manual_seed(0)
 onf = nfopp.ONF(0.0, 10.0, use_cos=True, use_normal_init=True, bias=True, angle_encoding=True).to("cuda")
@@ -80,6 +81,40 @@ if KERNEL == "k3":      # arc-length reparametrisation
         assert rc == 0, lib.nfopp_last_error()
     out = {k: engs[k].traj for k in libs}
 
+if KERNEL in ("seed", "post"):      # the two kernels that fit the quadratic spline of csrc/spline2.h
+    sys.path.insert(0, ROOT)
+    import bench
+    from nfopp import grid_search as gs
+    env = bench.GridMap()
+    grid = nfopp.OccupancyGrid.from_checker(env.device_checker(torch.device("cuda", 0)), 1.0, boundaries=(0.5, 100.0, 0.5, 100.0))
+    rng = np.random.default_rng(4321)
+    starts, goals = (torch.tensor(env.free_poses(rng, B), dtype=torch.float32, device="cuda") for _ in range(2))
+    cells, count, status, _, s, g = gs._search(grid, starts, goals)      # the cfg4 cell paths, traced by the product library
+    L, i32 = int(cells.shape[1]), torch.int32
+    ws_bytes = libs["product"].nfopp_grid_seed_workspace_bytes(B, L)
+    ws = torch.zeros(max(ws_bytes, 8), dtype=torch.uint8, device="cuda")
+    out = {k: torch.zeros(B, N, 3, device="cuda") for k in libs}
+
+    def run(lib, o):   # noqa: F811
+        rc = lib.nfopp_grid_seed_trajectories(_lib.ptr(cells, i32), _lib.ptr(count, i32), _lib.ptr(status, i32), B, L, _lib.ptr(s),
+                                              _lib.ptr(g), N, 3, 0, *grid.origin_resolution, _lib.ptr(o),
+                                              _lib.ptr(ws, torch.uint8) if ws_bytes else None, ws_bytes, _lib.stream_ptr())
+        assert rc == 0, lib.nfopp_last_error()
+    print("%d cfg4 cell paths, %d reached, %d cells at most" % (B, int((status == 0).sum()), L))
+
+if KERNEL == "post":      # 4096 paths of 258 poses: start | the seeded trajectory | goal; resampled every 0.25 m
+    run(libs["product"], out["product"])
+    paths = torch.cat([s[:, None], out["product"], g[:, None]], 1).contiguous()
+    MAX_OUT = 1024
+    counts = {k: torch.zeros(B, dtype=i32, device="cuda") for k in libs}
+    out = {k: torch.zeros(B, MAX_OUT, 3, dtype=torch.float64, device="cuda") for k in libs}
+
+    def run(lib, o, _libs=libs):   # noqa: F811
+        c = counts["product" if lib is _libs["product"] else "variant"]
+        rc = lib.nfopp_path_postprocess(_lib.ptr(paths), B, N + 2, 0.001, 0.25, MAX_OUT, _lib.ptr(o, torch.float64), _lib.ptr(c, i32),
+                                        _lib.stream_ptr())
+        assert rc == 0, lib.nfopp_last_error()
+
 times = {k: [] for k in libs}
 ROUNDS = int(sys.argv[3]) if len(sys.argv) > 3 else 8
 for rnd in range(ROUNDS):
@@ -99,6 +134,8 @@ for k, v in times.items():
     print("%-8s median %.4f ms  min %.4f  (rounds: %s)" % (k, float(np.median(v)), min(v), " ".join("%.3f" % x for x in v)))
 print("variant / product (median): %.4f" % (np.median(times["variant"]) / np.median(times["product"])))
 print("outputs identical:", bool(torch.equal(out["product"], out["variant"])))
+if KERNEL == "post":
+    print("  counts identical: %s (%d poses at most)" % (bool(torch.equal(counts["product"], counts["variant"])), int(counts["product"].max())))
 if KERNEL == "k2":
     for name in ("lam", "cm", "adam_m", "adam_v"):
         print("  %s identical: %s" % (name, bool(torch.equal(getattr(engs["product"], name), getattr(engs["variant"], name)))))
