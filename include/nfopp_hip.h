@@ -206,6 +206,58 @@ int nfopp_traj_steps(const nfopp_onf_config* cfg, const float* params_dev, const
                      const nfopp_traj_buffers* buf, const nfopp_step_schedule* sched, int32_t n_steps,
                      const float* t_steps_dev, float* terms_dev, void* stream);
 
+/* The distance-field collision model (csrc/sdf_field.hip): the obstacle cost of CHOMP / GPMP2 as a second
+ * producer of the [.., 4] rows nfopp_traj_update reads, for users who hold an occupancy grid and no fitted ONF.
+ *   sd_dev [rows, cols]: signed distance in metres at the cell centres, free positive, wall negative, every value finite
+ *     (OccupancyGrid.signed_distance_field).  The centre of cell (j, i) lies at (x0 + (i + 0.5) / inv_res, y0 + (j + 0.5) / inv_res).
+ *   The robot is n_discs discs (centre ox, oy in the body frame, radius r).  Per disc, all in fp32 and every operation
+ *   rounded on its own (no fused multiply-add):
+ *     cx = (x + ox c) - oy s,  cy = (y + ox s) + oy c,  (c, s) = (cos theta, sin theta); a disc with ox = oy = 0 sits at (x, y)
+ *       exactly, and a robot of such discs alone evaluates no sine: (c, s) = (1, 0) stands in
+ *     u = (cx - x0) inv_res - 0.5;  in_x = 0 < u < cols - 1;  u clamped to [0, cols - 1];  i = min((int)floor(u), cols - 2);
+ *       fu = u - i;  v, in_y, j, fv likewise with y0 and rows
+ *     a = sd[j][i+1] - sd[j][i];  b = sd[j+1][i+1] - sd[j+1][i];  top = sd[j][i] + fu a;  bot = sd[j+1][i] + fu b
+ *     d = top + fv (bot - top);  gx = in_x ? (a + fv (b - a)) inv_res : 0;  gy = in_y ? (bot - top) inv_res : 0
+ *     pen = (r + margin) - d
+ *   The disc that counts is the first one with the largest pen (strict >).  The row is
+ *     gain pen,  gain (-gx),  gain (-gy),  gain ((-gx) ((-ox) s - oy c) + (-gy) (ox c - oy s))   (0 for poses of 2 components)
+ *   A pose outside the image sees the clamped border value, with a zero gradient component along each clamped axis.  A pose
+ *   with a non-finite component gives four NaNs and reads nothing of sd_dev. */
+typedef struct nfopp_sdf_field {
+  const float* sd_dev;          /* [rows, cols] */
+  int32_t rows, cols;           /* both >= 2 */
+  float x0, y0, inv_res;        /* float(boundaries[0]), float(boundaries[2]), float(1.0 / resolution): each rounded once from double */
+  int32_t n_discs;              /* 1..8 */
+  float disc[8][3];             /* body-frame centre (ox, oy) and radius */
+  float margin, gain;           /* metres, logit per metre */
+} nfopp_sdf_field;
+
+/* The row above at explicit poses.
+ *   points_dev [P, point_dim], point_dim 3 (x, y, theta) or 2 (x, y: one disc with a zero offset only)
+ *   out4_dev   [P, 4], 16-byte aligned: all 4 P floats are written and nothing else
+ * Added within ABI 6 (no existing entry changed), as are the two entries below. */
+int nfopp_sdf_eval_points(const nfopp_sdf_field* field, const float* points_dev, int64_t n, int32_t point_dim,
+                          float* out4_dev, void* stream);
+
+/* The row above at the collision samples of a batch of trajectories: nfopp_traj_collision_eval with the distance field in
+ * the ONF's place.  The sample between waypoints j and j+1, the draw t, its Philox counter and traj_index_offset are that
+ * entry's (one device function forms the sample for both).
+ *   traj_dev [B, N, dim];  t_dev [B, N-1]: t_mode 0 reads it and never writes it, t_mode 1 writes the draw of every live row
+ *   out4_dev [B, N-1, 4], 16-byte aligned: the 4 floats of every live row are written
+ *   active_dev [B] uint8 or NULL: the t and out4 rows of trajectories with 0 keep their bytes; the rows of the others are
+ *     those of a launch without the mask.  No live-list workspace: one lane per sample, and a retired lane returns. */
+int nfopp_traj_sdf_collision_eval(const nfopp_sdf_field* field, const float* traj_dev, int64_t batch, int32_t n_waypoints,
+                                  int32_t dim, float* t_dev, int32_t t_mode, uint64_t seed, uint64_t rng_offset,
+                                  int64_t traj_index_offset, float* out4_dev, const uint8_t* active_dev, void* stream);
+
+/* nfopp_traj_steps with nfopp_traj_sdf_collision_eval as each step's first launch: the same loop (one function serves both
+ * entries), the same Adam scalars, update and reparametrisation schedule, so n_steps here equal n_steps single-step sequences
+ * bit for bit.  Writes what nfopp_traj_steps writes; buf->live_ws_dev is not used.  The field, the robot and the schedule are
+ * checked before the first launch: a call refused for one of them has written nothing. */
+int nfopp_traj_steps_sdf(const nfopp_sdf_field* field, const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf,
+                         const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev, float* terms_dev,
+                         void* stream);
+
 /* ONF fitting step, gradient part: BCE-with-logits (mean over ALL samples of the job) and its gradient w.r.t.
  * every parameter incl. the angle frequencies (nfop/nerf_opt_planner.py:83-89).
  *   samples_dev [P, point_dim], labels_dev [P] (0/1), inv_count = 1 / (global sample count)

@@ -220,6 +220,25 @@ __device__ __forceinline__ float mix_unfused(float p, float a, float q, float b)
   return pa + qb;
 }
 
+// The collision sample between two consecutive interior waypoints qa = traj[:-1][j] and qb = traj[1:][j] at the draw tt:
+// what every collision model (the ONF kernels, csrc/sdf_field.hip) is evaluated at.
+// Every product and sum rounded on its own, as the reference's separate torch ops do (no fused multiply-add): the
+// sample is then bit-identical to the oracle's for the same t, and K1 sees the reference's inputs.
+struct SamplePose { float x, y, ang; };   // ang = 0 without a heading
+__device__ __forceinline__ SamplePose collision_sample(int dim, const float* qa, const float* qb, float tt) {
+  float x, y, ang = 0.0f;
+  if (dim == 3) {
+    // constrained:79-81  p = traj[1:] + t * wrap-theta(traj[:-1] - traj[1:])
+    float dx = qa[0] - qb[0], dy = qa[1] - qb[1], dth = wrap_angle(qa[2] - qb[2]);
+    x = add_mul_unfused(qb[0], tt, dx); y = add_mul_unfused(qb[1], tt, dy); ang = add_mul_unfused(qb[2], tt, dth);
+  } else {
+    // nerf:117  p = traj[1:] * (1 - t) + traj[:-1] * t
+    float omt = 1.0f - tt;
+    x = mix_unfused(qb[0], omt, qa[0], tt); y = mix_unfused(qb[1], omt, qa[1], tt);
+  }
+  return SamplePose{x, y, ang};
+}
+
 // sin(x + q*pi/2) for q in Z: 3-term Cody-Waite reduction to [-pi/4, pi/4] + minimax polynomials
 // (<= 1.5 ulp for |x| < 1e5; checked against float64 in tests/test_host_logic.py through an fp32 emulation).
 __device__ __forceinline__ float sin_quadrant(float x, int q) {

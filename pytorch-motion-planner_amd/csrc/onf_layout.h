@@ -261,17 +261,8 @@ __device__ __forceinline__ long long point_finish(const OnfKernelArgs& a, const 
     tt = philox_uniform(a.seed, r.gp, a.rng_offset);
     if (g == 0 && r.valid) a.t[r.row] = tt;
   }
-  // every product and sum rounded on its own, as the reference's separate torch ops do (no fused multiply-add): the
-  // sample is then bit-identical to the oracle's for the same t, and K1 sees the reference's inputs
-  if (a.dim == 3) {
-    // constrained:79-81  p = traj[1:] + t * wrap-theta(traj[:-1] - traj[1:])
-    float dx = r.qa[0] - r.qb[0], dy = r.qa[1] - r.qb[1], dth = wrap_angle(r.qa[2] - r.qb[2]);
-    x = add_mul_unfused(r.qb[0], tt, dx); y = add_mul_unfused(r.qb[1], tt, dy); ang = add_mul_unfused(r.qb[2], tt, dth);
-  } else {
-    // nerf:117  p = traj[1:] * (1 - t) + traj[:-1] * t
-    float omt = 1.0f - tt;
-    x = mix_unfused(r.qb[0], omt, r.qa[0], tt); y = mix_unfused(r.qb[1], omt, r.qa[1], tt);
-  }
+  const SamplePose s = collision_sample(a.dim, r.qa, r.qb, tt);
+  x = s.x; y = s.y; ang = s.ang;
   return r.valid ? r.row : a.n_points;
 }
 

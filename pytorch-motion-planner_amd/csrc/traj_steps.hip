@@ -7,6 +7,7 @@
 // keeps the loop on the C side of the boundary: per step it forms the Adam scalars exactly as torch.optim.Adam does
 // (Python / C doubles: 1 - beta^k through pow(), lr / bc1, sqrt(bc2), rounded to fp32 once) and enqueues
 //   nfopp_traj_collision_eval -> nfopp_traj_update -> [nfopp_reparametrize when step_count % reparam_freq == 0]
+// (nfopp_traj_steps_sdf: nfopp_traj_sdf_collision_eval in the first place)
 // on the caller's stream -- the same three entry points, the same kernels, the same arguments as n single calls, so
 // the results are bit-identical to n calls of the single-step sequence (tests/test_gpu_multistep.py).  Nothing
 // synchronises; the field must not change during the n steps (the reference's step with ONF learning needs the host
@@ -17,10 +18,10 @@
 
 using namespace nfopp;
 
-extern "C" int nfopp_traj_steps(const nfopp_onf_config* cfg, const float* params_dev, const nfopp_traj_hyper* hp,
-                                const nfopp_traj_buffers* buf, const nfopp_step_schedule* sched, int32_t n_steps,
-                                const float* t_steps_dev, float* terms_dev, void* stream) {
-  NFOPP_REQUIRE(cfg && params_dev && hp && buf && sched, "null argument");
+// The step loop both collision models share: `collision(t_k, k)` enqueues the model's collision entry for step k.
+template <class Collision>
+static int run_steps(const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf, const nfopp_step_schedule* sched,
+                     int32_t n_steps, const float* t_steps_dev, float* terms_dev, void* stream, Collision collision) {
   NFOPP_REQUIRE(n_steps >= 0, "negative step count");
   NFOPP_REQUIRE(sched->reparam_freq >= 1, "reparam_freq must be >= 1 (pass a value beyond the step count to disable)");
   NFOPP_REQUIRE(sched->t_mode == 0 || sched->t_mode == 1, "t_mode must be 0 (injected draws) or 1 (in-kernel Philox)");
@@ -39,9 +40,7 @@ extern "C" int nfopp_traj_steps(const nfopp_onf_config* cfg, const float* params
     h.adam_bc2_sqrt = (float)sqrt(bc2);
     float* t_k = sched->t_mode == 0 ? const_cast<float*>(t_steps_dev) + (int64_t)k * row : buf->t_dev;
     NFOPP_REQUIRE(t_k, "t_dev scratch [B, N-1] is required for t_mode 1");
-    int rc = nfopp_traj_collision_eval(cfg, params_dev, buf->traj_dev, buf->batch, buf->n_waypoints, buf->dim, t_k,
-                                       sched->t_mode, sched->seed, sched->rng_offset + (uint64_t)k, sched->traj_index_offset,
-                                       buf->onf_out4_dev, buf->active_dev, buf->live_ws_dev, stream);
+    int rc = collision(t_k, k);
     if (rc != NFOPP_OK) return rc;
     rc = nfopp_traj_update(&h, buf->batch, buf->n_waypoints, buf->dim, buf->traj_dev, buf->start_dev, buf->goal_dev,
                            buf->lam_dev, buf->cm_dev, buf->adam_m_dev, buf->adam_v_dev, t_k, buf->onf_out4_dev,
@@ -55,4 +54,27 @@ extern "C" int nfopp_traj_steps(const nfopp_onf_config* cfg, const float* params
     }
   }
   return NFOPP_OK;
+}
+
+extern "C" int nfopp_traj_steps(const nfopp_onf_config* cfg, const float* params_dev, const nfopp_traj_hyper* hp,
+                                const nfopp_traj_buffers* buf, const nfopp_step_schedule* sched, int32_t n_steps,
+                                const float* t_steps_dev, float* terms_dev, void* stream) {
+  NFOPP_REQUIRE(cfg && params_dev && hp && buf && sched, "null argument");
+  return run_steps(hp, buf, sched, n_steps, t_steps_dev, terms_dev, stream, [&](float* t_k, int32_t k) {
+    return nfopp_traj_collision_eval(cfg, params_dev, buf->traj_dev, buf->batch, buf->n_waypoints, buf->dim, t_k,
+                                     sched->t_mode, sched->seed, sched->rng_offset + (uint64_t)k, sched->traj_index_offset,
+                                     buf->onf_out4_dev, buf->active_dev, buf->live_ws_dev, stream);
+  });
+}
+
+// The same loop on a distance field (csrc/sdf_field.hip): live_ws_dev is not used.
+extern "C" int nfopp_traj_steps_sdf(const nfopp_sdf_field* field, const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf,
+                                    const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev,
+                                    float* terms_dev, void* stream) {
+  NFOPP_REQUIRE(field && hp && buf && sched, "null argument");
+  return run_steps(hp, buf, sched, n_steps, t_steps_dev, terms_dev, stream, [&](float* t_k, int32_t k) {
+    return nfopp_traj_sdf_collision_eval(field, buf->traj_dev, buf->batch, buf->n_waypoints, buf->dim, t_k, sched->t_mode,
+                                         sched->seed, sched->rng_offset + (uint64_t)k, sched->traj_index_offset,
+                                         buf->onf_out4_dev, buf->active_dev, stream);
+  });
 }

@@ -69,6 +69,13 @@ class StepScheduleC(ctypes.Structure):
                 ("t_mode", ctypes.c_int32)]
 
 
+class SdfFieldC(ctypes.Structure):
+    """nfopp_sdf_field: the distance image, its frame, the robot's discs, margin and gain (nfopp/distance_field.py)."""
+    _fields_ = [("sd_dev", _P), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("x0", ctypes.c_float),
+                ("y0", ctypes.c_float), ("inv_res", ctypes.c_float), ("n_discs", ctypes.c_int32),
+                ("disc", (ctypes.c_float * 3) * 8), ("margin", ctypes.c_float), ("gain", ctypes.c_float)]
+
+
 _SIGNATURES = {
     "nfopp_abi_version": (ctypes.c_int, []),
     "nfopp_last_error": (ctypes.c_char_p, []),
@@ -84,6 +91,12 @@ _SIGNATURES = {
                                          ctypes.c_int32, _P, _P, _P]),
     "nfopp_traj_steps": (ctypes.c_int, [ctypes.POINTER(OnfConfigC), _P, ctypes.POINTER(TrajHyperC), ctypes.POINTER(TrajBuffersC),
                                         ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P, _P]),
+    "nfopp_sdf_eval_points": (ctypes.c_int, [ctypes.POINTER(SdfFieldC), _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
+    "nfopp_traj_sdf_collision_eval": (ctypes.c_int, [ctypes.POINTER(SdfFieldC), _P, ctypes.c_int64, ctypes.c_int32,
+                                                     ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64,
+                                                     ctypes.c_int64, _P, _P, _P]),
+    "nfopp_traj_steps_sdf": (ctypes.c_int, [ctypes.POINTER(SdfFieldC), ctypes.POINTER(TrajHyperC), ctypes.POINTER(TrajBuffersC),
+                                            ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P, _P]),
     "nfopp_reparametrize": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nfopp_update_endpoints": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P,
                                               _P, _P, _P, _P, _P]),

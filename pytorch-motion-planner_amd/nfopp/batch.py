@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .distance_field import DistanceField
 from .engine import TrajectoryEngine
 from .grid_search import AstarTrajectoryInitializer, OccupancyGrid, grid_search_init
 from .lattice import GearLattice, LatticeGrid, lattice_gear_search_init, lattice_search_init
@@ -137,14 +138,22 @@ class BatchPlanner(object):
     The planner owns the field's update loop, so it FREEZES the ONF object (`ONF.freeze()`): launches reuse the pre-split
     weight image until the planner's own Adam step (or an in-place torch op) changes the parameters.  A caller who writes
     the parameters behind torch's back while a planner exists -- `dist.broadcast(onf.flat_parameters, 0)`, `.data`
-    assignments -- must call `onf.mark_modified()` afterwards (or construct with `freeze_field=False`)."""
+    assignments -- must call `onf.mark_modified()` afterwards (or construct with `freeze_field=False`).
+
+    `onf` may be a `DistanceField` instead: the collision term then comes from the signed distance image of an occupancy
+    grid (csrc/sdf_field.hip) and everything else -- init, step(n), replan, evaluate, path_stats, the seeders -- is as it
+    is behind the network.  `freeze_field` does not apply and `checker=` raises ValueError: there is nothing to fit."""
 
     def __init__(self, onf, batch, n_waypoints, hyper, velocity_hessian_weight=0.5, reparametrize_trajectory_freq=10,
                  device="cuda", seed=0, traj_index_offset=0, checker=None, fit_lr=2e-2, fit_betas=(0.9, 0.9),
                  optimize_collision_model_freq=1, trajectory_random_offset=0.02, course_random_offset=1.5,
                  angle_offset=0.0, random_field_points=10, collision_point_count=100, group=None,
                  init_angles_with_trajectory=False, global_batch=None, freeze_field=True):
-        if freeze_field:
+        if isinstance(onf, DistanceField):
+            # the field is a nfopp.DistanceField (DESIGN.md 24): the map is the model, there is nothing to freeze or to fit
+            if checker is not None:
+                raise ValueError("a DistanceField is not fitted: checker= goes with an ONF (pass the checker to evaluate())")
+        elif freeze_field:
             onf.freeze()
         self.init_angles_with_trajectory = bool(init_angles_with_trajectory)
         # trajectories over ALL ranks (continuous learning: denominator of the BCE mean); default = equal shards

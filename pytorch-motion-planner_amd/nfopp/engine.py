@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .distance_field import DistanceField
 
 
 def inverse_hessian(n, weight):
@@ -136,7 +137,8 @@ class TrajectoryHyper(object):
 
 class TrajectoryEngine(object):
     """Owns the batched state and runs the step pipeline.  `traj` may be an externally owned [B,N,D] (or [N,D])
-    HIP tensor (the planner's `_trajectory`); it is updated in place."""
+    HIP tensor (the planner's `_trajectory`); it is updated in place.  `onf` is the collision model: an ONF, or a
+    `DistanceField`, whose rows come from nfopp_traj_sdf_collision_eval / nfopp_traj_steps_sdf."""
 
     def __init__(self, onf, batch, n_waypoints, dim, hyper, velocity_hessian_weight, device, traj=None, seed=0,
                  traj_index_offset=0):
@@ -199,11 +201,17 @@ class TrajectoryEngine(object):
         else:
             mode = 1
         cfg = self.onf.config_c()
-        active, live = self._active_ptrs()
-        _lib.check(lib.nfopp_traj_collision_eval(cfg, _lib.ptr(self.onf.flat_parameters), _lib.ptr(self.traj), self.B,
-                                                 self.N, self.D, _lib.ptr(self.t), mode, self.seed, self.rng_offset,
-                                                 self.traj_index_offset, _lib.ptr(self.onf_out),
-                                                 active, live, _lib.stream_ptr()))
+        if isinstance(self.onf, DistanceField):
+            _lib.check(lib.nfopp_traj_sdf_collision_eval(cfg, _lib.ptr(self.traj), self.B, self.N, self.D, _lib.ptr(self.t),
+                                                         mode, self.seed, self.rng_offset, self.traj_index_offset,
+                                                         _lib.ptr(self.onf_out), _lib.ptr(self.active, torch.uint8),
+                                                         _lib.stream_ptr()))
+        else:
+            active, live = self._active_ptrs()
+            _lib.check(lib.nfopp_traj_collision_eval(cfg, _lib.ptr(self.onf.flat_parameters), _lib.ptr(self.traj), self.B,
+                                                     self.N, self.D, _lib.ptr(self.t), mode, self.seed, self.rng_offset,
+                                                     self.traj_index_offset, _lib.ptr(self.onf_out),
+                                                     active, live, _lib.stream_ptr()))
         if mode == 1:
             self.rng_offset += 1
 
@@ -248,8 +256,12 @@ class TrajectoryEngine(object):
         sched = _lib.StepScheduleC(float(self.hyper.lr), float(b1), float(b2), self.adam_step, int(step_count),
                                    self.traj_index_offset, self.seed, self.rng_offset, int(reparam_freq),
                                    0 if tdev is not None else 1)
-        _lib.check(lib.nfopp_traj_steps(cfg, P(self.onf.flat_parameters), hp, buf, sched, n, P(tdev),
-                                        P(self.terms) if want_terms else None, _lib.stream_ptr()))
+        terms = P(self.terms) if want_terms else None
+        if isinstance(self.onf, DistanceField):
+            _lib.check(lib.nfopp_traj_steps_sdf(cfg, hp, buf, sched, n, P(tdev), terms, _lib.stream_ptr()))
+        else:
+            _lib.check(lib.nfopp_traj_steps(cfg, P(self.onf.flat_parameters), hp, buf, sched, n, P(tdev), terms,
+                                            _lib.stream_ptr()))
         self.adam_step += n
         if tdev is None:
             self.rng_offset += n

@@ -37,6 +37,7 @@ class OccupancyGrid(GridFrame):
         self._occupancy_dev = None
         self._edt = {}        # border -> (dist2, nearest)
         self._inflated = {}   # (cells2, border) -> OccupancyGrid
+        self._sdf = {}        # border -> signed distance image
 
     @classmethod
     def _from_device(cls, occupancy_dev, boundaries, resolution):
@@ -46,7 +47,7 @@ class OccupancyGrid(GridFrame):
         grid._shape = tuple(occupancy_dev.shape)
         grid.boundaries, grid.resolution, grid.device = boundaries, resolution, occupancy_dev.device
         grid._occupancy_dev = occupancy_dev
-        grid._edt, grid._inflated = {}, {}
+        grid._edt, grid._inflated, grid._sdf = {}, {}, {}
         return grid
 
     @property
@@ -95,16 +96,26 @@ class OccupancyGrid(GridFrame):
         dist2; nearest still names cells of the grid.  Computed once per `border` value."""
         border = bool(border)
         if border not in self._edt:
-            lib = _lib.load()
-            occ = self.occupancy
-            rows, cols = self.shape
-            dist2 = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
-            nearest = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
-            ws = workspace(lib.nfopp_grid_edt_workspace_bytes(rows, cols), occ.device)
-            _lib.check(lib.nfopp_grid_edt(_lib.ptr(occ, torch.uint8), rows, cols, int(border), _lib.ptr(dist2, torch.int32),
-                                          _lib.ptr(nearest, torch.int32), ws.ptr, ws.nbytes, _lib.stream_ptr()))
-            self._edt[border] = (dist2, nearest)
+            self._edt[border] = _edt_of(self.occupancy, border)
         return self._edt[border]
+
+    def signed_distance_field(self, border=False):
+        """-> fp32 [rows, cols] on the device: the signed distance in metres at each cell's centre, positive in free cells
+        and negative in walls, resolution * (sqrt(dist2 to the nearest wall cell) - sqrt(dist2 to the nearest free cell))
+        formed in float64 and rounded once.  Of two edge-adjacent cells on either side of a wall's edge one holds
+        +resolution and the other -resolution: a linear interpolation crosses zero on the edge.  `border` counts the cells
+        outside the grid as walls for the first distance.  Where there is no wall, or no free cell, at all the missing
+        distance is taken as rows + cols cells, so every value is finite and an interpolation never forms inf * 0.
+        Computed once per `border` value (nfopp.DistanceField plans on it)."""
+        border = bool(border)
+        if border not in self._sdf:
+            to_wall = self.distance_transform(border)[0]
+            to_free = _edt_of(1 - self.occupancy, False)[0]
+            far = float(self.shape[0] + self.shape[1])
+            cells = [torch.where(d2 == EDT_NONE, torch.full_like(d2, far, dtype=torch.float64), torch.sqrt(d2.double()))
+                     for d2 in (to_wall, to_free)]
+            self._sdf[border] = ((cells[0] - cells[1]) * self.resolution).float()
+        return self._sdf[border]
 
     def clearance_field(self, border=False):
         """-> fp32 [rows, cols] on the device: the distance in metres from each cell's centre to the centre of the nearest
@@ -130,6 +141,18 @@ class OccupancyGrid(GridFrame):
 
 
 EDT_NONE = 2 ** 31 - 1   # dist2 on a grid without walls (INT32_MAX)
+
+
+def _edt_of(occ, border):
+    """nfopp_grid_edt of a uint8 0 / 1 device image -> (dist2, nearest), int32 [rows, cols]."""
+    lib = _lib.load()
+    rows, cols = occ.shape
+    dist2 = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
+    nearest = torch.empty(rows, cols, dtype=torch.int32, device=occ.device)
+    ws = workspace(lib.nfopp_grid_edt_workspace_bytes(rows, cols), occ.device)
+    _lib.check(lib.nfopp_grid_edt(_lib.ptr(occ, torch.uint8), rows, cols, int(border), _lib.ptr(dist2, torch.int32),
+                                  _lib.ptr(nearest, torch.int32), ws.ptr, ws.nbytes, _lib.stream_ptr()))
+    return dist2, nearest
 
 
 def margin_cells2(margin, resolution):
