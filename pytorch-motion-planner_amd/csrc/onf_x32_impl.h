@@ -86,6 +86,39 @@ __host__ __device__ constexpr int pos_of_slot(int s) {
 __host__ __device__ constexpr int swz1(int row) { return (row >> 2) & 3; }
 __host__ __device__ constexpr int swz2(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
+// ---- feature kinds at compile time ----------------------------------------------------------------------------------
+// The kernels exist for four feature dimensions, one per NKB, and the kind of an input position is a function of
+// (n_enc, fin) alone (decode_feature, csrc/onf_layout.h): positional below n_enc, angle below fin, the ones feature at fin,
+// pads behind it.  A lane works on positions in groups of four -- in L1 elements e = 4 h .. 4 h + 3 of block kb are
+// positions 16 kb + 8 h + 4 g + (0 .. 3), in L1^T registers r = 4 q .. 4 q + 3 of output tile mt are 32 mt + 8 q + 4 g +
+// (0 .. 3) -- and n_enc and fin are multiples of four, so each lane half of a (block, h) group holds one kind.  The group's
+// kind is what both halves can run:
+//   POSITIONAL  arg = wx u_x + (wy u_y + b)             d arg / d pose = (wx, wy, 0)
+//   ANGLE       arg = (theta + b) * fr                  d arg / d pose = (0, 0, fr)      (fr is stored where wx is: tw.x)
+//   MIXED       the halves differ (120 inputs: 96..99 | 100..103): both forms and a select on the table's `isa`, as for
+//               every group from block FS on before the kinds were fixed.
+// A half of ones / pad positions is FREE and takes the other half's kind (POSITIONAL, what isa = 0 selected, if both are
+// free).  Why a free half gives the same bits under either form: its table entries (c0, c1, b) are all +0 (decode_feature
+// returns zeros from fin on; only the quadrant q is set, for the ones feature and in the derivative table), so
+//  * POSITIONAL: fmaf(+0, u_y, +0) = +0 and fmaf(+0, u_x, +0) = +0 (a product +-0 added to +0 under round-to-nearest);
+//    ANGLE: (theta + 0) * (+0) is +0 for theta >= +0 and -0 for theta < 0 (theta = -0: (-0) + (+0) = +0).
+//  * the reduction maps both to the same bits: t = fmaf(+-0, 1/2pi, 1.5 * 2^23) = 1.5 * 2^23, j = t - 1.5 * 2^23 = +0;
+//    r = fmaf(+0, -2pi_hi, arg) = (-0) + arg = arg, -0 kept; r = fmaf(+0, 2pi_lo, r) = (+0) + r = +0 for r of either sign:
+//    this is where the sign of zero dies.  v = sin(fmaf(+0, 1/2pi, q)) = sin(q) for q != 0 and sin(+0) = +0 for q = 0: the
+//    feature (+0), its derivative factor (q = 1/4) and the ones position's (q = 1/2) have the bits of the other form.
+//  * the ones position: L1 forces the feature to exactly 1.0f after the evaluation, as before; only the lane half and the
+//    element that hold position fin do so now (ONE_KB, ONE_E, ONE_G below), where every element compared its position.
+//  * L1^T epilogue: a row adds d * (d arg / d pose) to gxs, gys and gt.  All three fmas stay for every kind, with the
+//    literal 0.0f where the select gave 0.0f: `s + (+-0)` turns a partial sum -0 into +0, and s = -0 cannot be ruled out (a
+//    chain whose products all underflow), so not even the fma with a zero coefficient is dropped.  For a free half in an
+//    ANGLE group the coefficients swap places -- (tw.x, tw.y, 0.0f) becomes (0.0f, tw.y, tw.x) -- and tw.x is +0 there:
+//    the same three operands.
+//  (A non-finite theta makes (theta + 0) * 0 a NaN where the positional form gave +0.  It only does so in a group shared
+//  with angle features, whose own arguments (theta + b) * fr are NaN or infinite then and leave the reduction as NaN
+//  (inf - inf): a1 and everything behind it is NaN for that sample either way.)
+// Nothing else changes: no product, no sum, no order of the gxs / gys / gt chains.
+enum Kind { POSITIONAL = 0, ANGLE = 1, MIXED = 2, FREE = 3 };
+
 template <int NKB>
 struct Cfg {
   static constexpr int NMT = (NKB + 1) / 2;        // 32-position output tiles of L1^T
@@ -93,6 +126,22 @@ struct Cfg {
   static constexpr int S_L1 = 0, S_L2 = S_L1 + 4 * NKB, S_L2T = S_L2 + 4 * HK, S_L1T = S_L2T + 4 * HK;
   static constexpr int STEPS = S_L1T + HK * NMT;
   static constexpr size_t BLOB_BYTES = size_t(STEPS + 4) * 1024;   // + the three-step look-ahead past the last step
+  // the stock shape of this NKB (onf_route sends no other n_enc here; launch_x32 refuses another fin or angle dimension)
+  static constexpr int N_ENC = NKB >= 13 ? 200 : 100, ANG_DIM = (NKB == 14 || NKB == 8) ? 10 : 0, FIN = N_ENC + 2 * ANG_DIM;
+  static_assert(N_ENC % 4 == 0 && FIN % 4 == 0 && N_ENC / 16 == FS && (FIN + 16) / 16 == NKB, "one kind per lane half of a group");
+  static constexpr bool geometry_ok(int n_enc, int fin, int ang_dim) { return n_enc == N_ENC && fin == FIN && ang_dim == ANG_DIM; }
+  static constexpr Kind half_kind(int pos) { return pos < N_ENC ? POSITIONAL : pos < FIN ? ANGLE : FREE; }
+  // kind of elements 4 h .. 4 h + 3 of input block kb (= registers 4 q .. 4 q + 3 of output tile mt: kb = 2 mt + (q >> 1), h = q & 1)
+  static constexpr Kind group_kind(int kb, int h) {
+    const Kind k0 = half_kind(16 * kb + 8 * h), k1 = half_kind(16 * kb + 8 * h + 4);
+    return k0 == FREE ? (k1 == FREE ? POSITIONAL : k1) : (k1 == FREE || k1 == k0) ? k0 : MIXED;
+  }
+  // L1 prepares a block behind the 24 MFMAs of the block in front of it: evaluation instructions of a pair of features in
+  // group h (8 per feature, 11 with both argument forms and the select), and all of a block's with the 4 x 11 of the splits
+  static constexpr int l1_eval_items(int kb, int h) { return group_kind(kb, h) == MIXED ? 22 : 16; }
+  static constexpr int l1_items(int kb) { return 2 * l1_eval_items(kb, 0) + 2 * l1_eval_items(kb, 1) + 44; }
+  // position fin, the ones feature: block, element and lane half
+  static constexpr int ONE_KB = FIN >> 4, ONE_E = 4 * ((FIN >> 3) & 1) + (FIN & 3), ONE_G = (FIN >> 2) & 1;
 };
 
 // ---- extended weight matrices (the folded biases / skip row / ones unit) ---------------------------------------
@@ -290,6 +339,13 @@ __device__ __forceinline__ void eval_item(EvalState& s, const f32x4& tw, float u
   if constexpr (U == 6) s.v = fmaf(s.r, 0.159154943f, tw.w);
   if constexpr (U == 7) s.v = __builtin_amdgcn_sinf(s.v);
 }
+// the same for an angle feature sin((theta + b) * fr + q) (angle_encoder.py:16; fr in tw.x), 8 per feature
+template <int U>
+__device__ __forceinline__ void eval_angle_item(EvalState& s, const f32x4& tw, float th) {
+  if constexpr (U == 0) s.arg = th + tw.z;
+  else if constexpr (U == 1) s.arg = s.arg * tw.x;
+  else eval_item<U>(s, tw, 0.0f, 0.0f);   // (U >= 2: the reduction and the sine, no pose operand)
+}
 
 // Workgroup shapes: XT = 512 threads (two waves per SIMD, 256 samples per pass) fills the chip at scale; XT = 256 (one wave per
 // SIMD, 128 samples per pass) takes the launches that cannot give every CU a 256-sample chunk: twice the CUs take part and a
@@ -323,11 +379,11 @@ __device__ __forceinline__ void stepN(f32x16 (&acc)[NT], const u32x4& ah, const 
   });
 }
 
-// one instruction of the evaluation of a feature of ANY kind (positional / angle / ones / pad; the arithmetic of
-// feature_any in the kernel): 12 per feature.  isa != 0: angle feature (angle_encoder.py:16); is_one: the ones feature.
+// one instruction of the evaluation of a feature in a MIXED group (Cfg::group_kind: positional in one lane half, angle in
+// the other): both argument forms and a select, 11 per feature.  isa != 0: angle feature (angle_encoder.py:16).
 struct EvalAnyState { float arg, za, t, j, r, v; };
 template <int U>
-__device__ __forceinline__ void eval_any_item(EvalAnyState& s, const f32x4& tw, float isa, float ux, float uy, float th, bool is_one) {
+__device__ __forceinline__ void eval_any_item(EvalAnyState& s, const f32x4& tw, float isa, float ux, float uy, float th) {
   if constexpr (U == 0) s.arg = fmaf(tw.y, uy, tw.z);
   if constexpr (U == 1) s.arg = fmaf(tw.x, ux, s.arg);
   if constexpr (U == 2) s.za = th + tw.z;
@@ -339,7 +395,6 @@ __device__ __forceinline__ void eval_any_item(EvalAnyState& s, const f32x4& tw, 
   if constexpr (U == 8) s.r = fmaf(s.j, 1.74845553e-07f, s.r);
   if constexpr (U == 9) s.v = fmaf(s.r, 0.159154943f, tw.w);
   if constexpr (U == 10) s.v = __builtin_amdgcn_sinf(s.v);
-  if constexpr (U == 11) s.v = is_one ? 1.0f : s.v;
 }
 
 // NT = 32-sample tiles per wave.  Shapes launched by x32::launch_t (host side below): <512 threads, NT 1> two waves per SIMD; <256, 1> for small
@@ -412,7 +467,6 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     X32_OPAQUE2(t);   // (finished bases, image offset included: see bases_w2f)
   };
   int ftl = O_FT + 64 * g, ftdl = O_FTD + 64 * g, isl = O_ISA + 16 * g, w3al = O_W3A + 16 * g, w3ll = O_W3L + 48 * g;
-  int fin_rel = geo.fin - 4 * g;   // position == fin  <=>  16 kb + 8 (e >> 2) + (e & 3) == fin_rel
 
   const unsigned lane16 = lane * 16;
   const __amdgpu_buffer_rsrc_t blob_rsrc =
@@ -447,7 +501,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     long long pidx[NT];
     // table bases: opaque per chunk, so that (base + small constant) stays an immediate offset of the LDS read instead
     // of one hoisted register per constant
-    asm volatile("" : "+v"(ftl), "+v"(ftdl), "+v"(isl), "+v"(w3al), "+v"(w3ll), "+v"(fin_rel));
+    asm volatile("" : "+v"(ftl), "+v"(ftdl), "+v"(isl), "+v"(w3al), "+v"(w3ll));
     if (NT == 1 && have_next) {
       ux[0] = nux; uy[0] = nuy; th[0] = nth; pidx[0] = npidx;
       have_next = false;
@@ -509,27 +563,19 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
     }
     u32x4 fh[2], fm[2];   // hi / mid fragments: this step and the next
 
-    // generic evaluation of one input feature (any kind), used for the first block and the angle / ones / pad blocks
-    auto feature_any = [&](auto special_c, int T, int kb, int e) __attribute__((always_inline)) {
-      constexpr bool SPECIAL = decltype(special_c)::value;   // the block may hold angle / ones / pad positions
+    // evaluation of one positional input feature in one piece, used for the first block (every other block is prepared
+    // behind the MFMAs of the block in front of it)
+    auto feature_pos = [&](int T, int kb, int e) __attribute__((always_inline)) {
       const int off = 256 * kb + 128 * (e >> 2) + 16 * (e & 3);
       const f32x4 tw = lds128f(ftl + off);
-      float arg = fmaf(tw.x, ux[T], fmaf(tw.y, uy[T], tw.z));
-      if constexpr (SPECIAL) {
-        const float isa = lds_at<float>(isl + (off >> 2));
-        const float za = (th[T] + tw.z) * tw.x;
-        arg = isa != 0.0f ? za : arg;
-      }
-      const float v = sin_halfturns_hw(arg, tw.w);
-      if constexpr (SPECIAL) return (16 * kb + 8 * (e >> 2) + (e & 3)) == fin_rel ? 1.0f : v;
-      else return v;
+      return sin_halfturns_hw(fmaf(tw.x, ux[T], fmaf(tw.y, uy[T], tw.z)), tw.w);
     };
-    auto features_upfront = [&](auto special_c, int kb, u32x4 (&out)[NT][3]) __attribute__((always_inline)) {
+    static_assert(C::FS > 0, "block 0 is positional");
+    auto features_upfront = [&](int kb, u32x4 (&out)[NT][3]) __attribute__((always_inline)) {
 #pragma unroll
       for (int T = 0; T < NT; ++T)
 #pragma unroll
-        for (int p = 0; p < 4; ++p)
-          split_pair(feature_any(special_c, T, kb, 2 * p), feature_any(special_c, T, kb, 2 * p + 1), out[T], p);
+        for (int p = 0; p < 4; ++p) split_pair(feature_pos(T, kb, 2 * p), feature_pos(T, kb, 2 * p + 1), out[T], p);
     };
 
     // ================================================================ L1: a1 = W1ext in
@@ -541,7 +587,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       int w1m[2][2] = {{w1f[0][0] + O_W1M, w1f[0][1] + O_W1M}, {w1f[1][0] + O_W1M, w1f[1][1] + O_W1M}};
       X32_OPAQUE2(w1m);
       u32x4 bA[NT][3], bB[NT][3];
-      features_upfront(std::false_type{}, 0, bA);
+      features_upfront(0, bA);
       // hooked preparation of the NEXT block's fragments: per tile 4 pairs x (16 evaluation + 11 split) instructions, 5 per
       // slot, the tiles' items alternating.  Schedule of a tile (item w): E0 E1 S0 E2 S1 E3 S2 S3; the table entries of
       // pair p+1 (shared by the tiles) are loaded at the start of E(p).
@@ -571,42 +617,61 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           split_item<u>(ss[T], fv[T][2 * p], fv[T][2 * p + 1], out[T], p);
         }
       };
-      // the same for a block that may hold angle / ones / pad positions: per tile 4 pairs x (24 evaluation + 11 split)
-      // instructions, 6 per slot; the arithmetic (and its order) is feature_any's
+      // the same for block NB >= FS, which can hold angle / ones / pad positions: the kind of a pair's group (Cfg::group_kind)
+      // picks its evaluation.  A positional or an angle pair runs 16 evaluation + 11 split instructions like a plain one, a
+      // MIXED pair 22 + 11 (both argument forms and the select on the table's isa: eval_any_item); the items are dealt
+      // Cfg::l1_items / 24 per slot, rounded up: the 5 of a plain block for every block of the four shapes (120 inputs,
+      // block 6: 120 items).  The element at position fin is forced to 1.0f behind its sine, in the lane half that holds it.
       EvalAnyState eas[NT][2];
       float isa2[2][2];
-      int nxt_is = 0, nxt_pos = 0;
-      auto load_pair_any = [&](int p) __attribute__((always_inline)) {
+      int nxt_is = 0;
+      auto load_pair_kind = [&](auto nbc, auto pc) __attribute__((always_inline)) {
+        constexpr int NB = decltype(nbc)::value, p = decltype(pc)::value;
         load_pair(p);
-        const int off = nxt_is + 32 * ((2 * p) >> 2) + 4 * ((2 * p) & 3);
-        const f32x2 fl2 = lds_at<f32x2>(off);
-        isa2[p & 1][0] = fl2.x; isa2[p & 1][1] = fl2.y;
+        if constexpr (C::group_kind(NB, p >> 1) == MIXED) {
+          const int off = nxt_is + 32 * ((2 * p) >> 2) + 4 * ((2 * p) & 3);
+          const f32x2 fl2 = lds_at<f32x2>(off);
+          isa2[p & 1][0] = fl2.x; isa2[p & 1][1] = fl2.y;
+        }
       };
-      auto l1_item_any = [&](auto wc, u32x4 (&out)[NT][3]) __attribute__((always_inline)) {
-        constexpr int T = decltype(wc)::value % NT, w = decltype(wc)::value / NT;
-        constexpr int seg = w < 24 ? 0 : w < 48 ? 1 : w < 59 ? 2 : w < 83 ? 3 : w < 94 ? 4 : w < 118 ? 5 : w < 129 ? 6 : w < 140 ? 7 : 8;
-        constexpr int start[9] = {0, 24, 48, 59, 83, 94, 118, 129, 140};
+      auto l1_item_kind = [&](auto nbc, auto wc, u32x4 (&out)[NT][3]) __attribute__((always_inline)) {
+        constexpr int NB = decltype(nbc)::value, T = decltype(wc)::value % NT, w = decltype(wc)::value / NT;
+        constexpr int E0 = C::l1_eval_items(NB, 0), E1 = C::l1_eval_items(NB, 1);   // pairs 0, 1 | 2, 3
+        constexpr int start[9] = {0, E0, 2 * E0, 2 * E0 + 11, 2 * E0 + E1 + 11, 2 * E0 + E1 + 22, 2 * E0 + 2 * E1 + 22,
+                                  2 * E0 + 2 * E1 + 33, 2 * E0 + 2 * E1 + 44};
+        constexpr int seg = w < start[1] ? 0 : w < start[2] ? 1 : w < start[3] ? 2 : w < start[4] ? 3 : w < start[5] ? 4
+                            : w < start[6] ? 5 : w < start[7] ? 6 : w < start[8] ? 7 : 8;
         constexpr int evp[9] = {0, 1, -1, 2, -1, 3, -1, -1, -1}, spp[9] = {-1, -1, 0, -1, 1, -1, 2, 3, -1};
         constexpr int u = w - start[seg];
         if constexpr (evp[seg] >= 0) {
           constexpr int p = evp[seg], which = u & 1, st = u >> 1, e = 2 * p + which;
-          if constexpr (u == 0 && p < 3 && T == 0) load_pair_any(p + 1);
-          eval_any_item<st>(eas[T][which], tw[p & 1][which], isa2[p & 1][which], ux[T], uy[T], th[T],
-                            (nxt_pos + 8 * (e >> 2) + (e & 3)) == fin_rel);
-          if constexpr (st == 11) fv[T][e] = eas[T][which].v;
+          constexpr Kind K = C::group_kind(NB, p >> 1);
+          constexpr bool ONE = NB == C::ONE_KB && e == C::ONE_E;
+          if constexpr (u == 0 && p < 3 && T == 0) load_pair_kind(nbc, ic<p + 1>{});
+          if constexpr (K == MIXED) eval_any_item<st>(eas[T][which], tw[p & 1][which], isa2[p & 1][which], ux[T], uy[T], th[T]);
+          else if constexpr (K == ANGLE) eval_angle_item<st>(es[T][which], tw[p & 1][which], th[T]);
+          else eval_item<st>(es[T][which], tw[p & 1][which], ux[T], uy[T]);
+          if constexpr (st == (K == MIXED ? 10 : 7)) {
+            const float v = K == MIXED ? eas[T][which].v : es[T][which].v;
+            fv[T][e] = (ONE && g == C::ONE_G) ? 1.0f : v;
+          }
         } else if constexpr (spp[seg] >= 0) {
           constexpr int p = spp[seg];
           split_item<u>(ss[T], fv[T][2 * p], fv[T][2 * p + 1], out[T], p);
         }
       };
-      // MFMA steps of block kb (fragments in bc), preparing block kb + 1 into bn when HOOK (1: a plain block, 2: any kind)
-      auto l1_block = [&](auto hook_c, auto par_c, int kb, const u32x4 (&bc)[NT][3], u32x4 (&bn)[NT][3], auto first_c) __attribute__((always_inline)) {
-        constexpr int HOOK = decltype(hook_c)::value;
+      // MFMA steps of block kb (fragments in bc), preparing block kb + 1 into bn: PREP -1 nothing, 0 a plain block, from FS
+      // on block PREP (= kb + 1) by its kinds
+      auto l1_block = [&](auto prep_c, auto par_c, int kb, const u32x4 (&bc)[NT][3], u32x4 (&bn)[NT][3], auto first_c) __attribute__((always_inline)) {
+        constexpr int PREP = decltype(prep_c)::value;
+        constexpr int HOOK = PREP < 0 ? 0 : PREP == 0 ? 1 : 2;
+        static_assert(PREP <= 0 || PREP >= C::FS, "blocks below FS are plain");
+        constexpr int PER_SLOT = HOOK == 2 ? (C::l1_items(PREP) + 23) / 24 : 5;   // (5 for every block of the four shapes)
         constexpr bool FIRST = decltype(first_c)::value;   // block 0: the accumulators start here
         constexpr int PAR = decltype(par_c)::value;   // parity of kb
         const int kq = 64 * (kb >> 1);
         if constexpr (HOOK == 1) { nxt_ft = ftl + 256 * (kb + 1); load_pair(0); }
-        if constexpr (HOOK == 2) { nxt_ft = ftl + 256 * (kb + 1); nxt_is = isl + 64 * (kb + 1); nxt_pos = 16 * (kb + 1); load_pair_any(0); }
+        if constexpr (HOOK == 2) { nxt_ft = ftl + 256 * (kb + 1); nxt_is = isl + 64 * (kb + 1); load_pair_kind(prep_c, ic<0>{}); }
         sfor<0, 4>([&](auto mtc) {
           constexpr int mt = decltype(mtc)::value;
           // this step's hi / mid were fetched one step ago; fetch the next step's (past the last block: a harmless
@@ -623,27 +688,28 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           __builtin_amdgcn_sched_barrier(0);
           stepN<NT, 6 * NT * mt, FIRST>(acc1[mt], fh[mt & 1], fm[mt & 1], fl[(4 * PAR + mt) & (RL - 1)], bc, [&](auto slot) {
             if constexpr (HOOK == 1) sfor<0, 5>([&](auto i) { l1_item(ic<5 * decltype(slot)::value + decltype(i)::value>{}, bn); });
-            if constexpr (HOOK == 2) sfor<0, 6>([&](auto i) { l1_item_any(ic<6 * decltype(slot)::value + decltype(i)::value>{}, bn); });
+            if constexpr (HOOK == 2)
+              sfor<0, PER_SLOT>([&](auto i) { l1_item_kind(prep_c, ic<PER_SLOT * decltype(slot)::value + decltype(i)::value>{}, bn); });
           });
         });
       };
       constexpr int FS = C::FS;
       fh[0] = lds128(O_W1H + w1f[0][0]); fm[0] = lds128(w1m[0][0]);
-      l1_block(ic<1>{}, ic<0>{}, 0, bA, bB, std::true_type{});
-      l1_block(ic<1>{}, ic<1>{}, 1, bB, bA, std::false_type{});
+      l1_block(ic<0>{}, ic<0>{}, 0, bA, bB, std::true_type{});
+      l1_block(ic<0>{}, ic<1>{}, 1, bB, bA, std::false_type{});
 #pragma unroll 1
       for (int kp = 1; kp < FS / 2 - 1; ++kp) {
-        l1_block(ic<1>{}, ic<0>{}, 2 * kp, bA, bB, std::false_type{});
-        l1_block(ic<1>{}, ic<1>{}, 2 * kp + 1, bB, bA, std::false_type{});
+        l1_block(ic<0>{}, ic<0>{}, 2 * kp, bA, bB, std::false_type{});
+        l1_block(ic<0>{}, ic<1>{}, 2 * kp + 1, bB, bA, std::false_type{});
       }
-      l1_block(ic<1>{}, ic<0>{}, FS - 2, bA, bB, std::false_type{});
+      l1_block(ic<0>{}, ic<0>{}, FS - 2, bA, bB, std::false_type{});
       // blocks FS .. NKB-1 can hold angle / ones / pad features: each is prepared behind the block in front of it
-      l1_block(ic<2>{}, ic<1>{}, FS - 1, bB, bA, std::false_type{});
+      l1_block(ic<FS>{}, ic<1>{}, FS - 1, bB, bA, std::false_type{});
       sfor<FS, NKB>([&](auto kbc) {
         constexpr int kb = decltype(kbc)::value;
-        constexpr int HK2 = kb + 1 < NKB ? 2 : 0;
-        if constexpr ((kb - FS) % 2 == 0) l1_block(ic<HK2>{}, ic<(kb & 1)>{}, kb, bA, bB, std::false_type{});
-        else l1_block(ic<HK2>{}, ic<(kb & 1)>{}, kb, bB, bA, std::false_type{});
+        constexpr int NXT = kb + 1 < NKB ? kb + 1 : -1;
+        if constexpr ((kb - FS) % 2 == 0) l1_block(ic<NXT>{}, ic<(kb & 1)>{}, kb, bA, bB, std::false_type{});
+        else l1_block(ic<NXT>{}, ic<(kb & 1)>{}, kb, bB, bA, std::false_type{});
       });
     }
     float skipv[NT];   // position 100 = tile 3, g = 1, register 0: W3b . in + b3 (lanes g = 1)
@@ -922,29 +988,46 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
           });
         });
       };
-      // epilogue of a tile that can hold angle / ones / pad positions: evaluated after its steps
-      auto ep_any = [&](int mt, const f32x16 (&acc)[NT]) __attribute__((always_inline)) {
+      // epilogue of the last tile, which can hold angle / ones / pad positions: evaluated after its steps, each register by
+      // the kind of its group (Cfg::group_kind; a MIXED group: both argument forms and the selects on the table's isa).  The
+      // three fmas of a row stay for every kind, in this order (see "feature kinds at compile time" above).
+      auto ep_any = [&](auto mtc, const f32x16 (&acc)[NT]) __attribute__((always_inline)) {
+        constexpr int mt = decltype(mtc)::value;
 #pragma unroll
         for (int T = 0; T < NT; ++T)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int off = 512 * mt + 128 * (r >> 2) + 16 * (r & 3);
+          sfor<0, 16>([&](auto rc) {
+            constexpr int r = decltype(rc)::value;
+            constexpr Kind K = C::group_kind(2 * mt + (r >> 3), (r >> 2) & 1);
+            constexpr int off = 512 * mt + 128 * (r >> 2) + 16 * (r & 3);
             const f32x4 e = lds128f(ftdl + off);
-            const float isa = lds_at<float>(isl + (off >> 2));
-            float arg = fmaf(e.x, ux[T], fmaf(e.y, uy[T], e.z));
-            const float za = (th[T] + e.z) * e.x;
-            arg = isa != 0.0f ? za : arg;
+            float arg, cx, ct;   // argument, d arg / d u_x, d arg / d theta
+            if constexpr (K == MIXED) {
+              const float isa = lds_at<float>(isl + (off >> 2));
+              const float za = (th[T] + e.z) * e.x;
+              arg = fmaf(e.x, ux[T], fmaf(e.y, uy[T], e.z));
+              arg = isa != 0.0f ? za : arg;
+              cx = isa != 0.0f ? 0.0f : e.x;
+              ct = isa != 0.0f ? e.x : 0.0f;
+            } else if constexpr (K == ANGLE) {
+              arg = (th[T] + e.z) * e.x;
+              cx = 0.0f;
+              ct = e.x;
+            } else {
+              arg = fmaf(e.x, ux[T], fmaf(e.y, uy[T], e.z));
+              cx = e.x;
+              ct = 0.0f;
+            }
             const float d = acc[T][r] * sin_halfturns_hw(arg, e.w);
             if constexpr (TRAIN) {
               eq[T][r & 3] = d * rho[T];
               // (an odd number of input blocks: the row of de ends in the middle of the last tile)
-              if ((r & 3) == 3 && 2 * mt + (r >> 3) < NKB) st4(r_de, vo_de + 128 * mt + 32 * (r >> 2), eq[T][0], eq[T][1], eq[T][2], eq[T][3]);
+              if constexpr ((r & 3) == 3 && 2 * mt + (r >> 3) < NKB) st4(r_de, vo_de + 128 * mt + 32 * (r >> 2), eq[T][0], eq[T][1], eq[T][2], eq[T][3]);
             } else {
-              gxs[T][r & 1] = fmaf(d, isa != 0.0f ? 0.0f : e.x, gxs[T][r & 1]);
+              gxs[T][r & 1] = fmaf(d, cx, gxs[T][r & 1]);
               gys[T][r & 1] = fmaf(d, e.y, gys[T][r & 1]);
-              gt[T] = fmaf(d, isa != 0.0f ? e.x : 0.0f, gt[T]);
+              gt[T] = fmaf(d, ct, gt[T]);
             }
-          }
+          });
       };
       {
         fhn = lds_tr(t1[0][0], t1[1][0]);
@@ -958,7 +1041,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
 #pragma unroll
         for (int T = 0; T < NT; ++T) accp[T] = accc[T];
       }
-      ep_any(C::NMT - 1, accp);
+      ep_any(ic<C::NMT - 1>{}, accp);
 #pragma unroll
       for (int q = 0; q < LOOK; ++q) fl[q] = fl7[q];   // the first steps of the next chunk (fetched during the last tile)
     }

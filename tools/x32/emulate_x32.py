@@ -288,6 +288,83 @@ def run(fin, seed=0):
     print(f'fin={fin}: L1 / L2 / L2T / L1T fragments, chain, folded bias / skip / ones: OK')
 
 
+# ---- feature kinds at compile time (Cfg<NKB>::group_kind of onf_x32_impl.h, restated) ---------------------------------
+POSITIONAL, ANGLE, MIXED, FREE = 'positional', 'angle', 'mixed', 'free'
+STOCK = {14: (200, 220), 13: (200, 200), 8: (100, 120), 7: (100, 100)}      # NKB -> (n_enc, fin)
+
+
+def half_kind(n_enc, fin, pos):
+    return POSITIONAL if pos < n_enc else ANGLE if pos < fin else FREE
+
+
+def group_kind(n_enc, fin, kb, h):
+    k0, k1 = half_kind(n_enc, fin, 16 * kb + 8 * h), half_kind(n_enc, fin, 16 * kb + 8 * h + 4)
+    if k0 == FREE:
+        return POSITIONAL if k1 == FREE else k1
+    return k0 if (k1 == FREE or k1 == k0) else MIXED
+
+
+def decode_feature(n_enc, fin, f):
+    """csrc/onf_layout.h: (is_angle, table entry all zero) of input position f, the ones feature at fin"""
+    if f < n_enc:
+        return False, False
+    if f < fin:
+        return True, False
+    return False, True
+
+
+def sin_arg_f32(arg, q):
+    """the reduction of sin_halfturns_hw up to the operand of v_sin_f32, in float32, for arg = +-0 (every product is an
+    exact zero, so fmaf(a, b, c) = a * b + c with the IEEE signs of zero)"""
+    f = np.float32
+    assert arg == 0
+    t = f(arg * f(0.159154943)) + f(12582912.0)
+    j = f(t - f(12582912.0))
+    r = f(f(j * f(-6.28318548202514648)) + arg)
+    r = f(f(j * f(1.74845553e-07)) + r)
+    return f(f(r * f(0.159154943)) + q)
+
+
+def check_kinds():
+    f = np.float32
+    want = {14: {(12, 0): POSITIONAL, (12, 1): ANGLE, (13, 0): ANGLE, (13, 1): ANGLE},
+            13: {(12, 0): POSITIONAL, (12, 1): POSITIONAL},
+            8: {(6, 0): MIXED, (6, 1): ANGLE, (7, 0): ANGLE, (7, 1): POSITIONAL},
+            7: {(6, 0): POSITIONAL, (6, 1): POSITIONAL}}
+    for nkb, (n_enc, fin) in STOCK.items():
+        assert (fin + 16) // 16 == nkb and n_enc % 4 == 0 and fin % 4 == 0
+        fs = n_enc // 16
+        for kb in range(nkb + 1):          # (+ the block past the last one that an odd NKB's last output tile covers)
+            for h in range(2):
+                kind = group_kind(n_enc, fin, kb, h)
+                if kb < fs:
+                    assert kind == POSITIONAL, (nkb, kb, h)
+                elif kb < nkb:
+                    assert kind == want[nkb][(kb, h)], (nkb, kb, h, kind)
+                for g in range(2):
+                    for r in range(4):
+                        is_angle, zero = decode_feature(n_enc, fin, 16 * kb + 8 * h + 4 * g + r)
+                        if kind == MIXED:
+                            continue                 # the kernel selects on the table's isa there
+                        # a position runs its own form, or its table entry is all zero
+                        assert zero or is_angle == (kind == ANGLE), (nkb, kb, h, g, r)
+        # the ones position: block, element, lane half
+        one_kb, one_e, one_g = fin >> 4, 4 * ((fin >> 3) & 1) + (fin & 3), (fin >> 2) & 1
+        assert 16 * one_kb + 8 * (one_e >> 2) + 4 * one_g + (one_e & 3) == fin
+    # an all-zero table entry under either form: the same operand of v_sin_f32, bit for bit, for theta of either sign
+    zero = f(0.0)
+    for q in (f(0.0), f(0.25), f(0.5)):
+        pos = sin_arg_f32(f(zero * f(1.7)) + f(f(zero * f(-2.3)) + zero), q)
+        for th in (f(-1.3), f(-0.0), f(0.0), f(2.1), f(np.pi), f(-np.pi)):
+            arg = f(f(th + zero) * zero)
+            ang = sin_arg_f32(arg, q)
+            assert pos.tobytes() == ang.tobytes(), (q, th, pos, ang)
+        assert pos.tobytes() == q.tobytes()
+    assert np.signbit(f(f(f(-1.3) + zero) * zero)) and not np.signbit(f(f(f(-0.0) + zero) * zero))
+    print('feature kinds: the table of the four stock shapes agrees with decode_feature; zero entries give one operand under both forms: OK')
+
+
 if __name__ == '__main__':
+    check_kinds()
     for fin in (220, 200, 120, 100):
         run(fin)

@@ -1,0 +1,34 @@
+"""GPU dev tool: record the 32x32 ONF kernel's output bits on the cases of tests/k1_kind_bits_cases.py (the input blocks whose
+feature kinds are fixed at compile time, and the last output tile's epilogue) with the CURRENT build into
+tests/golden/k1_kind_bits.npz -- run on the build whose results are to be kept, before the kernel is changed.
+Usage: python tools/x32/record_k1_kind_bits.py [out.npz]        (--check out.npz: compare instead of writing)"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "pytorch-motion-planner_amd"), ROOT):
+    sys.path.insert(0, p)
+import k1_kind_bits_cases as kk  # noqa: E402
+
+
+def words(a):
+    return np.ascontiguousarray(np.asarray(a)).view(np.uint8)
+
+
+args = [a for a in sys.argv[1:] if a != "--check"]
+path = args[0] if args else os.path.join(ROOT, "tests", "golden", "k1_kind_bits.npz")
+res = kk.run_cases()
+again = kk.run_cases()     # the kernel is deterministic: a second run must give the same words
+for k in res:
+    assert np.array_equal(words(res[k]), words(again[k])), k
+if "--check" in sys.argv[1:]:
+    z = np.load(path)
+    assert sorted(z.files) == sorted(res), "case lists differ"
+    bad = [k for k in res if not np.array_equal(words(res[k]), words(z[k]))]
+    print("%d arrays, %d differ %s" % (len(res), len(bad), bad[:8]))
+    sys.exit(1 if bad else 0)
+os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+np.savez_compressed(path, **res)
+print("%s: %d arrays, %d bytes" % (path, len(res), os.path.getsize(path)))
