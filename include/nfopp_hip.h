@@ -1202,6 +1202,51 @@ int nfopp_fleet_assign_delays(const uint64_t* pair_mask_dev, const uint64_t* bas
                               const int32_t* order_dev, int64_t b, int32_t max_delay, int32_t* delay_dev, int32_t* status_dev,
                               uint64_t* forbidden_dev, void* stream);
 
+/* ---- shift masks of oriented boxes for the scheduler (csrc/fleet_box_schedule.hip), additive under ABI 6 --------------------
+ * nfopp_fleet_shift_masks shifts discs: a fleet of cars that nfopp_box_track_conflicts calls free can still be delayed by it,
+ * or left NFOPP_SCHEDULE_UNRESOLVED.  nfopp_fleet_box_shift_masks writes masks of the same layout from the box check's rule;
+ * nfopp_fleet_assign_delays reads them as they are.  Everything about tracks, delayed robots, masks, bad robots and obstacles
+ * stays as nfopp_fleet_shift_masks states it; the pair predicate changes.  The device is compared bit for bit with the numpy
+ * restatement in tests/fleet_box_schedule_ref.py when that is given the device's unit vectors.
+ *
+ * Tracks.  tracks_dev [b, k, stride >= 3] fp32, x, y, theta first in a row, and heading_dev [b, k, 2] float64 from
+ *   nfopp_track_headings.  A robot delayed by q is at track[clamp(h - q, 0, k - 1)] at instant h, and its unit vector is
+ *   gathered with the same clamped index.
+ * Pair predicate C_ij(r): "the status of the pair is not NFOPP_BOX_PAIR_FREE" (CONFLICT or UNDECIDED) by the rule of
+ *   nfopp_box_track_conflicts with the given refine, margin, boxes box_dev [b, 4] and rounding radii radius_dev [b] (null = 0)
+ *   -- one set of device functions, csrc/box_pairs.h, which both kernel files call -- applied to robot i delayed by max(r, 0)
+ *   and robot j delayed by max(-r, 0), over k + |r| instants.  UNDECIDED counts as forbidden: a schedule built from these masks
+ *   is FREE by the box check, not merely free of conflicts.  dt and t0 do not enter (only times depend on them).
+ * Order of the boxes.  The box arithmetic is not even in the order of the two boxes.  Only i < j is evaluated, with i as the
+ *   first box, for every r; mask_ji is mask_ij with its 2 * max_delay + 1 bits reversed -- a copy, as in the box check's self
+ *   mode.
+ * Obstacles (optional: obstacles_dev null or m == 0).  obstacles_dev [m, k + max_delay, obstacle_stride >= 3] with
+ *   obstacle_heading_dev [m, k + max_delay, 2], obstacle_box_dev [m, 4] and obstacle_radius_dev [m] (null = 0), in absolute
+ *   time, never shifted.  Bit d of base_mask_dev[i]: the predicate on robot i delayed by d (the first box) against obstacle j
+ *   (the second) over all k + max_delay instants, ORed over the good obstacles.
+ * Bad tracks.  The box check's rule: a non-finite x, y, unit vector, box entry or radius, x0 >= x1 or y0 >= y1, or r < 0.  The
+ *   consequences are those of nfopp_fleet_shift_masks.
+ * Horizon.  In an interval where both robots stand still the poses at its two ends are the same.  Step 1 frees the pair when
+ *   |d|^2 >= D2.  Otherwise step 2 reads the same sa that the neighbouring real interval (or the last-instant term) reads, and
+ *   if step 2 finds no conflict, step 3 is ((sa + sa) - 0) * 0.5 - R >= 0 with sa - R >= 0: doubling and halving are exact, so
+ *   it is FREE.  The waiting intervals in front and the parked intervals behind therefore add neither a CONFLICT nor an
+ *   UNDECIDED, and the bit depends on the two delays through their difference alone, as for the discs.
+ * pair_mask_dev [b, b, 2], base_mask_dev [b], bad_dev [b]: exactly the layout nfopp_fleet_assign_delays reads; all of the three
+ *   is written.  workspace_dev: nfopp_fleet_box_shift_masks_workspace_bytes(b, m, k, max_delay) bytes (shape rows and obstacle
+ *   partials; m = 0 without obstacles), rewritten by every call.
+ * Everything runs on `stream`; nothing synchronises.  Arguments refused before any launch: a negative batch size or one above
+ *   2^31 - 1, max_delay outside 0 .. 63, k < 1 or too large for an index, a stride < 3, refine outside
+ *   0 .. NFOPP_BOX_CONFLICT_MAX_REFINE, margin not finite, a null tracks / heading / box / mask / bad pointer, a null obstacle
+ *   heading or box pointer with obstacles to read, more tiles of 8 x 8 pairs than a grid holds, a workspace that is null or
+ *   too small.  b == 0 returns 0 with null pointers. */
+size_t nfopp_fleet_box_shift_masks_workspace_bytes(int64_t b, int64_t m, int32_t k, int32_t max_delay);
+int nfopp_fleet_box_shift_masks(const float* tracks_dev, const double* heading_dev, int64_t b, int32_t stride, int32_t k,
+                                const float* box_dev, const float* radius_dev, double margin, int32_t refine,
+                                int32_t max_delay, const float* obstacles_dev, const double* obstacle_heading_dev, int64_t m,
+                                int32_t obstacle_stride, const float* obstacle_box_dev, const float* obstacle_radius_dev,
+                                uint64_t* pair_mask_dev, uint64_t* base_mask_dev, int32_t* bad_dev, void* workspace_dev,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- space-time grid search for the robots a schedule cannot place (csrc/spacetime_search.hip), additive under ABI 6 ---------
  * nfopp_fleet_assign_delays ends with robots it cannot place: a robot placed before them waits on their path, crosses it at the
  * wrong time or parks on it for good, and no re-timing of a fixed path gets round that.  These entries give such a robot

@@ -44,8 +44,12 @@
 //  Summary row of track i over its good partners j: the lexicographic minima on (tc_ij, j) and on (tu_ij, j) -- the smaller j
 //    wins a tie -- and the numbers of partners whose status is CONFLICT and UNDECIDED.
 //
+// The device functions of the rule -- sep, steps 1 .. 5, the walk of an interval's tree, the last-instant term, the shape row --
+// live in box_pairs.h, which fleet_box_schedule.hip includes too; H above is box_pairs.h's BC_HALF_PI_UP = 0x1.921fb54442d19p+0;
+//
 // Loops: a pair visits at most 2^(refine + 1) - 1 nodes per interval, each found from the interval's end points in at most
 // `refine` halvings (no stack, so no scratch).  Nothing waits on another workgroup; no atomics and no float sums.
+#include "box_pairs.h"
 #include "common.h"
 #include "track_pairs.h"
 
@@ -58,12 +62,7 @@ constexpr int BC_CHUNK = 16;      // intervals staged per trip (BC_CHUNK + 1 ins
 constexpr int BC_THREADS = 256;   // 32 x 8 threads, 4 pairs each
 constexpr int BC_PITCH = BC_TILE + 1;
 constexpr int BC_PART = 7;        // doubles of a partial: tc, its partner, conflicts, tu, its partner, undecided, good partners (-1: bad)
-constexpr int BC_SHAPE = 8;       // doubles of a shape row: x0, x1, y0, y1, reach, r, bad, unused
-constexpr int BC_MAX_REFINE = NFOPP_BOX_CONFLICT_MAX_REFINE;
-constexpr double BC_HALF_PI_UP = 0x1.921fb54442d19p+0;   // the float64 next above pi / 2
 static_assert(BC_TILE == 32 && BC_THREADS == 256, "the thread map below is 32 x 8 threads on 32 x 32 pairs");
-
-struct Pose2 { double x, y, c, s; };
 
 struct BoxConflictArgs {
   const float* a; const float* b;            // b == a in self mode
@@ -76,73 +75,6 @@ struct BoxConflictArgs {
   double* part_a; double* part_b;            // [ba, ntb, BC_PART], [bb, nta, BC_PART] (self mode: part_a alone)
   long long nta, ntb;
 };
-
-__device__ __forceinline__ bool finite64(double v) { return fabs(v) < (double)__builtin_inff(); }
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
-__device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
-
-__device__ __forceinline__ double axis_gap(double t, const double* box, double cx, double cy, double s0, double s1) {
-#pragma clang fp contract(off)
-  const double a0 = box[0] * cx, a1 = box[1] * cx, b0 = box[2] * cy, b1 = box[3] * cy;
-  const double lo = (t + dmin(a0, a1)) + dmin(b0, b1);
-  const double hi = (t + dmax(a0, a1)) + dmax(b0, b1);
-  return dmax(lo - s1, s0 - hi);
-}
-
-__device__ __forceinline__ double box_separation(const Pose2& pi, const Pose2& pj, const double* bi, const double* bj) {
-#pragma clang fp contract(off)
-  const double dx = pj.x - pi.x, dy = pj.y - pi.y;
-  const double cr = pi.c * pj.c + pi.s * pj.s;
-  const double sr = pi.c * pj.s - pi.s * pj.c;
-  const double xi = dx * pi.c + dy * pi.s;
-  const double yi = dy * pi.c - dx * pi.s;
-  const double xj = -(dx * pj.c + dy * pj.s);
-  const double yj = -(dy * pj.c - dx * pj.s);
-  const double g1 = axis_gap(xi, bj, cr, -sr, bi[0], bi[1]);
-  const double g2 = axis_gap(yi, bj, sr, cr, bi[2], bi[3]);
-  const double g3 = axis_gap(xj, bi, cr, sr, bj[0], bj[1]);
-  const double g4 = axis_gap(yj, bi, -sr, cr, bj[2], bj[3]);
-  return dmax(dmax(g1, g2), dmax(g3, g4));
-}
-
-// |u + v| and |v - u| of two unit vectors
-__device__ __forceinline__ double unit_sum_norm(const Pose2& p, const Pose2& q) {
-#pragma clang fp contract(off)
-  const double sx = p.c + q.c, sy = p.s + q.s;
-  return sqrt(sx * sx + sy * sy);
-}
-__device__ __forceinline__ double unit_chord(const Pose2& p, const Pose2& q) {
-#pragma clang fp contract(off)
-  const double ex = q.c - p.c, ey = q.s - p.s;
-  return sqrt(ex * ex + ey * ey);
-}
-__device__ __forceinline__ Pose2 mid_pose(const Pose2& p, const Pose2& q, double l) {
-#pragma clang fp contract(off)
-  Pose2 m;
-  m.x = (p.x + q.x) * 0.5; m.y = (p.y + q.y) * 0.5;
-  m.c = (p.c + q.c) / l; m.s = (p.s + q.s) / l;
-  return m;
-}
-
-enum NodeClass { NODE_FREE = 0, NODE_CONFLICT = 1, NODE_SPLIT = 2, NODE_UNDECIDED = 3 };
-
-// steps 1 .. 5 on one sub-interval
-__device__ __forceinline__ int classify_node(const Pose2& ia, const Pose2& ja, const Pose2& ib, const Pose2& jb, const double* bi,
-                                             const double* bj, double reach_i, double reach_j, double R, double D2, bool may_split) {
-#pragma clang fp contract(off)
-  const double d0x = ia.x - ja.x, d0y = ia.y - ja.y, d1x = ib.x - jb.x, d1y = ib.y - jb.y;
-  const double cc = d0x * d0x + d0y * d0y, e = d1x * d1x + d1y * d1y;
-  const Approach q = closest_approach(d0x, d0y, cc, d1x, d1y, e);
-  if (q.m >= D2) return NODE_FREE;
-  const double sa = box_separation(ia, ja, bi, bj);
-  if (sa - R < 0.0) return NODE_CONFLICT;
-  const double sb = box_separation(ib, jb, bi, bj);
-  const double rot = reach_i * unit_chord(ia, ib) + reach_j * unit_chord(ja, jb);
-  const double mot = sqrt(q.a) + BC_HALF_PI_UP * rot;
-  if (((sa + sb) - mot) * 0.5 - R >= 0.0) return NODE_FREE;
-  if (may_split && unit_sum_norm(ia, ib) != 0.0 && unit_sum_norm(ja, jb) != 0.0) return NODE_SPLIT;
-  return NODE_UNDECIDED;
-}
 
 // (cos, sin) of every heading: heading_dev [b, k, 2]
 __global__ __launch_bounds__(BC_THREADS) void track_heading_kernel(const float* tracks, long long n, int stride, double* out) {
@@ -159,24 +91,7 @@ __global__ __launch_bounds__(BC_THREADS) void track_heading_kernel(const float* 
 __global__ __launch_bounds__(64) void box_shape_kernel(const float* tracks, const double* units, const float* box, const float* radius,
                                                        int stride, int k, double* shape) {
   const long long g = blockIdx.x;
-  const float* row = tracks + g * (long long)k * stride;
-  const double* u = units + g * (long long)k * 2;
-  int bad = 0;
-  for (int n = threadIdx.x; n < k; n += 64) {
-    const float x = row[(long long)n * stride], y = row[(long long)n * stride + 1];
-    if (!(finite32(x) && finite32(y) && finite64(u[2 * n]) && finite64(u[2 * n + 1]))) bad = 1;
-  }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x != 0) return;
-  const float x0 = box[4 * g], x1 = box[4 * g + 1], y0 = box[4 * g + 2], y1 = box[4 * g + 3];
-  const float r = radius ? radius[g] : 0.f;
-  if (!(finite32(x0) && finite32(x1) && finite32(y0) && finite32(y1) && finite32(r) && x0 < x1 && y0 < y1 && r >= 0.f)) bad = 1;
-  const double mx = (double)fmaxf(fabsf(x0), fabsf(x1)), my = (double)fmaxf(fabsf(y0), fabsf(y1));
-  const float corner = (float)sqrt(mx * mx + my * my);
-  const float reach = corner * 1.000001f;
-  double* o = shape + g * BC_SHAPE;
-  o[0] = (double)x0; o[1] = (double)x1; o[2] = (double)y0; o[3] = (double)y1;
-  o[4] = (double)reach; o[5] = (double)r; o[6] = bad ? 1.0 : 0.0; o[7] = 0.0;
+  box_shape_row(tracks + g * (long long)k * stride, units + g * (long long)k * 2, box, radius, g, stride, k, shape);
 }
 
 // (time, index) partial of one row over one tile's partners, in ascending partner order: strict < keeps the smaller index
@@ -268,32 +183,16 @@ __global__ __launch_bounds__(BC_THREADS) void box_conflict_tile_kernel(const Box
         const Pose2 ia0 = sP[kk * 2 * BC_TILE + li], ja0 = sP[kk * 2 * BC_TILE + BC_TILE + lj];
         const Pose2 ib0 = sP[(kk + 1) * 2 * BC_TILE + li], jb0 = sP[(kk + 1) * 2 * BC_TILE + BC_TILE + lj];
         const double tk = p.t0 + (double)(k0 + kk) * p.dt;
-        // the dyadic tree of the interval, depth first and left first, without a stack: node (depth, pos) is found from
-        // the interval's end points in `depth` halvings
-        int depth = 0, pos = 0;
-        for (int visit = 0; visit < (2 << BC_MAX_REFINE); ++visit) {
-          Pose2 ia = ia0, ja = ja0, ib = ib0, jb = jb0;
-          for (int l = depth - 1; l >= 0; --l) {
-            const Pose2 mi = mid_pose(ia, ib, unit_sum_norm(ia, ib)), mj = mid_pose(ja, jb, unit_sum_norm(ja, jb));
-            if ((pos >> l) & 1) { ia = mi; ja = mj; } else { ib = mi; jb = mj; }
-          }
-          const int cls = classify_node(ia, ja, ib, jb, bi, bj, reach_i, reach_j, R, D2, depth < p.refine);
-          if (cls == NODE_SPLIT) { ++depth; pos <<= 1; continue; }
-          if (cls != NODE_FREE) {
-            const double t = tk + ((double)pos / (double)(1 << depth)) * p.dt;
-            if (cls == NODE_CONFLICT) { ptc = t; break; }
-            if (!(ptu < inf)) ptu = t;
-          }
-          while (depth > 0 && (pos & 1)) { pos >>= 1; --depth; }
-          if (depth == 0) break;
-          ++pos;
-        }
+        walk_interval(ia0, ja0, ib0, jb0, bi, bj, reach_i, reach_j, R, D2, p.refine, [&](int cls, int depth, int pos) {
+          const double t = tk + ((double)pos / (double)(1 << depth)) * p.dt;
+          if (cls == NODE_CONFLICT) { ptc = t; return true; }
+          if (!(ptu < inf)) ptu = t;
+          return false;
+        });
       }
       if (k0 + n_int == p.k - 1 && !(ptc < inf)) {   // the last instant
         const Pose2 il = sP[n_int * 2 * BC_TILE + li], jl = sP[n_int * 2 * BC_TILE + BC_TILE + lj];
-        const double lx = il.x - jl.x, ly = il.y - jl.y;
-        const double cl = lx * lx + ly * ly;
-        if (!(cl >= D2) && box_separation(il, jl, bi, bj) - R < 0.0) ptc = (p.t0 + (double)(p.k - 1) * p.dt) + (0.0 / 1.0) * p.dt;
+        if (last_instant_conflict(il, jl, bi, bj, R, D2)) ptc = (p.t0 + (double)(p.k - 1) * p.dt) + (0.0 / 1.0) * p.dt;
       }
       tc[q] = ptc; tu[q] = ptu;
     }

@@ -7,7 +7,8 @@
 //   * fleet_shift_mask_kernel    one workgroup per FS_TILE x FS_TILE tile of pairs; work items are (pair, relative shift); a
 //                                window of both sides' tracks staged in LDS per FS_CHUNK instants; the bits of a pair are
 //                                collected by wave ballots.  Self mode: tiles of the upper triangle, mirrored by a bit reversal.
-//                                Obstacle mode: robots x obstacles, per-tile ORs of every robot's bits
+//                                Obstacle mode: robots x obstacles, per-tile ORs of every robot's bits.  The write-out is
+//                                fleet_masks.h's, which fleet_box_schedule.hip shares
 //   * fleet_base_kernel          one thread per robot: the OR of its obstacle tiles' partials
 //   * fleet_assign_kernel        ONE workgroup: the sequential pass over the priority order, ORs and a count-trailing-zeros
 //
@@ -39,23 +40,19 @@
 // Predicates, integer ORs and a count-trailing-zeros: no atomics, nothing depends on an order, two runs give the same bits.
 #include "block_collectives.h"
 #include "common.h"
+#include "fleet_masks.h"
 #include "track_pairs.h"
 
 #pragma clang fp contract(off)
 
 namespace nfopp {
 
-constexpr int FS_TILE = 8;                                   // a tile is 8 x 8 pairs
-constexpr int FS_PAIRS = FS_TILE * FS_TILE;
-constexpr int FS_THREADS = 256;
 constexpr int FS_CHUNK = 64;                                 // instants walked per trip
 constexpr int FS_WINDOW = FS_CHUNK + NFOPP_SCHEDULE_MAX_DELAY + 1;   // staged per track and trip: the chunk, max_delay before it, one more for d0
 constexpr int FS_ASSIGN_THREADS = 256;
 constexpr int FS_ASSIGN_WAVES = FS_ASSIGN_THREADS / 64;
 constexpr int FS_ASSIGN_HEAD = 64;                           // bytes in front of the state array: the reduction's scratch
-static_assert(FS_PAIRS == 64 && FS_THREADS == 256, "the write-out below is one wave on 64 pairs");
 static_assert((FS_WINDOW & (FS_WINDOW - 1)) == 0, "the staging loop splits its index by a mask");
-static_assert(FS_PAIRS * 128 / FS_THREADS <= 32, "one bit per item of a thread in a 32-bit register");
 static_assert(FS_ASSIGN_WAVES * 8 <= FS_ASSIGN_HEAD, "the reduction's scratch fits its head");
 
 struct ShiftMaskArgs {
@@ -88,22 +85,13 @@ __global__ __launch_bounds__(FS_THREADS) void fleet_bad_kernel(const float* trac
   if (lane == 0) flags[t] = (any || (radius && !finite32(radius[t]))) ? 1 : 0;
 }
 
-// the low 2 * max_delay + 1 bits of (lo, hi) reversed: bit p -> bit 2 * max_delay - p
-__device__ __forceinline__ void reverse_mask(unsigned long long lo, unsigned long long hi, int max_delay, unsigned long long* rlo,
-                                             unsigned long long* rhi) {
-  const unsigned long long flo = __brevll(hi), fhi = __brevll(lo);   // bit p -> bit 127 - p
-  const int s = 127 - 2 * max_delay;                                 // 1 .. 127
-  if (s >= 64) { *rlo = fhi >> (s - 64); *rhi = 0ull; }
-  else { *rlo = (flo >> s) | (fhi << (64 - s)); *rhi = fhi >> s; }
-}
-
 __global__ __launch_bounds__(FS_THREADS) void fleet_shift_mask_kernel(const ShiftMaskArgs p) {
   __shared__ float2 sA[FS_TILE * FS_WINDOW], sB[FS_TILE * FS_WINDOW];   // [track][slot]
   __shared__ float2 sLast[2 * FS_TILE];                                 // both sides' last samples
   __shared__ double sRad[2 * FS_TILE];
   __shared__ int sBad[2 * FS_TILE];                                     // bad, or past the end of its side
   __shared__ unsigned long long sMask[FS_PAIRS * 2];
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
 
   long long ta, tb;
   if (p.self) upper_triangle_tile(blockIdx.x, p.nta, &ta, &tb);
@@ -194,51 +182,17 @@ __global__ __launch_bounds__(FS_THREADS) void fleet_shift_mask_kernel(const Shif
     }
   }
 
-  // the bits of a pair sit in consecutive lanes: a ballot is the mask word
-  for (int s = 0, q = tid; q < n_items; ++s, q += FS_THREADS) {
-    const unsigned long long bal = __ballot((done >> s & 1u) != 0u);
-    if (p.ns_log2 >= 6) {
-      if (lane == 0) sMask[(q >> p.ns_log2) * 2 + ((q & (ns - 1)) >> 6)] = bal;
-    } else if ((lane & (ns - 1)) == 0) {
-      sMask[(q >> p.ns_log2) * 2] = (bal >> lane) & ((1ull << ns) - 1ull);
-    }
-  }
+  collect_item_bits(done, n_items, p.ns_log2, sMask);
   __syncthreads();
 
-  if (p.self) {
-    if (tid < FS_PAIRS) {
-      const int li = tid >> 3, lj = tid & 7;
-      const long long gi = a0 + li, gj = b0 + lj;
-      if (gi < p.ba && gj < p.bb) {
-        const unsigned long long lo = sMask[tid * 2], hi = sMask[tid * 2 + 1];
-        if (diagonal && li == lj) {
-          p.pair[(gi * p.bb + gj) * 2] = 0ull; p.pair[(gi * p.bb + gj) * 2 + 1] = 0ull;
-        } else if (!diagonal || li < lj) {   // the lower half of a diagonal tile is written by its mirror
-          unsigned long long rlo, rhi;
-          reverse_mask(lo, hi, p.max_delay, &rlo, &rhi);
-          p.pair[(gi * p.bb + gj) * 2] = lo; p.pair[(gi * p.bb + gj) * 2 + 1] = hi;
-          p.pair[(gj * p.bb + gi) * 2] = rlo; p.pair[(gj * p.bb + gi) * 2 + 1] = rhi;
-        }
-      }
-    }
-  } else if (tid < FS_TILE) {
-    const long long gi = a0 + tid;
-    if (gi < p.ba) {
-      unsigned long long m = 0ull;
-      for (int lj = 0; lj < FS_TILE; ++lj) m |= sMask[(tid * FS_TILE + lj) * 2];
-      p.part[gi * p.ntb + tb] = m;
-    }
-  }
+  if (p.self) store_pair_masks(sMask, diagonal, a0, b0, p.ba, p.max_delay, p.pair);
+  else store_obstacle_part(sMask, a0, p.ba, tb, p.ntb, p.part);
 }
 
 // base[i] <- the OR of robot i's obstacle partials (none: 0); 0 for a bad robot
 __global__ __launch_bounds__(FS_THREADS) void fleet_base_kernel(const unsigned long long* part, const int* bad, long long n, long long n_tiles,
                                                                  unsigned long long* base) {
-  const long long i = (long long)blockIdx.x * FS_THREADS + threadIdx.x;
-  if (i >= n) return;
-  unsigned long long m = 0ull;
-  for (long long t = 0; t < n_tiles; ++t) m |= part[i * n_tiles + t];
-  base[i] = bad[i] ? 0ull : m;
+  base_from_parts(part, bad, n, n_tiles, base);
 }
 
 struct AssignArgs {
@@ -300,8 +254,6 @@ __global__ __launch_bounds__(FS_ASSIGN_THREADS) void fleet_assign_kernel(const A
     }
 }
 
-static long long fs_tiles(long long n) { return (n + FS_TILE - 1) / FS_TILE; }
-static int fs_log2_ceil(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 static size_t fs_flag_bytes(long long m) { return (size_t)((m + 1) / 2 * 2) * sizeof(int); }
 
 }  // namespace nfopp

@@ -10,7 +10,7 @@ from .conflicts import (CONFLICT_BAD_TRACK, CONFLICT_COUNT, CONFLICT_FIRST_PARTN
                         CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_NO_PARTNER, CONFLICT_STATUS, BoxTrackConflicts,
                         TrackConflicts, box_track_conflicts, constant_velocity_tracks, track_conflicts, track_headings)
 from .schedule import (SCHEDULE_BAD_TRACK, SCHEDULE_MAX_DELAY, SCHEDULE_NOT_ORDERED, SCHEDULE_OK, SCHEDULE_UNRESOLVED, FleetMasks,
-                       FleetSchedule, delay_tracks, fleet_shift_masks, schedule_delays)
+                       FleetSchedule, delay_tracks, fleet_box_shift_masks, fleet_shift_masks, schedule_box_delays, schedule_delays)
 from .spacetime import (SPACETIME_BAD_CELL, SPACETIME_DIRECTIONS, SPACETIME_NOT_ORDERED, SPACETIME_OK, SPACETIME_UNREACHED,
                         SpaceTimePlan, SpaceTimeReservation, spacetime_plan)
 from .factory import DEFAULT_PARAMETERS, PlannerFactory, UniversalFactory
@@ -48,7 +48,7 @@ __all__ = [
     "TrackConflicts", "track_conflicts", "constant_velocity_tracks", "CONFLICT_MIN_GAP", "CONFLICT_MIN_PARTNER",
     "CONFLICT_MIN_TIME", "CONFLICT_FIRST_TIME", "CONFLICT_FIRST_PARTNER", "CONFLICT_COUNT", "CONFLICT_STATUS",
     "CONFLICT_BAD_TRACK", "CONFLICT_NO_PARTNER", "BoxTrackConflicts", "box_track_conflicts", "track_headings",
-    "FleetMasks", "FleetSchedule", "fleet_shift_masks", "schedule_delays", "delay_tracks", "SCHEDULE_OK", "SCHEDULE_BAD_TRACK",
+    "FleetMasks", "FleetSchedule", "fleet_shift_masks", "fleet_box_shift_masks", "schedule_delays", "schedule_box_delays", "delay_tracks", "SCHEDULE_OK", "SCHEDULE_BAD_TRACK",
     "SCHEDULE_UNRESOLVED", "SCHEDULE_NOT_ORDERED", "SCHEDULE_MAX_DELAY",
     "SpaceTimePlan", "SpaceTimeReservation", "spacetime_plan", "SPACETIME_OK", "SPACETIME_BAD_CELL", "SPACETIME_UNREACHED",
     "SPACETIME_NOT_ORDERED", "SPACETIME_DIRECTIONS",

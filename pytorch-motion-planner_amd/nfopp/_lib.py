@@ -223,6 +223,10 @@ _SIGNATURES = {
                                                ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P,
                                                ctypes.c_size_t, _P]),
     "nfopp_fleet_assign_delays": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P]),
+    "nfopp_fleet_box_shift_masks_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "nfopp_fleet_box_shift_masks": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_double,
+                                                   ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P,
+                                                   _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "nfopp_spacetime_reservation_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "nfopp_spacetime_reservation_init": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P]),
     "nfopp_spacetime_reserve_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),

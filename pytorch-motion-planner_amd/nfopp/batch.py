@@ -513,7 +513,8 @@ class BatchPlanner(object):
                                       other_v_max=obstacle_v_max, want_pairs=want_pairs, **shape)
 
     def fleet_schedule(self, limits, dt, count, radius, max_delay, margin="chord", order=None, best=False, obstacles=None,
-                       obstacle_radius=None, obstacle_v_max=None, v_start=None, v_goal=None, replan=None):
+                       obstacle_radius=None, obstacle_v_max=None, v_start=None, v_goal=None, box=None, refine=0, obstacle_box=None,
+                       obstacle_w_max=None, replan_radius=None, replan=None):
         """The B paths as B robots on one floor that may leave late: time-parametrise under `limits`, sample at k * dt
         (k < count) and give every robot, in priority `order` (None: robot 0 first; "longest_first"; or [B] indices), the
         smallest start delay of 0 .. max_delay grid steps that keeps it clear of the robots scheduled before it and of
@@ -523,11 +524,29 @@ class BatchPlanner(object):
         `replan`: an OccupancyGrid (inflated for the robot's footprint).  The robots the schedule could not place are then
         searched on it in space-time over count + max_delay instants (`FleetSchedule.replan`, with the snap added to the
         schedule's margin; `radius` must be one number); the schedule comes back with `plan` (an nfopp.SpaceTimePlan) and
-        `merged` [B, count + max_delay, 2].  Without it nothing changes."""
+        `merged` [B, count + max_delay, 2].  Without it nothing changes.
+
+        With `box` (x0, x1, y0, y1) the robots are oriented boxes (`TimedPaths.schedule_boxes`: `radius` rounds them, `refine`
+        halves undecided intervals, obstacles carry x, y, theta and take `obstacle_box` / `obstacle_w_max`), and the scheduled
+        fleet is FREE by `fleet_conflicts(box=, refine=)`.  The space-time search still reserves discs: with `box` and
+        `replan` it takes `replan_radius`, the radius of the disc it reserves for every robot (the box's circumscribed disc
+        plus its rounding radius is the safe choice); every obstacle is reserved as the disc that covers its box at every
+        heading, the farthest corner plus `obstacle_radius` (`nfopp.conflicts.box_disc_radius`)."""
         timed = self.timed_paths(limits, v_start=v_start, v_goal=v_goal, best=best)
-        sched = timed.schedule(dt, count, max_delay, radius, margin=margin, order=order, other=obstacles,
-                               other_radius=obstacle_radius, other_v_max=obstacle_v_max)
+        if box is None:
+            if refine != 0 or obstacle_box is not None or obstacle_w_max is not None or replan_radius is not None:
+                raise ValueError("refine, obstacle_box, obstacle_w_max and replan_radius belong to the box schedule: give box")
+            sched = timed.schedule(dt, count, max_delay, radius, margin=margin, order=order, other=obstacles,
+                                   other_radius=obstacle_radius, other_v_max=obstacle_v_max)
+        else:
+            if replan is not None and replan_radius is None:
+                raise ValueError("replan reserves discs: with box it needs replan_radius, the radius of the disc of a robot")
+            sched = timed.schedule_boxes(dt, count, max_delay, box, radius=radius, margin=margin, order=order, refine=refine,
+                                         other=obstacles, other_box=obstacle_box, other_radius=obstacle_radius,
+                                         other_v_max=obstacle_v_max, other_w_max=obstacle_w_max)
         if replan is not None:
+            if box is not None:
+                radius = replan_radius
             if isinstance(radius, torch.Tensor) or np.ndim(radius) != 0:
                 raise ValueError("replan plans a fleet of one robot radius: radius must be a number")
             sched.plan, sched.merged = sched.replan(sched.tracks, replan, int(count) + int(max_delay), robot_radius=radius,

@@ -190,6 +190,15 @@ def box_reach(box):
     return float(np.hypot(max(abs(x0), abs(x1)), max(abs(y0), abs(y1))))
 
 
+def box_disc_radius(box, radius, batch, device):
+    """[B] fp32 device tensor: the radius of the disc about the body origin that covers each rounded box at every heading --
+    the farthest corner, times 1.000001 as the box check's reach, plus the rounding radius -- for callers that reserve
+    discs (the space-time search).  `box`: one box or [B, 4]; `radius`: None, a number or [B].  Nothing is copied to the host."""
+    box = _per_row_boxes(box, batch, device, "box")
+    reach = torch.hypot(box[:, :2].abs().amax(1), box[:, 2:].abs().amax(1)) * 1.000001
+    return reach + per_row(0.0 if radius is None else radius, batch, device, "radius")
+
+
 def box_chord_margin(va_max, vb_max, dt, reach_a, wa_max, reach_b, wb_max):
     """`chord_margin` for boxes: a point at up to `reach` from the origin of a body that turns at up to w_max moves at up to
     v_max + reach * w_max, which adds reach * w_max * dt / 2 per side."""

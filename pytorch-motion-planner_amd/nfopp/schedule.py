@@ -85,10 +85,12 @@ class FleetMasks(object):
     """What `fleet_shift_masks` found.  Device tensors: `pair` [B, B, 2] int64 (the 128-bit mask of every pair as two
     little-endian words: bit r + max_delay says that robot i delayed by r grid steps more than robot j conflicts with it),
     `base` [B] int64 (bit d: robot i delayed by d conflicts with an obstacle), `bad` [B] int32.  `assign` may be called any
-    number of times, with other priority orders, without recomputing the masks."""
+    number of times, with other priority orders, without recomputing the masks.  `box` [B, 4] and `refine`: the boxes and
+    the refinement depth of `fleet_box_shift_masks` (a set bit then says "not FREE by the box check"); None and 0 for discs."""
 
-    def __init__(self, pair, base, bad, max_delay):
+    def __init__(self, pair, base, bad, max_delay, box=None, refine=0):
         self.pair, self.base, self.bad, self.max_delay = pair, base, bad, _check_max_delay(max_delay)
+        self.box, self.refine = box, refine
 
     def assign(self, order=None, want_forbidden=True):
         """order: None (robot 0 first), or [B] integers: the robots in priority order (an entry out of range or repeated is
@@ -142,6 +144,61 @@ def schedule_delays(tracks, *, max_delay, radius=0.0, margin=0.0, obstacles=None
     """`fleet_shift_masks` and `FleetMasks.assign` in one call -> `FleetSchedule`."""
     return fleet_shift_masks(tracks, max_delay=max_delay, radius=radius, margin=margin, obstacles=obstacles,
                              obstacle_radius=obstacle_radius).assign(order)
+
+
+def fleet_box_shift_masks(tracks, *, max_delay, box, radius=0.0, margin=0.0, refine=0, obstacles=None, obstacle_box=None,
+                          obstacle_radius=None):
+    """`fleet_shift_masks` for oriented boxes (csrc/fleet_box_schedule.hip).  tracks [B, K, >= 3]: fp32 HIP tensor of poses on
+    a common time grid, x, y, theta first in a row; `box`: one box (x0, x1, y0, y1) in the body frame or [B, 4]; `radius`: the
+    rounding radius, a number or [B]; `refine` (0 .. 8): how often an interval the certificate leaves undecided is halved.  A
+    bit is set when `box_track_conflicts` would not call the shifted pair FREE.  `obstacles` [M, K + max_delay, >= 3] with
+    `obstacle_box` (default: `box`, which must then be one box) and `obstacle_radius` -> `FleetMasks`."""
+    from .conflicts import _per_row_boxes, track_headings
+    max_delay = _check_max_delay(max_delay)
+    b, k, stride = check_tracks(tracks, "tracks")
+    if box is None:
+        raise ValueError("fleet_box_shift_masks needs box; discs go to fleet_shift_masks")
+    m, stride_o = 0, 3
+    if obstacles is not None:
+        m, ko, stride_o = check_tracks(obstacles, "obstacles")
+        if ko != k + max_delay:
+            raise ValueError("obstacles must cover K + max_delay = %d instants, got %d" % (k + max_delay, ko))
+    if tracks.shape[2] < 3 or (obstacles is not None and obstacles.shape[2] < 3):
+        raise ValueError("box tracks must be [B, K, >= 3] (x, y, theta)")
+    refine = int(refine)
+    if not 0 <= refine <= _lib.BOX_CONFLICT_MAX_REFINE:
+        raise ValueError("refine must be 0 .. %d, got %d" % (_lib.BOX_CONFLICT_MAX_REFINE, refine))
+    device = hip_device("fleet_box_shift_masks", "tracks", tracks, "obstacles", obstacles)
+    given_box, box = box, _per_row_boxes(box, b, device, "box")
+    radius = per_row(radius, b, device, "radius")
+    heading = track_headings(tracks)
+    obstacle_heading = None
+    if m:
+        if obstacle_box is None:
+            if int(np.prod(np.shape(given_box))) != 4:
+                raise ValueError("obstacles need obstacle_box when box is one per robot")
+            obstacle_box = given_box
+        obstacle_box = _per_row_boxes(obstacle_box, m, device, "obstacle_box")
+        obstacle_radius = per_row(0.0 if obstacle_radius is None else obstacle_radius, m, device, "obstacle_radius")
+        obstacle_heading = track_headings(obstacles)
+    lib = _lib.load()
+    pair = torch.empty(b, b, 2, dtype=torch.int64, device=device)
+    base = torch.empty(b, dtype=torch.int64, device=device)
+    bad = torch.empty(b, dtype=torch.int32, device=device)
+    ws = workspace(lib.nfopp_fleet_box_shift_masks_workspace_bytes(b, m, k, max_delay), device)
+    _lib.check(lib.nfopp_fleet_box_shift_masks(
+        raw_ptr(tracks), _lib.ptr(heading, torch.float64), b, stride, k, _lib.ptr(box), _lib.ptr(radius), float(margin), refine,
+        max_delay, raw_ptr(obstacles) if m else None, _lib.ptr(obstacle_heading, torch.float64), m, stride_o,
+        _lib.ptr(obstacle_box) if m else None, _lib.ptr(obstacle_radius) if m else None, _lib.ptr(pair, torch.int64),
+        _lib.ptr(base, torch.int64), _lib.ptr(bad, torch.int32), ws.ptr, ws.nbytes, _lib.stream_ptr()))
+    return FleetMasks(pair, base, bad, max_delay, box=box, refine=refine)
+
+
+def schedule_box_delays(tracks, *, max_delay, box, radius=0.0, margin=0.0, refine=0, obstacles=None, obstacle_box=None,
+                        obstacle_radius=None, order=None):
+    """`fleet_box_shift_masks` and `FleetMasks.assign` in one call -> `FleetSchedule`: `schedule_delays` for oriented boxes."""
+    return fleet_box_shift_masks(tracks, max_delay=max_delay, box=box, radius=radius, margin=margin, refine=refine, obstacles=obstacles,
+                                 obstacle_box=obstacle_box, obstacle_radius=obstacle_radius).assign(order)
 
 
 def delay_tracks(tracks, delay, count):

@@ -59,6 +59,19 @@ def _box_turn_margin(box, w_max, dt):
     return reach * float(w_max) * float(dt) / 2.0
 
 
+def _box_margin_or_number(margin, v_self, v_other, dt, box, w_self, other_box=None, w_other=None, one_for_both=False):
+    """`margin` of `TimedPaths.conflicts(box=)` / `.schedule_boxes`: a number as it is, "chord" -> the chord margin of the two
+    top speeds plus `_box_turn_margin` of the first side plus that of the second (`other_box` None: the paths against each
+    other, the second side is the first).  `one_for_both`: one margin for robot pairs and obstacle pairs alike, so the second
+    term is the larger of the two sides'."""
+    if not isinstance(margin, str):
+        return margin
+    chord = _chord_margin_or_number(margin, v_self, v_other, dt)
+    own = _box_turn_margin(box, w_self, dt)
+    far = own if other_box is None else _box_turn_margin(other_box, w_other, dt)
+    return chord + own + (max(own, far) if one_for_both else far)
+
+
 def _check_paths(traj, start, goal):
     """traj [B, N, D] with N >= 1 and D = 2 or 3, start / goal [B, D]: what the kernels index by."""
     if not all(isinstance(x, torch.Tensor) for x in (traj, start, goal)):
@@ -135,9 +148,7 @@ class TimedPaths(object):
             raise ValueError("the box check needs SE(2) paths (x, y, theta)")
         if other is not None and other_box is None:
             other_box = box
-        if isinstance(margin, str):
-            margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt) + _box_turn_margin(box, self.limits.w_max, dt) + \
-                _box_turn_margin(box if other is None else other_box, wb, dt)
+        margin = _box_margin_or_number(margin, self.limits.v_max, vb, dt, box, self.limits.w_max, other_box, wb)
         if other is None:
             return box_track_conflicts(self.sample(dt, count, t0=t0), dt=dt, t0=t0, box_a=box, radius_a=radius, margin=margin,
                                        refine=refine, want_pairs=want_pairs)
@@ -154,27 +165,64 @@ class TimedPaths(object):
         obstacles in absolute time.  `margin="chord"` is (v_max + the larger of v_max and the other side's v_max) * dt / 2:
         one margin serves robot pairs and obstacle pairs alike; for a tracks tensor it needs `other_v_max`.  A robot is
         `complete` when its total time fits the sampled instants, so that its last sample is its goal."""
-        from .schedule import fleet_shift_masks
+        return self._schedule(dt, count, max_delay, radius, margin, order, other, other_radius, other_v_max)
+
+    def schedule_boxes(self, dt, count, max_delay, box, radius=0.0, margin="chord", order=None, refine=0, other=None,
+                       other_box=None, other_radius=None, other_v_max=None, other_w_max=None):
+        """`schedule` for oriented boxes on SE(2) paths (`nfopp.fleet_box_shift_masks`): a delay is taken from a robot when
+        `conflicts(box=, refine=)` would not call the delayed pair FREE, so the scheduled fleet is FREE by that check.  `box`:
+        (x0, x1, y0, y1) in the body frame, or one per path; `radius` the rounding radius; `other` a `TimedPaths` or a tracks
+        tensor [M, count + max_delay, >= 3] with x, y, theta, `other_box` its boxes (default: `box`, which must then be one
+        box).  `margin="chord"` is the box chord margin as `conflicts(box=)` forms it, the larger of the robot-robot and the
+        robot-obstacle value: (v_max + the larger top speed) * dt / 2 plus reach * w_max * dt / 2 of the robots' side plus the
+        larger such term of the two sides (`other_w_max` for a tracks tensor)."""
+        if box is None:
+            raise ValueError("schedule_boxes needs box; discs go to schedule")
+        if self.traj.shape[2] != 3:
+            raise ValueError("the box schedule needs SE(2) paths (x, y, theta)")
+        return self._schedule(dt, count, max_delay, radius, margin, order, other, other_radius, other_v_max,
+                              shape=dict(box=box, refine=refine, other_box=other_box, other_w_max=other_w_max))
+
+    def _schedule(self, dt, count, max_delay, radius, margin, order, other, other_radius, other_v_max, shape=None):
+        from .schedule import fleet_box_shift_masks, fleet_shift_masks
         count, max_delay = int(count), int(max_delay)
-        obstacles, vb = None, self.limits.v_max
+        obstacles, vb, wb = None, self.limits.v_max, None
         if isinstance(other, TimedPaths):
-            obstacles, vb = other.sample(dt, count + max_delay), max(vb, other.limits.v_max)
+            obstacles, vb, wb = other.sample(dt, count + max_delay), max(vb, other.limits.v_max), other.limits.w_max
         elif other is not None:
             obstacles, vb = other, None if other_v_max is None else max(vb, float(other_v_max))
-        margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt)
+            wb = None if shape is None else shape["other_w_max"]
+        other_box = None
+        if shape is None:
+            margin = _chord_margin_or_number(margin, self.limits.v_max, vb, dt)
+        else:
+            if other is not None:
+                other_box = shape["box"] if shape["other_box"] is None else shape["other_box"]
+            margin = _box_margin_or_number(margin, self.limits.v_max, vb, dt, shape["box"], self.limits.w_max, other_box, wb,
+                                           one_for_both=True)
         total = self.summary[:, TIME_SUMMARY_TIME]
         if isinstance(order, str):
             if order != "longest_first":
                 raise ValueError("order must be None, \"longest_first\" or [B] indices, got %r" % (order,))
             order = torch.argsort(total, descending=True, stable=True)
         states = self.sample(dt, count)
-        masks = fleet_shift_masks(states, max_delay=max_delay, radius=radius, margin=margin, obstacles=obstacles,
-                                  obstacle_radius=other_radius)
+        if shape is None:
+            masks = fleet_shift_masks(states, max_delay=max_delay, radius=radius, margin=margin, obstacles=obstacles,
+                                      obstacle_radius=other_radius)
+        else:
+            masks = fleet_box_shift_masks(states, max_delay=max_delay, box=shape["box"], radius=radius, margin=margin,
+                                          refine=shape["refine"], obstacles=obstacles, obstacle_box=other_box,
+                                          obstacle_radius=other_radius)
+            if obstacles is not None:
+                # FleetSchedule.replan reserves discs: an obstacle box as its circumscribed disc plus its rounding radius
+                from .conflicts import box_disc_radius
+                other_radius = box_disc_radius(other_box, other_radius, obstacles.shape[0], obstacles.device)
         out = masks.assign(order)
         step = torch.tensor(float(dt), dtype=torch.float64, device=out.delay.device)
         out.delay_seconds = torch.where(out.delay >= 0, out.delay.double() * step, torch.full_like(step, float("nan")))
         out.complete = total <= (count - 1) * float(dt)
-        # what FleetSchedule.replan goes on from: the sampled tracks, the margin as a number, the obstacles as sampled
+        # what FleetSchedule.replan goes on from: the sampled tracks, the margin as a number, the obstacles as sampled (box
+        # obstacles with the radius of the disc that covers them)
         out.tracks, out.margin, out.obstacles, out.obstacle_radius = states, margin, obstacles, other_radius
         return out
 
