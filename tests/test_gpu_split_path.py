@@ -17,6 +17,8 @@ import nfopp  # noqa: E402
 from nfopp import _lib  # noqa: E402
 from oracle import nfopp_oracle as orc  # noqa: E402
 
+from float64_ref import onf_forward64 as _forward64  # noqa: E402
+
 F32 = np.float32
 
 
@@ -41,25 +43,6 @@ def _eval(onf, x, path):
         return out.cpu().numpy(), logits.cpu().numpy().reshape(-1)
     finally:
         _lib.check(lib.nfopp_set_matrix_path(before))
-
-
-def _forward64(params, cfg, x):
-    """float64 evaluation of the same network (weights are the fp32 parameters): the yardstick for both paths"""
-    p = orc.unpack_params(np.asarray(params, F32), cfg)
-    p = {k: (np.asarray(v, np.float64) if v is not None else None) for k, v in p.items()}
-    x = np.asarray(x, np.float64)
-    u = (x[:, :2] - cfg.mean) / cfg.sigma
-    e = u @ p["we"].T + (p["be"] if p["be"] is not None else 0.0)
-    feats = [np.sin(e[:, :100])]
-    if cfg.use_cos:
-        feats.append(np.cos(e[:, 100:]))
-    if cfg.angle_encoding:
-        z = (x[:, 2:3] + p["ang_b"][None]) * p["ang_f"][None]
-        feats += [np.sin(z[:, :cfg.angle_dim]), np.cos(z[:, cfg.angle_dim:])]
-    fin = np.concatenate(feats, 1)
-    h1 = np.maximum(fin @ p["w1"].T + p["b1"], 0)
-    h2 = np.maximum(h1 @ p["w2"].T + p["b2"], 0)
-    return np.concatenate([h2, fin], 1) @ p["w3"].reshape(-1) + p["b3"].reshape(-1)[0]
 
 
 @pytest.mark.parametrize("tag", ["a", "b", "c"])
