@@ -83,28 +83,48 @@ def onf_forward64(params, cfg, x):
     return onf_eval64(params, cfg, x)["logit"]
 
 
-def onf_fit64(params, cfg, x, labels):
+def fit_sums64(c, cfg, rho, rows=None, mag=False):
+    """The summed parameter gradient of the fit from the per-sample values `c` of onf_eval64 and the upstream rho [P] -> flat
+    gradient in cfg.layout() order.
+      rows   the samples that are summed (default: all): the contribution of those samples alone
+      mag    every factor of every product replaced by its absolute value (|dh1|^T |in|, sum |rho|, ...): the magnitude that
+             the rounding error of an fp32 evaluation of the same sums scales with, whatever cancels in the sums themselves"""
+    p = c["p"]
+    f = np.abs if mag else (lambda a: a)
+    sel = slice(None) if rows is None else rows
+    rho = np.asarray(rho, F64)[sel]
+    r = rho[:, None]
+    h1, h2, inp, u = (f(c[k][sel]) for k in ("h1", "h2", "inp", "u"))
+    dh2, dh1, de = f(r * c["dh2"][sel]), f(r * c["dh1"][sel]), r * c["darg"][sel]
+    den = f(de[:, :cfg.n_enc])
+    rho = f(rho)
+    g = dict(w3=rho @ np.concatenate([h2, inp], 1), b3=rho.sum(keepdims=True), w2=dh2.T @ h1, b2=dh2.sum(0),
+             w1=dh1.T @ inp, b1=dh1.sum(0), we=den.T @ u, be=den.sum(0))
+    if cfg.angle_encoding:
+        dz = f(de[:, cfg.n_enc:])
+        g["ang_b"] = (dz * f(p["ang_f"])[None]).sum(0)
+        g["ang_f"] = (dz * f(c["x"][sel, 2:3] + p["ang_b"][None])).sum(0)
+    return np.concatenate([np.asarray(g[name]).reshape(-1) for name, _ in cfg.layout()])
+
+
+def onf_fit64(params, cfg, x, labels, keep_eval=False):
     """The fit's step on P samples (mean BCE with logits) -> dict:
       loss, rho [P] = (sigmoid(logit) - y) / P, the pass-1 factors h1 [P, 100], rho_dh1 [P, 100], rho_de [P, feature_dim],
-      grad = the flat parameter gradient in cfg.layout() order, and kink / a2 / u of onf_eval64."""
+      grad = the flat parameter gradient in cfg.layout() order, and kink / a2 / u of onf_eval64.
+    keep_eval: also `eval` = the dict of onf_eval64 and `loss_p` [P], the per-sample losses (what fit_sums64 takes)."""
     c = onf_eval64(params, cfg, x)
-    p, x = c["p"], c["x"]
     y = np.asarray(labels, F64)
     P = len(y)
     logit = c["logit"]
-    loss = np.mean(np.maximum(logit, 0) - logit * y + np.log1p(np.exp(-np.abs(logit))))
+    loss_p = np.maximum(logit, 0) - logit * y + np.log1p(np.exp(-np.abs(logit)))
+    loss = np.mean(loss_p)
     rho = (1.0 / (1.0 + np.exp(-logit)) - y) / P
     r = rho[:, None]
-    dh2, dh1, de = r * c["dh2"], r * c["dh1"], r * c["darg"]
-    g = dict(w3=rho @ np.concatenate([c["h2"], c["inp"]], 1), b3=rho.sum(keepdims=True), w2=dh2.T @ c["h1"], b2=dh2.sum(0),
-             w1=dh1.T @ c["inp"], b1=dh1.sum(0), we=de[:, :cfg.n_enc].T @ c["u"], be=de[:, :cfg.n_enc].sum(0))
-    if cfg.angle_encoding:
-        dz = de[:, cfg.n_enc:]
-        g["ang_b"] = (dz * p["ang_f"][None]).sum(0)
-        g["ang_f"] = (dz * (x[:, 2:3] + p["ang_b"][None])).sum(0)
-    grad = np.concatenate([np.asarray(g[name]).reshape(-1) for name, _ in cfg.layout()])
-    return dict(loss=loss, rho=rho, h1=c["h1"], rho_dh1=dh1, rho_de=de, grad=grad, kink=c["kink"], a2=c["a2"], u=c["u"],
-                logit=logit)
+    out = dict(loss=loss, rho=rho, h1=c["h1"], rho_dh1=r * c["dh1"], rho_de=r * c["darg"], grad=fit_sums64(c, cfg, rho),
+               kink=c["kink"], a2=c["a2"], u=c["u"], logit=logit)
+    if keep_eval:
+        out.update(eval=c, loss_p=loss_p)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------
