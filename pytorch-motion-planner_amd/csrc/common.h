@@ -269,16 +269,22 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
 
-// Hardware path: exact Cody-Waite reduction of x + qh*pi modulo 2 pi (fma with a hi/lo split of 2 pi), then
-// v_sin_f32 on the remainder expressed in revolutions (|f| <= 0.5).  Measured on gfx950 (tools/micro/
-// vsin_accuracy.hip): max |v_sin_f32(f) - sin(2 pi f)| = 1.25e-7; with the 3e-8-revolution rounding of f the
-// feature error stays <= 3e-7 absolute for any |x| < 1e5, at 5 VALU + 1 transcendental op instead of 15 VALU.
+// Hardware path: Cody-Waite reduction of x modulo 2 pi (fma with a hi/lo split of 2 pi), then v_sin_f32 on the remainder
+// expressed in revolutions plus the offset qq: |r / 2 pi| <= 0.5006, so |f| reaches 0.5006 / 0.7506 / 1.0006 for qq = 0 /
+// 0.25 / 0.5 (a sine kind, a cosine kind or the derivative of a sine kind, the derivative of a cosine kind).  5 VALU + 1
+// transcendental op instead of 15 VALU.  Absolute error for any |x| < 1e5 (profiles/feature_probe.txt,
+// tests/test_gpu_feature_probe.py), per offset 0 / 0.25 / 0.5:
+//   the chain alone (an exact sine in v_sin_f32's place)   4.3e-7 / 3.5e-7 / 6.2e-7: the fp32 rounding of f, whose spacing
+//                                                          is 6e-8 revolutions = 3.7e-7 rad from |f| = 0.5 on
+//   on gfx950, worst over the feature probes               3.2e-7 / 3.3e-7 / 3.6e-7
+// v_sin_f32 itself: max |v_sin_f32(f) - sin(2 pi f)| = 1.25e-7 on the 4 M-point grid of tools/micro/vsin_accuracy.hip; the
+// probes see up to 1.35e-7 between the device and the chain with an exact sine.
 __device__ __forceinline__ float sin_halfturns_hw(float x, float qq) {  // qq = offset in REVOLUTIONS (q/4)
   const float jm = fmaf(x, 0.159154943f, 12582912.0f);  // 1.5*2^23 + x/2pi: the add rounds to the nearest turn
   const float j = jm - 12582912.0f;                      // whole turns, exact
   float r = fmaf(j, -6.28318548202514648f, x);           // x - j * 2pi  in [-pi, pi] (product exact in the fma)
   r = fmaf(j, 1.74845553e-07f, r);
-  return __builtin_amdgcn_sinf(fmaf(r, 0.159154943f, qq));  // |revolutions| <= 0.75
+  return __builtin_amdgcn_sinf(fmaf(r, 0.159154943f, qq));  // |revolutions| <= 1.0006 (qq = 0.5)
 }
 
 // sin_halfturns2(x, q * NFOPP_Q_UNIT) = sin(x + q*pi/2): the quadrant offset is pre-scaled to revolutions, the unit

@@ -293,25 +293,12 @@ def test_initializer_and_checkers_vs_golden():
 
 
 def test_device_trig_and_philox_restatements():
-    """fp32 emulation of csrc/common.h sin_quadrant (the only transcendental on the MFMA path) against float64."""
+    """fp32 emulation of csrc/common.h sin_quadrant against float64: the polynomial sine of the per-sample fit kernels
+    (csrc/onf_train.hip).  The MFMA paths evaluate their features with the hardware chain sin_halfturns_hw (a two-constant
+    2 pi reduction, one fma into revolutions, v_sin_f32), which tests/test_gpu_feature_probe.py holds to float64 on the device;
+    both emulations live in tests/feature_probe_gate.py."""
+    from feature_probe_gate import sin_quadrant
     F = np.float32
-
-    def fma(a, b, c):
-        return (np.float64(a) * np.float64(b) + np.float64(c)).astype(F)
-
-    def sin_quadrant(x, q):
-        j = np.rint((x * F(0.636619772)).astype(F)).astype(F)
-        r = fma(j, F(-1.57079601e+00), x)
-        r = fma(j, F(-3.13916473e-07), r)
-        r = fma(j, F(-5.39030253e-15), r)
-        n = j.astype(np.int64) + q
-        s = (r * r).astype(F)
-        ps = fma(fma(fma(np.full_like(x, F(2.86567956e-6)), s, F(-1.98559923e-4)), s, F(8.33338592e-3)), s, F(-1.66666672e-1))
-        sv = fma(ps, (r * s).astype(F), r)
-        pc = fma(fma(fma(np.full_like(x, F(2.44677067e-5)), s, F(-1.38877297e-3)), s, F(4.16666567e-2)), s, F(-0.5))
-        cv = fma(pc, s, F(1))
-        res = np.where(n & 1, cv, sv)
-        return np.where(n & 2, -res, res).astype(F)
 
     x = np.random.default_rng(0).uniform(-400, 400, 200000).astype(F)
     for q, fn in ((0, np.sin), (1, np.cos), (2, lambda v: -np.sin(v)), (3, lambda v: -np.cos(v))):
