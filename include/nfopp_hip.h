@@ -258,6 +258,57 @@ int nfopp_traj_steps_sdf(const nfopp_sdf_field* field, const nfopp_traj_hyper* h
                          const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev, float* terms_dev,
                          void* stream);
 
+/* The heading-layered distance field (csrc/heading_field.hip): a third producer of the [.., 4] rows, for a robot
+ * of any shape on an occupancy grid.  Slice k of the image is the signed distance of the occupancy the robot's footprint
+ * leaves at the heading k * 2 pi / layers (nfopp.HeadingDistanceField.from_checker): how far the centre may move at that
+ * heading before the checker says "collision".  A sample is one trilinear tap of the image; no sine or cosine is taken.
+ *   sd_dev [layers, rows, cols]; the centre of cell (j, i) lies where nfopp_sdf_field puts it.
+ *   All in fp32, every operation rounded on its own (no fused multiply-add); floorf and fmodf are exact:
+ *     u, in_x, i, fu and v, in_y, j, fv from (x, y) itself as in nfopp_sdf_field
+ *     w = theta layers_per_rad;  kf = floorf(w);  fw = w - kf
+ *     r = fmodf(kf, (float)layers) (|r| < layers);  k0 = (int)r, plus layers if negative;  k1 = k0 + 1, or 0 when that is layers
+ *     per slice l in {k0, k1}, s.. its four taps at (j, i):
+ *       a = s01 - s00;  b = s11 - s10;  top = s00 + fu a;  bot = s10 + fu b
+ *       d_l = top + fv (bot - top);  gx_l = (a + fv (b - a)) inv_res;  gy_l = (bot - top) inv_res
+ *     d = d0 + fw (d1 - d0);  gx = in_x ? gx0 + fw (gx1 - gx0) : 0;  gy = in_y ? gy0 + fw (gy1 - gy0) : 0
+ *     gth = (d1 - d0) layers_per_rad;  pen = margin - d
+ *   The row is  gain pen,  gain (-gx),  gain (-gy),  gain (-gth).
+ *   A pose outside the image sees the clamped border value, with a zero gradient component along each clamped axis.  A pose
+ *   with a non-finite component, or with a heading so large that w is not finite, gives four NaNs and reads nothing of sd_dev.
+ *   Between two slices the distance is interpolated: a long robot at a heading between them is judged by its neighbours
+ *   (choose layers and margin for the robot's length). */
+typedef struct nfopp_heading_field {
+  const float* sd_dev;        /* [layers, rows, cols]: signed distance in metres of heading slice k = heading k * 2 pi / layers,
+                                 free positive, blocked negative, every value finite */
+  int32_t layers, rows, cols; /* layers 2..64, rows >= 2, cols >= 2; layers * rows * cols < 2^31 */
+  float x0, y0, inv_res;      /* as nfopp_sdf_field */
+  float layers_per_rad;       /* float(layers / (2 pi)): formed in double, rounded once */
+  float margin, gain;         /* metres, logit per metre */
+} nfopp_heading_field;
+
+/* The row above at explicit poses.
+ *   points_dev [P, 3] (x, y, theta): a robot without a heading is nfopp_sdf_field's case
+ *   out4_dev   [P, 4], 16-byte aligned: all 4 P floats are written and nothing else
+ * Added within ABI 6 (no existing entry changed), as are the two entries below.  All three refuse, before any launch and
+ * without writing anything: a null field or image, layers outside 2..64, rows or cols below 2, an image beyond a 32-bit index,
+ * a non-finite x0, y0, inv_res, layers_per_rad, margin or gain, null pointers with a positive count, an unaligned out4_dev,
+ * t_mode outside {0, 1}, fewer than 2 waypoints and counts beyond one launch. */
+int nfopp_hdf_eval_points(const nfopp_heading_field* field, const float* points_dev, int64_t n, float* out4_dev, void* stream);
+
+/* The row above at the collision samples of a batch of SE(2) trajectories: nfopp_traj_sdf_collision_eval with the layered
+ * field in the disc field's place.  Sample, draw, Philox counter, t_mode, active_dev and traj_index_offset are that entry's
+ * (one device function forms the sample for all collision models).
+ *   traj_dev [B, N, 3];  t_dev [B, N-1];  out4_dev [B, N-1, 4], 16-byte aligned;  active_dev [B] uint8 or NULL */
+int nfopp_traj_hdf_collision_eval(const nfopp_heading_field* field, const float* traj_dev, int64_t batch, int32_t n_waypoints,
+                                  float* t_dev, int32_t t_mode, uint64_t seed, uint64_t rng_offset, int64_t traj_index_offset,
+                                  float* out4_dev, const uint8_t* active_dev, void* stream);
+
+/* nfopp_traj_steps with nfopp_traj_hdf_collision_eval as each step's first launch (the one loop serves all three entries): n_steps
+ * here equal n_steps single-step sequences bit for bit.  buf->dim must be 3; buf->live_ws_dev is not used. */
+int nfopp_traj_steps_hdf(const nfopp_heading_field* field, const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf,
+                         const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev, float* terms_dev,
+                         void* stream);
+
 /* ONF fitting step, gradient part: BCE-with-logits (mean over ALL samples of the job) and its gradient w.r.t.
  * every parameter incl. the angle frequencies (nfop/nerf_opt_planner.py:83-89).
  *   samples_dev [P, point_dim], labels_dev [P] (0/1), inv_count = 1 / (global sample count)

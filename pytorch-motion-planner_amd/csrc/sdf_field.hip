@@ -13,6 +13,8 @@
 
 #pragma clang fp contract(off)
 
+#include "sdf_axis.h"
+
 namespace nfopp {
 
 struct SdfArgs {
@@ -29,18 +31,6 @@ struct SdfArgs {
   long long n;               // samples: points, or B * (N - 1)
   float* out4;               // [n, 4], 16-byte aligned
 };
-
-// u -> (cell, fraction, strictly inside) on an axis of `count` cell centres.  NaN-safe: the two selects send a NaN to 0,
-// so the cell is in [0, count - 2] for every input.
-__device__ __forceinline__ void sdf_axis(float u, int count, int& cell, float& frac, bool& inside) {
-  const float last = (float)(count - 1);
-  inside = u > 0.0f && u < last;
-  float c = u > 0.0f ? u : 0.0f;
-  c = c < last ? c : last;
-  int i = (int)floorf(c);
-  cell = i < count - 2 ? i : count - 2;
-  frac = c - (float)cell;
-}
 
 // One pose -> the row (logit, dlogit/dx, dlogit/dy, dlogit/dtheta).  `dim` 2: no heading, dlogit/dtheta = 0.
 __device__ __forceinline__ float4 sdf_eval_pose(const nfopp_sdf_field& f, int dim, bool any_offset, float x, float y,

@@ -7,7 +7,8 @@
 // keeps the loop on the C side of the boundary: per step it forms the Adam scalars exactly as torch.optim.Adam does
 // (Python / C doubles: 1 - beta^k through pow(), lr / bc1, sqrt(bc2), rounded to fp32 once) and enqueues
 //   nfopp_traj_collision_eval -> nfopp_traj_update -> [nfopp_reparametrize when step_count % reparam_freq == 0]
-// (nfopp_traj_steps_sdf: nfopp_traj_sdf_collision_eval in the first place)
+// (nfopp_traj_steps_sdf: nfopp_traj_sdf_collision_eval in the first place; nfopp_traj_steps_hdf:
+// nfopp_traj_hdf_collision_eval)
 // on the caller's stream -- the same three entry points, the same kernels, the same arguments as n single calls, so
 // the results are bit-identical to n calls of the single-step sequence (tests/test_gpu_multistep.py).  Nothing
 // synchronises; the field must not change during the n steps (the reference's step with ONF learning needs the host
@@ -18,7 +19,7 @@
 
 using namespace nfopp;
 
-// The step loop both collision models share: `collision(t_k, k)` enqueues the model's collision entry for step k.
+// The step loop all collision models share: `collision(t_k, k)` enqueues the model's collision entry for step k.
 template <class Collision>
 static int run_steps(const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf, const nfopp_step_schedule* sched,
                      int32_t n_steps, const float* t_steps_dev, float* terms_dev, void* stream, Collision collision) {
@@ -76,5 +77,18 @@ extern "C" int nfopp_traj_steps_sdf(const nfopp_sdf_field* field, const nfopp_tr
     return nfopp_traj_sdf_collision_eval(field, buf->traj_dev, buf->batch, buf->n_waypoints, buf->dim, t_k, sched->t_mode,
                                          sched->seed, sched->rng_offset + (uint64_t)k, sched->traj_index_offset,
                                          buf->onf_out4_dev, buf->active_dev, stream);
+  });
+}
+
+// The same loop on a heading-layered distance field (csrc/heading_field.hip): SE(2) poses only.
+extern "C" int nfopp_traj_steps_hdf(const nfopp_heading_field* field, const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf,
+                                    const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev,
+                                    float* terms_dev, void* stream) {
+  NFOPP_REQUIRE(field && hp && buf && sched, "null argument");
+  NFOPP_REQUIRE(buf->dim == 3, "a heading field takes poses of 3 components, not %d", buf->dim);
+  return run_steps(hp, buf, sched, n_steps, t_steps_dev, terms_dev, stream, [&](float* t_k, int32_t k) {
+    return nfopp_traj_hdf_collision_eval(field, buf->traj_dev, buf->batch, buf->n_waypoints, t_k, sched->t_mode, sched->seed,
+                                         sched->rng_offset + (uint64_t)k, sched->traj_index_offset, buf->onf_out4_dev,
+                                         buf->active_dev, stream);
   });
 }

@@ -27,6 +27,15 @@ def cell_centres(boundaries, resolution):
     return x, y, x_cells, y_cells
 
 
+def heading_poses(x, y, n_headings):
+    """The poses a checker is asked at for `n_headings` footprint layers: float32 [n_headings * cells, 3], (cell centre,
+    float32(h * 2 pi / n_headings)) for h = 0 .. n_headings - 1, heading slowest (LatticeGrid.from_checker,
+    HeadingDistanceField.from_checker)."""
+    xy = np.stack([x, y], 1).astype(np.float32)
+    return np.concatenate([np.concatenate([xy, np.full((len(xy), 1), np.float32(h * (2 * np.pi) / n_headings), np.float32)], 1)
+                           for h in range(n_headings)], 0)
+
+
 class GridFrame(object):
     """`boundaries` (x0, x1, y0, y1) and `resolution` of the reference's raster: cell of a point = int((x - b0) // resolution),
     cell centre = j * resolution + resolution / 2 + b0 (csrc/grid_frame.h on the device).  OccupancyGrid and LatticeGrid are

@@ -76,6 +76,13 @@ class SdfFieldC(ctypes.Structure):
                 ("disc", (ctypes.c_float * 3) * 8), ("margin", ctypes.c_float), ("gain", ctypes.c_float)]
 
 
+class HeadingFieldC(ctypes.Structure):
+    """nfopp_heading_field: the layered distance image, its frame, layers / (2 pi), margin and gain (nfopp/heading_field.py)."""
+    _fields_ = [("sd_dev", _P), ("layers", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
+                ("x0", ctypes.c_float), ("y0", ctypes.c_float), ("inv_res", ctypes.c_float), ("layers_per_rad", ctypes.c_float),
+                ("margin", ctypes.c_float), ("gain", ctypes.c_float)]
+
+
 _SIGNATURES = {
     "nfopp_abi_version": (ctypes.c_int, []),
     "nfopp_last_error": (ctypes.c_char_p, []),
@@ -97,6 +104,13 @@ _SIGNATURES = {
                                                      ctypes.c_int64, _P, _P, _P]),
     "nfopp_traj_steps_sdf": (ctypes.c_int, [ctypes.POINTER(SdfFieldC), ctypes.POINTER(TrajHyperC), ctypes.POINTER(TrajBuffersC),
                                             ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P, _P]),
+    "nfopp_hdf_eval_points": (ctypes.c_int, [ctypes.POINTER(HeadingFieldC), _P, ctypes.c_int64, _P, _P]),
+    "nfopp_traj_hdf_collision_eval": (ctypes.c_int, [ctypes.POINTER(HeadingFieldC), _P, ctypes.c_int64, ctypes.c_int32, _P,
+                                                     ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, _P, _P,
+                                                     _P]),
+    "nfopp_traj_steps_hdf": (ctypes.c_int, [ctypes.POINTER(HeadingFieldC), ctypes.POINTER(TrajHyperC),
+                                            ctypes.POINTER(TrajBuffersC), ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P,
+                                            _P]),
     "nfopp_reparametrize": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nfopp_update_endpoints": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P,
                                               _P, _P, _P, _P, _P]),

@@ -14,8 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .distance_field import DistanceField
-from .engine import TrajectoryEngine
+from .engine import TrajectoryEngine, field_model
 from .grid_search import AstarTrajectoryInitializer, OccupancyGrid, grid_search_init
 from .lattice import GearLattice, LatticeGrid, lattice_gear_search_init, lattice_search_init
 from .path_tools import init_trajectories
@@ -140,19 +139,19 @@ class BatchPlanner(object):
     the parameters behind torch's back while a planner exists -- `dist.broadcast(onf.flat_parameters, 0)`, `.data`
     assignments -- must call `onf.mark_modified()` afterwards (or construct with `freeze_field=False`).
 
-    `onf` may be a `DistanceField` instead: the collision term then comes from the signed distance image of an occupancy
-    grid (csrc/sdf_field.hip) and everything else -- init, step(n), replan, evaluate, path_stats, the seeders -- is as it
-    is behind the network.  `freeze_field` does not apply and `checker=` raises ValueError: there is nothing to fit."""
+    `onf` may be a `DistanceField` or a `HeadingDistanceField` instead: the collision term then comes from the signed distance
+    image of an occupancy grid (csrc/sdf_field.hip, csrc/heading_field.hip) and everything else -- init, step(n), replan,
+    evaluate, path_stats, the seeders -- is as it is behind the network.  `freeze_field` does not apply and `checker=` raises ValueError: there is nothing to fit."""
 
     def __init__(self, onf, batch, n_waypoints, hyper, velocity_hessian_weight=0.5, reparametrize_trajectory_freq=10,
                  device="cuda", seed=0, traj_index_offset=0, checker=None, fit_lr=2e-2, fit_betas=(0.9, 0.9),
                  optimize_collision_model_freq=1, trajectory_random_offset=0.02, course_random_offset=1.5,
                  angle_offset=0.0, random_field_points=10, collision_point_count=100, group=None,
                  init_angles_with_trajectory=False, global_batch=None, freeze_field=True):
-        if isinstance(onf, DistanceField):
-            # the field is a nfopp.DistanceField (DESIGN.md 24): the map is the model, there is nothing to freeze or to fit
+        if field_model(onf):
+            # a distance field (engine.FIELD_MODELS; DESIGN.md 24, 26): the map is the model, there is nothing to freeze or to fit
             if checker is not None:
-                raise ValueError("a DistanceField is not fitted: checker= goes with an ONF (pass the checker to evaluate())")
+                raise ValueError("a distance field is not fitted: checker= goes with an ONF (pass the checker to evaluate())")
         elif freeze_field:
             onf.freeze()
         self.init_angles_with_trajectory = bool(init_angles_with_trajectory)

@@ -15,6 +15,23 @@ import torch
 
 from . import _lib
 from .distance_field import DistanceField
+from .heading_field import HeadingDistanceField
+
+# The collision models that are not an ONF: class -> (collision entry, step-loop entry, whether the collision entry takes the
+# pose dimension).  Both take the model's config_c() block first and no parameters or live-list workspace; the rest of their
+# arguments are those of nfopp_traj_sdf_collision_eval / nfopp_traj_steps_sdf.  A further model is one line here.
+FIELD_MODELS = {
+    DistanceField: ("nfopp_traj_sdf_collision_eval", "nfopp_traj_steps_sdf", True),
+    HeadingDistanceField: ("nfopp_traj_hdf_collision_eval", "nfopp_traj_steps_hdf", False),
+}
+
+
+def field_model(model):
+    """-> the FIELD_MODELS entry of a collision model, None for an ONF."""
+    for cls, entries in FIELD_MODELS.items():
+        if isinstance(model, cls):
+            return entries
+    return None
 
 
 def inverse_hessian(n, weight):
@@ -138,12 +155,13 @@ class TrajectoryHyper(object):
 class TrajectoryEngine(object):
     """Owns the batched state and runs the step pipeline.  `traj` may be an externally owned [B,N,D] (or [N,D])
     HIP tensor (the planner's `_trajectory`); it is updated in place.  `onf` is the collision model: an ONF, or a
-    `DistanceField`, whose rows come from nfopp_traj_sdf_collision_eval / nfopp_traj_steps_sdf."""
+    `DistanceField` or `HeadingDistanceField`, whose rows come from their own entries (FIELD_MODELS)."""
 
     def __init__(self, onf, batch, n_waypoints, dim, hyper, velocity_hessian_weight, device, traj=None, seed=0,
                  traj_index_offset=0):
         _lib.require_gpu()
         self.onf, self.hyper = onf, hyper
+        self._field_model = field_model(onf)
         self.B, self.N, self.D = int(batch), int(n_waypoints), int(dim)
         if self.D != onf.point_dim:
             raise ValueError("trajectory dim %d does not match the ONF point dim %d" % (self.D, onf.point_dim))
@@ -201,11 +219,12 @@ class TrajectoryEngine(object):
         else:
             mode = 1
         cfg = self.onf.config_c()
-        if isinstance(self.onf, DistanceField):
-            _lib.check(lib.nfopp_traj_sdf_collision_eval(cfg, _lib.ptr(self.traj), self.B, self.N, self.D, _lib.ptr(self.t),
-                                                         mode, self.seed, self.rng_offset, self.traj_index_offset,
-                                                         _lib.ptr(self.onf_out), _lib.ptr(self.active, torch.uint8),
-                                                         _lib.stream_ptr()))
+        if self._field_model:
+            entry, _, takes_dim = self._field_model
+            dim = (self.D,) if takes_dim else ()
+            _lib.check(getattr(lib, entry)(cfg, _lib.ptr(self.traj), self.B, self.N, *dim, _lib.ptr(self.t), mode, self.seed,
+                                           self.rng_offset, self.traj_index_offset, _lib.ptr(self.onf_out),
+                                           _lib.ptr(self.active, torch.uint8), _lib.stream_ptr()))
         else:
             active, live = self._active_ptrs()
             _lib.check(lib.nfopp_traj_collision_eval(cfg, _lib.ptr(self.onf.flat_parameters), _lib.ptr(self.traj), self.B,
@@ -257,8 +276,8 @@ class TrajectoryEngine(object):
                                    self.traj_index_offset, self.seed, self.rng_offset, int(reparam_freq),
                                    0 if tdev is not None else 1)
         terms = P(self.terms) if want_terms else None
-        if isinstance(self.onf, DistanceField):
-            _lib.check(lib.nfopp_traj_steps_sdf(cfg, hp, buf, sched, n, P(tdev), terms, _lib.stream_ptr()))
+        if self._field_model:
+            _lib.check(getattr(lib, self._field_model[1])(cfg, hp, buf, sched, n, P(tdev), terms, _lib.stream_ptr()))
         else:
             _lib.check(lib.nfopp_traj_steps(cfg, P(self.onf.flat_parameters), hp, buf, sched, n, P(tdev), terms,
                                             _lib.stream_ptr()))

@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._grid import (GridFrame, as_device_points, cell_centres, cell_keys, checker_boundaries, checker_device, goal_table, int32_on,
-                    seed_launch, traced_search, workspace)
+from ._grid import (GridFrame, as_device_points, cell_centres, cell_keys, checker_boundaries, checker_device, goal_table, heading_poses,
+                    int32_on, seed_launch, traced_search, workspace)
 from .grid_search import seed_trajectories
 
 HEADINGS = 8
@@ -97,10 +97,7 @@ class LatticeGrid(GridFrame):
         boundaries = checker_boundaries(checker, boundaries)
         x, y, x_cells, y_cells = cell_centres(boundaries, resolution)
         dev = checker_device(checker, device)
-        xy = np.stack([x, y], 1).astype(np.float32)
-        poses = np.concatenate([np.concatenate([xy, np.full((len(xy), 1), np.float32(h * np.pi / 4), np.float32)], 1)
-                                for h in range(HEADINGS)], 0)
-        labels = checker.labels(torch.tensor(poses, device=dev))
+        labels = checker.labels(torch.tensor(heading_poses(x, y, HEADINGS), device=dev))   # h * 2 pi / 8 = h * pi / 4 to the bit
         return cls((labels > 0).to(torch.uint8).reshape(HEADINGS, y_cells, x_cells), boundaries, resolution)
 
     def states_of(self, points, free_heading=False):
