@@ -309,6 +309,79 @@ int nfopp_traj_steps_hdf(const nfopp_heading_field* field, const nfopp_traj_hype
                          const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev, float* terms_dev,
                          void* stream);
 
+/* The moving-obstacle collision term (csrc/track_field.hip): a pass over the [.., 4] rows one of the three
+ * collision entries has written.  Where a moving obstacle penetrates the robot deeper than the row says, the row is replaced by
+ * the moving obstacle's: "the deepest disc gives the row" of nfopp_sdf_field, extended over time.
+ *   Tracks: tracks_dev [m, k, stride >= 2], x and y first in a row, the positions of m obstacles at t_n = t0 + n dt -- the
+ *     tensors nfopp_track_conflicts and nfopp_path_time_sample work on, consumed as they are.  Obstacle i is a disc of radius
+ *     radius_dev[i] (NULL: 0).  A track is linear in time between two instants, stands at its first position before t0 and at
+ *     its last after t_{k-1}.
+ *   Time of a sample: wp_time [B, N] says when the robot is at waypoint i.  The collision sample j is
+ *     traj[j+1] + t (traj[j] - traj[j+1]) (it runs backwards in the index), and its time is formed the same way:
+ *     tau = T[j+1] + t (T[j] - T[j+1]), one subtraction, one product, one sum.  Times are data: the term has no gradient in tau.
+ *   The robot is n_discs discs as in nfopp_sdf_field: the same centres cx, cy, the same rule that a robot of centred discs
+ *     takes no sine; poses of 2 components: one centred disc.
+ *   All in fp32, every operation rounded on its own (no fused multiply-add):
+ *     w = (tau - t0) inv_dt;  w = w > 0 ? w : 0;  w = w < k - 1 ? w : k - 1  (a NaN goes to 0)
+ *     n = max(min((int)floor(w), k - 2), 0);  n1 = min(n + 1, k - 1);  s = w - n      (k = 1: n = n1 = 0, s = 0)
+ *     per disc d (outer loop) and track i (inner loop), p = tracks[i]:
+ *       qx = p[n].x + s (p[n1].x - p[n].x), qy likewise;  ex = cx - qx;  ey = cy - qy
+ *       dist = sqrt(ex ex + ey ey), correctly rounded (sqrtf as hipcc compiles it by default; it equals numpy's sqrt on float32)
+ *       pen = ((r_d + radius[i]) + margin) - dist
+ *     The candidate that counts is the first one with the largest pen (strict >); a candidate whose pen is a NaN (a track with
+ *     a coordinate that is not finite) never counts.  For it alone: nx = ex / dist, ny = ey / dist (IEEE division), both 0 when
+ *     dist == 0.  The track row is
+ *       gain pen,  gain (-nx),  gain (-ny),  gain ((-nx) lx + (-ny) ly)      (0 for poses of 2 components)
+ *     with lx = (-ox) s - oy c, ly = ox c - oy s of that disc, as in nfopp_sdf_field.
+ *   Combination: the track row replaces the 16 bytes of the row iff track logit > row logit (strict; so a row whose logit is a
+ *     NaN or +inf stays, and so does every row when no candidate counts).  Otherwise the row is not written.  A sample with a
+ *     pose component or a time that is not finite reads no track and keeps its row. */
+typedef struct nfopp_track_field {
+  const float* tracks_dev;      /* [m, k, stride]; may be NULL when m == 0 */
+  const float* radius_dev;      /* [m] or NULL (= 0) */
+  int32_t m, k, stride;         /* m >= 0, k >= 1, stride >= 2; m * k * stride < 2^31 */
+  float t0, inv_dt;             /* float(t0), float(1.0 / dt): each rounded once from double; inv_dt > 0 */
+  int32_t n_discs;              /* 1..8 */
+  float disc[8][3];             /* body-frame centre (ox, oy) and radius */
+  float margin, gain;           /* metres, logit per metre */
+} nfopp_track_field;
+
+/* The overlay at explicit poses and times.
+ *   points_dev [n, dim], dim 3 (x, y, theta) or 2 (x, y: one disc with a zero offset only);  times_dev [n]
+ *   out4_dev [n, 4], 16-byte aligned, in-out: read as the rows to beat; only the 16 bytes of a row that a track row beats are
+ *     written, nothing else.  (Rows of logit -inf give back the pure track row.)
+ * m == 0 is a set of no obstacles: the call returns without a launch.  Added within ABI 6 (no existing entry changed), as are
+ * the two entries below.  All three refuse, before any launch and without writing anything: a null field, null tracks with
+ * m > 0, null times, m < 0, k < 1, stride < 2, n_discs outside 1..8, an offset disc or several discs with dim 2, a non-finite
+ * t0, inv_dt, margin or gain, inv_dt <= 0, m * k * stride beyond a 32-bit index, null pointers with a positive count, an
+ * unaligned out4_dev, fewer than 2 waypoints and counts beyond one launch. */
+int nfopp_track_field_eval_points(const nfopp_track_field* field, const float* points_dev, const float* times_dev, int64_t n,
+                                  int32_t dim, float* out4_dev, void* stream);
+
+/* The overlay at the collision samples of a batch of trajectories, after any of the three collision entries.
+ *   traj_dev [B, N, dim], wp_time_dev [B, N]
+ *   t_dev [B, N-1]: read only -- the draws the collision entry has just used (or written, in its t_mode 1)
+ *   out4_dev [B, N-1, 4], 16-byte aligned, in-out as above
+ *   active_dev [B] uint8 or NULL: the rows of trajectories with 0 are neither read nor written */
+int nfopp_traj_track_overlay(const nfopp_track_field* field, const float* traj_dev, const float* wp_time_dev, int64_t batch,
+                             int32_t n_waypoints, int32_t dim, const float* t_dev, float* out4_dev, const uint8_t* active_dev,
+                             void* stream);
+
+/* nfopp_traj_steps / _sdf / _hdf with moving obstacles: the one loop, with the collision entry of `kind` followed by
+ * nfopp_traj_track_overlay as each step's collision term, so n_steps here equal n_steps sequences of collision entry,
+ * overlay, update (and reparametrisation on its schedule) bit for bit.
+ *   kind NFOPP_MODEL_ONF: model = const nfopp_onf_config*, params_dev its parameters;  NFOPP_MODEL_SDF: model = const
+ *   nfopp_sdf_field*;  NFOPP_MODEL_HDF: model = const nfopp_heading_field* (buf->dim must be 3);  params_dev is ignored for both
+ * Writes what nfopp_traj_steps writes.  An unknown kind, the track field, wp_time_dev and the schedule are checked before the
+ * first launch: a call refused for one of them has written nothing. */
+#define NFOPP_MODEL_ONF 0
+#define NFOPP_MODEL_SDF 1
+#define NFOPP_MODEL_HDF 2
+int nfopp_traj_steps_moving(int32_t kind, const void* model, const float* params_dev, const nfopp_track_field* field,
+                            const float* wp_time_dev, const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf,
+                            const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev, float* terms_dev,
+                            void* stream);
+
 /* ONF fitting step, gradient part: BCE-with-logits (mean over ALL samples of the job) and its gradient w.r.t.
  * every parameter incl. the angle frequencies (nfop/nerf_opt_planner.py:83-89).
  *   samples_dev [P, point_dim], labels_dev [P] (0/1), inv_count = 1 / (global sample count)

@@ -8,7 +8,8 @@
 // (Python / C doubles: 1 - beta^k through pow(), lr / bc1, sqrt(bc2), rounded to fp32 once) and enqueues
 //   nfopp_traj_collision_eval -> nfopp_traj_update -> [nfopp_reparametrize when step_count % reparam_freq == 0]
 // (nfopp_traj_steps_sdf: nfopp_traj_sdf_collision_eval in the first place; nfopp_traj_steps_hdf:
-// nfopp_traj_hdf_collision_eval)
+// nfopp_traj_hdf_collision_eval; nfopp_traj_steps_moving: any of the three followed by nfopp_traj_track_overlay,
+// DESIGN.md 27)
 // on the caller's stream -- the same three entry points, the same kernels, the same arguments as n single calls, so
 // the results are bit-identical to n calls of the single-step sequence (tests/test_gpu_multistep.py).  Nothing
 // synchronises; the field must not change during the n steps (the reference's step with ONF learning needs the host
@@ -16,6 +17,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "track_field.h"
 
 using namespace nfopp;
 
@@ -90,5 +92,38 @@ extern "C" int nfopp_traj_steps_hdf(const nfopp_heading_field* field, const nfop
     return nfopp_traj_hdf_collision_eval(field, buf->traj_dev, buf->batch, buf->n_waypoints, t_k, sched->t_mode, sched->seed,
                                          sched->rng_offset + (uint64_t)k, sched->traj_index_offset, buf->onf_out4_dev,
                                          buf->active_dev, stream);
+  });
+}
+
+// The same loop with moving obstacles (csrc/track_field.hip): per step the collision entry of `kind`, then
+// nfopp_traj_track_overlay on the rows and draws it left, then the update.  The track field is checked before the first launch.
+extern "C" int nfopp_traj_steps_moving(int32_t kind, const void* model, const float* params_dev, const nfopp_track_field* field,
+                                       const float* wp_time_dev, const nfopp_traj_hyper* hp, const nfopp_traj_buffers* buf,
+                                       const nfopp_step_schedule* sched, int32_t n_steps, const float* t_steps_dev,
+                                       float* terms_dev, void* stream) {
+  NFOPP_REQUIRE(kind == NFOPP_MODEL_ONF || kind == NFOPP_MODEL_SDF || kind == NFOPP_MODEL_HDF, "unknown collision model %d", kind);
+  NFOPP_REQUIRE(model && hp && buf && sched, "null argument");
+  NFOPP_REQUIRE(kind != NFOPP_MODEL_ONF || params_dev, "null ONF parameters");
+  NFOPP_REQUIRE(kind != NFOPP_MODEL_HDF || buf->dim == 3, "a heading field takes poses of 3 components, not %d", buf->dim);
+  const int rc = check_track_overlay(field, wp_time_dev, buf->batch, buf->n_waypoints, buf->dim, buf->onf_out4_dev);
+  if (rc != NFOPP_OK) return rc;
+  return run_steps(hp, buf, sched, n_steps, t_steps_dev, terms_dev, stream, [&](float* t_k, int32_t k) {
+    const uint64_t word = sched->rng_offset + (uint64_t)k;
+    int rc_k;
+    if (kind == NFOPP_MODEL_ONF)
+      rc_k = nfopp_traj_collision_eval(static_cast<const nfopp_onf_config*>(model), params_dev, buf->traj_dev, buf->batch,
+                                       buf->n_waypoints, buf->dim, t_k, sched->t_mode, sched->seed, word, sched->traj_index_offset,
+                                       buf->onf_out4_dev, buf->active_dev, buf->live_ws_dev, stream);
+    else if (kind == NFOPP_MODEL_SDF)
+      rc_k = nfopp_traj_sdf_collision_eval(static_cast<const nfopp_sdf_field*>(model), buf->traj_dev, buf->batch, buf->n_waypoints,
+                                           buf->dim, t_k, sched->t_mode, sched->seed, word, sched->traj_index_offset,
+                                           buf->onf_out4_dev, buf->active_dev, stream);
+    else
+      rc_k = nfopp_traj_hdf_collision_eval(static_cast<const nfopp_heading_field*>(model), buf->traj_dev, buf->batch,
+                                           buf->n_waypoints, t_k, sched->t_mode, sched->seed, word, sched->traj_index_offset,
+                                           buf->onf_out4_dev, buf->active_dev, stream);
+    if (rc_k != NFOPP_OK) return rc_k;
+    return nfopp_traj_track_overlay(field, buf->traj_dev, wp_time_dev, buf->batch, buf->n_waypoints, buf->dim, t_k,
+                                    buf->onf_out4_dev, buf->active_dev, stream);
   });
 }

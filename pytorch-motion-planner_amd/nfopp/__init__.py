@@ -7,6 +7,7 @@ from .batch import BatchPlanner, OnfFitter, shard_range, straight_line_init
 from .engine import TrajectoryEngine, TrajectoryHyper, band_of, inverse_hessian
 from .distance_field import DistanceField
 from .heading_field import HeadingDistanceField
+from .moving import MovingObstacles
 from .conflicts import (CONFLICT_BAD_TRACK, CONFLICT_COUNT, CONFLICT_FIRST_PARTNER, CONFLICT_FIRST_TIME, CONFLICT_MIN_GAP,
                         CONFLICT_MIN_PARTNER, CONFLICT_MIN_TIME, CONFLICT_NO_PARTNER, CONFLICT_STATUS, BoxTrackConflicts,
                         TrackConflicts, box_track_conflicts, constant_velocity_tracks, track_conflicts, track_headings)
@@ -35,7 +36,7 @@ from .time_profile import (TIME_GOAL_UNREACHABLE, TIME_OUT_OF_RANGE, TIME_SLOT_S
  PATH_STAT_MIN_CLEARANCE, PATH_STAT_CLEARANCE_AT, PATH_STAT_MEAN_CLEARANCE) = range(NUM_PATH_STATS)
 
 __all__ = [
-    "BatchPlanner", "BatchSampler", "DistanceField", "HeadingDistanceField", "DeviceCircleChecker", "DeviceGridChecker", "DeviceGridMap", "DeviceRectangleChecker", "OnfFitter", "shard_range", "straight_line_init", "LIB_PATH", "NfoppError", "load_library", "TrajectoryEngine", "TrajectoryHyper", "band_of", "inverse_hessian",
+    "BatchPlanner", "BatchSampler", "DistanceField", "HeadingDistanceField", "MovingObstacles", "DeviceCircleChecker", "DeviceGridChecker", "DeviceGridMap", "DeviceRectangleChecker", "OnfFitter", "shard_range", "straight_line_init", "LIB_PATH", "NfoppError", "load_library", "TrajectoryEngine", "TrajectoryHyper", "band_of", "inverse_hessian",
     "DEFAULT_PARAMETERS", "PlannerFactory", "UniversalFactory", "AstarTrajectoryInitializer", "AttributeDict",
     "CircleCollisionChecker", "CircleDirectedCollisionChecker", "CollisionChecker", "Position2",
     "RectangleCollisionChecker", "TrajectoryInitializer", "ONF", "ConstrainedNERFOptPlanner", "ContinuousPlanner",

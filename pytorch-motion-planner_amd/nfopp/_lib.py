@@ -83,6 +83,15 @@ class HeadingFieldC(ctypes.Structure):
                 ("margin", ctypes.c_float), ("gain", ctypes.c_float)]
 
 
+class TrackFieldC(ctypes.Structure):
+    """nfopp_track_field: predicted tracks, their radii and time grid, the robot's discs, margin and gain (nfopp/moving.py)."""
+    _fields_ = [("tracks_dev", _P), ("radius_dev", _P), ("m", ctypes.c_int32), ("k", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("t0", ctypes.c_float), ("inv_dt", ctypes.c_float), ("n_discs", ctypes.c_int32),
+                ("disc", (ctypes.c_float * 3) * 8), ("margin", ctypes.c_float), ("gain", ctypes.c_float)]
+
+
+MODEL_ONF, MODEL_SDF, MODEL_HDF = 0, 1, 2   # NFOPP_MODEL_*: the `kind` of nfopp_traj_steps_moving
+
 _SIGNATURES = {
     "nfopp_abi_version": (ctypes.c_int, []),
     "nfopp_last_error": (ctypes.c_char_p, []),
@@ -111,6 +120,12 @@ _SIGNATURES = {
     "nfopp_traj_steps_hdf": (ctypes.c_int, [ctypes.POINTER(HeadingFieldC), ctypes.POINTER(TrajHyperC),
                                             ctypes.POINTER(TrajBuffersC), ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P,
                                             _P]),
+    "nfopp_track_field_eval_points": (ctypes.c_int, [ctypes.POINTER(TrackFieldC), _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
+    "nfopp_traj_track_overlay": (ctypes.c_int, [ctypes.POINTER(TrackFieldC), _P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                _P, _P, _P, _P]),
+    "nfopp_traj_steps_moving": (ctypes.c_int, [ctypes.c_int32, _P, _P, ctypes.POINTER(TrackFieldC), _P, ctypes.POINTER(TrajHyperC),
+                                               ctypes.POINTER(TrajBuffersC), ctypes.POINTER(StepScheduleC), ctypes.c_int32, _P, _P,
+                                               _P]),
     "nfopp_reparametrize": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nfopp_update_endpoints": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P,
                                               _P, _P, _P, _P, _P]),

@@ -139,6 +139,10 @@ class BatchPlanner(object):
     the parameters behind torch's back while a planner exists -- `dist.broadcast(onf.flat_parameters, 0)`, `.data`
     assignments -- must call `onf.mark_modified()` afterwards (or construct with `freeze_field=False`).
 
+    `moving` (an nfopp.MovingObstacles) makes the step yield to predicted tracks: behind the collision model's rows runs the
+    overlay of csrc/track_field.hip, which needs the time of every waypoint -- `set_waypoint_times`, before the
+    first step (a step without them raises ValueError).  With `moving=None` every call is the one it was.
+
     `onf` may be a `DistanceField` or a `HeadingDistanceField` instead: the collision term then comes from the signed distance
     image of an occupancy grid (csrc/sdf_field.hip, csrc/heading_field.hip) and everything else -- init, step(n), replan,
     evaluate, path_stats, the seeders -- is as it is behind the network.  `freeze_field` does not apply and `checker=` raises ValueError: there is nothing to fit."""
@@ -147,7 +151,7 @@ class BatchPlanner(object):
                  device="cuda", seed=0, traj_index_offset=0, checker=None, fit_lr=2e-2, fit_betas=(0.9, 0.9),
                  optimize_collision_model_freq=1, trajectory_random_offset=0.02, course_random_offset=1.5,
                  angle_offset=0.0, random_field_points=10, collision_point_count=100, group=None,
-                 init_angles_with_trajectory=False, global_batch=None, freeze_field=True):
+                 init_angles_with_trajectory=False, global_batch=None, freeze_field=True, moving=None):
         if field_model(onf):
             # a distance field (engine.FIELD_MODELS): the map is the model, there is nothing to freeze or to fit
             if checker is not None:
@@ -158,7 +162,7 @@ class BatchPlanner(object):
         # trajectories over ALL ranks (continuous learning: denominator of the BCE mean); default = equal shards
         self.global_batch = None if global_batch is None else int(global_batch)
         self.engine = TrajectoryEngine(onf, batch, n_waypoints, onf.point_dim, hyper, velocity_hessian_weight, device,
-                                       seed=seed, traj_index_offset=traj_index_offset)
+                                       seed=seed, traj_index_offset=traj_index_offset, moving=moving)
         self.onf = onf
         self.reparam_freq = int(reparametrize_trajectory_freq)
         self.step_count = 0
@@ -231,6 +235,20 @@ class BatchPlanner(object):
         eng.adam_step = 0
         self.step_count = 0
         self._prev = None
+
+    def set_waypoint_times(self, times):
+        """times [B, N], or [N] for every trajectory alike: when the robot is at interior waypoint i, for `moving`.  From a
+        `TimedPaths` profile of these paths (`timed_paths(limits)`) they are `profile[:, 1:-1, nfopp.TIME_SLOT_T]`: the profile
+        has the start and the goal around the N waypoints."""
+        self.engine.set_waypoint_times(times)
+
+    def uniform_waypoint_times(self, t_start, duration):
+        """Sets and returns the times of a robot that leaves the start at `t_start` and reaches the goal `duration` later at a
+        constant pace in the waypoint index: T[i] = t_start + duration * (i + 1) / (N + 1), formed in double and rounded once."""
+        n = self.engine.N
+        times = torch.from_numpy((float(t_start) + float(duration) * np.arange(1, n + 1) / (n + 1.0)).astype(np.float32))
+        self.engine.set_waypoint_times(times)
+        return times
 
     def fit_field(self):
         """One `_optimize_collision_model` over the batch (nerf:76-91): poses from the PREVIOUS trajectories, labels

@@ -7,6 +7,7 @@ plus per-step scratch  t [B,N-1]  and  onf_out [B,N-1,4].
 One step = 2 launches:  nfopp_traj_collision_eval (fused sampling + ONF fwd/bwd, MFMA)  ->  nfopp_traj_update
 (stencil terms, banded H^-1, Adam, multiplier ascent); every `reparam_freq` steps a third: nfopp_reparametrize.
 """
+import ctypes
 import math
 import operator
 
@@ -24,6 +25,8 @@ FIELD_MODELS = {
     DistanceField: ("nfopp_traj_sdf_collision_eval", "nfopp_traj_steps_sdf", True),
     HeadingDistanceField: ("nfopp_traj_hdf_collision_eval", "nfopp_traj_steps_hdf", False),
 }
+# step-loop entry of a field model -> its `kind` in nfopp_traj_steps_moving (an ONF is _lib.MODEL_ONF)
+MOVING_KINDS = {"nfopp_traj_steps_sdf": _lib.MODEL_SDF, "nfopp_traj_steps_hdf": _lib.MODEL_HDF}
 
 
 def field_model(model):
@@ -155,12 +158,17 @@ class TrajectoryHyper(object):
 class TrajectoryEngine(object):
     """Owns the batched state and runs the step pipeline.  `traj` may be an externally owned [B,N,D] (or [N,D])
     HIP tensor (the planner's `_trajectory`); it is updated in place.  `onf` is the collision model: an ONF, or a
-    `DistanceField` or `HeadingDistanceField`, whose rows come from their own entries (FIELD_MODELS)."""
+    `DistanceField` or `HeadingDistanceField`, whose rows come from their own entries (FIELD_MODELS).
+    `moving` is a `MovingObstacles` or None: with one, the overlay of csrc/track_field.hip runs behind the
+    model's collision entry, at the waypoint times `set_waypoint_times` was given."""
 
     def __init__(self, onf, batch, n_waypoints, dim, hyper, velocity_hessian_weight, device, traj=None, seed=0,
-                 traj_index_offset=0):
+                 traj_index_offset=0, moving=None):
         _lib.require_gpu()
         self.onf, self.hyper = onf, hyper
+        if moving is not None and moving.point_dim != int(dim):
+            raise ValueError("trajectory dim %d does not match the moving obstacles' robot (dim %d)" % (dim, moving.point_dim))
+        self.moving, self.wp_time = moving, None
         self._field_model = field_model(onf)
         self.B, self.N, self.D = int(batch), int(n_waypoints), int(dim)
         if self.D != onf.point_dim:
@@ -208,11 +216,30 @@ class TrajectoryEngine(object):
             self._live = torch.zeros(self.B + 1, dtype=torch.int32, device=self.device)
         return _lib.ptr(self.active, torch.uint8), _lib.ptr(self._live, torch.int32)
 
+    def set_waypoint_times(self, times):
+        """times [B, N], or [N] for every trajectory alike: when the robot is at waypoint i (fp32; a device tensor is not
+        copied to the host).  The arc-length reparametrisation keeps "waypoint i at T[i]"."""
+        if not isinstance(times, torch.Tensor):
+            times = torch.from_numpy(np.array(times, np.float32))
+        times = times.to(device=self.device, dtype=torch.float32)
+        if tuple(times.shape) not in ((self.N,), (self.B, self.N)):
+            raise ValueError("waypoint times must be [%d, %d] or [%d], got %s" % (self.B, self.N, self.N, tuple(times.shape)))
+        if self.wp_time is None:
+            self.wp_time = torch.empty(self.B, self.N, dtype=torch.float32, device=self.device)
+        self.wp_time.copy_(times.expand(self.B, self.N))
+
+    def _moving_times(self):
+        """The waypoint-time pointer of a step with moving obstacles."""
+        if self.wp_time is None:
+            raise ValueError("moving obstacles need waypoint times: call set_waypoint_times() first")
+        return _lib.ptr(self.wp_time)
+
     # ---- pipeline stages ------------------------------------------------------------------------------------------
     def collision_eval(self, t=None):
         """ONF logits + input gradients at the collision samples.  `t` [B,N-1] injects the draws (parity mode);
         None draws them on the device with Philox (counter = global sample index, rng_offset)."""
         lib = _lib.load()
+        times = self._moving_times() if self.moving is not None else None
         if t is not None:
             self.t.copy_(torch.as_tensor(t, dtype=torch.float32).reshape(self.B, self.N - 1))
             mode = 0
@@ -231,6 +258,10 @@ class TrajectoryEngine(object):
                                                      self.N, self.D, _lib.ptr(self.t), mode, self.seed, self.rng_offset,
                                                      self.traj_index_offset, _lib.ptr(self.onf_out),
                                                      active, live, _lib.stream_ptr()))
+        if self.moving is not None:
+            _lib.check(lib.nfopp_traj_track_overlay(self.moving.config_c(), _lib.ptr(self.traj), times, self.B, self.N, self.D,
+                                                    _lib.ptr(self.t), _lib.ptr(self.onf_out),
+                                                    _lib.ptr(self.active, torch.uint8), _lib.stream_ptr()))
         if mode == 1:
             self.rng_offset += 1
 
@@ -261,6 +292,7 @@ class TrajectoryEngine(object):
         if n <= 0:
             return
         lib = _lib.load()
+        times = self._moving_times() if self.moving is not None else None
         cfg = self.onf.config_c()
         hp = self.hyper.to_c(self.adam_step + 1)
         active, live = self._active_ptrs()
@@ -276,7 +308,12 @@ class TrajectoryEngine(object):
                                    self.traj_index_offset, self.seed, self.rng_offset, int(reparam_freq),
                                    0 if tdev is not None else 1)
         terms = P(self.terms) if want_terms else None
-        if self._field_model:
+        if self.moving is not None:
+            kind = MOVING_KINDS[self._field_model[1]] if self._field_model else _lib.MODEL_ONF
+            params = None if self._field_model else P(self.onf.flat_parameters)
+            _lib.check(lib.nfopp_traj_steps_moving(kind, ctypes.addressof(cfg), params, self.moving.config_c(), times, hp, buf,
+                                                   sched, n, P(tdev), terms, _lib.stream_ptr()))
+        elif self._field_model:
             _lib.check(getattr(lib, self._field_model[1])(cfg, hp, buf, sched, n, P(tdev), terms, _lib.stream_ptr()))
         else:
             _lib.check(lib.nfopp_traj_steps(cfg, P(self.onf.flat_parameters), hp, buf, sched, n, P(tdev), terms,
