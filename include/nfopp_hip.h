@@ -44,13 +44,25 @@ typedef enum nfopp_status {
  *   [_angle_encoder._biases (2*angle_dim), _angle_encoder._frequencies (2*angle_dim)]   if angle_dim > 0
  *   mlp.0.weight [100, F], mlp.0.bias [100], mlp.2.weight [100,100], mlp.2.bias [100],
  *   mlp2.0.weight [1, 100+F], mlp2.0.bias [1], encoding_layer.weight [E, 2], [encoding_layer.bias [E]] if has_bias
- * with E = use_cos ? 200 : 100 and F = E + 2*angle_dim (220 for every shipped script). */
+ * with E = use_cos ? 200 : 100 and F = E + 2*angle_dim (220 for every shipped script).
+ *
+ * angle_dim outside 0 .. 16 is a bad configuration for every entry.  Inside it:
+ *   E = 100: angle_dim 0 .. 14 (F <= 128),  E = 200: angle_dim 0 .. 12 (F <= 224) are evaluated; a larger one is refused with
+ *     "unsupported ONF feature dimension" by every ONF entry (inference, trajectory evaluation, both fit paths).
+ *   The default matrix path (1) evaluates the four shapes of the reference -- angle_dim 0 and 10 -- on its 32x32 kernels, and
+ *     F = 128 / 224 (angle_dim 14 / 12) on the 16x16 kernels; every other accepted angle_dim is REFUSED there (NFOPP_ERR_ARG,
+ *     "the 32x32 ONF kernel for .. input blocks is built for ..") and needs nfopp_set_matrix_path(0) or (2), which evaluate
+ *     all of them.
+ *   The MFMA fit (nfopp_onf_train_grad_ex path 2) needs one free pad position in the last input tile: F = 128 and 224 are
+ *     refused with "no pad feature available"; the per-sample fit (path 1) takes every accepted angle_dim.
+ * A refused call launches nothing and writes no output.  (Table: DESIGN.md section 3; tests/onf_geometry_cases.py.) */
 typedef struct nfopp_onf_config {
   float mean;         /* nfop/onf_model.py:38  x = (x - mean) / sigma */
   float sigma;
   int32_t use_cos;    /* 1: sin on the first 100 encodings, cos on the next 100 (onf_model.py:40-41) */
   int32_t has_bias;   /* encoding_layer bias present */
-  int32_t angle_dim;  /* 0 = no AngleEncoder (2-D points), 10 = nfop/angle_encoder.py default */
+  int32_t angle_dim;  /* 0 = no AngleEncoder (2-D points), 10 = nfop/angle_encoder.py default; accepted: 0 .. 14 (use_cos: 0 .. 12),
+                         and on the default matrix path only 0, 10 and 14 (12): see above */
 } nfopp_onf_config;
 
 /* Scalars of one trajectory optimisation step.  SE(2) terms: nfop/constrained_nerf_opt_planner.py:76-130,

@@ -38,7 +38,7 @@ int onf_route(const OnfGeom& g, OnfRoute* r) {
     *r = {ONF_X32, nkb};
     return NFOPP_OK;
   }
-  const int nkt = (g.fin + 15) / 16;
+  const int nkt = layout_p_tiles(g.fin);
   if (nkt != 14 && nkt != 13 && nkt != 8 && nkt != 7) return onf_unsupported(g);
   *r = {path == 0 ? ONF_FP32 : ONF_SPLIT16, nkt};
   return NFOPP_OK;

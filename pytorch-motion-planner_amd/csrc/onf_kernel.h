@@ -45,6 +45,11 @@ struct OnfKernelArgs {
 // 16-wide input tiles.
 enum OnfFamily { ONF_FP32, ONF_SPLIT16, ONF_X32 };
 struct OnfRoute { OnfFamily family; int nkt; };
+// Input tiles of 16 a 16x16 kernel has to visit for `fin` features.  Layout P (csrc/onf_layout.h: slot_layout_p) deals the
+// features of a block of 32 to a PAIR of tiles -- 0..7 and 16..23 to the even one, 8..15 and 24..31 to the odd one -- so the
+// odd tile is in use from the block's 9th feature on: fin = 105..112 needs 8 tiles and 201..208 needs 14, where
+// (fin + 15) / 16 says 7 and 13.
+inline int layout_p_tiles(int fin) { return 2 * ((fin - 1) >> 5) + (((fin - 1) & 31) >= 8 ? 2 : 1); }
 // Reads the matrix path once; sets "unsupported ONF feature dimension" and fails if the family has no kernel for g.
 int onf_route(const OnfGeom& g, OnfRoute* r);
 

@@ -251,6 +251,11 @@ extern "C" int nfopp_onf_train_grad_ex(const nfopp_onf_config* cfg, const float*
   OnfGeom g;
   NFOPP_REQUIRE(make_geom(cfg, &g), "bad ONF configuration");
   NFOPP_REQUIRE(g.fin <= 256, "feature dimension %d too large", g.fin);
+  {  // a feature dimension no inference entry evaluates is not fitted either, on either fit path
+    OnfRoute r;
+    const int rc = onf_route(g, &r);
+    if (rc != NFOPP_OK) return rc;
+  }
   NFOPP_REQUIRE(params_dev && samples_dev && labels_dev && grad_dev && workspace_dev, "null device pointer");
   NFOPP_REQUIRE(n_samples > 0 && n_samples <= 0x7fffffffLL, "sample count out of range");
   NFOPP_REQUIRE(path >= 0 && path <= 2, "path must be 0 (auto), 1 (per-sample) or 2 (MFMA)");

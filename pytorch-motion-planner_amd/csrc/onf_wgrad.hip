@@ -1046,8 +1046,12 @@ static WgradWs carve_wgrad(long long P, int nkt) {
 }
 
 // sized for the longer of the two row lengths (x32 order reserves a pad position for the ones feature: (fin + 16) / 16 tiles),
-// so the answer does not depend on the matrix path in force when the fit runs
-size_t wgrad_workspace_bytes(const OnfGeom& g, long long P) { return (size_t)carve_wgrad(P, (g.fin + 16) / 16).total * sizeof(float); }
+// or, where layout P needs more, for the tile count of the 16x16 kernels (layout_p_tiles: fin = 105..111, 201..207), so the
+// answer does not depend on the matrix path in force when the fit runs
+size_t wgrad_workspace_bytes(const OnfGeom& g, long long P) {
+  const int x32_tiles = (g.fin + 16) / 16, p_tiles = layout_p_tiles(g.fin);
+  return (size_t)carve_wgrad(P, x32_tiles > p_tiles ? x32_tiles : p_tiles).total * sizeof(float);
+}
 
 // pass 2 reads the factors in the order pass 1 wrote them: onf_wgrad_kernel behind the fp32 pass, onf_wgrad_split_kernel
 // behind a split pass (slot order after 16x16x32 tiles, x32 order after 32x32x16 tiles)

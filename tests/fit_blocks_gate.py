@@ -140,6 +140,12 @@ def reference(fin, P, C, keep_eval=False):
     """everything the comparer needs of the case (F, P) on C compute units, computed once and shared by every launch"""
     flat, cfg = network(fin)
     x, y = fc.inputs(fin, P, flat, cfg)
+    return reference_of(flat, cfg, x, y, C, keep_eval)
+
+
+def reference_of(flat, cfg, x, y, C, keep_eval=False):
+    """the same for any network (flat, cfg) and samples (x, y): what tests/onf_geometry_cases.py builds its fit cases with"""
+    fin, P = cfg.feature_dim, len(y)
     r64 = f64.onf_fit64(flat, cfg, x, y, keep_eval=True)
     c = r64["eval"]
     S = f64.fit_sums64(c, cfg, r64["rho"], mag=True)
