@@ -513,6 +513,10 @@ int nfopp_set_matrix_path(int32_t path);
  * per content over the life of the process (a counter), not per buffer. */
 int nfopp_onf_params_version(const float* params_dev, uint64_t version);
 int nfopp_get_matrix_path(void);
+/* Sample count from which matrix path 1 launches its 512-thread workgroup (two waves per SIMD); a launch of fewer samples
+ * runs the 256-thread one.  CUs x 256 on the current device.  Results do not depend on the shape; tests that want a launch
+ * on either side of the edge read it here.  Added within ABI 6 (no existing entry changed). */
+int64_t nfopp_onf_wide_launch_threshold(void);
 
 /* ---- the steps either side of the planner step ----------------------------------------
  * nfopp_init_trajectories: TrajectoryInitializer.initialize_trajectory (+ initialize_angle and, with

@@ -34,6 +34,8 @@ int hip_fail(hipError_t e, const char* what);
 constexpr int MAX_DEVICES = 64;
 int current_device();   // hipGetDevice, -1 on failure (error string set)
 int query_cus();        // CU count of the current device (cached), 256 if it cannot be queried
+// Samples from which the 32x32 ONF kernels launch 512 threads per workgroup (nfopp_onf_wide_launch_threshold): CUs x 256.
+inline long long onf_wide_launch_threshold() { return (long long)query_cus() * 256; }
 // Raises the dynamic-LDS limit of `kernel` on the current device the first time it is launched there.
 // `flags` is the caller's static bool[MAX_DEVICES] for that kernel instantiation.
 int ensure_dynamic_lds(const void* kernel, size_t bytes, bool* flags);

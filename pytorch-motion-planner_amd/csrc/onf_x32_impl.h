@@ -74,7 +74,9 @@ constexpr int O_ISA = O_FTD + 224 * 16;        // [224] 1.0 = angle feature
 constexpr int O_W3A = O_ISA + 224 * 4;         // [128] fp32 W3[:100] by hidden position
 constexpr int O_W3L = O_W3A + 128 * 4;         // [7 kb][2 g][3 levels][4 words]: W3[:100] pre-split in B-fragment order
 constexpr int IMG_BYTES = O_W3L + HK * 2 * 3 * 16;
-static_assert(IMG_BYTES % 16 == 0 && IMG_BYTES <= 160 * 1024, "LDS image");
+// behind the image: the workgroup's tile counter (one word; MODE 0 and 2 claim their tiles from it, see "Tiles by claim")
+constexpr int O_CLAIM = IMG_BYTES, LDS_BYTES = IMG_BYTES + 16;
+static_assert(IMG_BYTES % 16 == 0 && LDS_BYTES <= 160 * 1024, "LDS image");
 // hi -> mid distance of the W2 images: with the largest tile offset of either W2 GEMM it fits the 16-bit offset of a DS read
 constexpr int W2_MID = O_W2M - O_W2H;
 static_assert(O_W2H % 256 == 0 && W2_MID % 256 == 0, "the XOR addressing of the W2 reads passes the image offsets by");
@@ -352,6 +354,22 @@ __device__ __forceinline__ void eval_angle_item(EvalState& s, const f32x4& tw, f
 // wave alone on its SIMD finishes its tile in about half the time (B = 1 drop-in latency).  A tile's arithmetic does not
 // depend on the shape, so results are bit-identical either way (sharding-independent).
 
+// Tiles by claim (MODE 0 and 2).  A workgroup owns the chunks blockIdx.x + k gridDim.x < n_chunks, K of them, as ever; with
+// TPC = XT / 64 tiles per chunk they are the tickets 0 .. K TPC - 1 of its pool:
+//   ticket t  ->  chunk blockIdx.x + (t / TPC) gridDim.x,  tile t % TPC,  first sample chunk * CH + 32 (t % TPC)
+// so the workgroup computes the samples it always did.  Which WAVE runs a tile is not fixed: a wave takes two tickets per
+// claim with one atomic add on the LDS word at O_CLAIM,
+//   claim c  ->  tickets t = 2 TPC (c / TPC) + c % TPC  and  t + TPC:  one tile of two consecutive owned chunks
+// (restated in tools/x32/emulate_x32.py: claim_tickets), and leaves when the first is past the pool -- no wave waits for
+// another, and the two waves of a SIMD stay resident until the pool is empty instead of the favoured one leaving early with
+// its fixed share.  The lower lane half forms the poses of t, the upper half those of t + TPC (the pose exchange below:
+// this chunk's tile and the next chunk's, as in the fixed walk); a second ticket past the pool gives padding lanes and no
+// second tile.  The first TPC claims are one chunk wide, so a launch with a chunk or two per workgroup still starts every
+// wave at once: pairing t with t + 1 left half the waves of such a launch without a tile and cost the small launches of the
+// 256-thread shape 58 % (profiles/k1_tile_claims.txt).  load_point(p) depends on p alone, so a tile's bits do not depend on
+// the wave that ran it.  MODE 1 keeps the fixed walk (wave = tile, chunk += gridDim.x): its per-wave loss rows make the
+// summation order a function of the assignment.
+
 // Third-level (blob) fragments are fetched LOOK steps ahead into a ring of RL registers sets
 constexpr int LOOK = 3, RL = 4;
 
@@ -419,6 +437,10 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       for (int q = 0; q < 4; ++q) if (k0 + XT * q < N16) reinterpret_cast<u32x4*>(lds)[k0 + XT * q] = v[q];
     }
   }
+  constexpr bool CLAIM = !TRAIN && NT == 1;   // tiles by claim (see above); the fit and two-tile waves walk a fixed stride
+  constexpr int TPC = XT / 64;                // tiles per chunk
+  unsigned* const claim_word = reinterpret_cast<unsigned*>(lds + O_CLAIM);
+  if (CLAIM && threadIdx.x == 0) *claim_word = 0u;
   __syncthreads();
   // static priority for the younger half (MI355X_MICROARCH.md); the condition must be provably wave-uniform, or hipcc
   // lowers it to an exec mask around an UNCONDITIONAL s_setprio
@@ -487,7 +509,8 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
   // Samples.  Both lane halves of a wave need each tile's 32 poses, so forming them in all 64 lanes would do every draw,
   // interpolation and normalisation twice.  Each pose is formed by exactly ONE lane (the arithmetic of load_point: same
   // bits) and the halves exchange (5 cross-half moves).  NT = 2: the lower half forms tile 0's poses, the upper half tile
-  // 1's.  NT = 1: every OTHER chunk the lower half forms this chunk's poses and the upper half the next chunk's.
+  // 1's.  NT = 1: every OTHER tile the lower half forms this tile's poses and the upper half the next one's (by claim: the
+  // two tickets of one claim; the fit: this chunk's tile and the next chunk's).
   float nux = 0.f, nuy = 0.f, nth = 0.f;
   long long npidx = 0;
   bool have_next = false;
@@ -496,7 +519,9 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
   auto st4 = [](const __amdgpu_buffer_rsrc_t& r, int voff, float x0, float x1, float x2, float x3) __attribute__((always_inline)) {
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)}, r, voff, 0, 0);
   };
-  for (long long chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+  // CLAIM: the loop ends on a claim past the pool (a ticket whose chunk is past the last one).  `chunk` is the fixed walk's
+  // alone: under CLAIM nothing may read it -- its only readers are the fit's helpers (train_rsrc), which MODE 1 alone calls.
+  for (long long chunk = blockIdx.x; CLAIM || chunk < n_chunks; chunk += gridDim.x) {
     float ux[NT], uy[NT], th[NT];
     long long pidx[NT];
     // table bases: opaque per chunk, so that (base + small constant) stays an immediate offset of the LDS read instead
@@ -507,8 +532,22 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
       have_next = false;
     } else {
       float x, y, ang;
-      // NT = 1: this chunk (lower half) / the next one (upper half; past the last chunk: padding lanes, nothing stored)
-      const long long p = NT == 1 ? (chunk + (g ? (long long)gridDim.x : 0)) * CH + wave * 32 + j : chunk * CH + wave * 64 + lane;
+      long long p;
+      bool second = true;   // CLAIM: the claim's second ticket is in the pool
+      if constexpr (CLAIM) {
+        // one claim from the workgroup's counter: one lane adds, the wave reads the result
+        unsigned c = 0u;
+        if (lane == 0) c = atomicAdd(claim_word, 1u);
+        c = (unsigned)__builtin_amdgcn_readfirstlane((int)c);
+        // tile c % TPC of the owned chunks 2 (c / TPC) (lower half) and 2 (c / TPC) + 1 (upper half)
+        const long long chunk0 = (long long)blockIdx.x + 2LL * (c / TPC) * gridDim.x, chunk1 = chunk0 + gridDim.x;
+        if (chunk0 >= n_chunks) break;
+        second = chunk1 < n_chunks;   // past the pool: padding lanes in the upper half, and no second tile
+        p = (g ? chunk1 : chunk0) * CH + 32 * (c % TPC) + j;
+      } else {
+        // NT = 1: this chunk (lower half) / the next one (upper half; past the last chunk: padding lanes, nothing stored)
+        p = NT == 1 ? (chunk + (g ? (long long)gridDim.x : 0)) * CH + wave * 32 + j : chunk * CH + wave * 64 + lane;
+      }
       long long row;
       if constexpr (TRAIN) {   // the fit's samples are explicit poses: the trajectory half of load_point (and the dozen scalar
                                // registers of its arguments) is not part of this kernel
@@ -529,7 +568,7 @@ __global__ __launch_bounds__(XT, XT / 256) void onf_x32_kernel(const OnfKernelAr
         ux[NT - 1] = g ? sx : ox; uy[NT - 1] = g ? sy : oy; th[NT - 1] = g ? ang : oa; pidx[NT - 1] = g ? row : orow;
       } else {
         nux = g ? sx : ox; nuy = g ? sy : oy; nth = g ? ang : oa; npidx = g ? row : orow;
-        have_next = true;
+        have_next = second;
       }
     }
     // TRAIN: one buffer resource per stored array over the wave's 32 rows (scalar base, byte offsets j * row + 16 g + a
@@ -1102,14 +1141,14 @@ static int launch_shape(const OnfKernelArgs& a, hipStream_t stream, int* grid_ou
                   (size_t)fa.sharedSizeBytes);
     lds_checked[dev] = true;
   }
-  return launch_persistent<onf_x32_kernel<NKB, MODE, XT, 1>>(IMG_BYTES, XT, (a.n_points + CH - 1) / CH, stream, grid_out, a,
+  return launch_persistent<onf_x32_kernel<NKB, MODE, XT, 1>>(LDS_BYTES, XT, (a.n_points + CH - 1) / CH, stream, grid_out, a,
                                                              (const u32x4*)img, (const u32x4*)blob);
 }
 
 // 256 threads for small launches, 512 (two waves per SIMD) otherwise
 template <int NKB, int MODE>
 static int launch_t(const OnfKernelArgs& a, hipStream_t stream, int* grid_out) {
-  return a.n_points < (long long)query_cus() * 256 ? launch_shape<NKB, MODE, 256>(a, stream, grid_out)
+  return a.n_points < onf_wide_launch_threshold() ? launch_shape<NKB, MODE, 256>(a, stream, grid_out)
                                                    : launch_shape<NKB, MODE, 512>(a, stream, grid_out);
 }
 

@@ -97,6 +97,8 @@ extern "C" int nfopp_abi_version(void) { return NFOPP_ABI_VERSION; }
 
 extern "C" const char* nfopp_last_error(void) { return g_err; }
 
+extern "C" int64_t nfopp_onf_wide_launch_threshold(void) { return onf_wide_launch_threshold(); }
+
 extern "C" int nfopp_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) {

@@ -135,6 +135,7 @@ _SIGNATURES = {
                                               _P, _P, _P, _P, _P]),
     "nfopp_set_matrix_path": (ctypes.c_int, [ctypes.c_int32]),
     "nfopp_get_matrix_path": (ctypes.c_int, []),
+    "nfopp_onf_wide_launch_threshold": (ctypes.c_int64, []),
     "nfopp_onf_params_version": (ctypes.c_int, [_P, ctypes.c_uint64]),
     "nfopp_init_trajectories": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                _P, _P]),

@@ -39,6 +39,42 @@ def addr2(row, ch, half=0):
     return row * RS2 + 16 * (ch ^ swz2(row)) + 8 * half
 
 
+# ---- tiles by claim (MODE 0 and 2): the ticket map of a workgroup's pool, as in onf_x32_impl.h ----------------------
+def pool_tickets(n_work, threads, block, grid):
+    """number of tickets of workgroup `block`: TPC per chunk it owns (chunks block + k grid < n_chunks)"""
+    tpc = threads // 64
+    ch = 32 * tpc
+    n_chunks = (n_work + ch - 1) // ch
+    return 0 if block >= n_chunks else (n_chunks - block + grid - 1) // grid * tpc
+
+
+def ticket_first_sample(ticket, threads, block, grid):
+    """ticket t -> chunk block + (t / TPC) grid, tile t % TPC, first sample chunk * CH + 32 (t % TPC)"""
+    tpc = threads // 64
+    return (block + (ticket // tpc) * grid) * (32 * tpc) + 32 * (ticket % tpc)
+
+
+def claim_tickets(claim, threads):
+    """claim c -> its two tickets t = 2 TPC (c / TPC) + c % TPC and t + TPC: tile c % TPC of two consecutive owned chunks"""
+    tpc = threads // 64
+    t = 2 * tpc * (claim // tpc) + claim % tpc
+    return t, t + tpc
+
+
+def claim_is_past_pool(claim, n_work, threads, block, grid):
+    """the kernel's exit test: the chunk of the claim's first ticket is past the last one"""
+    tpc = threads // 64
+    ch = 32 * tpc
+    return block + 2 * (claim // tpc) * grid >= (n_work + ch - 1) // ch
+
+
+def launch_shape(n_points, cus=256):
+    """(threads, grid) of a launch: 256 threads below CUs x 256 samples, one workgroup per CU at the most"""
+    threads = 256 if n_points < cus * 256 else 512
+    ch = 32 * (threads // 64)
+    return threads, min(cus, (n_points + ch - 1) // ch)
+
+
 class Net:
     def __init__(self, fin, rng):
         self.fin = fin
